@@ -16,9 +16,12 @@ the collective and the extension, on forces them at N = 1 (where the "gathered" 
 Workload at every N: BASELINE.json configs[1] per GPU ("synthetic 12-ch sEMG, 41-class one-hot, batch
 4096, bf16"): 4096 groups = 167,936 windows per GPU per step (weak scaling; configs[2] is N=8).
 
-Prints ONE JSON line (rank 0).  `roofline` is measured live, inside the timed region, with HIP
-events recorded by the library on the stream the kernels run on (cp_profile_*); `cpu_baseline` is
-the CPU oracle (a port of the reference step, see oracle/ref_cpu.py) timed on this box's host cores.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the --steps steps and prints the headline
+(`value`, `ms_per_step`, the per-step spread of the same region); --dump-outputs DIR also writes what the last timed
+step computed (dump_outputs).  Everything else needs --full: `roofline` is measured live, inside the timed region, with
+HIP events recorded by the library on the stream the kernels run on (cp_profile_*); `cpu_baseline` is the CPU oracle
+(a port of the reference step, see oracle/ref_cpu.py) timed on the host cores; `other_steps`, `config4_fp8`,
+`config3_glove`, `small_batch` and `eval` are side records with timed regions of their own.
 """
 import argparse
 import json
@@ -26,6 +29,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -345,6 +349,30 @@ def _timed_mode(mode, k_other, step, barrier, args, use_dist, dist, dev, world, 
                       "reduce": "global negatives, partial sums + two 64-float all-reduces"}[mode])
 
 
+DUMP_MAX_ELEMENTS = 3 << 20     # per array (12 MiB of float32): every dump stays under 64 MB at any batch size
+
+
+def dump_outputs(out_dir, eng, state):
+    """--dump-outputs: what the last timed step handed its caller, as float32 DIR/<name>.npy -- z (encoder output, windows x 16),
+    out ([loss, correct windows]), pred (per-window argmax), zg (glove class encoder only), and the state the step left: params
+    (the flat parameter buffer after Adam), grads (the flat gradient buffer), bn_running (stock BN: running means then variances,
+    layer by layer).  An array larger than DUMP_MAX_ELEMENTS keeps a fixed sample of its rows (seed 0, ascending; it depends on
+    the shape alone, so two runs with the same arguments sample the same rows)."""
+    arrays = dict(z=state["z"], out=state["out"], pred=state["pred"], params=eng.values.flat, grads=eng.grads.flat)
+    if "zg" in state:
+        arrays["zg"] = state["zg"]
+    if eng.running:
+        arrays["bn_running"] = torch.cat([v.reshape(-1) for k, v in eng.running.items() if not k.endswith("num_batches_tracked")])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMENTS:
+            rows = DUMP_MAX_ELEMENTS // max(1, t[0].numel())
+            idx = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:rows].sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -356,23 +384,30 @@ def main():
     ap.add_argument("--dp_emg", type=float, default=BEST["dp_emg"])
     ap.add_argument("--cpu_seconds", type=float, default=15.0)
     ap.add_argument("--no_cpu_baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the live roofline, the CPU baseline and the side records (other_steps, config4_fp8, config3_glove, "
+                         "small_batch, eval); a plain run times the main region alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--main_only", action="store_true",
-                    help="profiling runs (tools/profile_round.sh): the timed region alone -- no CPU baseline, no other_steps, no small_batch")
+                    help="with --full: the timed region and its roofline alone -- no CPU baseline, no other_steps, no small_batch")
     ap.add_argument("--breakdown", action="store_true", help="extra untimed pass: per-kernel-kind times to stderr")
     ap.add_argument("--profile_every", type=int, default=20,
                     help="bracket the fc GEMM launches with HIP events (the live roofline numbers) on every n-th timed step")
     ap.add_argument("--global_negatives", default="auto", choices=["auto", "on", "gather", "reduce", "off"],
                     help="auto: gather when N > 1 (BASELINE.json configs[2] names the z all-gather; it must have a reader), off at N = 1 (configs[1]: "
                          "the reference's per-group loss).  on = gather.  reduce: the same {G, H} table from per-rank partial sums and two "
-                         "64-float all-reduces (cp_global_negatives_g / _h): no z moves.  Whatever is chosen, the line also carries the "
-                         "other workloads' step times from a second, shorter timed region (`other_steps`), so that the N = 1 and N > 1 "
+                         "64-float all-reduces (cp_global_negatives_g / _h): no z moves.  Whatever is chosen, a --full line also carries "
+                         "the other workloads' step times from a second, shorter timed region (`other_steps`), so that the N = 1 and N > 1 "
                          "lines of a scaling run hold one workload between them")
     ap.add_argument("--sync_bn", action="store_true", help="BatchNorm statistics over the global batch (18 small all-reduces per step)")
     ap.add_argument("--class_encoder", default="onehot", choices=["onehot", "glove"],
                     help="glove = BASELINE.json configs[3] (glove-angle class encoder); the default line is configs[1] (one-hot)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.main_only:
         args.no_cpu_baseline = True
+    side = args.full and not args.main_only           # the side records, each with a timed region of its own
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -456,6 +491,7 @@ def main():
             out, pred, _ = eng.head_glove(z, zg, labels, 1, want_grad=True)
             eng.glove_backward()             # first: its gradients sit in the bucket that encoder_backward's event releases
             eng.encoder_backward(x)
+            state["zg"] = zg
         else:
             out, pred, _ = eng.head(z, labels, 1, want_grad=True, gneg=gh)
             eng.encoder_backward(x)
@@ -464,7 +500,7 @@ def main():
             # backward call records before its conv kernels (~0.5 ms of them); averaged by grad_scale inside Adam
             reduce_grads()
         eng.adam_step(params, grad_scale=1.0 / world)
-        state["out"] = out
+        state.update(out=out, pred=pred, z=z)
 
     def barrier():
         if use_dist:
@@ -474,7 +510,8 @@ def main():
     for i in range(args.warmup):
         step(i)
     gemm_kinds = ["fc_fwd_ws", "fc_fwd", "fc_dgrad", "fc_dgrad_bn", "fc_dgrad_conv", "fc_dgrad_stats", "fc_wgrad"]
-    eng.profile_enable(gemm_kinds, max_records=64 * (args.steps + 1))
+    if args.full:
+        eng.profile_enable(gemm_kinds, max_records=64 * (args.steps + 1))
     # one event per step boundary on the launch stream: min / median / max step time inside the timed region (the same
     # launch moves by +-10 % with the clock state of the box; the spread says how steady this run was)
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
@@ -483,25 +520,29 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
-        # the live per-kernel timing brackets each fc GEMM launch with two HIP events, and every event record idles
+        # --full: the live per-kernel timing brackets each fc GEMM launch with two HIP events, and every event record idles
         # the queue for ~5 us (58 of them per step = 6 % of it): sample every --profile_every-th step
         # The profiled step runs on ONE stream: with the second stream (cp_config.aux_stream) the floating weight gradients share the
         # chip with the critical path's launches, and an event pair around a launch then times the contention too, not the kernel.
-        if i % args.profile_every == 0:
-            eng.profile_resume()
-            eng.aux_stream_enabled = False
-        else:
-            eng.profile_disable()
-            eng.aux_stream_enabled = aux_default
+        if args.full:
+            if i % args.profile_every == 0:
+                eng.profile_resume()
+                eng.aux_stream_enabled = False
+            else:
+                eng.profile_disable()
+                eng.aux_stream_enabled = aux_default
         step(args.warmup + i)
         marks[i + 1].record()
     barrier()
     elapsed = time.perf_counter() - t0
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
-    profiled_steps = len(range(0, args.steps, args.profile_every))
-    eng.profile_disable()
-    eng.aux_stream_enabled = aux_default
-    prof = eng.profile_summary()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, state)
+    if args.full:
+        profiled_steps = len(range(0, args.steps, args.profile_every))
+        eng.profile_disable()
+        eng.aux_stream_enabled = aux_default
+        prof = eng.profile_summary()
     if use_dist:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -510,7 +551,7 @@ def main():
 
     # the other loss workloads on the same engine, shorter: one scaling run's N = 1 and N > 1 lines then hold a common step
     other_steps = {}
-    if args.class_encoder == "onehot" and not args.main_only:
+    if args.class_encoder == "onehot" and side:
         k_other = max(4, args.steps // 2)
         for mode in ("off", "gather", "reduce"):
             if mode == gn or "error" in other_steps:
@@ -549,67 +590,68 @@ def main():
 
     if rank == 0:
         dt = args.dtype
-        prefix = {"bf16": "r04", "fp8": "r04_fp8", "f32": "r04_f32"}[dt]          # the newest committed set of this command (else round 3's)
-        if not os.path.exists(os.path.join(ROOT, "profiles", prefix + "_traffic.json")):
-            prefix = prefix.replace("r04", "r03")
-        dom = max(gemm_kinds, key=lambda k: prof.get(k, (0.0, 0))[0])
-        ms, launches = prof[dom]
-        dyn = "true" if eng.tile_schedule else "false"
-        kname = gemm_symbol(dom, dyn, dt)
-        # counter evidence from the COMMITTED profiles of this same command on the builder's box (tools/profile_round.sh): not
-        # measured in this run, and labelled so
-        mfma_busy = traffic = None
-        mpath = os.path.join(ROOT, "profiles", prefix + "_mfma.json")
-        tpath = os.path.join(ROOT, "profiles", prefix + "_traffic.json")
-        if B == 4096 and os.path.exists(mpath):
-            for k, v in json.load(open(mpath))["kernels"].items():
-                if kname in k:
-                    mfma_busy = dict(value=v["mfma_busy_frac"], source="profiles/" + os.path.basename(mpath) + " (SQ counters, builder's box)")
-        if B == 4096 and os.path.exists(tpath):
-            for k, v in json.load(open(tpath))["kernels"].items():
-                if kname in k:
-                    traffic = dict(value=v["hbm_bytes_per_launch"], source="profiles/" + os.path.basename(tpath) + " (PMC FETCH_SIZE / WRITE_SIZE passes, builder's box)")
-        avg_s = ms / launches / 1e3
-        paired = 2                  # (the profiled steps run on one stream: fc7+fc6 and fc5+fc4 share a launch each)
-        byts, flops = gemm_model(dom, N, dt, args.dp_emg > 0, paired)
-        gbs = byts / avg_s / 1e9
-        tfl = flops / avg_s / 1e12
-        mfma_peak = MFMA_PEAK_TFLOPS[dt]
-        practical = measure_practical_peaks(dev, dt)
-        per_kernel = {}
-        for k in gemm_kinds:
-            if k in prof and prof[k][1] > 0:
-                kb, kf = gemm_model(k, N, dt, args.dp_emg > 0, paired)
-                ks_ = prof[k][0] / prof[k][1] / 1e3
-                per_kernel[k] = dict(symbol=gemm_symbol(k, dyn, dt), launches=prof[k][1], avg_us=ks_ * 1e6, algorithmic_bytes=kb,
-                                     gbs=kb / ks_ / 1e9, hbm_frac=kb / ks_ / 1e9 / HBM_PEAK_GBS, tflops=kf / ks_ / 1e12)
-        bound = "hbm" if byts / (HBM_PEAK_GBS * 1e9) >= flops / (mfma_peak * 1e12) else "mfma"
-        # the same question against what the chip sustains: a launch whose FLOP/byte lies above practical MFMA / practical HBM is
-        # bounded by the matrix pipe's power budget, and its HBM fraction cannot reach 1
-        bound_practical = "hbm" if byts / (practical["hbm_gbs"] * 1e9) >= flops / (practical["mfma_tflops"] * 1e12) else "mfma"
-        frac_practical = max(gbs / practical["hbm_gbs"], tfl / practical["mfma_tflops"])
-        roof = dict(bound=bound, kernel=dom, kernel_symbol=kname, launches=launches, avg_us=avg_s * 1e6,
-                    achieved=gbs if bound == "hbm" else tfl, peak=HBM_PEAK_GBS if bound == "hbm" else mfma_peak,
-                    unit="GB/s" if bound == "hbm" else "TFLOP/s",
-                    frac=(gbs / HBM_PEAK_GBS) if bound == "hbm" else (tfl / mfma_peak),
-                    traffic=traffic["value"] if traffic else None, traffic_source=traffic["source"] if traffic else None,
-                    algorithmic_bytes=byts,
-                    practical_peak=practical, bound_practical=bound_practical, frac_practical=frac_practical,
-                    mfma_tflops=tfl, mfma_frac=tfl / mfma_peak,
-                    mfma_busy_frac=mfma_busy["value"] if mfma_busy else None, mfma_busy_source=mfma_busy["source"] if mfma_busy else None,
-                    hbm_gbs=gbs, hbm_frac=gbs / HBM_PEAK_GBS,
-                    gemm_ms_per_step={k: prof[k][0] / profiled_steps for k in gemm_kinds if k in prof},
-                    second_stream=bool(aux_default and eng._aux is not None),
-                    note="per-kernel durations: HIP events around each launch on the profiled steps, which run on ONE stream, as the timed steps do "
-                         "by default (second_stream false; with CPNATIVE_AUX_STREAM=1 the timed steps float the weight gradients behind a dropout on "
-                         "cp_config.aux_stream and a launch's wall time includes what it shares the chip with)",
-                    profiled_steps=profiled_steps,
-                    per_kernel=per_kernel)
-        # the step as a whole against SURVEY 8d's byte model (51.3 KB per window in 16-bit storage, 102.5 in f32, 25.6 in 8-bit)
-        kb_per_window = {"bf16": 51.3, "f32": 102.5, "fp8": 25.6}[dt]
-        step_s = elapsed / args.steps
-        roof["step"] = dict(model_kb_per_window=kb_per_window, hbm_frac=kb_per_window * 1e3 * N / step_s / (HBM_PEAK_GBS * 1e9),
-                            mfma_frac=12.74e6 * N / step_s / (mfma_peak * 1e12))
+        if args.full:
+            prefix = {"bf16": "r04", "fp8": "r04_fp8", "f32": "r04_f32"}[dt]          # the newest committed set of this command (else round 3's)
+            if not os.path.exists(os.path.join(ROOT, "profiles", prefix + "_traffic.json")):
+                prefix = prefix.replace("r04", "r03")
+            dom = max(gemm_kinds, key=lambda k: prof.get(k, (0.0, 0))[0])
+            ms, launches = prof[dom]
+            dyn = "true" if eng.tile_schedule else "false"
+            kname = gemm_symbol(dom, dyn, dt)
+            # counter evidence from the COMMITTED profiles of this same command on the builder's box (tools/profile_round.sh): not
+            # measured in this run, and labelled so
+            mfma_busy = traffic = None
+            mpath = os.path.join(ROOT, "profiles", prefix + "_mfma.json")
+            tpath = os.path.join(ROOT, "profiles", prefix + "_traffic.json")
+            if B == 4096 and os.path.exists(mpath):
+                for k, v in json.load(open(mpath))["kernels"].items():
+                    if kname in k:
+                        mfma_busy = dict(value=v["mfma_busy_frac"], source="profiles/" + os.path.basename(mpath) + " (SQ counters, builder's box)")
+            if B == 4096 and os.path.exists(tpath):
+                for k, v in json.load(open(tpath))["kernels"].items():
+                    if kname in k:
+                        traffic = dict(value=v["hbm_bytes_per_launch"], source="profiles/" + os.path.basename(tpath) + " (PMC FETCH_SIZE / WRITE_SIZE passes, builder's box)")
+            avg_s = ms / launches / 1e3
+            paired = 2                  # (the profiled steps run on one stream: fc7+fc6 and fc5+fc4 share a launch each)
+            byts, flops = gemm_model(dom, N, dt, args.dp_emg > 0, paired)
+            gbs = byts / avg_s / 1e9
+            tfl = flops / avg_s / 1e12
+            mfma_peak = MFMA_PEAK_TFLOPS[dt]
+            practical = measure_practical_peaks(dev, dt)
+            per_kernel = {}
+            for k in gemm_kinds:
+                if k in prof and prof[k][1] > 0:
+                    kb, kf = gemm_model(k, N, dt, args.dp_emg > 0, paired)
+                    ks_ = prof[k][0] / prof[k][1] / 1e3
+                    per_kernel[k] = dict(symbol=gemm_symbol(k, dyn, dt), launches=prof[k][1], avg_us=ks_ * 1e6, algorithmic_bytes=kb,
+                                         gbs=kb / ks_ / 1e9, hbm_frac=kb / ks_ / 1e9 / HBM_PEAK_GBS, tflops=kf / ks_ / 1e12)
+            bound = "hbm" if byts / (HBM_PEAK_GBS * 1e9) >= flops / (mfma_peak * 1e12) else "mfma"
+            # the same question against what the chip sustains: a launch whose FLOP/byte lies above practical MFMA / practical HBM is
+            # bounded by the matrix pipe's power budget, and its HBM fraction cannot reach 1
+            bound_practical = "hbm" if byts / (practical["hbm_gbs"] * 1e9) >= flops / (practical["mfma_tflops"] * 1e12) else "mfma"
+            frac_practical = max(gbs / practical["hbm_gbs"], tfl / practical["mfma_tflops"])
+            roof = dict(bound=bound, kernel=dom, kernel_symbol=kname, launches=launches, avg_us=avg_s * 1e6,
+                        achieved=gbs if bound == "hbm" else tfl, peak=HBM_PEAK_GBS if bound == "hbm" else mfma_peak,
+                        unit="GB/s" if bound == "hbm" else "TFLOP/s",
+                        frac=(gbs / HBM_PEAK_GBS) if bound == "hbm" else (tfl / mfma_peak),
+                        traffic=traffic["value"] if traffic else None, traffic_source=traffic["source"] if traffic else None,
+                        algorithmic_bytes=byts,
+                        practical_peak=practical, bound_practical=bound_practical, frac_practical=frac_practical,
+                        mfma_tflops=tfl, mfma_frac=tfl / mfma_peak,
+                        mfma_busy_frac=mfma_busy["value"] if mfma_busy else None, mfma_busy_source=mfma_busy["source"] if mfma_busy else None,
+                        hbm_gbs=gbs, hbm_frac=gbs / HBM_PEAK_GBS,
+                        gemm_ms_per_step={k: prof[k][0] / profiled_steps for k in gemm_kinds if k in prof},
+                        second_stream=bool(aux_default and eng._aux is not None),
+                        note="per-kernel durations: HIP events around each launch on the profiled steps, which run on ONE stream, as the timed steps do "
+                             "by default (second_stream false; with CPNATIVE_AUX_STREAM=1 the timed steps float the weight gradients behind a dropout on "
+                             "cp_config.aux_stream and a launch's wall time includes what it shares the chip with)",
+                        profiled_steps=profiled_steps,
+                        per_kernel=per_kernel)
+            # the step as a whole against SURVEY 8d's byte model (51.3 KB per window in 16-bit storage, 102.5 in f32, 25.6 in 8-bit)
+            kb_per_window = {"bf16": 51.3, "f32": 102.5, "fp8": 25.6}[dt]
+            step_s = elapsed / args.steps
+            roof["step"] = dict(model_kb_per_window=kb_per_window, hbm_frac=kb_per_window * 1e3 * N / step_s / (HBM_PEAK_GBS * 1e9),
+                                mfma_frac=12.74e6 * N / step_s / (mfma_peak * 1e12))
         rec = dict(metric="sEMG windows/sec contrastive step, 12-ch Ninapro, 1/2/4/8 MI355X", value=world * N * args.steps / elapsed,
                    unit="windows/s", n_gpus=world, steps=args.steps, warmup=args.warmup,
                    ms_per_step=1e3 * elapsed / args.steps, higher_is_better=True, scaling="weak", vs_baseline=None,
@@ -624,17 +666,19 @@ def main():
                                      "reduce": "global negatives (partial sums + two 64-float all-reduces, no z all-gather)",
                                      "off": "reference per-group loss"}[gn],
                                tile_schedule="dynamic" if eng.tile_schedule else "static"),
-                   loss=loss, train_acc=correct / N, roofline=roof,
-                   steps_spread=dict(min_ms=step_ms[0], median_ms=step_ms[len(step_ms) // 2], max_ms=step_ms[-1],
-                                     note="per-step HIP events on the launch stream, rank 0"))
+                   loss=loss, train_acc=correct / N)
+        if args.full:
+            rec["roofline"] = roof
+        rec["steps_spread"] = dict(min_ms=step_ms[0], median_ms=step_ms[len(step_ms) // 2], max_ms=step_ms[-1],
+                                   note="per-step HIP events on the launch stream, rank 0")
         if other_steps:
             rec["other_steps"] = other_steps
         if rehearse:
             rec["rehearsal"] = f"ranks share one GPU over {rehearse}: control-flow check only, not a measurement"
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(args.cpu_seconds, threads=min(16, os.cpu_count() or 1))
             rec["gpu_over_cpu"] = rec["value"] / rec["cpu_baseline"]["value"]
-        if world == 1 and not rehearse and args.class_encoder == "onehot" and not args.main_only and args.dtype == "bf16":
+        if world == 1 and not rehearse and args.class_encoder == "onehot" and side and args.dtype == "bf16":
             try:
                 # BASELINE.json configs[4]'s storage on the same workload, same run (its own line: python bench.py --dtype fp8): 8-bit activations,
                 # weights and gradients on the block-scaled MFMA.  Parity unpinned by construction; it is not `value`.
@@ -664,20 +708,20 @@ def main():
                 del e8
             except Exception as ex:                       # a side record: never at the cost of the line
                 _side_failed("config4_fp8", rec, ex, dev)
-        if world == 1 and not rehearse and args.class_encoder == "onehot" and not args.main_only:
+        if world == 1 and not rehearse and args.class_encoder == "onehot" and side:
             try:
                 rec["small_batch"] = small_batch_record(dev, args.dtype)
                 if "cpu_baseline" in rec and "b8" in rec["cpu_baseline"]:
                     rec["small_batch"]["b8"]["over_cpu_b8"] = rec["small_batch"]["b8"]["windows_per_s"] / rec["cpu_baseline"]["b8"]["value"]
             except Exception as ex:
                 _side_failed("small_batch", rec, ex, dev)
-        if world == 1 and not rehearse and args.class_encoder == "onehot" and not args.main_only and args.dtype == "bf16" and B == 4096:
+        if world == 1 and not rehearse and args.class_encoder == "onehot" and side and args.dtype == "bf16" and B == 4096:
             try:
                 rec["config3_glove"] = glove_record(dev, args.dtype, B, table, emg_rand, perms, labels, max(5, args.steps // 2))
                 rec["config3_glove"]["over_onehot_ms"] = rec["config3_glove"]["ms_per_step"] - rec["ms_per_step"]
             except Exception as ex:
                 _side_failed("config3_glove", rec, ex, dev)
-        if world == 1 and not rehearse and not args.main_only:
+        if world == 1 and not rehearse and side:
             try:
                 rec["eval"] = eval_record(dev, ["f32", "bf16", "fp8"] if args.dtype == "bf16" else [args.dtype])
             except Exception as ex:

@@ -9,7 +9,7 @@ cd "$(dirname "$0")/.."
 for i in $(seq $R); do
   for L in default "$OTHER"; do
     if [ "$L" = default ]; then unset CPNATIVE_LIB; else export CPNATIVE_LIB=$PWD/$L; fi
-    python bench.py --no_cpu_baseline "$@" 2>/dev/null | tail -1 | python -c "
+    python bench.py --full --no_cpu_baseline "$@" 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 pk=d['roofline']['per_kernel']

@@ -11,7 +11,7 @@ for L in ${LEGS:-default WSD32 WS32}; do
   [ $L = TN16 ] && export CPNATIVE_TN16=1
   [ $L = NO_WSK ] && export CPNATIVE_NO_WSK=1
   [ $L = TN_W4 ] && export CPNATIVE_TN_W4=1
-  python bench.py --no_cpu_baseline 2>/dev/null | tail -1 | python -c "
+  python bench.py --full --no_cpu_baseline 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 pk=d['roofline']['per_kernel']

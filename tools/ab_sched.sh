@@ -4,7 +4,7 @@ R=${1:-2}
 cd "$(dirname "$0")/.."
 for i in $(seq $R); do
   for S in static dynamic; do
-    CPNATIVE_TILE_SCHEDULE=$S python bench.py --no_cpu_baseline 2>/dev/null | tail -1 | python -c "
+    CPNATIVE_TILE_SCHEDULE=$S python bench.py --full --no_cpu_baseline 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 pk=d['roofline']['per_kernel']

@@ -1,8 +1,11 @@
 #!/bin/bash
 # VGPR / spill / scratch / LDS / occupancy of every kernel in libcpnative (hipcc -Rpass-analysis=kernel-resource-usage), one line each.
 # usage: tools/kernel_resources.sh [filter-regex]
-cd /tmp
-hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared /root/repo/contrastiveprosthetics_amd/csrc/api.hip -o /tmp/_res.so \
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+TMP=$(mktemp -d)                 # hipcc's temporaries and the throwaway library stay out of the checkout
+trap 'rm -rf "$TMP"' EXIT
+cd "$TMP"
+hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared "$ROOT/contrastiveprosthetics_amd/csrc/api.hip" -o "$TMP/_res.so" \
   -Rpass-analysis=kernel-resource-usage 2>&1 | python3 -c '
 import re, sys, subprocess
 cur = None

@@ -5,8 +5,8 @@
 R=${1:-r02}; shift     # further arguments go to every bench.py run (e.g. --dtype fp8)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out
-# the plain bench line first: behind the four profiled runs the chip is warm and the same build reads 2-4 % slower
-timeout -k 10 400 python bench.py "$@" > $O/${R}_bench.log 2>&1; tail -1 $O/${R}_bench.log > $O/${R}_bench.json
+# the full bench line first: behind the four profiled runs the chip is warm and the same build reads 2-4 % slower
+timeout -k 10 400 python bench.py --full "$@" > $O/${R}_bench.log 2>&1; tail -1 $O/${R}_bench.log > $O/${R}_bench.json
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/${R}_stats -- python3 bench.py --main_only --steps 10 --warmup 3 "$@" > $O/${R}_stats.log 2>&1 || exit 1
 # counter passes (one stream, the default: a kernel's HBM bytes and matrix-pipe cycles are read over its own execution)
 for Cn in FETCH_SIZE WRITE_SIZE; do
