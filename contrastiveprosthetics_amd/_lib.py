@@ -10,7 +10,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# CPNATIVE_LIB: another build of the same library (A/B measurements of kernel variants)
+# CPNATIVE_LIB: another build of the same library, e.g. from tools/build_prev.sh (A/B measurements of two builds)
 LIB_PATH = os.environ.get("CPNATIVE_LIB") or os.path.join(_HERE, "libcpnative.so")
 
 CP_F32, CP_BF16, CP_FP8 = 0, 1, 2
@@ -69,7 +69,6 @@ class cp_glove_params(C.Structure):
 SYMBOLS = {
     "cp_version": (C.c_int, []),
     "cp_last_error": (C.c_char_p, []),
-    "cp_has_variants": (C.c_int, []),
     "cp_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_float]),
     "cp_gather_groups": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, C.c_int32, _fp, _fp]),
     "cp_gather_oob_count": (C.c_int, [_fp, C.c_int32, _fp]),
@@ -110,8 +109,7 @@ SYMBOLS = {
     "cp_profile_summary": (C.c_int, [C.c_int32, _P(C.c_double), _P(C.c_int64)]),
     "cp_debug_activation": (C.c_int, [_P(cp_config), _P(cp_params), _fp, _fp, C.c_size_t, C.c_int32, _fp, _fp]),
     "cp_debug_bn_stats": (C.c_int, [_P(cp_config), _fp, C.c_size_t, C.c_int32, _fp, _fp]),
-    "cp_debug_gemm": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp,
-                                C.c_int32, _fp]),
+    "cp_debug_gemm": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
 }
 
 KERNEL_KINDS = ["gather", "prep", "conv1_fwd", "bn_finalize", "conv2_fwd", "fold", "fc_fwd", "dropout", "proj_fwd",
@@ -144,7 +142,7 @@ def load():
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
-    if lib.cp_version() < 110:
+    if lib.cp_version() < 111:
         raise CpNativeError("libcpnative.so is older than this binding")
     _lib = lib
     return lib

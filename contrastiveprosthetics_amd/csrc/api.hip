@@ -2,16 +2,12 @@
 // One enqueue-only function per stage; no allocation, no synchronisation.
 #include <hip/hip_runtime.h>
 #include <cstdio>
-#include <cstring>
 #include <cmath>
-#include <cstdlib>
-#include <cctype>
 #include <mutex>
 
 #include "../../include/cpnative.h"
 #include "common.cuh"
 #include "gemm_nt.cuh"
-#include "gemm_nt256.cuh"
 #include "gemm_nt256p.cuh"
 #include "gemm_ws.cuh"
 #include "gemm_tn.cuh"
@@ -47,38 +43,9 @@ extern "C" int cp_version(void) { return CP_VERSION; }
 
 // ---------------------------------------------------------------------------------------
 // No process-wide switches: a call's options, tile schedule, synchronised-BatchNorm hook and gradient tap travel in its
-// cp_config (include/cpnative.h).  Only the tools-only build keeps a global (common.cuh, CpVariantOptions): one switch per
-// superseded kernel, seeded ONCE from $CPNATIVE_<NAME> when that library is loaded (tools/ab_env.sh and friends).
+// cp_config (include/cpnative.h).
 // ---------------------------------------------------------------------------------------
 static inline bool opt(const cp_config* c, uint32_t bit) { return (c->options & bit) != 0; }
-extern "C" int cp_has_variants(void) {
-#ifdef CP_VARIANTS
-    return 1;
-#else
-    return 0;
-#endif
-}
-#ifdef CP_VARIANTS
-struct VarName { const char* name; int CpVariantOptions::*field; };
-static const VarName kVarNames[] = {
-    {"no_ws", &CpVariantOptions::no_ws}, {"no_wsk", &CpVariantOptions::no_wsk}, {"no_wsd", &CpVariantOptions::no_wsd},
-    {"no_wsd_st", &CpVariantOptions::no_wsd_st}, {"staged_r_epilogue", &CpVariantOptions::staged_r_epilogue},
-    {"ws32", &CpVariantOptions::ws32}, {"wsd32", &CpVariantOptions::wsd32}, {"tn_w4", &CpVariantOptions::tn_w4},
-    {"tn16", &CpVariantOptions::tn16}, {"materialize_u8", &CpVariantOptions::materialize_u8},
-    {"no_proj_fused", &CpVariantOptions::no_proj_fused},
-};
-static int seed_variants_from_env() {
-    for (const VarName& o : kVarNames) {
-        char env[64] = "CPNATIVE_";
-        size_t n = strlen(env);
-        for (const char* c = o.name; *c && n + 1 < sizeof(env); ++c) env[n++] = (char)toupper(*c);
-        env[n] = 0;
-        if (getenv(env)) g_var.*(o.field) = 1;
-    }
-    return 0;
-}
-static const int g_var_seeded = seed_variants_from_env();
-#endif
 extern "C" const char* cp_last_error(void) { return g_err; }
 
 // tile schedule of the persistent fc GEMM kernels: cp_config.tile_schedule (cpnative.h)
@@ -189,6 +156,7 @@ struct WS {
 static const size_t kSlabFloats = (size_t)64 * 512 * 512 + 1024;   // 64 splits of a 512x512 (or 40 of a 512x768) f32 slab
 static const int kHeadBlocksMax = 1024;          // (512 / 256 measured: 44.4 / 54.1 us against 43.6)
 static const int kSumSlices = 16;           // row slices (= partial rows) of bn_bwd_sums_from_wgrad_kernel
+static const int kProjSplits = 128;         // row splits of the projection's weight-gradient launch
 
 static WS carve(int64_t N, int dtype, float dp) {
     WS w{};
@@ -394,34 +362,13 @@ template <typename T, int EPI>
 static inline hipError_t launch_fc_gemm(const GemmNTArgs& a, hipStream_t st, int* stat_rows = nullptr, bool dyn_schedule = false) {
     if (stat_rows) *stat_rows = (int)((a.M + fc_bm<T>() - 1) / fc_bm<T>());
     if constexpr (sizeof(T) == 2) {
-#ifdef CP_VARIANTS
-        // tools-only build: dbg bits (cp_debug_gemm) and the options pick superseded kernels -- dbg 64 / 128 force the dynamic /
-        // static schedule, 256 / no_ws the tile-staged kernels, 16 / staged_r_epilogue the one-tile kernel with its LDS-staged epilogue
-        const bool dyn = (a.dbg & 64) ? true : (a.dbg & 128) ? false : dyn_schedule;
-        const bool ws_ok = !dyn && !(a.dbg & (16 | 256)) && !g_var.no_ws;
-        const bool wsk_ok = ws_ok && !g_var.no_wsk;
-        const bool wsd_ok = ws_ok && !g_var.no_wsd && (a.coef != nullptr || !g_var.no_wsd_st);
-        const bool staged = (a.dbg & 16) || g_var.staged_r_epilogue;
-#else
-        const bool dyn = dyn_schedule;
-        const bool ws_ok = !dyn, wsk_ok = !dyn, wsd_ok = !dyn;
-#endif
         // a process that has the GPU to itself (static schedule): the weight-stationary kernels (gemm_ws.cuh) -- K = 512 forward,
         // fc1 (K = 768) on its narrow form (32 features per wave), data gradients with BatchNorm + ReLU backward or (behind a dropout) the mask + sums
-        if (EPI == EPI_FWD && a.K == WS_K && a.lda == WS_K && a.relu && ws_ok) return launch_gemm_ws<EPI_FWD>(a, st, stat_rows);
-#ifdef CP_VARIANTS
-        if (EPI == EPI_FWD && a.K == WSK_K && a.lda == WSK_K && a.F == 512 && a.relu && wsk_ok && (a.dbg & 1024)) return launch_gemm_ws16k(a, st, stat_rows);
-#endif
-        if (EPI == EPI_FWD && a.K == WSK_K && a.lda == WSK_K && a.F == 512 && a.relu && wsk_ok) return launch_gemm_ws16n(a, st, stat_rows);
-#ifdef CP_VARIANTS
-        if ((EPI == EPI_FWD || (a.R == nullptr && a.dp_thresh == 0)) && !(a.dbg & 16)) return launch_gemm_nt256p<EPI>(a, st, stat_rows, dyn);
-#else
+        const bool dyn = dyn_schedule, ws_ok = !dyn;
+        if (EPI == EPI_FWD && a.K == WS_K && a.lda == WS_K && a.relu && ws_ok) return launch_gemm_ws(a, st, stat_rows);
+        if (EPI == EPI_FWD && a.K == WSK_K && a.lda == WSK_K && a.F == 512 && a.relu && ws_ok) return launch_gemm_ws16n(a, st, stat_rows);
         if (EPI == EPI_FWD || (a.R == nullptr && a.dp_thresh == 0)) return launch_gemm_nt256p<EPI>(a, st, stat_rows, dyn);
-#endif
-        if (EPI == EPI_DGRAD && a.R != nullptr && a.K == WS_K && a.lda == WS_K && wsd_ok) return launch_gemm_wsd_bn(a, st, stat_rows);
-#ifdef CP_VARIANTS
-        if (staged) return launch_gemm_nt256<EPI>(a, st);
-#endif
+        if (EPI == EPI_DGRAD && a.R != nullptr && a.K == WS_K && a.lda == WS_K && ws_ok) return launch_gemm_wsd_bn(a, st, stat_rows);
         // the persistent kernel's R epilogues (dynamic schedule, or K != 512): BN + ReLU backward of the layer below (coef), or
         // dropout + BN-backward sums
         if constexpr (EPI == EPI_DGRAD)
@@ -590,17 +537,10 @@ static int encoder_forward_t(const cp_config* c, const cp_params* p, const cp_bn
         // (evaluation with the running statistics: nobody reads the column sums -- the weight-stationary kernels then skip them; the
         //  other dispatch targets ignore the distinction and write rows nobody reads)
         a.partials = (batch_stats || sizeof(T) != 2 || dyn_tiles(c)) ? partials : nullptr;
-#ifdef CP_VARIANTS
-        a.partials = partials;
-#endif
         int nrows = 0;
         {
-            // (profiler kinds name ONE kernel each: K = 512 bf16 launches under the static schedule run gemm_ws_kernel)
-#ifdef CP_VARIANTS
-            const bool ws = sizeof(T) == 2 && K == WS_K && !dyn_tiles(c) && !g_var.no_ws;
-#else
+            // (profiler kinds name ONE kernel each: K = 512 bf16 launches under the static schedule run gemm_ws16_kernel)
             const bool ws = sizeof(T) == 2 && K == WS_K && !dyn_tiles(c);
-#endif
             ProfScope ps(ws ? CP_K_FC_FWD_WS : CP_K_FC_FWD, st);
             CK((launch_fc_gemm<T, EPI_FWD>(a, st, &nrows, dyn_tiles(c))));
         }
@@ -613,20 +553,7 @@ static int encoder_forward_t(const cp_config* c, const cp_params* p, const cp_bn
         const float *s = stats(Lp) + 2 * 512, *t = stats(Lp) + 3 * 512;
         // dropout(BN(fc7)) is NOT written out for the projection: its two consumers (this launch and the projection's weight
         // gradient) form it from the saved activation while staging their operand -- both are bound by reading those 172 MB, and
-        // the pass that materialised it moved 344 MB.  (tools-only build, option materialize_u8: the separate pass, as fc4..fc6 still have.)
-#ifdef CP_VARIANTS
-        const bool fused_u8 = drop && !g_var.materialize_u8;
-#else
-        const bool fused_u8 = drop;
-#endif
-        if (drop && !fused_u8) {
-            T* u = (T*)(base + w.u[Lp - 5]);
-            ProfScope ps(CP_K_DROPOUT, st);
-            hipLaunchKernelGGL((bn_dropout_apply_kernel<T>), dim3(grid_rows(N, 256 / (512 / D::EPC), CAP_BDA16)), dim3(256), 0, st,
-                               act(Lp), stats(Lp), u, N, 512, dp_thresh(c->dp_emg), dp_key(c, Lp), dp_inv_keep(c->dp_emg), dp_salt(c));
-            CKL("bn_dropout_apply_kernel");
-            A = u;
-        }
+        // the pass that materialised it moved 344 MB.  (That pass, as fc4..fc6 keep it, was removed here; see git history.)
         if (!drop && batch_stats) {        // (with dropout: copied by fold_copy_batch_kernel at the start of the pass; running statistics: folded up front)
             ProfScope ps(CP_K_FOLD, st);
             hipLaunchKernelGGL((fold_linear_kernel<T>), dim3(32), dim3(256), 0, st, p->last_w, (const float*)nullptr, s, t,
@@ -639,7 +566,7 @@ static int encoder_forward_t(const cp_config* c, const cp_params* p, const cp_bn
         a.C = z; a.ldc = CP_D_E; a.f_valid = CP_D_E; a.bias = (float*)(base + w.blast);
         {
             ProfScope ps(CP_K_PROJ_FWD, st);
-            if (fused_u8) {
+            if (drop) {
                 a.a_scale = stats(Lp) + 2 * 512; a.a_shift = stats(Lp) + 3 * 512;
                 a.dp_thresh = dp_thresh(c->dp_emg); a.dp_key = dp_key(c, Lp); a.dp_inv_keep = dp_inv_keep(c->dp_emg); a.dp_salt = dp_salt(c);
                 CK((launch_gemm_nt<T, 128, 32, ALOAD_BNDROP, EPI_PLAIN_F32>(a, st)));
@@ -1262,9 +1189,6 @@ static int tap_gradient(const cp_config* c, int slot, const void* src, int64_t n
 }
 
 static inline void split_rows(int64_t M, int target_splits, int* splits, int64_t* rows_per_split);
-#ifndef CP_PROJ_SPLITS
-#define CP_PROJ_SPLITS 128                    // row splits of the projection's weight-gradient launch (tools: -DCP_PROJ_SPLITS=... for A/B runs)
-#endif
 
 // ---------------------------------------------------------------------------------------
 // glove-angle class encoder
@@ -1773,7 +1697,6 @@ static int encoder_backward_t(const cp_config* c, const cp_params* p, const floa
     // ---- projection ------------------------------------------------------------------
     {
         ProfScope ps(CP_K_PROJ_BWD, st);
-        const T* Y = drop ? (const T*)(base + w.u[3]) : act(8);
         const float *s = nullptr, *t = nullptr;
         float* dzsum = (float*)(base + w.dzsum);
         if (!drop) {
@@ -1785,16 +1708,10 @@ static int encoder_backward_t(const cp_config* c, const cp_params* p, const floa
         }
         GemmTNArgs ta{};
         const hipStream_t sw = aux.s();                 // (with dropout nothing waits for this weight gradient: second stream)
-        ta.X = dz; ta.ldx = 64; ta.Y = Y; ta.ldy = 512; ta.slabs = aux.on ? slabs_b : slabs; ta.M = N; ta.P = 64; ta.Q = 512;
+        ta.X = dz; ta.ldx = 64; ta.Y = act(8); ta.ldy = 512; ta.slabs = aux.on ? slabs_b : slabs; ta.M = N; ta.P = 64; ta.Q = 512;
         int S;
-        split_rows(N, CP_PROJ_SPLITS, &S, &ta.rows_per_split);
-#ifdef CP_VARIANTS
-        const bool fused_u8 = drop && !g_var.materialize_u8;
-        const bool proj_alg = fuse_ok && drop && sizeof(T) == 2 && !g_var.materialize_u8 && !g_var.no_proj_fused;
-#else
-        const bool fused_u8 = drop;
+        split_rows(N, kProjSplits, &S, &ta.rows_per_split);
         const bool proj_alg = fuse_ok && drop && sizeof(T) == 2;
-#endif
         if (proj_alg) {
             // behind fc7's dropout, 16-bit storage (round 4): the weight gradient's launch reads r8 ONCE and leaves both dW and fc7's
             // BatchNorm-backward sums (gemm_tn.cuh, proj_wgrad_sums_kernel); on the critical path -- the data gradient below needs the sums
@@ -1808,9 +1725,9 @@ static int encoder_backward_t(const cp_config* c, const cp_params* p, const floa
                                    dp_inv_keep(c->dp_emg), (const int*)nullptr, g->last_w, partials);
                 CKL("proj_wgrad_finish_kernel");
             }
-        } else if (fused_u8) {
+        } else if (drop) {
             // u8 = dropout(BN(fc7)) was never written (encoder_forward_t): formed from the saved activation while staging
-            ta.Y = act(8); ta.y_scale = stats(8) + 2 * 512; ta.y_shift = stats(8) + 3 * 512;
+            ta.y_scale = stats(8) + 2 * 512; ta.y_shift = stats(8) + 3 * 512;
             ta.dp_thresh = dp_thresh(c->dp_emg); ta.dp_key = dp_key(c, 8); ta.dp_inv_keep = dp_inv_keep(c->dp_emg); ta.dp_salt = dp_salt(c);
             CK((launch_gemm_tn<T, 64, 128, YLOAD_BNDROP>(ta, S, sw)));
         } else {
@@ -1847,28 +1764,15 @@ static int encoder_backward_t(const cp_config* c, const cp_params* p, const floa
             hipLaunchKernelGGL(colsum_finalize_kernel, dim3(FIN_GRID(512)), dim3(FIN_THREADS), 0, st, pp, nr, 512, g->fc_b[6]);
             CKL("colsum_finalize_kernel(fc7, fused)");
             bn_done = true;
-#ifdef CP_VARIANTS
-        } else if (fuse_ok && drop && sizeof(T) == 2 && !g_var.no_proj_fused) {
-#else
-        } else if (fuse_ok && drop && sizeof(T) == 2) {
-#endif
-            // behind fc7's dropout: the rank-16 product is formed with fc7's BN + ReLU backward applied (gemm_ws.cuh, proj_dgrad_kernel<1>)
+        } else if (proj_alg) {
+            // behind fc7's dropout: the rank-16 product is formed with fc7's BN + ReLU backward applied (gemm_ws.cuh, proj_dgrad_kernel)
             // instead of being written out for a separate bn_relu_bwd pass; the BatchNorm-backward sums it needs came with the weight
-            // gradient above (round 3 and the tools build: a first pass of the same product, proj_dgrad_kernel<0>)
-            int nr = PROJ_FINISH_ROWS;
-            const float* pp = partials;
-#ifdef CP_VARIANTS
-            if (!proj_alg) {
-                CK(launch_proj_dgrad<0>(a, st, &drows));
-                nr = drows;
-                pp = pre(nr, 2 * 512);
-            }
-#endif
-            if (int e = bwd_finalize(pp, nr, (double)N, 8, 512, 1, "bn_bwd_finalize_kernel(fc7, projection)")) return e;
+            // gradient above (round 3's first pass of the same product was removed; see git history)
+            if (int e = bwd_finalize(partials, PROJ_FINISH_ROWS, (double)N, 8, 512, 1, "bn_bwd_finalize_kernel(fc7, projection)")) return e;
             a.coef = coef; a.coef_mod = 512;
-            CK(launch_proj_dgrad<1>(a, st, &drows));
-            nr = drows;
-            pp = pre(nr, 512);
+            CK(launch_proj_dgrad(a, st, &drows));
+            int nr = drows;
+            const float* pp = pre(nr, 512);
             hipLaunchKernelGGL(colsum_finalize_kernel, dim3(FIN_GRID(512)), dim3(FIN_THREADS), 0, st, pp, nr, 512, g->fc_b[6]);
             CKL("colsum_finalize_kernel(fc7, projection)");
             bn_done = true;
@@ -1881,7 +1785,7 @@ static int encoder_backward_t(const cp_config* c, const cp_params* p, const floa
     // bn_done: BatchNorm + ReLU backward of layer L were applied by the data-gradient launch of the layer above (its
     // staged epilogue, GemmNTArgs::coef), so `cur` already is dL/d(pre-activation) and the bias gradient is written.
     // bf16 only, and only where no dropout sits between the layers (the coefficients must exist before the launch:
-    // they do when the BN-backward sums come from the weight gradient).  CPNATIVE_UNFUSED_BN_BWD (read per call)
+    // they do when the BN-backward sums come from the weight gradient).  CP_OPT_UNFUSED_BN_BWD (cp_config.options)
     // keeps the separate pass, for the test that compares the two orders.
     struct { const T* X; const T* Y; int i; } pend{};     // a weight gradient waiting for the next layer's (see defer_wgrad)
     bool pending = false;
@@ -2083,7 +1987,7 @@ static int encoder_backward_fp8(const cp_config* c, const cp_params* p, const fl
         ta.X = dz; ta.ldx = 64; ta.Y = base + w.act8[8]; ta.ldy = 512; ta.slabs = aux.on ? slabs_b : slabs; ta.M = N; ta.P = 64; ta.Q = 512;
         ta.y_exp = &fs->e[F8_T_ACT + 8];
         int S;
-        split_rows(N, CP_PROJ_SPLITS, &S, &ta.rows_per_split);
+        split_rows(N, kProjSplits, &S, &ta.rows_per_split);
         if (drop) {
             // (encoder_backward_t: one pass over r8 for the weight gradient AND fc7's BatchNorm-backward sums, on the critical path)
             ProjWgradArgs pa{};
@@ -2114,7 +2018,7 @@ static int encoder_backward_fp8(const cp_config* c, const cp_params* p, const fl
             if (int e = bwd_finalize(partials, 1, (double)N, 8, 512, 1, "bn_bwd_finalize_kernel(fc7, fused)")) return e;
         }
         a.coef = coef;
-        CK(launch_proj_dgrad8<1>(a, st, &drows));
+        CK(launch_proj_dgrad8(a, st, &drows));
         int nr = drows;
         const float* pp = pre(nr, 512);
         hipLaunchKernelGGL(colsum_finalize_kernel, dim3(FIN_GRID(512)), dim3(FIN_THREADS), 0, st, pp, nr, 512, g->fc_b[6]);
@@ -2425,17 +2329,11 @@ extern "C" int cp_debug_activation(const cp_config* cfg, const cp_params* p, con
         return 0;
     }
     const size_t off = layer < CP_N_BN ? w.act[layer] : w.u[layer - CP_N_BN];
-#ifdef CP_VARIANTS
-    const bool u8_stored = g_var.materialize_u8 != 0;
-#else
-    const bool u8_stored = false;
-#endif
-    (void)u8_stored;
     // dropout(BN(.)) of fc4..fc6 is STORED by the large-batch forward: read what it stored.  fc7's (formed while staging, never
     // written) and all four after a small-batch forward (csrc/small.cuh applies BatchNorm + dropout while staging) are recomputed from
     // the stored activation with the forward pass's key, into the otherwise unused buffer.
-    const bool stored_u = layer >= CP_N_BN && layer < CP_N_BN + 3 && last_forward_path(ws) == PATH_LARGE && !u8_stored;
-    if (layer >= CP_N_BN && !stored_u && !(u8_stored && layer == CP_N_BN + 3)) {
+    const bool stored_u = layer >= CP_N_BN && layer < CP_N_BN + 3 && last_forward_path(ws) == PATH_LARGE;
+    if (layer >= CP_N_BN && !stored_u) {
         const int Lp = 5 + (layer - CP_N_BN);
         const int64_t N = cfg->n_windows;
         const float* stp = (const float*)(base + w.stats[Lp]);
@@ -2459,7 +2357,7 @@ extern "C" int cp_debug_activation(const cp_config* cfg, const cp_params* p, con
 
 template <typename T>
 static int debug_gemm_t(int kind, int64_t M, int K, int F, const void* A, const void* W, void* C, const float* bias,
-                        const void* R, float* partials, int dbg, hipStream_t st) {
+                        const void* R, float* partials, hipStream_t st) {
     if (kind == 2) {
         int S;
         if constexpr (sizeof(T) == 2) {
@@ -2478,7 +2376,7 @@ static int debug_gemm_t(int kind, int64_t M, int K, int F, const void* A, const 
     }
     GemmNTArgs a{};
     a.A = A; a.lda = K; a.M = M; a.K = K; a.W = W; a.F = F; a.C = C; a.ldc = F; a.bias = bias; a.relu = 1;
-    a.R = R; a.ldr = F; a.partials = partials; a.dbg = dbg;
+    a.R = R; a.ldr = F; a.partials = partials;
     if (kind == 0) CK((launch_fc_gemm<T, EPI_FWD>(a, st)));
     else CK((launch_fc_gemm<T, EPI_DGRAD>(a, st)));
     return 0;
@@ -2499,11 +2397,11 @@ extern "C" int cp_debug_hog(int32_t blocks, int32_t microseconds, void* stream) 
 }
 
 extern "C" int cp_debug_gemm(int32_t dtype, int32_t kind, int64_t M, int32_t K, int32_t F, const void* A, const void* W,
-                             void* C, const float* bias, const void* R, float* partials, int32_t dbg, void* stream) {
+                             void* C, const float* bias, const void* R, float* partials, void* stream) {
     if (!A || !W || !C || !partials || M <= 0 || K % 64 || F % 256 || kind < 0 || kind > 2)
         return fail(CP_ERR_ARG, "cp_debug_gemm args");
-    if (dtype == CP_BF16) return debug_gemm_t<bf16_t>(kind, M, K, F, A, W, C, bias, R, partials, dbg, (hipStream_t)stream);
-    return debug_gemm_t<float>(kind, M, K, F, A, W, C, bias, R, partials, dbg, (hipStream_t)stream);
+    if (dtype == CP_BF16) return debug_gemm_t<bf16_t>(kind, M, K, F, A, W, C, bias, R, partials, (hipStream_t)stream);
+    return debug_gemm_t<float>(kind, M, K, F, A, W, C, bias, R, partials, (hipStream_t)stream);
 }
 
 extern "C" int cp_debug_bn_stats(const cp_config* cfg, void* ws, size_t ws_bytes, int32_t layer, float* out, void* stream) {

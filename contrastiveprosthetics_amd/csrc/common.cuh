@@ -24,16 +24,7 @@ __device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make
 
 // The product library has NO process-wide switches: everything a call depends on travels in its cp_config (include/cpnative.h:
 // options, tile_schedule, the synchronised-BatchNorm hook, the gradient tap), so two engines in one process cannot see each other's
-// settings.  Only the tools-only build (-DCP_VARIANTS: make -C csrc variants -> build/libcpnative_variants.so), which also carries
-// the kernels that were measured and superseded (tools/variants/*.cuh), keeps a global: one switch per superseded kernel, seeded
-// ONCE from $CPNATIVE_<NAME> when that library is loaded (tools/ab_env.sh).
-#ifdef CP_VARIANTS
-struct CpVariantOptions {
-    int no_ws = 0, no_wsk = 0, no_wsd = 0, no_wsd_st = 0, staged_r_epilogue = 0, ws32 = 0, wsd32 = 0, tn_w4 = 0, tn16 = 0,
-        materialize_u8 = 0, no_proj_fused = 0;
-};
-static CpVariantOptions g_var;
-#endif
+// settings.
 
 __device__ __forceinline__ float bf2f(bf16_t h) { return __uint_as_float(((uint32_t)h) << 16); }
 __device__ __forceinline__ bf16_t f2bf(float f) {                   // RNE, NaN stays NaN (v_cvt_pk_bf16_f32)

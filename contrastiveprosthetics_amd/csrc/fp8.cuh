@@ -330,9 +330,6 @@ __global__ __launch_bounds__(256, 1) void gemm_ws8_kernel(Ws8Args a) {
         fsrc[q] = (uint32_t)(row * K + (((pc & ~15) | ((pc ^ row) & 15)) << 4));
     }
     auto fetch_unit = [&](uint32_t tile_soff, int buf, int q) {
-#ifdef WS8_NO_FETCH
-        tile_soff = 0xFFF00000u;                    // ablation build (tools only): every fetch is out of range (zeros, no memory traffic)
-#endif
         bufl16_lds(a_rsrc, fsrc[q], tile_soff, lds0 + buf * TILE_BYTES + (wave * UPW + q) * 1024);
     };
     auto row0 = [&](int ti) -> int64_t { return ((int64_t)ti * stride + first) * RT; };
@@ -350,13 +347,6 @@ __global__ __launch_bounds__(256, 1) void gemm_ws8_kernel(Ws8Args a) {
 
     // epilogue of sample tile st of a finished tile: clamp(relu), sums, maximum, convert, transpose over the sample's 4 lanes, store
     auto epi_st = [&](f32x4_t (&old)[4][ST], int st, uint32_t s_old, bool live) {
-#ifdef WS8_NO_EPI
-        // ablation build (tools only): keep the finished accumulators alive, do nothing with them
-#pragma unroll
-        for (int ft = 0; ft < 4; ++ft) asm volatile("" :: "v"(old[ft][st]));
-        (void)s_old; (void)live;
-        return;
-#endif
         uint32_t d[4];
 #pragma unroll
         for (int ft = 0; ft < 4; ++ft) {
@@ -414,10 +404,6 @@ __global__ __launch_bounds__(256, 1) void gemm_ws8_kernel(Ws8Args a) {
     uint32_t dq[4] = {0u, 0u, 0u, 0u};
     auto epi_uop = [&](f32x4_t (&old)[4][ST], auto uc, uint32_t s_old) {
         constexpr int u = decltype(uc)::value, st = u / 19, r = u % 19;
-#ifdef WS8_NO_EPI
-        if constexpr (r == 0) asm volatile("" :: "v"(old[0][st]), "v"(old[1][st]), "v"(old[2][st]), "v"(old[3][st]));   // ablation build (tools only)
-        return;
-#endif
         if constexpr (r < 16) {
             // one output: clamp (ReLU and the format's range), column sum, column sum of squares; with the odd ones the running maximum of
             // the pair and its conversion into one half of the feature tile's dword.  Whole statements: nothing of them moves, and
@@ -449,11 +435,7 @@ __global__ __launch_bounds__(256, 1) void gemm_ws8_kernel(Ws8Args a) {
             asm volatile("" : "+v"(dq[0]), "+v"(dq[1]), "+v"(dq[2]), "+v"(dq[3]));
         } else {
             const u32x4_t c = {dq[0], dq[1], dq[2], dq[3]};
-#ifdef WS8_NO_STORE
-            asm volatile("" :: "v"(c));                                      // ablation build (tools only): everything but the store
-#else
             store_b128_settled(c, c_rsrc, c_lane, s_old + (uint32_t)(st * 16 * a.F), 0);
-#endif
         }
     };
 
@@ -504,15 +486,10 @@ __global__ __launch_bounds__(256, 1) void gemm_ws8_kernel(Ws8Args a) {
         // tile ti + 1 must have landed.  vmcnt retires in issue order (tools/vmcnt_order_probe.hip); younger than its LAST fetch are the
         // fetches of tiles ti + 2 .. ti + AHEAD and the stores of the epilogues that ran since: min(AHEAD, ti) epilogues, of the
         // oldest of which only the SA stores behind that step's last fetch count when all AHEAD are there
-#if defined(WS8_NO_STORE) || defined(WS8_NO_EPI)
-        constexpr int STC = 0, SAC = 0;                                      // ablation builds (tools only): no stores to count
-#else
-        constexpr int STC = ST, SAC = SA;
-#endif
         const int ne = ti < AHEAD ? ti : AHEAD;
         if (ne == 0) wait_vmcnt<(AHEAD - 1) * UPW>();
-        else if (ne < AHEAD) { if (ne == 1) wait_vmcnt<(AHEAD - 1) * UPW + STC>(); else wait_vmcnt<(AHEAD - 1) * UPW + 2 * STC>(); }
-        else wait_vmcnt<(AHEAD - 1) * UPW + (AHEAD - 1) * STC + SAC>();
+        else if (ne < AHEAD) { if (ne == 1) wait_vmcnt<(AHEAD - 1) * UPW + ST>(); else wait_vmcnt<(AHEAD - 1) * UPW + 2 * ST>(); }
+        else wait_vmcnt<(AHEAD - 1) * UPW + (AHEAD - 1) * ST + SA>();
         __builtin_amdgcn_s_barrier();
     };
     auto drain = [&](f32x4_t (&old)[4][ST], int64_t m_old) {
@@ -1353,18 +1330,18 @@ __global__ __launch_bounds__(256) void bn_relu_bwd8_kernel(uint8_t* __restrict__
 
 // ------------------------------------------------------------------------------------------------------------------------
 // The projection's data gradient behind fc7's dropout, 8-bit form of proj_dgrad_kernel (gemm_ws.cuh): g = mask (dz W) / (1 - p) is a
-// rank-16 product.  PASS 1 (coefficients final) is what the step launches: g, r > 0 ? ca g + cb r + cz : 0, stored as e5m2 (F8_T_GRAD + 8),
-// column sums = fc7's bias gradient.  PASS 0 -- the same product reduced to the two BatchNorm-backward sums against the saved e4m3
-// activation R, nothing stored -- was round 3's way to the coefficients and is no longer instantiated: the sums come with the projection's
-// weight gradient now (gemm_tn.cuh, proj_wgrad_sums_kernel<true>).  dz stays bf16 (16 live columns, [M][lda]); W = last_w^T in bf16 [512][K].
+// rank-16 product.  With the coefficients final: g, r > 0 ? ca g + cb r + cz : 0, stored as e5m2 (F8_T_GRAD + 8), column sums = fc7's
+// bias gradient.  The BatchNorm-backward sums behind the coefficients come with the projection's weight gradient (gemm_tn.cuh,
+// proj_wgrad_sums_kernel<true>); round 3's first pass of the same product for them was removed (see DESIGN.md / git history).
+// dz stays bf16 (16 live columns, [M][lda]); W = last_w^T in bf16 [512][K].
 // ------------------------------------------------------------------------------------------------------------------------
 struct Proj8Args {
     const bf16_t* A;        // dz [M][lda]
     const bf16_t* W;        // [512][K] bf16 (K >= 16: the first 16 columns are read)
     const uint8_t* R;       // [M][512] e4m3
-    uint8_t* C;             // [M][512] e5m2 (PASS 1)
+    uint8_t* C;             // [M][512] e5m2
     float* partials;
-    const float* coef;      // PASS 1: [3][512]
+    const float* coef;      // [3][512]
     Fp8State* st;
     int t_r, t_out;
     int64_t M;
@@ -1374,7 +1351,6 @@ struct Proj8Args {
     float dp_inv_keep;
 };
 
-template <int PASS>
 __global__ __launch_bounds__(256, 2) void proj_dgrad8_kernel(Proj8Args a) {
     f8_saturating_conversions();
     constexpr int RT = 32, ST = RT / 16, R_BYTES = RT * 64, F = 512;
@@ -1393,22 +1369,20 @@ __global__ __launch_bounds__(256, 2) void proj_dgrad8_kernel(Proj8Args a) {
     if (ntile == 0) return;
     const int f0 = fb * 256 + wave * 64;
     const uint32_t dkey = a.dp_thresh != 0 ? (a.dp_salt ? (a.dp_key ^ *a.dp_salt) : a.dp_key) : 0u;
-    const int e_r = a.st->e[a.t_r], e_o = PASS == 1 ? a.st->e[a.t_out] : 0;
+    const int e_r = a.st->e[a.t_r], e_o = a.st->e[a.t_out];
 
-    float4 cfa[PASS == 1 ? 4 : 1], cfb[PASS == 1 ? 4 : 1], cfz[PASS == 1 ? 4 : 1];
-    if constexpr (PASS == 1) {
-        const float so = f8_exp2i(e_o), sr = f8_exp2i(e_o - e_r);
+    float4 cfa[4], cfb[4], cfz[4];
+    const float so = f8_exp2i(e_o), sr = f8_exp2i(e_o - e_r);
 #pragma unroll
-        for (int ft = 0; ft < 4; ++ft) {
-            float v[3][4];
+    for (int ft = 0; ft < 4; ++ft) {
+        float v[3][4];
 #pragma unroll
-            for (int c = 0; c < 3; ++c)
+        for (int c = 0; c < 3; ++c)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[c][e] = a.coef[c * F + f0 + ft * 16 + 4 * q4 + e];
-            cfa[ft] = make_float4(v[0][0] * so, v[0][1] * so, v[0][2] * so, v[0][3] * so);
-            cfb[ft] = make_float4(v[1][0] * sr, v[1][1] * sr, v[1][2] * sr, v[1][3] * sr);
-            cfz[ft] = make_float4(v[2][0] * so, v[2][1] * so, v[2][2] * so, v[2][3] * so);
-        }
+            for (int e = 0; e < 4; ++e) v[c][e] = a.coef[c * F + f0 + ft * 16 + 4 * q4 + e];
+        cfa[ft] = make_float4(v[0][0] * so, v[0][1] * so, v[0][2] * so, v[0][3] * so);
+        cfb[ft] = make_float4(v[1][0] * sr, v[1][1] * sr, v[1][2] * sr, v[1][3] * sr);
+        cfz[ft] = make_float4(v[2][0] * so, v[2][1] * so, v[2][2] * so, v[2][3] * so);
     }
 
     typedef short s16x4_t __attribute__((ext_vector_type(4)));
@@ -1436,11 +1410,9 @@ __global__ __launch_bounds__(256, 2) void proj_dgrad8_kernel(Proj8Args a) {
         }
     };
 
-    float s1[16], s2[PASS == 0 ? 16 : 1], amax = 0.f;
+    float s1[16], amax = 0.f;
 #pragma unroll
     for (int p = 0; p < 16; ++p) s1[p] = 0.f;
-#pragma unroll
-    for (int p = 0; p < (PASS == 0 ? 16 : 1); ++p) s2[p] = 0.f;
     const auto c_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.C, 0, (int)((int64_t)a.M * F), 0x00020000);
     const uint32_t c_lane = (uint32_t)(s16 * F + f0 + q4 * 16);
 
@@ -1450,8 +1422,8 @@ __global__ __launch_bounds__(256, 2) void proj_dgrad8_kernel(Proj8Args a) {
     for (int ti = 0; ti < ntile; ++ti) {
         const int buf = ti & 1;
         const int64_t m0 = row0(ti);
-        // this tile's R sub-tile has landed (own DMA only).  PASS 1: the previous tile's ST stores are younger and stay in flight
-        if (PASS == 1 && ti > 0) wait_vmcnt<ST>();
+        // this tile's R sub-tile has landed (own DMA only); the previous tile's ST stores are younger and stay in flight
+        if (ti > 0) wait_vmcnt<ST>();
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (ti + 1 < ntile) { fetch_r(row0(ti + 1), buf ^ 1); load_dz(row0(ti + 1), dzn); }
         f32x4_t acc[4][ST];
@@ -1482,70 +1454,55 @@ __global__ __launch_bounds__(256, 2) void proj_dgrad8_kernel(Proj8Args a) {
                     y[2] *= dropout_scale(p1, 0, a.dp_thresh, a.dp_inv_keep);
                     y[3] *= dropout_scale(p1, 1, a.dp_thresh, a.dp_inv_keep);
                 }
-                if constexpr (PASS == 1) {
-                    const float4 ca = cfa[ft], cb = cfb[ft], cz = cfz[ft];
-                    y[0] = rv[0] > 0.f ? fmaf(ca.x, y[0], fmaf(cb.x, rv[0], cz.x)) : 0.f;
-                    y[1] = rv[1] > 0.f ? fmaf(ca.y, y[1], fmaf(cb.y, rv[1], cz.y)) : 0.f;
-                    y[2] = rv[2] > 0.f ? fmaf(ca.z, y[2], fmaf(cb.z, rv[2], cz.z)) : 0.f;
-                    y[3] = rv[3] > 0.f ? fmaf(ca.w, y[3], fmaf(cb.w, rv[3], cz.w)) : 0.f;
-                    amax = fmaxf(fmaxf(amax, fabsf(y[0])), fabsf(y[1]));
-                    amax = fmaxf(fmaxf(amax, fabsf(y[2])), fabsf(y[3]));
-                    d[ft] = f8_pack4_e5m2(y[0], y[1], y[2], y[3]);
-                    f8_unpack4_e5m2(d[ft], y);                       // (column sums of the values as stored)
-                }
+                const float4 ca = cfa[ft], cb = cfb[ft], cz = cfz[ft];
+                y[0] = rv[0] > 0.f ? fmaf(ca.x, y[0], fmaf(cb.x, rv[0], cz.x)) : 0.f;
+                y[1] = rv[1] > 0.f ? fmaf(ca.y, y[1], fmaf(cb.y, rv[1], cz.y)) : 0.f;
+                y[2] = rv[2] > 0.f ? fmaf(ca.z, y[2], fmaf(cb.z, rv[2], cz.z)) : 0.f;
+                y[3] = rv[3] > 0.f ? fmaf(ca.w, y[3], fmaf(cb.w, rv[3], cz.w)) : 0.f;
+                amax = fmaxf(fmaxf(amax, fabsf(y[0])), fabsf(y[1]));
+                amax = fmaxf(fmaxf(amax, fabsf(y[2])), fabsf(y[3]));
+                d[ft] = f8_pack4_e5m2(y[0], y[1], y[2], y[3]);
+                f8_unpack4_e5m2(d[ft], y);                           // (column sums of the values as stored)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float w = live ? y[e] : 0.f;
-                    s1[ft * 4 + e] += w;
-                    if constexpr (PASS == 0) s2[ft * 4 + e] = fmaf(w, rv[e], s2[ft * 4 + e]);
-                }
+                for (int e = 0; e < 4; ++e) s1[ft * 4 + e] += live ? y[e] : 0.f;
             }
-            if constexpr (PASS == 1) {
-                { const auto x = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false); d[0] = x[0]; d[2] = x[1]; }
-                { const auto x = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false); d[1] = x[0]; d[3] = x[1]; }
-                { const auto x = __builtin_amdgcn_permlane16_swap(d[0], d[1], false, false); d[0] = x[0]; d[1] = x[1]; }
-                { const auto x = __builtin_amdgcn_permlane16_swap(d[2], d[3], false, false); d[2] = x[0]; d[3] = x[1]; }
-                const u32x4_t c = {d[0], d[1], d[2], d[3]};
-                store_b128_settled(c, c_rsrc, c_lane, (uint32_t)((m0 + st * 16) * F), 0);
-            }
+            { const auto x = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false); d[0] = x[0]; d[2] = x[1]; }
+            { const auto x = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false); d[1] = x[0]; d[3] = x[1]; }
+            { const auto x = __builtin_amdgcn_permlane16_swap(d[0], d[1], false, false); d[0] = x[0]; d[1] = x[1]; }
+            { const auto x = __builtin_amdgcn_permlane16_swap(d[2], d[3], false, false); d[2] = x[0]; d[3] = x[1]; }
+            const u32x4_t c = {d[0], d[1], d[2], d[3]};
+            store_b128_settled(c, c_rsrc, c_lane, (uint32_t)((m0 + st * 16) * F), 0);
         }
 #pragma unroll
         for (int st = 0; st < ST; ++st) dzf[st] = dzn[st];
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const float u1 = f8_exp2i(-e_o), u2 = f8_exp2i(-e_r);
-    float r1[2], r2[2];
+    const float u1 = f8_exp2i(-e_o);
+    float r1[2];
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh) {
-        float v1[8], v2[8];
+        float v1[8];
 #pragma unroll
-        for (int p = 0; p < 8; ++p) { v1[p] = s1[hh * 8 + p]; v2[p] = PASS == 0 ? s2[hh * 8 + p] : 0.f; }
+        for (int p = 0; p < 8; ++p) v1[p] = s1[hh * 8 + p];
         r1[hh] = row16_fold8(v1, lane) * u1;
-        r2[hh] = PASS == 0 ? row16_fold8(v2, lane) * u2 : 0.f;
     }
     if (s16 < 8) {
         const int64_t prow = (int64_t)wkr * 8 + xcd;
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh) {
             const int idx = hh * 8 + s16, f = f0 + (idx >> 2) * 16 + 4 * q4 + (idx & 3);
-            if constexpr (PASS == 0) {
-                a.partials[(prow * 2 + 0) * F + f] = r1[hh];
-                a.partials[(prow * 2 + 1) * F + f] = r2[hh];
-            } else {
-                a.partials[prow * F + f] = r1[hh];
-            }
+            a.partials[prow * F + f] = r1[hh];
         }
     }
-    if constexpr (PASS == 1) f8_atomic_amax(&a.st->amax[a.t_out], amax);
+    f8_atomic_amax(&a.st->amax[a.t_out], amax);
 }
 
-template <int PASS>
 static inline hipError_t launch_proj_dgrad8(const Proj8Args& a, hipStream_t st, int* stat_rows) {
-    if (a.K < 16 || (a.K & 3) || !a.R || (PASS == 1 && !a.coef) || (uint64_t)a.M * 512 >= 0xFFF00000ull) return hipErrorInvalidValue;
+    if (a.K < 16 || (a.K & 3) || !a.R || !a.coef || (uint64_t)a.M * 512 >= 0xFFF00000ull) return hipErrorInvalidValue;
     const int blocks = PROJ_DGRAD_BLOCKS, nwk = (blocks >> 3) / 2;
     const int64_t tiles = (a.M + 31) / 32, workers = (int64_t)nwk * 8;
     if (stat_rows) *stat_rows = (int)(tiles < workers ? tiles : workers);
-    hipLaunchKernelGGL(proj_dgrad8_kernel<PASS>, dim3(blocks), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(proj_dgrad8_kernel, dim3(blocks), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 

@@ -1,4 +1,4 @@
-// Persistent form of the bf16 256 x 256 NT GEMM (gemm_nt256.cuh) for the fc forward pass and for
+// Persistent form of the bf16 256 x 256 NT GEMM for the fc forward pass and for
 // data gradients that carry no statistics: ONE 8-wave block per CU for the whole launch, each block
 // walking its own list of output tiles.
 //
@@ -7,8 +7,8 @@
 // nothing else on the CU, (a) the fill of its first stage, (b) its K loop, (c) the drain of its
 // 128 KiB of C stores.  Here the K loop is flattened across the block's tiles: the first stage of
 // tile n+1 is requested during the last K step of tile n, and tile n's stores -- written straight
-// from the accumulator registers, no LDS staging, no barrier (see the register-direct epilogue in
-// gemm_nt256.cuh) -- drain underneath tile n+1's first K step.
+// from the accumulator registers, no LDS staging, no barrier (nt256p_convert) -- drain underneath
+// tile n+1's first K step.  (The one-tile-per-block kernel was removed; see DESIGN.md / git history.)
 //
 // Tile schedule, XCD-aware, two forms behind one template flag (cp_set_tile_schedule picks per process).
 // Dynamic: block b runs on XCD b & 7 and draws that XCD's tiles -- sample tile
@@ -66,7 +66,21 @@
 // with a lone wave per SIMD nothing covers its LDS and barrier latencies, and hipcc's schedule does not either.
 #pragma once
 #include <mutex>
-#include "gemm_nt256.cuh"
+#include "common.cuh"
+#include "gemm_nt.cuh"
+
+// One LDS-DMA wave instruction (1 KiB): LDS[lds_dst + 16*lane] = *(16 bytes at gsrc), issued from
+// inline asm so that hipcc does NOT track it: with the builtin the compiler waits vmcnt(0) before
+// the next ds_read of the same __shared__ array, which serialises the next tile's loads with the
+// current tile's MFMAs.  M0 (the LDS base) is compiler-reserved, so it is saved, set and restored
+// inside the one statement (guide 5.7).  Completion is ordered by the explicit vmcnt waits of the callers.
+__device__ __forceinline__ void glds16(const void* gsrc, uint32_t lds_dst_uniform) {
+    uint32_t keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(gsrc), "s"(lds_dst_uniform)
+                 : "memory");
+}
 
 #define NT256P_MAX_TILES_F 3      // F <= 768: the encoder's widest data gradient
 #define NT256P_SCHED_SLOTS 64     // streams per process that may run this kernel
@@ -82,7 +96,9 @@ __device__ __forceinline__ float dpp_quad(float w) {
 __device__ __forceinline__ void store_c16(bf16_t* p, const uint4& c) { *(uint4*)p = c; }
 // (cvt_pk_bf16<RELU>: common.cuh)
 
-// Register-direct epilogue of one tile (see gemm_nt256.cuh for the lane algebra): converts the accumulators
+// Register-direct epilogue of one tile.  A lane holds, per 32x32 tile, 4 runs of 4 consecutive features of ONE
+// sample row; v_permlane32_swap exchanges the upper half-wave of run q with the lower half-wave of run q+1, after
+// which every lane owns 8 consecutive features = one 16-byte store (guide T21).  Converts the accumulators
 // into 16-byte chunks (features i*32 + 8*(2kk + h) .. +7 of row mw0 + jj*32 + r; base = &C[mw0 + r][fw0 + 8h]),
 // stores them and folds the BatchNorm sums.  FULL = every row of the tile exists (only the launch's very
 // last sample tile can be ragged).  EPI_FWD: the accumulators already hold the bias (they were initialised

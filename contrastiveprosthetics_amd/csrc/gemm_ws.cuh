@@ -30,8 +30,6 @@
 #include "gemm_nt256p.cuh"     // glds16, quad_fold
 
 #define WS_K 512
-#define WS_RT 64
-#define WS_TILE_BYTES (WS_RT * WS_K * 2)
 
 // A 16-byte buffer store of freshly computed data.  hipcc (ROCm 7.2) may place a VALU instruction that overwrites the store's data
 // registers directly behind the store -- for MUBUF stores with the offset in an SGPR LLVM's hazard recogniser assumes that is safe.  On
@@ -47,7 +45,7 @@ __device__ __forceinline__ void store_b128_settled(const V4& c, RSRC rsrc, uint3
 
 // One LDS-DMA row fetch through a buffer descriptor: LDS[lds_dst + 16*lane] = 16 bytes at base + soff + voff, ZERO where
 // that lies past the end of the buffer (the rows behind the last one of a ragged tile need no clamping).  Issued from
-// inline asm so that hipcc does not track it (gemm_nt256.cuh, glds16); M0 saved, set and restored in the statement.
+// inline asm so that hipcc does not track it (gemm_nt256p.cuh, glds16); M0 saved, set and restored in the statement.
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 __device__ __forceinline__ void bufl16_lds(const u32x4_t& rsrc, uint32_t voff, uint32_t soff_uniform, uint32_t lds_dst_uniform) {
     uint32_t keep;
@@ -56,10 +54,6 @@ __device__ __forceinline__ void bufl16_lds(const u32x4_t& rsrc, uint32_t voff, u
                  : "v"(voff), "s"(rsrc), "s"(soff_uniform), "s"(lds_dst_uniform)
                  : "memory");
 }
-
-#ifdef CP_VARIANTS   // the 32x32x16 form of the weight-stationary forward kernel (superseded by gemm_ws16_kernel)
-#include "../../tools/variants/gemm_ws32_fwd.cuh"
-#endif
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The forward kernel on v_mfma_f32_16x16x32_bf16.  Under the chip's power cap the 16x16x32 shape delivers 1.12-1.15x the
@@ -92,14 +86,9 @@ __device__ __forceinline__ float row16_fold8(float (&v)[8], int lane) {
     for (int p = 0; p < 2; ++p) v[p] = (b1 ? v[2 * p + 1] : v[2 * p]) + dpp_quad<0x4E>(b1 ? v[2 * p] : v[2 * p + 1]);
     const float give = b2 ? v[0] : v[1];
     // lane ^ 4 and lane ^ 8 inside a row of 16 by DPP alone (no LDS crossbar): quad reverse (^3) then row_half_mirror (^7) = ^4;
-    // row_ror:8 = ^8.  (-DFOLD_SWIZZLE: the ds_swizzle form, same lanes.)
-#ifdef FOLD_SWIZZLE
-    const float w = (b2 ? v[1] : v[0]) + __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(give), 0x101F));            // lane ^ 4
-    return w + __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(w), 0x201F));                                          // lane ^ 8
-#else
+    // row_ror:8 = ^8.  (The ds_swizzle form of the same two steps was removed; see DESIGN.md / git history.)
     const float w = (b2 ? v[1] : v[0]) + dpp_quad<0x141>(dpp_quad<0x1B>(give));
     return w + dpp_quad<0x128>(w);
-#endif
 }
 
 // STATS = false (round 4): evaluation with the running statistics -- nobody reads the column sums, so the epilogue is max / convert / store
@@ -221,15 +210,11 @@ __global__ __launch_bounds__(256, 1) void gemm_ws16_kernel(GemmNTArgs a) {
                     acc.t[ft][st] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wreg[ft][kb], __builtin_bit_cast(s16x8, fa[st]), acc.t[ft][st], 0, 0, 0);
                 if (kb + 1 < KB) fa[st] = *(const uint4*)(At + st * 16384 + ((((kb + 1) * 4) << 4) ^ d16));
             }
-#ifdef WS16_WOVEN_EPI
-            if constexpr (WITH_EPI)
-                if (kb >= 6 && kb < 6 + 2 * ST) epi_slot(old, kb - 6, s_old, all_live);
-#endif
         }
-#ifndef WS16_WOVEN_EPI
         // The previous tile's epilogue runs BEHIND the k loop, not inside it: with the matrix pipe of every CU busy, vector
         // instructions issued beside the MFMAs cost more than their own time (tools/coissue_probe.hip: 257 us of MFMAs + 141 us of
-        // FMAs take 472 us interleaved); measured in the step 99-101 us per launch against 106-107 woven (-DWS16_WOVEN_EPI).
+        // FMAs take 472 us interleaved); measured in the step 99-101 us per launch against 106-107 woven into the k loop (that form
+        // was removed; see DESIGN.md / git history).
         // It stays the PREVIOUS tile's epilogue (two accumulator sets): with one set and the tile's own epilogue behind its k loop
         // the epilogue waits for the last MFMAs and the next tile's first MFMAs for the epilogue -- 114-119 us.
         if constexpr (WITH_EPI) {
@@ -246,9 +231,6 @@ __global__ __launch_bounds__(256, 1) void gemm_ws16_kernel(GemmNTArgs a) {
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-#else
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
         __builtin_amdgcn_s_barrier();
     };
     auto drain = [&](Ws16Acc& old, int64_t m_old) {
@@ -301,9 +283,6 @@ __global__ __launch_bounds__(256, 1) void gemm_ws16_kernel(GemmNTArgs a) {
 #define WSK_RT 32
 #define WSK_ROWB (WSK_K * 2)
 #define WSK_TILE_BYTES (WSK_RT * WSK_ROWB)
-#ifdef CP_VARIANTS   // rounds 2-3's form: the k range split over wave pairs, partial sums exchanged through LDS (superseded by gemm_ws16n_kernel)
-#include "../../tools/variants/gemm_ws16k_splitk.cuh"
-#endif
 
 // ---------------------------------------------------------------------------------------------------------------------
 // fc1 forward (K = 768), round 4 ("the 8-bit kernel got rid of the wave-pair exchange by making one wave own a whole
@@ -509,13 +488,7 @@ static inline hipError_t launch_gemm_ws16n(const GemmNTArgs& a, hipStream_t st, 
 // what it fetched itself, so its own vmcnt wait at the end of the tile is all the ordering that is needed.  Two accumulator
 // sets of 32 registers.  The three coefficient rows of the block's 256 features sit in LDS.
 // ---------------------------------------------------------------------------------------------------------------------
-#define WSD_RT 32
-#define WSD_TILE_BYTES (WSD_RT * WS_K * 2)
 #define WSD16_RT 32          // 48-row tiles (as in the forward) spill here: the epilogue holds R and the coefficients as well
-
-#ifdef CP_VARIANTS   // the 32x32x16 form of the BN-fused data gradient (superseded by gemm_wsd16_kernel<0>)
-#include "../../tools/variants/gemm_wsd32_bn.cuh"
-#endif
 
 // The data-gradient kernel on v_mfma_f32_16x16x32_bf16 (see gemm_ws16_kernel): 32-row tiles = 2 sample tiles of 16, the saved
 // activation read in the 16x16 accumulator layout (lane (q4, s): features ft*16 + 4*q4 .. +3 of row st*16 + s).
@@ -746,13 +719,12 @@ __global__ __launch_bounds__(256, 1) void gemm_wsd16_kernel(GemmNTArgs a) {
 
 // ---- the projection's data gradient (K = 16 live columns of dz, F = 512) behind fc7's dropout ---------------------------------
 // g = mask * (dz W) is a rank-16 product: cheap enough to compute TWICE instead of writing it out and reading it back for the
-// BatchNorm + ReLU backward pass (172 MB each way + the pass's own launch).  PASS 0: the two BatchNorm-backward sums of g against the
-// saved activation R, nothing stored (reads R once).  PASS 1, after the coefficients are final: recompute g, apply
-// r > 0 ? ca*g + cb*r + cz : 0, store, column sums of the result (= fc7's bias gradient).  One v_mfma_f32_16x16x16_bf16 per 16 x 16
+// BatchNorm + ReLU backward pass (172 MB each way + the pass's own launch).  After the coefficients are final (their sums come with the
+// projection's weight gradient, gemm_tn.cuh proj_wgrad_sums_kernel): recompute g, apply r > 0 ? ca*g + cb*r + cz : 0, store, column sums of the result (= fc7's bias gradient).
+// (A first pass of the same product for the two BatchNorm-backward sums was removed; see DESIGN.md / git history.)  One v_mfma_f32_16x16x16_bf16 per 16 x 16
 // outputs, its operands straight from global memory (8 bytes per lane); a wave owns 64 features of a 32-row tile, fetches its R sub-tile
 // by LDS-DMA one tile ahead and never meets the other waves (no barrier in the loop).  Partial rows as gemm_wsd16_kernel writes them.
 #define PROJ_RT 32
-template <int PASS>
 __global__ __launch_bounds__(256, 2) void proj_dgrad_kernel(GemmNTArgs a) {
     constexpr int RT = PROJ_RT, ST = RT / 16, R_BYTES = RT * 128;
     constexpr int COEF_OFF = 4 * 2 * R_BYTES;
@@ -770,13 +742,11 @@ __global__ __launch_bounds__(256, 2) void proj_dgrad_kernel(GemmNTArgs a) {
     const int first = wkr * 8 + xcd, stride = nwk * 8;
     const int ntile = (wkr < nwk && first < tiles) ? (int)((tiles - first + stride - 1) / stride) : 0;
     if (ntile == 0) return;
-    if constexpr (PASS == 1) {
-        for (int q = tid; q < 3 * 256; q += 256) {
-            const int c = q >> 8, f = fb * 256 + (q & 255);
-            coef_s[q] = a.coef[c * a.coef_mod + f % a.coef_mod];
-        }
-        __syncthreads();
+    for (int q = tid; q < 3 * 256; q += 256) {
+        const int c = q >> 8, f = fb * 256 + (q & 255);
+        coef_s[q] = a.coef[c * a.coef_mod + f % a.coef_mod];
     }
+    __syncthreads();
     const int f0 = fb * 256 + wave * 64, fl0 = wave * 64;
     const uint32_t dkey = a.dp_thresh != 0 ? (a.dp_salt ? (a.dp_key ^ *a.dp_salt) : a.dp_key) : 0u;
 
@@ -808,7 +778,7 @@ __global__ __launch_bounds__(256, 2) void proj_dgrad_kernel(GemmNTArgs a) {
         }
     };
 
-    float qs1[2] = {0.f, 0.f}, qs2[2] = {0.f, 0.f};
+    float qs1[2] = {0.f, 0.f};
     const auto c_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.C, 0, (int)((int64_t)a.M * a.ldc * 2), 0x00020000);
     const int foff = ((q4 & 1) << 4) | ((q4 >> 1) << 3);
     const uint32_t c_lane = (uint32_t)(s16 * a.ldc + f0 + foff) * 2;
@@ -819,9 +789,9 @@ __global__ __launch_bounds__(256, 2) void proj_dgrad_kernel(GemmNTArgs a) {
     for (int ti = 0; ti < ntile; ++ti) {
         const int buf = ti & 1;
         const int64_t m0 = row0(ti);
-        // this tile's R sub-tile has landed (own DMA only).  PASS 1: the previous tile's 2*ST stores are younger than that fetch and
+        // this tile's R sub-tile has landed (own DMA only); the previous tile's 2*ST stores are younger than that fetch and
         // stay in flight (tools/vmcnt_order_probe.hip)
-        if (PASS == 1 && ti > 0) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        if (ti > 0) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (ti + 1 < ntile) { fetch_r(row0(ti + 1), buf ^ 1); load_dz(row0(ti + 1), dzn); }
         f32x4_t acc[4][ST];
@@ -832,7 +802,7 @@ __global__ __launch_bounds__(256, 2) void proj_dgrad_kernel(GemmNTArgs a) {
                 acc[ft][st] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(wfrag[ft], dzf[st], (f32x4_t){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
         const unsigned char* Rw = smem + (wave * 2 + buf) * R_BYTES;
         const uint32_t s_out = (uint32_t)(m0 * a.ldc * 2);
-        float t1[8], t2[8];
+        float t1[8];
 #pragma unroll
         for (int u = 0; u < 2 * ST; ++u) {
             const int fp = u / ST, st = u % ST;
@@ -860,38 +830,27 @@ __global__ __launch_bounds__(256, 2) void proj_dgrad_kernel(GemmNTArgs a) {
                 // the masked gradient as the two-kernel path stores it (bf16), so both orders see the same numbers
                 const uint32_t gx = cvt_pk_bf16<false>(y0, y1), gy = cvt_pk_bf16<false>(y2, y3);
                 float g[4] = {__uint_as_float(gx << 16), __uint_as_float(gx & 0xffff0000u), __uint_as_float(gy << 16), __uint_as_float(gy & 0xffff0000u)};
-                const float rv[4] = {r0, r1, r2, r3};
-                if constexpr (PASS == 1) {
-                    const int fl = fl0 + ft * 16 + 4 * q4;
-                    const float4 ca = *(const float4*)(coef_s + fl), cb = *(const float4*)(coef_s + 256 + fl), cz = *(const float4*)(coef_s + 512 + fl);
-                    g[0] = r0 > 0.f ? fmaf(ca.x, g[0], fmaf(cb.x, r0, cz.x)) : 0.f;
-                    g[1] = r1 > 0.f ? fmaf(ca.y, g[1], fmaf(cb.y, r1, cz.y)) : 0.f;
-                    g[2] = r2 > 0.f ? fmaf(ca.z, g[2], fmaf(cb.z, r2, cz.z)) : 0.f;
-                    g[3] = r3 > 0.f ? fmaf(ca.w, g[3], fmaf(cb.w, r3, cz.w)) : 0.f;
-                    pk[o].x = cvt_pk_bf16<false>(g[0], g[1]);
-                    pk[o].y = cvt_pk_bf16<false>(g[2], g[3]);
-                    g[0] = __uint_as_float(pk[o].x << 16); g[1] = __uint_as_float(pk[o].x & 0xffff0000u);
-                    g[2] = __uint_as_float(pk[o].y << 16); g[3] = __uint_as_float(pk[o].y & 0xffff0000u);
-                }
+                const int fl = fl0 + ft * 16 + 4 * q4;
+                const float4 ca = *(const float4*)(coef_s + fl), cb = *(const float4*)(coef_s + 256 + fl), cz = *(const float4*)(coef_s + 512 + fl);
+                g[0] = r0 > 0.f ? fmaf(ca.x, g[0], fmaf(cb.x, r0, cz.x)) : 0.f;
+                g[1] = r1 > 0.f ? fmaf(ca.y, g[1], fmaf(cb.y, r1, cz.y)) : 0.f;
+                g[2] = r2 > 0.f ? fmaf(ca.z, g[2], fmaf(cb.z, r2, cz.z)) : 0.f;
+                g[3] = r3 > 0.f ? fmaf(ca.w, g[3], fmaf(cb.w, r3, cz.w)) : 0.f;
+                pk[o].x = cvt_pk_bf16<false>(g[0], g[1]);
+                pk[o].y = cvt_pk_bf16<false>(g[2], g[3]);
+                g[0] = __uint_as_float(pk[o].x << 16); g[1] = __uint_as_float(pk[o].x & 0xffff0000u);
+                g[2] = __uint_as_float(pk[o].y << 16); g[3] = __uint_as_float(pk[o].y & 0xffff0000u);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float w = live ? g[e] : 0.f;
                     if (st == 0) t1[o * 4 + e] = w; else t1[o * 4 + e] += w;
-                    if constexpr (PASS == 0) {
-                        if (st == 0) t2[o * 4 + e] = w * rv[e]; else t2[o * 4 + e] = fmaf(w, rv[e], t2[o * 4 + e]);
-                    }
                 }
             }
-            if constexpr (PASS == 1) {
-                const auto sx = __builtin_amdgcn_permlane16_swap(pk[0].x, pk[1].x, false, false);
-                const auto sy = __builtin_amdgcn_permlane16_swap(pk[0].y, pk[1].y, false, false);
-                const u32x4_t c = {sx[0], sy[0], sx[1], sy[1]};
-                store_b128_settled(c, c_rsrc, c_lane, s_out + (uint32_t)(st * 16 * a.ldc + fp * 32) * 2, 0);
-            }
-            if (st == ST - 1) {
-                qs1[fp] += row16_fold8(t1, lane);
-                if constexpr (PASS == 0) qs2[fp] += row16_fold8(t2, lane);
-            }
+            const auto sx = __builtin_amdgcn_permlane16_swap(pk[0].x, pk[1].x, false, false);
+            const auto sy = __builtin_amdgcn_permlane16_swap(pk[0].y, pk[1].y, false, false);
+            const u32x4_t c = {sx[0], sy[0], sx[1], sy[1]};
+            store_b128_settled(c, c_rsrc, c_lane, s_out + (uint32_t)(st * 16 * a.ldc + fp * 32) * 2, 0);
+            if (st == ST - 1) qs1[fp] += row16_fold8(t1, lane);
         }
 #pragma unroll
         for (int st = 0; st < ST; ++st) dzf[st] = dzn[st];
@@ -901,77 +860,43 @@ __global__ __launch_bounds__(256, 2) void proj_dgrad_kernel(GemmNTArgs a) {
 #pragma unroll
         for (int fp = 0; fp < 2; ++fp) {
             const int f = f0 + fp * 32 + (s16 >> 2) * 16 + 4 * q4 + (s16 & 3);
-            if constexpr (PASS == 0) {
-                a.partials[(prow * 2 + 0) * a.F + f] = qs1[fp];
-                a.partials[(prow * 2 + 1) * a.F + f] = qs2[fp];
-            } else {
-                a.partials[prow * a.F + f] = qs1[fp];
-            }
+            a.partials[prow * a.F + f] = qs1[fp];
         }
     }
 }
 
 // grid: 4 workgroups per CU (32 KiB of LDS and ~100 registers each); *stat_rows = partial rows written
-template <int PASS>
 static inline hipError_t launch_proj_dgrad(const GemmNTArgs& a, hipStream_t st, int* stat_rows) {
-    if ((a.F & 255) || a.K < 16 || (a.K & 3) || !a.R || (PASS == 1 && !a.coef)) return hipErrorInvalidValue;
+    if ((a.F & 255) || a.K < 16 || (a.K & 3) || !a.R || !a.coef) return hipErrorInvalidValue;
 // workgroups of the projection's data-gradient launches (this one and fp8.cuh's): two per CU.  1024 / 768 / 512 / 384 / 256 on one box:
 // 84-89 / 82-84 / 76-81 / 95 / 98 us (16-bit), 62-63 / 57 / 54-57 / 70 / 68 (8-bit)
 #define PROJ_DGRAD_BLOCKS 512
     const int blocks = PROJ_DGRAD_BLOCKS, nwk = (blocks >> 3) / (a.F >> 8);
     const int64_t tiles = (a.M + PROJ_RT - 1) / PROJ_RT, workers = (int64_t)nwk * 8;
     if (stat_rows) *stat_rows = (int)(tiles < workers ? tiles : workers);
-    hipLaunchKernelGGL(proj_dgrad_kernel<PASS>, dim3(blocks), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(proj_dgrad_kernel, dim3(blocks), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 
 static inline hipError_t launch_gemm_wsd_bn(const GemmNTArgs& a, hipStream_t st, int* stat_rows) {
     if (a.K != WS_K || (a.F & 255) || a.F > 768 || a.lda != WS_K || !a.R) return hipErrorInvalidValue;
-    if (!a.coef) {
-        // behind a dropout: mask + BatchNorm-backward sums (16x16x32 form only)
-        const int nwk_ = 32 / (a.F >> 8);
-        const int64_t tiles_ = (a.M + WSD16_RT - 1) / WSD16_RT, workers_ = (int64_t)nwk_ * 8;
-        if (stat_rows) *stat_rows = (int)(tiles_ < workers_ ? tiles_ : workers_);
-        hipLaunchKernelGGL(gemm_wsd16_kernel<1>, dim3(256), dim3(256), 0, st, a);
-        return hipGetLastError();
-    }
-#ifdef CP_VARIANTS
-    const bool m16 = !(a.dbg & 512) && !g_var.ws32 && !g_var.wsd32;          // (else the 32x32x16 form)
-#else
-    const bool m16 = true;
-#endif
-    const int nfb = a.F >> 8, nwk = 32 / nfb, rt = m16 ? WSD16_RT : WSD_RT;
-    const int64_t tiles = (a.M + rt - 1) / rt;
+    const int nfb = a.F >> 8, nwk = 32 / nfb;
+    const int64_t tiles = (a.M + WSD16_RT - 1) / WSD16_RT;
     const int64_t workers = (int64_t)nwk * 8;
     if (stat_rows) *stat_rows = (int)(tiles < workers ? tiles : workers);
-#ifdef CP_VARIANTS
-    if (!m16) { hipLaunchKernelGGL(gemm_wsd_bn_kernel, dim3(256), dim3(256), 0, st, a); return hipGetLastError(); }
-#endif
-    hipLaunchKernelGGL(gemm_wsd16_kernel<0>, dim3(256), dim3(256), 0, st, a);
+    // without coefficients: behind a dropout, mask + BatchNorm-backward sums
+    if (!a.coef) hipLaunchKernelGGL(gemm_wsd16_kernel<1>, dim3(256), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(gemm_wsd16_kernel<0>, dim3(256), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 
 // static schedule only (a process that has the GPU to itself); *stat_rows = partial rows written
-template <int EPI>
 static inline hipError_t launch_gemm_ws(const GemmNTArgs& a, hipStream_t st, int* stat_rows) {
     if (a.K != WS_K || (a.F & 255) || a.F > 768 || a.lda != WS_K) return hipErrorInvalidValue;
     const int nfb = a.F >> 8, nwk = 32 / nfb;
-#ifdef CP_VARIANTS
-    const bool m16 = EPI == EPI_FWD && !(a.dbg & 512) && !g_var.ws32;
-#else
-    const bool m16 = true;
-#endif
-    const int rt = m16 ? WS16_RT : WS_RT;
-    const int64_t tiles = (a.M + rt - 1) / rt;
+    const int64_t tiles = (a.M + WS16_RT - 1) / WS16_RT;
     const int64_t workers = (int64_t)nwk * 8;
     if (stat_rows) *stat_rows = (int)(tiles < workers ? tiles : workers);
-#ifndef WS_WAVES
-#define WS_WAVES 4
-#endif
-#ifdef CP_VARIANTS
-    // (dbg 512 / option ws32: the v_mfma_f32_32x32x16_bf16 form instead of the 16x16x32 one)
-    if (!m16) { hipLaunchKernelGGL((gemm_ws_kernel<EPI, WS_WAVES>), dim3(256), dim3(64 * WS_WAVES), 0, st, a); return hipGetLastError(); }
-#endif
     if (a.partials != nullptr) hipLaunchKernelGGL(gemm_ws16_kernel<true>, dim3(256), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(gemm_ws16_kernel<false>, dim3(256), dim3(256), 0, st, a);
     return hipGetLastError();

@@ -108,9 +108,9 @@ __device__ __forceinline__ uint4 sm_bn_drop_chunk(const uint4& in, const float* 
 // i + 2 are issued as soon as step i's registers have gone to LDS.  `mid()` runs between the first two steps' loads and their first use:
 // the kernels pass their statistics prologue (a round trip of its own, and a barrier) there, so it hides under the operand fetch.
 // One LDS stage: store, barrier, MFMAs, barrier -- with every load already in flight the second buffer bought nothing.
-// History (tools/small_stamps.py, k loop of one fc forward launch at 328 rows, bf16): one 64-deep sub-tile per step, loads one step
-// ahead, 21 us per layer; two sub-tiles, loads two steps ahead but TRANSFORMED in the load phase (every step waited for the load it had
-// just issued) 6.5 us; raw loads, transforms at store time 4.6 us; this form: see DESIGN.md 7g.
+// History (timestamps of the k loop of one fc forward launch at 328 rows, bf16; that diagnostic build is in git history): one 64-deep
+// sub-tile per step, loads one step ahead, 21 us per layer; two sub-tiles, loads two steps ahead but TRANSFORMED in the load phase
+// (every step waited for the load it had just issued) 6.5 us; raw loads, transforms at store time 4.6 us; this form: see DESIGN.md 7g.
 template <typename T> struct SmNsub { static constexpr int v = sizeof(T) == 2 ? 4 : 2; };
 // f32: a wave's k loop is a chain of 64-cycle v_mfma_f32_32x32x2_f32 on one accumulator (256 of them for K = 512: 7.8 us at best, 13 us
 // measured, of a 17 us launch), so the contraction is split over wave PAIRS: 64-feature tiles, wave w = feature group w & 1, k half
@@ -123,7 +123,7 @@ template <typename T> static inline bool sm_ksplit(int64_t n_windows) { return (
 // thread's 16-byte chunk (row tid >> 3 [+ 32 i], chunk tid & 7) of sub-tile `sub`; xformA(raw, sub) turns the raw A chunk into the operand.
 template <typename T, int BN, typename RawA, bool KSPLIT = false, typename FA, typename XA, typename FW, typename Mid>
 __device__ __forceinline__ void sm_nt_loop(f32x16& acc, unsigned char* smem, int nsub, FA&& loadA, XA&& xformA, FW&& loadW, int wrow, bool do_mma,
-                                           Mid&& mid, long long* dbg = nullptr) {
+                                           Mid&& mid) {
     constexpr int NSUB = SmNsub<T>::v;
     constexpr int A_BYTES = SM_BM * 128, W_BYTES = BN * 128, SUB = A_BYTES + W_BYTES, W_IT = BN / 32;
     const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5, sc = tid & 7, sr = tid >> 3;
@@ -168,40 +168,21 @@ __device__ __forceinline__ void sm_nt_loop(f32x16& acc, unsigned char* smem, int
             }
         }
     };
-#ifdef SM_STAMP
-    auto lstamp = [&](int slot) {
-        __builtin_amdgcn_sched_barrier(0);
-        if (dbg && blockIdx.x == 0 && threadIdx.x == 0) dbg[slot] = (long long)__builtin_amdgcn_s_memrealtime();
-        __builtin_amdgcn_sched_barrier(0);
-    };
-#else
-    auto lstamp = [&](int) {};
-#endif
     load(0, 0);
     if (nit > 1) load(1, 1);
-    lstamp(0);
     mid();
-    lstamp(1);
     for (int it = 0; it < nit; it += 2) {
         store(it, 0);
-        lstamp(2 + 4 * it);
         __syncthreads();
         if (it + 2 < nit) load(it + 2, 0);
-        lstamp(3 + 4 * it);
         compute();
-        lstamp(4 + 4 * it);
         __syncthreads();
-        lstamp(5 + 4 * it);
         if (it + 1 >= nit) break;
         store(it + 1, 1);
-        lstamp(6 + 4 * it);
         __syncthreads();
         if (it + 3 < nit) load(it + 3, 1);
-        lstamp(7 + 4 * it);
         compute();
-        lstamp(8 + 4 * it);
         __syncthreads();
-        lstamp(9 + 4 * it);
     }
 }
 template <typename T, int BN> struct SmNT {
@@ -387,17 +368,6 @@ __global__ __launch_bounds__(256) void sm_fc_fwd_kernel(SmFwdArgs a) {
     const int64_t m0 = tile_m * BM;
     const int f0 = tile_f * BN;
 
-#ifdef SM_STAMP
-    // diagnostic build (tools/small_stamps.py): 100 MHz timestamps of workgroup 0 into the unused tail of the output accumulator block
-    auto stamp = [&](int slot) {
-        __builtin_amdgcn_sched_barrier(0);
-        if (MODE == 0 && blockIdx.x == 0 && threadIdx.x == 0) a.out_acc[1100 + slot] = (long long)__builtin_amdgcn_s_memrealtime();
-        __builtin_amdgcn_sched_barrier(0);
-    };
-#else
-    auto stamp = [&](int) {};
-#endif
-    stamp(0);
     const uint32_t key = a.dp_thresh != 0 ? (a.dp_salt ? (a.dp_key ^ *a.dp_salt) : a.dp_key) : 0u;
 
     const T* __restrict__ Ag = (const T*)a.A;
@@ -419,13 +389,7 @@ __global__ __launch_bounds__(256) void sm_fc_fwd_kernel(SmFwdArgs a) {
         MODE == 0 ? (KSPLIT ? (wave & 1) * 32 : wave * 32) : 0, MODE == 0 || wave == 0,
         [&]() {                                           // (under the first two steps' loads)
             sm_finalize_stats<256>(a.bn_in, s_in, t_in, blockIdx.x == 0);
-            stamp(1);
-        }
-#ifdef SM_STAMP
-        , MODE == 0 ? a.out_acc + 1110 : nullptr
-#endif
-        );
-    stamp(2);
+        });
     // accumulator register g: feature (wave*32 +) (g&3) + 8*(g>>2) + 4*h of sample row r
     if constexpr (MODE == 1) {
         if (wave == 0) {
@@ -468,7 +432,6 @@ __global__ __launch_bounds__(256) void sm_fc_fwd_kernel(SmFwdArgs a) {
 #pragma unroll
             for (int e = 0; e < EPC; ++e) { s1[e] += v[e]; s2[e] = fmaf(v[e], v[e], s2[e]); }
         });
-        stamp(3);
     }
 }
 

@@ -28,7 +28,8 @@
 extern "C" {
 #endif
 
-#define CP_VERSION 110            /* 0.1.1: per-call state (cp_config carries options, tile schedule, sync-BN hook, gradient tap) */
+#define CP_VERSION 111            /* 0.1.1: per-call state (cp_config carries options, tile schedule, sync-BN hook, gradient tap);
+                                     111: cp_debug_gemm without its ablation argument */
 #define CP_F32 0
 #define CP_BF16 1
 #define CP_FP8 2                  /* e4m3 activations and fc weights on the block-scaled MFMA (BASELINE config 4); see cp_config.dtype */
@@ -155,10 +156,6 @@ typedef struct cp_step_state {
 
 int cp_version(void);
 const char* cp_last_error(void);
-
-/* 1 in the tools-only build (make -C csrc variants), which also carries the superseded kernels of tools/variants/ with one
- * $CPNATIVE_<NAME> switch each; 0 in the product library. */
-int cp_has_variants(void);
 
 /* bytes of scratch needed by the calls below for up to `max_windows` encoder rows */
 size_t cp_workspace_bytes(int64_t max_windows, int32_t dtype, float dp_emg);
@@ -363,17 +360,16 @@ int cp_profile_summary(int32_t kind, double* total_ms, int64_t* count);
  * is recomputed here the same way from `p` and `x` (both may be NULL for the other layers). */
 int cp_debug_activation(const cp_config* cfg, const cp_params* p, const float* x, void* ws,
                         size_t ws_bytes, int32_t layer, float* out, void* stream);
-/* micro-benchmark access (tools/gemm_bench.py): one fc-layer GEMM launch on caller buffers.
- * kind 0: forward   C[M][F] = relu(A[M][K] W[F][K]^T + bias), column sums -> partials
- * kind 1: data grad C[M][F] = A[M][K] W[F][K]^T, sums against R[M][F] -> partials
- * kind 2: weight grad slabs[S][P][Q] = sum_m X[m][P] Y[m][Q]   (A = X, W = Y, K = P, F = Q)
- * dbg: ablation bits of the bf16 kernels (1 skip MFMA, 2 skip epilogue, 4 skip staging loads). */
 /* test aid: `blocks` workgroups of 256 threads that each hold a CU's LDS (so nothing else fits next to them there) and spin
  * for about `microseconds` -- stands in for another stream's kernel (an RCCL collective) competing for CUs. */
 int cp_debug_hog(int32_t blocks, int32_t microseconds, void* stream);
+/* micro-benchmark access (tools/gemm_bench.py): one fc-layer GEMM launch on caller buffers.
+ * kind 0: forward   C[M][F] = relu(A[M][K] W[F][K]^T + bias), column sums -> partials
+ * kind 1: data grad C[M][F] = A[M][K] W[F][K]^T, sums against R[M][F] -> partials
+ * kind 2: weight grad slabs[S][P][Q] = sum_m X[m][P] Y[m][Q]   (A = X, W = Y, K = P, F = Q) */
 int cp_debug_gemm(int32_t dtype, int32_t kind, int64_t M, int32_t K, int32_t F, const void* A,
                   const void* W, void* C, const float* bias, const void* R, float* partials,
-                  int32_t dbg, void* stream);
+                  void* stream);
 
 
 /* BN statistics of `layer` as computed by the last forward: out[4][C] = mean, invstd, scale, shift */

@@ -32,7 +32,9 @@ def declared_functions():
     return sorted(set(re.findall(r"\b(cp_[a-z0-9_]+)\s*\(", src)))
 
 
-def test_header_symbols_exported_and_bound(lib):
+def test_header_symbols_exported_bound_and_versioned(lib):
+    """every function include/cpnative.h declares is exported and has a ctypes prototype, nothing else is bound, and the library
+    reports the header's CP_VERSION (111: cp_debug_gemm without its ablation argument), which is also the binding's minimum"""
     from contrastiveprosthetics_amd import _lib
     names = declared_functions()
     assert len(names) >= 15
@@ -41,7 +43,9 @@ def test_header_symbols_exported_and_bound(lib):
         assert hasattr(raw, n), f"{n} declared in cpnative.h but not exported"
         assert n in _lib.SYMBOLS, f"{n} has no ctypes prototype in _lib.SYMBOLS"
     assert set(_lib.SYMBOLS) == set(names)
-    assert lib.cp_version() == 110
+    version = int(re.search(r"#define CP_VERSION (\d+)", open(HEADER).read()).group(1))
+    assert lib.cp_version() == version == 111
+    assert f"lib.cp_version() < {version}:" in open(os.path.join(ROOT, "contrastiveprosthetics_amd", "_lib.py")).read()
 
 
 def test_struct_layouts_match_header():
@@ -185,15 +189,14 @@ def test_register_stationary_gemm_kernel_has_no_spills():
         assert re.search(r"spill\s+0\s+scratch\s+0\b", l), l
 
 
-def test_no_buffer_store_is_followed_by_a_write_of_its_data_registers():
+def test_library_assembly_has_no_buffer_store_data_hazard():
     """gfx950 store-data hazard (csrc/gemm_ws.cuh, store_b128_settled; DESIGN.md section 4, "The lanes 12-15 fault"): hipcc places a
     VALU write of a buffer_store_dwordx4's data registers directly behind the store when the store's soffset is an SGPR, and the
     store then sends the new values for some lanes.  tools/store_hazard_scan.py reads the device assembly of the whole library: no
     96/128-bit buffer store may have such a write within the next two instructions."""
-    for extra in ([], ["--variants"]):       # the product library, and the tools-only build whose timings DESIGN.md quotes
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "store_hazard_scan.py")] + extra, capture_output=True, text=True)
-        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-        assert out.stdout.strip().startswith("0 unprotected"), out.stdout[-500:]
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "store_hazard_scan.py")], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    assert out.stdout.strip().startswith("0 unprotected"), out.stdout[-500:]
 
 
 def test_pinned_mfmas_keep_their_wait_states():
@@ -207,24 +210,32 @@ def test_pinned_mfmas_keep_their_wait_states():
     assert first.endswith("0 finding(s)") and int(first.split()[0]) >= 6, out.stdout[-500:]
 
 
-def test_no_getenv_on_a_launch_path():
-    """the product library never reads the environment (a call's settings travel in its cp_config); the tools-only build reads it
-    once, when it is loaded, to seed the variant switches (csrc/api.hip, seed_variants_from_env, under #ifdef CP_VARIANTS)"""
+def test_library_never_reads_the_environment():
+    """no getenv anywhere in the library (sources and the .so's imports): a call's settings travel in its cp_config"""
     import glob
     hits = []
     for f in glob.glob(os.path.join(ROOT, "contrastiveprosthetics_amd", "csrc", "*")):
         for i, line in enumerate(open(f, errors="replace")):
             if "getenv(" in line and not line.lstrip().startswith("//"):
                 hits.append((os.path.basename(f), i + 1, line.strip()))
-    assert len(hits) == 1 and hits[0][0] == "api.hip" and "getenv(env)" in hits[0][2], hits
+    assert hits == [], hits
     src = open(os.path.join(ROOT, "contrastiveprosthetics_amd", "csrc", "api.hip")).read()
-    block = src[src.index("static int seed_variants_from_env()"):]
-    assert src[:src.index("static int seed_variants_from_env()")].rstrip().split("#")[-1].startswith("ifdef CP_VARIANTS") or \
-        "#ifdef CP_VARIANTS" in src[src.index("extern \"C\" int cp_has_variants"):src.index("static int seed_variants_from_env()")]
     # and nothing process-wide is left for the training path to consult
     assert not re.search(r"^static [^(]*\bg_(opt|sync_fn|sync_user|sync_world|grad_tap|tile_schedule)\b", src, flags=re.M)
     out = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True, check=True).stdout
     assert "getenv" not in subprocess.run(["nm", "-D", "--undefined-only", LIB], capture_output=True, text=True, check=True).stdout
+
+
+def test_library_sources_have_no_preprocessor_conditionals():
+    """every line under csrc/ is compiled into libcpnative.so: no build-time switches, no code only another build sees"""
+    import glob
+    hits = []
+    for f in glob.glob(os.path.join(ROOT, "contrastiveprosthetics_amd", "csrc", "*")):
+        if f.endswith((".hip", ".cuh")):
+            for i, line in enumerate(open(f, errors="replace")):
+                if re.match(r"\s*#\s*(if|ifdef|ifndef|elif|else|endif)\b", line):
+                    hits.append((os.path.basename(f), i + 1, line.strip()))
+    assert hits == [], hits
 
 
 def test_dropout_hash_keeps_every_index_bit_live():

@@ -29,9 +29,9 @@ side = torch.cuda.Stream()
 
 def gemm(kind):
     if kind == "wgrad":
-        _lib.check(lib.cp_debug_gemm(1, 2, M, 512, 512, A.data_ptr(), R.data_ptr(), slabs.data_ptr(), 0, 0, partials.data_ptr(), 0, main.cuda_stream), "wgrad")
+        _lib.check(lib.cp_debug_gemm(1, 2, M, 512, 512, A.data_ptr(), R.data_ptr(), slabs.data_ptr(), 0, 0, partials.data_ptr(), main.cuda_stream), "wgrad")
     elif kind == "fwd":
-        _lib.check(lib.cp_debug_gemm(1, 0, M, K, F, A.data_ptr(), W.data_ptr(), C.data_ptr(), bias.data_ptr(), 0, partials.data_ptr(), 128,
+        _lib.check(lib.cp_debug_gemm(1, 0, M, K, F, A.data_ptr(), W.data_ptr(), C.data_ptr(), bias.data_ptr(), 0, partials.data_ptr(),
                                      main.cuda_stream), "fwd")
 
 

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def assembly_file(tmp):
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     from _device_asm import assembly_path          # compiled once into build/, reused while no source is newer
-    return assembly_path(False)
+    return assembly_path()
 
 
 def regs(tok):
