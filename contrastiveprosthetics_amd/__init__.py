@@ -7,3 +7,11 @@ C ABI of ``include/cpnative.h``.  Importing the package never touches the GPU; t
 kernel call loads ``libcpnative.so`` and fails loudly if it is absent.
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # OnlineDecoder pulls in torch and the engine; importing the package stays light until it is asked for
+    if name == "OnlineDecoder":
+        from .online import OnlineDecoder
+        return OnlineDecoder
+    raise AttributeError(name)

@@ -66,6 +66,13 @@ class cp_glove_params(C.Structure):
                 ("running_mean", C.c_void_p), ("running_var", C.c_void_p)]
 
 
+class cp_online_config(C.Structure):
+    _fields_ = [("dtype", C.c_int32), ("max_windows", C.c_int32), ("vote", C.c_int32), ("phase", C.c_int32),
+                ("n_coef", C.c_int32), ("reserved0", C.c_int32), ("b", C.c_double * 17), ("a", C.c_double * 17)]
+
+
+CP_ONLINE_MAX_CLASSES, CP_ONLINE_MAX_VOTE, CP_ONLINE_MAX_WINDOWS, CP_ONLINE_STRIDE = 64, 256, 256, 20
+
 SYMBOLS = {
     "cp_version": (C.c_int, []),
     "cp_last_error": (C.c_char_p, []),
@@ -110,6 +117,11 @@ SYMBOLS = {
     "cp_debug_activation": (C.c_int, [_P(cp_config), _P(cp_params), _fp, _fp, C.c_size_t, C.c_int32, _fp, _fp]),
     "cp_debug_bn_stats": (C.c_int, [_P(cp_config), _fp, C.c_size_t, C.c_int32, _fp, _fp]),
     "cp_debug_gemm": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "cp_online_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "cp_online_prepare": (C.c_int, [_P(cp_online_config), _P(cp_params), _P(cp_bn_buffers), C.c_float, _fp, C.c_size_t, _fp]),
+    "cp_online_set_classes": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, _fp, C.c_int32, _fp]),
+    "cp_online_push": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "cp_online_reset": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp]),
 }
 
 KERNEL_KINDS = ["gather", "prep", "conv1_fwd", "bn_finalize", "conv2_fwd", "fold", "fc_fwd", "dropout", "proj_fwd",

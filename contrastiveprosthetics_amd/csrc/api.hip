@@ -21,6 +21,7 @@
 #include "glove.cuh"
 #include "fp8.cuh"
 #include "small.cuh"
+#include "online.cuh"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* what) {
@@ -2411,4 +2412,160 @@ extern "C" int cp_debug_bn_stats(const cp_config* cfg, void* ws, size_t ws_bytes
     CK(hipMemcpyAsync(out, (unsigned char*)ws + w.stats[layer], (size_t)4 * kLayerC[layer] * 4, hipMemcpyDeviceToDevice,
                       (hipStream_t)stream));
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// online grasp decoding (csrc/online.cuh): per-stream state, folded weights and activations in the caller's workspace
+// ---------------------------------------------------------------------------------------
+static_assert(OL_MAXM == CP_ONLINE_MAX_WINDOWS && OL_MAXVOTE == CP_ONLINE_MAX_VOTE && OL_MAXK == CP_ONLINE_MAX_CLASSES, "online limits");
+struct OlWS {
+    size_t state, c1w, c1b, c2w, c2b, fcw[CP_N_FC], fcb[CP_N_FC], pw, pb, X, H0, H1, total;
+};
+static OlWS ol_carve(int64_t max_windows, int dtype) {
+    const size_t es = dtype == CP_BF16 ? 2 : 4;
+    const size_t rows = (size_t)((max_windows + 15) / 16 * 16);
+    OlWS w{};
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t r = o; o = align256(o + bytes); return r; };
+    w.state = take(sizeof(OlState));
+    w.c1w = take(64 * 3 * 4);
+    w.c1b = take(64 * 4);
+    w.c2w = take(64 * OL_CONV_K * es);
+    w.c2b = take(OL_C * 64 * 4);
+    for (int i = 0; i < CP_N_FC; ++i) {
+        w.fcw[i] = take((size_t)512 * fcK(i) * es);
+        w.fcb[i] = take(512 * 4);
+    }
+    w.pw = take(CP_D_E * 512 * es);
+    w.pb = take(CP_D_E * 4);
+    w.X = take(rows * OL_C * 4);
+    w.H0 = take(rows * 768 * es);
+    w.H1 = take(rows * 512 * es);
+    w.total = o;
+    return w;
+}
+
+static int ol_check(const cp_online_config* c, void* ws, size_t ws_bytes, OlWS* out) {
+    if (!c || !ws) return fail(CP_ERR_ARG, "cp_online: config and workspace are required");
+    if (c->dtype != CP_F32 && c->dtype != CP_BF16) return fail(CP_ERR_ARG, "cp_online: dtype must be CP_F32 or CP_BF16 (no 8-bit path)");
+    if (c->max_windows < 1 || c->max_windows > CP_ONLINE_MAX_WINDOWS) return fail(CP_ERR_ARG, "cp_online: max_windows outside 1..256");
+    if (c->vote < 1 || c->vote > CP_ONLINE_MAX_VOTE) return fail(CP_ERR_ARG, "cp_online: vote outside 1..256");
+    if (c->phase < 0 || c->phase >= CP_ONLINE_STRIDE) return fail(CP_ERR_ARG, "cp_online: phase outside 0..19");
+    if (c->n_coef < 2 || c->n_coef > OL_MAXCOEF || c->a[0] == 0.0) return fail(CP_ERR_ARG, "cp_online: IIR coefficients");
+    if ((uintptr_t)ws % 256) return fail(CP_ERR_ARG, "cp_online: workspace not 256-byte aligned");
+    *out = ol_carve(c->max_windows, c->dtype);
+    if (ws_bytes < out->total) return fail(CP_ERR_WORKSPACE, "cp_online: workspace too small");
+    return 0;
+}
+
+extern "C" size_t cp_online_workspace_bytes(int32_t max_windows_per_push, int32_t dtype) {
+    if (max_windows_per_push < 1) max_windows_per_push = 1;
+    return ol_carve(max_windows_per_push, dtype).total;
+}
+
+template <typename T>
+static int online_prepare_t(const cp_params* p, const cp_bn_buffers* bn, float eps, unsigned char* base, const OlWS& w, hipStream_t st) {
+    OlFoldArgs f{};
+    f.eps = eps;
+    auto set_bn = [&](int l) { f.g = p->bn_g[l]; f.beta = p->bn_b[l]; f.mean = bn->running_mean[l]; f.var = bn->running_var[l]; };
+    set_bn(0);                                            // BN1 -> conv2 (and conv1 copied as it is)
+    f.W = p->conv2_w; f.b = p->conv2_b; f.Wd = base + w.c2w; f.bd = (float*)(base + w.c2b); f.K = OL_CONV_K; f.mode = 2;
+    f.c1w_src = p->conv1_w; f.c1b_src = p->conv1_b; f.c1w = (float*)(base + w.c1w); f.c1b = (float*)(base + w.c1b);
+    hipLaunchKernelGGL((ol_fold_kernel<T>), dim3(64), dim3(256), 0, st, f);
+    CKL("ol_fold_kernel");
+    for (int i = 0; i < CP_N_FC; ++i) {                   // BN(i+1) -> fc(i+1); fc1's columns to the position-major layout
+        set_bn(i + 1);
+        f.W = p->fc_w[i]; f.b = p->fc_b[i]; f.Wd = base + w.fcw[i]; f.bd = (float*)(base + w.fcb[i]); f.K = fcK(i); f.mode = i == 0 ? 1 : 0;
+        hipLaunchKernelGGL((ol_fold_kernel<T>), dim3(512), dim3(256), 0, st, f);
+        CKL("ol_fold_kernel");
+    }
+    set_bn(CP_N_BN - 1);                                  // BN9 -> projection, which gains a bias
+    f.W = p->last_w; f.b = nullptr; f.Wd = base + w.pw; f.bd = (float*)(base + w.pb); f.K = 512; f.mode = 0;
+    hipLaunchKernelGGL((ol_fold_kernel<T>), dim3(CP_D_E), dim3(256), 0, st, f);
+    CKL("ol_fold_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_prepare(const cp_online_config* cfg, const cp_params* p, const cp_bn_buffers* bn, float bn_eps, void* ws,
+                                 size_t ws_bytes, void* stream) {
+    OlWS w;
+    if (int e = ol_check(cfg, ws, ws_bytes, &w)) return e;
+    if (!p || !p->conv1_w || !p->conv1_b || !p->conv2_w || !p->conv2_b || !p->last_w) return fail(CP_ERR_ARG, "cp_online_prepare: parameters");
+    for (int i = 0; i < CP_N_FC; ++i)
+        if (!p->fc_w[i] || !p->fc_b[i]) return fail(CP_ERR_ARG, "cp_online_prepare: parameters");
+    if (!bn) return fail(CP_ERR_ARG, "cp_online_prepare: stock BatchNorm with running statistics required (AdaBN has none)");
+    for (int l = 0; l < CP_N_BN; ++l)
+        if (!p->bn_g[l] || !p->bn_b[l] || !bn->running_mean[l] || !bn->running_var[l])
+            return fail(CP_ERR_ARG, "cp_online_prepare: stock BatchNorm with running statistics required (AdaBN has none)");
+    unsigned char* base = (unsigned char*)ws;
+    if (cfg->dtype == CP_BF16) return online_prepare_t<bf16_t>(p, bn, bn_eps, base, w, (hipStream_t)stream);
+    return online_prepare_t<float>(p, bn, bn_eps, base, w, (hipStream_t)stream);
+}
+
+extern "C" int cp_online_set_classes(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* table, const int32_t* ids,
+                                     int32_t n_classes, void* stream) {
+    OlWS w;
+    if (int e = ol_check(cfg, ws, ws_bytes, &w)) return e;
+    if (!table || !ids || n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return fail(CP_ERR_ARG, "cp_online_set_classes: 1..64 classes");
+    hipLaunchKernelGGL(ol_set_classes_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (OlState*)((unsigned char*)ws + w.state), table,
+                       ids, (int)n_classes);
+    CKL("ol_set_classes_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_reset(const cp_online_config* cfg, void* ws, size_t ws_bytes, void* stream) {
+    OlWS w;
+    if (int e = ol_check(cfg, ws, ws_bytes, &w)) return e;
+    CK(hipMemsetAsync((unsigned char*)ws + w.state, 0, offsetof(OlState, K), (hipStream_t)stream));
+    return 0;
+}
+
+template <typename T>
+static int online_push_t(const cp_online_config* c, unsigned char* base, const OlWS& w, const float* raw, int64_t n,
+                         const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, hipStream_t st) {
+    OlState* state = (OlState*)(base + w.state);
+    OlFrontArgs fa{};
+    fa.raw = raw; fa.n = n; fa.st = state; fa.X = (float*)(base + w.X); fa.windows = windows; fa.mean_std = mean_std;
+    fa.n_coef = c->n_coef; fa.phase = c->phase; fa.gain = 1024.f;            // code/load.py:105, 2**10
+    for (int i = 0; i < c->n_coef; ++i) { fa.b[i] = c->b[i] / c->a[0]; fa.a[i] = c->a[i] / c->a[0]; }
+    if (c->n_coef == 9) hipLaunchKernelGGL((ol_frontend_kernel<9>), dim3(1), dim3(256), 0, st, fa);
+    else hipLaunchKernelGGL((ol_frontend_kernel<0>), dim3(1), dim3(256), 0, st, fa);
+    CKL("ol_frontend_kernel");
+    OlLayerArgs la{};
+    la.st = state;
+    la.x = (const float*)(base + w.X); la.c1w = (const float*)(base + w.c1w); la.c1b = (const float*)(base + w.c1b);
+    la.w = base + w.c2w; la.bias = (const float*)(base + w.c2b); la.out = base + w.H0; la.K = OL_CONV_K; la.F = 64; la.ldo = 768;
+    la.out_pos = 64;
+    hipLaunchKernelGGL((ol_layer_kernel<T, true>), dim3(4, OL_C), dim3(OL_THREADS), 0, st, la);
+    CKL("ol_layer_kernel<conv>");
+    for (int i = 0; i < CP_N_FC; ++i) {                   // H0 -> H1 -> H0 ...: fc7 leaves its output in H1
+        la.act = base + (i % 2 == 0 ? w.H0 : w.H1);
+        la.out = base + (i % 2 == 0 ? w.H1 : w.H0);
+        la.w = base + w.fcw[i]; la.bias = (const float*)(base + w.fcb[i]); la.K = fcK(i); la.F = 512; la.ldo = 512; la.out_pos = 0;
+        hipLaunchKernelGGL((ol_layer_kernel<T, false>), dim3(512 / 16), dim3(OL_THREADS), 0, st, la);
+        CKL("ol_layer_kernel<fc>");
+    }
+    OlTailArgs ta{};
+    ta.proj = la;
+    ta.proj.act = base + w.H1; ta.proj.out = nullptr; ta.proj.w = base + w.pw; ta.proj.bias = (const float*)(base + w.pb); ta.proj.K = 512;
+    ta.proj.F = CP_D_E;
+    ta.st = state; ta.vote = c->vote; ta.pred = pred; ta.voted = voted; ta.logits = logits;
+    hipLaunchKernelGGL((ol_tail_kernel<T>), dim3(1), dim3(OL_THREADS), 0, st, ta);
+    CKL("ol_tail_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_push(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* raw, int64_t n_samples,
+                              const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, void* stream) {
+    OlWS w;
+    if (int e = ol_check(cfg, ws, ws_bytes, &w)) return e;
+    if (n_samples < 0 || n_samples > (int64_t)CP_ONLINE_STRIDE * cfg->max_windows)
+        return fail(CP_ERR_ARG, "cp_online_push: a push takes at most 20 * max_windows samples");
+    if (n_samples == 0) return 0;
+    if (!raw || !mean_std || !pred || !voted) return fail(CP_ERR_ARG, "cp_online_push: raw, mean_std, pred and voted are required");
+    if ((uintptr_t)raw % 4 || (uintptr_t)mean_std % 4) return fail(CP_ERR_ARG, "cp_online_push: misaligned input");
+    unsigned char* base = (unsigned char*)ws;
+    if (cfg->dtype == CP_BF16)
+        return online_push_t<bf16_t>(cfg, base, w, raw, n_samples, mean_std, pred, voted, logits, windows, (hipStream_t)stream);
+    return online_push_t<float>(cfg, base, w, raw, n_samples, mean_std, pred, voted, logits, windows, (hipStream_t)stream);
 }

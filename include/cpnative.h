@@ -376,6 +376,52 @@ int cp_debug_gemm(int32_t dtype, int32_t kind, int64_t M, int32_t K, int32_t F, 
 int cp_debug_bn_stats(const cp_config* cfg, void* ws, size_t ws_bytes, int32_t layer, float* out,
                       void* stream);
 
+/* ---- online grasp decoding (README.md:11-19 of the reference: a prosthetic hand reads a live sEMG stream) ----------------
+ * Consecutive chunks of raw 2 kHz, 12-channel sEMG -> for every 10 ms window a chunk completes, the predicted class and the
+ * class voted over the last `vote` predictions.  Per sample: the transform of cp_preprocess_emg (gain 2**10, the IIR b/a,
+ * float64 RMS sum over 11 samples with the 'nearest' start) and cp_emg_normalize, carried across calls; window k is the RMS-series
+ * position phase + 20 k, final once raw sample phase + 20 k + 10 has arrived, and bit-identical to cp_preprocess_emg +
+ * cp_emg_normalize of the whole recording at that position.  Then the sEMG encoder in eval mode with running-statistics
+ * BatchNorm folded into the layer behind each BN (f32 or bf16), z / |z| against a table of K <= 64 L2-normalised class rows,
+ * argmax (first maximum) and the mode of the vote ring (ties: smallest class id).
+ * The library keeps no state: the filter, RMS history, sample count, vote ring, class table and folded weights live in the
+ * workspace; the caller keeps the config and passes it to every call.  A push of n samples emits
+ *     M = c(n_seen + n) - c(n_seen),  c(N) = max(0, floor((N - phase + 9) / 20))
+ * windows (n_seen = samples pushed since the last reset), so the caller sizes the outputs without reading the device. */
+#define CP_ONLINE_MAX_CLASSES 64
+#define CP_ONLINE_MAX_VOTE 256
+#define CP_ONLINE_MAX_WINDOWS 256     /* windows per push (the tail launch keeps their predictions in LDS) */
+#define CP_ONLINE_STRIDE 20      /* raw samples per window (2 kHz -> 100 Hz) */
+typedef struct cp_online_config {
+    int32_t dtype;           /* CP_F32 | CP_BF16 */
+    int32_t max_windows;     /* windows one push may emit: a push takes at most 20 * max_windows samples */
+    int32_t vote;            /* length of the vote ring, 1..256 (25 = 250 ms, code/constants.py:74-78) */
+    int32_t phase;           /* 0..19 */
+    int32_t n_coef;          /* IIR coefficients, 2..17 (the reference's band-pass: 9) */
+    int32_t reserved0;
+    double b[17], a[17];     /* host values, as for cp_preprocess_emg */
+} cp_online_config;
+
+/* bytes of the workspace for up to max_windows_per_push windows per push (cp_online_config.max_windows).  A fresh workspace
+ * must be zeroed (or cp_online_reset) before the first push. */
+size_t cp_online_workspace_bytes(int32_t max_windows_per_push, int32_t dtype);
+/* folds the model's parameters (f32, as for cp_encoder_forward) into the workspace in the compute dtype: BN1 -> conv2 (the
+ * shift is position-dependent at the two edge positions: zero padding), BN2 -> fc1, BN_l -> fc_{l+1}, BN9 -> projection.
+ * bn must hold all running statistics: AdaBN (bn == NULL) is refused with CP_ERR_ARG.  Pushes use this copy until the next
+ * call. */
+int cp_online_prepare(const cp_online_config* cfg, const cp_params* p, const cp_bn_buffers* bn, float bn_eps, void* ws,
+                      size_t ws_bytes, void* stream);
+/* table (n_classes,16) f32 (normalised here), ids (n_classes) int32 ascending: the class id each row reports.  Empties the vote
+ * ring; the filter state stays. */
+int cp_online_set_classes(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* table, const int32_t* ids,
+                          int32_t n_classes, void* stream);
+/* raw (n_samples,12) f32 -> pred, voted (M) int32 class ids; logits (M,n_classes) f32 and windows (M,12) f32 (the normalised
+ * windows) may be NULL.  mean_std (2,12) f32: the normalisation of the training data (cp_emg_stats). */
+int cp_online_push(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* raw, int64_t n_samples,
+                   const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, void* stream);
+/* zeroes the stream part of the state (filter, RMS history, sample count, vote ring); class table and weights stay */
+int cp_online_reset(const cp_online_config* cfg, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,113 @@
+"""Latency of the online decoder against the composition of existing calls that computes the same result.
+
+For pushes of 20 and 500 raw samples (1 and 25 windows) in f32 and bf16:
+  decoder      OnlineDecoder.push (contrastiveprosthetics_amd/online.py)
+  composition  preprocess_segments over the last 2,010 samples (the offline transform restarts its filter from zero on every
+               call, so it needs a segment of history) + normalize_ + Engine.encoder_forward(training=False) + z/|z| . E/|E| +
+               argmax over the subset
+Each push is timed from the host with a synchronisation behind it (the latency a control loop sees); kernels per push are
+counted with torch.profiler over a few pushes.  One JSON line per case, and a table with --out.
+
+    python tools/online_bench.py --iters 200 --out profiles/online_latency.txt
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from contrastiveprosthetics_amd import OnlineDecoder                      # noqa: E402
+from contrastiveprosthetics_amd.engine import Engine                       # noqa: E402
+from contrastiveprosthetics_amd.preprocess import normalize_, preprocess_segments   # noqa: E402
+
+
+def count_kernels(fn, pushes=5):
+    from torch.profiler import ProfilerActivity, profile
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        for _ in range(pushes):
+            fn()
+        torch.cuda.synchronize()
+    n = sum(1 for ev in prof.events() if ev.device_type == torch.autograd.DeviceType.CUDA and "Memcpy" not in ev.name
+            and "Memset" not in ev.name)
+    return n / pushes
+
+
+def time_pushes(fn, iters, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(iters):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    ts = np.array(ts) * 1e6
+    return float(np.median(ts)), float(np.percentile(ts, 90))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    torch.manual_seed(0)
+    e = Engine(adabn=False, dtype="f32", device="cuda:0")
+    e.init_parameters(1)
+    stream = (torch.randn(200000, 12) * 2e-3).cuda()
+    mean, std = torch.full((12,), 0.4).cuda(), torch.full((12,), 0.1).cuda()
+    classes = list(range(41))
+    table = (e.values.views["glove_net.easy.0.weight"].t() + e.values.views["glove_net.easy.0.bias"]).contiguous()
+    tn = table / table.norm(dim=-1, keepdim=True)
+    rows = []
+    for dtype in ("f32", "bf16"):
+        e.dtype = 0 if dtype == "f32" else 1
+        e._ws = None                                           # the engine's workspace is carved per dtype
+        for n in (20, 500):
+            m = n // 20
+            dec = OnlineDecoder(e, mean, std, classes=classes, dtype=dtype)
+            pos = [0]
+
+            def push():
+                s = pos[0] % (stream.shape[0] - n)
+                pos[0] += n
+                return dec.push(stream[s:s + n])
+
+            keep = 2000 - 20 * np.arange(m)[::-1]                    # the last m windows of a 2,010-sample segment
+
+            def compose():
+                s = pos[0] % (stream.shape[0] - 2010)
+                pos[0] += n
+                w = normalize_(preprocess_segments(stream[s:s + 2010][None].contiguous(), keep=keep - 10), mean, std)[0]
+                x = torch.zeros(41, 12, device=w.device)                 # the encoder takes whole groups of 41 rows
+                x[:m] = w
+                z = e.encoder_forward(x, training=False)[:m]
+                return ((z / z.norm(dim=-1, keepdim=True)) @ tn.t()).argmax(1)
+
+            for name, fn in (("decoder", push), ("composition", compose)):
+                med, p90 = time_pushes(fn, a.iters, a.warmup)
+                k = count_kernels(fn)
+                r = dict(kind=name, dtype=dtype, samples=n, windows=m, median_us=round(med, 1), p90_us=round(p90, 1),
+                         kernels_per_push=k)
+                print(json.dumps(r), flush=True)
+                rows.append(r)
+    if a.out:
+        dev = torch.cuda.get_device_name(0)
+        with open(a.out, "w") as f:
+            f.write(f"# tools/online_bench.py --iters {a.iters} --warmup {a.warmup} on {dev}\n")
+            f.write("# per-push wall time, host-synchronised (median, p90), and kernels per push (torch.profiler)\n")
+            f.write(f"{'kind':<12} {'dtype':<5} {'samples':>7} {'windows':>7} {'median_us':>10} {'p90_us':>9} {'kernels':>8}\n")
+            for r in rows:
+                f.write(f"{r['kind']:<12} {r['dtype']:<5} {r['samples']:>7} {r['windows']:>7} {r['median_us']:>10.1f} "
+                        f"{r['p90_us']:>9.1f} {r['kernels_per_push']:>8.1f}\n")
+
+
+if __name__ == "__main__":
+    main()
