@@ -40,8 +40,14 @@ OPTIONS = {"unfused_bn_bwd": 1, "unpaired_wgrad": 2, "fp8_bridge": 4, "no_small"
 CP_TILES_STATIC, CP_TILES_DYNAMIC = 0, 1
 
 
+class cp_forward_record(C.Structure):
+    """What the last cp_encoder_forward left in a workspace: host memory, zeroed, one per workspace buffer (include/cpnative.h)."""
+    _fields_ = [("n_windows", C.c_int64), ("path", C.c_int32), ("backwards", C.c_int32), ("transposed", C.c_int32),
+                ("pad", C.c_int32), ("join_event", C.c_void_p)]
+
+
 class cp_config(C.Structure):
-    """Everything a call depends on besides its tensors: the library keeps no per-process state for the training path."""
+    """Everything a call depends on besides its tensors; what a forward pass leaves for the backward is in `record`."""
     _fields_ = [
         ("n_windows", C.c_int64), ("dtype", C.c_int32), ("adabn", C.c_int32),
         ("training", C.c_int32), ("step_state_lo", C.c_uint32),
@@ -51,6 +57,7 @@ class cp_config(C.Structure):
         ("stats_allreduce", C.c_void_p), ("stats_user", C.c_void_p), ("stats_world", C.c_int32), ("reserved0", C.c_int32),
         ("grad_tap", C.c_void_p), ("grad_tap_bytes", C.c_size_t),
         ("aux_stream", C.c_void_p), ("aux_fork", C.c_void_p), ("aux_join", C.c_void_p),
+        ("record", C.POINTER(cp_forward_record)),
     ]
 
 
@@ -154,7 +161,7 @@ def load():
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
-    if lib.cp_version() < 111:
+    if lib.cp_version() < 112:
         raise CpNativeError("libcpnative.so is older than this binding")
     _lib = lib
     return lib

@@ -3,7 +3,6 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cmath>
-#include <mutex>
 
 #include "../../include/cpnative.h"
 #include "common.cuh"
@@ -906,46 +905,9 @@ static int encoder_backward_small_t(const cp_config* c, const cp_params* p, cons
     return conv_backward_tail<T>(c, p, x, base, w, g, st, fc_grads_ready, gb[cur], gb[cur ^ 1], false, tiles_m, nullptr, 0, nullptr, true);
 }
 
-// Which kernel path the last forward pass over a workspace took, keyed by the workspace address: the backward pass must take the same
-// one (the small-batch form and the large-batch form leave different things in the workspace) and learns here whether it is the first
-// backward over this forward (a repeat finds the small-batch form's fixed-point totals already summed and zeroes them first).  A
-// consistency check only -- nothing an engine computes depends on another engine's entries.
+// The kernel path of a forward pass (cp_forward_record.path): the backward pass must take the same one -- the small-batch form and the
+// large-batch form leave different things in the workspace.
 enum { PATH_LARGE = 0, PATH_SMALL = 1, PATH_FP8 = 2 };
-struct FwdNote { const void* ws; int64_t n; int path; int backwards; uint64_t tick; int tposed; };
-static FwdNote g_notes[64];
-static uint64_t g_note_tick = 0;
-static std::mutex g_notes_mu;
-static void note_forward(const void* ws, int64_t n, int path, int tposed = 0) {
-    std::lock_guard<std::mutex> lk(g_notes_mu);
-    FwdNote* slot = &g_notes[0];
-    for (FwdNote& f : g_notes) {
-        if (f.ws == ws) { slot = &f; break; }
-        if (f.tick < slot->tick) slot = &f;
-    }
-    *slot = FwdNote{ws, n, path, 0, ++g_note_tick, tposed};
-}
-// returns the number of backward passes already run over this forward, or -1 when the configurations disagree (-2: no forward on record)
-static int note_backward(const void* ws, int64_t n, int path) {
-    std::lock_guard<std::mutex> lk(g_notes_mu);
-    for (FwdNote& f : g_notes)
-        if (f.ws == ws && f.tick) {
-            if (f.n != n || f.path != path) return -1;
-            return f.backwards++;
-        }
-    return -2;
-}
-static bool forward_made_transposes(const void* ws) {
-    std::lock_guard<std::mutex> lk(g_notes_mu);
-    for (const FwdNote& f : g_notes)
-        if (f.ws == ws && f.tick) return f.tposed != 0;
-    return false;
-}
-static int last_forward_path(const void* ws) {
-    std::lock_guard<std::mutex> lk(g_notes_mu);
-    for (const FwdNote& f : g_notes)
-        if (f.ws == ws && f.tick) return f.path;
-    return -1;
-}
 static int forward_path(const cp_config* cfg) { return cfg->dtype == CP_FP8 ? PATH_FP8 : use_small(cfg) ? PATH_SMALL : PATH_LARGE; }
 
 extern "C" int cp_encoder_forward(const cp_config* cfg, const cp_params* p, const cp_bn_buffers* bn, const float* x,
@@ -960,7 +922,8 @@ extern "C" int cp_encoder_forward(const cp_config* cfg, const cp_params* p, cons
     const bool drop = cfg->training && cfg->dp_emg > 0.f;
     const Aux aux = make_aux(cfg, (hipStream_t)stream, drop && path != PATH_SMALL && cfg->dtype != CP_F32 && !dyn_tiles(cfg) &&
                                                            !opt(cfg, CP_OPT_UNPAIRED_WGRAD) && !opt(cfg, CP_OPT_UNFUSED_BN_BWD) && !opt(cfg, CP_OPT_FP8_BRIDGE));
-    note_forward(ws, cfg->n_windows, path, aux.on ? 1 : 0);
+    if (cp_forward_record* r = cfg->record)
+        *r = cp_forward_record{cfg->n_windows, path, 0, aux.on ? 1 : 0, 0, aux.on ? (void*)aux.join_ev : nullptr};
     if (cfg->dtype == CP_FP8) {
         if (int e = encoder_forward_fp8(cfg, p, bn, x, (unsigned char*)ws, w, z_out, (hipStream_t)stream)) return e;
         if (aux.on) {
@@ -1692,8 +1655,9 @@ static int encoder_backward_t(const cp_config* c, const cp_params* p, const floa
     const Aux aux = make_aux(c, st, fuse_ok && drop && !dyn_tiles(c) && !opt(c, CP_OPT_UNPAIRED_WGRAD) && c->dtype != CP_FP8);
     float* slabs_b = (float*)(base + w.slabs_b);
     if (aux.on) { cur = (T*)(base + w.gkeep[0]); nxt = (T*)(base + w.gkeep[1]); }
-    if (aux.on && tposed) CK(hipStreamWaitEvent(st, aux.join_ev, 0));      // the transposes made beside the forward pass (cp_encoder_forward)
-    else if (int e = launch_weight_transposes<T>(p, base, w, st)) return e;
+    if (!(aux.on && tposed)) {              // (else made beside the forward pass and waited for by cp_encoder_backward_ev)
+        if (int e = launch_weight_transposes<T>(p, base, w, st)) return e;
+    }
     if (int e = aux.fork()) return e;           // dz (cp_head) is final
     // ---- projection ------------------------------------------------------------------
     {
@@ -1968,8 +1932,9 @@ static int encoder_backward_fp8(const cp_config* c, const cp_params* p, const fl
     const Aux aux = make_aux(c, st, drop);
     float* slabs_b = (float*)(base + w.slabs_b);
     if (aux.on) { cur = base + w.gkeep[0]; nxt = base + w.gkeep[1]; }
-    if (aux.on && tposed) CK(hipStreamWaitEvent(st, aux.join_ev, 0));
-    else if (int e = launch_weight_transposes_fp8(p, base, w, st)) return e;
+    if (!(aux.on && tposed)) {
+        if (int e = launch_weight_transposes_fp8(p, base, w, st)) return e;
+    }
     if (int e = aux.fork()) return e;
     // ---- projection ------------------------------------------------------------------
     {
@@ -2149,11 +2114,17 @@ extern "C" int cp_encoder_backward_ev(const cp_config* cfg, const cp_params* p, 
     if (int e = check_cfg(cfg, ws, ws_bytes, &w)) return e;
     if (!p || !x || !grads) return fail(CP_ERR_ARG, "cp_encoder_backward args");
     if (((uintptr_t)x & 15) != 0) return fail(CP_ERR_ARG, "x must be 16-byte aligned");
+    cp_forward_record* r = cfg->record;
+    if (!r) return fail(CP_ERR_ARG, "cp_encoder_backward: cfg->record is NULL (pass the record cp_encoder_forward filled)");
+    if (!r->n_windows) return fail(CP_ERR_ARG, "cp_encoder_backward: no cp_encoder_forward has filled cfg->record");
     // the path is the FORWARD's: use_small() ignores `training`, which a backward call may not carry, only through (training || adabn)
-    const int repeats = note_backward(ws, cfg->n_windows, forward_path(cfg));
-    if (repeats == -1)
-        return fail(CP_ERR_ARG, "cp_encoder_backward: the configuration (n_windows, dtype, options, hooks) differs from the forward pass that filled this workspace");
-    if (repeats == -2) return fail(CP_ERR_ARG, "cp_encoder_backward: no cp_encoder_forward has run on this workspace");
+    if (r->n_windows != cfg->n_windows || r->path != forward_path(cfg))
+        return fail(CP_ERR_ARG, "cp_encoder_backward: n_windows or the kernel path differs from the forward pass that filled cfg->record");
+    const int repeats = r->backwards++;
+    const bool tposed = r->transposed != 0;
+    // the transposed weights made beside the forward pass (cp_encoder_forward) precede every launch of this call, whether or not this
+    // call uses the second stream itself
+    if (tposed) CK(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)r->join_event, 0));
     if (cfg->dtype != CP_FP8 && use_small(cfg)) {
         if (repeats > 0) {
             // a second backward over the same forward: the small-batch form's BatchNorm-backward totals (fixed-point atomics, zeroed by the
@@ -2164,7 +2135,6 @@ extern "C" int cp_encoder_backward_ev(const cp_config* cfg, const cp_params* p, 
             return encoder_backward_small_t<bf16_t>(cfg, p, x, (unsigned char*)ws, w, grads, (hipStream_t)stream, (hipEvent_t)fc_grads_ready);
         return encoder_backward_small_t<float>(cfg, p, x, (unsigned char*)ws, w, grads, (hipStream_t)stream, (hipEvent_t)fc_grads_ready);
     }
-    const bool tposed = forward_made_transposes(ws);
     if (cfg->dtype == CP_FP8 && !opt(cfg, CP_OPT_FP8_BRIDGE))
         return encoder_backward_fp8(cfg, p, x, (unsigned char*)ws, w, grads, (hipStream_t)stream, (hipEvent_t)fc_grads_ready, tposed);
     if (cfg->dtype == CP_FP8) {
@@ -2333,7 +2303,8 @@ extern "C" int cp_debug_activation(const cp_config* cfg, const cp_params* p, con
     // dropout(BN(.)) of fc4..fc6 is STORED by the large-batch forward: read what it stored.  fc7's (formed while staging, never
     // written) and all four after a small-batch forward (csrc/small.cuh applies BatchNorm + dropout while staging) are recomputed from
     // the stored activation with the forward pass's key, into the otherwise unused buffer.
-    const bool stored_u = layer >= CP_N_BN && layer < CP_N_BN + 3 && last_forward_path(ws) == PATH_LARGE;
+    const bool stored_u = layer >= CP_N_BN && layer < CP_N_BN + 3 &&
+                          (cfg->record && cfg->record->n_windows ? cfg->record->path : forward_path(cfg)) == PATH_LARGE;
     if (layer >= CP_N_BN && !stored_u) {
         const int Lp = 5 + (layer - CP_N_BN);
         const int64_t N = cfg->n_windows;

@@ -225,7 +225,7 @@ class Engine:
         self._graph_state: Optional[torch.Tensor] = None      # device cp_step_state while a GraphStep owns the engine
         # per-engine call state, carried in every cp_config (the library has no process-wide switches)
         self.options: Dict[str, int] = {}                     # _lib.OPTIONS names -> 0/1 (tests, measurements)
-        self.tile_schedule = _lib.CP_TILES_STATIC             # dist.use_dynamic_tiles() flips the default for packed sweeps
+        self.tile_schedule = _lib.CP_TILES_STATIC             # dist.share_gpu_with_other_kernels() flips this default (read below through dist.default_tile_schedule())
         from . import dist as _cpdist
         if _cpdist.default_tile_schedule() == "dynamic":
             self.tile_schedule = _lib.CP_TILES_DYNAMIC
@@ -241,6 +241,7 @@ class Engine:
         self._aux = None
         self.grad_tap: Optional[torch.Tensor] = None          # test aid (cp_config.grad_tap)
         self._ws: Optional[torch.Tensor] = None
+        self._rec: Optional[_lib.cp_forward_record] = None   # cp_config.record of self._ws, replaced with it
         self._ws_windows = 0
         names = list(self.specs)
         self._tab_n = len(names)
@@ -310,6 +311,7 @@ class Engine:
             keep = self._ws[:_lib.FP8_STATE_BYTES].clone() if (self.dtype == CP_FP8 and self._ws is not None) else None
             self._ws = None                                   # (frees the old block first unless a GraphStep holds it)
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._rec = _lib.cp_forward_record()              # what the last forward left in this buffer (zeroed: nothing yet)
             if self.dtype == CP_FP8:
                 if keep is not None:
                     self._ws[:_lib.FP8_STATE_BYTES].copy_(keep)
@@ -318,9 +320,10 @@ class Engine:
             self._ws_windows = n_windows
         return self._ws
 
-    def _ws_args(self, n_windows):
-        # the carve depends on n_windows, so a call always passes the size for ITS n_windows
-        ws = self.workspace(n_windows)
+    def _ws_args(self, cfg: _lib.cp_config):
+        # the carve depends on n_windows, so a call always passes the size for ITS n_windows; the record goes with the buffer
+        ws = self.workspace(cfg.n_windows)
+        cfg.record = C.pointer(self._rec)
         return ws.data_ptr(), ws.numel()
 
     # ------------------------------------------------------------------ stages
@@ -339,7 +342,7 @@ class Engine:
             self.step_count += 1
         cfg = self._cfg(n, training)
         z = torch.empty(n, CP_D_E, dtype=torch.float32, device=self.device)
-        ws, nb = self._ws_args(n)
+        ws, nb = self._ws_args(cfg)
         bn = C.byref(self._bn) if not self.adabn else None
         if self.dtype == CP_FP8 and not training and not self._fp8_seen_forward:
             # CP_FP8 scales are "delayed": a forward pass stores with the scales the PREVIOUS pass measured.  An engine whose first
@@ -374,7 +377,7 @@ class Engine:
         out = torch.empty(2, dtype=torch.float32, device=self.device)
         pred = torch.empty(G, CP_TASKS, dtype=torch.int32, device=self.device)
         logits = torch.empty(G, CP_TASKS, CP_TASKS, dtype=torch.float32, device=self.device) if want_logits else None
-        ws, nb = self._ws_args(n)
+        ws, nb = self._ws_args(cfg)
         if gneg is None:
             _lib.check(self.lib.cp_head(C.byref(cfg), C.byref(self._p), z.data_ptr(), labels.data_ptr(), G, V,
                                         1 if want_grad else 0, ws, nb, out.data_ptr(), pred.data_ptr(),
@@ -478,7 +481,7 @@ class Engine:
         out = torch.empty(2, dtype=torch.float32, device=self.device)
         pred = torch.empty(G, CP_TASKS, dtype=torch.int32, device=self.device)
         logits = torch.empty(G, CP_TASKS, CP_TASKS, dtype=torch.float32, device=self.device) if want_logits else None
-        ws, nb = self._ws_args(n)
+        ws, nb = self._ws_args(cfg)
         gws, gnb = self._gws_args(zg.shape[0])
         _lib.check(self.lib.cp_head_glove(C.byref(cfg), z.data_ptr(), zg.data_ptr(), labels.data_ptr(), G, V,
                                           1 if want_grad else 0, ws, nb, gws, gnb, out.data_ptr(), pred.data_ptr(),
@@ -498,7 +501,7 @@ class Engine:
         x = x.reshape(-1, 12)
         n = x.shape[0]
         cfg = self._cfg(n, True)
-        ws, nb = self._ws_args(n)
+        ws, nb = self._ws_args(cfg)
         ev = getattr(self, "fc_grads_ready", None)
         _lib.check(self.lib.cp_encoder_backward_ev(C.byref(cfg), C.byref(self._p), x.data_ptr(), ws, nb, C.byref(self._g),
                                                    self._stream(), ev.cuda_event if ev is not None else None),
@@ -555,7 +558,7 @@ class Engine:
         C_ = 768 if layer < 2 else 512
         out = torch.empty(n, C_, dtype=torch.float32, device=self.device)
         cfg = self._cfg(n, training)
-        ws, nb = self._ws_args(n)
+        ws, nb = self._ws_args(cfg)
         _lib.check(self.lib.cp_debug_activation(C.byref(cfg), C.byref(self._p), self._last_x.data_ptr(), ws, nb, layer,
                                                 out.data_ptr(), self._stream()), "cp_debug_activation")
         return out
@@ -565,7 +568,7 @@ class Engine:
         C_ = 64 if layer < 2 else 512
         out = torch.empty(4, C_, dtype=torch.float32, device=self.device)
         cfg = self._cfg(n, training)
-        ws, nb = self._ws_args(n)
+        ws, nb = self._ws_args(cfg)
         _lib.check(self.lib.cp_debug_bn_stats(C.byref(cfg), ws, nb, layer, out.data_ptr(), self._stream()),
                    "cp_debug_bn_stats")
         return out
@@ -663,6 +666,7 @@ class GraphStep:
         self.table, self.emg_rand = table, emg_rand.clone()
         # the graph's own reference to the buffers whose addresses it bakes (see Engine.workspace)
         self._ws = engine.workspace(self.B * CP_TASKS)
+        self._rec = engine._rec                             # (its forward record: read and written only while capturing)
         self._gws = None
         self._push()
         # the warm-up below is a real step on real state, and capturing runs the host side of every call once more:

@@ -28,8 +28,9 @@
 extern "C" {
 #endif
 
-#define CP_VERSION 111            /* 0.1.1: per-call state (cp_config carries options, tile schedule, sync-BN hook, gradient tap);
-                                     111: cp_debug_gemm without its ablation argument */
+#define CP_VERSION 112            /* 0.1.1: per-call state (cp_config carries options, tile schedule, sync-BN hook, gradient tap);
+                                     111: cp_debug_gemm without its ablation argument;
+                                     112: cp_config.record (cp_forward_record) */
 #define CP_F32 0
 #define CP_BF16 1
 #define CP_FP8 2                  /* e4m3 activations and fc weights on the block-scaled MFMA (BASELINE config 4); see cp_config.dtype */
@@ -81,18 +82,35 @@ typedef int (*cp_allreduce_fn)(void* user, void* row_dev, int64_t count, void* s
  * another stream's or process's kernels (a packed sweep, collectives that stay resident for long) no longer waits for its
  * latest-starting workgroup (+35 % with 8-32 CUs held).  BatchNorm partial sums are grouped per sample tile in the dynamic
  * mode and per workgroup in the static one, so the two differ in the last bits; each is run-to-run reproducible.
- * (The dynamic schedule's tile counters live in a module-global device table with one slot per stream: the only device-side
- * state shared between engines, and two streams never share a slot.) */
+ * (The dynamic schedule's tile counters live in a module-global device table with one slot per stream; two streams never
+ * share a slot.) */
 enum { CP_TILES_STATIC = 0, CP_TILES_DYNAMIC = 1 };
 
-/* Everything a call depends on besides its tensors.  The library keeps NO per-process state for the training path: two
- * engines (two cp_config / workspace pairs) in one process, on one or several streams, do not see each other.  The config of
- * a cp_encoder_backward call must equal that of the cp_encoder_forward call whose workspace it consumes (the library checks
- * the kernel path and the size and returns CP_ERR_ARG otherwise). */
+/* What the last cp_encoder_forward left in a workspace (cp_config.record).  The caller allocates it in HOST memory, zeroes it and
+ * keeps one per workspace buffer (a new buffer gets a new, zeroed record); the library reads and writes it only inside the calls.
+ * cp_encoder_forward fills it; cp_encoder_backward reads it and counts itself in `backwards`. */
+typedef struct cp_forward_record {
+    int64_t n_windows;   /* the forward's n_windows; 0 = no forward has filled this record */
+    int32_t path;        /* the forward's kernel path: 0 large-batch, 1 small-batch, 2 CP_FP8 */
+    int32_t backwards;   /* backward passes run over this forward so far */
+    int32_t transposed;  /* 1: the forward made the backward's transposed weights on cp_config.aux_stream */
+    int32_t pad;
+    void* join_event;    /* transposed: the forward's aux_join (a hipEvent_t recorded behind those transposes), else NULL */
+} cp_forward_record;
+
+/* Everything a call depends on besides its tensors.  Process-wide in the library are only: the thread-local error string of
+ * cp_last_error; the opt-in profiler of cp_profile_enable (one profiled stream at a time); the out-of-range row count of
+ * cp_gather_groups (see cp_gather_oob_count); and, for CP_TILES_DYNAMIC only, the tile counters of the persistent fc GEMM kernels,
+ * one device slot per stream (see cp_config.tile_schedule).  Everything else lives in the caller's cp_config, workspace and
+ * cp_forward_record: two engines (two cp_config / workspace / record triples) in one process, on one or several streams, do not
+ * see each other.  A cp_encoder_backward call consumes the workspace of the cp_encoder_forward that filled its `record`: the
+ * library checks that its config has the forward's n_windows and takes the forward's kernel path (dtype, and for 16/32 bits
+ * whether the batch runs the small-batch form) and returns CP_ERR_ARG otherwise.  Nothing else in the config is checked. */
 typedef struct cp_config {
     int64_t n_windows;   /* rows through the encoder = groups * 41 (train: B*41, eval: B*41*25) */
     int32_t dtype;       /* CP_F32 | CP_BF16 | CP_FP8 (the first F8_STATE_BYTES = 1024 bytes of a CP_FP8 workspace hold the tensors' scales across
-                          * steps: zero them once after allocating it; see cp_fp8_copy_state) */
+                          * steps: zero them once after allocating it, and copy them into a buffer that replaces it, as
+                          * contrastiveprosthetics_amd.engine.Engine.workspace does when it grows the workspace) */
     int32_t adabn;       /* 1: batch statistics in train AND eval (AdaBN); 0: stock BN */
     int32_t training;    /* 1: model.train()  (batch stats, dropout, running-stat update) */
     uint32_t step_state_lo; /* low / high half of the DEVICE address of a cp_step_state, or 0/0 (see below) */
@@ -136,10 +154,15 @@ typedef struct cp_config {
      * recorded), so the caller sees the same stream-ordered semantics as without it.  Same kernels; fc5's and fc4's weight gradients are then summed over
      * 64 row splits each instead of 32 (alone instead of in one paired launch): equal to the rounding of an f32 sum, run-to-run exact.
      * Used by the large-batch 16- and 8-bit paths when dp_emg > 0; ignored elsewhere (f32, small batches, synchronised BatchNorm,
-     * a gradient tap). */
+     * a gradient tap).  A training forward pass with it makes the backward's transposed weights on aux_stream and records aux_join
+     * behind them (cp_forward_record.join_event): the backward over that forward waits for this event on `stream` before its
+     * first launch, whether or not its own config uses the second stream. */
     void* aux_stream;
     void* aux_fork;
     void* aux_join;
+    /* ---- the cp_forward_record of this workspace (above): filled by cp_encoder_forward when non-NULL, required by
+     * cp_encoder_backward, consulted by cp_debug_activation when non-NULL; ignored by every other call */
+    cp_forward_record* record;
 } cp_config;
 
 /* Per-step values kept in DEVICE memory so that a whole training step can be captured in a HIP graph and replayed
@@ -219,7 +242,9 @@ int cp_global_negatives_h(int64_t n_local_windows, const int64_t* labels, float*
 
 
 /* autograd of EMGNet (what loss.backward() does at code/train.py:105 for emg_net):
- * consumes dL/dz left in ws by cp_head, writes every emg_net gradient into `grads`. */
+ * consumes dL/dz left in ws by cp_head, writes every emg_net gradient into `grads`.  cfg->record must be the record that
+ * the forward over ws filled (CP_ERR_ARG if it is NULL, was never filled, or names another n_windows or kernel path); a
+ * repeated backward over one forward gives the same gradients. */
 int cp_encoder_backward(const cp_config* cfg, const cp_params* p, const float* x, void* ws,
                         size_t ws_bytes, cp_params* grads, void* stream);
 /* The same, for data-parallel training: `fc_grads_ready` (a hipEvent_t, or NULL) is recorded on `stream` as soon as every
@@ -357,7 +382,8 @@ int cp_profile_summary(int32_t kind, double* total_ms, int64_t* count);
  * conv2, fc1..fc7; rows x C in the internal layout, conv layers position-major [w][c]; 9..12 =
  * dropout(BN(.)) of fc4..fc7, present only when dp_emg > 0 and the forward ran in training) to f32.
  * Layer 0 (conv1) is never stored by the forward pass -- its consumers recompute it from x -- so it
- * is recomputed here the same way from `p` and `x` (both may be NULL for the other layers). */
+ * is recomputed here the same way from `p` and `x` (both may be NULL for the other layers).  Layers 9..11 are read as the
+ * forward's kernel path stored them: the path of cfg->record when it is non-NULL and filled, else the path `cfg` selects. */
 int cp_debug_activation(const cp_config* cfg, const cp_params* p, const float* x, void* ws,
                         size_t ws_bytes, int32_t layer, float* out, void* stream);
 /* test aid: `blocks` workgroups of 256 threads that each hold a CU's LDS (so nothing else fits next to them there) and spin

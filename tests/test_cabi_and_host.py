@@ -32,9 +32,9 @@ def declared_functions():
     return sorted(set(re.findall(r"\b(cp_[a-z0-9_]+)\s*\(", src)))
 
 
-def test_header_symbols_exported_bound_and_versioned(lib):
+def test_header_symbols_exported_bound_and_at_version_112(lib):
     """every function include/cpnative.h declares is exported and has a ctypes prototype, nothing else is bound, and the library
-    reports the header's CP_VERSION (111: cp_debug_gemm without its ablation argument), which is also the binding's minimum"""
+    reports the header's CP_VERSION (112: cp_config.record), which is also the binding's minimum"""
     from contrastiveprosthetics_amd import _lib
     names = declared_functions()
     assert len(names) >= 15
@@ -44,20 +44,23 @@ def test_header_symbols_exported_bound_and_versioned(lib):
         assert n in _lib.SYMBOLS, f"{n} has no ctypes prototype in _lib.SYMBOLS"
     assert set(_lib.SYMBOLS) == set(names)
     version = int(re.search(r"#define CP_VERSION (\d+)", open(HEADER).read()).group(1))
-    assert lib.cp_version() == version == 111
+    assert lib.cp_version() == version == 112
     assert f"lib.cp_version() < {version}:" in open(os.path.join(ROOT, "contrastiveprosthetics_amd", "_lib.py")).read()
 
 
-def test_struct_layouts_match_header():
+def test_struct_layouts_match_header_with_forward_record():
     from contrastiveprosthetics_amd import _lib
     assert ctypes.sizeof(_lib.cp_params) == 8 * (4 + 7 + 7 + 9 + 9 + 3)
     assert ctypes.sizeof(_lib.cp_bn_buffers) == 8 * 18
-    # 56 bytes of round 1-3 fields + options, tile_schedule, the sync-BN hook (fn, user, world, pad) and the gradient tap (ptr, bytes)
-    assert ctypes.sizeof(_lib.cp_config) == (8 + 4 * 4 + 4 * 4 + 8 + 8) + 4 + 4 + 8 + 8 + 4 + 4 + 8 + 8 + 3 * 8
+    # 56 bytes of round 1-3 fields + options, tile_schedule, the sync-BN hook (fn, user, world, pad), the gradient tap (ptr, bytes),
+    # the second stream (stream, fork, join) and the forward record
+    assert ctypes.sizeof(_lib.cp_config) == (8 + 4 * 4 + 4 * 4 + 8 + 8) + 4 + 4 + 8 + 8 + 4 + 4 + 8 + 8 + 3 * 8 + 8
+    assert ctypes.sizeof(_lib.cp_forward_record) == 8 + 4 * 4 + 8
     hdr = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    body = hdr[hdr.index("typedef struct cp_config {"):hdr.index("} cp_config;")]
-    fields = re.findall(r"\b(\w+)\s*;", body)
-    assert fields == [f[0] for f in _lib.cp_config._fields_], fields
+    for struct in ("cp_config", "cp_forward_record"):
+        body = hdr[hdr.index("typedef struct %s {" % struct):hdr.index("} %s;" % struct)]
+        fields = re.findall(r"\b(\w+)\s*;", body)
+        assert fields == [f[0] for f in getattr(_lib, struct)._fields_], fields
     for name, bit in _lib.OPTIONS.items():
         assert re.search(r"#define CP_OPT_%s %du\b" % (name.upper(), bit), open(HEADER).read()), name
     assert ctypes.sizeof(_lib.cp_adam_hyper) == 32
@@ -221,7 +224,9 @@ def test_library_never_reads_the_environment():
     assert hits == [], hits
     src = open(os.path.join(ROOT, "contrastiveprosthetics_amd", "csrc", "api.hip")).read()
     # and nothing process-wide is left for the training path to consult
-    assert not re.search(r"^static [^(]*\bg_(opt|sync_fn|sync_user|sync_world|grad_tap|tile_schedule)\b", src, flags=re.M)
+    assert not re.search(r"^static [^(]*\bg_(opt|sync_fn|sync_user|sync_world|grad_tap|tile_schedule|notes)\b", src, flags=re.M)
+    # what a forward pass leaves for the backward is the caller's cp_forward_record, not a table keyed by workspace address
+    assert "g_notes" not in src and "FwdNote" not in src and "std::mutex" not in src
     out = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True, check=True).stdout
     assert "getenv" not in subprocess.run(["nm", "-D", "--undefined-only", LIB], capture_output=True, text=True, check=True).stdout
 
