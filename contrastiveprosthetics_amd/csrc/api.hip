@@ -21,6 +21,7 @@
 #include "fp8.cuh"
 #include "small.cuh"
 #include "online.cuh"
+#include "online_adapt.cuh"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* what) {
@@ -2491,17 +2492,23 @@ extern "C" int cp_online_reset(const cp_online_config* cfg, void* ws, size_t ws_
     return 0;
 }
 
-template <typename T>
-static int online_push_t(const cp_online_config* c, unsigned char* base, const OlWS& w, const float* raw, int64_t n,
-                         const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, hipStream_t st) {
-    OlState* state = (OlState*)(base + w.state);
+static int ol_launch_frontend(const cp_online_config* c, OlState* state, float* X, const float* raw, int64_t n, const float* mean_std,
+                              float* windows, hipStream_t st) {
     OlFrontArgs fa{};
-    fa.raw = raw; fa.n = n; fa.st = state; fa.X = (float*)(base + w.X); fa.windows = windows; fa.mean_std = mean_std;
+    fa.raw = raw; fa.n = n; fa.st = state; fa.X = X; fa.windows = windows; fa.mean_std = mean_std;
     fa.n_coef = c->n_coef; fa.phase = c->phase; fa.gain = 1024.f;            // code/load.py:105, 2**10
     for (int i = 0; i < c->n_coef; ++i) { fa.b[i] = c->b[i] / c->a[0]; fa.a[i] = c->a[i] / c->a[0]; }
     if (c->n_coef == 9) hipLaunchKernelGGL((ol_frontend_kernel<9>), dim3(1), dim3(256), 0, st, fa);
     else hipLaunchKernelGGL((ol_frontend_kernel<0>), dim3(1), dim3(256), 0, st, fa);
     CKL("ol_frontend_kernel");
+    return 0;
+}
+
+template <typename T>
+static int online_push_t(const cp_online_config* c, unsigned char* base, const OlWS& w, const float* raw, int64_t n,
+                         const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, hipStream_t st) {
+    OlState* state = (OlState*)(base + w.state);
+    if (int e = ol_launch_frontend(c, state, (float*)(base + w.X), raw, n, mean_std, windows, st)) return e;
     OlLayerArgs la{};
     la.st = state;
     la.x = (const float*)(base + w.X); la.c1w = (const float*)(base + w.c1w); la.c1b = (const float*)(base + w.c1b);
@@ -2539,4 +2546,271 @@ extern "C" int cp_online_push(const cp_online_config* cfg, void* ws, size_t ws_b
     if (cfg->dtype == CP_BF16)
         return online_push_t<bf16_t>(cfg, base, w, raw, n_samples, mean_std, pred, voted, logits, windows, (hipStream_t)stream);
     return online_push_t<float>(cfg, base, w, raw, n_samples, mean_std, pred, voted, logits, windows, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------
+// adaptive online decoding (csrc/online_adapt.cuh): BatchNorm unfolded, float64 statistics per stream in the workspace
+// ---------------------------------------------------------------------------------------
+struct OlaWS {
+    size_t state, head, c1w, c1b, c2w, c2b, fcw[CP_N_FC], fcb[CP_N_FC], pw, pb, gb, stats, X, C1, R2, H0, H1, total;
+};
+static OlaWS ola_carve(int64_t max_windows, int dtype) {
+    const size_t es = dtype == CP_BF16 ? 2 : 4;
+    const size_t rows = (size_t)((max_windows + 15) / 16 * 16);
+    OlaWS w{};
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t r = o; o = align256(o + bytes); return r; };
+    w.state = take(sizeof(OlState));                      // first, as in the folded carve: cp_online_set_classes / reset apply
+    w.head = take(sizeof(OlaHead));
+    w.c1w = take(64 * 3 * 4);
+    w.c1b = take(64 * 4);
+    w.c2w = take(64 * OL_CONV_K * es);
+    w.c2b = take(64 * 4);
+    for (int i = 0; i < CP_N_FC; ++i) {
+        w.fcw[i] = take((size_t)512 * fcK(i) * es);
+        w.fcb[i] = take(512 * 4);
+    }
+    w.pw = take(CP_D_E * 512 * es);
+    w.pb = take(CP_D_E * 4);                              // zeros: the tail adds a bias the unfolded projection does not have
+    w.gb = take((size_t)CP_N_BN * 2 * OLA_F * 4);
+    w.stats = take((size_t)CP_N_BN * 2 * OLA_F * 8);
+    w.X = take(rows * OL_C * 4);
+    w.C1 = take(rows * OL_C * OL_CONV_K * es);            // conv2's operand: rows (window, position)
+    w.R2 = take(rows * OL_C * 64 * 4);                    // conv2's pre-BN output, f32
+    w.H0 = take(rows * 768 * es);
+    w.H1 = take(rows * 512 * es);
+    w.total = o;
+    return w;
+}
+
+static int ola_check(const cp_online_config* c, void* ws, size_t ws_bytes, OlaWS* out) {
+    OlWS folded;
+    if (int e = ol_check(c, ws, ws_bytes, &folded)) return e;      // (the adaptive carve is the larger)
+    *out = ola_carve(c->max_windows, c->dtype);
+    if (ws_bytes < out->total) return fail(CP_ERR_WORKSPACE, "cp_online_adapt: workspace too small");
+    return 0;
+}
+
+extern "C" size_t cp_online_adapt_workspace_bytes(int32_t max_windows_per_push, int32_t dtype) {
+    if (max_windows_per_push < 1) max_windows_per_push = 1;
+    return ola_carve(max_windows_per_push, dtype).total;
+}
+
+static OlaBn ola_bn(unsigned char* base, const OlaWS& w, int l, int mode, double* acc, int first, int last) {
+    OlaBn b{};
+    b.stats = (double*)(base + w.stats) + (size_t)l * 2 * OLA_F;
+    b.acc = acc ? acc + (size_t)l * 3 * OLA_F : nullptr;
+    b.gamma = (const float*)(base + w.gb) + (size_t)l * 2 * OLA_F;
+    b.beta = b.gamma + OLA_F;
+    b.head = (const OlaHead*)(base + w.head);
+    b.mode = mode; b.first = first; b.last = last;
+    return b;
+}
+
+template <typename T>
+static int online_adapt_prepare_t(const cp_params* p, const cp_bn_buffers* bn, float eps, double alpha, unsigned char* base,
+                                  const OlaWS& w, hipStream_t st) {
+    OlaBnInitArgs ia{};
+    for (int l = 0; l < CP_N_BN; ++l) {
+        ia.g[l] = p->bn_g[l]; ia.beta[l] = p->bn_b[l];
+        ia.mean[l] = bn ? bn->running_mean[l] : nullptr; ia.var[l] = bn ? bn->running_var[l] : nullptr;
+    }
+    ia.c1w = p->conv1_w; ia.c1b = p->conv1_b; ia.gb = (float*)(base + w.gb); ia.stats = (double*)(base + w.stats);
+    ia.c1w_d = (float*)(base + w.c1w); ia.c1b_d = (float*)(base + w.c1b); ia.head = (OlaHead*)(base + w.head);
+    ia.alpha = alpha; ia.eps = eps;
+    hipLaunchKernelGGL(ola_bn_init_kernel, dim3(CP_N_BN), dim3(512), 0, st, ia);
+    CKL("ola_bn_init_kernel");
+    OlaCopyArgs f{};
+    f.W = p->conv2_w; f.b = p->conv2_b; f.Wd = base + w.c2w; f.bd = (float*)(base + w.c2b); f.K = OL_CONV_K; f.mode = 2;
+    hipLaunchKernelGGL((ola_copy_kernel<T>), dim3(64), dim3(256), 0, st, f);
+    CKL("ola_copy_kernel");
+    for (int i = 0; i < CP_N_FC; ++i) {
+        f.W = p->fc_w[i]; f.b = p->fc_b[i]; f.Wd = base + w.fcw[i]; f.bd = (float*)(base + w.fcb[i]); f.K = fcK(i); f.mode = i == 0 ? 1 : 0;
+        hipLaunchKernelGGL((ola_copy_kernel<T>), dim3(512), dim3(256), 0, st, f);
+        CKL("ola_copy_kernel");
+    }
+    f.W = p->last_w; f.b = nullptr; f.Wd = base + w.pw; f.bd = (float*)(base + w.pb); f.K = 512; f.mode = 0;
+    hipLaunchKernelGGL((ola_copy_kernel<T>), dim3(CP_D_E), dim3(256), 0, st, f);
+    CKL("ola_copy_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_adapt_prepare(const cp_online_config* cfg, const cp_params* p, const cp_bn_buffers* bn, float bn_eps,
+                                       double alpha, void* ws, size_t ws_bytes, void* stream) {
+    if (!(alpha >= 0.0 && alpha < 1.0)) return fail(CP_ERR_ARG, "cp_online_adapt_prepare: alpha outside [0, 1)");
+    if (!(bn_eps > 0.f)) return fail(CP_ERR_ARG, "cp_online_adapt_prepare: bn_eps must be positive");
+    OlaWS w;
+    if (int e = ola_check(cfg, ws, ws_bytes, &w)) return e;
+    if (!p || !p->conv1_w || !p->conv1_b || !p->conv2_w || !p->conv2_b || !p->last_w) return fail(CP_ERR_ARG, "cp_online_adapt_prepare: parameters");
+    for (int i = 0; i < CP_N_FC; ++i)
+        if (!p->fc_w[i] || !p->fc_b[i]) return fail(CP_ERR_ARG, "cp_online_adapt_prepare: parameters");
+    for (int l = 0; l < CP_N_BN; ++l) {
+        if (!p->bn_g[l] || !p->bn_b[l]) return fail(CP_ERR_ARG, "cp_online_adapt_prepare: parameters");
+        if (bn && (!bn->running_mean[l] || !bn->running_var[l])) return fail(CP_ERR_ARG, "cp_online_adapt_prepare: running statistics");
+    }
+    unsigned char* base = (unsigned char*)ws;
+    if (cfg->dtype == CP_BF16) return online_adapt_prepare_t<bf16_t>(p, bn, bn_eps, alpha, base, w, (hipStream_t)stream);
+    return online_adapt_prepare_t<float>(p, bn, bn_eps, alpha, base, w, (hipStream_t)stream);
+}
+
+// conv2 GEMM: row-tile groups per feature tile for `rows` rows
+static int ola_conv2_groups(int64_t rows) {
+    const int64_t tiles = (rows + 15) / 16;
+    return (int)(tiles < 16 ? tiles : 16);
+}
+
+// BN1 -> conv2 -> BN2 for M windows (m_fixed < 0: the push's count; max_rows bounds the row-tile groups)
+template <typename T>
+static int ola_conv_chain(unsigned char* base, const OlaWS& w, const OlState* state, const float* x, int m_fixed, int64_t max_rows,
+                          void* c1, float* r2, void* out, const OlaBn& bn1, const OlaBn& bn2, hipStream_t st) {
+    OlaConvBnArgs cb{};
+    cb.x = x; cb.c1w = (const float*)(base + w.c1w); cb.c1b = (const float*)(base + w.c1b); cb.out = c1; cb.st = state;
+    cb.m_fixed = m_fixed; cb.conv1 = 1; cb.bn = bn1;
+    hipLaunchKernelGGL((ola_conv_bn_kernel<T>), dim3(1), dim3(64), 0, st, cb);
+    CKL("ola_conv_bn_kernel<BN1>");
+    OlaGemmArgs g{};
+    g.l.act = c1; g.l.w = base + w.c2w; g.l.bias = (const float*)(base + w.c2b); g.l.out = r2; g.l.st = state; g.l.K = OL_CONV_K;
+    g.l.F = 64; g.l.ldo = 64; g.m_fixed = m_fixed; g.rows_per_window = OL_C;
+    hipLaunchKernelGGL((ola_gemm_kernel<T>), dim3(64 / 16, ola_conv2_groups(max_rows * OL_C)), dim3(OL_THREADS), 0, st, g);
+    CKL("ola_gemm_kernel");
+    cb.pre = r2; cb.out = out; cb.conv1 = 0; cb.bn = bn2;
+    hipLaunchKernelGGL((ola_conv_bn_kernel<T>), dim3(1), dim3(64), 0, st, cb);
+    CKL("ola_conv_bn_kernel<BN2>");
+    return 0;
+}
+
+// fc layer i: act [M][K] -> out [M][512] (normalised; nothing under OLA_ACC)
+template <typename T>
+static int ola_fc(unsigned char* base, const OlaWS& w, const OlState* state, int i, const void* act, void* out, int m_fixed,
+                  const OlaBn& bn, hipStream_t st) {
+    OlaGemmArgs g{};
+    g.l.act = act; g.l.out = out; g.l.w = base + w.fcw[i]; g.l.bias = (const float*)(base + w.fcb[i]); g.l.st = state;
+    g.l.K = fcK(i); g.l.F = 512; g.l.ldo = 512; g.m_fixed = m_fixed; g.rows_per_window = 1; g.bn = bn;
+    hipLaunchKernelGGL((ola_fc_kernel<T>), dim3(512 / 16), dim3(OL_THREADS), 0, st, g);
+    CKL("ola_fc_kernel");
+    return 0;
+}
+
+template <typename T>
+static int online_adapt_push_t(const cp_online_config* c, unsigned char* base, const OlaWS& w, const float* raw, int64_t n,
+                               const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, hipStream_t st) {
+    OlState* state = (OlState*)(base + w.state);
+    if (int e = ol_launch_frontend(c, state, (float*)(base + w.X), raw, n, mean_std, windows, st)) return e;
+    if (int e = ola_conv_chain<T>(base, w, state, (const float*)(base + w.X), -1, c->max_windows, base + w.C1, (float*)(base + w.R2),
+                                  base + w.H0, ola_bn(base, w, 0, OLA_TRACK, nullptr, 0, 0), ola_bn(base, w, 1, OLA_TRACK, nullptr, 0, 0), st))
+        return e;
+    for (int i = 0; i < CP_N_FC; ++i)                     // H0 -> H1 -> H0 ...: fc7 leaves its output in H1
+        if (int e = ola_fc<T>(base, w, state, i, base + (i % 2 == 0 ? w.H0 : w.H1), base + (i % 2 == 0 ? w.H1 : w.H0), -1,
+                              ola_bn(base, w, i + 2, OLA_TRACK, nullptr, 0, 0), st))
+            return e;
+    OlTailArgs ta{};
+    ta.proj.st = state;
+    ta.proj.act = base + w.H1; ta.proj.w = base + w.pw; ta.proj.bias = (const float*)(base + w.pb); ta.proj.K = 512; ta.proj.F = CP_D_E;
+    ta.st = state; ta.vote = c->vote; ta.pred = pred; ta.voted = voted; ta.logits = logits;
+    hipLaunchKernelGGL((ol_tail_kernel<T>), dim3(1), dim3(OL_THREADS), 0, st, ta);
+    CKL("ol_tail_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_adapt_push(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* raw, int64_t n_samples,
+                                    const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, void* stream) {
+    OlaWS w;
+    if (int e = ola_check(cfg, ws, ws_bytes, &w)) return e;
+    if (n_samples < 0 || n_samples > (int64_t)CP_ONLINE_STRIDE * cfg->max_windows)
+        return fail(CP_ERR_ARG, "cp_online_adapt_push: a push takes at most 20 * max_windows samples");
+    if (n_samples == 0) return 0;
+    if (!raw || !mean_std || !pred || !voted) return fail(CP_ERR_ARG, "cp_online_adapt_push: raw, mean_std, pred and voted are required");
+    if ((uintptr_t)raw % 4 || (uintptr_t)mean_std % 4) return fail(CP_ERR_ARG, "cp_online_adapt_push: misaligned input");
+    unsigned char* base = (unsigned char*)ws;
+    if (cfg->dtype == CP_BF16)
+        return online_adapt_push_t<bf16_t>(cfg, base, w, raw, n_samples, mean_std, pred, voted, logits, windows, (hipStream_t)stream);
+    return online_adapt_push_t<float>(cfg, base, w, raw, n_samples, mean_std, pred, voted, logits, windows, (hipStream_t)stream);
+}
+
+// calibration scratch: the normalised activations of all windows (two buffers), one chunk of conv2 operand and output, and
+// the float64 accumulators
+struct OlaCalib {
+    size_t A0, A1, C1, R2, acc, total;
+};
+static OlaCalib ola_calib_carve(int64_t n_windows, int dtype) {
+    const size_t es = dtype == CP_BF16 ? 2 : 4;
+    OlaCalib c{};
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t r = o; o = align256(o + bytes); return r; };
+    c.A0 = take((size_t)n_windows * 768 * es);
+    c.A1 = take((size_t)n_windows * 512 * es);
+    c.C1 = take((size_t)OL_MAXM * OL_C * OL_CONV_K * es);
+    c.R2 = take((size_t)OL_MAXM * OL_C * 64 * 4);
+    c.acc = take((size_t)CP_N_BN * 3 * OLA_F * 8);
+    c.total = o;
+    return c;
+}
+
+extern "C" size_t cp_online_adapt_calibrate_scratch_bytes(int64_t n_windows, int32_t dtype) {
+    if (n_windows < 1) n_windows = 1;
+    return ola_calib_carve(n_windows, dtype).total;
+}
+
+template <typename T>
+static int online_adapt_calibrate_t(unsigned char* base, const OlaWS& w, const float* x, int64_t N, unsigned char* sc,
+                                    const OlaCalib& k, hipStream_t st) {
+    const OlState* state = (const OlState*)(base + w.state);
+    const size_t es = sizeof(T);
+    double* acc = (double*)(sc + k.acc);
+    const int64_t nch = (N + OL_MAXM - 1) / OL_MAXM;
+    auto rows_of = [&](int64_t ci) { return (int)(ci + 1 < nch ? OL_MAXM : N - ci * OL_MAXM); };
+    // BN1: conv1 of all windows, one launch
+    OlaConvBnArgs cb{};
+    cb.x = x; cb.c1w = (const float*)(base + w.c1w); cb.c1b = (const float*)(base + w.c1b); cb.st = state;
+    cb.m_fixed = (int)N; cb.conv1 = 1; cb.bn = ola_bn(base, w, 0, OLA_ACC, acc, 1, 1);
+    hipLaunchKernelGGL((ola_conv_bn_kernel<T>), dim3(1), dim3(64), 0, st, cb);
+    CKL("ola_conv_bn_kernel<BN1>");
+    // BN2: per chunk BN1 (frozen) -> conv2 -> accumulate; then again with BN2 frozen into A0
+    const OlaBn bn1 = ola_bn(base, w, 0, OLA_FROZEN, nullptr, 0, 0);
+    for (int pass = 0; pass < 2; ++pass)
+        for (int64_t ci = 0; ci < nch; ++ci) {
+            const OlaBn bn2 = pass == 0 ? ola_bn(base, w, 1, OLA_ACC, acc, ci == 0, ci + 1 == nch) : ola_bn(base, w, 1, OLA_FROZEN, nullptr, 0, 0);
+            if (int e = ola_conv_chain<T>(base, w, state, x + ci * OL_MAXM * OL_C, rows_of(ci), OL_MAXM, sc + k.C1, (float*)(sc + k.R2),
+                                          sc + k.A0 + (size_t)ci * OL_MAXM * 768 * es, bn1, bn2, st))
+                return e;
+        }
+    // fc1..fc7: accumulate over the chunks, then (but for fc7) normalise them into the other buffer
+    for (int i = 0; i < CP_N_FC; ++i) {
+        const int K = fcK(i);
+        unsigned char* in = sc + (i % 2 == 0 ? k.A0 : k.A1);
+        unsigned char* out = sc + (i % 2 == 0 ? k.A1 : k.A0);
+        for (int pass = 0; pass < (i + 1 < CP_N_FC ? 2 : 1); ++pass)
+            for (int64_t ci = 0; ci < nch; ++ci) {
+                const OlaBn bn = pass == 0 ? ola_bn(base, w, i + 2, OLA_ACC, acc, ci == 0, ci + 1 == nch)
+                                           : ola_bn(base, w, i + 2, OLA_FROZEN, nullptr, 0, 0);
+                if (int e = ola_fc<T>(base, w, state, i, in + (size_t)ci * OL_MAXM * K * es, out + (size_t)ci * OL_MAXM * 512 * es,
+                                      rows_of(ci), bn, st))
+                    return e;
+            }
+    }
+    return 0;
+}
+
+extern "C" int cp_online_adapt_calibrate(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* windows,
+                                         int64_t n_windows, void* scratch, size_t scratch_bytes, void* stream) {
+    if (n_windows < 2) return fail(CP_ERR_ARG, "cp_online_adapt_calibrate: calibration takes at least 2 windows");
+    if (n_windows > (int64_t)1 << 24) return fail(CP_ERR_ARG, "cp_online_adapt_calibrate: at most 2**24 windows");
+    OlaWS w;
+    if (int e = ola_check(cfg, ws, ws_bytes, &w)) return e;
+    if (!windows || !scratch) return fail(CP_ERR_ARG, "cp_online_adapt_calibrate: windows and scratch are required");
+    if ((uintptr_t)windows % 4 || (uintptr_t)scratch % 256) return fail(CP_ERR_ARG, "cp_online_adapt_calibrate: misaligned input or scratch");
+    const OlaCalib k = ola_calib_carve(n_windows, cfg->dtype);
+    if (scratch_bytes < k.total) return fail(CP_ERR_WORKSPACE, "cp_online_adapt_calibrate: scratch too small");
+    unsigned char* base = (unsigned char*)ws;
+    if (cfg->dtype == CP_BF16)
+        return online_adapt_calibrate_t<bf16_t>(base, w, windows, n_windows, (unsigned char*)scratch, k, (hipStream_t)stream);
+    return online_adapt_calibrate_t<float>(base, w, windows, n_windows, (unsigned char*)scratch, k, (hipStream_t)stream);
+}
+
+extern "C" int cp_online_adapt_statistics(const cp_online_config* cfg, void* ws, size_t ws_bytes, double* out, void* stream) {
+    OlaWS w;
+    if (int e = ola_check(cfg, ws, ws_bytes, &w)) return e;
+    if (!out) return fail(CP_ERR_ARG, "cp_online_adapt_statistics: out is required");
+    CK(hipMemcpyAsync(out, (unsigned char*)ws + w.stats, (size_t)CP_N_BN * 2 * OLA_F * 8, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
 }

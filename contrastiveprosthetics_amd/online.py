@@ -12,6 +12,10 @@ entries of include/cpnative.h (csrc/online.cuh):
 * the class table holds K <= 64 rows (one-hot class ids, glove rows through the glove encoder, or raw embeddings), the
   prediction is the argmax of z/|z| . E/|E| (first maximum), the vote the mode of the last `vote` predictions (ties: smallest id).
 
+`adapt=alpha` builds the adaptive form (cp_online_adapt_*, csrc/online_adapt.cuh): BatchNorm stays unfolded, its float64
+statistics live in the workspace, `calibrate()` sets them from a recording (AdaBN: the reference's default model, which the
+folded form cannot run), and every push can track the stream with rate alpha per window (0: frozen).
+
 The number of windows a push emits follows from sample counts alone (`windows_emitted`), so a push never waits for the device:
 its outputs are device tensors on torch's current stream.
 """
@@ -62,14 +66,21 @@ class OnlineDecoder:
 
     The weights are folded once, here: the decoder keeps using that folded copy after an optimiser step or a
     `load_state_dict` on the model until `refresh()` folds them again.
+
+    adapt: None (the folded form: stock BatchNorm only) or alpha in [0, 1): the adaptive form, which also takes AdaBN models.
+    It starts from the running statistics (stock BatchNorm) or uncalibrated (AdaBN: `calibrate()` before the first push);
+    each window then moves every BatchNorm's statistics towards its own by the fraction alpha (include/cpnative.h).
     """
 
     def __init__(self, model_or_engine, mean, std, classes=None, vote: int = VOTE, dtype: Optional[str] = None, phase: int = 0,
-                 max_windows_per_push: int = 256, b=None, a=None):
+                 max_windows_per_push: int = 256, b=None, a=None, adapt: Optional[float] = None):
         e = _engine_of(model_or_engine)
-        if e.adabn:
+        if adapt is None and e.adabn:
             raise _lib.CpNativeError("OnlineDecoder needs stock BatchNorm with running statistics: an AdaBN model normalises with "
-                                     "the statistics of its batch, which a live stream of a few windows does not have")
+                                     "the statistics of its batch, which a live stream of a few windows does not have "
+                                     "(adapt= builds the adaptive form, which calibrates them)")
+        if adapt is not None and not 0.0 <= float(adapt) < 1.0:
+            raise ValueError("adapt (alpha) must lie in [0, 1)")
         if dtype is None:
             dtype = {CP_F32: "f32", CP_BF16: "bf16", CP_FP8: "fp8"}[e.dtype]
         if dtype == "fp8":
@@ -93,6 +104,10 @@ class OnlineDecoder:
         if len(b) != len(a) or not 2 <= len(b) <= 17 or a[0] == 0.0:
             raise ValueError("b and a: 2..17 coefficients each, a[0] != 0")
         self.engine = e
+        self.adapt = None if adapt is None else float(adapt)
+        self.calibrated = adapt is None or not e.adabn     # the running statistics are a calibration
+        self._b, self._a = b, a
+        self._prepared = False
         self.lib = _lib.load()
         self.device = e.device
         self.dtype = dtype
@@ -109,7 +124,8 @@ class OnlineDecoder:
             cfg.b[i], cfg.a[i] = float(b[i]), float(a[i])
         self._cfg = cfg
         self.mean_std = torch.stack([self._channels(mean), self._channels(std)]).contiguous()
-        self.ws = torch.zeros(self.lib.cp_online_workspace_bytes(self.max_windows, cfg.dtype), dtype=torch.uint8, device=self.device)
+        nbytes = (self.lib.cp_online_workspace_bytes if adapt is None else self.lib.cp_online_adapt_workspace_bytes)(self.max_windows, cfg.dtype)
+        self.ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
         self.n_seen = 0
         self.class_ids: Optional[torch.Tensor] = None
         self.refresh()
@@ -142,10 +158,17 @@ class OnlineDecoder:
     def refresh(self):
         """Fold the model's current weights and running statistics into the decoder (after an optimiser step or a
         load_state_dict; until then the decoder keeps the copy of the last fold).  A class table that comes from the model
-        (one-hot ids, glove rows) is derived again too, which empties the vote ring."""
+        (one-hot ids, glove rows) is derived again too, which empties the vote ring.  The adaptive form re-reads weights, gamma
+        and beta and keeps its BatchNorm statistics."""
         e = self.engine
-        _lib.check(self.lib.cp_online_prepare(C.byref(self._cfg), C.byref(e._p), C.byref(e._bn), C.c_float(1e-5), *self._ws(),
-                                              self._stream()), "cp_online_prepare")
+        if self.adapt is None:
+            _lib.check(self.lib.cp_online_prepare(C.byref(self._cfg), C.byref(e._p), C.byref(e._bn), C.c_float(1e-5), *self._ws(),
+                                                  self._stream()), "cp_online_prepare")
+        else:
+            bn = C.byref(e._bn) if not (e.adabn or self._prepared) else None
+            _lib.check(self.lib.cp_online_adapt_prepare(C.byref(self._cfg), C.byref(e._p), bn, C.c_float(1e-5), C.c_double(self.adapt),
+                                                        *self._ws(), self._stream()), "cp_online_adapt_prepare")
+        self._prepared = True
         if self.class_ids is not None and self._source[2] is None:
             classes, glove, _, ids = self._source
             self.set_classes(classes, glove=glove, ids=ids)
@@ -160,6 +183,9 @@ class OnlineDecoder:
         if sum(x is not None for x in (classes, glove, table)) != 1:
             raise ValueError("set_classes takes exactly one of classes, glove, table")
         e = self.engine
+        if glove is not None and e.adabn:
+            raise _lib.CpNativeError("glove class rows need a glove encoder with running statistics: on an AdaBN model its "
+                                     "batch statistics would come from a zero-padded group; pass classes= or table=")
         if classes is not None:
             cid = torch.as_tensor(np.asarray(classes, dtype=np.int64).reshape(-1))
             self._check_count(cid.numel())
@@ -201,7 +227,8 @@ class OnlineDecoder:
                                                   int(ids_t.numel()), self._stream()), "cp_online_set_classes")
 
     def reset(self):
-        """Start a new stream: filter, RMS history, sample count and vote ring to zero; classes and weights stay."""
+        """Start a new stream: filter, RMS history, sample count and vote ring to zero; classes and weights (and the adaptive
+        form's BatchNorm statistics: the same user keeps their calibration) stay."""
         _lib.check(self.lib.cp_online_reset(C.byref(self._cfg), *self._ws(), self._stream()), "cp_online_reset")
         self.n_seen = 0
 
@@ -211,6 +238,8 @@ class OnlineDecoder:
         windows (M, 12) f32 (the normalised windows, a test aid)."""
         if self.class_ids is None:
             raise _lib.CpNativeError("set_classes() first")
+        if not self.calibrated:
+            raise _lib.CpNativeError("an AdaBN model has no BatchNorm statistics: calibrate() first")
         if raw.device.type != "cuda" or raw.dtype != torch.float32 or raw.dim() != 2 or raw.shape[1] != EMG_DIM:
             raise ValueError("raw must be an (n, 12) float32 tensor on the GPU")
         raw = raw.contiguous()
@@ -227,9 +256,10 @@ class OnlineDecoder:
             pred, voted = pv[0, :M], pv[1, :M]
             logits = torch.empty(M, K, dtype=torch.float32, device=self.device) if return_logits else None
             wins = torch.empty(M, EMG_DIM, dtype=torch.float32, device=self.device) if return_windows else None
-            _lib.check(self.lib.cp_online_push(C.byref(self._cfg), *self._ws(), piece.data_ptr(), n, self.mean_std.data_ptr(),
-                                               pv[0].data_ptr(), pv[1].data_ptr(), logits.data_ptr() if logits is not None else None,
-                                               wins.data_ptr() if wins is not None else None, self._stream()), "cp_online_push")
+            fn = self.lib.cp_online_push if self.adapt is None else self.lib.cp_online_adapt_push
+            _lib.check(fn(C.byref(self._cfg), *self._ws(), piece.data_ptr(), n, self.mean_std.data_ptr(),
+                          pv[0].data_ptr(), pv[1].data_ptr(), logits.data_ptr() if logits is not None else None,
+                          wins.data_ptr() if wins is not None else None, self._stream()), "cp_online_push")
             self.n_seen += n
             outs.append((pred, voted, logits, wins))
         if not outs:
@@ -246,3 +276,45 @@ class OnlineDecoder:
         if return_windows:
             res.append(cat(3))
         return tuple(res)
+
+    # ------------------------------------------------------------------ adaptive form
+    def _need_adapt(self, what: str):
+        if self.adapt is None:
+            raise _lib.CpNativeError(f"{what} needs the adaptive form: OnlineDecoder(..., adapt=alpha)")
+
+    def calibration_windows(self, raw: torch.Tensor) -> torch.Tensor:
+        """The windows a fresh stream would emit for `raw` (n, 12), by the offline path: preprocess_segments + normalize_ with
+        this decoder's filter, phase, mean and std."""
+        from .preprocess import normalize_, preprocess_segments
+        if raw.device.type != "cuda" or raw.dtype != torch.float32 or raw.dim() != 2 or raw.shape[1] != EMG_DIM:
+            raise ValueError("raw must be an (n, 12) float32 tensor on the GPU")
+        k = windows_before(raw.shape[0], self.phase)
+        if k < 2:
+            raise ValueError("calibration takes at least 2 windows")
+        raw = raw.contiguous()[None]
+        keep = self.phase + STRIDE * np.arange(k)
+        step = _lib.CP_ONLINE_MAX_WINDOWS                  # positions one call of the offline transform keeps
+        w = torch.cat([preprocess_segments(raw, b=self._b, a=self._a, keep=keep[i:i + step]) for i in range(0, k, step)], dim=1)
+        return normalize_(w.contiguous(), self.mean_std[0], self.mean_std[1])[0]
+
+    def calibrate(self, raw: torch.Tensor):
+        """AdaBN calibration from a recording raw (n, 12) f32 on the GPU: every BatchNorm's statistics become the batch
+        statistics of the recording's windows, layer by layer (include/cpnative.h).  Stream state, vote ring and classes stay."""
+        self._need_adapt("calibrate()")
+        if raw.dim() != 2 or windows_before(raw.shape[0], self.phase) < 2:
+            raise ValueError("calibration takes at least 2 windows")
+        w = self.calibration_windows(raw).contiguous()
+        scratch = torch.empty(self.lib.cp_online_adapt_calibrate_scratch_bytes(w.shape[0], self._cfg.dtype), dtype=torch.uint8,
+                              device=self.device)
+        _lib.check(self.lib.cp_online_adapt_calibrate(C.byref(self._cfg), *self._ws(), w.data_ptr(), w.shape[0], scratch.data_ptr(),
+                                                      scratch.numel(), self._stream()), "cp_online_adapt_calibrate")
+        self.calibrated = True
+
+    def bn_statistics(self) -> torch.Tensor:
+        """(9, 2, 512) float64 on the GPU: mean and variance of each BatchNorm as the next window sees them (conv BatchNorms
+        fill channels 0..63)."""
+        self._need_adapt("bn_statistics()")
+        out = torch.zeros(9, 2, 512, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.cp_online_adapt_statistics(C.byref(self._cfg), *self._ws(), out.data_ptr(), self._stream()),
+                   "cp_online_adapt_statistics")
+        return out

@@ -448,6 +448,41 @@ int cp_online_push(const cp_online_config* cfg, void* ws, size_t ws_bytes, const
 /* zeroes the stream part of the state (filter, RMS history, sample count, vote ring); class table and weights stay */
 int cp_online_reset(const cp_online_config* cfg, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- adaptive online decoding: BatchNorm unfolded, per-stream statistics (AdaBN calibration and drift tracking) ----------
+ * The same decoder with the 9 BatchNorms kept unfolded.  For BN b (layer order) and channel c the workspace holds float64
+ * (mu, v); P = the values one window gives a channel: 12 for BN1 and BN2 (positions, as BatchNorm2d pools them), 1 for
+ * BN3..BN9.  With x_1..x_P the channel's pre-BN values of window t, m their mean and w their biased variance, a push runs
+ * the windows in stream order and, for each BN in layer order:
+ *     y = gamma (x - mu) / sqrt(v + eps) + beta                    with the statistics before window t, then
+ *     d = m - mu,  mu <- mu + alpha d,  v <- (1 - alpha)(v + alpha d^2) + alpha w
+ * (the exact moments of the mixture with weights (1 - alpha, alpha); alpha = 0 freezes the statistics; alpha is per window,
+ * 100 Hz, so the time constant is about 1 / (100 alpha) s).  conv2 zero-pads the normalised conv1 output.  The recurrence is
+ * serial in float64 in a fixed order and the GEMMs sum fixed-order tiles, so pred, voted, logits and the statistics after a
+ * push are bit-identical for any chunking.
+ * The workspace begins with the state of the folded form: cp_online_set_classes and cp_online_reset take an adaptive
+ * workspace (reset keeps the statistics); cp_online_prepare and cp_online_push do not. */
+size_t cp_online_adapt_workspace_bytes(int32_t max_windows_per_push, int32_t dtype);
+/* copies the model's parameters (f32, as for cp_online_prepare) into the workspace in the compute dtype, unfolded, with
+ * gamma, beta, bn_eps and alpha in [0, 1).  bn != NULL: the statistics become the running statistics (mu = running_mean,
+ * v = running_var, what eval mode uses); bn == NULL (AdaBN, or a refresh of the weights): the statistics stay as they are,
+ * which on a fresh (zeroed) workspace means uncalibrated -- the caller must not push before cp_online_adapt_calibrate. */
+int cp_online_adapt_prepare(const cp_online_config* cfg, const cp_params* p, const cp_bn_buffers* bn, float bn_eps, double alpha,
+                            void* ws, size_t ws_bytes, void* stream);
+/* bytes of the caller-owned scratch of a calibration over n_windows windows */
+size_t cp_online_adapt_calibrate_scratch_bytes(int64_t n_windows, int32_t dtype);
+/* windows (n_windows >= 2, 12) f32, normalised as a push's windows are: sets every (mu, v) to the batch statistics of the
+ * windows -- mean and biased variance over n_windows * P values -- layer by layer, each layer normalised with its own final
+ * statistics before the next layer's are taken (the reference's AdaBN in eval, models.py:17-35, on that batch).  float64
+ * (n, mean, M2) per chunk of <= 256 windows are merged in a fixed order.  Leaves the stream state, vote ring and class
+ * table alone. */
+int cp_online_adapt_calibrate(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* windows, int64_t n_windows,
+                              void* scratch, size_t scratch_bytes, void* stream);
+/* as cp_online_push, on an adaptive workspace; updates the statistics by the workspace's alpha */
+int cp_online_adapt_push(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* raw, int64_t n_samples,
+                         const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, void* stream);
+/* out (9, 2, 512) float64 on the device: mu, v of each BN (the conv BNs fill channels 0..63, the rest is zero) */
+int cp_online_adapt_statistics(const cp_online_config* cfg, void* ws, size_t ws_bytes, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,10 +5,13 @@ For pushes of 20 and 500 raw samples (1 and 25 windows) in f32 and bf16:
   composition  preprocess_segments over the last 2,010 samples (the offline transform restarts its filter from zero on every
                call, so it needs a segment of history) + normalize_ + Engine.encoder_forward(training=False) + z/|z| . E/|E| +
                argmax over the subset
+With --adapt the adaptive form (OnlineDecoder(..., adapt=0.01), csrc/online_adapt.cuh) is timed next to the folded decoder
+instead of the composition, plus the wall time of calibrate() on 6,000 windows (60 s of stream).
 Each push is timed from the host with a synchronisation behind it (the latency a control loop sees); kernels per push are
 counted with torch.profiler over a few pushes.  One JSON line per case, and a table with --out.
 
     python tools/online_bench.py --iters 200 --out profiles/online_latency.txt
+    python tools/online_bench.py --adapt --iters 200 --out profiles/online_adapt_latency.txt
 """
 import argparse
 import json
@@ -57,6 +60,7 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--adapt", action="store_true", help="adaptive form against the folded decoder, and calibrate()")
     a = ap.parse_args()
     torch.manual_seed(0)
     e = Engine(adabn=False, dtype="f32", device="cuda:0")
@@ -67,6 +71,8 @@ def main():
     table = (e.values.views["glove_net.easy.0.weight"].t() + e.values.views["glove_net.easy.0.bias"]).contiguous()
     tn = table / table.norm(dim=-1, keepdim=True)
     rows = []
+    if a.adapt:
+        return adapt_main(a, e, stream, mean, std, classes)
     for dtype in ("f32", "bf16"):
         e.dtype = 0 if dtype == "f32" else 1
         e._ws = None                                           # the engine's workspace is carved per dtype
@@ -107,6 +113,64 @@ def main():
             for r in rows:
                 f.write(f"{r['kind']:<12} {r['dtype']:<5} {r['samples']:>7} {r['windows']:>7} {r['median_us']:>10.1f} "
                         f"{r['p90_us']:>9.1f} {r['kernels_per_push']:>8.1f}\n")
+
+
+def adapt_main(a, e, stream, mean, std, classes):
+    rows, cal = [], []
+    for dtype in ("f32", "bf16"):
+        for n in (20, 500):
+            m = n // 20
+            for kind, adapt in (("folded", None), ("adaptive", 0.01)):
+                dec = OnlineDecoder(e, mean, std, classes=classes, dtype=dtype, adapt=adapt)
+                pos = [0]
+
+                def push():
+                    s = pos[0] % (stream.shape[0] - n)
+                    pos[0] += n
+                    return dec.push(stream[s:s + n])
+
+                med, p90 = time_pushes(push, a.iters, a.warmup)
+                k = count_kernels(push)
+                r = dict(kind=kind, dtype=dtype, samples=n, windows=m, median_us=round(med, 1), p90_us=round(p90, 1),
+                         kernels_per_push=k)
+                print(json.dumps(r), flush=True)
+                rows.append(r)
+        dec = OnlineDecoder(e, mean, std, classes=classes, dtype=dtype, adapt=0.01)
+        rec = stream[:20 * 6000 + 10].contiguous()
+        dec.calibrate(rec)
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(5):
+            t0 = time.perf_counter()
+            dec.calibrate(rec)
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        r = dict(kind="calibrate", dtype=dtype, windows=6000, median_ms=round(float(np.median(ts)) * 1e3, 2))
+        print(json.dumps(r), flush=True)
+        cal.append(r)
+        ts = []
+        for _ in range(5):                                     # of which: the windows by the offline transform
+            t0 = time.perf_counter()
+            dec.calibration_windows(rec)
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        r = dict(kind="cal_windows", dtype=dtype, windows=6000, median_ms=round(float(np.median(ts)) * 1e3, 2))
+        print(json.dumps(r), flush=True)
+        cal.append(r)
+    if a.out:
+        dev = torch.cuda.get_device_name(0)
+        with open(a.out, "w") as f:
+            f.write(f"# tools/online_bench.py --adapt --iters {a.iters} --warmup {a.warmup} on {dev}\n")
+            f.write("# per-push wall time, host-synchronised (median, p90), and kernels per push (torch.profiler);\n")
+            f.write("# adaptive: OnlineDecoder(..., adapt=0.01), statistics tracked on every window\n")
+            f.write(f"{'kind':<12} {'dtype':<5} {'samples':>7} {'windows':>7} {'median_us':>10} {'p90_us':>9} {'kernels':>8}\n")
+            for r in rows:
+                f.write(f"{r['kind']:<12} {r['dtype']:<5} {r['samples']:>7} {r['windows']:>7} {r['median_us']:>10.1f} "
+                        f"{r['p90_us']:>9.1f} {r['kernels_per_push']:>8.1f}\n")
+            f.write("# calibrate() on 6,000 windows (60 s of stream), host-synchronised wall time, median of 5; cal_windows: the\n"
+                    "# part of it that makes the windows with the offline transform (preprocess_segments + normalize_)\n")
+            for r in cal:
+                f.write(f"{r['kind']:<12} {r['dtype']:<5} {'':>7} {r['windows']:>7} {r['median_ms']:>8.2f} ms\n")
 
 
 if __name__ == "__main__":
