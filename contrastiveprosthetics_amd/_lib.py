@@ -79,6 +79,7 @@ class cp_online_config(C.Structure):
 
 
 CP_ONLINE_MAX_CLASSES, CP_ONLINE_MAX_VOTE, CP_ONLINE_MAX_WINDOWS, CP_ONLINE_STRIDE = 64, 256, 256, 20
+CP_ONLINE_MULTI_MAX_STREAMS, CP_ONLINE_MULTI_MAX_ROWS = 256, 65536
 
 SYMBOLS = {
     "cp_version": (C.c_int, []),
@@ -136,6 +137,14 @@ SYMBOLS = {
     "cp_online_adapt_calibrate": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, C.c_int64, _fp, C.c_size_t, _fp]),
     "cp_online_adapt_push": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, _fp]),
     "cp_online_adapt_statistics": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, _fp]),
+    "cp_online_multi_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "cp_online_multi_prepare": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _P(cp_params), _P(cp_bn_buffers), C.c_float,
+                                          _fp, C.c_size_t, _fp]),
+    "cp_online_multi_set_classes": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, C.c_int32, _fp, _fp,
+                                              C.c_int32, _fp]),
+    "cp_online_multi_reset": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, C.c_int32, _fp]),
+    "cp_online_multi_push": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, _fp, _fp, C.c_int64, C.c_int32,
+                                       _fp, _fp, _fp, _fp, _fp, _fp]),
 }
 
 KERNEL_KINDS = ["gather", "prep", "conv1_fwd", "bn_finalize", "conv2_fwd", "fold", "fc_fwd", "dropout", "proj_fwd",

@@ -22,6 +22,7 @@
 #include "small.cuh"
 #include "online.cuh"
 #include "online_adapt.cuh"
+#include "online_multi.cuh"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* what) {
@@ -2393,13 +2394,15 @@ static_assert(OL_MAXM == CP_ONLINE_MAX_WINDOWS && OL_MAXVOTE == CP_ONLINE_MAX_VO
 struct OlWS {
     size_t state, c1w, c1b, c2w, c2b, fcw[CP_N_FC], fcb[CP_N_FC], pw, pb, X, H0, H1, total;
 };
-static OlWS ol_carve(int64_t max_windows, int dtype) {
+// max_windows: rows of one push.  The multi-stream carve (meta != NULL) holds n_streams states and their OlmMeta.
+static OlWS ol_carve(int64_t max_windows, int dtype, int n_streams = 1, size_t* meta = nullptr) {
     const size_t es = dtype == CP_BF16 ? 2 : 4;
     const size_t rows = (size_t)((max_windows + 15) / 16 * 16);
     OlWS w{};
     size_t o = 0;
     auto take = [&](size_t bytes) { const size_t r = o; o = align256(o + bytes); return r; };
-    w.state = take(sizeof(OlState));
+    w.state = take((size_t)n_streams * sizeof(OlState));
+    if (meta) *meta = take((size_t)n_streams * sizeof(OlmMeta));
     w.c1w = take(64 * 3 * 4);
     w.c1b = take(64 * 4);
     w.c2w = take(64 * OL_CONV_K * es);
@@ -2417,7 +2420,7 @@ static OlWS ol_carve(int64_t max_windows, int dtype) {
     return w;
 }
 
-static int ol_check(const cp_online_config* c, void* ws, size_t ws_bytes, OlWS* out) {
+static int ol_check_config(const cp_online_config* c, void* ws) {
     if (!c || !ws) return fail(CP_ERR_ARG, "cp_online: config and workspace are required");
     if (c->dtype != CP_F32 && c->dtype != CP_BF16) return fail(CP_ERR_ARG, "cp_online: dtype must be CP_F32 or CP_BF16 (no 8-bit path)");
     if (c->max_windows < 1 || c->max_windows > CP_ONLINE_MAX_WINDOWS) return fail(CP_ERR_ARG, "cp_online: max_windows outside 1..256");
@@ -2425,6 +2428,11 @@ static int ol_check(const cp_online_config* c, void* ws, size_t ws_bytes, OlWS* 
     if (c->phase < 0 || c->phase >= CP_ONLINE_STRIDE) return fail(CP_ERR_ARG, "cp_online: phase outside 0..19");
     if (c->n_coef < 2 || c->n_coef > OL_MAXCOEF || c->a[0] == 0.0) return fail(CP_ERR_ARG, "cp_online: IIR coefficients");
     if ((uintptr_t)ws % 256) return fail(CP_ERR_ARG, "cp_online: workspace not 256-byte aligned");
+    return 0;
+}
+
+static int ol_check(const cp_online_config* c, void* ws, size_t ws_bytes, OlWS* out) {
+    if (int e = ol_check_config(c, ws)) return e;
     *out = ol_carve(c->max_windows, c->dtype);
     if (ws_bytes < out->total) return fail(CP_ERR_WORKSPACE, "cp_online: workspace too small");
     return 0;
@@ -2813,4 +2821,141 @@ extern "C" int cp_online_adapt_statistics(const cp_online_config* cfg, void* ws,
     if (!out) return fail(CP_ERR_ARG, "cp_online_adapt_statistics: out is required");
     CK(hipMemcpyAsync(out, (unsigned char*)ws + w.stats, (size_t)CP_N_BN * 2 * OLA_F * 8, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// multi-stream online decoding (csrc/online_multi.cuh): S states, the folded weights once, rows of all streams packed
+// ---------------------------------------------------------------------------------------
+static_assert(OLM_MAXS == CP_ONLINE_MULTI_MAX_STREAMS && OL_MAXK == 64, "multi-stream limits");
+struct OlmWS {
+    OlWS w;                  // w.state: stream 0's state, w.X / H0 / H1: max_rows rows
+    size_t meta;
+};
+
+static int olm_check(const cp_online_config* c, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes, OlmWS* out) {
+    if (n_streams < 1 || n_streams > CP_ONLINE_MULTI_MAX_STREAMS) return fail(CP_ERR_ARG, "cp_online_multi: n_streams outside 1..256");
+    if (max_rows < 1 || max_rows > CP_ONLINE_MULTI_MAX_ROWS) return fail(CP_ERR_ARG, "cp_online_multi: max_rows outside 1..65536");
+    if (int e = ol_check_config(c, ws)) return e;
+    out->w = ol_carve(max_rows, c->dtype, n_streams, &out->meta);
+    if (ws_bytes < out->w.total) return fail(CP_ERR_WORKSPACE, "cp_online_multi: workspace too small");
+    return 0;
+}
+
+extern "C" size_t cp_online_multi_workspace_bytes(int32_t n_streams, int32_t max_rows, int32_t dtype) {
+    if (n_streams < 1) n_streams = 1;
+    if (max_rows < 1) max_rows = 1;
+    size_t meta;
+    return ol_carve(max_rows, dtype, n_streams, &meta).total;
+}
+
+extern "C" int cp_online_multi_prepare(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, const cp_params* p,
+                                       const cp_bn_buffers* bn, float bn_eps, void* ws, size_t ws_bytes, void* stream) {
+    OlmWS w;
+    if (int e = olm_check(cfg, n_streams, max_rows, ws, ws_bytes, &w)) return e;
+    if (!p || !p->conv1_w || !p->conv1_b || !p->conv2_w || !p->conv2_b || !p->last_w) return fail(CP_ERR_ARG, "cp_online_multi_prepare: parameters");
+    for (int i = 0; i < CP_N_FC; ++i)
+        if (!p->fc_w[i] || !p->fc_b[i]) return fail(CP_ERR_ARG, "cp_online_multi_prepare: parameters");
+    if (!bn) return fail(CP_ERR_ARG, "cp_online_multi_prepare: stock BatchNorm with running statistics required (AdaBN has none)");
+    for (int l = 0; l < CP_N_BN; ++l)
+        if (!p->bn_g[l] || !p->bn_b[l] || !bn->running_mean[l] || !bn->running_var[l])
+            return fail(CP_ERR_ARG, "cp_online_multi_prepare: stock BatchNorm with running statistics required (AdaBN has none)");
+    unsigned char* base = (unsigned char*)ws;
+    if (cfg->dtype == CP_BF16) return online_prepare_t<bf16_t>(p, bn, bn_eps, base, w.w, (hipStream_t)stream);
+    return online_prepare_t<float>(p, bn, bn_eps, base, w.w, (hipStream_t)stream);
+}
+
+extern "C" int cp_online_multi_set_classes(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                           int32_t index, const float* table, const int32_t* ids, int32_t n_classes, void* stream) {
+    OlmWS w;
+    if (int e = olm_check(cfg, n_streams, max_rows, ws, ws_bytes, &w)) return e;
+    if (index < 0 || index >= n_streams) return fail(CP_ERR_ARG, "cp_online_multi_set_classes: stream index outside 0..n_streams-1");
+    if (!table || !ids || n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return fail(CP_ERR_ARG, "cp_online_multi_set_classes: 1..64 classes");
+    OlState* states = (OlState*)((unsigned char*)ws + w.w.state);
+    hipLaunchKernelGGL(ol_set_classes_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, states + index, table, ids, (int)n_classes);
+    CKL("ol_set_classes_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_multi_reset(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                     int32_t index, void* stream) {
+    OlmWS w;
+    if (int e = olm_check(cfg, n_streams, max_rows, ws, ws_bytes, &w)) return e;
+    if (index < -1 || index >= n_streams) return fail(CP_ERR_ARG, "cp_online_multi_reset: stream index outside -1..n_streams-1");
+    OlState* states = (OlState*)((unsigned char*)ws + w.w.state);
+    hipLaunchKernelGGL(olm_reset_kernel, dim3(index < 0 ? n_streams : 1), dim3(256), 0, (hipStream_t)stream, states, index < 0 ? 0 : index);
+    CKL("olm_reset_kernel");
+    return 0;
+}
+
+// row blocks of an encoder launch with `ftiles` workgroups per row block: about OLM_TARGET_WG workgroups when there are rows
+static void olm_row_blocks(int rows, int ftiles, int* blocks, int* tiles_per_block) {
+    const int tiles = (rows + 15) / 16;
+    int b = (OLM_TARGET_WG + ftiles - 1) / ftiles;
+    if (b > tiles) b = tiles;
+    *tiles_per_block = (tiles + b - 1) / b;
+    *blocks = (tiles + *tiles_per_block - 1) / *tiles_per_block;
+}
+
+template <typename T>
+static int online_multi_push_t(const cp_online_config* c, int n_streams, unsigned char* base, const OlmWS& m, const float* raw,
+                               const int32_t* counts, int64_t total, int rows, const float* mean_std, int32_t* pred,
+                               int32_t* voted, float* logits, float* windows, hipStream_t st) {
+    const OlWS& w = m.w;
+    OlState* states = (OlState*)(base + w.state);
+    OlmMeta* meta = (OlmMeta*)(base + m.meta);
+    OlmFrontArgs fa{};
+    fa.f.raw = raw; fa.f.X = (float*)(base + w.X); fa.f.windows = windows; fa.f.mean_std = mean_std;
+    fa.f.n_coef = c->n_coef; fa.f.phase = c->phase; fa.f.gain = 1024.f;       // as ol_launch_frontend
+    for (int i = 0; i < c->n_coef; ++i) { fa.f.b[i] = c->b[i] / c->a[0]; fa.f.a[i] = c->a[i] / c->a[0]; }
+    fa.states = states; fa.meta = meta; fa.counts = counts; fa.total_samples = total; fa.rows = rows; fa.max_m = c->max_windows;
+    if (c->n_coef == 9) hipLaunchKernelGGL((olm_frontend_kernel<9>), dim3(n_streams), dim3(256), 0, st, fa);
+    else hipLaunchKernelGGL((olm_frontend_kernel<0>), dim3(n_streams), dim3(256), 0, st, fa);
+    CKL("olm_frontend_kernel");
+    OlmLayerArgs la{};
+    la.rows = rows;
+    if (rows > 0) {
+        OlLayerArgs& l = la.l;
+        l.x = (const float*)(base + w.X); l.c1w = (const float*)(base + w.c1w); l.c1b = (const float*)(base + w.c1b);
+        l.w = base + w.c2w; l.bias = (const float*)(base + w.c2b); l.out = base + w.H0; l.K = OL_CONV_K; l.F = 64; l.ldo = 768;
+        l.out_pos = 64;
+        int blocks;
+        olm_row_blocks(rows, 4 * OL_C, &blocks, &la.tiles_per_block);
+        hipLaunchKernelGGL((olm_layer_kernel<T, true>), dim3(4, OL_C, blocks), dim3(OL_THREADS), 0, st, la);
+        CKL("olm_layer_kernel<conv>");
+        olm_row_blocks(rows, 512 / 16, &blocks, &la.tiles_per_block);
+        for (int i = 0; i < CP_N_FC; ++i) {               // H0 -> H1 -> H0 ...: fc7 leaves its output in H1
+            l.act = base + (i % 2 == 0 ? w.H0 : w.H1);
+            l.out = base + (i % 2 == 0 ? w.H1 : w.H0);
+            l.w = base + w.fcw[i]; l.bias = (const float*)(base + w.fcb[i]); l.K = fcK(i); l.F = 512; l.ldo = 512; l.out_pos = 0;
+            hipLaunchKernelGGL((olm_layer_kernel<T, false>), dim3(512 / 16, blocks), dim3(OL_THREADS), 0, st, la);
+            CKL("olm_layer_kernel<fc>");
+        }
+    }
+    OlmTailArgs ta{};
+    ta.proj = la.l;
+    ta.proj.act = base + w.H1; ta.proj.out = nullptr; ta.proj.w = base + w.pw; ta.proj.bias = (const float*)(base + w.pb); ta.proj.K = 512;
+    ta.proj.F = CP_D_E;
+    ta.states = states; ta.meta = meta; ta.vote = c->vote; ta.pred = pred; ta.voted = voted; ta.logits = logits;
+    hipLaunchKernelGGL((olm_tail_kernel<T>), dim3(n_streams), dim3(OL_THREADS), 0, st, ta);
+    CKL("olm_tail_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_multi_push(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                    const float* raw, const int32_t* counts, int64_t total_samples, int32_t total_windows,
+                                    const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, void* stream) {
+    OlmWS w;
+    if (int e = olm_check(cfg, n_streams, max_rows, ws, ws_bytes, &w)) return e;
+    if (total_windows < 0 || total_windows > max_rows) return fail(CP_ERR_ARG, "cp_online_multi_push: total_windows outside 0..max_rows");
+    if (total_samples < 0) return fail(CP_ERR_ARG, "cp_online_multi_push: negative total_samples");
+    if (total_samples == 0) return 0;
+    if (!raw || !counts || !mean_std) return fail(CP_ERR_ARG, "cp_online_multi_push: raw, counts and mean_std are required");
+    if (total_windows > 0 && (!pred || !voted)) return fail(CP_ERR_ARG, "cp_online_multi_push: pred and voted are required");
+    if ((uintptr_t)raw % 4 || (uintptr_t)mean_std % 4 || (uintptr_t)counts % 4) return fail(CP_ERR_ARG, "cp_online_multi_push: misaligned input");
+    unsigned char* base = (unsigned char*)ws;
+    if (cfg->dtype == CP_BF16)
+        return online_multi_push_t<bf16_t>(cfg, n_streams, base, w, raw, counts, total_samples, total_windows, mean_std, pred, voted,
+                                           logits, windows, (hipStream_t)stream);
+    return online_multi_push_t<float>(cfg, n_streams, base, w, raw, counts, total_samples, total_windows, mean_std, pred, voted, logits,
+                                      windows, (hipStream_t)stream);
 }

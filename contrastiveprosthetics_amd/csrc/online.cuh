@@ -62,14 +62,21 @@ struct OlFrontArgs {
     double b[OL_MAXCOEF], a[OL_MAXCOEF]; // normalised (a[0] == 1)
 };
 
+// Windows final once N raw samples have arrived (include/cpnative.h: c(N))
+__device__ __forceinline__ long long ol_windows_before(long long N, int phase) {
+    const long long v = (N - phase + 9) / OL_STRIDE;
+    return v > 0 ? v : 0;
+}
+
 // The recurrences of preprocess_kernel<NB, 11> carried across calls: same operations, same order, same rounding points,
 // floating-point contraction off.  Window k is the RMS-series position phase + 20 k, i.e. raw sample phase + 20 k + 10.
+// One workgroup of 256 threads runs one stream: n samples of raw from the stream's state st (n0 samples seen so far), the
+// windows to X and windows (if not NULL) from row 0.  Updates the filter and RMS state, not n_seen; returns the number
+// of windows on thread 0.  Behind a barrier on return.
 template <int NB>
-__global__ __launch_bounds__(256) void ol_frontend_kernel(OlFrontArgs p) {
+__device__ __forceinline__ int ol_frontend_run(const OlFrontArgs& p, OlState* st, const float* raw, long long n, long long n0,
+                                               float* X, float* windows, float* xs) {
 #pragma clang fp contract(off)
-    __shared__ float xs[OL_FRONT_PIECE * OL_C];
-    OlState* st = p.st;
-    const long long n0 = st->n_seen;
     const int c = threadIdx.x;
     const bool on = c < OL_C;
     const int nb = NB > 0 ? NB : p.n_coef;
@@ -91,10 +98,10 @@ __global__ __launch_bounds__(256) void ol_frontend_kernel(OlFrontArgs p) {
         sd = p.mean_std[OL_C + c];
     }
     int j = 0;
-    for (long long base = 0; base < p.n; base += OL_FRONT_PIECE) {
-        const int len = (int)((p.n - base) < OL_FRONT_PIECE ? (p.n - base) : OL_FRONT_PIECE);
+    for (long long base = 0; base < n; base += OL_FRONT_PIECE) {
+        const int len = (int)((n - base) < OL_FRONT_PIECE ? (n - base) : OL_FRONT_PIECE);
         __syncthreads();
-        for (int e = threadIdx.x; e < len * OL_C; e += 256) xs[e] = p.raw[base * OL_C + e];
+        for (int e = threadIdx.x; e < len * OL_C; e += 256) xs[e] = raw[base * OL_C + e];
         __syncthreads();
         if (!on) continue;
         for (int tl = 0; tl < len; ++tl) {
@@ -127,8 +134,8 @@ __global__ __launch_bounds__(256) void ol_frontend_kernel(OlFrontArgs p) {
                 if (i >= p.phase && (i - p.phase) % OL_STRIDE == 0) {
                     const float r = sqrtf((float)(tmp / dwin));
                     const float v = (r - mean) / sd;                  // emg_normalize_kernel
-                    p.X[j * OL_C + c] = v;
-                    if (p.windows) p.windows[j * OL_C + c] = v;
+                    X[j * OL_C + c] = v;
+                    if (windows) windows[j * OL_C + c] = v;
                     ++j;
                 }
             }
@@ -142,8 +149,17 @@ __global__ __launch_bounds__(256) void ol_frontend_kernel(OlFrontArgs p) {
         st->tmp[c] = tmp;
         st->sq0[c] = sq0;
     }
-    __syncthreads();                                  // every thread has read n_seen
-    if (c == 0) {
+    __syncthreads();
+    return j;
+}
+
+template <int NB>
+__global__ __launch_bounds__(256) void ol_frontend_kernel(OlFrontArgs p) {
+    __shared__ float xs[OL_FRONT_PIECE * OL_C];
+    OlState* st = p.st;
+    const long long n0 = st->n_seen;
+    const int j = ol_frontend_run<NB>(p, st, p.raw, p.n, n0, p.X, p.windows, xs);     // (every thread has read n_seen)
+    if (threadIdx.x == 0) {
         st->n_seen = n0 + p.n;
         st->m_cur = j;
     }
@@ -260,20 +276,15 @@ __device__ __forceinline__ void ol_tile(const OlLayerArgs& a, OlTileLds<T>& L, i
     __syncthreads();
 }
 
-// conv2 (CONV: grid 4 feature tiles x 12 positions, conv1 recomputed from the windows) or one fc layer (grid F/16):
-// out = relu(A W'^T + b') in the compute dtype
+// Tiles m_begin, m_begin + 16, .. < m_end of M rows for features f0..f0+15 (and position pos): out = relu(A W'^T + b')
 template <typename T, bool CONV>
-__global__ __launch_bounds__(OL_THREADS) void ol_layer_kernel(OlLayerArgs a) {
+__device__ __forceinline__ void ol_layer_tiles(const OlLayerArgs& a, OlTileLds<T>& L, int f0, int pos, int m_begin, int m_end, int M) {
 #pragma clang fp contract(off)
-    __shared__ OlTileLds<T> L;
-    const int M = a.st->m_cur;
-    if (M <= 0) return;
-    const int f0 = blockIdx.x * 16, pos = CONV ? (int)blockIdx.y : 0;
     const int K = CONV ? OL_CONV_K : a.K;
     uint4 wf[OL_MAXCH][OL_KC * (int)sizeof(T) / 64];
     ol_load_weights<T>((const T*)a.w, K, f0, wf);
     const int tid = threadIdx.x;
-    for (int m0 = 0; m0 < M; m0 += 16) {
+    for (int m0 = m_begin; m0 < m_end; m0 += 16) {
         ol_tile<T, CONV>(a, L, K, pos, m0, M, wf);
         if (tid < 256) {
             const int row = tid >> 4, col = tid & 15;
@@ -286,6 +297,16 @@ __global__ __launch_bounds__(OL_THREADS) void ol_layer_kernel(OlLayerArgs a) {
     }
 }
 
+// conv2 (CONV: grid 4 feature tiles x 12 positions, conv1 recomputed from the windows) or one fc layer (grid F/16):
+// out = relu(A W'^T + b') in the compute dtype
+template <typename T, bool CONV>
+__global__ __launch_bounds__(OL_THREADS) void ol_layer_kernel(OlLayerArgs a) {
+    __shared__ OlTileLds<T> L;
+    const int M = a.st->m_cur;
+    if (M <= 0) return;
+    ol_layer_tiles<T, CONV>(a, L, blockIdx.x * 16, CONV ? (int)blockIdx.y : 0, 0, M, M);
+}
+
 struct OlTailArgs {
     OlLayerArgs proj;         // act = fc7 output, w / bias = folded projection
     OlState* st;
@@ -295,30 +316,39 @@ struct OlTailArgs {
     float* logits;            // optional [M][K]
 };
 
-// projection -> z, z / |z|, logits against the table, argmax (first maximum), then one wave runs the vote ring over the
-// push's windows in order: mode of the last `vote` predictions, ties to the smallest class id (the table is sorted by id)
+// LDS of the tail
 template <typename T>
-__global__ __launch_bounds__(OL_THREADS) void ol_tail_kernel(OlTailArgs t) {
+struct OlTailLds {
+    OlTileLds<T> L;
+    float zn[16][17];
+    float lg[16][OL_MAXK + 1];
+    int pidx[OL_MAXM];
+    int ring[OL_MAXVOTE];
+};
+
+// projection -> z, z / |z|, logits against the table, argmax (first maximum), then one wave runs the vote ring over the
+// push's windows in order: mode of the last `vote` predictions, ties to the smallest class id (the table is sorted by id).
+// M (1..OL_MAXM) rows of proj.act; row j's outputs go to pred[j], voted[j] and logits[j * ldl ..] (columns 0..K-1).
+template <typename T>
+__device__ __forceinline__ void ol_tail_run(const OlLayerArgs& proj, OlState* st, int M, int vote, int32_t* pred, int32_t* voted,
+                                            float* logits, int ldl, OlTailLds<T>& S) {
 #pragma clang fp contract(off)
-    __shared__ OlTileLds<T> L;
-    __shared__ float zn[16][17];
-    __shared__ float lg[16][OL_MAXK + 1];
-    __shared__ int pidx[OL_MAXM];
-    __shared__ int ring[OL_MAXVOTE];
-    OlState* st = t.st;
-    const int M = st->m_cur;
-    if (M <= 0) return;
+    OlTileLds<T>& L = S.L;
+    auto& zn = S.zn;
+    auto& lg = S.lg;
+    auto& pidx = S.pidx;
+    auto& ring = S.ring;
     const int K = st->K;
     const int tid = threadIdx.x;
     uint4 wf[OL_MAXCH][OL_KC * (int)sizeof(T) / 64];
-    ol_load_weights<T>((const T*)t.proj.w, 512, 0, wf);
+    ol_load_weights<T>((const T*)proj.w, 512, 0, wf);
     for (int m0 = 0; m0 < M; m0 += 16) {
-        ol_tile<T, false>(t.proj, L, 512, 0, m0, M, wf);
+        ol_tile<T, false>(proj, L, 512, 0, m0, M, wf);
         if (tid < 16) {
             float z[16], ss = 0.f;
 #pragma unroll
             for (int d = 0; d < 16; ++d) {
-                z[d] = L.red[0][tid][d] + t.proj.bias[d];
+                z[d] = L.red[0][tid][d] + proj.bias[d];
                 ss += z[d] * z[d];
             }
             const float nrm = sqrtf(ss);
@@ -332,7 +362,7 @@ __global__ __launch_bounds__(OL_THREADS) void ol_tail_kernel(OlTailArgs t) {
 #pragma unroll
             for (int d = 0; d < 16; ++d) s += zn[row][d] * st->table[k][d];
             lg[row][k] = s;
-            if (t.logits && m0 + row < M) t.logits[(size_t)(m0 + row) * K + k] = s;
+            if (logits && m0 + row < M) logits[(size_t)(m0 + row) * ldl + k] = s;
         }
         __syncthreads();
         if (tid < 16 && m0 + tid < M) {
@@ -345,7 +375,7 @@ __global__ __launch_bounds__(OL_THREADS) void ol_tail_kernel(OlTailArgs t) {
         __syncthreads();
     }
     if (tid < 64) {
-        const int lane = tid, V = t.vote;
+        const int lane = tid, V = vote;
         int head = st->vote_head, len = st->vote_len;
         for (int i = lane; i < V; i += 64) ring[i] = st->vote_ring[i];
         __builtin_amdgcn_wave_barrier();
@@ -363,8 +393,8 @@ __global__ __launch_bounds__(OL_THREADS) void ol_tail_kernel(OlTailArgs t) {
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) key = max(key, __shfl_xor(key, o, 64));
             if (lane == 0) {
-                t.pred[j] = st->ids[pj];
-                t.voted[j] = st->ids[255 - (key & 255)];
+                pred[j] = st->ids[pj];
+                voted[j] = st->ids[255 - (key & 255)];
             }
         }
         __builtin_amdgcn_wave_barrier();
@@ -374,6 +404,15 @@ __global__ __launch_bounds__(OL_THREADS) void ol_tail_kernel(OlTailArgs t) {
             st->vote_len = len;
         }
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(OL_THREADS) void ol_tail_kernel(OlTailArgs t) {
+    __shared__ OlTailLds<T> S;
+    OlState* st = t.st;
+    const int M = st->m_cur;
+    if (M <= 0) return;
+    ol_tail_run<T>(t.proj, st, M, t.vote, t.pred, t.voted, t.logits, st->K, S);
 }
 
 // ---- cp_online_prepare: fold running-statistics BatchNorm into the layer behind it ------------------------------------

@@ -16,6 +16,10 @@ entries of include/cpnative.h (csrc/online.cuh):
 statistics live in the workspace, `calibrate()` sets them from a recording (AdaBN: the reference's default model, which the
 folded form cannot run), and every push can track the stream with rate alpha per window (0: frozen).
 
+`MultiStreamDecoder` decodes up to 256 streams through one model in one chain of launches per push (cp_online_multi_*,
+csrc/online_multi.cuh): the folded weights once, each stream's state and class table of its own, and every stream's outputs
+bit-identical to those of its own `OnlineDecoder`.
+
 The number of windows a push emits follows from sample counts alone (`windows_emitted`), so a push never waits for the device:
 its outputs are device tensors on torch's current stream.
 """
@@ -49,11 +53,113 @@ def windows_emitted(n_seen: int, n: int, phase: int = 0) -> int:
     return windows_before(n_seen + n, phase) - windows_before(n_seen, phase)
 
 
-def _engine_of(model_or_engine) -> Engine:
+def _engine_of(model_or_engine, who: str = "OnlineDecoder") -> Engine:
     e = getattr(model_or_engine, "engine", model_or_engine)
     if not isinstance(e, Engine):
-        raise TypeError("OnlineDecoder takes a contrastiveprosthetics_amd Model or Engine")
+        raise TypeError(f"{who} takes a contrastiveprosthetics_amd Model or Engine")
     return e
+
+
+def _check_settings(e: Engine, dtype, vote, phase, max_windows_per_push, who: str) -> str:
+    """The settings every online decoder checks before it allocates anything; returns the dtype name."""
+    if dtype is None:
+        dtype = {CP_F32: "f32", CP_BF16: "bf16", CP_FP8: "fp8"}[e.dtype]
+    if dtype == "fp8":
+        raise _lib.CpNativeError(f"{who} runs in 'f32' or 'bf16'; there is no 8-bit online path")
+    if dtype not in ("f32", "bf16"):
+        raise ValueError("dtype must be 'f32' or 'bf16'")
+    if e.specs["emg_net.last.0.weight"][0] != CP_D_E:
+        raise _lib.CpNativeError(f"{who} is built for d_e={CP_D_E}")
+    if not 1 <= int(vote) <= _lib.CP_ONLINE_MAX_VOTE:
+        raise ValueError(f"vote must lie in 1..{_lib.CP_ONLINE_MAX_VOTE}")
+    if not 0 <= int(phase) < STRIDE:
+        raise ValueError(f"phase must lie in 0..{STRIDE - 1}")
+    if not 1 <= int(max_windows_per_push) <= _lib.CP_ONLINE_MAX_WINDOWS:
+        raise ValueError(f"max_windows_per_push must lie in 1..{_lib.CP_ONLINE_MAX_WINDOWS}")
+    return dtype
+
+
+def _filter(b, a):
+    if b is None:
+        b, a = butter_bandpass()
+    b = np.asarray(b, dtype=np.float64).reshape(-1)
+    a = np.asarray(a, dtype=np.float64).reshape(-1)
+    if len(b) != len(a) or not 2 <= len(b) <= 17 or a[0] == 0.0:
+        raise ValueError("b and a: 2..17 coefficients each, a[0] != 0")
+    return b, a
+
+
+def _config(dtype: str, max_windows: int, vote: int, phase: int, b, a):
+    cfg = _lib.cp_online_config()
+    cfg.dtype = CP_F32 if dtype == "f32" else CP_BF16
+    cfg.max_windows = max_windows
+    cfg.vote = vote
+    cfg.phase = phase
+    cfg.n_coef = len(b)
+    for i in range(len(b)):
+        cfg.b[i], cfg.a[i] = float(b[i]), float(a[i])
+    return cfg
+
+
+def _channels(v, device) -> torch.Tensor:
+    t = torch.as_tensor(v, dtype=torch.float32).to(device).reshape(-1)
+    if t.numel() == 1:
+        t = t.expand(EMG_DIM)
+    if t.numel() != EMG_DIM:
+        raise ValueError("mean and std: one value or one per channel (12)")
+    return t
+
+
+def _check_count(k: int):
+    if k < 1:
+        raise ValueError("the class list is empty")
+    if k > MAX_CLASSES:
+        raise ValueError(f"at most {MAX_CLASSES} classes, got {k}")
+
+
+def _class_table(e: Engine, classes=None, glove=None, table=None, ids=None):
+    """The class table of `set_classes` (see OnlineDecoder.set_classes): (K, 16) f32 rows on the device, sorted by id, and the
+    sorted ids (K,) int64.  Raises before anything is enqueued on a decoder."""
+    if sum(x is not None for x in (classes, glove, table)) != 1:
+        raise ValueError("set_classes takes exactly one of classes, glove, table")
+    if glove is not None and e.adabn:
+        raise _lib.CpNativeError("glove class rows need a glove encoder with running statistics: on an AdaBN model its "
+                                 "batch statistics would come from a zero-padded group; pass classes= or table=")
+    if classes is not None:
+        cid = torch.as_tensor(np.asarray(classes, dtype=np.int64).reshape(-1))
+        _check_count(cid.numel())
+        if int(cid.min()) < 0 or int(cid.max()) >= CP_TASKS:
+            raise ValueError(f"class ids must lie in 0..{CP_TASKS - 1}")
+        ids_t = cid
+        rows = None
+    else:
+        src = glove if glove is not None else table
+        width = 20 if glove is not None else CP_D_E
+        src = torch.as_tensor(src, dtype=torch.float32)
+        if src.dim() != 2 or src.shape[1] != width:
+            raise ValueError(f"{'glove' if glove is not None else 'table'} must be (K, {width})")
+        _check_count(src.shape[0])
+        ids_t = torch.arange(src.shape[0]) if ids is None else torch.as_tensor(np.asarray(ids, dtype=np.int64).reshape(-1))
+        if ids_t.numel() != src.shape[0]:
+            raise ValueError("one id per row")
+        rows = src
+    if len(set(ids_t.tolist())) != ids_t.numel():
+        raise ValueError("class ids must be distinct")
+    device = e.device
+    order = torch.argsort(ids_t)
+    ids_t = ids_t[order]
+    if rows is None:
+        w, b = e.values.views["glove_net.easy.0.weight"], e.values.views["glove_net.easy.0.bias"]
+        tab = (w[:, ids_t.to(device)].t() + b).contiguous()
+    elif glove is not None:
+        k = rows.shape[0]
+        padded = torch.zeros((k + CP_TASKS - 1) // CP_TASKS * CP_TASKS, 20)     # the glove encoder takes whole groups of 41 rows
+        padded[:k] = rows[order]
+        zg = e.glove_forward(padded.to(device).reshape(1, -1, 20), training=False)
+        tab = zg[:k].contiguous()
+    else:
+        tab = rows[order].to(device).contiguous()
+    return tab.to(torch.float32).contiguous(), ids_t
 
 
 class OnlineDecoder:
@@ -81,28 +187,10 @@ class OnlineDecoder:
                                      "(adapt= builds the adaptive form, which calibrates them)")
         if adapt is not None and not 0.0 <= float(adapt) < 1.0:
             raise ValueError("adapt (alpha) must lie in [0, 1)")
-        if dtype is None:
-            dtype = {CP_F32: "f32", CP_BF16: "bf16", CP_FP8: "fp8"}[e.dtype]
-        if dtype == "fp8":
-            raise _lib.CpNativeError("OnlineDecoder runs in 'f32' or 'bf16'; there is no 8-bit online path")
-        if dtype not in ("f32", "bf16"):
-            raise ValueError("dtype must be 'f32' or 'bf16'")
-        if e.specs["emg_net.last.0.weight"][0] != CP_D_E:
-            raise _lib.CpNativeError(f"OnlineDecoder is built for d_e={CP_D_E}")
-        if not 1 <= int(vote) <= _lib.CP_ONLINE_MAX_VOTE:
-            raise ValueError(f"vote must lie in 1..{_lib.CP_ONLINE_MAX_VOTE}")
-        if not 0 <= int(phase) < STRIDE:
-            raise ValueError(f"phase must lie in 0..{STRIDE - 1}")
-        if not 1 <= int(max_windows_per_push) <= _lib.CP_ONLINE_MAX_WINDOWS:
-            raise ValueError(f"max_windows_per_push must lie in 1..{_lib.CP_ONLINE_MAX_WINDOWS}")
+        dtype = _check_settings(e, dtype, vote, phase, max_windows_per_push, "OnlineDecoder")
         if classes is not None:
             self._check_count(len(classes))
-        if b is None:
-            b, a = butter_bandpass()
-        b = np.asarray(b, dtype=np.float64).reshape(-1)
-        a = np.asarray(a, dtype=np.float64).reshape(-1)
-        if len(b) != len(a) or not 2 <= len(b) <= 17 or a[0] == 0.0:
-            raise ValueError("b and a: 2..17 coefficients each, a[0] != 0")
+        b, a = _filter(b, a)
         self.engine = e
         self.adapt = None if adapt is None else float(adapt)
         self.calibrated = adapt is None or not e.adabn     # the running statistics are a calibration
@@ -114,15 +202,7 @@ class OnlineDecoder:
         self.vote = int(vote)
         self.phase = int(phase)
         self.max_windows = int(max_windows_per_push)
-        cfg = _lib.cp_online_config()
-        cfg.dtype = CP_F32 if dtype == "f32" else CP_BF16
-        cfg.max_windows = self.max_windows
-        cfg.vote = self.vote
-        cfg.phase = self.phase
-        cfg.n_coef = len(b)
-        for i in range(len(b)):
-            cfg.b[i], cfg.a[i] = float(b[i]), float(a[i])
-        self._cfg = cfg
+        cfg = self._cfg = _config(dtype, self.max_windows, self.vote, self.phase, b, a)
         self.mean_std = torch.stack([self._channels(mean), self._channels(std)]).contiguous()
         nbytes = (self.lib.cp_online_workspace_bytes if adapt is None else self.lib.cp_online_adapt_workspace_bytes)(self.max_windows, cfg.dtype)
         self.ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
@@ -134,19 +214,11 @@ class OnlineDecoder:
 
     # ------------------------------------------------------------------ helpers
     def _channels(self, v) -> torch.Tensor:
-        t = torch.as_tensor(v, dtype=torch.float32).to(self.device).reshape(-1)
-        if t.numel() == 1:
-            t = t.expand(EMG_DIM)
-        if t.numel() != EMG_DIM:
-            raise ValueError("mean and std: one value or one per channel (12)")
-        return t
+        return _channels(v, self.device)
 
     @staticmethod
     def _check_count(k: int):
-        if k < 1:
-            raise ValueError("the class list is empty")
-        if k > MAX_CLASSES:
-            raise ValueError(f"at most {MAX_CLASSES} classes, got {k}")
+        _check_count(k)
 
     def _stream(self) -> int:
         return torch.cuda.current_stream(self.device).cuda_stream
@@ -180,47 +252,9 @@ class OnlineDecoder:
         table: (K, 16) class embeddings, ids default 0..K-1.
         Rows are L2-normalised once, here.  Outputs report ids; ties go to the smallest id.  Empties the vote ring and keeps the
         filter state."""
-        if sum(x is not None for x in (classes, glove, table)) != 1:
-            raise ValueError("set_classes takes exactly one of classes, glove, table")
-        e = self.engine
-        if glove is not None and e.adabn:
-            raise _lib.CpNativeError("glove class rows need a glove encoder with running statistics: on an AdaBN model its "
-                                     "batch statistics would come from a zero-padded group; pass classes= or table=")
-        if classes is not None:
-            cid = torch.as_tensor(np.asarray(classes, dtype=np.int64).reshape(-1))
-            self._check_count(cid.numel())
-            if int(cid.min()) < 0 or int(cid.max()) >= CP_TASKS:
-                raise ValueError(f"class ids must lie in 0..{CP_TASKS - 1}")
-            ids_t = cid
-            rows = None
-        else:
-            src = glove if glove is not None else table
-            width = 20 if glove is not None else CP_D_E
-            src = torch.as_tensor(src, dtype=torch.float32)
-            if src.dim() != 2 or src.shape[1] != width:
-                raise ValueError(f"{'glove' if glove is not None else 'table'} must be (K, {width})")
-            self._check_count(src.shape[0])
-            ids_t = torch.arange(src.shape[0]) if ids is None else torch.as_tensor(np.asarray(ids, dtype=np.int64).reshape(-1))
-            if ids_t.numel() != src.shape[0]:
-                raise ValueError("one id per row")
-            rows = src
-        if len(set(ids_t.tolist())) != ids_t.numel():
-            raise ValueError("class ids must be distinct")
-        order = torch.argsort(ids_t)
-        ids_t = ids_t[order]
-        if rows is None:
-            w, b = e.values.views["glove_net.easy.0.weight"], e.values.views["glove_net.easy.0.bias"]
-            tab = (w[:, ids_t.to(self.device)].t() + b).contiguous()
-        elif glove is not None:
-            k = rows.shape[0]
-            padded = torch.zeros((k + CP_TASKS - 1) // CP_TASKS * CP_TASKS, 20)     # the glove encoder takes whole groups of 41 rows
-            padded[:k] = rows[order]
-            zg = e.glove_forward(padded.to(self.device).reshape(1, -1, 20), training=False)
-            tab = zg[:k].contiguous()
-        else:
-            tab = rows[order].to(self.device).contiguous()
+        tab, ids_t = _class_table(self.engine, classes, glove, table, ids)
         self._source = (classes, glove, table, ids)
-        self._table = tab.to(torch.float32).contiguous()
+        self._table = tab
         self.class_ids = ids_t.to(torch.int32)
         self._ids_dev = self.class_ids.to(self.device)
         _lib.check(self.lib.cp_online_set_classes(C.byref(self._cfg), *self._ws(), self._table.data_ptr(), self._ids_dev.data_ptr(),
@@ -318,3 +352,251 @@ class OnlineDecoder:
         _lib.check(self.lib.cp_online_adapt_statistics(C.byref(self._cfg), *self._ws(), out.data_ptr(), self._stream()),
                    "cp_online_adapt_statistics")
         return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# many streams: one model, one chain of launches per push (cp_online_multi_*, csrc/online_multi.cuh)
+# ---------------------------------------------------------------------------------------------------------------------------
+MAX_STREAMS = _lib.CP_ONLINE_MULTI_MAX_STREAMS
+DEFAULT_MAX_ROWS = 4096
+
+
+def _windows_before_np(n, phase: int) -> np.ndarray:
+    return np.maximum(0, (np.asarray(n, dtype=np.int64) - phase - 2 * WINDOW_EDGE - 1 + STRIDE) // STRIDE)
+
+
+def packed_rows(n_seen, counts, phase: int = 0):
+    """Where a multi-stream push packs each stream's windows: (row0, m), int64 arrays over streams, with m[s] =
+    windows_emitted(n_seen[s], counts[s], phase) and row0 the exclusive prefix sum of m (include/cpnative.h)."""
+    seen = np.asarray(n_seen, dtype=np.int64)
+    m = _windows_before_np(seen + np.asarray(counts, dtype=np.int64), phase) - _windows_before_np(seen, phase)
+    row0 = np.zeros_like(m)
+    np.cumsum(m[:-1], out=row0[1:])
+    return row0, m
+
+
+def plan_push(n_seen, counts, phase: int, max_windows: int, max_rows: int):
+    """Split a push of counts[s] samples per stream into rounds that each emit at most `max_windows` windows per stream and
+    `max_rows` windows in all: a list of int64 arrays (samples per stream), whose sum per stream is counts[s].  Every stream's
+    samples keep their order; a stream's outputs do not depend on how its samples are chunked."""
+    seen = np.array(n_seen, dtype=np.int64)
+    left = np.array(counts, dtype=np.int64)
+    rounds = []
+    while left.any():
+        take = np.minimum(left, STRIDE * max_windows)                  # 20 W samples complete at most W windows
+        _, m = packed_rows(seen, take, phase)
+        if m.sum() > max_rows:
+            rows = 0
+            for s in np.nonzero(take)[0]:
+                k = max_rows - rows
+                if m[s] > k:                                            # the most samples that complete k windows
+                    first = int(_windows_before_np(seen[s], phase))
+                    take[s] = min(take[s], STRIDE * (first + k + 1) + phase - 2 * WINDOW_EDGE - seen[s])
+                    m[s] = windows_emitted(int(seen[s]), int(take[s]), phase)
+                rows += int(m[s])
+        rounds.append(take)
+        seen += take
+        left -= take
+    return rounds
+
+
+class MultiStreamDecoder:
+    """`OnlineDecoder` for n_streams (1..256) streams at once: one model, one set of folded weights, one dtype, vote length,
+    phase, filter and normalisation for all; per stream its own filter and RMS state, sample count, vote ring and class table.
+    A push is one chain of ten launches for all streams, and every stream's pred, voted, logits and windows equal bit for bit
+    those of an `OnlineDecoder` with the same settings and class table fed the same chunks of that stream alone.
+
+    max_windows_per_push bounds the windows of one stream per launch chain, max_rows (default min(n_streams *
+    max_windows_per_push, 4096)) the windows of all streams; larger pushes are split on the host.  Stock BatchNorm only: the
+    adaptive form (adapt=) and AdaBN models are refused, as is fp8."""
+
+    def __init__(self, model_or_engine, mean, std, n_streams: int, vote: int = VOTE, dtype: Optional[str] = None, phase: int = 0,
+                 max_windows_per_push: int = 256, max_rows: Optional[int] = None, b=None, a=None, adapt: Optional[float] = None):
+        e = _engine_of(model_or_engine, "MultiStreamDecoder")
+        if adapt is not None:
+            raise _lib.CpNativeError("MultiStreamDecoder has no adaptive form (adapt=): decode an adapting stream with "
+                                     "OnlineDecoder(..., adapt=alpha)")
+        if e.adabn:
+            raise _lib.CpNativeError("MultiStreamDecoder needs stock BatchNorm with running statistics: an AdaBN model normalises "
+                                     "with the statistics of its batch (OnlineDecoder(..., adapt=alpha) calibrates them)")
+        dtype = _check_settings(e, dtype, vote, phase, max_windows_per_push, "MultiStreamDecoder")
+        if not 1 <= int(n_streams) <= MAX_STREAMS:
+            raise ValueError(f"n_streams must lie in 1..{MAX_STREAMS}")
+        if max_rows is None:
+            max_rows = max(int(max_windows_per_push), min(int(n_streams) * int(max_windows_per_push), DEFAULT_MAX_ROWS))
+        if not 1 <= int(max_rows) <= _lib.CP_ONLINE_MULTI_MAX_ROWS:
+            raise ValueError(f"max_rows must lie in 1..{_lib.CP_ONLINE_MULTI_MAX_ROWS}")
+        b, a = _filter(b, a)
+        self.engine = e
+        self.lib = _lib.load()
+        self.device = e.device
+        self.dtype = dtype
+        self.vote = int(vote)
+        self.phase = int(phase)
+        self.max_windows = int(max_windows_per_push)
+        self.max_rows = int(max_rows)
+        self.n_streams = int(n_streams)
+        self._cfg = _config(dtype, self.max_windows, self.vote, self.phase, b, a)
+        self.mean_std = torch.stack([_channels(mean, self.device), _channels(std, self.device)]).contiguous()
+        nbytes = self.lib.cp_online_multi_workspace_bytes(self.n_streams, self.max_rows, self._cfg.dtype)
+        self.ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        self._seen = np.zeros(self.n_streams, dtype=np.int64)
+        self.class_ids = [None] * self.n_streams           # per stream: sorted ids (K,) int32, or None before set_classes
+        self._source = [None] * self.n_streams
+        self._tables = [None] * self.n_streams             # kept alive until the next set_classes of the stream
+        self._has_table = np.zeros(self.n_streams, dtype=bool)
+        self._k = [0] * self.n_streams                     # classes per stream
+        self._counts_cache = None
+        self.refresh()
+
+    # ------------------------------------------------------------------ helpers
+    def _stream(self) -> int:
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _args(self):
+        return (C.byref(self._cfg), self.n_streams, self.max_rows, self.ws.data_ptr(), self.ws.numel())
+
+    def _index(self, stream) -> int:
+        if isinstance(stream, bool) or not isinstance(stream, (int, np.integer)) or not 0 <= int(stream) < self.n_streams:
+            raise IndexError(f"stream index must be an int in 0..{self.n_streams - 1}, got {stream!r}")
+        return int(stream)
+
+    @property
+    def n_seen(self) -> np.ndarray:
+        """samples pushed into each stream since its last reset"""
+        return self._seen.copy()
+
+    # ------------------------------------------------------------------ API
+    def refresh(self):
+        """Fold the model's current weights and running statistics again (as OnlineDecoder.refresh); the class tables that come
+        from the model (classes=, glove=) are derived again, which empties those streams' vote rings."""
+        e = self.engine
+        _lib.check(self.lib.cp_online_multi_prepare(C.byref(self._cfg), self.n_streams, self.max_rows, C.byref(e._p), C.byref(e._bn),
+                                                    C.c_float(1e-5), self.ws.data_ptr(), self.ws.numel(), self._stream()),
+                   "cp_online_multi_prepare")
+        for s, src in enumerate(self._source):
+            if src is not None and src[2] is None:
+                classes, glove, _, ids = src
+                self.set_classes(s, classes, glove=glove, ids=ids)
+
+    def set_classes(self, stream: int, classes=None, *, glove=None, table=None, ids=None):
+        """The class table of one stream, as OnlineDecoder.set_classes: classes= (one-hot ids), glove= (K, 20) or table= (K, 16),
+        ids.  Empties that stream's vote ring; its filter state and every other stream stay."""
+        s = self._index(stream)
+        tab, ids_t = _class_table(self.engine, classes, glove, table, ids)
+        ids32 = ids_t.to(torch.int32)
+        ids_dev = ids32.to(self.device)
+        _lib.check(self.lib.cp_online_multi_set_classes(*self._args(), s, tab.data_ptr(), ids_dev.data_ptr(), int(ids32.numel()),
+                                                        self._stream()), "cp_online_multi_set_classes")
+        self._source[s] = (classes, glove, table, ids)
+        self._tables[s] = (tab, ids_dev)
+        self.class_ids[s] = ids32
+        self._has_table[s] = True
+        self._k[s] = int(ids32.numel())
+
+    def reset(self, streams=None):
+        """Start new streams: filter, RMS history, sample count and vote ring of the listed streams (default: all) to zero;
+        their classes, the weights and the other streams stay."""
+        if streams is None:
+            _lib.check(self.lib.cp_online_multi_reset(*self._args(), -1, self._stream()), "cp_online_multi_reset")
+            self._seen[:] = 0
+            return
+        idx = sorted({self._index(s) for s in streams})
+        for s in idx:
+            _lib.check(self.lib.cp_online_multi_reset(*self._args(), s, self._stream()), "cp_online_multi_reset")
+            self._seen[s] = 0
+
+    def push(self, chunks, return_logits: bool = False, return_windows: bool = False):
+        """chunks: n_streams entries, each None or an (n_s, 12) float32 GPU tensor, the next samples of stream s.  Returns one
+        tuple per stream, (pred, voted[, logits][, windows]) for its windows_emitted(n_seen[s], n_s, phase) windows: views into
+        the packed outputs (pred, voted int32 class ids, logits (M_s, K_s) f32, windows (M_s, 12) f32)."""
+        if isinstance(chunks, torch.Tensor) or len(chunks) != self.n_streams:
+            raise ValueError(f"chunks must be a sequence of {self.n_streams} entries (None or (n, 12) tensors)")
+        counts, parts = [], []
+        for c in chunks:
+            if c is None:
+                counts.append(0)
+                continue
+            self._check_raw(c, "each chunk")
+            counts.append(int(c.shape[0]))
+            if c.shape[0]:
+                parts.append(c)
+        if not parts:
+            raw = torch.empty(0, EMG_DIM, dtype=torch.float32, device=self.device)
+        elif len(parts) == 1:
+            raw = parts[0].contiguous()
+        else:
+            raw = torch.cat(parts)
+        return self._push(raw, np.asarray(counts, dtype=np.int64), return_logits, return_windows)
+
+    def push_packed(self, raw: torch.Tensor, counts, return_logits: bool = False, return_windows: bool = False):
+        """As push, for samples already packed in stream order: raw (sum(counts), 12) float32 on the GPU, counts[s] >= 0 the
+        samples of stream s."""
+        self._check_raw(raw, "raw")
+        cnt = np.asarray(counts, dtype=np.int64).reshape(-1)
+        if cnt.shape[0] != self.n_streams:
+            raise ValueError(f"counts must hold {self.n_streams} entries")
+        if (cnt < 0).any():
+            raise ValueError("counts must be >= 0")
+        if int(cnt.sum()) != raw.shape[0]:
+            raise ValueError(f"counts sum to {int(cnt.sum())} samples, raw holds {raw.shape[0]}")
+        return self._push(raw.contiguous(), cnt, return_logits, return_windows)
+
+    @staticmethod
+    def _check_raw(t, what: str):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != torch.float32 or t.dim() != 2 \
+                or t.shape[1] != EMG_DIM:
+            raise ValueError(f"{what} must be an (n, 12) float32 tensor on the GPU")
+
+    def _counts_on_device(self, take: np.ndarray) -> torch.Tensor:
+        """take as int32 on the device.  A stream of pushes usually repeats its counts: the last device copy is reused (it is
+        only ever read), else a fresh one goes through pinned memory, whose block torch's host allocator keeps until the copy
+        has run."""
+        key = (take.tobytes(), self._stream())
+        if self._counts_cache is not None and self._counts_cache[0] == key:
+            return self._counts_cache[1]
+        dev = torch.from_numpy(take.astype(np.int32)).pin_memory().to(self.device, non_blocking=True)
+        self._counts_cache = (key, dev)
+        return dev
+
+    def _push(self, raw: torch.Tensor, counts: np.ndarray, return_logits: bool, return_windows: bool):
+        if ((counts > 0) & ~self._has_table).any():
+            s = int(np.nonzero((counts > 0) & ~self._has_table)[0][0])
+            raise _lib.CpNativeError(f"stream {s} has samples but no class table: set_classes({s}, ...) first")
+        row0, m = packed_rows(self._seen, counts, self.phase)
+        if m.max() <= self.max_windows and m.sum() <= self.max_rows:
+            rounds = [(counts, raw, m)]                        # the usual case: one chain of launches
+        else:
+            start = np.zeros_like(counts)                      # each stream's first sample in raw
+            np.cumsum(counts[:-1], out=start[1:])
+            done = np.zeros_like(counts)
+            seen = self._seen.copy()
+            rounds = []
+            for take in plan_push(self._seen, counts, self.phase, self.max_windows, self.max_rows):
+                piece = torch.cat([raw[start[s] + done[s]:start[s] + done[s] + take[s]] for s in np.nonzero(take)[0]])
+                rounds.append((take, piece, packed_rows(seen, take, self.phase)[1]))
+                seen += take
+                done += take
+        outs = []                                              # per round: per-stream (pred, voted, logits, windows) views
+        for take, piece, m in rounds:
+            R = int(m.sum())
+            pv = torch.empty(2, max(R, 1), dtype=torch.int32, device=self.device)     # (an empty tensor's pointer is NULL)
+            logits = torch.empty(R, MAX_CLASSES, dtype=torch.float32, device=self.device) if return_logits else None
+            wins = torch.empty(R, EMG_DIM, dtype=torch.float32, device=self.device) if return_windows else None
+            if piece.shape[0]:
+                _lib.check(self.lib.cp_online_multi_push(*self._args(), piece.data_ptr(), self._counts_on_device(take).data_ptr(),
+                                                         int(piece.shape[0]), R, self.mean_std.data_ptr(), pv[0].data_ptr(),
+                                                         pv[1].data_ptr(), logits.data_ptr() if logits is not None else None,
+                                                         wins.data_ptr() if wins is not None else None, self._stream()),
+                           "cp_online_multi_push")
+            self._seen += take
+            ml = m.tolist()
+            cols = [pv[0, :R].split(ml), pv[1, :R].split(ml)]
+            if return_logits:
+                cols.append([x[:, :k] for x, k in zip(logits.split(ml), self._k)])
+            if return_windows:
+                cols.append(wins.split(ml))
+            outs.append(list(zip(*cols)))
+        if len(outs) == 1:
+            return outs[0]
+        return [tuple(torch.cat([o[s][i] for o in outs]) for i in range(len(outs[0][s]))) for s in range(self.n_streams)]

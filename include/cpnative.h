@@ -483,6 +483,35 @@ int cp_online_adapt_push(const cp_online_config* cfg, void* ws, size_t ws_bytes,
 /* out (9, 2, 512) float64 on the device: mu, v of each BN (the conv BNs fill channels 0..63, the rest is zero) */
 int cp_online_adapt_statistics(const cp_online_config* cfg, void* ws, size_t ws_bytes, double* out, void* stream);
 
+/* ---- multi-stream online decoding: n_streams <= 256 streams, one model, one chain of launches per push -----------------
+ * The decoder of cp_online_* with the folded weights stored once and one state (filter, RMS history, sample count, vote ring,
+ * class table) per stream.  All streams share cfg (dtype, vote, phase, IIR; cfg.max_windows bounds the windows ONE stream
+ * emits in a push) and mean_std.  Every call takes n_streams and max_rows, the windows one push may emit over all streams
+ * (1..65536), as the workspace was sized with.  A push takes the samples of all streams packed in stream order: raw
+ * (total_samples, 12), counts (n_streams) int32 on the device, counts[s] >= 0 samples of stream s.  Stream s emits
+ *     M_s = c(n_seen_s + counts[s]) - c(n_seen_s)
+ * windows (c as for cp_online_push), total_windows = sum M_s <= max_rows; its outputs are the rows row0_s = M_0 + .. + M_{s-1}
+ * .. row0_s + M_s - 1 of pred, voted (total_windows) int32, logits (total_windows, 64) f32 (columns >= the stream's class
+ * count are not written) and windows (total_windows, 12), and equal bit for bit those of cp_online_push on a workspace of that
+ * stream alone fed the same chunks.  The caller sizes the outputs from its own sample counts: nothing is read back.  A stream
+ * whose counts disagree with total_samples, total_windows or cfg.max_windows is left untouched (its outputs are not written).
+ * A push is ten launches for any n_streams (front end, conv2, fc1..fc7, tail); none when total_samples is 0. */
+#define CP_ONLINE_MULTI_MAX_STREAMS 256
+#define CP_ONLINE_MULTI_MAX_ROWS 65536
+size_t cp_online_multi_workspace_bytes(int32_t n_streams, int32_t max_rows, int32_t dtype);
+/* as cp_online_prepare: folds the weights once for all streams */
+int cp_online_multi_prepare(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, const cp_params* p,
+                            const cp_bn_buffers* bn, float bn_eps, void* ws, size_t ws_bytes, void* stream);
+/* as cp_online_set_classes, for stream `index` (0..n_streams-1) */
+int cp_online_multi_set_classes(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                int32_t index, const float* table, const int32_t* ids, int32_t n_classes, void* stream);
+/* as cp_online_reset, for stream `index`, or every stream for index -1 */
+int cp_online_multi_reset(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                          int32_t index, void* stream);
+int cp_online_multi_push(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                         const float* raw, const int32_t* counts, int64_t total_samples, int32_t total_windows,
+                         const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,11 +7,14 @@ For pushes of 20 and 500 raw samples (1 and 25 windows) in f32 and bf16:
                argmax over the subset
 With --adapt the adaptive form (OnlineDecoder(..., adapt=0.01), csrc/online_adapt.cuh) is timed next to the folded decoder
 instead of the composition, plus the wall time of calibrate() on 6,000 windows (60 s of stream).
+With --streams the multi-stream decoder (MultiStreamDecoder.push, csrc/online_multi.cuh) is timed against S single-stream
+decoders pushing one after another, for S in 1, 8, 64, 256 streams of 1 and 25 windows each.
 Each push is timed from the host with a synchronisation behind it (the latency a control loop sees); kernels per push are
 counted with torch.profiler over a few pushes.  One JSON line per case, and a table with --out.
 
     python tools/online_bench.py --iters 200 --out profiles/online_latency.txt
     python tools/online_bench.py --adapt --iters 200 --out profiles/online_adapt_latency.txt
+    python tools/online_bench.py --streams --iters 50 --out profiles/online_multi_latency.txt
 """
 import argparse
 import json
@@ -24,7 +27,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from contrastiveprosthetics_amd import OnlineDecoder                      # noqa: E402
+from contrastiveprosthetics_amd import MultiStreamDecoder, OnlineDecoder  # noqa: E402
 from contrastiveprosthetics_amd.engine import Engine                       # noqa: E402
 from contrastiveprosthetics_amd.preprocess import normalize_, preprocess_segments   # noqa: E402
 
@@ -61,6 +64,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--out", default=None)
     ap.add_argument("--adapt", action="store_true", help="adaptive form against the folded decoder, and calibrate()")
+    ap.add_argument("--streams", action="store_true", help="multi-stream decoder against S single-stream decoders in turn")
+    ap.add_argument("--counts", default="1,8,64,256", help="--streams: stream counts")
     a = ap.parse_args()
     torch.manual_seed(0)
     e = Engine(adabn=False, dtype="f32", device="cuda:0")
@@ -73,6 +78,8 @@ def main():
     rows = []
     if a.adapt:
         return adapt_main(a, e, stream, mean, std, classes)
+    if a.streams:
+        return streams_main(a, e, stream, mean, std, classes)
     for dtype in ("f32", "bf16"):
         e.dtype = 0 if dtype == "f32" else 1
         e._ws = None                                           # the engine's workspace is carved per dtype
@@ -171,6 +178,56 @@ def adapt_main(a, e, stream, mean, std, classes):
                     "# part of it that makes the windows with the offline transform (preprocess_segments + normalize_)\n")
             for r in cal:
                 f.write(f"{r['kind']:<12} {r['dtype']:<5} {'':>7} {r['windows']:>7} {r['median_ms']:>8.2f} ms\n")
+
+
+def streams_main(a, e, stream, mean, std, classes):
+    rows = []
+    counts = [int(x) for x in a.counts.split(",")]
+    for dtype in ("f32", "bf16"):
+        for S in counts:
+            for n in (20, 500):
+                m = n // 20
+                multi = MultiStreamDecoder(e, mean, std, S, dtype=dtype, max_rows=S * m)
+                for s in range(S):
+                    multi.set_classes(s, classes=classes)
+                singles = [OnlineDecoder(e, mean, std, classes=classes, dtype=dtype) for _ in range(S)]
+                pos = [0]
+                span = stream.shape[0] - S * n
+
+                def batched():
+                    base = pos[0] % span
+                    pos[0] += S * n
+                    return multi.push_packed(stream[base:base + S * n], [n] * S)
+
+                def sequential():
+                    base = pos[0] % span
+                    pos[0] += S * n
+                    return [d.push(stream[base + i * n:base + (i + 1) * n]) for i, d in enumerate(singles)]
+
+                res = {}
+                for name, fn in (("batched", batched), ("sequential", sequential)):
+                    med, p90 = time_pushes(fn, a.iters, a.warmup)
+                    k = count_kernels(fn, pushes=2)
+                    res[name] = med
+                    r = dict(kind=name, dtype=dtype, streams=S, samples=n, windows=m, median_us=round(med, 1), p90_us=round(p90, 1),
+                             kernels_per_push=k)
+                    print(json.dumps(r), flush=True)
+                    rows.append(r)
+                rows[-2]["speedup"] = rows[-1]["speedup"] = round(res["sequential"] / res["batched"], 2)
+                del multi, singles
+                torch.cuda.empty_cache()
+    if a.out:
+        dev = torch.cuda.get_device_name(0)
+        with open(a.out, "w") as f:
+            f.write(f"# tools/online_bench.py --streams --counts {a.counts} --iters {a.iters} --warmup {a.warmup} on {dev}\n")
+            f.write("# one push of S streams x `windows` windows each: batched = MultiStreamDecoder.push_packed, sequential = S\n"
+                    "# OnlineDecoder.push one after another; host-synchronised wall time (median, p90), kernels per push\n"
+                    "# (torch.profiler: library kernels plus torch's own, e.g. the copy of the counts), speedup = sequential / batched\n")
+            f.write(f"{'kind':<11} {'dtype':<5} {'streams':>7} {'samples':>7} {'windows':>7} {'median_us':>10} {'p90_us':>9} "
+                    f"{'kernels':>8} {'speedup':>8}\n")
+            for r in rows:
+                f.write(f"{r['kind']:<11} {r['dtype']:<5} {r['streams']:>7} {r['samples']:>7} {r['windows']:>7} {r['median_us']:>10.1f} "
+                        f"{r['p90_us']:>9.1f} {r['kernels_per_push']:>8.1f} {r['speedup']:>8.2f}\n")
 
 
 if __name__ == "__main__":
