@@ -145,6 +145,19 @@ SYMBOLS = {
     "cp_online_multi_reset": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, C.c_int32, _fp]),
     "cp_online_multi_push": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, _fp, _fp, C.c_int64, C.c_int32,
                                        _fp, _fp, _fp, _fp, _fp, _fp]),
+    "cp_online_multi_adapt_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "cp_online_multi_adapt_prepare": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _P(cp_params), _P(cp_bn_buffers),
+                                                C.c_float, _P(C.c_double), _fp, C.c_size_t, _fp]),
+    "cp_online_multi_adapt_set_alpha": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, C.c_int32,
+                                                  C.c_double, _fp]),
+    "cp_online_multi_adapt_reset_statistics": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, C.c_int32,
+                                                         _P(cp_bn_buffers), _fp]),
+    "cp_online_multi_adapt_calibrate": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, C.c_int32, _fp,
+                                                  C.c_int64, _fp, C.c_size_t, _fp]),
+    "cp_online_multi_adapt_push": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, _fp, _fp, C.c_int64,
+                                             C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "cp_online_multi_adapt_statistics": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, C.c_int32, _fp,
+                                                   _fp]),
 }
 
 KERNEL_KINDS = ["gather", "prep", "conv1_fwd", "bn_finalize", "conv2_fwd", "fold", "fc_fwd", "dropout", "proj_fwd",

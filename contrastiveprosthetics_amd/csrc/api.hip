@@ -23,6 +23,7 @@
 #include "online.cuh"
 #include "online_adapt.cuh"
 #include "online_multi.cuh"
+#include "online_multi_adapt.cuh"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* what) {
@@ -2958,4 +2959,270 @@ extern "C" int cp_online_multi_push(const cp_online_config* cfg, int32_t n_strea
                                            logits, windows, (hipStream_t)stream);
     return online_multi_push_t<float>(cfg, n_streams, base, w, raw, counts, total_samples, total_windows, mean_std, pred, voted, logits,
                                       windows, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------
+// adaptive multi-stream online decoding (csrc/online_multi_adapt.cuh): the unfolded weights once; per stream its OlState, head
+// and float64 statistics; rows of all streams packed
+// ---------------------------------------------------------------------------------------
+struct OlamWS {
+    OlaWS w;                 // w.state, w.head, w.stats: stream 0's; w.X, C1, R2, H0, H1: max_rows rows
+    size_t meta;
+};
+// Begins as the folded multi-stream carve (n_streams states, then their OlmMeta), so cp_online_multi_set_classes and
+// cp_online_multi_reset take this workspace
+static OlamWS olam_carve(int64_t max_rows, int dtype, int n_streams) {
+    const size_t es = dtype == CP_BF16 ? 2 : 4;
+    const size_t rows = (size_t)((max_rows + 15) / 16 * 16);
+    OlamWS m{};
+    OlaWS& w = m.w;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t r = o; o = align256(o + bytes); return r; };
+    w.state = take((size_t)n_streams * sizeof(OlState));
+    m.meta = take((size_t)n_streams * sizeof(OlmMeta));
+    w.head = take((size_t)n_streams * sizeof(OlaHead));
+    w.stats = take((size_t)n_streams * OLAM_STATS * 8);
+    w.c1w = take(64 * 3 * 4);
+    w.c1b = take(64 * 4);
+    w.c2w = take(64 * OL_CONV_K * es);
+    w.c2b = take(64 * 4);
+    for (int i = 0; i < CP_N_FC; ++i) {
+        w.fcw[i] = take((size_t)512 * fcK(i) * es);
+        w.fcb[i] = take(512 * 4);
+    }
+    w.pw = take(CP_D_E * 512 * es);
+    w.pb = take(CP_D_E * 4);                              // zeros, as in the single-stream adaptive carve
+    w.gb = take((size_t)CP_N_BN * 2 * OLA_F * 4);
+    w.X = take(rows * OL_C * 4);
+    w.C1 = take(rows * OL_C * OL_CONV_K * es);
+    w.R2 = take(rows * OL_C * 64 * 4);
+    w.H0 = take(rows * 768 * es);
+    w.H1 = take(rows * 512 * es);
+    w.total = o;
+    return m;
+}
+
+// the single-stream view of stream s: its state, head and statistics, the shared weights and buffers
+static OlaWS olam_stream(const OlamWS& m, int s) {
+    OlaWS w = m.w;
+    w.state += (size_t)s * sizeof(OlState);
+    w.head += (size_t)s * sizeof(OlaHead);
+    w.stats += (size_t)s * OLAM_STATS * 8;
+    return w;
+}
+
+static int olam_check(const cp_online_config* c, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes, OlamWS* out) {
+    if (n_streams < 1 || n_streams > CP_ONLINE_MULTI_MAX_STREAMS) return fail(CP_ERR_ARG, "cp_online_multi_adapt: n_streams outside 1..256");
+    if (max_rows < 1 || max_rows > CP_ONLINE_MULTI_MAX_ROWS) return fail(CP_ERR_ARG, "cp_online_multi_adapt: max_rows outside 1..65536");
+    if (int e = ol_check_config(c, ws)) return e;
+    *out = olam_carve(max_rows, c->dtype, n_streams);
+    if (ws_bytes < out->w.total) return fail(CP_ERR_WORKSPACE, "cp_online_multi_adapt: workspace too small");
+    return 0;
+}
+
+static int olam_index(int32_t index, int32_t n_streams, const char* who) {
+    if (index < 0 || index >= n_streams) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "%s: stream index outside 0..n_streams-1", who);
+        return fail(CP_ERR_ARG, msg);
+    }
+    return 0;
+}
+
+extern "C" size_t cp_online_multi_adapt_workspace_bytes(int32_t n_streams, int32_t max_rows, int32_t dtype) {
+    if (n_streams < 1) n_streams = 1;
+    if (max_rows < 1) max_rows = 1;
+    return olam_carve(max_rows, dtype, n_streams).w.total;
+}
+
+template <typename T>
+static int online_multi_adapt_prepare_t(const cp_params* p, const cp_bn_buffers* bn, float eps, const double* alpha, int n_streams,
+                                        unsigned char* base, const OlamWS& m, hipStream_t st) {
+    const OlaWS& w = m.w;
+    OlamInitArgs ia{};
+    for (int l = 0; l < CP_N_BN; ++l) {
+        ia.g[l] = p->bn_g[l]; ia.beta[l] = p->bn_b[l];
+        ia.mean[l] = bn ? bn->running_mean[l] : nullptr; ia.var[l] = bn ? bn->running_var[l] : nullptr;
+    }
+    ia.c1w = p->conv1_w; ia.c1b = p->conv1_b; ia.gb = (float*)(base + w.gb); ia.stats = (double*)(base + w.stats);
+    ia.c1w_d = (float*)(base + w.c1w); ia.c1b_d = (float*)(base + w.c1b); ia.heads = (OlaHead*)(base + w.head);
+    ia.eps = eps; ia.first = 0; ia.zero = 0; ia.set_alpha = alpha != nullptr;
+    for (int s = 0; alpha && s < n_streams; ++s) ia.alpha[s] = alpha[s];
+    hipLaunchKernelGGL(olam_init_kernel, dim3(CP_N_BN, n_streams), dim3(512), 0, st, ia);
+    CKL("olam_init_kernel");
+    OlaCopyArgs f{};                                      // as online_adapt_prepare_t
+    f.W = p->conv2_w; f.b = p->conv2_b; f.Wd = base + w.c2w; f.bd = (float*)(base + w.c2b); f.K = OL_CONV_K; f.mode = 2;
+    hipLaunchKernelGGL((ola_copy_kernel<T>), dim3(64), dim3(256), 0, st, f);
+    CKL("ola_copy_kernel");
+    for (int i = 0; i < CP_N_FC; ++i) {
+        f.W = p->fc_w[i]; f.b = p->fc_b[i]; f.Wd = base + w.fcw[i]; f.bd = (float*)(base + w.fcb[i]); f.K = fcK(i); f.mode = i == 0 ? 1 : 0;
+        hipLaunchKernelGGL((ola_copy_kernel<T>), dim3(512), dim3(256), 0, st, f);
+        CKL("ola_copy_kernel");
+    }
+    f.W = p->last_w; f.b = nullptr; f.Wd = base + w.pw; f.bd = (float*)(base + w.pb); f.K = 512; f.mode = 0;
+    hipLaunchKernelGGL((ola_copy_kernel<T>), dim3(CP_D_E), dim3(256), 0, st, f);
+    CKL("ola_copy_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_multi_adapt_prepare(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, const cp_params* p,
+                                             const cp_bn_buffers* bn, float bn_eps, const double* alpha, void* ws, size_t ws_bytes,
+                                             void* stream) {
+    if (!(bn_eps > 0.f)) return fail(CP_ERR_ARG, "cp_online_multi_adapt_prepare: bn_eps must be positive");
+    OlamWS m;
+    if (int e = olam_check(cfg, n_streams, max_rows, ws, ws_bytes, &m)) return e;
+    for (int s = 0; alpha && s < n_streams; ++s)
+        if (!(alpha[s] >= 0.0 && alpha[s] < 1.0)) return fail(CP_ERR_ARG, "cp_online_multi_adapt_prepare: alpha outside [0, 1)");
+    if (!p || !p->conv1_w || !p->conv1_b || !p->conv2_w || !p->conv2_b || !p->last_w)
+        return fail(CP_ERR_ARG, "cp_online_multi_adapt_prepare: parameters");
+    for (int i = 0; i < CP_N_FC; ++i)
+        if (!p->fc_w[i] || !p->fc_b[i]) return fail(CP_ERR_ARG, "cp_online_multi_adapt_prepare: parameters");
+    for (int l = 0; l < CP_N_BN; ++l) {
+        if (!p->bn_g[l] || !p->bn_b[l]) return fail(CP_ERR_ARG, "cp_online_multi_adapt_prepare: parameters");
+        if (bn && (!bn->running_mean[l] || !bn->running_var[l])) return fail(CP_ERR_ARG, "cp_online_multi_adapt_prepare: running statistics");
+    }
+    unsigned char* base = (unsigned char*)ws;
+    if (cfg->dtype == CP_BF16) return online_multi_adapt_prepare_t<bf16_t>(p, bn, bn_eps, alpha, n_streams, base, m, (hipStream_t)stream);
+    return online_multi_adapt_prepare_t<float>(p, bn, bn_eps, alpha, n_streams, base, m, (hipStream_t)stream);
+}
+
+extern "C" int cp_online_multi_adapt_set_alpha(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
+                                               size_t ws_bytes, int32_t index, double alpha, void* stream) {
+    OlamWS m;
+    if (int e = olam_check(cfg, n_streams, max_rows, ws, ws_bytes, &m)) return e;
+    if (int e = olam_index(index, n_streams, "cp_online_multi_adapt_set_alpha")) return e;
+    if (!(alpha >= 0.0 && alpha < 1.0)) return fail(CP_ERR_ARG, "cp_online_multi_adapt_set_alpha: alpha outside [0, 1)");
+    hipLaunchKernelGGL(olam_set_alpha_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream,
+                       (OlaHead*)((unsigned char*)ws + olam_stream(m, index).head), alpha);
+    CKL("olam_set_alpha_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_multi_adapt_reset_statistics(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
+                                                      size_t ws_bytes, int32_t index, const cp_bn_buffers* bn, void* stream) {
+    OlamWS m;
+    if (int e = olam_check(cfg, n_streams, max_rows, ws, ws_bytes, &m)) return e;
+    if (int e = olam_index(index, n_streams, "cp_online_multi_adapt_reset_statistics")) return e;
+    OlamInitArgs ia{};
+    for (int l = 0; l < CP_N_BN; ++l) {
+        if (bn && (!bn->running_mean[l] || !bn->running_var[l]))
+            return fail(CP_ERR_ARG, "cp_online_multi_adapt_reset_statistics: running statistics");
+        ia.mean[l] = bn ? bn->running_mean[l] : nullptr; ia.var[l] = bn ? bn->running_var[l] : nullptr;
+    }
+    ia.stats = (double*)((unsigned char*)ws + m.w.stats); ia.first = index; ia.zero = bn ? 0 : 1;
+    hipLaunchKernelGGL(olam_init_kernel, dim3(CP_N_BN, 1), dim3(512), 0, (hipStream_t)stream, ia);
+    CKL("olam_init_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_multi_adapt_calibrate(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
+                                               size_t ws_bytes, int32_t index, const float* windows, int64_t n_windows, void* scratch,
+                                               size_t scratch_bytes, void* stream) {
+    if (n_windows < 2) return fail(CP_ERR_ARG, "cp_online_multi_adapt_calibrate: calibration takes at least 2 windows");
+    if (n_windows > (int64_t)1 << 24) return fail(CP_ERR_ARG, "cp_online_multi_adapt_calibrate: at most 2**24 windows");
+    OlamWS m;
+    if (int e = olam_check(cfg, n_streams, max_rows, ws, ws_bytes, &m)) return e;
+    if (int e = olam_index(index, n_streams, "cp_online_multi_adapt_calibrate")) return e;
+    if (!windows || !scratch) return fail(CP_ERR_ARG, "cp_online_multi_adapt_calibrate: windows and scratch are required");
+    if ((uintptr_t)windows % 4 || (uintptr_t)scratch % 256)
+        return fail(CP_ERR_ARG, "cp_online_multi_adapt_calibrate: misaligned input or scratch");
+    const OlaCalib k = ola_calib_carve(n_windows, cfg->dtype);
+    if (scratch_bytes < k.total) return fail(CP_ERR_WORKSPACE, "cp_online_multi_adapt_calibrate: scratch too small");
+    unsigned char* base = (unsigned char*)ws;
+    const OlaWS w = olam_stream(m, index);
+    if (cfg->dtype == CP_BF16)
+        return online_adapt_calibrate_t<bf16_t>(base, w, windows, n_windows, (unsigned char*)scratch, k, (hipStream_t)stream);
+    return online_adapt_calibrate_t<float>(base, w, windows, n_windows, (unsigned char*)scratch, k, (hipStream_t)stream);
+}
+
+// row blocks of the fc launches: about OLM_TARGET_WG workgroups of 512 / 16 feature tiles when there are rows enough
+static void olam_fc_blocks(int rows, int* blocks, int* rows_per_block) {
+    int b = (OLM_TARGET_WG + 512 / 16 - 1) / (512 / 16);
+    if (b > rows) b = rows;
+    *rows_per_block = (rows + b - 1) / b;
+    *blocks = (rows + *rows_per_block - 1) / *rows_per_block;
+}
+
+template <typename T>
+static int online_multi_adapt_push_t(const cp_online_config* c, int n_streams, unsigned char* base, const OlamWS& m, const float* raw,
+                                     const int32_t* counts, int64_t total, int rows, const float* mean_std, int32_t* pred,
+                                     int32_t* voted, float* logits, float* windows, hipStream_t st) {
+    const OlaWS& w = m.w;
+    OlState* states = (OlState*)(base + w.state);
+    OlmMeta* meta = (OlmMeta*)(base + m.meta);
+    OlmFrontArgs fa{};
+    fa.f.raw = raw; fa.f.X = (float*)(base + w.X); fa.f.windows = windows; fa.f.mean_std = mean_std;
+    fa.f.n_coef = c->n_coef; fa.f.phase = c->phase; fa.f.gain = 1024.f;       // as ol_launch_frontend
+    for (int i = 0; i < c->n_coef; ++i) { fa.f.b[i] = c->b[i] / c->a[0]; fa.f.a[i] = c->a[i] / c->a[0]; }
+    fa.states = states; fa.meta = meta; fa.counts = counts; fa.total_samples = total; fa.rows = rows; fa.max_m = c->max_windows;
+    if (c->n_coef == 9) hipLaunchKernelGGL((olm_frontend_kernel<9>), dim3(n_streams), dim3(256), 0, st, fa);
+    else hipLaunchKernelGGL((olm_frontend_kernel<0>), dim3(n_streams), dim3(256), 0, st, fa);
+    CKL("olm_frontend_kernel");
+    if (rows > 0) {
+        OlamConvBnArgs cb{};                              // BN1 -> conv2 -> BN2, as ola_conv_chain
+        cb.meta = meta;
+        cb.a.x = (const float*)(base + w.X); cb.a.c1w = (const float*)(base + w.c1w); cb.a.c1b = (const float*)(base + w.c1b);
+        cb.a.out = base + w.C1; cb.a.m_fixed = 0; cb.a.conv1 = 1; cb.a.bn = ola_bn(base, w, 0, OLA_TRACK, nullptr, 0, 0);
+        hipLaunchKernelGGL((olam_conv_bn_kernel<T>), dim3(n_streams), dim3(64), 0, st, cb);
+        CKL("olam_conv_bn_kernel<BN1>");
+        OlaGemmArgs g{};
+        g.l.act = base + w.C1; g.l.w = base + w.c2w; g.l.bias = (const float*)(base + w.c2b); g.l.out = base + w.R2; g.l.K = OL_CONV_K;
+        g.l.F = 64; g.l.ldo = 64; g.m_fixed = rows; g.rows_per_window = OL_C;
+        int blocks, tiles_per_block;
+        olm_row_blocks(rows * OL_C, 64 / 16, &blocks, &tiles_per_block);
+        hipLaunchKernelGGL((ola_gemm_kernel<T>), dim3(64 / 16, blocks), dim3(OL_THREADS), 0, st, g);
+        CKL("ola_gemm_kernel");
+        cb.a.pre = (const float*)(base + w.R2); cb.a.out = base + w.H0; cb.a.conv1 = 0; cb.a.bn = ola_bn(base, w, 1, OLA_TRACK, nullptr, 0, 0);
+        hipLaunchKernelGGL((olam_conv_bn_kernel<T>), dim3(n_streams), dim3(64), 0, st, cb);
+        CKL("olam_conv_bn_kernel<BN2>");
+        OlamFcArgs fc{};
+        fc.meta = meta; fc.n_streams = n_streams;
+        olam_fc_blocks(rows, &blocks, &fc.rows_per_block);
+        for (int i = 0; i < CP_N_FC; ++i) {               // H0 -> H1 -> H0 ...: fc7 leaves its output in H1
+            OlaGemmArgs& a = fc.g;
+            a.l.act = base + (i % 2 == 0 ? w.H0 : w.H1); a.l.out = base + (i % 2 == 0 ? w.H1 : w.H0);
+            a.l.w = base + w.fcw[i]; a.l.bias = (const float*)(base + w.fcb[i]); a.l.K = fcK(i); a.l.F = 512; a.l.ldo = 512;
+            a.rows_per_window = 1; a.bn = ola_bn(base, w, i + 2, OLA_TRACK, nullptr, 0, 0);
+            hipLaunchKernelGGL((olam_fc_kernel<T>), dim3(512 / 16, blocks), dim3(OL_THREADS), 0, st, fc);
+            CKL("olam_fc_kernel");
+        }
+    }
+    OlmTailArgs ta{};
+    ta.proj.act = base + w.H1; ta.proj.w = base + w.pw; ta.proj.bias = (const float*)(base + w.pb); ta.proj.K = 512; ta.proj.F = CP_D_E;
+    ta.states = states; ta.meta = meta; ta.vote = c->vote; ta.pred = pred; ta.voted = voted; ta.logits = logits;
+    hipLaunchKernelGGL((olm_tail_kernel<T>), dim3(n_streams), dim3(OL_THREADS), 0, st, ta);
+    CKL("olm_tail_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_multi_adapt_push(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                          const float* raw, const int32_t* counts, int64_t total_samples, int32_t total_windows,
+                                          const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows,
+                                          void* stream) {
+    OlamWS m;
+    if (int e = olam_check(cfg, n_streams, max_rows, ws, ws_bytes, &m)) return e;
+    if (total_windows < 0 || total_windows > max_rows) return fail(CP_ERR_ARG, "cp_online_multi_adapt_push: total_windows outside 0..max_rows");
+    if (total_samples < 0) return fail(CP_ERR_ARG, "cp_online_multi_adapt_push: negative total_samples");
+    if (total_samples == 0) return 0;
+    if (!raw || !counts || !mean_std) return fail(CP_ERR_ARG, "cp_online_multi_adapt_push: raw, counts and mean_std are required");
+    if (total_windows > 0 && (!pred || !voted)) return fail(CP_ERR_ARG, "cp_online_multi_adapt_push: pred and voted are required");
+    if ((uintptr_t)raw % 4 || (uintptr_t)mean_std % 4 || (uintptr_t)counts % 4)
+        return fail(CP_ERR_ARG, "cp_online_multi_adapt_push: misaligned input");
+    unsigned char* base = (unsigned char*)ws;
+    if (cfg->dtype == CP_BF16)
+        return online_multi_adapt_push_t<bf16_t>(cfg, n_streams, base, m, raw, counts, total_samples, total_windows, mean_std, pred, voted,
+                                                 logits, windows, (hipStream_t)stream);
+    return online_multi_adapt_push_t<float>(cfg, n_streams, base, m, raw, counts, total_samples, total_windows, mean_std, pred, voted,
+                                            logits, windows, (hipStream_t)stream);
+}
+
+extern "C" int cp_online_multi_adapt_statistics(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
+                                                size_t ws_bytes, int32_t index, double* out, void* stream) {
+    OlamWS m;
+    if (int e = olam_check(cfg, n_streams, max_rows, ws, ws_bytes, &m)) return e;
+    if (int e = olam_index(index, n_streams, "cp_online_multi_adapt_statistics")) return e;
+    if (!out) return fail(CP_ERR_ARG, "cp_online_multi_adapt_statistics: out is required");
+    CK(hipMemcpyAsync(out, (unsigned char*)ws + olam_stream(m, index).stats, (size_t)OLAM_STATS * 8, hipMemcpyDeviceToDevice,
+                      (hipStream_t)stream));
+    return 0;
 }

@@ -104,12 +104,11 @@ struct OlaConvBnArgs {
     OlaBn bn;
 };
 
-// BN1 or BN2: one thread per channel, serial over the windows
+// BN1 or BN2 over M >= 1 windows from row 0 of a.x / a.pre / a.out with the statistics of a.bn: thread c (64 threads) runs
+// channel c, serial over the windows
 template <typename T>
-__global__ __launch_bounds__(64) void ola_conv_bn_kernel(OlaConvBnArgs a) {
+__device__ __forceinline__ void ola_conv_bn_run(const OlaConvBnArgs& a, int M) {
 #pragma clang fp contract(off)
-    const int M = a.m_fixed >= 0 ? a.m_fixed : a.st->m_cur;
-    if (M <= 0) return;
     const int c = threadIdx.x;
     OlaChan s;
     s.load(a.bn, c);
@@ -172,6 +171,13 @@ __global__ __launch_bounds__(64) void ola_conv_bn_kernel(OlaConvBnArgs a) {
     s.store(a.bn, c);
 }
 
+template <typename T>
+__global__ __launch_bounds__(64) void ola_conv_bn_kernel(OlaConvBnArgs a) {
+    const int M = a.m_fixed >= 0 ? a.m_fixed : a.st->m_cur;
+    if (M <= 0) return;
+    ola_conv_bn_run<T>(a, M);
+}
+
 struct OlaGemmArgs {
     OlLayerArgs l;            // act [rows][K], w [F][K] compute dtype, bias [F], out: see the kernels
     int m_fixed;              // as OlaConvBnArgs
@@ -199,18 +205,13 @@ __global__ __launch_bounds__(OL_THREADS) void ola_gemm_kernel(OlaGemmArgs a) {
     }
 }
 
-// fc1..fc7: relu(A W^T + b) for 16 features and all rows into LDS, then the BN scan of each feature over the windows in
-// order; OLA_TRACK / OLA_FROZEN write the normalised rows [M][512] in the compute dtype.  Grid 512 / 16.
+// fc1..fc7, in three steps that the single-stream and the multi-stream kernels share.
+// M (1..OL_MAXM) rows of a.l.act from row 0: relu(A W^T + b) for features f0..f0+15 into pre.  Ends behind a barrier.
 template <typename T>
-__global__ __launch_bounds__(OL_THREADS) void ola_fc_kernel(OlaGemmArgs a) {
+__device__ __forceinline__ void ola_fc_gemm(const OlaGemmArgs& a, OlTileLds<T>& L, float (*pre)[17], int f0, int M,
+                                            const uint4 (&wf)[OL_MAXCH][OL_KC * (int)sizeof(T) / 64]) {
 #pragma clang fp contract(off)
-    __shared__ OlTileLds<T> L;
-    __shared__ float pre[OL_MAXM][17];
-    const int M = a.m_fixed >= 0 ? a.m_fixed : a.l.st->m_cur;
-    if (M <= 0) return;
-    const int f0 = blockIdx.x * 16, tid = threadIdx.x;
-    uint4 wf[OL_MAXCH][OL_KC * (int)sizeof(T) / 64];
-    ol_load_weights<T>((const T*)a.l.w, a.l.K, f0, wf);
+    const int tid = threadIdx.x;
     for (int m0 = 0; m0 < M; m0 += 16) {
         ol_tile<T, false>(a.l, L, a.l.K, 0, m0, M, wf);
         if (tid < 256) {
@@ -219,31 +220,56 @@ __global__ __launch_bounds__(OL_THREADS) void ola_fc_kernel(OlaGemmArgs a) {
         }
     }
     __syncthreads();
-    if (tid < 16) {
-        const int f = f0 + tid;
-        OlaChan s;
-        s.load(a.bn, f);
-        if (a.bn.mode == OLA_ACC) {
-            for (int t = 0; t < M; ++t) ola_merge(s.n, s.mean, s.m2, 1.0, (double)pre[t][tid], 0.0);
-        } else {
-            double sc = s.scale();
-            for (int t = 0; t < M; ++t) {
-                const float x = pre[t][tid];
-                pre[t][tid] = s.norm(x, sc);
-                if (s.alpha != 0.0) {
-                    ola_update(s.mu, s.v, (double)x, 0.0, s.alpha);
-                    sc = s.scale();
-                }
+}
+
+// One thread: the BN scan of feature f0 + col over the M rows pre[0..M-1][col] with the statistics of bn; OLA_TRACK /
+// OLA_FROZEN leave the normalised values in pre
+__device__ __forceinline__ void ola_fc_scan(const OlaBn& bn, float (*pre)[17], int f0, int col, int M) {
+#pragma clang fp contract(off)
+    const int f = f0 + col;
+    OlaChan s;
+    s.load(bn, f);
+    if (bn.mode == OLA_ACC) {
+        for (int t = 0; t < M; ++t) ola_merge(s.n, s.mean, s.m2, 1.0, (double)pre[t][col], 0.0);
+    } else {
+        double sc = s.scale();
+        for (int t = 0; t < M; ++t) {
+            const float x = pre[t][col];
+            pre[t][col] = s.norm(x, sc);
+            if (s.alpha != 0.0) {
+                ola_update(s.mu, s.v, (double)x, 0.0, s.alpha);
+                sc = s.scale();
             }
         }
-        s.store(a.bn, f);
     }
-    if (a.bn.mode == OLA_ACC) return;
-    __syncthreads();
-    for (int e = tid; e < M * 16; e += OL_THREADS) {
+    s.store(bn, f);
+}
+
+// The M normalised rows of pre into a.l.out from row 0 (ldo a.l.ldo) in the compute dtype
+template <typename T>
+__device__ __forceinline__ void ola_fc_store(const OlaGemmArgs& a, float (*pre)[17], int f0, int M) {
+    for (int e = threadIdx.x; e < M * 16; e += OL_THREADS) {
         const int row = e >> 4, col = e & 15;
         ((T*)a.l.out)[(size_t)row * a.l.ldo + f0 + col] = ol_cvt<T>(pre[row][col]);
     }
+}
+
+// fc1..fc7: relu(A W^T + b) for 16 features and all rows into LDS, then the BN scan of each feature over the windows in
+// order; OLA_TRACK / OLA_FROZEN write the normalised rows [M][512] in the compute dtype.  Grid 512 / 16.
+template <typename T>
+__global__ __launch_bounds__(OL_THREADS) void ola_fc_kernel(OlaGemmArgs a) {
+    __shared__ OlTileLds<T> L;
+    __shared__ float pre[OL_MAXM][17];
+    const int M = a.m_fixed >= 0 ? a.m_fixed : a.l.st->m_cur;
+    if (M <= 0) return;
+    const int f0 = blockIdx.x * 16, tid = threadIdx.x;
+    uint4 wf[OL_MAXCH][OL_KC * (int)sizeof(T) / 64];
+    ol_load_weights<T>((const T*)a.l.w, a.l.K, f0, wf);
+    ola_fc_gemm<T>(a, L, pre, f0, M, wf);
+    if (tid < 16) ola_fc_scan(a.bn, pre, f0, tid, M);
+    if (a.bn.mode == OLA_ACC) return;
+    __syncthreads();
+    ola_fc_store<T>(a, pre, f0, M);
 }
 
 // ---- cp_online_adapt_prepare: the model's parameters into the workspace, unfolded ----------------------------------------

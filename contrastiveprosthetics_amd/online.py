@@ -18,7 +18,9 @@ folded form cannot run), and every push can track the stream with rate alpha per
 
 `MultiStreamDecoder` decodes up to 256 streams through one model in one chain of launches per push (cp_online_multi_*,
 csrc/online_multi.cuh): the folded weights once, each stream's state and class table of its own, and every stream's outputs
-bit-identical to those of its own `OnlineDecoder`.
+bit-identical to those of its own `OnlineDecoder`.  `AdaptiveMultiStreamDecoder` is its adaptive form (cp_online_multi_adapt_*,
+csrc/online_multi_adapt.cuh): per stream float64 BatchNorm statistics, calibration and alpha, each stream bit-identical to its
+own `OnlineDecoder(adapt=alpha)`.
 
 The number of windows a push emits follows from sample counts alone (`windows_emitted`), so a push never waits for the device:
 its outputs are device tensors on torch's current stream.
@@ -160,6 +162,21 @@ def _class_table(e: Engine, classes=None, glove=None, table=None, ids=None):
     else:
         tab = rows[order].to(device).contiguous()
     return tab.to(torch.float32).contiguous(), ids_t
+
+
+def _calibration_windows(raw: torch.Tensor, b, a, phase: int, mean_std: torch.Tensor) -> torch.Tensor:
+    """The windows a fresh stream emits for `raw` (n, 12), by the offline path (preprocess_segments + normalize_)."""
+    from .preprocess import normalize_, preprocess_segments
+    if raw.device.type != "cuda" or raw.dtype != torch.float32 or raw.dim() != 2 or raw.shape[1] != EMG_DIM:
+        raise ValueError("raw must be an (n, 12) float32 tensor on the GPU")
+    k = windows_before(raw.shape[0], phase)
+    if k < 2:
+        raise ValueError("calibration takes at least 2 windows")
+    raw = raw.contiguous()[None]
+    keep = phase + STRIDE * np.arange(k)
+    step = _lib.CP_ONLINE_MAX_WINDOWS                      # positions one call of the offline transform keeps
+    w = torch.cat([preprocess_segments(raw, b=b, a=a, keep=keep[i:i + step]) for i in range(0, k, step)], dim=1)
+    return normalize_(w.contiguous(), mean_std[0], mean_std[1])[0]
 
 
 class OnlineDecoder:
@@ -319,17 +336,7 @@ class OnlineDecoder:
     def calibration_windows(self, raw: torch.Tensor) -> torch.Tensor:
         """The windows a fresh stream would emit for `raw` (n, 12), by the offline path: preprocess_segments + normalize_ with
         this decoder's filter, phase, mean and std."""
-        from .preprocess import normalize_, preprocess_segments
-        if raw.device.type != "cuda" or raw.dtype != torch.float32 or raw.dim() != 2 or raw.shape[1] != EMG_DIM:
-            raise ValueError("raw must be an (n, 12) float32 tensor on the GPU")
-        k = windows_before(raw.shape[0], self.phase)
-        if k < 2:
-            raise ValueError("calibration takes at least 2 windows")
-        raw = raw.contiguous()[None]
-        keep = self.phase + STRIDE * np.arange(k)
-        step = _lib.CP_ONLINE_MAX_WINDOWS                  # positions one call of the offline transform keeps
-        w = torch.cat([preprocess_segments(raw, b=self._b, a=self._a, keep=keep[i:i + step]) for i in range(0, k, step)], dim=1)
-        return normalize_(w.contiguous(), self.mean_std[0], self.mean_std[1])[0]
+        return _calibration_windows(raw, self._b, self._a, self.phase, self.mean_std)
 
     def calibrate(self, raw: torch.Tensor):
         """AdaBN calibration from a recording raw (n, 12) f32 on the GPU: every BatchNorm's statistics become the batch
@@ -400,26 +407,14 @@ def plan_push(n_seen, counts, phase: int, max_windows: int, max_rows: int):
     return rounds
 
 
-class MultiStreamDecoder:
-    """`OnlineDecoder` for n_streams (1..256) streams at once: one model, one set of folded weights, one dtype, vote length,
-    phase, filter and normalisation for all; per stream its own filter and RMS state, sample count, vote ring and class table.
-    A push is one chain of ten launches for all streams, and every stream's pred, voted, logits and windows equal bit for bit
-    those of an `OnlineDecoder` with the same settings and class table fed the same chunks of that stream alone.
+class _MultiStreamBase:
+    """What the multi-stream decoders share: settings, workspace, per-stream class tables and sample counts, packing and
+    splitting of pushes.  Subclasses name their C entries (_ENTRY: cp_online_multi or cp_online_multi_adapt) and prepare."""
+    _WHO = "MultiStreamDecoder"
+    _ENTRY = "cp_online_multi"
 
-    max_windows_per_push bounds the windows of one stream per launch chain, max_rows (default min(n_streams *
-    max_windows_per_push, 4096)) the windows of all streams; larger pushes are split on the host.  Stock BatchNorm only: the
-    adaptive form (adapt=) and AdaBN models are refused, as is fp8."""
-
-    def __init__(self, model_or_engine, mean, std, n_streams: int, vote: int = VOTE, dtype: Optional[str] = None, phase: int = 0,
-                 max_windows_per_push: int = 256, max_rows: Optional[int] = None, b=None, a=None, adapt: Optional[float] = None):
-        e = _engine_of(model_or_engine, "MultiStreamDecoder")
-        if adapt is not None:
-            raise _lib.CpNativeError("MultiStreamDecoder has no adaptive form (adapt=): decode an adapting stream with "
-                                     "OnlineDecoder(..., adapt=alpha)")
-        if e.adabn:
-            raise _lib.CpNativeError("MultiStreamDecoder needs stock BatchNorm with running statistics: an AdaBN model normalises "
-                                     "with the statistics of its batch (OnlineDecoder(..., adapt=alpha) calibrates them)")
-        dtype = _check_settings(e, dtype, vote, phase, max_windows_per_push, "MultiStreamDecoder")
+    def _setup(self, e: Engine, mean, std, n_streams, vote, dtype, phase, max_windows_per_push, max_rows, b, a):
+        dtype = _check_settings(e, dtype, vote, phase, max_windows_per_push, self._WHO)
         if not 1 <= int(n_streams) <= MAX_STREAMS:
             raise ValueError(f"n_streams must lie in 1..{MAX_STREAMS}")
         if max_rows is None:
@@ -436,9 +431,10 @@ class MultiStreamDecoder:
         self.max_windows = int(max_windows_per_push)
         self.max_rows = int(max_rows)
         self.n_streams = int(n_streams)
+        self._b, self._a = b, a
         self._cfg = _config(dtype, self.max_windows, self.vote, self.phase, b, a)
         self.mean_std = torch.stack([_channels(mean, self.device), _channels(std, self.device)]).contiguous()
-        nbytes = self.lib.cp_online_multi_workspace_bytes(self.n_streams, self.max_rows, self._cfg.dtype)
+        nbytes = getattr(self.lib, self._ENTRY + "_workspace_bytes")(self.n_streams, self.max_rows, self._cfg.dtype)
         self.ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
         self._seen = np.zeros(self.n_streams, dtype=np.int64)
         self.class_ids = [None] * self.n_streams           # per stream: sorted ids (K,) int32, or None before set_classes
@@ -447,7 +443,6 @@ class MultiStreamDecoder:
         self._has_table = np.zeros(self.n_streams, dtype=bool)
         self._k = [0] * self.n_streams                     # classes per stream
         self._counts_cache = None
-        self.refresh()
 
     # ------------------------------------------------------------------ helpers
     def _stream(self) -> int:
@@ -467,13 +462,8 @@ class MultiStreamDecoder:
         return self._seen.copy()
 
     # ------------------------------------------------------------------ API
-    def refresh(self):
-        """Fold the model's current weights and running statistics again (as OnlineDecoder.refresh); the class tables that come
-        from the model (classes=, glove=) are derived again, which empties those streams' vote rings."""
-        e = self.engine
-        _lib.check(self.lib.cp_online_multi_prepare(C.byref(self._cfg), self.n_streams, self.max_rows, C.byref(e._p), C.byref(e._bn),
-                                                    C.c_float(1e-5), self.ws.data_ptr(), self.ws.numel(), self._stream()),
-                   "cp_online_multi_prepare")
+    def _set_model_tables(self):
+        """derive the class tables that come from the model again"""
         for s, src in enumerate(self._source):
             if src is not None and src[2] is None:
                 classes, glove, _, ids = src
@@ -542,6 +532,9 @@ class MultiStreamDecoder:
             raise ValueError(f"counts sum to {int(cnt.sum())} samples, raw holds {raw.shape[0]}")
         return self._push(raw.contiguous(), cnt, return_logits, return_windows)
 
+    def _check_push(self, counts: np.ndarray):
+        """refusals of a subclass, before anything is enqueued"""
+
     @staticmethod
     def _check_raw(t, what: str):
         if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != torch.float32 or t.dim() != 2 \
@@ -563,6 +556,7 @@ class MultiStreamDecoder:
         if ((counts > 0) & ~self._has_table).any():
             s = int(np.nonzero((counts > 0) & ~self._has_table)[0][0])
             raise _lib.CpNativeError(f"stream {s} has samples but no class table: set_classes({s}, ...) first")
+        self._check_push(counts)
         row0, m = packed_rows(self._seen, counts, self.phase)
         if m.max() <= self.max_windows and m.sum() <= self.max_rows:
             rounds = [(counts, raw, m)]                        # the usual case: one chain of launches
@@ -584,11 +578,10 @@ class MultiStreamDecoder:
             logits = torch.empty(R, MAX_CLASSES, dtype=torch.float32, device=self.device) if return_logits else None
             wins = torch.empty(R, EMG_DIM, dtype=torch.float32, device=self.device) if return_windows else None
             if piece.shape[0]:
-                _lib.check(self.lib.cp_online_multi_push(*self._args(), piece.data_ptr(), self._counts_on_device(take).data_ptr(),
-                                                         int(piece.shape[0]), R, self.mean_std.data_ptr(), pv[0].data_ptr(),
-                                                         pv[1].data_ptr(), logits.data_ptr() if logits is not None else None,
-                                                         wins.data_ptr() if wins is not None else None, self._stream()),
-                           "cp_online_multi_push")
+                _lib.check(getattr(self.lib, self._ENTRY + "_push")(
+                    *self._args(), piece.data_ptr(), self._counts_on_device(take).data_ptr(), int(piece.shape[0]), R,
+                    self.mean_std.data_ptr(), pv[0].data_ptr(), pv[1].data_ptr(), logits.data_ptr() if logits is not None else None,
+                    wins.data_ptr() if wins is not None else None, self._stream()), self._ENTRY + "_push")
             self._seen += take
             ml = m.tolist()
             cols = [pv[0, :R].split(ml), pv[1, :R].split(ml)]
@@ -600,3 +593,133 @@ class MultiStreamDecoder:
         if len(outs) == 1:
             return outs[0]
         return [tuple(torch.cat([o[s][i] for o in outs]) for i in range(len(outs[0][s]))) for s in range(self.n_streams)]
+
+
+class MultiStreamDecoder(_MultiStreamBase):
+    """`OnlineDecoder` for n_streams (1..256) streams at once: one model, one set of folded weights, one dtype, vote length,
+    phase, filter and normalisation for all; per stream its own filter and RMS state, sample count, vote ring and class table.
+    A push is one chain of ten launches for all streams, and every stream's pred, voted, logits and windows equal bit for bit
+    those of an `OnlineDecoder` with the same settings and class table fed the same chunks of that stream alone.
+
+    max_windows_per_push bounds the windows of one stream per launch chain, max_rows (default min(n_streams *
+    max_windows_per_push, 4096)) the windows of all streams; larger pushes are split on the host.  Stock BatchNorm only: the
+    adaptive form (adapt=) and AdaBN models are refused, as is fp8 (`AdaptiveMultiStreamDecoder` is the adaptive form)."""
+
+    def __init__(self, model_or_engine, mean, std, n_streams: int, vote: int = VOTE, dtype: Optional[str] = None, phase: int = 0,
+                 max_windows_per_push: int = 256, max_rows: Optional[int] = None, b=None, a=None, adapt: Optional[float] = None):
+        e = _engine_of(model_or_engine, "MultiStreamDecoder")
+        if adapt is not None:
+            raise _lib.CpNativeError("MultiStreamDecoder has no adaptive form (adapt=): decode adapting streams with "
+                                     "AdaptiveMultiStreamDecoder, or one with OnlineDecoder(..., adapt=alpha)")
+        if e.adabn:
+            raise _lib.CpNativeError("MultiStreamDecoder needs stock BatchNorm with running statistics: an AdaBN model normalises "
+                                     "with the statistics of its batch (AdaptiveMultiStreamDecoder calibrates them)")
+        self._setup(e, mean, std, n_streams, vote, dtype, phase, max_windows_per_push, max_rows, b, a)
+        self.refresh()
+
+    def refresh(self):
+        """Fold the model's current weights and running statistics again (as OnlineDecoder.refresh); the class tables that come
+        from the model (classes=, glove=) are derived again, which empties those streams' vote rings."""
+        e = self.engine
+        _lib.check(self.lib.cp_online_multi_prepare(C.byref(self._cfg), self.n_streams, self.max_rows, C.byref(e._p), C.byref(e._bn),
+                                                    C.c_float(1e-5), self.ws.data_ptr(), self.ws.numel(), self._stream()),
+                   "cp_online_multi_prepare")
+        self._set_model_tables()
+
+
+
+class AdaptiveMultiStreamDecoder(_MultiStreamBase):
+    """`OnlineDecoder(adapt=alpha)` for n_streams (1..256) streams at once (cp_online_multi_adapt_*,
+    csrc/online_multi_adapt.cuh): one model with its BatchNorms unfolded, stored once; per stream, besides what
+    `MultiStreamDecoder` keeps, float64 statistics of the 9 BatchNorms and its own alpha in [0, 1) (a float for all streams,
+    or one per stream; 0 freezes).  A push is one chain of twelve launches for all streams, and every stream's pred, voted,
+    logits, windows and `bn_statistics` equal bit for bit those of an `OnlineDecoder(adapt=alpha_s)` with the same settings,
+    class table and calibration fed the same chunks of that stream alone.
+
+    Stock models start every stream at the running statistics; under an AdaBN model every stream starts uncalibrated and
+    takes samples only after `calibrate(stream, raw)`.  fp8, and glove class rows under an AdaBN model, are refused."""
+    _WHO = "AdaptiveMultiStreamDecoder"
+    _ENTRY = "cp_online_multi_adapt"
+
+    def __init__(self, model_or_engine, mean, std, n_streams: int, alpha, vote: int = VOTE, dtype: Optional[str] = None,
+                 phase: int = 0, max_windows_per_push: int = 256, max_rows: Optional[int] = None, b=None, a=None):
+        e = _engine_of(model_or_engine, "AdaptiveMultiStreamDecoder")
+        if not 1 <= int(n_streams) <= MAX_STREAMS:
+            raise ValueError(f"n_streams must lie in 1..{MAX_STREAMS}")
+        alphas = np.broadcast_to(np.asarray(alpha, dtype=np.float64), (int(n_streams),)).copy() \
+            if np.ndim(alpha) == 0 else np.asarray(alpha, dtype=np.float64).reshape(-1)
+        if alphas.shape[0] != int(n_streams):
+            raise ValueError(f"alpha: one value, or one per stream ({int(n_streams)})")
+        for x in alphas:
+            self._check_alpha(x)
+        self._setup(e, mean, std, n_streams, vote, dtype, phase, max_windows_per_push, max_rows, b, a)
+        self.alpha = alphas
+        self.calibrated = np.full(self.n_streams, not e.adabn)     # the running statistics are a calibration
+        self._prepared = False
+        self.refresh()
+
+    @staticmethod
+    def _check_alpha(x):
+        if not 0.0 <= float(x) < 1.0:
+            raise ValueError("alpha must lie in [0, 1)")
+
+    def _check_push(self, counts: np.ndarray):
+        bad = np.nonzero((counts > 0) & ~self.calibrated)[0]
+        if bad.size:
+            s = int(bad[0])
+            raise _lib.CpNativeError(f"stream {s} is uncalibrated (an AdaBN model has no BatchNorm statistics): "
+                                     f"calibrate({s}, raw) first")
+
+    # ------------------------------------------------------------------ API
+    def refresh(self):
+        """Re-read the model's weights, gamma and beta; every stream keeps its BatchNorm statistics and alpha (as
+        OnlineDecoder(adapt=).refresh).  Class tables that come from the model are derived again."""
+        e = self.engine
+        first = not self._prepared                         # the first prepare also sets the statistics (stock) and every alpha
+        bn = C.byref(e._bn) if first and not e.adabn else None
+        alpha = (C.c_double * self.n_streams)(*self.alpha.tolist()) if first else None
+        _lib.check(self.lib.cp_online_multi_adapt_prepare(C.byref(self._cfg), self.n_streams, self.max_rows, C.byref(e._p), bn,
+                                                          C.c_float(1e-5), alpha, self.ws.data_ptr(), self.ws.numel(),
+                                                          self._stream()), "cp_online_multi_adapt_prepare")
+        self._prepared = True
+        self._set_model_tables()
+
+    def set_alpha(self, stream: int, alpha: float):
+        """The tracking rate of one stream from its next window on (0 freezes its statistics)."""
+        s = self._index(stream)
+        self._check_alpha(alpha)
+        _lib.check(self.lib.cp_online_multi_adapt_set_alpha(*self._args(), s, C.c_double(float(alpha)), self._stream()),
+                   "cp_online_multi_adapt_set_alpha")
+        self.alpha[s] = float(alpha)
+
+    def calibrate(self, stream: int, raw: torch.Tensor):
+        """AdaBN calibration of one stream from a recording raw (n, 12) f32 on the GPU, as OnlineDecoder.calibrate.  No other
+        stream's statistics, and no stream's filter state, vote ring or class table, change."""
+        s = self._index(stream)
+        if raw.dim() != 2 or windows_before(raw.shape[0], self.phase) < 2:
+            raise ValueError("calibration takes at least 2 windows")
+        w = _calibration_windows(raw, self._b, self._a, self.phase, self.mean_std).contiguous()
+        scratch = torch.empty(self.lib.cp_online_adapt_calibrate_scratch_bytes(w.shape[0], self._cfg.dtype), dtype=torch.uint8,
+                              device=self.device)
+        _lib.check(self.lib.cp_online_multi_adapt_calibrate(*self._args(), s, w.data_ptr(), w.shape[0], scratch.data_ptr(),
+                                                            scratch.numel(), self._stream()), "cp_online_multi_adapt_calibrate")
+        self.calibrated[s] = True
+
+    def reset_statistics(self, stream: int):
+        """Hand a stream to a new user: its statistics return to the model's current running statistics (stock BatchNorm) or
+        to uncalibrated (AdaBN).  With reset(stream) too, the stream is a freshly built OnlineDecoder(adapt=alpha)."""
+        s = self._index(stream)
+        e = self.engine
+        bn = None if e.adabn else C.byref(e._bn)
+        _lib.check(self.lib.cp_online_multi_adapt_reset_statistics(*self._args(), s, bn, self._stream()),
+                   "cp_online_multi_adapt_reset_statistics")
+        self.calibrated[s] = not e.adabn
+
+    def bn_statistics(self, stream: int) -> torch.Tensor:
+        """(9, 2, 512) float64 on the GPU: one stream's BatchNorm statistics as its next window sees them (as
+        OnlineDecoder.bn_statistics)."""
+        s = self._index(stream)
+        out = torch.zeros(9, 2, 512, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.cp_online_multi_adapt_statistics(*self._args(), s, out.data_ptr(), self._stream()),
+                   "cp_online_multi_adapt_statistics")
+        return out

@@ -512,6 +512,45 @@ int cp_online_multi_push(const cp_online_config* cfg, int32_t n_streams, int32_t
                          const float* raw, const int32_t* counts, int64_t total_samples, int32_t total_windows,
                          const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, void* stream);
 
+/* ---- adaptive multi-stream online decoding: cp_online_adapt_* for n_streams <= 256 streams in one chain per push ----------
+ * The streams of cp_online_multi_* with the BatchNorms of cp_online_adapt_* kept unfolded.  The unfolded weights, gamma and
+ * beta are stored once; each stream has its own state (as cp_online_multi_*), its own alpha in [0, 1) and eps, and its own
+ * float64 statistics (9, 2, 512), which the recurrence of cp_online_adapt_* updates window by window in stream order.  Calls
+ * take n_streams and max_rows as the cp_online_multi_* ones do; packing, counts, outputs and untouched streams are as for
+ * cp_online_multi_push.  Every stream's pred, voted, logits, windows and statistics after a push equal bit for bit those of a
+ * cp_online_adapt_* workspace with that stream's alpha, statistics, class table and state fed the same chunks.  A push is
+ * twelve launches for any n_streams (front end, BN1, conv2, BN2, fc1..fc7, tail); none when total_samples is 0.
+ * The workspace begins as a cp_online_multi_* workspace of the same n_streams and max_rows: cp_online_multi_set_classes and
+ * cp_online_multi_reset take it (reset keeps the statistics and alpha); cp_online_multi_prepare and cp_online_multi_push do
+ * not.  A fresh (zeroed) workspace has alpha 0 on every stream. */
+size_t cp_online_multi_adapt_workspace_bytes(int32_t n_streams, int32_t max_rows, int32_t dtype);
+/* as cp_online_adapt_prepare, once for all streams: copies the weights, gamma, beta and conv1 unfolded and sets every stream's
+ * eps.  bn != NULL: every stream's statistics become the running statistics; bn == NULL: they stay (AdaBN, or a refresh).
+ * alpha: n_streams host values in [0, 1), stream s's alpha; NULL: every alpha stays (cp_online_multi_adapt_set_alpha changes
+ * one). */
+int cp_online_multi_adapt_prepare(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, const cp_params* p,
+                                  const cp_bn_buffers* bn, float bn_eps, const double* alpha, void* ws, size_t ws_bytes,
+                                  void* stream);
+/* alpha in [0, 1) of stream `index` from the next push on (0 freezes its statistics) */
+int cp_online_multi_adapt_set_alpha(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                    int32_t index, double alpha, void* stream);
+/* the statistics of stream `index` only: bn != NULL: the running statistics (as cp_online_multi_adapt_prepare); bn == NULL:
+ * zero, as on a fresh workspace (uncalibrated: the caller must not push samples to it before calibrating it) */
+int cp_online_multi_adapt_reset_statistics(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
+                                           size_t ws_bytes, int32_t index, const cp_bn_buffers* bn, void* stream);
+/* cp_online_adapt_calibrate of stream `index` against the shared weights; scratch of cp_online_adapt_calibrate_scratch_bytes.
+ * No other stream's statistics, and no stream's state, vote ring or class table, change. */
+int cp_online_multi_adapt_calibrate(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                    int32_t index, const float* windows, int64_t n_windows, void* scratch, size_t scratch_bytes,
+                                    void* stream);
+/* as cp_online_multi_push, on an adaptive multi-stream workspace */
+int cp_online_multi_adapt_push(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                               const float* raw, const int32_t* counts, int64_t total_samples, int32_t total_windows,
+                               const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, void* stream);
+/* out (9, 2, 512) float64 on the device: the statistics of stream `index`, laid out as cp_online_adapt_statistics */
+int cp_online_multi_adapt_statistics(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                     int32_t index, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,12 +9,16 @@ With --adapt the adaptive form (OnlineDecoder(..., adapt=0.01), csrc/online_adap
 instead of the composition, plus the wall time of calibrate() on 6,000 windows (60 s of stream).
 With --streams the multi-stream decoder (MultiStreamDecoder.push, csrc/online_multi.cuh) is timed against S single-stream
 decoders pushing one after another, for S in 1, 8, 64, 256 streams of 1 and 25 windows each.
+With --streams --adapt the adaptive multi-stream decoder (AdaptiveMultiStreamDecoder.push, csrc/online_multi_adapt.cuh, alpha
+0.01) is timed against S OnlineDecoder(adapt=0.01) pushing one after another and against the folded MultiStreamDecoder at
+the same S, plus the library part of calibrate(stream) on 6,000 windows (cp_online_multi_adapt_calibrate alone).
 Each push is timed from the host with a synchronisation behind it (the latency a control loop sees); kernels per push are
 counted with torch.profiler over a few pushes.  One JSON line per case, and a table with --out.
 
     python tools/online_bench.py --iters 200 --out profiles/online_latency.txt
     python tools/online_bench.py --adapt --iters 200 --out profiles/online_adapt_latency.txt
     python tools/online_bench.py --streams --iters 50 --out profiles/online_multi_latency.txt
+    python tools/online_bench.py --streams --adapt --iters 100 --out profiles/online_multi_adapt_latency.txt
 """
 import argparse
 import json
@@ -27,7 +31,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from contrastiveprosthetics_amd import MultiStreamDecoder, OnlineDecoder  # noqa: E402
+from contrastiveprosthetics_amd import AdaptiveMultiStreamDecoder, MultiStreamDecoder, OnlineDecoder  # noqa: E402
 from contrastiveprosthetics_amd.engine import Engine                       # noqa: E402
 from contrastiveprosthetics_amd.preprocess import normalize_, preprocess_segments   # noqa: E402
 
@@ -76,6 +80,8 @@ def main():
     table = (e.values.views["glove_net.easy.0.weight"].t() + e.values.views["glove_net.easy.0.bias"]).contiguous()
     tn = table / table.norm(dim=-1, keepdim=True)
     rows = []
+    if a.adapt and a.streams:
+        return streams_adapt_main(a, e, stream, mean, std, classes)
     if a.adapt:
         return adapt_main(a, e, stream, mean, std, classes)
     if a.streams:
@@ -228,6 +234,96 @@ def streams_main(a, e, stream, mean, std, classes):
             for r in rows:
                 f.write(f"{r['kind']:<11} {r['dtype']:<5} {r['streams']:>7} {r['samples']:>7} {r['windows']:>7} {r['median_us']:>10.1f} "
                         f"{r['p90_us']:>9.1f} {r['kernels_per_push']:>8.1f} {r['speedup']:>8.2f}\n")
+
+
+def streams_adapt_main(a, e, stream, mean, std, classes):
+    import ctypes as C
+    from contrastiveprosthetics_amd import _lib
+    from contrastiveprosthetics_amd.online import _calibration_windows
+    rows, cal = [], []
+    counts = [int(x) for x in a.counts.split(",")]
+    for dtype in ("f32", "bf16"):
+        for S in counts:
+            for n in (20, 500):
+                m = n // 20
+                multi = AdaptiveMultiStreamDecoder(e, mean, std, S, 0.01, dtype=dtype, max_rows=S * m)
+                folded = MultiStreamDecoder(e, mean, std, S, dtype=dtype, max_rows=S * m)
+                for s in range(S):
+                    multi.set_classes(s, classes=classes)
+                    folded.set_classes(s, classes=classes)
+                singles = [OnlineDecoder(e, mean, std, classes=classes, dtype=dtype, adapt=0.01) for _ in range(S)]
+                pos = [0]
+                span = stream.shape[0] - S * n
+
+                def batched():
+                    base = pos[0] % span
+                    pos[0] += S * n
+                    return multi.push_packed(stream[base:base + S * n], [n] * S)
+
+                def sequential():
+                    base = pos[0] % span
+                    pos[0] += S * n
+                    return [d.push(stream[base + i * n:base + (i + 1) * n]) for i, d in enumerate(singles)]
+
+                def folded_push():
+                    base = pos[0] % span
+                    pos[0] += S * n
+                    return folded.push_packed(stream[base:base + S * n], [n] * S)
+
+                res = {}
+                for name, fn in (("batched", batched), ("sequential", sequential), ("folded", folded_push)):
+                    med, p90 = time_pushes(fn, a.iters, a.warmup)
+                    k = count_kernels(fn, pushes=2)
+                    res[name] = med
+                    r = dict(kind=name, dtype=dtype, streams=S, samples=n, windows=m, median_us=round(med, 1), p90_us=round(p90, 1),
+                             kernels_per_push=k)
+                    print(json.dumps(r), flush=True)
+                    rows.append(r)
+                for r in rows[-3:]:
+                    r["seq_over_batched"] = round(res["sequential"] / res["batched"], 2)
+                    r["batched_over_folded"] = round(res["batched"] / res["folded"], 2)
+                del multi, folded, singles
+                torch.cuda.empty_cache()
+        # the library part of calibrate(stream): cp_online_multi_adapt_calibrate on 6,000 windows, windows and scratch made once
+        dec = AdaptiveMultiStreamDecoder(e, mean, std, 64, 0.01, dtype=dtype, max_rows=64)
+        rec = stream[:20 * 6000 + 10].contiguous()
+        w = _calibration_windows(rec, dec._b, dec._a, dec.phase, dec.mean_std).contiguous()
+        scratch = torch.empty(dec.lib.cp_online_adapt_calibrate_scratch_bytes(w.shape[0], dec._cfg.dtype), dtype=torch.uint8,
+                              device=dec.device)
+
+        def lib_calibrate():
+            _lib.check(dec.lib.cp_online_multi_adapt_calibrate(*dec._args(), 17, w.data_ptr(), w.shape[0], scratch.data_ptr(),
+                                                               scratch.numel(), C.c_void_p(dec._stream())), "calibrate")
+
+        lib_calibrate()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(20):
+            t0 = time.perf_counter()
+            lib_calibrate()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        r = dict(kind="calibrate_lib", dtype=dtype, windows=int(w.shape[0]), median_ms=round(float(np.median(ts)) * 1e3, 2))
+        print(json.dumps(r), flush=True)
+        cal.append(r)
+        del dec, scratch
+        torch.cuda.empty_cache()
+    if a.out:
+        dev = torch.cuda.get_device_name(0)
+        with open(a.out, "w") as f:
+            f.write(f"# tools/online_bench.py --streams --adapt --counts {a.counts} --iters {a.iters} --warmup {a.warmup} on {dev}\n")
+            f.write("# one push of S streams x `windows` windows each, alpha 0.01: batched = AdaptiveMultiStreamDecoder.push_packed,\n"
+                    "# sequential = S OnlineDecoder(adapt=0.01).push one after another, folded = MultiStreamDecoder.push_packed;\n"
+                    "# host-synchronised wall time (median, p90), kernels per push (torch.profiler: library kernels plus torch's own);\n"
+                    "# seq/bat = sequential / batched, bat/fold = batched / folded\n")
+            f.write(f"{'kind':<11} {'dtype':<5} {'streams':>7} {'samples':>7} {'windows':>7} {'median_us':>10} {'p90_us':>9} "
+                    f"{'kernels':>8} {'seq/bat':>8} {'bat/fold':>8}\n")
+            for r in rows:
+                f.write(f"{r['kind']:<11} {r['dtype']:<5} {r['streams']:>7} {r['samples']:>7} {r['windows']:>7} {r['median_us']:>10.1f} "
+                        f"{r['p90_us']:>9.1f} {r['kernels_per_push']:>8.1f} {r['seq_over_batched']:>8.2f} {r['batched_over_folded']:>8.2f}\n")
+            f.write("# cp_online_multi_adapt_calibrate of one stream (of 64) on 6,000 windows, host-synchronised, median of 20\n")
+            for r in cal:
+                f.write(f"{r['kind']:<13} {r['dtype']:<5} {r['windows']:>7} {r['median_ms']:>8.2f} ms\n")
 
 
 if __name__ == "__main__":
