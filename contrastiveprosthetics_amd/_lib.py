@@ -158,6 +158,17 @@ SYMBOLS = {
                                              C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp]),
     "cp_online_multi_adapt_statistics": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, C.c_int32, _fp,
                                                    _fp]),
+    "cp_online_frontend_state_bytes": (C.c_size_t, []),
+    "cp_online_windows": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, C.c_int64, _fp, _fp, _fp]),
+    "cp_online_enroll_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "cp_online_enroll": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, C.c_int64, _fp, C.c_int32, _fp, _fp, C.c_size_t, _fp]),
+    "cp_online_adapt_enroll": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, C.c_int64, _fp, C.c_int32, _fp, _fp, C.c_size_t,
+                                         _fp]),
+    "cp_online_multi_enroll": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, _fp, C.c_int64, _fp, C.c_int32,
+                                         _fp, _fp, C.c_size_t, _fp]),
+    "cp_online_multi_adapt_enroll": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, C.c_int32, _fp, C.c_int64,
+                                               _fp, C.c_int32, _fp, _fp, C.c_size_t, _fp]),
+    "cp_online_enroll_table": (C.c_int, [_fp, C.c_int32, _fp, C.c_double, C.c_int32, _fp, _fp]),
 }
 
 KERNEL_KINDS = ["gather", "prep", "conv1_fwd", "bn_finalize", "conv2_fwd", "fold", "fc_fwd", "dropout", "proj_fwd",

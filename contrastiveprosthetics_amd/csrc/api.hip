@@ -24,6 +24,7 @@
 #include "online_adapt.cuh"
 #include "online_multi.cuh"
 #include "online_multi_adapt.cuh"
+#include "online_enroll.cuh"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* what) {
@@ -3224,5 +3225,203 @@ extern "C" int cp_online_multi_adapt_statistics(const cp_online_config* cfg, int
     if (!out) return fail(CP_ERR_ARG, "cp_online_multi_adapt_statistics: out is required");
     CK(hipMemcpyAsync(out, (unsigned char*)ws + olam_stream(m, index).stats, (size_t)OLAM_STATS * 8, hipMemcpyDeviceToDevice,
                       (hipStream_t)stream));
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// class enrolment (csrc/online_enroll.cuh): the front end alone, per-class sums of z / |z| in the caller's float64
+// accumulator, and the blend of those directions with the rows a decoder has
+// ---------------------------------------------------------------------------------------
+extern "C" size_t cp_online_frontend_state_bytes(void) { return align256(offsetof(OlState, K)); }
+
+extern "C" int cp_online_windows(const cp_online_config* cfg, void* state, size_t state_bytes, const float* raw, int64_t n_samples,
+                                 const float* mean_std, float* windows, void* stream) {
+    if (!cfg || !state) return fail(CP_ERR_ARG, "cp_online_windows: config and state are required");
+    if (int e = ol_check_config(cfg, state)) return e;
+    if (state_bytes < cp_online_frontend_state_bytes()) return fail(CP_ERR_ARG, "cp_online_windows: state too small");
+    if (n_samples < 0 || n_samples > (int64_t)CP_ONLINE_STRIDE * cfg->max_windows)
+        return fail(CP_ERR_ARG, "cp_online_windows: a call takes at most 20 * max_windows samples");
+    if (n_samples == 0) return 0;
+    if (!raw || !mean_std || !windows) return fail(CP_ERR_ARG, "cp_online_windows: raw, mean_std and windows are required");
+    if ((uintptr_t)raw % 4 || (uintptr_t)mean_std % 4 || (uintptr_t)windows % 4) return fail(CP_ERR_ARG, "cp_online_windows: misaligned input");
+    OlFrontArgs fa{};
+    fa.raw = raw; fa.n = n_samples; fa.st = (OlState*)state; fa.X = windows; fa.windows = nullptr; fa.mean_std = mean_std;
+    fa.n_coef = cfg->n_coef; fa.phase = cfg->phase; fa.gain = 1024.f;         // as ol_launch_frontend
+    for (int i = 0; i < cfg->n_coef; ++i) { fa.b[i] = cfg->b[i] / cfg->a[0]; fa.a[i] = cfg->a[i] / cfg->a[0]; }
+    if (cfg->n_coef == 9) hipLaunchKernelGGL((ole_windows_kernel<9>), dim3(1), dim3(256), 0, (hipStream_t)stream, fa);
+    else hipLaunchKernelGGL((ole_windows_kernel<0>), dim3(1), dim3(256), 0, (hipStream_t)stream, fa);
+    CKL("ole_windows_kernel");
+    return 0;
+}
+
+// enrolment scratch: the activations of one chunk of <= 256 windows (the adaptive form also conv2's operand and output)
+struct OleScratch {
+    size_t C1, R2, H0, H1, total;
+};
+static OleScratch ole_carve(int64_t n_windows, int dtype) {
+    const size_t es = dtype == CP_BF16 ? 2 : 4;
+    const size_t rows = (size_t)(((n_windows < OL_MAXM ? n_windows : OL_MAXM) + 15) / 16 * 16);
+    OleScratch c{};
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t r = o; o = align256(o + bytes); return r; };
+    c.C1 = take(rows * OL_C * OL_CONV_K * es);
+    c.R2 = take(rows * OL_C * 64 * 4);
+    c.H0 = take(rows * 768 * es);
+    c.H1 = take(rows * 512 * es);
+    c.total = o;
+    return c;
+}
+
+extern "C" size_t cp_online_enroll_scratch_bytes(int64_t n_windows, int32_t dtype) {
+    if (n_windows < 1) n_windows = 1;
+    return ole_carve(n_windows, dtype).total;
+}
+
+// what the four accumulate entries check alike; n_windows == 0 is a valid empty call (the caller returns 0)
+static int ole_check(const char* who, const float* windows, int64_t n_windows, const int32_t* slots, int32_t n_classes, double* acc,
+                     void* scratch, size_t scratch_bytes, int dtype, OleScratch* out) {
+    char msg[160];
+    auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", who, what); return fail(CP_ERR_ARG, msg); };
+    if (n_windows < 0 || n_windows > (int64_t)1 << 24) return bad("n_windows outside 0..2**24");
+    if (n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return bad("1..64 classes");
+    if (!acc) return bad("acc is required");
+    if ((uintptr_t)acc % 8) return bad("misaligned acc");
+    if (n_windows == 0) return 0;
+    if (!windows || !slots || !scratch) return bad("windows, slots and scratch are required");
+    if ((uintptr_t)windows % 4 || (uintptr_t)slots % 4 || (uintptr_t)scratch % 256) return bad("misaligned input or scratch");
+    *out = ole_carve(n_windows, dtype);
+    if (scratch_bytes < out->total) {
+        snprintf(msg, sizeof msg, "%s: scratch too small", who);
+        return fail(CP_ERR_WORKSPACE, msg);
+    }
+    return 0;
+}
+
+template <typename T>
+static int ole_accumulate(const void* act, const void* pw, const float* pb, const int32_t* slots, int m, int n_classes, double* acc,
+                          hipStream_t st) {
+    OleAccArgs a{};
+    a.proj.act = act; a.proj.w = pw; a.proj.bias = pb; a.proj.K = 512; a.proj.F = CP_D_E;
+    a.slots = slots; a.acc = acc; a.M = m; a.n_classes = n_classes;
+    hipLaunchKernelGGL((ole_accumulate_kernel<T>), dim3(1), dim3(OL_THREADS), 0, st, a);
+    CKL("ole_accumulate_kernel");
+    return 0;
+}
+
+// the folded encoder of online_push_t over the caller's windows, chunk by chunk
+template <typename T>
+static int online_enroll_t(unsigned char* base, const OlWS& w, const float* x, int64_t N, const int32_t* slots, int n_classes,
+                           double* acc, unsigned char* sc, const OleScratch& k, hipStream_t st) {
+    for (int64_t r0 = 0; r0 < N; r0 += OL_MAXM) {
+        const int m = (int)(N - r0 < OL_MAXM ? N - r0 : OL_MAXM);
+        OlLayerArgs la{};
+        la.x = x + r0 * OL_C; la.c1w = (const float*)(base + w.c1w); la.c1b = (const float*)(base + w.c1b);
+        la.w = base + w.c2w; la.bias = (const float*)(base + w.c2b); la.out = sc + k.H0; la.K = OL_CONV_K; la.F = 64; la.ldo = 768;
+        la.out_pos = 64;
+        hipLaunchKernelGGL((ole_layer_kernel<T, true>), dim3(4, OL_C), dim3(OL_THREADS), 0, st, la, m);
+        CKL("ole_layer_kernel<conv>");
+        for (int i = 0; i < CP_N_FC; ++i) {               // H0 -> H1 -> H0 ...: fc7 leaves its output in H1
+            la.act = sc + (i % 2 == 0 ? k.H0 : k.H1);
+            la.out = sc + (i % 2 == 0 ? k.H1 : k.H0);
+            la.w = base + w.fcw[i]; la.bias = (const float*)(base + w.fcb[i]); la.K = fcK(i); la.F = 512; la.ldo = 512; la.out_pos = 0;
+            hipLaunchKernelGGL((ole_layer_kernel<T, false>), dim3(512 / 16), dim3(OL_THREADS), 0, st, la, m);
+            CKL("ole_layer_kernel<fc>");
+        }
+        if (int e = ole_accumulate<T>(sc + k.H1, base + w.pw, (const float*)(base + w.pb), slots + r0, m, n_classes, acc, st)) return e;
+    }
+    return 0;
+}
+
+// the unfolded encoder with the statistics frozen (the OLA_FROZEN pass of online_adapt_calibrate_t), chunk by chunk
+template <typename T>
+static int online_adapt_enroll_t(unsigned char* base, const OlaWS& w, const float* x, int64_t N, const int32_t* slots, int n_classes,
+                                 double* acc, unsigned char* sc, const OleScratch& k, hipStream_t st) {
+    const OlState* state = (const OlState*)(base + w.state);
+    for (int64_t r0 = 0; r0 < N; r0 += OL_MAXM) {
+        const int m = (int)(N - r0 < OL_MAXM ? N - r0 : OL_MAXM);
+        if (int e = ola_conv_chain<T>(base, w, state, x + r0 * OL_C, m, m, sc + k.C1, (float*)(sc + k.R2), sc + k.H0,
+                                      ola_bn(base, w, 0, OLA_FROZEN, nullptr, 0, 0), ola_bn(base, w, 1, OLA_FROZEN, nullptr, 0, 0), st))
+            return e;
+        for (int i = 0; i < CP_N_FC; ++i)                 // H0 -> H1 -> H0 ...: fc7 leaves its output in H1
+            if (int e = ola_fc<T>(base, w, state, i, sc + (i % 2 == 0 ? k.H0 : k.H1), sc + (i % 2 == 0 ? k.H1 : k.H0), m,
+                                  ola_bn(base, w, i + 2, OLA_FROZEN, nullptr, 0, 0), st))
+                return e;
+        if (int e = ole_accumulate<T>(sc + k.H1, base + w.pw, (const float*)(base + w.pb), slots + r0, m, n_classes, acc, st)) return e;
+    }
+    return 0;
+}
+
+extern "C" int cp_online_enroll(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* windows, int64_t n_windows,
+                                const int32_t* slots, int32_t n_classes, double* acc, void* scratch, size_t scratch_bytes, void* stream) {
+    OlWS w;
+    if (int e = ol_check(cfg, ws, ws_bytes, &w)) return e;
+    OleScratch k;
+    if (int e = ole_check("cp_online_enroll", windows, n_windows, slots, n_classes, acc, scratch, scratch_bytes, cfg->dtype, &k)) return e;
+    if (n_windows == 0) return 0;
+    unsigned char* base = (unsigned char*)ws;
+    if (cfg->dtype == CP_BF16)
+        return online_enroll_t<bf16_t>(base, w, windows, n_windows, slots, n_classes, acc, (unsigned char*)scratch, k, (hipStream_t)stream);
+    return online_enroll_t<float>(base, w, windows, n_windows, slots, n_classes, acc, (unsigned char*)scratch, k, (hipStream_t)stream);
+}
+
+extern "C" int cp_online_adapt_enroll(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* windows, int64_t n_windows,
+                                      const int32_t* slots, int32_t n_classes, double* acc, void* scratch, size_t scratch_bytes,
+                                      void* stream) {
+    OlaWS w;
+    if (int e = ola_check(cfg, ws, ws_bytes, &w)) return e;
+    OleScratch k;
+    if (int e = ole_check("cp_online_adapt_enroll", windows, n_windows, slots, n_classes, acc, scratch, scratch_bytes, cfg->dtype, &k))
+        return e;
+    if (n_windows == 0) return 0;
+    unsigned char* base = (unsigned char*)ws;
+    if (cfg->dtype == CP_BF16)
+        return online_adapt_enroll_t<bf16_t>(base, w, windows, n_windows, slots, n_classes, acc, (unsigned char*)scratch, k,
+                                             (hipStream_t)stream);
+    return online_adapt_enroll_t<float>(base, w, windows, n_windows, slots, n_classes, acc, (unsigned char*)scratch, k, (hipStream_t)stream);
+}
+
+extern "C" int cp_online_multi_enroll(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                      const float* windows, int64_t n_windows, const int32_t* slots, int32_t n_classes, double* acc,
+                                      void* scratch, size_t scratch_bytes, void* stream) {
+    OlmWS m;
+    if (int e = olm_check(cfg, n_streams, max_rows, ws, ws_bytes, &m)) return e;
+    OleScratch k;
+    if (int e = ole_check("cp_online_multi_enroll", windows, n_windows, slots, n_classes, acc, scratch, scratch_bytes, cfg->dtype, &k))
+        return e;
+    if (n_windows == 0) return 0;
+    unsigned char* base = (unsigned char*)ws;
+    if (cfg->dtype == CP_BF16)
+        return online_enroll_t<bf16_t>(base, m.w, windows, n_windows, slots, n_classes, acc, (unsigned char*)scratch, k, (hipStream_t)stream);
+    return online_enroll_t<float>(base, m.w, windows, n_windows, slots, n_classes, acc, (unsigned char*)scratch, k, (hipStream_t)stream);
+}
+
+extern "C" int cp_online_multi_adapt_enroll(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                            int32_t index, const float* windows, int64_t n_windows, const int32_t* slots,
+                                            int32_t n_classes, double* acc, void* scratch, size_t scratch_bytes, void* stream) {
+    OlamWS m;
+    if (int e = olam_check(cfg, n_streams, max_rows, ws, ws_bytes, &m)) return e;
+    if (int e = olam_index(index, n_streams, "cp_online_multi_adapt_enroll")) return e;
+    OleScratch k;
+    if (int e = ole_check("cp_online_multi_adapt_enroll", windows, n_windows, slots, n_classes, acc, scratch, scratch_bytes, cfg->dtype, &k))
+        return e;
+    if (n_windows == 0) return 0;
+    unsigned char* base = (unsigned char*)ws;
+    const OlaWS w = olam_stream(m, index);
+    if (cfg->dtype == CP_BF16)
+        return online_adapt_enroll_t<bf16_t>(base, w, windows, n_windows, slots, n_classes, acc, (unsigned char*)scratch, k,
+                                             (hipStream_t)stream);
+    return online_adapt_enroll_t<float>(base, w, windows, n_windows, slots, n_classes, acc, (unsigned char*)scratch, k, (hipStream_t)stream);
+}
+
+extern "C" int cp_online_enroll_table(const double* acc, int32_t n_classes, const float* prior, double mix, int32_t min_windows,
+                                      float* table, void* stream) {
+    if (!acc || !prior || !table) return fail(CP_ERR_ARG, "cp_online_enroll_table: acc, prior and table are required");
+    if ((uintptr_t)acc % 8 || (uintptr_t)prior % 4 || (uintptr_t)table % 4) return fail(CP_ERR_ARG, "cp_online_enroll_table: misaligned input");
+    if (n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return fail(CP_ERR_ARG, "cp_online_enroll_table: 1..64 classes");
+    if (!(mix >= 0.0 && mix <= 1.0)) return fail(CP_ERR_ARG, "cp_online_enroll_table: mix outside [0, 1]");
+    if (min_windows < 1) return fail(CP_ERR_ARG, "cp_online_enroll_table: min_windows must be at least 1");
+    hipLaunchKernelGGL(ole_table_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, acc, (int)n_classes, prior, mix, (double)min_windows,
+                       table);
+    CKL("ole_table_kernel");
     return 0;
 }

@@ -179,7 +179,152 @@ def _calibration_windows(raw: torch.Tensor, b, a, phase: int, mean_std: torch.Te
     return normalize_(w.contiguous(), mean_std[0], mean_std[1])[0]
 
 
-class OnlineDecoder:
+# ---------------------------------------------------------------------------------------------------------------------------
+# class enrolment: per-user class rows from the user's own labelled recording (cp_online_*enroll*, csrc/online_enroll.cuh)
+# ---------------------------------------------------------------------------------------------------------------------------
+def window_labels(labels, phase: int = 0) -> np.ndarray:
+    """The label of each window of a recording with one label per raw sample (a class id, or a negative value for "not
+    labelled"; what Ninapro's `restimulus` is): window k covers the raw samples phase + 20 k .. phase + 20 k + 2 WINDOW_EDGE and
+    takes their label if all 11 carry the same non-negative label, else -1.  (K,) int64 with K = windows_before(n, phase).
+    Host only (numpy)."""
+    lab = np.asarray(labels)
+    if lab.ndim != 1 or lab.dtype.kind not in "iu":
+        raise ValueError("labels must be a 1-d integer array: one class id (or a negative value) per raw sample")
+    if not 0 <= int(phase) < STRIDE:
+        raise ValueError(f"phase must lie in 0..{STRIDE - 1}")
+    lab = lab.astype(np.int64)
+    k = windows_before(lab.shape[0], int(phase))
+    if k == 0:
+        return np.zeros(0, dtype=np.int64)
+    span = lab[(int(phase) + STRIDE * np.arange(k))[:, None] + np.arange(2 * WINDOW_EDGE + 1)]
+    same = (span == span[:, :1]).all(axis=1) & (span[:, 0] >= 0)
+    return np.where(same, span[:, 0], -1)
+
+
+def recording_windows(raw: torch.Tensor, mean_std: torch.Tensor, b=None, a=None, phase: int = 0) -> torch.Tensor:
+    """The windows a fresh stream emits for `raw` (n, 12) f32 on the GPU, (K, 12) with K = windows_before(n, phase): one pass
+    of the stateful front end (cp_online_windows) over the recording, bit-identical to the offline path
+    (`preprocess_segments` + `normalize_`), which filters the recording again for every 256 positions it keeps.  mean_std
+    (2, 12) f32 on the GPU."""
+    if not isinstance(raw, torch.Tensor) or raw.device.type != "cuda" or raw.dtype != torch.float32 or raw.dim() != 2 \
+            or raw.shape[1] != EMG_DIM:
+        raise ValueError("raw must be an (n, 12) float32 tensor on the GPU")
+    if not 0 <= int(phase) < STRIDE:
+        raise ValueError(f"phase must lie in 0..{STRIDE - 1}")
+    b, a = _filter(b, a)
+    lib = _lib.load()
+    cfg = _config("f32", _lib.CP_ONLINE_MAX_WINDOWS, 1, int(phase), b, a)
+    raw = raw.contiguous()
+    mean_std = mean_std.to(device=raw.device, dtype=torch.float32).contiguous()
+    if tuple(mean_std.shape) != (2, EMG_DIM):
+        raise ValueError("mean_std must be (2, 12)")
+    n = raw.shape[0]
+    out = torch.empty(max(windows_before(n, phase), 1), EMG_DIM, dtype=torch.float32, device=raw.device)
+    state = torch.zeros(lib.cp_online_frontend_state_bytes(), dtype=torch.uint8, device=raw.device)
+    stream = torch.cuda.current_stream(raw.device).cuda_stream
+    step = STRIDE * _lib.CP_ONLINE_MAX_WINDOWS
+    for s in range(0, n, step):
+        m = min(step, n - s)
+        row = windows_before(s, phase)                         # 20 W samples complete at most W windows: out has the room
+        _lib.check(lib.cp_online_windows(C.byref(cfg), state.data_ptr(), state.numel(), raw[s:].data_ptr(), m, mean_std.data_ptr(),
+                                         out[row:].data_ptr() if row < out.shape[0] else out.data_ptr(), stream),
+                   "cp_online_windows")
+    return out[:windows_before(n, phase)]
+
+
+class _Enrolment:
+    """the accumulator of one decoder (or stream): acc (64, 17) float64 on the device, laid out by `ids` (ascending), and the
+    window counts per slot as the host knows them"""
+
+    def __init__(self, ids: np.ndarray, device):
+        self.ids = ids.astype(np.int64)
+        self.counts = np.zeros(ids.shape[0], dtype=np.int64)
+        self.acc = torch.zeros(MAX_CLASSES, 17, dtype=torch.float64, device=device)
+
+
+def _sample_labels(labels, n: int) -> np.ndarray:
+    if isinstance(labels, torch.Tensor):
+        if labels.is_floating_point() or labels.dtype == torch.bool:
+            raise ValueError("labels must be integers: one class id (or a negative value) per raw sample")
+        labels = labels.detach().cpu().numpy()
+    lab = np.asarray(labels)
+    if lab.dtype.kind not in "iu":
+        raise ValueError("labels must be integers: one class id (or a negative value) per raw sample")
+    if lab.ndim != 1 or lab.shape[0] != n:
+        raise ValueError(f"labels must hold one entry per raw sample ({n}), got shape {tuple(lab.shape)}")
+    return lab.astype(np.int64)
+
+
+class _EnrollMixin:
+    """`enroll` of the online decoders.  `key` is None (OnlineDecoder) or a stream index; a decoder supplies _enroll_view,
+    _enroll_call and _enroll_install."""
+
+    def _enroll(self, key, raw, labels, mix, min_windows, add, accumulate):
+        ids_cur, prior, calibrated = self._enroll_view(key)
+        if ids_cur is None:
+            raise _lib.CpNativeError("enroll() needs a class table: set_classes() first (it is the prior and the id list)")
+        if not calibrated:
+            raise _lib.CpNativeError("an AdaBN model has no BatchNorm statistics: calibrate() first, then enroll()")
+        if not 0.0 <= float(mix) <= 1.0:
+            raise ValueError("mix must lie in [0, 1]")
+        if int(min_windows) < 1:
+            raise ValueError("min_windows must be at least 1")
+        if not isinstance(raw, torch.Tensor) or raw.device.type != "cuda" or raw.dtype != torch.float32 or raw.dim() != 2 \
+                or raw.shape[1] != EMG_DIM:
+            raise ValueError("raw must be an (n, 12) float32 tensor on the GPU")
+        wl = window_labels(_sample_labels(labels, raw.shape[0]), self.phase)
+        keep = np.nonzero(wl >= 0)[0]
+        if keep.size == 0:
+            raise ValueError("the recording has no labelled window: a window needs 11 samples in a row of one non-negative label")
+        rec = self._enroll_rec.get(key)
+        old_ids = rec.ids if rec is not None else ids_cur
+        new = np.setdiff1d(np.unique(wl[keep]), old_ids)
+        if new.size and not add:
+            raise ValueError(f"labels hold class ids the decoder does not have: {new.tolist()} (add=True enrols them as new classes)")
+        ids = np.union1d(old_ids, new)
+        if ids.size > MAX_CLASSES:
+            raise ValueError(f"at most {MAX_CLASSES} classes, got {ids.size}")
+        if int(ids.max()) >= 2 ** 31:
+            raise ValueError("class ids must fit int32")
+        counts = np.zeros(ids.size, dtype=np.int64)
+        if rec is not None:
+            counts[np.searchsorted(ids, rec.ids)] = rec.counts
+        slots = np.searchsorted(ids, wl[keep])
+        counts += np.bincount(slots, minlength=ids.size)
+        if not accumulate:
+            short = [int(i) for i, c in zip(ids, counts) if i not in set(ids_cur.tolist()) and c < int(min_windows)]
+            if short:
+                raise ValueError(f"new classes {short} have fewer than min_windows={int(min_windows)} windows: a new class has no "
+                                 "prior row to fall back on")
+        # ---- everything is checked: from here on work is enqueued
+        if rec is None:
+            rec = _Enrolment(ids, self.device)
+        elif ids.size != rec.ids.size:                       # new classes: the slots of the old ones move
+            acc = torch.zeros_like(rec.acc)
+            acc[torch.as_tensor(np.searchsorted(ids, rec.ids), device=self.device)] = rec.acc[:rec.ids.size]
+            rec.acc, rec.ids = acc, ids
+        rec.counts = counts
+        self._enroll_rec[key] = rec
+        w = recording_windows(raw, self.mean_std, self._b, self._a, self.phase)
+        w = w[torch.as_tensor(keep, device=self.device)].contiguous()
+        slots_dev = torch.as_tensor(slots.astype(np.int32), device=self.device)
+        scratch = torch.empty(self.lib.cp_online_enroll_scratch_bytes(w.shape[0], self._cfg.dtype), dtype=torch.uint8, device=self.device)
+        self._enroll_call(key, w.data_ptr(), int(w.shape[0]), slots_dev.data_ptr(), int(ids.size), rec.acc.data_ptr(),
+                          scratch.data_ptr(), scratch.numel())
+        out = {int(i): int(c) for i, c in zip(ids, counts)}
+        if accumulate:
+            return out
+        full = torch.zeros(ids.size, CP_D_E, dtype=torch.float32, device=self.device)       # a zero row: no prior (a new class)
+        full[torch.as_tensor(np.searchsorted(ids, ids_cur), device=self.device)] = prior
+        table = torch.empty_like(full)
+        _lib.check(self.lib.cp_online_enroll_table(rec.acc.data_ptr(), int(ids.size), full.data_ptr(), C.c_double(float(mix)),
+                                                   int(min_windows), table.data_ptr(), self._stream()), "cp_online_enroll_table")
+        self._enroll_install(key, table, ids)                  # (set_classes drops the accumulator: it is kept across this one)
+        self._enroll_rec[key] = rec
+        return out
+
+
+class OnlineDecoder(_EnrollMixin):
     """Streaming decoder over a trained model (eval mode, stock BatchNorm with running statistics).
 
     model_or_engine: `Model` or `Engine`; mean, std: the normalisation of the training data (`build_emg_tensor` / `emg_stats`);
@@ -225,6 +370,7 @@ class OnlineDecoder:
         self.ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
         self.n_seen = 0
         self.class_ids: Optional[torch.Tensor] = None
+        self._enroll_rec = {}
         self.refresh()
         if classes is not None:
             self.set_classes(classes)
@@ -272,6 +418,7 @@ class OnlineDecoder:
         tab, ids_t = _class_table(self.engine, classes, glove, table, ids)
         self._source = (classes, glove, table, ids)
         self._table = tab
+        self._enroll_rec.clear()                               # the accumulator is laid out by the id list
         self.class_ids = ids_t.to(torch.int32)
         self._ids_dev = self.class_ids.to(self.device)
         _lib.check(self.lib.cp_online_set_classes(C.byref(self._cfg), *self._ws(), self._table.data_ptr(), self._ids_dev.data_ptr(),
@@ -327,6 +474,52 @@ class OnlineDecoder:
         if return_windows:
             res.append(cat(3))
         return tuple(res)
+
+    # ------------------------------------------------------------------ class enrolment
+    def enroll(self, raw: torch.Tensor, labels, *, mix: float = 1.0, min_windows: int = 25, add: bool = False,
+               accumulate: bool = False) -> dict:
+        """Class rows from the user's own signals (cosine prototypes, no gradient).  raw (n, 12) f32 on the GPU: a cued
+        recording of the user, a stream of its own (the live filter state, sample count and vote ring are not touched);
+        labels (n,) integers: the class id each raw sample was cued with, negative for "not labelled" (`window_labels` gives
+        the rule).  Every labelled window's z / |z| -- computed as a push computes it; the adaptive form with its current
+        statistics frozen, whatever alpha is -- is added to a float64 accumulator per class, in window order.  Then each class
+        with at least `min_windows` windows gets the row (1 - mix) E_c + mix S_c / |S_c| (E_c: its current unit row, S_c: its
+        sum); the others keep their row.  mix = 0 reproduces the current table exactly.  The new table goes in as
+        `set_classes(table=...)` does: the vote ring empties and `refresh()` no longer derives the table from the model.
+
+        add: a label that is not in `class_ids` is a ValueError, or with add=True a new class whose row is its prototype
+        alone (it needs min_windows windows; at most 64 classes in all).  accumulate=True only adds to the accumulator and
+        leaves the table alone, so several recordings can be enrolled before the table changes; the accumulator lives until
+        `enroll_reset()` or the next `set_classes()`.  Returns {class id: windows accumulated so far}.
+
+        Prototypes belong to the weights and statistics they were taken with: enrol after `calibrate()`, and again (after
+        `enroll_reset()`) after a `refresh()` that changed the weights."""
+        return self._enroll(None, raw, labels, mix, min_windows, add, accumulate)
+
+    def enroll_reset(self):
+        """Forget the windows accumulated so far (the class table stays)."""
+        self._enroll_rec.clear()
+
+    def class_table(self):
+        """(rows (K, 16) f32 on the GPU, ids (K,) int32): the class table as `set_classes(table=rows, ids=ids)` takes it, so a
+        user's table can be stored and put back; the decoder normalises the rows the same way each time, and a table put
+        back decodes bit for bit as this one does."""
+        if self.class_ids is None:
+            raise _lib.CpNativeError("set_classes() first")
+        return self._table.clone(), self.class_ids.clone()
+
+    def _enroll_view(self, key):
+        if self.class_ids is None:
+            return None, None, self.calibrated
+        return self.class_ids.numpy().astype(np.int64), self._table, self.calibrated
+
+    def _enroll_call(self, key, *args):
+        fn, name = (self.lib.cp_online_enroll, "cp_online_enroll") if self.adapt is None \
+            else (self.lib.cp_online_adapt_enroll, "cp_online_adapt_enroll")
+        _lib.check(fn(C.byref(self._cfg), *self._ws(), *args, self._stream()), name)
+
+    def _enroll_install(self, key, table, ids):
+        self.set_classes(table=table, ids=ids)
 
     # ------------------------------------------------------------------ adaptive form
     def _need_adapt(self, what: str):
@@ -407,7 +600,7 @@ def plan_push(n_seen, counts, phase: int, max_windows: int, max_rows: int):
     return rounds
 
 
-class _MultiStreamBase:
+class _MultiStreamBase(_EnrollMixin):
     """What the multi-stream decoders share: settings, workspace, per-stream class tables and sample counts, packing and
     splitting of pushes.  Subclasses name their C entries (_ENTRY: cp_online_multi or cp_online_multi_adapt) and prepare."""
     _WHO = "MultiStreamDecoder"
@@ -443,6 +636,7 @@ class _MultiStreamBase:
         self._has_table = np.zeros(self.n_streams, dtype=bool)
         self._k = [0] * self.n_streams                     # classes per stream
         self._counts_cache = None
+        self._enroll_rec = {}
 
     # ------------------------------------------------------------------ helpers
     def _stream(self) -> int:
@@ -483,6 +677,38 @@ class _MultiStreamBase:
         self.class_ids[s] = ids32
         self._has_table[s] = True
         self._k[s] = int(ids32.numel())
+        self._enroll_rec.pop(s, None)                          # the accumulator is laid out by the id list
+
+    def enroll(self, stream: int, raw: torch.Tensor, labels, *, mix: float = 1.0, min_windows: int = 25, add: bool = False,
+               accumulate: bool = False) -> dict:
+        """`OnlineDecoder.enroll` for one stream: its class table becomes, bit for bit, the one its own `OnlineDecoder` gets
+        from the same call; no other stream's table, state or statistics change."""
+        return self._enroll(self._index(stream), raw, labels, mix, min_windows, add, accumulate)
+
+    def enroll_reset(self, stream: int):
+        """Forget the windows accumulated for one stream (its class table stays)."""
+        self._enroll_rec.pop(self._index(stream), None)
+
+    def class_table(self, stream: int):
+        """(rows (K, 16) f32 on the GPU, ids (K,) int32) of one stream, as `OnlineDecoder.class_table`."""
+        s = self._index(stream)
+        if not self._has_table[s]:
+            raise _lib.CpNativeError(f"stream {s} has no class table: set_classes({s}, ...) first")
+        return self._tables[s][0].clone(), self.class_ids[s].clone()
+
+    def _enroll_calibrated(self, s: int) -> bool:
+        return True
+
+    def _enroll_view(self, s):
+        if not self._has_table[s]:
+            return None, None, self._enroll_calibrated(s)
+        return self.class_ids[s].numpy().astype(np.int64), self._tables[s][0], self._enroll_calibrated(s)
+
+    def _enroll_call(self, s, *args):
+        _lib.check(self.lib.cp_online_multi_enroll(*self._args(), *args, self._stream()), "cp_online_multi_enroll")
+
+    def _enroll_install(self, s, table, ids):
+        self.set_classes(s, table=table, ids=ids)
 
     def reset(self, streams=None):
         """Start new streams: filter, RMS history, sample count and vote ring of the listed streams (default: all) to zero;
@@ -669,6 +895,12 @@ class AdaptiveMultiStreamDecoder(_MultiStreamBase):
             s = int(bad[0])
             raise _lib.CpNativeError(f"stream {s} is uncalibrated (an AdaBN model has no BatchNorm statistics): "
                                      f"calibrate({s}, raw) first")
+
+    def _enroll_calibrated(self, s: int) -> bool:
+        return bool(self.calibrated[s])
+
+    def _enroll_call(self, s, *args):
+        _lib.check(self.lib.cp_online_multi_adapt_enroll(*self._args(), s, *args, self._stream()), "cp_online_multi_adapt_enroll")
 
     # ------------------------------------------------------------------ API
     def refresh(self):

@@ -551,6 +551,62 @@ int cp_online_multi_adapt_push(const cp_online_config* cfg, int32_t n_streams, i
 int cp_online_multi_adapt_statistics(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
                                      int32_t index, double* out, void* stream);
 
+/* ---- class enrolment: per-user class rows (cosine prototypes) for the online decoders, without a gradient ----------------
+ * The logits of a decoder are cosines z^ . E^_c, so the row that serves one user best for class c is the mean direction of
+ * that user's own z^ = z / |z| over windows of c.  Enrolment takes a labelled recording of the user, sums z^ per class into a
+ * caller-owned accumulator and blends the summed directions with the rows the decoder has.
+ * Windows and labels.  A recording is raw (n,12) f32 with one label per raw sample: a class id, or a negative value for "not
+ * labelled".  It is a fresh stream of its own (cp_online_windows on a zeroed state): the decoder's filter state, sample count
+ * and vote ring are not touched.  Window k (RMS-series position phase + 20 k) covers the raw samples phase + 20 k ..
+ * phase + 20 k + 10; it takes their label if all 11 carry the same non-negative label, else it is skipped.  The caller maps
+ * labels to slots: slot = position of the class id in the ascending id list of cp_online_set_classes.
+ * Embedding.  z of a window is what the decoder's own push computes for it: the folded weights (cp_online_enroll,
+ * cp_online_multi_enroll), or the unfolded weights with the stream's current statistics frozen, whatever its alpha
+ * (cp_online_adapt_enroll, cp_online_multi_adapt_enroll); enrolment never moves statistics.  The layers run through the
+ * device functions of the push, a row's value does not depend on the tile, chunk or call it falls in, and z^ is
+ * z / sqrtf(sum z^2) in f32 as in the push's tail.
+ * Accumulator.  acc (64,17) float64 on the device, zeroed by the caller before the first call: per slot 16 sums of z^ (the
+ * f32 values widened) and the window count.  Every (slot, dimension) sum takes one float64 add per window, in window order
+ * (no atomics, no reduction across workgroups), so acc after any sequence of calls depends only on the sequence of (window,
+ * slot) pairs, not on how it was cut into calls or chunks.  Windows whose slot lies outside 0..n_classes-1 are skipped.
+ * Several recordings accumulate into one acc.
+ * Table.  With E^_c = prior_c / |prior_c| (f32, as cp_online_set_classes normalises) and S_c the sums of slot c, a slot with
+ * count >= min_windows and |S_c| > 0 gets the direction (1 - mix) E^_c + mix S_c / |S_c|, mix in [0, 1], computed in float64
+ * and written at the prior's length, table_c = (1 - mix) prior_c + mix |prior_c| S_c / |S_c|; every other slot gets prior_c.
+ * So mix = 0, and a slot that is not enrolled, return prior_c bit for bit, and cp_online_set_classes of `table` (which
+ * normalises the rows and empties the vote ring) then reproduces the row the decoder had exactly.  A zero prior row has no
+ * direction: its row is S_c / |S_c| alone (a class the decoder did not have).
+ * None of these entries allocates, synchronises or keeps state in the library; each validates on the host and returns
+ * CP_ERR_ARG before anything is enqueued. */
+/* bytes of the caller-owned front-end state of cp_online_windows; zero it to start a recording */
+size_t cp_online_frontend_state_bytes(void);
+/* the front end of a push alone (one launch): raw (n_samples,12) f32, at most 20 * cfg.max_windows samples, the next chunk of the
+ * recording whose state (256-byte aligned) the caller holds -> the c(n_seen + n_samples) - c(n_seen) windows the chunk
+ * completes, (M,12) f32 from row 0 of `windows`, bit-identical to those of cp_online_push */
+int cp_online_windows(const cp_online_config* cfg, void* state, size_t state_bytes, const float* raw, int64_t n_samples,
+                      const float* mean_std, float* windows, void* stream);
+/* bytes of the caller-owned scratch of an accumulate call over n_windows windows (the activations of one chunk of <= 256) */
+size_t cp_online_enroll_scratch_bytes(int64_t n_windows, int32_t dtype);
+/* windows (n_windows,12) f32 as a push makes them, slots (n_windows) int32, acc (64,17) float64: adds the windows to acc in
+ * order, in chunks of <= 256 windows (8 encoder launches and ole_accumulate_kernel per chunk; the adaptive forms 10 and
+ * ole_accumulate_kernel).  n_windows == 0 is a valid empty call.  ws: the decoder's workspace, prepared. */
+int cp_online_enroll(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* windows, int64_t n_windows,
+                     const int32_t* slots, int32_t n_classes, double* acc, void* scratch, size_t scratch_bytes, void* stream);
+/* on an adaptive workspace: the statistics as they are, frozen */
+int cp_online_adapt_enroll(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* windows, int64_t n_windows,
+                           const int32_t* slots, int32_t n_classes, double* acc, void* scratch, size_t scratch_bytes, void* stream);
+/* on a multi-stream workspace: the folded weights are shared, so there is no stream index */
+int cp_online_multi_enroll(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                           const float* windows, int64_t n_windows, const int32_t* slots, int32_t n_classes, double* acc,
+                           void* scratch, size_t scratch_bytes, void* stream);
+/* on an adaptive multi-stream workspace: the frozen statistics of stream `index` */
+int cp_online_multi_adapt_enroll(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                 int32_t index, const float* windows, int64_t n_windows, const int32_t* slots, int32_t n_classes,
+                                 double* acc, void* scratch, size_t scratch_bytes, void* stream);
+/* acc (64,17) float64, prior (n_classes,16) f32 -> table (n_classes,16) f32 (see Table above); all on the device */
+int cp_online_enroll_table(const double* acc, int32_t n_classes, const float* prior, double mix, int32_t min_windows, float* table,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,11 @@ decoders pushing one after another, for S in 1, 8, 64, 256 streams of 1 and 25 w
 With --streams --adapt the adaptive multi-stream decoder (AdaptiveMultiStreamDecoder.push, csrc/online_multi_adapt.cuh, alpha
 0.01) is timed against S OnlineDecoder(adapt=0.01) pushing one after another and against the folded MultiStreamDecoder at
 the same S, plus the library part of calibrate(stream) on 6,000 windows (cp_online_multi_adapt_calibrate alone).
+With --enroll class enrolment (OnlineDecoder.enroll, csrc/online_enroll.cuh) is measured: (a) enroll() of 41 classes x 500
+windows, split into windows / accumulate / table, next to the same table composed from the offline windows, the engine's
+eval forward and index_add_; (b) recording_windows against the offline windows on a 60 s recording; (c) on synthetic people
+(a channel-amplitude pattern per class times a gain pattern per person) the accuracy of the model's one-hot rows and of
+enrolled rows on a held-out recording of a person the model has not seen.
 Each push is timed from the host with a synchronisation behind it (the latency a control loop sees); kernels per push are
 counted with torch.profiler over a few pushes.  One JSON line per case, and a table with --out.
 
@@ -19,6 +24,7 @@ counted with torch.profiler over a few pushes.  One JSON line per case, and a ta
     python tools/online_bench.py --adapt --iters 200 --out profiles/online_adapt_latency.txt
     python tools/online_bench.py --streams --iters 50 --out profiles/online_multi_latency.txt
     python tools/online_bench.py --streams --adapt --iters 100 --out profiles/online_multi_adapt_latency.txt
+    python tools/online_bench.py --enroll --iters 10 --out profiles/online_enroll.txt
 """
 import argparse
 import json
@@ -70,7 +76,10 @@ def main():
     ap.add_argument("--adapt", action="store_true", help="adaptive form against the folded decoder, and calibrate()")
     ap.add_argument("--streams", action="store_true", help="multi-stream decoder against S single-stream decoders in turn")
     ap.add_argument("--counts", default="1,8,64,256", help="--streams: stream counts")
+    ap.add_argument("--enroll", action="store_true", help="class enrolment: time, one-pass windows, accuracy on a synthetic person")
     a = ap.parse_args()
+    if a.enroll:
+        return enroll_main(a)
     torch.manual_seed(0)
     e = Engine(adabn=False, dtype="f32", device="cuda:0")
     e.init_parameters(1)
@@ -126,6 +135,160 @@ def main():
             for r in rows:
                 f.write(f"{r['kind']:<12} {r['dtype']:<5} {r['samples']:>7} {r['windows']:>7} {r['median_us']:>10.1f} "
                         f"{r['p90_us']:>9.1f} {r['kernels_per_push']:>8.1f}\n")
+
+
+def _cue_recording(rng, pattern, gain, windows_per_class, order):
+    """a cued recording of one synthetic person: per class a block of 20 * windows_per_class + 10 samples of noise with the
+    class's channel amplitudes times the person's channel gains, 100 unlabelled samples in between"""
+    raws, labs = [], []
+    for c in order:
+        n = 20 * windows_per_class + 10
+        raws += [rng.standard_normal((100, 12)) * gain, rng.standard_normal((n, 12)) * pattern[c] * gain]
+        labs += [np.full(100, -1), np.full(n, c)]
+    raw = torch.from_numpy((np.concatenate(raws) * 2e-3).astype(np.float32)).cuda()
+    return raw, np.concatenate(labs).astype(np.int64)
+
+
+def _wall(fn, iters, warmup=2):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(iters):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    return float(np.median(ts)) * 1e3
+
+
+def enroll_main(a):
+    import ctypes as C
+    from contrastiveprosthetics_amd.online import _calibration_windows, recording_windows, window_labels
+    torch.manual_seed(0)
+    rng = np.random.default_rng(0)
+    classes = list(range(41))
+    pattern = rng.uniform(0.4, 3.0, (41, 12))
+    people = np.exp(rng.normal(0.0, 0.35, (10, 12)))              # per-person channel gains; person 9 is never trained on
+    params = dict(d_e=16, lr_emg=1e-3, reg_emg=1e-5, dp_emg=0.0, lr_glove=1e-3, reg_glove=1e-6, dp_glove=0.0)
+    e = Engine(adabn=False, dtype="f32", device="cuda:0")
+    e.init_parameters(1)
+    raw0, _ = _cue_recording(rng, pattern, people[0], 30, classes)
+    ident = torch.stack([torch.zeros(12), torch.ones(12)]).cuda()  # (r - 0) / 1: the RMS windows as they are
+    w0 = recording_windows(raw0, ident)
+    mean, std = w0.mean(0), w0.std(0)
+    lines = []
+
+    def out(r):
+        print(json.dumps(r), flush=True)
+        lines.append(r)
+
+    # (c) first, so that (a) and (b) run on the trained model: train on people 0..8, one window per class and group
+    probe = OnlineDecoder(e, mean, std, classes=classes)
+    train = []
+    for p in range(9):
+        raw, lab = _cue_recording(rng, pattern, people[p], 40, classes)
+        w = recording_windows(raw, probe.mean_std, probe._b, probe._a, 0)
+        wl = window_labels(lab, 0)
+        train.append(torch.stack([w[torch.as_tensor(np.nonzero(wl == c)[0][:40]).cuda()] for c in classes]))     # (41, 40, 12)
+    train = torch.stack(train)                                     # (9, 41, 40, 12)
+    labels = torch.arange(41).repeat(8).cuda()
+    for step in range(400):
+        pi = torch.randint(0, 9, (8,))
+        wi = torch.randint(0, 40, (8, 41))
+        x = torch.stack([train[pi[g], torch.arange(41), wi[g]] for g in range(8)]).reshape(-1, 12).contiguous()
+        z = e.encoder_forward(x, training=True)
+        e.head(z, labels, 1, want_grad=True)
+        e.encoder_backward(x)
+        e.adam_step(params)
+    torch.cuda.synchronize()
+    rawE, labE = _cue_recording(rng, pattern, people[9], 100, rng.permutation(41))
+    rawT, labT = _cue_recording(rng, pattern, people[9], 100, rng.permutation(41))
+    wlT = window_labels(labT, 0)
+    for dtype in ("f32", "bf16"):
+        dec = OnlineDecoder(e, mean, std, classes=classes, dtype=dtype)
+        acc = {}
+        for name in ("one-hot rows", "enrolled rows"):
+            if name == "enrolled rows":
+                dec.enroll(rawE, labE)
+            dec.reset()
+            pred, voted = (t.cpu().numpy() for t in dec.push(rawT))
+            ok = wlT >= 0
+            acc[name] = (float((pred[ok] == wlT[ok]).mean()), float((voted[ok] == wlT[ok]).mean()))
+        out(dict(part="c", dtype=dtype, windows=int((wlT >= 0).sum()), acc_onehot=round(acc["one-hot rows"][0], 4),
+                 acc_onehot_voted=round(acc["one-hot rows"][1], 4), acc_enrolled=round(acc["enrolled rows"][0], 4),
+                 acc_enrolled_voted=round(acc["enrolled rows"][1], 4)))
+
+    # (a) 41 classes x 500 windows
+    raw, lab = _cue_recording(rng, pattern, people[9], 500, classes)
+    wl = window_labels(lab, 0)
+    keep = torch.as_tensor(np.nonzero(wl >= 0)[0]).cuda()
+    slots_np = wl[wl >= 0]
+    slots = torch.as_tensor(slots_np.astype(np.int32)).cuda()
+    for dtype in ("f32", "bf16"):
+        dec = OnlineDecoder(e, mean, std, classes=classes, dtype=dtype)
+        prior = dec.class_table()[0]
+        lib = dec.lib
+
+        def whole():
+            dec.enroll_reset()
+            dec.enroll(raw, lab)
+
+        def windows():
+            return recording_windows(raw, dec.mean_std, dec._b, dec._a, 0)[keep].contiguous()
+
+        w = windows()
+        accb = torch.zeros(64, 17, dtype=torch.float64, device="cuda")
+        scratch = torch.empty(lib.cp_online_enroll_scratch_bytes(w.shape[0], dec._cfg.dtype), dtype=torch.uint8, device="cuda")
+        tab = torch.empty_like(prior)
+        st = torch.cuda.current_stream().cuda_stream
+
+        def accumulate():
+            lib.cp_online_enroll(C.byref(dec._cfg), dec.ws.data_ptr(), dec.ws.numel(), w.data_ptr(), w.shape[0], slots.data_ptr(), 41,
+                                 accb.data_ptr(), scratch.data_ptr(), scratch.numel(), st)
+
+        def table():
+            lib.cp_online_enroll_table(accb.data_ptr(), 41, prior.data_ptr(), C.c_double(1.0), 25, tab.data_ptr(), st)
+
+        def composed():
+            wc = _calibration_windows(raw, dec._b, dec._a, 0, dec.mean_std)[keep]
+            x = torch.zeros((wc.shape[0] + 40) // 41 * 41, 12, device="cuda")
+            x[:wc.shape[0]] = wc
+            z = e.encoder_forward(x, training=False)[:wc.shape[0]].double()
+            zn = z / z.norm(dim=-1, keepdim=True)
+            S = torch.zeros(41, 16, dtype=torch.float64, device="cuda").index_add_(0, slots.long(), zn)
+            return (S / S.norm(dim=-1, keepdim=True)).float()
+
+        e.dtype = 0 if dtype == "f32" else 1
+        e._ws = None                                           # the engine's workspace is carved per dtype
+        out(dict(part="a", dtype=dtype, windows=int(w.shape[0]), enroll_ms=round(_wall(whole, a.iters), 3),
+                 windows_ms=round(_wall(windows, a.iters), 3), accumulate_ms=round(_wall(accumulate, a.iters), 3),
+                 table_ms=round(_wall(table, a.iters), 3), composed_ms=round(_wall(composed, max(2, a.iters // 3)), 3)))
+    e.dtype = 0
+    e._ws = None
+
+    # (b) a 60 s recording
+    raw60 = (torch.randn(120000, 12) * 2e-3).cuda()
+    one = _wall(lambda: recording_windows(raw60, probe.mean_std, probe._b, probe._a, 0), a.iters)
+    off = _wall(lambda: _calibration_windows(raw60, probe._b, probe._a, 0, probe.mean_std), max(2, a.iters // 3))
+    w_one = recording_windows(raw60, probe.mean_std, probe._b, probe._a, 0)
+    w_off = _calibration_windows(raw60, probe._b, probe._a, 0, probe.mean_std)
+    k16 = 32767 // 20 + 1                                          # the offline transform keeps its positions in 16 bits
+    push = OnlineDecoder(e, mean, std, classes=classes).push(raw60, return_windows=True)[2]
+    out(dict(part="b", samples=120000, recording_windows_ms=round(one, 3), calibration_windows_ms=round(off, 3),
+             ratio=round(off / one, 1), equal_to_push=torch.equal(w_one, push), equal_to_offline=torch.equal(w_one, w_off),
+             equal_to_offline_below_32768_samples=torch.equal(w_one[:k16], w_off[:k16])))
+    if a.out:
+        dev = torch.cuda.get_device_name(0)
+        with open(a.out, "w") as f:
+            f.write(f"# tools/online_bench.py --enroll --iters {a.iters} on {dev}\n")
+            f.write("# wall time, host-synchronised, median.  (a) enroll() of 41 classes x 500 windows and its parts, next to the same\n"
+                    "# table from _calibration_windows + Engine.encoder_forward(training=False) + index_add_;  (b) one-pass windows\n"
+                    "# against the offline windows on 60 s;  (c) accuracy on a held-out recording of a synthetic person the model was\n"
+                    "# not trained on (class amplitude pattern x per-person channel gains; 400 training steps on nine other people),\n"
+                    "# per window and voted over 25 windows\n")
+            for r in lines:
+                f.write(json.dumps(r) + "\n")
 
 
 def adapt_main(a, e, stream, mean, std, classes):
