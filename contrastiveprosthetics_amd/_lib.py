@@ -78,6 +78,11 @@ class cp_online_config(C.Structure):
                 ("n_coef", C.c_int32), ("reserved0", C.c_int32), ("b", C.c_double * 17), ("a", C.c_double * 17)]
 
 
+class cp_online_gate_config(C.Structure):
+    _fields_ = [("vote", C.c_int32), ("min_votes", C.c_int32), ("dwell", C.c_int32), ("release", C.c_int32),
+                ("weight", C.c_int32), ("min_margin", C.c_float)]
+
+
 CP_ONLINE_MAX_CLASSES, CP_ONLINE_MAX_VOTE, CP_ONLINE_MAX_WINDOWS, CP_ONLINE_STRIDE = 64, 256, 256, 20
 CP_ONLINE_MULTI_MAX_STREAMS, CP_ONLINE_MULTI_MAX_ROWS = 256, 65536
 
@@ -169,6 +174,12 @@ SYMBOLS = {
     "cp_online_multi_adapt_enroll": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, C.c_int32, _fp, C.c_int64,
                                                _fp, C.c_int32, _fp, _fp, C.c_size_t, _fp]),
     "cp_online_enroll_table": (C.c_int, [_fp, C.c_int32, _fp, C.c_double, C.c_int32, _fp, _fp]),
+    "cp_online_gate_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "cp_online_gate_set_classes": (C.c_int, [_P(cp_online_gate_config), C.c_int32, _fp, C.c_size_t, C.c_int32, _P(C.c_int32),
+                                             _P(C.c_float), C.c_int32, _fp]),
+    "cp_online_gate_reset": (C.c_int, [_P(cp_online_gate_config), C.c_int32, _fp, C.c_size_t, C.c_int32, _fp]),
+    "cp_online_gate_push": (C.c_int, [_P(cp_online_gate_config), C.c_int32, _fp, C.c_size_t, _fp, C.c_int32, _fp, _fp, C.c_int32,
+                                      _fp, _fp, _fp, _fp, _fp]),
 }
 
 KERNEL_KINDS = ["gather", "prep", "conv1_fwd", "bn_finalize", "conv2_fwd", "fold", "fc_fwd", "dropout", "proj_fwd",

@@ -25,6 +25,7 @@
 #include "online_multi.cuh"
 #include "online_multi_adapt.cuh"
 #include "online_enroll.cuh"
+#include "online_gate.cuh"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* what) {
@@ -3423,5 +3424,87 @@ extern "C" int cp_online_enroll_table(const double* acc, int32_t n_classes, cons
     hipLaunchKernelGGL(ole_table_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, acc, (int)n_classes, prior, mix, (double)min_windows,
                        table);
     CKL("ole_table_kernel");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// grasp command gate (csrc/online_gate.cuh): one OgState per stream in a workspace of its own, behind any decoder's logits
+// ---------------------------------------------------------------------------------------
+static_assert(OG_MAXK == CP_ONLINE_MAX_CLASSES && OG_MAXVOTE == CP_ONLINE_MAX_VOTE && OG_MAXM == CP_ONLINE_MAX_WINDOWS, "gate limits");
+static_assert(sizeof(OgState) == 4 * (8 + 2 * OG_MAXK + 2 * OG_MAXVOTE), "OgState is 648 words (CommandGate.state reads it back)");
+
+static int og_check(const char* who, const cp_online_gate_config* c, int32_t n_streams, void* ws, size_t ws_bytes) {
+    static char msg[160];
+    auto bad = [&](const char* what) {
+        snprintf(msg, sizeof(msg), "%s: %s", who, what);
+        return fail(CP_ERR_ARG, msg);
+    };
+    if (!c || !ws) return bad("config and workspace are required");
+    if (n_streams < 1 || n_streams > CP_ONLINE_MULTI_MAX_STREAMS) return bad("n_streams outside 1..256");
+    if (c->vote < 1 || c->vote > CP_ONLINE_MAX_VOTE) return bad("vote outside 1..256");
+    if (c->min_votes < 1) return bad("min_votes must be at least 1");
+    if (c->dwell < 1) return bad("dwell must be at least 1");
+    if (c->release < 0) return bad("release must not be negative");
+    if (c->weight != 0 && c->weight != 1) return bad("weight must be 0 (count) or 1 (margin)");
+    if (!(c->min_margin >= 0.f) || std::isinf(c->min_margin)) return bad("min_margin must be finite and >= 0");
+    if ((uintptr_t)ws % 256) return bad("workspace not 256-byte aligned");
+    if (ws_bytes < (size_t)n_streams * sizeof(OgState)) return bad("workspace too small");
+    return 0;
+}
+
+extern "C" size_t cp_online_gate_workspace_bytes(int32_t n_streams) {
+    if (n_streams < 1) n_streams = 1;
+    return align256((size_t)n_streams * sizeof(OgState));
+}
+
+extern "C" int cp_online_gate_set_classes(const cp_online_gate_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index,
+                                          const int32_t* ids, const float* min_cosine, int32_t n_classes, void* stream) {
+    if (int e = og_check("cp_online_gate_set_classes", cfg, n_streams, ws, ws_bytes)) return e;
+    if (index < 0 || index >= n_streams) return fail(CP_ERR_ARG, "cp_online_gate_set_classes: stream index outside 0..n_streams-1");
+    if (!ids || !min_cosine || n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES)
+        return fail(CP_ERR_ARG, "cp_online_gate_set_classes: 1..64 classes, with ids and min_cosine");
+    OgClassArgs c{};
+    c.K = n_classes;
+    for (int k = 0; k < n_classes; ++k) {
+        if (ids[k] < 0 || ids[k] == INT32_MAX || (k > 0 && ids[k] <= ids[k - 1]))
+            return fail(CP_ERR_ARG, "cp_online_gate_set_classes: ids must be ascending, distinct and in 0..2^31-2");
+        if (std::isnan(min_cosine[k])) return fail(CP_ERR_ARG, "cp_online_gate_set_classes: min_cosine must not be NaN");
+        c.ids[k] = ids[k];
+        c.min_cosine[k] = min_cosine[k];
+    }
+    hipLaunchKernelGGL(og_set_classes_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (OgState*)ws + index, c);
+    CKL("og_set_classes_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_gate_reset(const cp_online_gate_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index,
+                                    void* stream) {
+    if (int e = og_check("cp_online_gate_reset", cfg, n_streams, ws, ws_bytes)) return e;
+    if (index < -1 || index >= n_streams) return fail(CP_ERR_ARG, "cp_online_gate_reset: stream index outside -1..n_streams-1");
+    hipLaunchKernelGGL(og_reset_kernel, dim3(index < 0 ? n_streams : 1), dim3(64), 0, (hipStream_t)stream, (OgState*)ws,
+                       index < 0 ? 0 : index);
+    CKL("og_reset_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_gate_push(const cp_online_gate_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, const float* logits,
+                                   int32_t ldl, const int32_t* row0, const int32_t* m, int32_t total_rows, int32_t* command,
+                                   int32_t* accepted, float* conf, float* margin, void* stream) {
+    if (int e = og_check("cp_online_gate_push", cfg, n_streams, ws, ws_bytes)) return e;
+    if (total_rows < 0 || total_rows > CP_ONLINE_MULTI_MAX_ROWS) return fail(CP_ERR_ARG, "cp_online_gate_push: total_rows outside 0..65536");
+    if (total_rows == 0) return 0;
+    if (ldl < 1) return fail(CP_ERR_ARG, "cp_online_gate_push: ldl must be at least 1");
+    if (!logits || !row0 || !m || !command || !accepted)
+        return fail(CP_ERR_ARG, "cp_online_gate_push: logits, row0, m, command and accepted are required");
+    if ((uintptr_t)logits % 4 || (uintptr_t)row0 % 4 || (uintptr_t)m % 4 || (uintptr_t)command % 4 || (uintptr_t)accepted % 4 ||
+        (uintptr_t)conf % 4 || (uintptr_t)margin % 4)
+        return fail(CP_ERR_ARG, "cp_online_gate_push: misaligned argument");
+    OgPushArgs a{};
+    a.states = (OgState*)ws; a.logits = logits; a.row0 = row0; a.m = m; a.ldl = ldl; a.total_rows = total_rows;
+    a.command = command; a.accepted = accepted; a.conf = conf; a.margin = margin;
+    a.c.vote = cfg->vote; a.c.min_votes = cfg->min_votes; a.c.dwell = cfg->dwell; a.c.release = cfg->release; a.c.weight = cfg->weight;
+    a.c.min_margin = cfg->min_margin;
+    hipLaunchKernelGGL(og_push_kernel, dim3(n_streams), dim3(64), 0, (hipStream_t)stream, a);
+    CKL("og_push_kernel");
     return 0;
 }

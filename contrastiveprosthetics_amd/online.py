@@ -22,6 +22,10 @@ bit-identical to those of its own `OnlineDecoder`.  `AdaptiveMultiStreamDecoder`
 csrc/online_multi_adapt.cuh): per stream float64 BatchNorm statistics, calibration and alpha, each stream bit-identical to its
 own `OnlineDecoder(adapt=alpha)`.
 
+`CommandGate` wraps any of the four decoders and turns the logits of every push into a command a hand can follow, on the
+device (cp_online_gate_*, csrc/online_gate.cuh): rejection by cosine threshold and margin, a weighted vote ring, a dwell time
+before a new grasp and a release time before none.
+
 The number of windows a push emits follows from sample counts alone (`windows_emitted`), so a push never waits for the device:
 its outputs are device tensors on torch's current stream.
 """
@@ -955,3 +959,329 @@ class AdaptiveMultiStreamDecoder(_MultiStreamBase):
         _lib.check(self.lib.cp_online_multi_adapt_statistics(*self._args(), s, out.data_ptr(), self._stream()),
                    "cp_online_multi_adapt_statistics")
         return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# grasp command gate: rejection, weighted vote and dwell behind any of the decoders (cp_online_gate_*, csrc/online_gate.cuh)
+# ---------------------------------------------------------------------------------------------------------------------------
+def thresholds_from_logits(logits, labels, ids, keep: float = 0.95) -> dict:
+    """Per-class cosine thresholds from a cued recording: logits (M, K) as `push(..., return_logits=True)` gives them, labels
+    (M,) the label of each window (`window_labels`; negative: not labelled), ids (K,) the ascending class ids of the columns.
+    For class c the windows count whose label is c and whose argmax (first maximum) is c; with v their top cosines in ascending
+    order and n their number, the threshold is v[floor((1 - keep) * n)]: about the fraction `keep` of the user's own correct
+    windows passes it.  Classes without such a window are left out.  {class id: threshold}; host only (numpy)."""
+    lg = logits.detach().cpu().numpy() if isinstance(logits, torch.Tensor) else np.asarray(logits)
+    lab = labels.detach().cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+    cid = ids.detach().cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
+    cid = cid.reshape(-1)
+    if lg.ndim != 2 or lg.shape[1] != cid.shape[0] or lg.shape[1] < 1:
+        raise ValueError("logits must be (M, K) with one column per id")
+    if lab.shape != (lg.shape[0],):
+        raise ValueError(f"labels must hold one entry per window ({lg.shape[0]})")
+    if not 0.0 < float(keep) <= 1.0:
+        raise ValueError("keep must lie in (0, 1]")
+    lg = lg.astype(np.float32)
+    top = lg.argmax(axis=1) if lg.shape[0] else np.zeros(0, dtype=np.int64)
+    out = {}
+    for k, c in enumerate(cid.tolist()):
+        v = np.sort(lg[(lab == c) & (top == k), k])
+        if v.size:
+            out[int(c)] = float(v[int(np.floor((1.0 - float(keep)) * v.size))])
+    return out
+
+
+_GATE_WEIGHTS = {"count": 0, "margin": 1}
+
+
+class CommandGate:
+    """A command a hand can follow, from any of the four decoders: per stream one state machine on the device that reads the
+    logits of every push (include/cpnative.h, cp_online_gate_*; one launch more per push, nothing is copied to the host).
+
+    A window is accepted if its top cosine reaches `min_cosine` of its class and leads the runner-up by `min_margin`; accepted
+    or not, it enters a ring of `vote` windows (default: the decoder's) with weight 1 (weight='count') or a weight that grows
+    with its margin (weight='margin').  The candidate is the class with the largest weight in the ring among those with at
+    least `min_votes` accepted windows there, or none.  A new grasp becomes the command after it has been the candidate for
+    `dwell` windows in a row, none after `release` windows in a row (release=0: a grasp is never released, only replaced).
+
+    min_cosine: one float, or {class id: float} with `default` for the ids it does not name (`thresholds_from_logits` makes
+    one from a cued recording).  With the defaults every gate is open and `command` equals the decoder's `voted` bit for bit.
+
+    The gate follows the decoder: a new `class_ids` object (set_classes, enroll, refresh) is installed before the next launch
+    -- the ring empties and the command survives if its class id does -- and a push or reset of the decoder behind the gate's
+    back makes the next `push` raise `CpNativeError` before anything is enqueued."""
+
+    def __init__(self, decoder, min_cosine=-2.0, min_margin: float = 0.0, min_votes: int = 1, dwell: int = 1, release: int = 1,
+                 weight: str = "count", vote: Optional[int] = None, default: float = -2.0):
+        for name in ("class_ids", "n_seen", "vote", "push"):
+            if not hasattr(decoder, name):
+                raise TypeError("CommandGate wraps an OnlineDecoder, MultiStreamDecoder or AdaptiveMultiStreamDecoder")
+        self.decoder = decoder
+        self.multi = isinstance(decoder.class_ids, (list, tuple))
+        self.n_streams = len(decoder.class_ids) if self.multi else 1
+        vote = decoder.vote if vote is None else vote
+        if not 1 <= int(vote) <= _lib.CP_ONLINE_MAX_VOTE:
+            raise ValueError(f"vote must lie in 1..{_lib.CP_ONLINE_MAX_VOTE}")
+        self.vote = int(vote)
+        self._cfg = _lib.cp_online_gate_config()
+        self._cfg.vote = self.vote
+        self._cfg.min_votes, self._cfg.dwell, self._cfg.release, self._cfg.weight, self._cfg.min_margin = 1, 1, 1, 0, 0.0
+        self.set(min_margin=min_margin, min_votes=min_votes, dwell=dwell, release=release, weight=weight)
+        spec = self._check_thresholds(min_cosine, default)
+        self._thr = [spec] * self.n_streams
+        self._ids_seen = [None] * self.n_streams            # the class_ids object each stream's gate was installed from
+        self._k = [0] * self.n_streams
+        self.device = getattr(decoder, "device", None)
+        self.ws = None                                      # allocated with the first launch
+        self._rows_cache = {}
+        self._left = self._seen_now()
+
+    # ------------------------------------------------------------------ settings
+    def set(self, **kw):
+        """Change min_margin, min_votes, dwell, release or weight from the next window on (vote is fixed at construction)."""
+        c = self._cfg
+        new = dict(min_margin=c.min_margin, min_votes=c.min_votes, dwell=c.dwell, release=c.release,
+                   weight="margin" if c.weight else "count")
+        for k, v in kw.items():
+            if k == "vote":
+                raise ValueError("vote is fixed at construction: the ring is laid out by it")
+            if k not in new:
+                raise TypeError(f"set() takes min_margin, min_votes, dwell, release and weight, not {k!r}")
+            new[k] = v
+        if new["weight"] not in _GATE_WEIGHTS:
+            raise ValueError("weight must be 'count' or 'margin'")
+        mm = float(new["min_margin"])
+        if not (mm >= 0.0 and np.isfinite(mm)):
+            raise ValueError("min_margin must be finite and >= 0")
+        for k, low in (("min_votes", 1), ("dwell", 1), ("release", 0)):
+            v = new[k]
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not low <= int(v) < 2 ** 31:
+                raise ValueError(f"{k} must be an int >= {low}")
+        c.min_margin, c.min_votes, c.dwell, c.release = mm, int(new["min_votes"]), int(new["dwell"]), int(new["release"])
+        c.weight = _GATE_WEIGHTS[new["weight"]]
+
+    @staticmethod
+    def _check_thresholds(min_cosine, default):
+        d = float(default)
+        if isinstance(min_cosine, dict):
+            spec = {int(k): float(v) for k, v in min_cosine.items()}
+        else:
+            spec, d = {}, float(min_cosine)
+        if any(np.isnan(v) for v in list(spec.values()) + [d]):
+            raise ValueError("min_cosine must not be NaN")
+        return spec, d
+
+    def set_thresholds(self, *args, default: float = -2.0):
+        """set_thresholds(min_cosine) on a single-stream decoder, set_thresholds(stream, min_cosine) on a multi-stream one:
+        a float or {class id: float} with `default` for the other ids.  They go in with the next launch, as a new class list
+        does: that stream's ring empties and its command stays."""
+        if len(args) != (2 if self.multi else 1):
+            raise TypeError("set_thresholds(stream, min_cosine) on a multi-stream decoder, set_thresholds(min_cosine) otherwise")
+        s = 0
+        if self.multi:
+            s = args[0]
+            if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 0 <= int(s) < self.n_streams:
+                raise IndexError(f"stream index must be an int in 0..{self.n_streams - 1}, got {s!r}")
+            s = int(s)
+        self._thr[s] = self._check_thresholds(args[-1], default)
+        self._ids_seen[s] = None
+
+    # ------------------------------------------------------------------ the device side (one method per C entry)
+    def _stream(self) -> int:
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _args(self):
+        if self.ws is None:
+            self.lib = _lib.load()
+            self.ws = torch.zeros(self.lib.cp_online_gate_workspace_bytes(self.n_streams), dtype=torch.uint8, device=self.device)
+        return C.byref(self._cfg), self.n_streams, self.ws.data_ptr(), self.ws.numel()
+
+    def _dev_set_classes(self, s: int, ids: np.ndarray, thr: np.ndarray):
+        k = int(ids.shape[0])
+        args = self._args()
+        _lib.check(self.lib.cp_online_gate_set_classes(*args, s, (C.c_int32 * k)(*ids.tolist()), (C.c_float * k)(*thr.tolist()), k,
+                                                       self._stream()), "cp_online_gate_set_classes")
+
+    def _dev_reset(self, s: int):
+        args = self._args()
+        _lib.check(self.lib.cp_online_gate_reset(*args, s, self._stream()), "cp_online_gate_reset")
+
+    def _dev_push(self, logits_ptr: int, ldl: int, row0: np.ndarray, m: np.ndarray, rows: int):
+        """one launch over `rows` packed rows -> (command, accepted) (2, rows) int32 and (conf, margin) (2, rows) f32"""
+        args = self._args()
+        key = (row0.tobytes(), m.tobytes(), self._stream())
+        rm = self._rows_cache.get(key)
+        if rm is None:
+            if len(self._rows_cache) >= 16:
+                self._rows_cache.clear()
+            rm = torch.from_numpy(np.stack([row0, m]).astype(np.int32)).pin_memory().to(self.device, non_blocking=True)
+            self._rows_cache[key] = rm
+        ca = torch.empty(2, rows, dtype=torch.int32, device=self.device)
+        cm = torch.empty(2, rows, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.cp_online_gate_push(*args, logits_ptr, ldl, rm[0].data_ptr(), rm[1].data_ptr(), rows, ca[0].data_ptr(),
+                                                ca[1].data_ptr(), cm[0].data_ptr(), cm[1].data_ptr(), self._stream()),
+                   "cp_online_gate_push")
+        return ca, cm
+
+    # ------------------------------------------------------------------ staying in step with the decoder
+    def _seen_now(self) -> np.ndarray:
+        return np.array(self.decoder.n_seen, dtype=np.int64).reshape(-1).copy()
+
+    def _class_ids(self, s: int):
+        return self.decoder.class_ids[s] if self.multi else self.decoder.class_ids
+
+    def _sync_classes(self):
+        for s in range(self.n_streams):
+            cur = self._class_ids(s)
+            if cur is None or cur is self._ids_seen[s]:
+                continue
+            ids = np.asarray(cur.cpu() if isinstance(cur, torch.Tensor) else cur, dtype=np.int64).reshape(-1)
+            if not 1 <= ids.shape[0] <= MAX_CLASSES or (np.diff(ids) <= 0).any() or ids[0] < 0 or ids[-1] >= 2 ** 31 - 1:
+                raise ValueError("the gate takes 1..64 ascending class ids in 0..2**31-2 (-1 is its 'none')")
+            spec, d = self._thr[s]
+            thr = np.array([spec.get(int(i), d) for i in ids], dtype=np.float32)
+            self._dev_set_classes(s, ids, thr)
+            self._ids_seen[s] = cur
+            self._k[s] = int(ids.shape[0])
+
+    def _check_in_step(self):
+        if not np.array_equal(self._seen_now(), self._left):
+            raise _lib.CpNativeError("the decoder was pushed or reset behind the gate (its n_seen is not what the gate left): the "
+                                     "gate's ring no longer follows the stream; push and reset through the gate, or reset() it")
+
+    # ------------------------------------------------------------------ the gate over per-stream logits
+    def _gate(self, per_stream, trusted: bool = False):
+        """per_stream: n_streams entries, None or (M_s, K_s) f32 logits -> per stream (command, accepted, conf, margin).
+        trusted: the entries are what the decoder's own push just returned (their layout is known, see _packed)."""
+        self._sync_classes()
+        step = _lib.CP_ONLINE_MAX_WINDOWS
+        if trusted:
+            ms = [0 if t is None else t.shape[0] for t in per_stream]
+        else:
+            ms = []
+            for s, t in enumerate(per_stream):
+                if t is None:
+                    ms.append(0)
+                    continue
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2:
+                    raise ValueError("logits must be (M, K) float32 tensors")
+                if t.shape[0] and self._ids_seen[s] is None:
+                    raise _lib.CpNativeError(f"stream {s} has logits but no class list: set_classes on the decoder first")
+                if t.shape[0] and t.shape[1] != self._k[s]:
+                    raise ValueError(f"stream {s}: logits have {t.shape[1]} columns, its class list {self._k[s]} ids")
+                ms.append(int(t.shape[0]))
+        outs = []                                              # per round: per stream (command, accepted, conf, margin)
+        for lo in range(0, max(max(ms), 1), step):
+            m = np.array([min(max(n - lo, 0), step) for n in ms], dtype=np.int64)
+            rows = int(m.sum())
+            row0 = np.zeros_like(m)
+            np.cumsum(m[:-1], out=row0[1:])
+            if rows == 0:
+                dev = next((t.device for t in per_stream if t is not None), self.device)
+                ca, cm = torch.empty(2, 0, dtype=torch.int32, device=dev), torch.empty(2, 0, dtype=torch.float32, device=dev)
+            else:
+                whole = lo == 0 and max(ms) <= step
+                views = [None if n == 0 else (per_stream[s] if whole else per_stream[s][lo:lo + n]) for s, n in enumerate(m.tolist())]
+                base, ldl = self._packed(views, row0, trusted)
+                ca, cm = self._dev_push(base.data_ptr(), ldl, row0, m, rows)
+            if self.n_streams == 1:
+                outs.append([(ca[0], ca[1], cm[0], cm[1])])
+                continue
+            ml = m.tolist()
+            outs.append(list(zip(ca[0].split(ml), ca[1].split(ml), cm[0].split(ml), cm[1].split(ml))))
+        if len(outs) == 1:
+            return outs[0]
+        return [tuple(torch.cat([o[s][i] for o in outs]) for i in range(4)) for s in range(self.n_streams)]
+
+    @staticmethod
+    def _packed(views, row0, trusted: bool = False):
+        """the rows of one launch as (tensor whose data_ptr is row 0, leading dimension): the views as they lie if they are
+        the packed output of a decoder's push (one buffer, stream order, one row stride), else a packed (rows, 64) copy.
+        Every view is checked; of a decoder's own output (trusted) only the first and the last one, which tell its one
+        packed buffer from the per-stream concatenations of a push it had to split."""
+        live = [(s, v) for s, v in enumerate(views) if v is not None]
+        s0, v0 = live[0]
+        ldl = int(v0.stride(0)) if v0.shape[0] > 1 or len(live) > 1 else max(int(v0.shape[1]), 1)
+        ok = ldl >= 1
+        for s, v in ((live[0], live[-1]) if trusted else live):
+            ok = ok and v.stride(1) == 1 and (v.shape[0] == 1 or v.stride(0) == ldl) and ldl >= v.shape[1] \
+                and v.untyped_storage().data_ptr() == v0.untyped_storage().data_ptr() \
+                and v.data_ptr() == v0.data_ptr() + 4 * ldl * int(row0[s] - row0[s0])
+        if ok:
+            return v0, ldl
+        buf = torch.zeros(int(sum(v.shape[0] for _, v in live)), MAX_CLASSES, dtype=torch.float32, device=v0.device)
+        for s, v in live:
+            buf[int(row0[s]):int(row0[s]) + v.shape[0], :v.shape[1]] = v
+        return buf, MAX_CLASSES
+
+    # ------------------------------------------------------------------ API
+    def apply(self, logits):
+        """The gate alone on logits the caller already has (of the decoder's next windows, in order): (M, K) f32 on the GPU ->
+        (command, accepted, conf, margin); on a multi-stream decoder a list with one entry per stream (None: no windows) -> one
+        such tuple per stream.  command, accepted (M,) int32 class ids or -1; conf, margin (M,) f32."""
+        if self.multi:
+            if isinstance(logits, torch.Tensor) or len(logits) != self.n_streams:
+                raise ValueError(f"logits must be a sequence of {self.n_streams} entries (None or (M, K) tensors)")
+            out = self._gate(list(logits))
+        else:
+            out = self._gate([logits])[0]
+        self._left = self._seen_now()
+        return out
+
+    def _extend(self, res, gated, return_logits: bool):
+        keep = [x for i, x in enumerate(res) if i != 2 or return_logits]
+        return tuple(keep) + tuple(gated)
+
+    def push(self, raw, return_logits: bool = False, return_windows: bool = False):
+        """What the decoder's `push` takes (raw (n, 12), or one chunk per stream) -> the decoder's tuple(s) extended by
+        command, accepted, conf, margin: (pred, voted[, logits][, windows], command, accepted, conf, margin)."""
+        self._check_in_step()
+        self._sync_classes()
+        res = self.decoder.push(raw, return_logits=True, return_windows=return_windows)
+        return self._finish(res, return_logits)
+
+    def push_packed(self, raw, counts, return_logits: bool = False, return_windows: bool = False):
+        """`push` for samples packed in stream order, as the multi-stream decoders' `push_packed`."""
+        if not self.multi:
+            raise TypeError("push_packed belongs to the multi-stream decoders")
+        self._check_in_step()
+        self._sync_classes()
+        res = self.decoder.push_packed(raw, counts, return_logits=True, return_windows=return_windows)
+        return self._finish(res, return_logits)
+
+    def _finish(self, res, return_logits: bool):
+        self._left = self._seen_now()
+        if self.multi:
+            gated = self._gate([r[2] for r in res], trusted=True)
+            return [self._extend(r, g, return_logits) for r, g in zip(res, gated)]
+        return self._extend(res, self._gate([res[2]], trusted=True)[0], return_logits)
+
+    def state(self, stream: int = 0) -> dict:
+        """One stream's state as the device holds it, read back (this waits for the device; a test and debugging aid):
+        command (class id or -1), pending (class slot, -1 for none, or None if nothing is pending), run, and ring, the
+        (slot or -1, weight) entries from the oldest to the newest.  The layout is that of OgState (csrc/online_gate.cuh):
+        int32 K, head, len, command + 1, pending, run, 2 unused, ids[64], f32 min_cosine[64], int32 ring slots [256] and ring
+        weights [256]."""
+        if isinstance(stream, bool) or not 0 <= int(stream) < self.n_streams:
+            raise IndexError(f"stream index must lie in 0..{self.n_streams - 1}")
+        if self.ws is None:
+            return dict(command=-1, pending=None, run=0, ring=[])
+        per = 8 + 2 * MAX_CLASSES + 2 * _lib.CP_ONLINE_MAX_VOTE
+        w = self.ws[:self.n_streams * per * 4].view(torch.int32).reshape(self.n_streams, per)[int(stream)].cpu().numpy()
+        head, n, run = int(w[1]), int(w[2]), int(w[5])
+        slots, weights = w[8 + 2 * MAX_CLASSES:][:_lib.CP_ONLINE_MAX_VOTE], w[8 + 2 * MAX_CLASSES + _lib.CP_ONLINE_MAX_VOTE:]
+        at = [(head - n + i) % self.vote for i in range(n)]
+        return dict(command=int(w[3]) - 1, pending=int(w[4]) if run else None, run=run,
+                    ring=[(int(slots[i]), int(weights[i])) for i in at])
+
+    def reset(self, streams=None):
+        """Reset the decoder and the gate (ring, pending state and command to none; classes and thresholds stay); on a
+        multi-stream decoder the listed streams, default all."""
+        if self.multi and streams is not None:
+            idx = sorted({int(s) for s in streams})
+            self.decoder.reset(idx)
+            for s in idx:
+                self._dev_reset(s)
+        else:
+            self.decoder.reset()
+            self._dev_reset(-1)
+        self._left = self._seen_now()

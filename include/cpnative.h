@@ -607,6 +607,59 @@ int cp_online_multi_adapt_enroll(const cp_online_config* cfg, int32_t n_streams,
 int cp_online_enroll_table(const double* acc, int32_t n_classes, const float* prior, double mix, int32_t min_windows, float* table,
                            void* stream);
 
+/* ---- grasp command gate: rejection, weighted vote and dwell behind the online decoders --------------------------------------
+ * A decoder forces every window onto one of its K class rows.  The gate is a stage behind it that reads the logits a push emits
+ * (cosines in [-1, 1]) and keeps one state machine per stream, so that the stream can answer "none of these", report how sure
+ * it is, hold a grasp through a few ambiguous windows and ask that a new grasp win for some time before the hand moves.  One
+ * launch per push for any n_streams <= 256 (one wave per stream, lane k = class slot k); the decoders' own kernels and outputs
+ * do not change.  The state lives in a workspace of the gate's own: per stream K, ids[64], min_cosine[64], ring slots [256] and
+ * ring weights [256], head and len, the command (a class id, or none), the pending slot and the run length.  A zeroed
+ * workspace is a valid start (no classes, empty ring, command none).  cfg.vote is the same on every call of a workspace.
+ * Per window, in window order, all float arithmetic in f32 without contraction:
+ *   row        k1 = first maximum of the row's K logits, c1 = l[k1], c2 = the maximum over k != k1 (K = 1: -1.0f),
+ *              margin = c1 - c2.  A row with a non-finite logit is rejected with conf = margin = NaN; any other row is
+ *              accepted iff c1 >= min_cosine[k1] and margin >= min_margin.
+ *   ring       the entry (k1 if accepted else -1, w) enters the ring; the oldest leaves once `vote` entries are in.  w = 1
+ *              (weight 0, count) or 1 + (int32) rint(min(margin, 2) * 2^20) (weight 1, margin; round-half-even, the product
+ *              is exact).  Weights are integers, a full ring sums below 2^31, and sliding sums are exact in any order.
+ *   candidate  the slot with the largest weight sum among the slots with >= min_votes ring entries (ties: the smallest slot);
+ *              none if no slot qualifies.
+ *   command    candidate == command: nothing is pending (run = 0).  candidate none and release == 0: nothing is pending and
+ *              the command stays (never release).  candidate == pending: run += 1.  Otherwise pending = candidate, run = 1.
+ *              Then, with something pending and run >= dwell (a grasp) or run >= release (none): command = pending, and
+ *              nothing is pending.
+ *   outputs    command (class id, or -1 for none), accepted (ids[k1] if accepted else -1), conf = c1, margin.
+ * So a stream's outputs depend neither on how its rows are cut into calls nor on the streams that share a launch, and with
+ * every gate open (min_cosine -2, min_margin 0, min_votes 1, dwell 1, release 1, count weights, the decoder's vote) command
+ * equals the decoder's voted bit for bit.
+ * The entries keep no state in the library and validate on the host: a bad argument -- a short workspace included -- returns
+ * CP_ERR_ARG with a cp_last_error that names the entry, before anything is enqueued. */
+typedef struct cp_online_gate_config {
+    int32_t vote;            /* ring length, 1..256 */
+    int32_t min_votes;       /* >= 1: ring entries a slot needs to be a candidate */
+    int32_t dwell;           /* >= 1: windows in a row a new grasp must win before it becomes the command */
+    int32_t release;         /* >= 0: windows in a row of "no candidate" before the command becomes none; 0: never */
+    int32_t weight;          /* 0: count, 1: margin */
+    float min_margin;        /* >= 0 */
+} cp_online_gate_config;
+/* bytes of the gate's workspace (256-byte aligned) for n_streams streams; zero it before the first call */
+size_t cp_online_gate_workspace_bytes(int32_t n_streams);
+/* ids (n_classes) int32 ascending, distinct, >= 0 and min_cosine (n_classes) f32, one threshold per row, both on the HOST (they
+ * travel as kernel arguments).  Installs them for stream `index`, empties that stream's ring and pending state, and keeps its
+ * command if the command's class id is among the new ids (else the command becomes none). */
+int cp_online_gate_set_classes(const cp_online_gate_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index,
+                               const int32_t* ids, const float* min_cosine, int32_t n_classes, void* stream);
+/* ring, pending state and command of stream `index` (every stream for index -1) to none; classes and thresholds stay */
+int cp_online_gate_reset(const cp_online_gate_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index, void* stream);
+/* logits (total_rows, ldl) f32 as a decoder's push emits them (ldl = 64 behind the multi-stream decoders, K behind the single
+ * ones); row0, m (n_streams) int32 on the device: stream s owns the rows row0[s] .. row0[s] + m[s] - 1, m[s] <=
+ * CP_ONLINE_MAX_WINDOWS, total_rows <= CP_ONLINE_MULTI_MAX_ROWS.  command, accepted (total_rows) int32 and conf, margin
+ * (total_rows) f32, which may be NULL, receive the rows' outputs.  A stream with m[s] = 0, without classes, with more classes than
+ * ldl, or whose rows do not lie inside 0..total_rows-1 is left untouched (its outputs are not written).  Nothing is enqueued for total_rows = 0. */
+int cp_online_gate_push(const cp_online_gate_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, const float* logits,
+                        int32_t ldl, const int32_t* row0, const int32_t* m, int32_t total_rows, int32_t* command,
+                        int32_t* accepted, float* conf, float* margin, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,9 @@ windows, split into windows / accumulate / table, next to the same table compose
 eval forward and index_add_; (b) recording_windows against the offline windows on a 60 s recording; (c) on synthetic people
 (a channel-amplitude pattern per class times a gain pattern per person) the accuracy of the model's one-hot rows and of
 enrolled rows on a held-out recording of a person the model has not seen.
+With --gate the command gate (CommandGate.push, csrc/online_gate.cuh) is timed against the ungated decoder.push(
+return_logits=True) in the same run: 1 and 25 windows on OnlineDecoder and 256 streams x 1 window on MultiStreamDecoder, plus
+the gate's launch alone (CommandGate.apply on the logits of one push).
 Each push is timed from the host with a synchronisation behind it (the latency a control loop sees); kernels per push are
 counted with torch.profiler over a few pushes.  One JSON line per case, and a table with --out.
 
@@ -25,6 +28,7 @@ counted with torch.profiler over a few pushes.  One JSON line per case, and a ta
     python tools/online_bench.py --streams --iters 50 --out profiles/online_multi_latency.txt
     python tools/online_bench.py --streams --adapt --iters 100 --out profiles/online_multi_adapt_latency.txt
     python tools/online_bench.py --enroll --iters 10 --out profiles/online_enroll.txt
+    python tools/online_bench.py --gate --iters 200 --out profiles/online_gate_latency.txt
 """
 import argparse
 import json
@@ -37,7 +41,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from contrastiveprosthetics_amd import AdaptiveMultiStreamDecoder, MultiStreamDecoder, OnlineDecoder  # noqa: E402
+from contrastiveprosthetics_amd import AdaptiveMultiStreamDecoder, CommandGate, MultiStreamDecoder, OnlineDecoder  # noqa: E402
 from contrastiveprosthetics_amd.engine import Engine                       # noqa: E402
 from contrastiveprosthetics_amd.preprocess import normalize_, preprocess_segments   # noqa: E402
 
@@ -77,6 +81,7 @@ def main():
     ap.add_argument("--streams", action="store_true", help="multi-stream decoder against S single-stream decoders in turn")
     ap.add_argument("--counts", default="1,8,64,256", help="--streams: stream counts")
     ap.add_argument("--enroll", action="store_true", help="class enrolment: time, one-pass windows, accuracy on a synthetic person")
+    ap.add_argument("--gate", action="store_true", help="the command gate against the ungated push with logits")
     a = ap.parse_args()
     if a.enroll:
         return enroll_main(a)
@@ -89,6 +94,8 @@ def main():
     table = (e.values.views["glove_net.easy.0.weight"].t() + e.values.views["glove_net.easy.0.bias"]).contiguous()
     tn = table / table.norm(dim=-1, keepdim=True)
     rows = []
+    if a.gate:
+        return gate_main(a, e, stream, mean, std, classes)
     if a.adapt and a.streams:
         return streams_adapt_main(a, e, stream, mean, std, classes)
     if a.adapt:
@@ -347,6 +354,67 @@ def adapt_main(a, e, stream, mean, std, classes):
                     "# part of it that makes the windows with the offline transform (preprocess_segments + normalize_)\n")
             for r in cal:
                 f.write(f"{r['kind']:<12} {r['dtype']:<5} {'':>7} {r['windows']:>7} {r['median_ms']:>8.2f} ms\n")
+
+
+def gate_main(a, e, stream, mean, std, classes):
+    """gated against ungated pushes, interleaved case by case in one run; the gate closes nothing here (its work per window
+    does not depend on the thresholds) but runs dwell, release and margin weights"""
+    rows = []
+    settings = dict(min_cosine=0.2, min_margin=0.02, min_votes=3, dwell=5, release=10, weight="margin")
+    for dtype in ("f32", "bf16"):
+        for S, n in ((1, 20), (1, 500), (256, 20)):
+            m = n // 20
+            if S == 1:
+                plain = OnlineDecoder(e, mean, std, classes=classes, dtype=dtype)
+                gated = OnlineDecoder(e, mean, std, classes=classes, dtype=dtype)
+            else:
+                plain = MultiStreamDecoder(e, mean, std, S, dtype=dtype, max_rows=S * m)
+                gated = MultiStreamDecoder(e, mean, std, S, dtype=dtype, max_rows=S * m)
+                for s in range(S):
+                    plain.set_classes(s, classes=classes)
+                    gated.set_classes(s, classes=classes)
+            gate = CommandGate(gated, **settings)
+            pos = [0]
+            span = stream.shape[0] - S * n
+
+            def chunk():
+                base = pos[0] % span
+                pos[0] += S * n
+                return stream[base:base + S * n]
+
+            if S == 1:
+                fns = (("ungated", lambda: plain.push(chunk(), return_logits=True)), ("gated", lambda: gate.push(chunk())))
+            else:
+                fns = (("ungated", lambda: plain.push_packed(chunk(), [n] * S, return_logits=True)),
+                       ("gated", lambda: gate.push_packed(chunk(), [n] * S)))
+            res = {}
+            for name, fn in fns:
+                med, p90 = time_pushes(fn, a.iters, a.warmup)
+                res[name] = med
+                rows.append(dict(kind=name, dtype=dtype, streams=S, windows=m, median_us=round(med, 1), p90_us=round(p90, 1),
+                                 kernels_per_push=count_kernels(fn, pushes=3)))
+            logits = [r[2] for r in plain.push_packed(chunk(), [n] * S, return_logits=True)] if S > 1 \
+                else plain.push(chunk(), return_logits=True)[2]
+            alone = CommandGate(plain, **settings)
+            med, p90 = time_pushes(lambda: alone.apply(logits), a.iters, a.warmup)
+            rows.append(dict(kind="gate alone", dtype=dtype, streams=S, windows=m, median_us=round(med, 1), p90_us=round(p90, 1),
+                             kernels_per_push=count_kernels(lambda: alone.apply(logits), pushes=3)))
+            for r in rows[-3:]:
+                r["gated_minus_ungated_us"] = round(res["gated"] - res["ungated"], 1)
+                print(json.dumps(r), flush=True)
+            del plain, gated, gate, alone
+            torch.cuda.empty_cache()
+    if a.out:
+        dev = torch.cuda.get_device_name(0)
+        with open(a.out, "w") as f:
+            f.write(f"# tools/online_bench.py --gate --iters {a.iters} --warmup {a.warmup} on {dev}\n")
+            f.write("# ungated = decoder.push(return_logits=True), gated = CommandGate.push on a decoder of its own, gate alone =\n"
+                    "# CommandGate.apply on the logits of one push; per-push wall time, host-synchronised (median, p90), kernels per\n"
+                    "# push (torch.profiler: library kernels plus torch's own), delta = gated - ungated median\n")
+            f.write(f"{'kind':<11} {'dtype':<5} {'streams':>7} {'windows':>7} {'median_us':>10} {'p90_us':>9} {'kernels':>8} {'delta_us':>9}\n")
+            for r in rows:
+                f.write(f"{r['kind']:<11} {r['dtype']:<5} {r['streams']:>7} {r['windows']:>7} {r['median_us']:>10.1f} {r['p90_us']:>9.1f} "
+                        f"{r['kernels_per_push']:>8.1f} {r['gated_minus_ungated_us']:>9.1f}\n")
 
 
 def streams_main(a, e, stream, mean, std, classes):
