@@ -1096,7 +1096,8 @@ extern "C" int cp_preprocess_emg(const float* raw, int64_t n_segments, int32_t s
                                  int32_t n_coef, int32_t rms_window, float gain, const int32_t* time_idx, int32_t n_out,
                                  float* out, void* stream) {
     if (!raw || !b || !a || !time_idx || !out || n_segments <= 0 || n_coef < 2 || n_coef > PP_MAXCOEF || a[0] == 0.0 ||
-        rms_window < 1 || rms_window > PP_MAXWIN || n_out <= 0 || n_out > PP_MAXOUT || seg_len < rms_window)
+        rms_window < 1 || rms_window > PP_MAXWIN || n_out <= 0 || n_out > PP_MAXOUT || seg_len < rms_window ||
+        seg_len > 2147483647 - 16)                         // the kernel indexes 16 samples ahead of t in int
         return fail(CP_ERR_ARG, "cp_preprocess_emg args");
     PreprocArgs p{};
     p.raw = raw; p.out = out; p.S = n_segments; p.L = seg_len; p.n_out = n_out; p.n_coef = n_coef; p.win = rms_window; p.gain = gain;
@@ -1114,7 +1115,7 @@ extern "C" int cp_preprocess_emg(const float* raw, int64_t n_segments, int32_t s
         while (k >= 0 && time_idx[order[k]] > time_idx[v]) { order[k + 1] = order[k]; --k; }
         order[k + 1] = v;
     }
-    for (int i = 0; i < n_out; ++i) { p.t_sorted[i] = (short)time_idx[order[i]]; p.slot_sorted[i] = (short)order[i]; }
+    for (int i = 0; i < n_out; ++i) { p.t_sorted[i] = time_idx[order[i]]; p.slot_sorted[i] = (short)order[i]; }
     const int64_t threads = n_segments * PP_C;
     const dim3 grid((unsigned)((threads + 255) / 256));
     if (n_coef == 9 && rms_window == 11) hipLaunchKernelGGL((preprocess_kernel<9, 11>), grid, dim3(256), 0, (hipStream_t)stream, p);

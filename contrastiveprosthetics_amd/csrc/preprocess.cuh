@@ -22,8 +22,12 @@ struct PreprocArgs {
     int L, n_out, n_coef, win;
     float gain;
     double b[PP_MAXCOEF], a[PP_MAXCOEF];          // normalised (a[0] == 1)
-    short t_sorted[PP_MAXOUT], slot_sorted[PP_MAXOUT];   // kept samples sorted by time (a time may repeat)
+    int32_t t_sorted[PP_MAXOUT];    // kept positions of the RMS series, ascending (a position may repeat): 32 bits, as
+                                    // every other position in the kernel, so any seg_len an int32 holds is served
+    short slot_sorted[PP_MAXOUT];   // the output row of each (n_out <= 256)
 };
+// passed by value: 1,856 bytes (1 KB of positions, 512 B of slots, 272 B of coefficients), far below the 4 KB of kernel arguments
+static_assert(sizeof(PreprocArgs) <= 2048, "PreprocArgs is a kernel argument");
 
 // NB / WIN > 0: coefficient count and RMS window known at compile time (the reference's 9 and 11): the filter state
 // and the window of squares stay in registers with static indices.  0 = take them from the arguments (any filter).

@@ -169,7 +169,9 @@ def _class_table(e: Engine, classes=None, glove=None, table=None, ids=None):
 
 
 def _calibration_windows(raw: torch.Tensor, b, a, phase: int, mean_std: torch.Tensor) -> torch.Tensor:
-    """The windows a fresh stream emits for `raw` (n, 12), by the offline path (preprocess_segments + normalize_)."""
+    """The windows a fresh stream emits for `raw` (n, 12), by the offline path (preprocess_segments + normalize_): the whole
+    recording as one segment, 256 kept positions per call.  Valid for a recording of any length: cp_preprocess_emg keeps
+    its positions in 32 bits."""
     from .preprocess import normalize_, preprocess_segments
     if raw.device.type != "cuda" or raw.dtype != torch.float32 or raw.dim() != 2 or raw.shape[1] != EMG_DIM:
         raise ValueError("raw must be an (n, 12) float32 tensor on the GPU")

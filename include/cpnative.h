@@ -285,7 +285,10 @@ int cp_confusion(const int32_t* y_pred, const int64_t* labels, int64_t n_groups,
  * IIR coefficients (scipy.signal.butter(4, (20, 450)/1000, "bandpass") in the reference); gain = 2**10;
  * rms_window = 11; time_idx: HOST pointer to the n_out <= 256 kept positions of the RMS series
  * (load.py:115 time_mask, whose uint8 wraps modulo 256 -- pass what the reference computes).
- * out (n_segments, n_out, 12) f32.  Rounding points follow NumPy/SciPy exactly: bit-identical samples. */
+ * out (n_segments, n_out, 12) f32.  Rounding points follow NumPy/SciPy exactly: bit-identical samples.
+ * Accepted range: rms_window <= seg_len <= 2**31 - 17; every time_idx[i] in 0 .. n_rms - 1 with
+ * n_rms = seg_len - 2 * (rms_window / 2), in any order, repeats allowed.  Positions are 32-bit from here to the
+ * kernel, so a segment may be a whole recording.  Anything else is CP_ERR_ARG before a launch. */
 int cp_preprocess_emg(const float* raw, int64_t n_segments, int32_t seg_len, const double* b, const double* a,
                       int32_t n_coef, int32_t rms_window, float gain, const int32_t* time_idx, int32_t n_out,
                       float* out, void* stream);

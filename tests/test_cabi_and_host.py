@@ -79,6 +79,30 @@ def test_host_only_entry_points(lib):
     assert lib.cp_optimizer_scratch_floats(numel, 3) >= 3 + 1 + 1
 
 
+def test_preprocess_entry_validates_long_segments_before_it_launches(lib):
+    """cp_preprocess_emg checks its keep list against the RMS series in 32 bits, at a segment length a 16-bit position
+    cannot hold: every refusal returns before a launch (the device pointers are dummies)"""
+    seg_len, win = 70000, 11
+    n_rms = seg_len - 2 * (win // 2)
+    b = (ctypes.c_double * 9)(*([0.1] * 9))
+    a = (ctypes.c_double * 9)(1.0, *([0.0] * 8))
+    dummy = ctypes.create_string_buffer(64)
+
+    def call(idx, n_out=None, length=seg_len):
+        t = (ctypes.c_int32 * len(idx))(*idx)
+        return lib.cp_preprocess_emg(dummy, 1, length, b, a, 9, win, 1024.0, t, len(idx) if n_out is None else n_out, dummy, None)
+
+    for name, rc in (("time_idx = [n_rms]", call([n_rms])),
+                     ("time_idx = [0, n_rms - 1, n_rms]", call([0, n_rms - 1, n_rms])),
+                     ("time_idx = [-1]", call([-1])),
+                     ("time_idx = [65536 + n_rms]", call([65536 + n_rms])),       # in range once truncated to 16 bits
+                     ("n_out = 257", call([0] * 257)),
+                     ("n_out = 0", call([0], n_out=0)),
+                     ("seg_len < rms_window", call([0], length=win - 1))):
+        assert rc == 10001, (name, rc, lib.cp_last_error())
+        assert b"cp_preprocess_emg" in lib.cp_last_error(), name
+
+
 def test_missing_library_is_an_error(monkeypatch):
     from contrastiveprosthetics_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)

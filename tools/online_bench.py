@@ -280,11 +280,9 @@ def enroll_main(a):
     off = _wall(lambda: _calibration_windows(raw60, probe._b, probe._a, 0, probe.mean_std), max(2, a.iters // 3))
     w_one = recording_windows(raw60, probe.mean_std, probe._b, probe._a, 0)
     w_off = _calibration_windows(raw60, probe._b, probe._a, 0, probe.mean_std)
-    k16 = 32767 // 20 + 1                                          # the offline transform keeps its positions in 16 bits
     push = OnlineDecoder(e, mean, std, classes=classes).push(raw60, return_windows=True)[2]
     out(dict(part="b", samples=120000, recording_windows_ms=round(one, 3), calibration_windows_ms=round(off, 3),
-             ratio=round(off / one, 1), equal_to_push=torch.equal(w_one, push), equal_to_offline=torch.equal(w_one, w_off),
-             equal_to_offline_below_32768_samples=torch.equal(w_one[:k16], w_off[:k16])))
+             ratio=round(off / one, 1), equal_to_push=torch.equal(w_one, push), equal_to_offline=torch.equal(w_one, w_off)))
     if a.out:
         dev = torch.cuda.get_device_name(0)
         with open(a.out, "w") as f:
