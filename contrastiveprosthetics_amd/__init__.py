@@ -12,7 +12,8 @@ __version__ = "0.1.0"
 def __getattr__(name):
     # OnlineDecoder pulls in torch and the engine; importing the package stays light until it is asked for
     if name in ("OnlineDecoder", "MultiStreamDecoder", "AdaptiveMultiStreamDecoder", "recording_windows", "window_labels",
-                "CommandGate", "thresholds_from_logits"):
+                "CommandGate", "thresholds_from_logits", "REST", "IGNORE", "expected_commands", "score_commands", "pick_gate",
+                "sweep_gate", "gate_grid"):
         from . import online
         return getattr(online, name)
     raise AttributeError(name)

@@ -3509,3 +3509,39 @@ extern "C" int cp_online_gate_push(const cp_online_gate_config* cfg, int32_t n_s
     CKL("og_push_kernel");
     return 0;
 }
+
+// gate sweep: n_configs settings over one recording, one wave each, scored on the device (og_rows_kernel, og_sweep_kernel)
+static_assert(OG_SCORES == CP_ONLINE_GATE_SCORES && sizeof(OgRow) == 12, "gate sweep layout");
+static_assert(sizeof(OgConfig) == sizeof(cp_online_gate_config), "the sweep reads cp_online_gate_config from the device as OgConfig");
+
+extern "C" size_t cp_online_gate_sweep_scratch_bytes(int64_t n_rows) {
+    if (n_rows < 1) n_rows = 1;
+    return align256((size_t)n_rows * sizeof(OgRow));
+}
+
+extern "C" int cp_online_gate_sweep(const float* logits, int32_t ldl, int64_t n_rows, int32_t n_classes, const int32_t* expected_slot,
+                                    const cp_online_gate_config* configs, const float* min_cosine, int32_t n_configs, void* scratch,
+                                    size_t scratch_bytes, int64_t* scores, int32_t* commands, void* stream) {
+    if (n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return fail(CP_ERR_ARG, "cp_online_gate_sweep: n_classes outside 1..64");
+    if (ldl < n_classes) return fail(CP_ERR_ARG, "cp_online_gate_sweep: ldl must be at least n_classes");
+    if (n_configs < 1 || n_configs > CP_ONLINE_GATE_SWEEP_MAX_CONFIGS)
+        return fail(CP_ERR_ARG, "cp_online_gate_sweep: n_configs outside 1..65536");
+    if (n_rows < 1 || n_rows > INT32_MAX) return fail(CP_ERR_ARG, "cp_online_gate_sweep: n_rows outside 1..2^31-1");
+    if (!logits || !expected_slot || !configs || !min_cosine || !scratch || !scores)
+        return fail(CP_ERR_ARG, "cp_online_gate_sweep: logits, expected_slot, configs, min_cosine, scratch and scores are required");
+    if ((uintptr_t)logits % 4 || (uintptr_t)expected_slot % 4 || (uintptr_t)configs % 4 || (uintptr_t)min_cosine % 4 ||
+        (uintptr_t)scratch % 4 || (uintptr_t)scores % 8 || (uintptr_t)commands % 4)
+        return fail(CP_ERR_ARG, "cp_online_gate_sweep: misaligned argument");
+    if (scratch_bytes < (size_t)n_rows * sizeof(OgRow)) return fail(CP_ERR_ARG, "cp_online_gate_sweep: scratch too small");
+    const int rows_per_block = 4 * OG_ROWS_PER_WAVE;
+    hipLaunchKernelGGL(og_rows_kernel, dim3((unsigned)((n_rows + rows_per_block - 1) / rows_per_block)), dim3(256), 0, (hipStream_t)stream,
+                       logits, (int)ldl, (long long)n_rows, (int)n_classes, (OgRow*)scratch);
+    CKL("og_rows_kernel");
+    OgSweepArgs a{};
+    a.rows = (const OgRow*)scratch; a.expected = expected_slot; a.configs = (const OgConfig*)configs; a.min_cosine = min_cosine;
+    a.n_rows = n_rows; a.n_configs = n_configs; a.K = n_classes; a.scores = (long long*)scores; a.commands = commands;
+    hipLaunchKernelGGL(og_sweep_kernel, dim3((n_configs + OG_SWEEP_WAVES - 1) / OG_SWEEP_WAVES), dim3(64 * OG_SWEEP_WAVES), 0,
+                       (hipStream_t)stream, a);
+    CKL("og_sweep_kernel");
+    return 0;
+}

@@ -24,7 +24,9 @@ own `OnlineDecoder(adapt=alpha)`.
 
 `CommandGate` wraps any of the four decoders and turns the logits of every push into a command a hand can follow, on the
 device (cp_online_gate_*, csrc/online_gate.cuh): rejection by cosine threshold and margin, a weighted vote ring, a dwell time
-before a new grasp and a release time before none.
+before a new grasp and a release time before none.  `sweep_gate` chooses its settings: it runs many of them over the logits
+of a cued recording in one pass on the device (cp_online_gate_sweep) and returns each one's score against the cues
+(`expected_commands`, `score_commands`, `pick_gate`).
 
 The number of windows a push emits follows from sample counts alone (`windows_emitted`), so a push never waits for the device:
 its outputs are device tensors on torch's current stream.
@@ -993,6 +995,21 @@ def thresholds_from_logits(logits, labels, ids, keep: float = 0.95) -> dict:
 
 
 _GATE_WEIGHTS = {"count": 0, "margin": 1}
+_GATE_KEYS = ("min_cosine", "default", "min_margin", "min_votes", "dwell", "release", "weight", "vote")
+
+
+def _gate_settings(new: dict):
+    """min_margin, min_votes, dwell, release, weight of a gate as the C config takes them, or ValueError"""
+    if not isinstance(new["weight"], str) or new["weight"] not in _GATE_WEIGHTS:
+        raise ValueError("weight must be 'count' or 'margin'")
+    mm = float(new["min_margin"])
+    if not (mm >= 0.0 and np.isfinite(mm)):
+        raise ValueError("min_margin must be finite and >= 0")
+    for k, low in (("min_votes", 1), ("dwell", 1), ("release", 0)):
+        v = new[k]
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not low <= int(v) < 2 ** 31:
+            raise ValueError(f"{k} must be an int >= {low}")
+    return mm, int(new["min_votes"]), int(new["dwell"]), int(new["release"]), _GATE_WEIGHTS[new["weight"]]
 
 
 class CommandGate:
@@ -1049,17 +1066,26 @@ class CommandGate:
             if k not in new:
                 raise TypeError(f"set() takes min_margin, min_votes, dwell, release and weight, not {k!r}")
             new[k] = v
-        if new["weight"] not in _GATE_WEIGHTS:
-            raise ValueError("weight must be 'count' or 'margin'")
-        mm = float(new["min_margin"])
-        if not (mm >= 0.0 and np.isfinite(mm)):
-            raise ValueError("min_margin must be finite and >= 0")
-        for k, low in (("min_votes", 1), ("dwell", 1), ("release", 0)):
-            v = new[k]
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not low <= int(v) < 2 ** 31:
-                raise ValueError(f"{k} must be an int >= {low}")
-        c.min_margin, c.min_votes, c.dwell, c.release = mm, int(new["min_votes"]), int(new["dwell"]), int(new["release"])
-        c.weight = _GATE_WEIGHTS[new["weight"]]
+        mm, mv, dw, rl, w = _gate_settings(new)
+        c.min_margin, c.min_votes, c.dwell, c.release, c.weight = mm, mv, dw, rl, w
+
+    def use(self, config: dict):
+        """Apply one config of `sweep_gate` / `gate_grid` (a dict with CommandGate's keys): the settings through `set`, and
+        `min_cosine` (with `default`), if it is there, through `set_thresholds` on every stream.  `vote` is fixed at construction:
+        a config that names another one is refused.  Nothing changes if a value is refused."""
+        extra = set(config) - set(_GATE_KEYS)
+        if extra:
+            raise ValueError(f"a gate config takes {', '.join(_GATE_KEYS)}, not {sorted(extra)[0]!r}")
+        if "vote" in config and config["vote"] != self.vote:
+            raise ValueError("vote is fixed at construction: the ring is laid out by it")
+        if "default" in config and "min_cosine" not in config:
+            raise ValueError("default goes with min_cosine")
+        spec = self._check_thresholds(config["min_cosine"], config.get("default", -2.0)) if "min_cosine" in config else None
+        self.set(**{k: v for k, v in config.items() if k not in ("vote", "min_cosine", "default")})
+        if spec is not None:
+            for s in range(self.n_streams):
+                self._thr[s] = spec
+                self._ids_seen[s] = None
 
     @staticmethod
     def _check_thresholds(min_cosine, default):
@@ -1287,3 +1313,194 @@ class CommandGate:
             self.decoder.reset()
             self._dev_reset(-1)
         self._left = self._seen_now()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# gate sweep: many CommandGate settings over one cued recording, scored on the device (cp_online_gate_sweep)
+# ---------------------------------------------------------------------------------------------------------------------------
+REST = -1                               # expected: the hand should do nothing
+IGNORE = -2                             # expected: the window is not scored
+SCORE_KEYS = ("n_cue", "n_rest", "hit", "wrong", "false_active", "switches", "segments", "reached", "latency_sum",
+              "wrong_segments")
+
+
+def _ids_array(ids) -> np.ndarray:
+    cid = np.asarray(ids.detach().cpu() if isinstance(ids, torch.Tensor) else ids).reshape(-1)
+    if cid.dtype.kind not in "iu" or not 1 <= cid.shape[0] <= MAX_CLASSES:
+        raise ValueError(f"ids must hold 1..{MAX_CLASSES} integer class ids")
+    cid = cid.astype(np.int64)
+    if (np.diff(cid) <= 0).any() or cid[0] < 0 or cid[-1] >= 2 ** 31 - 1:
+        raise ValueError("ids must be ascending, distinct and in 0..2**31-2")
+    return cid
+
+
+def expected_commands(labels, ids, phase: int = 0, rest=None) -> np.ndarray:
+    """What the cue asks of each window of a recording with one label per raw sample (`window_labels(labels, phase)`): the
+    class id if the window's label is one of `ids`, REST if it is `rest` (the label that means "do nothing"; None: there is no
+    such label), IGNORE for a mixed or unlabelled window and for any other label.  (K_w,) int64; host only (numpy)."""
+    cid = _ids_array(ids)
+    wl = window_labels(labels, phase)
+    out = np.full(wl.shape, IGNORE, dtype=np.int64)
+    known = (wl >= 0) & np.isin(wl, cid)
+    out[known] = wl[known]
+    if rest is not None:
+        out[(wl >= 0) & (wl == int(rest))] = REST
+    return out
+
+
+def score_commands(command, expected) -> dict:
+    """The score of a command sequence against the cues; this function is its definition (the sweep kernel restates it).
+    command (M,): class ids or -1 for none; expected (M,): class ids, REST or IGNORE.  With command[-1] = -1 and a segment a
+    maximal run of consecutive windows with the same expected >= 0 (any other value ends it), all integers:
+    n_cue            windows with expected >= 0
+    n_rest           windows with expected == REST
+    hit              cue windows with command == expected
+    wrong            cue windows with command >= 0 and command != expected
+    false_active     rest windows with command != -1
+    switches         windows (all of them) with command[j] != command[j-1]
+    segments         number of segments
+    reached          segments with at least one hit
+    latency_sum      over reached segments, index of the first hit - index of the segment's first window
+    wrong_segments   segments with at least one wrong window
+    Host only (numpy)."""
+    cmd = np.asarray(command.detach().cpu() if isinstance(command, torch.Tensor) else command).astype(np.int64).reshape(-1)
+    exp = np.asarray(expected.detach().cpu() if isinstance(expected, torch.Tensor) else expected).astype(np.int64).reshape(-1)
+    if cmd.shape != exp.shape:
+        raise ValueError("command and expected must hold one entry per window each")
+    cue, rest = exp >= 0, exp == REST
+    is_hit = cue & (cmd == exp)
+    is_wrong = cue & (cmd >= 0) & (cmd != exp)
+    prev_cmd = np.concatenate([[-1], cmd[:-1]])
+    prev_exp = np.concatenate([[IGNORE], exp[:-1]])
+    start = np.nonzero(cue & (exp != prev_exp))[0]                   # the first window of every segment
+    seg = np.cumsum(cue & (exp != prev_exp)) - 1                     # the segment a cue window lies in
+    n_seg = int(start.shape[0])
+    first_hit = np.full(n_seg, -1, dtype=np.int64)
+    hits = np.nonzero(is_hit)[0]
+    first_hit[seg[hits][::-1]] = hits[::-1]                          # (the earliest hit is written last)
+    reached = first_hit >= 0
+    out = dict(n_cue=cue.sum(), n_rest=rest.sum(), hit=is_hit.sum(), wrong=is_wrong.sum(),
+               false_active=(rest & (cmd != -1)).sum(), switches=(cmd != prev_cmd).sum(), segments=n_seg, reached=reached.sum(),
+               latency_sum=(first_hit - start)[reached].sum(), wrong_segments=np.unique(seg[is_wrong]).shape[0])
+    assert tuple(out) == SCORE_KEYS
+    return {k: int(v) for k, v in out.items()}
+
+
+def pick_gate(scores, max_false_rate: float = 0.02, max_wrong_rate: float = 0.05):
+    """The index of the config to use, from the scores of `sweep_gate` (a dict of (G,) arrays): among the configs with
+    false_active / n_rest <= max_false_rate and wrong / n_cue <= max_wrong_rate (a rate with a zero denominator is 0) the one with
+    the most hits, then the smallest latency_sum / max(reached, 1), then the smallest index; None if no config is eligible."""
+    sc = {k: np.asarray(scores[k], dtype=np.int64).reshape(-1) for k in SCORE_KEYS}
+
+    def rate(num, den):
+        return np.where(den > 0, num / np.maximum(den, 1), 0.0)
+
+    ok = (rate(sc["false_active"], sc["n_rest"]) <= max_false_rate) & (rate(sc["wrong"], sc["n_cue"]) <= max_wrong_rate)
+    if not ok.any():
+        return None
+    latency = sc["latency_sum"] / np.maximum(sc["reached"], 1)
+    idx = np.nonzero(ok)[0]
+    return int(min(idx.tolist(), key=lambda g: (-int(sc["hit"][g]), float(latency[g]), g)))
+
+
+def gate_grid(**lists) -> list:
+    """The cartesian product of lists of CommandGate settings as a list of config dicts, the last name varying fastest:
+    gate_grid(dwell=[1, 3], release=[0, 5]) -> [{dwell: 1, release: 0}, {dwell: 1, release: 5}, {dwell: 3, ...}, ...]."""
+    import itertools
+    extra = set(lists) - set(_GATE_KEYS)
+    if extra:
+        raise ValueError(f"a gate config takes {', '.join(_GATE_KEYS)}, not {sorted(extra)[0]!r}")
+    names = list(lists)
+    return [dict(zip(names, combo)) for combo in itertools.product(*(list(lists[n]) for n in names))]
+
+
+def _sweep_configs(configs, cid: np.ndarray):
+    """configs (dicts with CommandGate's keys) -> the device arrays' host images: (G, 6) int32 in the layout of
+    cp_online_gate_config (min_margin as its f32 bits) and (G, 64) f32 thresholds per class slot.  ValueError as CommandGate raises."""
+    configs = list(configs)
+    if not 1 <= len(configs) <= _lib.CP_ONLINE_GATE_SWEEP_MAX_CONFIGS:
+        raise ValueError(f"sweep_gate takes 1..{_lib.CP_ONLINE_GATE_SWEEP_MAX_CONFIGS} configs, got {len(configs)}")
+    cfg = np.zeros((len(configs), 6), dtype=np.int32)
+    thr = np.zeros((len(configs), MAX_CLASSES), dtype=np.float32)
+    known = set(cid.tolist())
+    for g, c in enumerate(configs):
+        if not isinstance(c, dict):
+            raise ValueError(f"config {g} is not a dict")
+        extra = set(c) - set(_GATE_KEYS)
+        if extra:
+            raise ValueError(f"config {g}: a gate config takes {', '.join(_GATE_KEYS)}, not {sorted(extra, key=str)[0]!r}")
+        new = dict(min_margin=0.0, min_votes=1, dwell=1, release=1, weight="count")
+        new.update({k: c[k] for k in new if k in c})
+        vote = c.get("vote", VOTE)
+        if isinstance(vote, bool) or not isinstance(vote, (int, np.integer)) or not 1 <= int(vote) <= _lib.CP_ONLINE_MAX_VOTE:
+            raise ValueError(f"vote must lie in 1..{_lib.CP_ONLINE_MAX_VOTE}")
+        mm, mv, dw, rl, w = _gate_settings(new)
+        spec, d = CommandGate._check_thresholds(c.get("min_cosine", -2.0), c.get("default", -2.0))
+        stray = set(spec) - known
+        if stray:
+            raise ValueError(f"config {g}: min_cosine names class id {sorted(stray)[0]}, which is not among ids")
+        cfg[g, :5] = int(vote), mv, dw, rl, w
+        cfg[g, 5:].view(np.float32)[0] = mm
+        thr[g, :cid.shape[0]] = [spec.get(int(i), d) for i in cid]
+    return cfg, thr
+
+
+def _sweep_dev(logits: torch.Tensor, slots: np.ndarray, k: int, cfg: np.ndarray, thr: np.ndarray, want_commands: bool):
+    """the device side of `sweep_gate` (one call of cp_online_gate_sweep) -> scores (G, 10) int64 on the host, commands (G, M)
+    int32 slots on the device or None"""
+    lib = _lib.load()
+    dev, m, g = logits.device, int(logits.shape[0]), int(cfg.shape[0])
+    with torch.cuda.device(dev):
+        exp_d = torch.from_numpy(slots).to(dev)
+        cfg_d = torch.from_numpy(cfg).to(dev)
+        thr_d = torch.from_numpy(thr).to(dev)
+        scratch = torch.empty(lib.cp_online_gate_sweep_scratch_bytes(m), dtype=torch.uint8, device=dev)
+        scores = torch.empty(g, _lib.CP_ONLINE_GATE_SCORES, dtype=torch.int64, device=dev)
+        commands = torch.empty(g, m, dtype=torch.int32, device=dev) if want_commands else None
+        _lib.check(lib.cp_online_gate_sweep(logits.data_ptr(), int(logits.stride(0)), m, k, exp_d.data_ptr(), cfg_d.data_ptr(),
+                                            thr_d.data_ptr(), g, scratch.data_ptr(), scratch.numel(), scores.data_ptr(),
+                                            commands.data_ptr() if want_commands else None,
+                                            torch.cuda.current_stream(dev).cuda_stream), "cp_online_gate_sweep")
+        return scores.cpu().numpy(), commands
+
+
+def sweep_gate(logits, expected, ids, configs, return_commands: bool = False):
+    """Score many CommandGate settings over one cued recording in one pass on the device (cp_online_gate_sweep: one wave per
+    config, each from a fresh gate).  logits (M, K) f32 on the GPU, what `push(..., return_logits=True)` returned for the
+    recording; expected (M,) as `expected_commands` gives it; ids the K ascending class ids of the columns; configs a sequence
+    of dicts with CommandGate's keys (min_cosine: a float or {id: float} with `default`; min_margin, min_votes, dwell, release,
+    weight, vote), missing keys at CommandGate's defaults (vote: 25), checked as CommandGate checks them before anything is
+    enqueued.  Returns {key: (G,) int64 array} with the keys of `score_commands`: config g's entry is `score_commands` of the
+    commands a fresh CommandGate with config g returns for these logits.  return_commands=True: (scores, commands) with
+    commands (G, M) int32 on the GPU, class ids or -1.  One host synchronisation: the copy of the score table."""
+    cid = _ids_array(ids)
+    cfg, thr = _sweep_configs(configs, cid)
+    if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.dim() != 2 or logits.shape[1] != cid.shape[0]:
+        raise ValueError("logits must be an (M, K) float32 tensor with one column per id")
+    exp = np.asarray(expected.detach().cpu() if isinstance(expected, torch.Tensor) else expected)
+    if exp.shape != (logits.shape[0],) or exp.dtype.kind not in "iu":
+        raise ValueError(f"expected must hold one integer entry per window ({logits.shape[0]})")
+    exp = exp.astype(np.int64)
+    pos = np.minimum(np.searchsorted(cid, exp), cid.shape[0] - 1)
+    if ((exp >= 0) & (cid[pos] != exp)).any() or (exp < IGNORE).any():
+        raise ValueError("expected holds class ids among ids, REST or IGNORE")
+    slots = np.where(exp >= 0, pos, exp).astype(np.int32)
+    g, m = cfg.shape[0], int(logits.shape[0])
+    if m == 0:
+        scores = np.zeros((g, len(SCORE_KEYS)), dtype=np.int64)
+        commands = torch.empty(g, 0, dtype=torch.int32, device=logits.device) if return_commands else None
+    else:
+        if logits.device.type != "cuda":
+            raise ValueError("logits must be on the GPU")
+        if logits.stride(1) != 1 or (m > 1 and logits.stride(0) < logits.shape[1]):
+            logits = logits.contiguous()
+        scores, commands = _sweep_dev(logits, slots, int(cid.shape[0]), cfg, thr, return_commands)
+    out = {k: scores[:, i].copy() for i, k in enumerate(SCORE_KEYS)}
+    if not return_commands:
+        return out
+    if m and not np.array_equal(cid, np.arange(cid.shape[0])):        # slots -> class ids, a block of rows at a time
+        table = torch.from_numpy(np.concatenate([[-1], cid]).astype(np.int32)).to(commands.device)
+        step = max(1, (1 << 24) // m)
+        for lo in range(0, g, step):
+            commands[lo:lo + step] = table[(commands[lo:lo + step] + 1).long()]
+    return out, commands

@@ -663,6 +663,43 @@ int cp_online_gate_push(const cp_online_gate_config* cfg, int32_t n_streams, voi
                         int32_t ldl, const int32_t* row0, const int32_t* m, int32_t total_rows, int32_t* command,
                         int32_t* accepted, float* conf, float* margin, void* stream);
 
+/* ---- gate sweep: many gate settings over one cued recording, scored on the device ------------------------------------------
+ * A search over the gate's settings is a set of independent runs of the state machine over the same logits.  The sweep runs
+ * n_configs of them in one pair of launches (og_rows_kernel: the part of a row no setting enters, once per row; og_sweep_kernel:
+ * one wave per config) and scores each command sequence against the cues, so that only a table of integer counters has to
+ * leave the device.
+ * - Every config starts from the zero gate state: empty ring, nothing pending, command none.
+ * - Config g's command sequence is the one cp_online_gate_push produces for the same rows, config and thresholds
+ *   (min_cosine[g], one per class slot), in any cut into calls.  Commands are reported as class slots (-1: none): with a fixed
+ *   id list slots and ids are the same information.
+ * - expected_slot[j] says what the cue asked for in window j: a class slot 0..n_classes-1, -1 for rest (the hand should do
+ *   nothing), -2 (or any other negative value) for a window that is not scored.  scores[g] is, with command[-1] = -1 and a
+ *   segment a maximal run of consecutive windows with the same expected >= 0, in this order: n_cue (windows with expected >=
+ *   0), n_rest (expected == -1), hit (cue windows with command == expected), wrong (cue windows with command >= 0 and command
+ *   != expected), false_active (rest windows with command != -1), switches (windows, the unscored ones included, with command[j]
+ *   != command[j-1]), segments, reached (segments with a hit), latency_sum (over reached segments: index of the first hit -
+ *   index of the segment's first window), wrong_segments (segments with a wrong window).  score_commands of
+ *   contrastiveprosthetics_amd/online.py is the definition.
+ * - A config's results do not depend on the other configs in the call.
+ * - The host checks n_classes in 1..64 and <= ldl, n_configs in 1..CP_ONLINE_GATE_SWEEP_MAX_CONFIGS, n_rows in 1..2^31-1, the
+ *   size of scratch and the pointers (commands may be NULL), and returns CP_ERR_ARG with a cp_last_error that names the entry
+ *   before anything is enqueued.
+ * - The values inside `configs` lie on the device, where the host cannot check them: the caller does (min_margin finite and
+ *   >= 0, weight 0 or 1, thresholds not NaN).  A config with vote outside 1..256, min_votes < 1, dwell < 1 or release < 0 gets
+ *   all scores -1 and its row of `commands` is not written; the kernel never indexes with such a value. */
+#define CP_ONLINE_GATE_SCORES 10
+#define CP_ONLINE_GATE_SWEEP_MAX_CONFIGS 65536
+/* bytes of the sweep's scratch (256-byte aligned): 12 per row */
+size_t cp_online_gate_sweep_scratch_bytes(int64_t n_rows);
+int cp_online_gate_sweep(const float* logits, int32_t ldl, int64_t n_rows, int32_t n_classes,
+                         const int32_t* expected_slot,          /* (n_rows) device: slot 0..K-1, -1 rest, -2 ignore */
+                         const cp_online_gate_config* configs,  /* (n_configs) device */
+                         const float* min_cosine,               /* (n_configs, 64) device */
+                         int32_t n_configs, void* scratch, size_t scratch_bytes,
+                         int64_t* scores,                       /* (n_configs, CP_ONLINE_GATE_SCORES) device */
+                         int32_t* commands,                     /* optional (n_configs, n_rows): slot or -1 */
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,9 @@ enrolled rows on a held-out recording of a person the model has not seen.
 With --gate the command gate (CommandGate.push, csrc/online_gate.cuh) is timed against the ungated decoder.push(
 return_logits=True) in the same run: 1 and 25 windows on OnlineDecoder and 256 streams x 1 window on MultiStreamDecoder, plus
 the gate's launch alone (CommandGate.apply on the logits of one push).
+With --gate-sweep the gate sweep (sweep_gate, csrc/online_gate.cuh og_sweep_kernel) is timed against the way without it: G
+CommandGate.apply calls one after another over the same logits plus the copy of each one's commands to the host; synthetic
+cued logits of 8 classes, 6,000 and 60,000 windows, G = 64, 256 and 1,024 configs, every timed case under a time limit of its own.
 Each push is timed from the host with a synchronisation behind it (the latency a control loop sees); kernels per push are
 counted with torch.profiler over a few pushes.  One JSON line per case, and a table with --out.
 
@@ -29,6 +32,7 @@ counted with torch.profiler over a few pushes.  One JSON line per case, and a ta
     python tools/online_bench.py --streams --adapt --iters 100 --out profiles/online_multi_adapt_latency.txt
     python tools/online_bench.py --enroll --iters 10 --out profiles/online_enroll.txt
     python tools/online_bench.py --gate --iters 200 --out profiles/online_gate_latency.txt
+    python tools/online_bench.py --gate-sweep --iters 20 --out profiles/online_gate_sweep.txt
 """
 import argparse
 import json
@@ -82,9 +86,13 @@ def main():
     ap.add_argument("--counts", default="1,8,64,256", help="--streams: stream counts")
     ap.add_argument("--enroll", action="store_true", help="class enrolment: time, one-pass windows, accuracy on a synthetic person")
     ap.add_argument("--gate", action="store_true", help="the command gate against the ungated push with logits")
+    ap.add_argument("--gate-sweep", action="store_true", help="sweep_gate against G CommandGate.apply calls in turn")
+    ap.add_argument("--case-seconds", type=float, default=150.0, help="--gate-sweep: time limit of each timed case")
     a = ap.parse_args()
     if a.enroll:
         return enroll_main(a)
+    if a.gate_sweep:
+        return gate_sweep_main(a)
     torch.manual_seed(0)
     e = Engine(adabn=False, dtype="f32", device="cuda:0")
     e.init_parameters(1)
@@ -413,6 +421,104 @@ def gate_main(a, e, stream, mean, std, classes):
             for r in rows:
                 f.write(f"{r['kind']:<11} {r['dtype']:<5} {r['streams']:>7} {r['windows']:>7} {r['median_us']:>10.1f} {r['p90_us']:>9.1f} "
                         f"{r['kernels_per_push']:>8.1f} {r['gated_minus_ungated_us']:>9.1f}\n")
+
+
+class _Ids:
+    """the part of a single-stream decoder that CommandGate.apply reads"""
+    phase, n_seen = 0, 0
+
+    def __init__(self, ids, vote, device):
+        self.class_ids, self.vote, self.device = torch.as_tensor(ids, dtype=torch.int32), vote, device
+
+    def push(self, *a, **k):
+        raise RuntimeError("apply() does not push the decoder")
+
+
+def _cued_logits(m, k, seed=0):
+    """synthetic cosines of a cued session on the device: 3 s of a class (raised by 0.5 over its first 12 windows), two
+    unscored windows, 2 s of rest, over noise as wide as the raise -> logits (m, k) f32, expected (m,) class ids / REST / IGNORE"""
+    from contrastiveprosthetics_amd.online import IGNORE, REST
+    g = torch.Generator().manual_seed(seed)
+    lg = torch.rand(m, k, generator=g) * 0.6 - 0.2
+    exp = np.full(m, IGNORE, dtype=np.int64)
+    j, c = 0, 0
+    while j < m:
+        n = min(300, m - j)
+        lg[j:j + n, c % k] += 0.5 * torch.clamp((torch.arange(n) + 1) / 12.0, max=1.0)
+        exp[j:j + n] = c % k
+        exp[j + 302:j + 500] = REST
+        j += 502
+        c += 1
+    return lg.cuda(), exp
+
+
+def gate_sweep_main(a):
+    """one sweep_gate call against G CommandGate.apply calls in turn plus the copy of their commands to the host, in one
+    process, case by case.  Every timed case has its own time limit (--case-seconds): repetitions stop when it is used up, and
+    a sequential pass that has used it up stops between two configs and is reported as partial, per config."""
+    from contrastiveprosthetics_amd.online import gate_grid, sweep_gate
+    K = 8
+    ids = list(range(K))
+    grids = {64: dict(min_cosine=[0.2, 0.3, 0.4, 0.5], dwell=[1, 3, 5, 8], release=[2, 5, 10, 20])}
+    grids[256] = dict(grids[64], weight=["count", "margin"], min_votes=[1, 3])
+    grids[1024] = dict(grids[256], vote=[10, 25, 50, 100])
+    device = torch.device("cuda:0")
+    rows = []
+    for m in (6000, 60000):
+        logits, exp = _cued_logits(m, K)
+        for G, lists in grids.items():
+            configs = gate_grid(**lists)
+            assert len(configs) == G
+
+            def swept():
+                return sweep_gate(logits, exp, ids, configs)
+
+            def sequential(limit):
+                """-> configs done within the limit"""
+                t0 = time.perf_counter()
+                for g, c in enumerate(configs):
+                    if time.perf_counter() - t0 > limit:
+                        return g
+                    gate = CommandGate(_Ids(ids, 25, device), vote=c.get("vote", 25))
+                    gate.use(c)
+                    gate.apply(logits)[0].cpu()
+                return G
+
+            swept()
+            torch.cuda.synchronize()
+            ts, t_case = [], time.perf_counter()
+            while len(ts) < a.iters and (not ts or time.perf_counter() - t_case < a.case_seconds):
+                t0 = time.perf_counter()
+                swept()                                          # (returns host arrays: it has synchronised)
+                ts.append(time.perf_counter() - t0)
+            sweep_ms = float(np.median(ts)) * 1e3
+            sequential(min(a.case_seconds, 2.0))                 # warm-up: a part of a pass
+            torch.cuda.synchronize()
+            qs, done, t_case = [], G, time.perf_counter()
+            while len(qs) < min(a.iters, 5) and (not qs or time.perf_counter() - t_case + 1.5 * qs[-1] < a.case_seconds):
+                t0 = time.perf_counter()
+                done = sequential(a.case_seconds - (t0 - t_case))
+                torch.cuda.synchronize()
+                if done < G:
+                    qs = [(time.perf_counter() - t0) / max(done, 1) * G]     # partial: scaled from the configs it got through
+                    break
+                qs.append(time.perf_counter() - t0)
+            seq_ms = float(np.median(qs)) * 1e3
+            r = dict(windows=m, configs=G, sweep_ms=round(sweep_ms, 3), sweep_reps=len(ts), sequential_ms=round(seq_ms, 1),
+                     sequential_reps=len(qs), sequential_configs_done=done, ratio=round(seq_ms / sweep_ms, 1))
+            print(json.dumps(r), flush=True)
+            rows.append(r)
+    if a.out:
+        dev = torch.cuda.get_device_name(0)
+        with open(a.out, "w") as f:
+            f.write(f"# tools/online_bench.py --gate-sweep --iters {a.iters} --case-seconds {a.case_seconds:g} on {dev}\n")
+            f.write("# synthetic cued logits, 8 classes; sweep = one sweep_gate call (scores on the host), sequential = G\n"
+                    "# CommandGate.apply calls in turn over the same logits, each one's commands copied to the host; wall time,\n"
+                    "# median over reps; done < configs: the sequential pass hit its time limit and is scaled from the configs done\n")
+            f.write(f"{'windows':>7} {'configs':>7} {'sweep_ms':>9} {'reps':>5} {'sequential_ms':>14} {'reps':>5} {'done':>6} {'ratio':>8}\n")
+            for r in rows:
+                f.write(f"{r['windows']:>7} {r['configs']:>7} {r['sweep_ms']:>9.3f} {r['sweep_reps']:>5} {r['sequential_ms']:>14.1f} "
+                        f"{r['sequential_reps']:>5} {r['sequential_configs_done']:>6} {r['ratio']:>8.1f}\n")
 
 
 def streams_main(a, e, stream, mean, std, classes):
