@@ -2391,1157 +2391,4 @@ extern "C" int cp_debug_bn_stats(const cp_config* cfg, void* ws, size_t ws_bytes
     return 0;
 }
 
-// ---------------------------------------------------------------------------------------
-// online grasp decoding (csrc/online.cuh): per-stream state, folded weights and activations in the caller's workspace
-// ---------------------------------------------------------------------------------------
-static_assert(OL_MAXM == CP_ONLINE_MAX_WINDOWS && OL_MAXVOTE == CP_ONLINE_MAX_VOTE && OL_MAXK == CP_ONLINE_MAX_CLASSES, "online limits");
-struct OlWS {
-    size_t state, c1w, c1b, c2w, c2b, fcw[CP_N_FC], fcb[CP_N_FC], pw, pb, X, H0, H1, total;
-};
-// max_windows: rows of one push.  The multi-stream carve (meta != NULL) holds n_streams states and their OlmMeta.
-static OlWS ol_carve(int64_t max_windows, int dtype, int n_streams = 1, size_t* meta = nullptr) {
-    const size_t es = dtype == CP_BF16 ? 2 : 4;
-    const size_t rows = (size_t)((max_windows + 15) / 16 * 16);
-    OlWS w{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t r = o; o = align256(o + bytes); return r; };
-    w.state = take((size_t)n_streams * sizeof(OlState));
-    if (meta) *meta = take((size_t)n_streams * sizeof(OlmMeta));
-    w.c1w = take(64 * 3 * 4);
-    w.c1b = take(64 * 4);
-    w.c2w = take(64 * OL_CONV_K * es);
-    w.c2b = take(OL_C * 64 * 4);
-    for (int i = 0; i < CP_N_FC; ++i) {
-        w.fcw[i] = take((size_t)512 * fcK(i) * es);
-        w.fcb[i] = take(512 * 4);
-    }
-    w.pw = take(CP_D_E * 512 * es);
-    w.pb = take(CP_D_E * 4);
-    w.X = take(rows * OL_C * 4);
-    w.H0 = take(rows * 768 * es);
-    w.H1 = take(rows * 512 * es);
-    w.total = o;
-    return w;
-}
-
-static int ol_check_config(const cp_online_config* c, void* ws) {
-    if (!c || !ws) return fail(CP_ERR_ARG, "cp_online: config and workspace are required");
-    if (c->dtype != CP_F32 && c->dtype != CP_BF16) return fail(CP_ERR_ARG, "cp_online: dtype must be CP_F32 or CP_BF16 (no 8-bit path)");
-    if (c->max_windows < 1 || c->max_windows > CP_ONLINE_MAX_WINDOWS) return fail(CP_ERR_ARG, "cp_online: max_windows outside 1..256");
-    if (c->vote < 1 || c->vote > CP_ONLINE_MAX_VOTE) return fail(CP_ERR_ARG, "cp_online: vote outside 1..256");
-    if (c->phase < 0 || c->phase >= CP_ONLINE_STRIDE) return fail(CP_ERR_ARG, "cp_online: phase outside 0..19");
-    if (c->n_coef < 2 || c->n_coef > OL_MAXCOEF || c->a[0] == 0.0) return fail(CP_ERR_ARG, "cp_online: IIR coefficients");
-    if ((uintptr_t)ws % 256) return fail(CP_ERR_ARG, "cp_online: workspace not 256-byte aligned");
-    return 0;
-}
-
-static int ol_check(const cp_online_config* c, void* ws, size_t ws_bytes, OlWS* out) {
-    if (int e = ol_check_config(c, ws)) return e;
-    *out = ol_carve(c->max_windows, c->dtype);
-    if (ws_bytes < out->total) return fail(CP_ERR_WORKSPACE, "cp_online: workspace too small");
-    return 0;
-}
-
-extern "C" size_t cp_online_workspace_bytes(int32_t max_windows_per_push, int32_t dtype) {
-    if (max_windows_per_push < 1) max_windows_per_push = 1;
-    return ol_carve(max_windows_per_push, dtype).total;
-}
-
-template <typename T>
-static int online_prepare_t(const cp_params* p, const cp_bn_buffers* bn, float eps, unsigned char* base, const OlWS& w, hipStream_t st) {
-    OlFoldArgs f{};
-    f.eps = eps;
-    auto set_bn = [&](int l) { f.g = p->bn_g[l]; f.beta = p->bn_b[l]; f.mean = bn->running_mean[l]; f.var = bn->running_var[l]; };
-    set_bn(0);                                            // BN1 -> conv2 (and conv1 copied as it is)
-    f.W = p->conv2_w; f.b = p->conv2_b; f.Wd = base + w.c2w; f.bd = (float*)(base + w.c2b); f.K = OL_CONV_K; f.mode = 2;
-    f.c1w_src = p->conv1_w; f.c1b_src = p->conv1_b; f.c1w = (float*)(base + w.c1w); f.c1b = (float*)(base + w.c1b);
-    hipLaunchKernelGGL((ol_fold_kernel<T>), dim3(64), dim3(256), 0, st, f);
-    CKL("ol_fold_kernel");
-    for (int i = 0; i < CP_N_FC; ++i) {                   // BN(i+1) -> fc(i+1); fc1's columns to the position-major layout
-        set_bn(i + 1);
-        f.W = p->fc_w[i]; f.b = p->fc_b[i]; f.Wd = base + w.fcw[i]; f.bd = (float*)(base + w.fcb[i]); f.K = fcK(i); f.mode = i == 0 ? 1 : 0;
-        hipLaunchKernelGGL((ol_fold_kernel<T>), dim3(512), dim3(256), 0, st, f);
-        CKL("ol_fold_kernel");
-    }
-    set_bn(CP_N_BN - 1);                                  // BN9 -> projection, which gains a bias
-    f.W = p->last_w; f.b = nullptr; f.Wd = base + w.pw; f.bd = (float*)(base + w.pb); f.K = 512; f.mode = 0;
-    hipLaunchKernelGGL((ol_fold_kernel<T>), dim3(CP_D_E), dim3(256), 0, st, f);
-    CKL("ol_fold_kernel");
-    return 0;
-}
-
-extern "C" int cp_online_prepare(const cp_online_config* cfg, const cp_params* p, const cp_bn_buffers* bn, float bn_eps, void* ws,
-                                 size_t ws_bytes, void* stream) {
-    OlWS w;
-    if (int e = ol_check(cfg, ws, ws_bytes, &w)) return e;
-    if (!p || !p->conv1_w || !p->conv1_b || !p->conv2_w || !p->conv2_b || !p->last_w) return fail(CP_ERR_ARG, "cp_online_prepare: parameters");
-    for (int i = 0; i < CP_N_FC; ++i)
-        if (!p->fc_w[i] || !p->fc_b[i]) return fail(CP_ERR_ARG, "cp_online_prepare: parameters");
-    if (!bn) return fail(CP_ERR_ARG, "cp_online_prepare: stock BatchNorm with running statistics required (AdaBN has none)");
-    for (int l = 0; l < CP_N_BN; ++l)
-        if (!p->bn_g[l] || !p->bn_b[l] || !bn->running_mean[l] || !bn->running_var[l])
-            return fail(CP_ERR_ARG, "cp_online_prepare: stock BatchNorm with running statistics required (AdaBN has none)");
-    unsigned char* base = (unsigned char*)ws;
-    if (cfg->dtype == CP_BF16) return online_prepare_t<bf16_t>(p, bn, bn_eps, base, w, (hipStream_t)stream);
-    return online_prepare_t<float>(p, bn, bn_eps, base, w, (hipStream_t)stream);
-}
-
-extern "C" int cp_online_set_classes(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* table, const int32_t* ids,
-                                     int32_t n_classes, void* stream) {
-    OlWS w;
-    if (int e = ol_check(cfg, ws, ws_bytes, &w)) return e;
-    if (!table || !ids || n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return fail(CP_ERR_ARG, "cp_online_set_classes: 1..64 classes");
-    hipLaunchKernelGGL(ol_set_classes_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (OlState*)((unsigned char*)ws + w.state), table,
-                       ids, (int)n_classes);
-    CKL("ol_set_classes_kernel");
-    return 0;
-}
-
-extern "C" int cp_online_reset(const cp_online_config* cfg, void* ws, size_t ws_bytes, void* stream) {
-    OlWS w;
-    if (int e = ol_check(cfg, ws, ws_bytes, &w)) return e;
-    CK(hipMemsetAsync((unsigned char*)ws + w.state, 0, offsetof(OlState, K), (hipStream_t)stream));
-    return 0;
-}
-
-static int ol_launch_frontend(const cp_online_config* c, OlState* state, float* X, const float* raw, int64_t n, const float* mean_std,
-                              float* windows, hipStream_t st) {
-    OlFrontArgs fa{};
-    fa.raw = raw; fa.n = n; fa.st = state; fa.X = X; fa.windows = windows; fa.mean_std = mean_std;
-    fa.n_coef = c->n_coef; fa.phase = c->phase; fa.gain = 1024.f;            // code/load.py:105, 2**10
-    for (int i = 0; i < c->n_coef; ++i) { fa.b[i] = c->b[i] / c->a[0]; fa.a[i] = c->a[i] / c->a[0]; }
-    if (c->n_coef == 9) hipLaunchKernelGGL((ol_frontend_kernel<9>), dim3(1), dim3(256), 0, st, fa);
-    else hipLaunchKernelGGL((ol_frontend_kernel<0>), dim3(1), dim3(256), 0, st, fa);
-    CKL("ol_frontend_kernel");
-    return 0;
-}
-
-template <typename T>
-static int online_push_t(const cp_online_config* c, unsigned char* base, const OlWS& w, const float* raw, int64_t n,
-                         const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, hipStream_t st) {
-    OlState* state = (OlState*)(base + w.state);
-    if (int e = ol_launch_frontend(c, state, (float*)(base + w.X), raw, n, mean_std, windows, st)) return e;
-    OlLayerArgs la{};
-    la.st = state;
-    la.x = (const float*)(base + w.X); la.c1w = (const float*)(base + w.c1w); la.c1b = (const float*)(base + w.c1b);
-    la.w = base + w.c2w; la.bias = (const float*)(base + w.c2b); la.out = base + w.H0; la.K = OL_CONV_K; la.F = 64; la.ldo = 768;
-    la.out_pos = 64;
-    hipLaunchKernelGGL((ol_layer_kernel<T, true>), dim3(4, OL_C), dim3(OL_THREADS), 0, st, la);
-    CKL("ol_layer_kernel<conv>");
-    for (int i = 0; i < CP_N_FC; ++i) {                   // H0 -> H1 -> H0 ...: fc7 leaves its output in H1
-        la.act = base + (i % 2 == 0 ? w.H0 : w.H1);
-        la.out = base + (i % 2 == 0 ? w.H1 : w.H0);
-        la.w = base + w.fcw[i]; la.bias = (const float*)(base + w.fcb[i]); la.K = fcK(i); la.F = 512; la.ldo = 512; la.out_pos = 0;
-        hipLaunchKernelGGL((ol_layer_kernel<T, false>), dim3(512 / 16), dim3(OL_THREADS), 0, st, la);
-        CKL("ol_layer_kernel<fc>");
-    }
-    OlTailArgs ta{};
-    ta.proj = la;
-    ta.proj.act = base + w.H1; ta.proj.out = nullptr; ta.proj.w = base + w.pw; ta.proj.bias = (const float*)(base + w.pb); ta.proj.K = 512;
-    ta.proj.F = CP_D_E;
-    ta.st = state; ta.vote = c->vote; ta.pred = pred; ta.voted = voted; ta.logits = logits;
-    hipLaunchKernelGGL((ol_tail_kernel<T>), dim3(1), dim3(OL_THREADS), 0, st, ta);
-    CKL("ol_tail_kernel");
-    return 0;
-}
-
-extern "C" int cp_online_push(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* raw, int64_t n_samples,
-                              const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, void* stream) {
-    OlWS w;
-    if (int e = ol_check(cfg, ws, ws_bytes, &w)) return e;
-    if (n_samples < 0 || n_samples > (int64_t)CP_ONLINE_STRIDE * cfg->max_windows)
-        return fail(CP_ERR_ARG, "cp_online_push: a push takes at most 20 * max_windows samples");
-    if (n_samples == 0) return 0;
-    if (!raw || !mean_std || !pred || !voted) return fail(CP_ERR_ARG, "cp_online_push: raw, mean_std, pred and voted are required");
-    if ((uintptr_t)raw % 4 || (uintptr_t)mean_std % 4) return fail(CP_ERR_ARG, "cp_online_push: misaligned input");
-    unsigned char* base = (unsigned char*)ws;
-    if (cfg->dtype == CP_BF16)
-        return online_push_t<bf16_t>(cfg, base, w, raw, n_samples, mean_std, pred, voted, logits, windows, (hipStream_t)stream);
-    return online_push_t<float>(cfg, base, w, raw, n_samples, mean_std, pred, voted, logits, windows, (hipStream_t)stream);
-}
-
-// ---------------------------------------------------------------------------------------
-// adaptive online decoding (csrc/online_adapt.cuh): BatchNorm unfolded, float64 statistics per stream in the workspace
-// ---------------------------------------------------------------------------------------
-struct OlaWS {
-    size_t state, head, c1w, c1b, c2w, c2b, fcw[CP_N_FC], fcb[CP_N_FC], pw, pb, gb, stats, X, C1, R2, H0, H1, total;
-};
-static OlaWS ola_carve(int64_t max_windows, int dtype) {
-    const size_t es = dtype == CP_BF16 ? 2 : 4;
-    const size_t rows = (size_t)((max_windows + 15) / 16 * 16);
-    OlaWS w{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t r = o; o = align256(o + bytes); return r; };
-    w.state = take(sizeof(OlState));                      // first, as in the folded carve: cp_online_set_classes / reset apply
-    w.head = take(sizeof(OlaHead));
-    w.c1w = take(64 * 3 * 4);
-    w.c1b = take(64 * 4);
-    w.c2w = take(64 * OL_CONV_K * es);
-    w.c2b = take(64 * 4);
-    for (int i = 0; i < CP_N_FC; ++i) {
-        w.fcw[i] = take((size_t)512 * fcK(i) * es);
-        w.fcb[i] = take(512 * 4);
-    }
-    w.pw = take(CP_D_E * 512 * es);
-    w.pb = take(CP_D_E * 4);                              // zeros: the tail adds a bias the unfolded projection does not have
-    w.gb = take((size_t)CP_N_BN * 2 * OLA_F * 4);
-    w.stats = take((size_t)CP_N_BN * 2 * OLA_F * 8);
-    w.X = take(rows * OL_C * 4);
-    w.C1 = take(rows * OL_C * OL_CONV_K * es);            // conv2's operand: rows (window, position)
-    w.R2 = take(rows * OL_C * 64 * 4);                    // conv2's pre-BN output, f32
-    w.H0 = take(rows * 768 * es);
-    w.H1 = take(rows * 512 * es);
-    w.total = o;
-    return w;
-}
-
-static int ola_check(const cp_online_config* c, void* ws, size_t ws_bytes, OlaWS* out) {
-    OlWS folded;
-    if (int e = ol_check(c, ws, ws_bytes, &folded)) return e;      // (the adaptive carve is the larger)
-    *out = ola_carve(c->max_windows, c->dtype);
-    if (ws_bytes < out->total) return fail(CP_ERR_WORKSPACE, "cp_online_adapt: workspace too small");
-    return 0;
-}
-
-extern "C" size_t cp_online_adapt_workspace_bytes(int32_t max_windows_per_push, int32_t dtype) {
-    if (max_windows_per_push < 1) max_windows_per_push = 1;
-    return ola_carve(max_windows_per_push, dtype).total;
-}
-
-static OlaBn ola_bn(unsigned char* base, const OlaWS& w, int l, int mode, double* acc, int first, int last) {
-    OlaBn b{};
-    b.stats = (double*)(base + w.stats) + (size_t)l * 2 * OLA_F;
-    b.acc = acc ? acc + (size_t)l * 3 * OLA_F : nullptr;
-    b.gamma = (const float*)(base + w.gb) + (size_t)l * 2 * OLA_F;
-    b.beta = b.gamma + OLA_F;
-    b.head = (const OlaHead*)(base + w.head);
-    b.mode = mode; b.first = first; b.last = last;
-    return b;
-}
-
-template <typename T>
-static int online_adapt_prepare_t(const cp_params* p, const cp_bn_buffers* bn, float eps, double alpha, unsigned char* base,
-                                  const OlaWS& w, hipStream_t st) {
-    OlaBnInitArgs ia{};
-    for (int l = 0; l < CP_N_BN; ++l) {
-        ia.g[l] = p->bn_g[l]; ia.beta[l] = p->bn_b[l];
-        ia.mean[l] = bn ? bn->running_mean[l] : nullptr; ia.var[l] = bn ? bn->running_var[l] : nullptr;
-    }
-    ia.c1w = p->conv1_w; ia.c1b = p->conv1_b; ia.gb = (float*)(base + w.gb); ia.stats = (double*)(base + w.stats);
-    ia.c1w_d = (float*)(base + w.c1w); ia.c1b_d = (float*)(base + w.c1b); ia.head = (OlaHead*)(base + w.head);
-    ia.alpha = alpha; ia.eps = eps;
-    hipLaunchKernelGGL(ola_bn_init_kernel, dim3(CP_N_BN), dim3(512), 0, st, ia);
-    CKL("ola_bn_init_kernel");
-    OlaCopyArgs f{};
-    f.W = p->conv2_w; f.b = p->conv2_b; f.Wd = base + w.c2w; f.bd = (float*)(base + w.c2b); f.K = OL_CONV_K; f.mode = 2;
-    hipLaunchKernelGGL((ola_copy_kernel<T>), dim3(64), dim3(256), 0, st, f);
-    CKL("ola_copy_kernel");
-    for (int i = 0; i < CP_N_FC; ++i) {
-        f.W = p->fc_w[i]; f.b = p->fc_b[i]; f.Wd = base + w.fcw[i]; f.bd = (float*)(base + w.fcb[i]); f.K = fcK(i); f.mode = i == 0 ? 1 : 0;
-        hipLaunchKernelGGL((ola_copy_kernel<T>), dim3(512), dim3(256), 0, st, f);
-        CKL("ola_copy_kernel");
-    }
-    f.W = p->last_w; f.b = nullptr; f.Wd = base + w.pw; f.bd = (float*)(base + w.pb); f.K = 512; f.mode = 0;
-    hipLaunchKernelGGL((ola_copy_kernel<T>), dim3(CP_D_E), dim3(256), 0, st, f);
-    CKL("ola_copy_kernel");
-    return 0;
-}
-
-extern "C" int cp_online_adapt_prepare(const cp_online_config* cfg, const cp_params* p, const cp_bn_buffers* bn, float bn_eps,
-                                       double alpha, void* ws, size_t ws_bytes, void* stream) {
-    if (!(alpha >= 0.0 && alpha < 1.0)) return fail(CP_ERR_ARG, "cp_online_adapt_prepare: alpha outside [0, 1)");
-    if (!(bn_eps > 0.f)) return fail(CP_ERR_ARG, "cp_online_adapt_prepare: bn_eps must be positive");
-    OlaWS w;
-    if (int e = ola_check(cfg, ws, ws_bytes, &w)) return e;
-    if (!p || !p->conv1_w || !p->conv1_b || !p->conv2_w || !p->conv2_b || !p->last_w) return fail(CP_ERR_ARG, "cp_online_adapt_prepare: parameters");
-    for (int i = 0; i < CP_N_FC; ++i)
-        if (!p->fc_w[i] || !p->fc_b[i]) return fail(CP_ERR_ARG, "cp_online_adapt_prepare: parameters");
-    for (int l = 0; l < CP_N_BN; ++l) {
-        if (!p->bn_g[l] || !p->bn_b[l]) return fail(CP_ERR_ARG, "cp_online_adapt_prepare: parameters");
-        if (bn && (!bn->running_mean[l] || !bn->running_var[l])) return fail(CP_ERR_ARG, "cp_online_adapt_prepare: running statistics");
-    }
-    unsigned char* base = (unsigned char*)ws;
-    if (cfg->dtype == CP_BF16) return online_adapt_prepare_t<bf16_t>(p, bn, bn_eps, alpha, base, w, (hipStream_t)stream);
-    return online_adapt_prepare_t<float>(p, bn, bn_eps, alpha, base, w, (hipStream_t)stream);
-}
-
-// conv2 GEMM: row-tile groups per feature tile for `rows` rows
-static int ola_conv2_groups(int64_t rows) {
-    const int64_t tiles = (rows + 15) / 16;
-    return (int)(tiles < 16 ? tiles : 16);
-}
-
-// BN1 -> conv2 -> BN2 for M windows (m_fixed < 0: the push's count; max_rows bounds the row-tile groups)
-template <typename T>
-static int ola_conv_chain(unsigned char* base, const OlaWS& w, const OlState* state, const float* x, int m_fixed, int64_t max_rows,
-                          void* c1, float* r2, void* out, const OlaBn& bn1, const OlaBn& bn2, hipStream_t st) {
-    OlaConvBnArgs cb{};
-    cb.x = x; cb.c1w = (const float*)(base + w.c1w); cb.c1b = (const float*)(base + w.c1b); cb.out = c1; cb.st = state;
-    cb.m_fixed = m_fixed; cb.conv1 = 1; cb.bn = bn1;
-    hipLaunchKernelGGL((ola_conv_bn_kernel<T>), dim3(1), dim3(64), 0, st, cb);
-    CKL("ola_conv_bn_kernel<BN1>");
-    OlaGemmArgs g{};
-    g.l.act = c1; g.l.w = base + w.c2w; g.l.bias = (const float*)(base + w.c2b); g.l.out = r2; g.l.st = state; g.l.K = OL_CONV_K;
-    g.l.F = 64; g.l.ldo = 64; g.m_fixed = m_fixed; g.rows_per_window = OL_C;
-    hipLaunchKernelGGL((ola_gemm_kernel<T>), dim3(64 / 16, ola_conv2_groups(max_rows * OL_C)), dim3(OL_THREADS), 0, st, g);
-    CKL("ola_gemm_kernel");
-    cb.pre = r2; cb.out = out; cb.conv1 = 0; cb.bn = bn2;
-    hipLaunchKernelGGL((ola_conv_bn_kernel<T>), dim3(1), dim3(64), 0, st, cb);
-    CKL("ola_conv_bn_kernel<BN2>");
-    return 0;
-}
-
-// fc layer i: act [M][K] -> out [M][512] (normalised; nothing under OLA_ACC)
-template <typename T>
-static int ola_fc(unsigned char* base, const OlaWS& w, const OlState* state, int i, const void* act, void* out, int m_fixed,
-                  const OlaBn& bn, hipStream_t st) {
-    OlaGemmArgs g{};
-    g.l.act = act; g.l.out = out; g.l.w = base + w.fcw[i]; g.l.bias = (const float*)(base + w.fcb[i]); g.l.st = state;
-    g.l.K = fcK(i); g.l.F = 512; g.l.ldo = 512; g.m_fixed = m_fixed; g.rows_per_window = 1; g.bn = bn;
-    hipLaunchKernelGGL((ola_fc_kernel<T>), dim3(512 / 16), dim3(OL_THREADS), 0, st, g);
-    CKL("ola_fc_kernel");
-    return 0;
-}
-
-template <typename T>
-static int online_adapt_push_t(const cp_online_config* c, unsigned char* base, const OlaWS& w, const float* raw, int64_t n,
-                               const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, hipStream_t st) {
-    OlState* state = (OlState*)(base + w.state);
-    if (int e = ol_launch_frontend(c, state, (float*)(base + w.X), raw, n, mean_std, windows, st)) return e;
-    if (int e = ola_conv_chain<T>(base, w, state, (const float*)(base + w.X), -1, c->max_windows, base + w.C1, (float*)(base + w.R2),
-                                  base + w.H0, ola_bn(base, w, 0, OLA_TRACK, nullptr, 0, 0), ola_bn(base, w, 1, OLA_TRACK, nullptr, 0, 0), st))
-        return e;
-    for (int i = 0; i < CP_N_FC; ++i)                     // H0 -> H1 -> H0 ...: fc7 leaves its output in H1
-        if (int e = ola_fc<T>(base, w, state, i, base + (i % 2 == 0 ? w.H0 : w.H1), base + (i % 2 == 0 ? w.H1 : w.H0), -1,
-                              ola_bn(base, w, i + 2, OLA_TRACK, nullptr, 0, 0), st))
-            return e;
-    OlTailArgs ta{};
-    ta.proj.st = state;
-    ta.proj.act = base + w.H1; ta.proj.w = base + w.pw; ta.proj.bias = (const float*)(base + w.pb); ta.proj.K = 512; ta.proj.F = CP_D_E;
-    ta.st = state; ta.vote = c->vote; ta.pred = pred; ta.voted = voted; ta.logits = logits;
-    hipLaunchKernelGGL((ol_tail_kernel<T>), dim3(1), dim3(OL_THREADS), 0, st, ta);
-    CKL("ol_tail_kernel");
-    return 0;
-}
-
-extern "C" int cp_online_adapt_push(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* raw, int64_t n_samples,
-                                    const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, void* stream) {
-    OlaWS w;
-    if (int e = ola_check(cfg, ws, ws_bytes, &w)) return e;
-    if (n_samples < 0 || n_samples > (int64_t)CP_ONLINE_STRIDE * cfg->max_windows)
-        return fail(CP_ERR_ARG, "cp_online_adapt_push: a push takes at most 20 * max_windows samples");
-    if (n_samples == 0) return 0;
-    if (!raw || !mean_std || !pred || !voted) return fail(CP_ERR_ARG, "cp_online_adapt_push: raw, mean_std, pred and voted are required");
-    if ((uintptr_t)raw % 4 || (uintptr_t)mean_std % 4) return fail(CP_ERR_ARG, "cp_online_adapt_push: misaligned input");
-    unsigned char* base = (unsigned char*)ws;
-    if (cfg->dtype == CP_BF16)
-        return online_adapt_push_t<bf16_t>(cfg, base, w, raw, n_samples, mean_std, pred, voted, logits, windows, (hipStream_t)stream);
-    return online_adapt_push_t<float>(cfg, base, w, raw, n_samples, mean_std, pred, voted, logits, windows, (hipStream_t)stream);
-}
-
-// calibration scratch: the normalised activations of all windows (two buffers), one chunk of conv2 operand and output, and
-// the float64 accumulators
-struct OlaCalib {
-    size_t A0, A1, C1, R2, acc, total;
-};
-static OlaCalib ola_calib_carve(int64_t n_windows, int dtype) {
-    const size_t es = dtype == CP_BF16 ? 2 : 4;
-    OlaCalib c{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t r = o; o = align256(o + bytes); return r; };
-    c.A0 = take((size_t)n_windows * 768 * es);
-    c.A1 = take((size_t)n_windows * 512 * es);
-    c.C1 = take((size_t)OL_MAXM * OL_C * OL_CONV_K * es);
-    c.R2 = take((size_t)OL_MAXM * OL_C * 64 * 4);
-    c.acc = take((size_t)CP_N_BN * 3 * OLA_F * 8);
-    c.total = o;
-    return c;
-}
-
-extern "C" size_t cp_online_adapt_calibrate_scratch_bytes(int64_t n_windows, int32_t dtype) {
-    if (n_windows < 1) n_windows = 1;
-    return ola_calib_carve(n_windows, dtype).total;
-}
-
-template <typename T>
-static int online_adapt_calibrate_t(unsigned char* base, const OlaWS& w, const float* x, int64_t N, unsigned char* sc,
-                                    const OlaCalib& k, hipStream_t st) {
-    const OlState* state = (const OlState*)(base + w.state);
-    const size_t es = sizeof(T);
-    double* acc = (double*)(sc + k.acc);
-    const int64_t nch = (N + OL_MAXM - 1) / OL_MAXM;
-    auto rows_of = [&](int64_t ci) { return (int)(ci + 1 < nch ? OL_MAXM : N - ci * OL_MAXM); };
-    // BN1: conv1 of all windows, one launch
-    OlaConvBnArgs cb{};
-    cb.x = x; cb.c1w = (const float*)(base + w.c1w); cb.c1b = (const float*)(base + w.c1b); cb.st = state;
-    cb.m_fixed = (int)N; cb.conv1 = 1; cb.bn = ola_bn(base, w, 0, OLA_ACC, acc, 1, 1);
-    hipLaunchKernelGGL((ola_conv_bn_kernel<T>), dim3(1), dim3(64), 0, st, cb);
-    CKL("ola_conv_bn_kernel<BN1>");
-    // BN2: per chunk BN1 (frozen) -> conv2 -> accumulate; then again with BN2 frozen into A0
-    const OlaBn bn1 = ola_bn(base, w, 0, OLA_FROZEN, nullptr, 0, 0);
-    for (int pass = 0; pass < 2; ++pass)
-        for (int64_t ci = 0; ci < nch; ++ci) {
-            const OlaBn bn2 = pass == 0 ? ola_bn(base, w, 1, OLA_ACC, acc, ci == 0, ci + 1 == nch) : ola_bn(base, w, 1, OLA_FROZEN, nullptr, 0, 0);
-            if (int e = ola_conv_chain<T>(base, w, state, x + ci * OL_MAXM * OL_C, rows_of(ci), OL_MAXM, sc + k.C1, (float*)(sc + k.R2),
-                                          sc + k.A0 + (size_t)ci * OL_MAXM * 768 * es, bn1, bn2, st))
-                return e;
-        }
-    // fc1..fc7: accumulate over the chunks, then (but for fc7) normalise them into the other buffer
-    for (int i = 0; i < CP_N_FC; ++i) {
-        const int K = fcK(i);
-        unsigned char* in = sc + (i % 2 == 0 ? k.A0 : k.A1);
-        unsigned char* out = sc + (i % 2 == 0 ? k.A1 : k.A0);
-        for (int pass = 0; pass < (i + 1 < CP_N_FC ? 2 : 1); ++pass)
-            for (int64_t ci = 0; ci < nch; ++ci) {
-                const OlaBn bn = pass == 0 ? ola_bn(base, w, i + 2, OLA_ACC, acc, ci == 0, ci + 1 == nch)
-                                           : ola_bn(base, w, i + 2, OLA_FROZEN, nullptr, 0, 0);
-                if (int e = ola_fc<T>(base, w, state, i, in + (size_t)ci * OL_MAXM * K * es, out + (size_t)ci * OL_MAXM * 512 * es,
-                                      rows_of(ci), bn, st))
-                    return e;
-            }
-    }
-    return 0;
-}
-
-extern "C" int cp_online_adapt_calibrate(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* windows,
-                                         int64_t n_windows, void* scratch, size_t scratch_bytes, void* stream) {
-    if (n_windows < 2) return fail(CP_ERR_ARG, "cp_online_adapt_calibrate: calibration takes at least 2 windows");
-    if (n_windows > (int64_t)1 << 24) return fail(CP_ERR_ARG, "cp_online_adapt_calibrate: at most 2**24 windows");
-    OlaWS w;
-    if (int e = ola_check(cfg, ws, ws_bytes, &w)) return e;
-    if (!windows || !scratch) return fail(CP_ERR_ARG, "cp_online_adapt_calibrate: windows and scratch are required");
-    if ((uintptr_t)windows % 4 || (uintptr_t)scratch % 256) return fail(CP_ERR_ARG, "cp_online_adapt_calibrate: misaligned input or scratch");
-    const OlaCalib k = ola_calib_carve(n_windows, cfg->dtype);
-    if (scratch_bytes < k.total) return fail(CP_ERR_WORKSPACE, "cp_online_adapt_calibrate: scratch too small");
-    unsigned char* base = (unsigned char*)ws;
-    if (cfg->dtype == CP_BF16)
-        return online_adapt_calibrate_t<bf16_t>(base, w, windows, n_windows, (unsigned char*)scratch, k, (hipStream_t)stream);
-    return online_adapt_calibrate_t<float>(base, w, windows, n_windows, (unsigned char*)scratch, k, (hipStream_t)stream);
-}
-
-extern "C" int cp_online_adapt_statistics(const cp_online_config* cfg, void* ws, size_t ws_bytes, double* out, void* stream) {
-    OlaWS w;
-    if (int e = ola_check(cfg, ws, ws_bytes, &w)) return e;
-    if (!out) return fail(CP_ERR_ARG, "cp_online_adapt_statistics: out is required");
-    CK(hipMemcpyAsync(out, (unsigned char*)ws + w.stats, (size_t)CP_N_BN * 2 * OLA_F * 8, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------
-// multi-stream online decoding (csrc/online_multi.cuh): S states, the folded weights once, rows of all streams packed
-// ---------------------------------------------------------------------------------------
-static_assert(OLM_MAXS == CP_ONLINE_MULTI_MAX_STREAMS && OL_MAXK == 64, "multi-stream limits");
-struct OlmWS {
-    OlWS w;                  // w.state: stream 0's state, w.X / H0 / H1: max_rows rows
-    size_t meta;
-};
-
-static int olm_check(const cp_online_config* c, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes, OlmWS* out) {
-    if (n_streams < 1 || n_streams > CP_ONLINE_MULTI_MAX_STREAMS) return fail(CP_ERR_ARG, "cp_online_multi: n_streams outside 1..256");
-    if (max_rows < 1 || max_rows > CP_ONLINE_MULTI_MAX_ROWS) return fail(CP_ERR_ARG, "cp_online_multi: max_rows outside 1..65536");
-    if (int e = ol_check_config(c, ws)) return e;
-    out->w = ol_carve(max_rows, c->dtype, n_streams, &out->meta);
-    if (ws_bytes < out->w.total) return fail(CP_ERR_WORKSPACE, "cp_online_multi: workspace too small");
-    return 0;
-}
-
-extern "C" size_t cp_online_multi_workspace_bytes(int32_t n_streams, int32_t max_rows, int32_t dtype) {
-    if (n_streams < 1) n_streams = 1;
-    if (max_rows < 1) max_rows = 1;
-    size_t meta;
-    return ol_carve(max_rows, dtype, n_streams, &meta).total;
-}
-
-extern "C" int cp_online_multi_prepare(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, const cp_params* p,
-                                       const cp_bn_buffers* bn, float bn_eps, void* ws, size_t ws_bytes, void* stream) {
-    OlmWS w;
-    if (int e = olm_check(cfg, n_streams, max_rows, ws, ws_bytes, &w)) return e;
-    if (!p || !p->conv1_w || !p->conv1_b || !p->conv2_w || !p->conv2_b || !p->last_w) return fail(CP_ERR_ARG, "cp_online_multi_prepare: parameters");
-    for (int i = 0; i < CP_N_FC; ++i)
-        if (!p->fc_w[i] || !p->fc_b[i]) return fail(CP_ERR_ARG, "cp_online_multi_prepare: parameters");
-    if (!bn) return fail(CP_ERR_ARG, "cp_online_multi_prepare: stock BatchNorm with running statistics required (AdaBN has none)");
-    for (int l = 0; l < CP_N_BN; ++l)
-        if (!p->bn_g[l] || !p->bn_b[l] || !bn->running_mean[l] || !bn->running_var[l])
-            return fail(CP_ERR_ARG, "cp_online_multi_prepare: stock BatchNorm with running statistics required (AdaBN has none)");
-    unsigned char* base = (unsigned char*)ws;
-    if (cfg->dtype == CP_BF16) return online_prepare_t<bf16_t>(p, bn, bn_eps, base, w.w, (hipStream_t)stream);
-    return online_prepare_t<float>(p, bn, bn_eps, base, w.w, (hipStream_t)stream);
-}
-
-extern "C" int cp_online_multi_set_classes(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
-                                           int32_t index, const float* table, const int32_t* ids, int32_t n_classes, void* stream) {
-    OlmWS w;
-    if (int e = olm_check(cfg, n_streams, max_rows, ws, ws_bytes, &w)) return e;
-    if (index < 0 || index >= n_streams) return fail(CP_ERR_ARG, "cp_online_multi_set_classes: stream index outside 0..n_streams-1");
-    if (!table || !ids || n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return fail(CP_ERR_ARG, "cp_online_multi_set_classes: 1..64 classes");
-    OlState* states = (OlState*)((unsigned char*)ws + w.w.state);
-    hipLaunchKernelGGL(ol_set_classes_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, states + index, table, ids, (int)n_classes);
-    CKL("ol_set_classes_kernel");
-    return 0;
-}
-
-extern "C" int cp_online_multi_reset(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
-                                     int32_t index, void* stream) {
-    OlmWS w;
-    if (int e = olm_check(cfg, n_streams, max_rows, ws, ws_bytes, &w)) return e;
-    if (index < -1 || index >= n_streams) return fail(CP_ERR_ARG, "cp_online_multi_reset: stream index outside -1..n_streams-1");
-    OlState* states = (OlState*)((unsigned char*)ws + w.w.state);
-    hipLaunchKernelGGL(olm_reset_kernel, dim3(index < 0 ? n_streams : 1), dim3(256), 0, (hipStream_t)stream, states, index < 0 ? 0 : index);
-    CKL("olm_reset_kernel");
-    return 0;
-}
-
-// row blocks of an encoder launch with `ftiles` workgroups per row block: about OLM_TARGET_WG workgroups when there are rows
-static void olm_row_blocks(int rows, int ftiles, int* blocks, int* tiles_per_block) {
-    const int tiles = (rows + 15) / 16;
-    int b = (OLM_TARGET_WG + ftiles - 1) / ftiles;
-    if (b > tiles) b = tiles;
-    *tiles_per_block = (tiles + b - 1) / b;
-    *blocks = (tiles + *tiles_per_block - 1) / *tiles_per_block;
-}
-
-template <typename T>
-static int online_multi_push_t(const cp_online_config* c, int n_streams, unsigned char* base, const OlmWS& m, const float* raw,
-                               const int32_t* counts, int64_t total, int rows, const float* mean_std, int32_t* pred,
-                               int32_t* voted, float* logits, float* windows, hipStream_t st) {
-    const OlWS& w = m.w;
-    OlState* states = (OlState*)(base + w.state);
-    OlmMeta* meta = (OlmMeta*)(base + m.meta);
-    OlmFrontArgs fa{};
-    fa.f.raw = raw; fa.f.X = (float*)(base + w.X); fa.f.windows = windows; fa.f.mean_std = mean_std;
-    fa.f.n_coef = c->n_coef; fa.f.phase = c->phase; fa.f.gain = 1024.f;       // as ol_launch_frontend
-    for (int i = 0; i < c->n_coef; ++i) { fa.f.b[i] = c->b[i] / c->a[0]; fa.f.a[i] = c->a[i] / c->a[0]; }
-    fa.states = states; fa.meta = meta; fa.counts = counts; fa.total_samples = total; fa.rows = rows; fa.max_m = c->max_windows;
-    if (c->n_coef == 9) hipLaunchKernelGGL((olm_frontend_kernel<9>), dim3(n_streams), dim3(256), 0, st, fa);
-    else hipLaunchKernelGGL((olm_frontend_kernel<0>), dim3(n_streams), dim3(256), 0, st, fa);
-    CKL("olm_frontend_kernel");
-    OlmLayerArgs la{};
-    la.rows = rows;
-    if (rows > 0) {
-        OlLayerArgs& l = la.l;
-        l.x = (const float*)(base + w.X); l.c1w = (const float*)(base + w.c1w); l.c1b = (const float*)(base + w.c1b);
-        l.w = base + w.c2w; l.bias = (const float*)(base + w.c2b); l.out = base + w.H0; l.K = OL_CONV_K; l.F = 64; l.ldo = 768;
-        l.out_pos = 64;
-        int blocks;
-        olm_row_blocks(rows, 4 * OL_C, &blocks, &la.tiles_per_block);
-        hipLaunchKernelGGL((olm_layer_kernel<T, true>), dim3(4, OL_C, blocks), dim3(OL_THREADS), 0, st, la);
-        CKL("olm_layer_kernel<conv>");
-        olm_row_blocks(rows, 512 / 16, &blocks, &la.tiles_per_block);
-        for (int i = 0; i < CP_N_FC; ++i) {               // H0 -> H1 -> H0 ...: fc7 leaves its output in H1
-            l.act = base + (i % 2 == 0 ? w.H0 : w.H1);
-            l.out = base + (i % 2 == 0 ? w.H1 : w.H0);
-            l.w = base + w.fcw[i]; l.bias = (const float*)(base + w.fcb[i]); l.K = fcK(i); l.F = 512; l.ldo = 512; l.out_pos = 0;
-            hipLaunchKernelGGL((olm_layer_kernel<T, false>), dim3(512 / 16, blocks), dim3(OL_THREADS), 0, st, la);
-            CKL("olm_layer_kernel<fc>");
-        }
-    }
-    OlmTailArgs ta{};
-    ta.proj = la.l;
-    ta.proj.act = base + w.H1; ta.proj.out = nullptr; ta.proj.w = base + w.pw; ta.proj.bias = (const float*)(base + w.pb); ta.proj.K = 512;
-    ta.proj.F = CP_D_E;
-    ta.states = states; ta.meta = meta; ta.vote = c->vote; ta.pred = pred; ta.voted = voted; ta.logits = logits;
-    hipLaunchKernelGGL((olm_tail_kernel<T>), dim3(n_streams), dim3(OL_THREADS), 0, st, ta);
-    CKL("olm_tail_kernel");
-    return 0;
-}
-
-extern "C" int cp_online_multi_push(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
-                                    const float* raw, const int32_t* counts, int64_t total_samples, int32_t total_windows,
-                                    const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, void* stream) {
-    OlmWS w;
-    if (int e = olm_check(cfg, n_streams, max_rows, ws, ws_bytes, &w)) return e;
-    if (total_windows < 0 || total_windows > max_rows) return fail(CP_ERR_ARG, "cp_online_multi_push: total_windows outside 0..max_rows");
-    if (total_samples < 0) return fail(CP_ERR_ARG, "cp_online_multi_push: negative total_samples");
-    if (total_samples == 0) return 0;
-    if (!raw || !counts || !mean_std) return fail(CP_ERR_ARG, "cp_online_multi_push: raw, counts and mean_std are required");
-    if (total_windows > 0 && (!pred || !voted)) return fail(CP_ERR_ARG, "cp_online_multi_push: pred and voted are required");
-    if ((uintptr_t)raw % 4 || (uintptr_t)mean_std % 4 || (uintptr_t)counts % 4) return fail(CP_ERR_ARG, "cp_online_multi_push: misaligned input");
-    unsigned char* base = (unsigned char*)ws;
-    if (cfg->dtype == CP_BF16)
-        return online_multi_push_t<bf16_t>(cfg, n_streams, base, w, raw, counts, total_samples, total_windows, mean_std, pred, voted,
-                                           logits, windows, (hipStream_t)stream);
-    return online_multi_push_t<float>(cfg, n_streams, base, w, raw, counts, total_samples, total_windows, mean_std, pred, voted, logits,
-                                      windows, (hipStream_t)stream);
-}
-
-// ---------------------------------------------------------------------------------------
-// adaptive multi-stream online decoding (csrc/online_multi_adapt.cuh): the unfolded weights once; per stream its OlState, head
-// and float64 statistics; rows of all streams packed
-// ---------------------------------------------------------------------------------------
-struct OlamWS {
-    OlaWS w;                 // w.state, w.head, w.stats: stream 0's; w.X, C1, R2, H0, H1: max_rows rows
-    size_t meta;
-};
-// Begins as the folded multi-stream carve (n_streams states, then their OlmMeta), so cp_online_multi_set_classes and
-// cp_online_multi_reset take this workspace
-static OlamWS olam_carve(int64_t max_rows, int dtype, int n_streams) {
-    const size_t es = dtype == CP_BF16 ? 2 : 4;
-    const size_t rows = (size_t)((max_rows + 15) / 16 * 16);
-    OlamWS m{};
-    OlaWS& w = m.w;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t r = o; o = align256(o + bytes); return r; };
-    w.state = take((size_t)n_streams * sizeof(OlState));
-    m.meta = take((size_t)n_streams * sizeof(OlmMeta));
-    w.head = take((size_t)n_streams * sizeof(OlaHead));
-    w.stats = take((size_t)n_streams * OLAM_STATS * 8);
-    w.c1w = take(64 * 3 * 4);
-    w.c1b = take(64 * 4);
-    w.c2w = take(64 * OL_CONV_K * es);
-    w.c2b = take(64 * 4);
-    for (int i = 0; i < CP_N_FC; ++i) {
-        w.fcw[i] = take((size_t)512 * fcK(i) * es);
-        w.fcb[i] = take(512 * 4);
-    }
-    w.pw = take(CP_D_E * 512 * es);
-    w.pb = take(CP_D_E * 4);                              // zeros, as in the single-stream adaptive carve
-    w.gb = take((size_t)CP_N_BN * 2 * OLA_F * 4);
-    w.X = take(rows * OL_C * 4);
-    w.C1 = take(rows * OL_C * OL_CONV_K * es);
-    w.R2 = take(rows * OL_C * 64 * 4);
-    w.H0 = take(rows * 768 * es);
-    w.H1 = take(rows * 512 * es);
-    w.total = o;
-    return m;
-}
-
-// the single-stream view of stream s: its state, head and statistics, the shared weights and buffers
-static OlaWS olam_stream(const OlamWS& m, int s) {
-    OlaWS w = m.w;
-    w.state += (size_t)s * sizeof(OlState);
-    w.head += (size_t)s * sizeof(OlaHead);
-    w.stats += (size_t)s * OLAM_STATS * 8;
-    return w;
-}
-
-static int olam_check(const cp_online_config* c, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes, OlamWS* out) {
-    if (n_streams < 1 || n_streams > CP_ONLINE_MULTI_MAX_STREAMS) return fail(CP_ERR_ARG, "cp_online_multi_adapt: n_streams outside 1..256");
-    if (max_rows < 1 || max_rows > CP_ONLINE_MULTI_MAX_ROWS) return fail(CP_ERR_ARG, "cp_online_multi_adapt: max_rows outside 1..65536");
-    if (int e = ol_check_config(c, ws)) return e;
-    *out = olam_carve(max_rows, c->dtype, n_streams);
-    if (ws_bytes < out->w.total) return fail(CP_ERR_WORKSPACE, "cp_online_multi_adapt: workspace too small");
-    return 0;
-}
-
-static int olam_index(int32_t index, int32_t n_streams, const char* who) {
-    if (index < 0 || index >= n_streams) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "%s: stream index outside 0..n_streams-1", who);
-        return fail(CP_ERR_ARG, msg);
-    }
-    return 0;
-}
-
-extern "C" size_t cp_online_multi_adapt_workspace_bytes(int32_t n_streams, int32_t max_rows, int32_t dtype) {
-    if (n_streams < 1) n_streams = 1;
-    if (max_rows < 1) max_rows = 1;
-    return olam_carve(max_rows, dtype, n_streams).w.total;
-}
-
-template <typename T>
-static int online_multi_adapt_prepare_t(const cp_params* p, const cp_bn_buffers* bn, float eps, const double* alpha, int n_streams,
-                                        unsigned char* base, const OlamWS& m, hipStream_t st) {
-    const OlaWS& w = m.w;
-    OlamInitArgs ia{};
-    for (int l = 0; l < CP_N_BN; ++l) {
-        ia.g[l] = p->bn_g[l]; ia.beta[l] = p->bn_b[l];
-        ia.mean[l] = bn ? bn->running_mean[l] : nullptr; ia.var[l] = bn ? bn->running_var[l] : nullptr;
-    }
-    ia.c1w = p->conv1_w; ia.c1b = p->conv1_b; ia.gb = (float*)(base + w.gb); ia.stats = (double*)(base + w.stats);
-    ia.c1w_d = (float*)(base + w.c1w); ia.c1b_d = (float*)(base + w.c1b); ia.heads = (OlaHead*)(base + w.head);
-    ia.eps = eps; ia.first = 0; ia.zero = 0; ia.set_alpha = alpha != nullptr;
-    for (int s = 0; alpha && s < n_streams; ++s) ia.alpha[s] = alpha[s];
-    hipLaunchKernelGGL(olam_init_kernel, dim3(CP_N_BN, n_streams), dim3(512), 0, st, ia);
-    CKL("olam_init_kernel");
-    OlaCopyArgs f{};                                      // as online_adapt_prepare_t
-    f.W = p->conv2_w; f.b = p->conv2_b; f.Wd = base + w.c2w; f.bd = (float*)(base + w.c2b); f.K = OL_CONV_K; f.mode = 2;
-    hipLaunchKernelGGL((ola_copy_kernel<T>), dim3(64), dim3(256), 0, st, f);
-    CKL("ola_copy_kernel");
-    for (int i = 0; i < CP_N_FC; ++i) {
-        f.W = p->fc_w[i]; f.b = p->fc_b[i]; f.Wd = base + w.fcw[i]; f.bd = (float*)(base + w.fcb[i]); f.K = fcK(i); f.mode = i == 0 ? 1 : 0;
-        hipLaunchKernelGGL((ola_copy_kernel<T>), dim3(512), dim3(256), 0, st, f);
-        CKL("ola_copy_kernel");
-    }
-    f.W = p->last_w; f.b = nullptr; f.Wd = base + w.pw; f.bd = (float*)(base + w.pb); f.K = 512; f.mode = 0;
-    hipLaunchKernelGGL((ola_copy_kernel<T>), dim3(CP_D_E), dim3(256), 0, st, f);
-    CKL("ola_copy_kernel");
-    return 0;
-}
-
-extern "C" int cp_online_multi_adapt_prepare(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, const cp_params* p,
-                                             const cp_bn_buffers* bn, float bn_eps, const double* alpha, void* ws, size_t ws_bytes,
-                                             void* stream) {
-    if (!(bn_eps > 0.f)) return fail(CP_ERR_ARG, "cp_online_multi_adapt_prepare: bn_eps must be positive");
-    OlamWS m;
-    if (int e = olam_check(cfg, n_streams, max_rows, ws, ws_bytes, &m)) return e;
-    for (int s = 0; alpha && s < n_streams; ++s)
-        if (!(alpha[s] >= 0.0 && alpha[s] < 1.0)) return fail(CP_ERR_ARG, "cp_online_multi_adapt_prepare: alpha outside [0, 1)");
-    if (!p || !p->conv1_w || !p->conv1_b || !p->conv2_w || !p->conv2_b || !p->last_w)
-        return fail(CP_ERR_ARG, "cp_online_multi_adapt_prepare: parameters");
-    for (int i = 0; i < CP_N_FC; ++i)
-        if (!p->fc_w[i] || !p->fc_b[i]) return fail(CP_ERR_ARG, "cp_online_multi_adapt_prepare: parameters");
-    for (int l = 0; l < CP_N_BN; ++l) {
-        if (!p->bn_g[l] || !p->bn_b[l]) return fail(CP_ERR_ARG, "cp_online_multi_adapt_prepare: parameters");
-        if (bn && (!bn->running_mean[l] || !bn->running_var[l])) return fail(CP_ERR_ARG, "cp_online_multi_adapt_prepare: running statistics");
-    }
-    unsigned char* base = (unsigned char*)ws;
-    if (cfg->dtype == CP_BF16) return online_multi_adapt_prepare_t<bf16_t>(p, bn, bn_eps, alpha, n_streams, base, m, (hipStream_t)stream);
-    return online_multi_adapt_prepare_t<float>(p, bn, bn_eps, alpha, n_streams, base, m, (hipStream_t)stream);
-}
-
-extern "C" int cp_online_multi_adapt_set_alpha(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
-                                               size_t ws_bytes, int32_t index, double alpha, void* stream) {
-    OlamWS m;
-    if (int e = olam_check(cfg, n_streams, max_rows, ws, ws_bytes, &m)) return e;
-    if (int e = olam_index(index, n_streams, "cp_online_multi_adapt_set_alpha")) return e;
-    if (!(alpha >= 0.0 && alpha < 1.0)) return fail(CP_ERR_ARG, "cp_online_multi_adapt_set_alpha: alpha outside [0, 1)");
-    hipLaunchKernelGGL(olam_set_alpha_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream,
-                       (OlaHead*)((unsigned char*)ws + olam_stream(m, index).head), alpha);
-    CKL("olam_set_alpha_kernel");
-    return 0;
-}
-
-extern "C" int cp_online_multi_adapt_reset_statistics(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
-                                                      size_t ws_bytes, int32_t index, const cp_bn_buffers* bn, void* stream) {
-    OlamWS m;
-    if (int e = olam_check(cfg, n_streams, max_rows, ws, ws_bytes, &m)) return e;
-    if (int e = olam_index(index, n_streams, "cp_online_multi_adapt_reset_statistics")) return e;
-    OlamInitArgs ia{};
-    for (int l = 0; l < CP_N_BN; ++l) {
-        if (bn && (!bn->running_mean[l] || !bn->running_var[l]))
-            return fail(CP_ERR_ARG, "cp_online_multi_adapt_reset_statistics: running statistics");
-        ia.mean[l] = bn ? bn->running_mean[l] : nullptr; ia.var[l] = bn ? bn->running_var[l] : nullptr;
-    }
-    ia.stats = (double*)((unsigned char*)ws + m.w.stats); ia.first = index; ia.zero = bn ? 0 : 1;
-    hipLaunchKernelGGL(olam_init_kernel, dim3(CP_N_BN, 1), dim3(512), 0, (hipStream_t)stream, ia);
-    CKL("olam_init_kernel");
-    return 0;
-}
-
-extern "C" int cp_online_multi_adapt_calibrate(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
-                                               size_t ws_bytes, int32_t index, const float* windows, int64_t n_windows, void* scratch,
-                                               size_t scratch_bytes, void* stream) {
-    if (n_windows < 2) return fail(CP_ERR_ARG, "cp_online_multi_adapt_calibrate: calibration takes at least 2 windows");
-    if (n_windows > (int64_t)1 << 24) return fail(CP_ERR_ARG, "cp_online_multi_adapt_calibrate: at most 2**24 windows");
-    OlamWS m;
-    if (int e = olam_check(cfg, n_streams, max_rows, ws, ws_bytes, &m)) return e;
-    if (int e = olam_index(index, n_streams, "cp_online_multi_adapt_calibrate")) return e;
-    if (!windows || !scratch) return fail(CP_ERR_ARG, "cp_online_multi_adapt_calibrate: windows and scratch are required");
-    if ((uintptr_t)windows % 4 || (uintptr_t)scratch % 256)
-        return fail(CP_ERR_ARG, "cp_online_multi_adapt_calibrate: misaligned input or scratch");
-    const OlaCalib k = ola_calib_carve(n_windows, cfg->dtype);
-    if (scratch_bytes < k.total) return fail(CP_ERR_WORKSPACE, "cp_online_multi_adapt_calibrate: scratch too small");
-    unsigned char* base = (unsigned char*)ws;
-    const OlaWS w = olam_stream(m, index);
-    if (cfg->dtype == CP_BF16)
-        return online_adapt_calibrate_t<bf16_t>(base, w, windows, n_windows, (unsigned char*)scratch, k, (hipStream_t)stream);
-    return online_adapt_calibrate_t<float>(base, w, windows, n_windows, (unsigned char*)scratch, k, (hipStream_t)stream);
-}
-
-// row blocks of the fc launches: about OLM_TARGET_WG workgroups of 512 / 16 feature tiles when there are rows enough
-static void olam_fc_blocks(int rows, int* blocks, int* rows_per_block) {
-    int b = (OLM_TARGET_WG + 512 / 16 - 1) / (512 / 16);
-    if (b > rows) b = rows;
-    *rows_per_block = (rows + b - 1) / b;
-    *blocks = (rows + *rows_per_block - 1) / *rows_per_block;
-}
-
-template <typename T>
-static int online_multi_adapt_push_t(const cp_online_config* c, int n_streams, unsigned char* base, const OlamWS& m, const float* raw,
-                                     const int32_t* counts, int64_t total, int rows, const float* mean_std, int32_t* pred,
-                                     int32_t* voted, float* logits, float* windows, hipStream_t st) {
-    const OlaWS& w = m.w;
-    OlState* states = (OlState*)(base + w.state);
-    OlmMeta* meta = (OlmMeta*)(base + m.meta);
-    OlmFrontArgs fa{};
-    fa.f.raw = raw; fa.f.X = (float*)(base + w.X); fa.f.windows = windows; fa.f.mean_std = mean_std;
-    fa.f.n_coef = c->n_coef; fa.f.phase = c->phase; fa.f.gain = 1024.f;       // as ol_launch_frontend
-    for (int i = 0; i < c->n_coef; ++i) { fa.f.b[i] = c->b[i] / c->a[0]; fa.f.a[i] = c->a[i] / c->a[0]; }
-    fa.states = states; fa.meta = meta; fa.counts = counts; fa.total_samples = total; fa.rows = rows; fa.max_m = c->max_windows;
-    if (c->n_coef == 9) hipLaunchKernelGGL((olm_frontend_kernel<9>), dim3(n_streams), dim3(256), 0, st, fa);
-    else hipLaunchKernelGGL((olm_frontend_kernel<0>), dim3(n_streams), dim3(256), 0, st, fa);
-    CKL("olm_frontend_kernel");
-    if (rows > 0) {
-        OlamConvBnArgs cb{};                              // BN1 -> conv2 -> BN2, as ola_conv_chain
-        cb.meta = meta;
-        cb.a.x = (const float*)(base + w.X); cb.a.c1w = (const float*)(base + w.c1w); cb.a.c1b = (const float*)(base + w.c1b);
-        cb.a.out = base + w.C1; cb.a.m_fixed = 0; cb.a.conv1 = 1; cb.a.bn = ola_bn(base, w, 0, OLA_TRACK, nullptr, 0, 0);
-        hipLaunchKernelGGL((olam_conv_bn_kernel<T>), dim3(n_streams), dim3(64), 0, st, cb);
-        CKL("olam_conv_bn_kernel<BN1>");
-        OlaGemmArgs g{};
-        g.l.act = base + w.C1; g.l.w = base + w.c2w; g.l.bias = (const float*)(base + w.c2b); g.l.out = base + w.R2; g.l.K = OL_CONV_K;
-        g.l.F = 64; g.l.ldo = 64; g.m_fixed = rows; g.rows_per_window = OL_C;
-        int blocks, tiles_per_block;
-        olm_row_blocks(rows * OL_C, 64 / 16, &blocks, &tiles_per_block);
-        hipLaunchKernelGGL((ola_gemm_kernel<T>), dim3(64 / 16, blocks), dim3(OL_THREADS), 0, st, g);
-        CKL("ola_gemm_kernel");
-        cb.a.pre = (const float*)(base + w.R2); cb.a.out = base + w.H0; cb.a.conv1 = 0; cb.a.bn = ola_bn(base, w, 1, OLA_TRACK, nullptr, 0, 0);
-        hipLaunchKernelGGL((olam_conv_bn_kernel<T>), dim3(n_streams), dim3(64), 0, st, cb);
-        CKL("olam_conv_bn_kernel<BN2>");
-        OlamFcArgs fc{};
-        fc.meta = meta; fc.n_streams = n_streams;
-        olam_fc_blocks(rows, &blocks, &fc.rows_per_block);
-        for (int i = 0; i < CP_N_FC; ++i) {               // H0 -> H1 -> H0 ...: fc7 leaves its output in H1
-            OlaGemmArgs& a = fc.g;
-            a.l.act = base + (i % 2 == 0 ? w.H0 : w.H1); a.l.out = base + (i % 2 == 0 ? w.H1 : w.H0);
-            a.l.w = base + w.fcw[i]; a.l.bias = (const float*)(base + w.fcb[i]); a.l.K = fcK(i); a.l.F = 512; a.l.ldo = 512;
-            a.rows_per_window = 1; a.bn = ola_bn(base, w, i + 2, OLA_TRACK, nullptr, 0, 0);
-            hipLaunchKernelGGL((olam_fc_kernel<T>), dim3(512 / 16, blocks), dim3(OL_THREADS), 0, st, fc);
-            CKL("olam_fc_kernel");
-        }
-    }
-    OlmTailArgs ta{};
-    ta.proj.act = base + w.H1; ta.proj.w = base + w.pw; ta.proj.bias = (const float*)(base + w.pb); ta.proj.K = 512; ta.proj.F = CP_D_E;
-    ta.states = states; ta.meta = meta; ta.vote = c->vote; ta.pred = pred; ta.voted = voted; ta.logits = logits;
-    hipLaunchKernelGGL((olm_tail_kernel<T>), dim3(n_streams), dim3(OL_THREADS), 0, st, ta);
-    CKL("olm_tail_kernel");
-    return 0;
-}
-
-extern "C" int cp_online_multi_adapt_push(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
-                                          const float* raw, const int32_t* counts, int64_t total_samples, int32_t total_windows,
-                                          const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows,
-                                          void* stream) {
-    OlamWS m;
-    if (int e = olam_check(cfg, n_streams, max_rows, ws, ws_bytes, &m)) return e;
-    if (total_windows < 0 || total_windows > max_rows) return fail(CP_ERR_ARG, "cp_online_multi_adapt_push: total_windows outside 0..max_rows");
-    if (total_samples < 0) return fail(CP_ERR_ARG, "cp_online_multi_adapt_push: negative total_samples");
-    if (total_samples == 0) return 0;
-    if (!raw || !counts || !mean_std) return fail(CP_ERR_ARG, "cp_online_multi_adapt_push: raw, counts and mean_std are required");
-    if (total_windows > 0 && (!pred || !voted)) return fail(CP_ERR_ARG, "cp_online_multi_adapt_push: pred and voted are required");
-    if ((uintptr_t)raw % 4 || (uintptr_t)mean_std % 4 || (uintptr_t)counts % 4)
-        return fail(CP_ERR_ARG, "cp_online_multi_adapt_push: misaligned input");
-    unsigned char* base = (unsigned char*)ws;
-    if (cfg->dtype == CP_BF16)
-        return online_multi_adapt_push_t<bf16_t>(cfg, n_streams, base, m, raw, counts, total_samples, total_windows, mean_std, pred, voted,
-                                                 logits, windows, (hipStream_t)stream);
-    return online_multi_adapt_push_t<float>(cfg, n_streams, base, m, raw, counts, total_samples, total_windows, mean_std, pred, voted,
-                                            logits, windows, (hipStream_t)stream);
-}
-
-extern "C" int cp_online_multi_adapt_statistics(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
-                                                size_t ws_bytes, int32_t index, double* out, void* stream) {
-    OlamWS m;
-    if (int e = olam_check(cfg, n_streams, max_rows, ws, ws_bytes, &m)) return e;
-    if (int e = olam_index(index, n_streams, "cp_online_multi_adapt_statistics")) return e;
-    if (!out) return fail(CP_ERR_ARG, "cp_online_multi_adapt_statistics: out is required");
-    CK(hipMemcpyAsync(out, (unsigned char*)ws + olam_stream(m, index).stats, (size_t)OLAM_STATS * 8, hipMemcpyDeviceToDevice,
-                      (hipStream_t)stream));
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------
-// class enrolment (csrc/online_enroll.cuh): the front end alone, per-class sums of z / |z| in the caller's float64
-// accumulator, and the blend of those directions with the rows a decoder has
-// ---------------------------------------------------------------------------------------
-extern "C" size_t cp_online_frontend_state_bytes(void) { return align256(offsetof(OlState, K)); }
-
-extern "C" int cp_online_windows(const cp_online_config* cfg, void* state, size_t state_bytes, const float* raw, int64_t n_samples,
-                                 const float* mean_std, float* windows, void* stream) {
-    if (!cfg || !state) return fail(CP_ERR_ARG, "cp_online_windows: config and state are required");
-    if (int e = ol_check_config(cfg, state)) return e;
-    if (state_bytes < cp_online_frontend_state_bytes()) return fail(CP_ERR_ARG, "cp_online_windows: state too small");
-    if (n_samples < 0 || n_samples > (int64_t)CP_ONLINE_STRIDE * cfg->max_windows)
-        return fail(CP_ERR_ARG, "cp_online_windows: a call takes at most 20 * max_windows samples");
-    if (n_samples == 0) return 0;
-    if (!raw || !mean_std || !windows) return fail(CP_ERR_ARG, "cp_online_windows: raw, mean_std and windows are required");
-    if ((uintptr_t)raw % 4 || (uintptr_t)mean_std % 4 || (uintptr_t)windows % 4) return fail(CP_ERR_ARG, "cp_online_windows: misaligned input");
-    OlFrontArgs fa{};
-    fa.raw = raw; fa.n = n_samples; fa.st = (OlState*)state; fa.X = windows; fa.windows = nullptr; fa.mean_std = mean_std;
-    fa.n_coef = cfg->n_coef; fa.phase = cfg->phase; fa.gain = 1024.f;         // as ol_launch_frontend
-    for (int i = 0; i < cfg->n_coef; ++i) { fa.b[i] = cfg->b[i] / cfg->a[0]; fa.a[i] = cfg->a[i] / cfg->a[0]; }
-    if (cfg->n_coef == 9) hipLaunchKernelGGL((ole_windows_kernel<9>), dim3(1), dim3(256), 0, (hipStream_t)stream, fa);
-    else hipLaunchKernelGGL((ole_windows_kernel<0>), dim3(1), dim3(256), 0, (hipStream_t)stream, fa);
-    CKL("ole_windows_kernel");
-    return 0;
-}
-
-// enrolment scratch: the activations of one chunk of <= 256 windows (the adaptive form also conv2's operand and output)
-struct OleScratch {
-    size_t C1, R2, H0, H1, total;
-};
-static OleScratch ole_carve(int64_t n_windows, int dtype) {
-    const size_t es = dtype == CP_BF16 ? 2 : 4;
-    const size_t rows = (size_t)(((n_windows < OL_MAXM ? n_windows : OL_MAXM) + 15) / 16 * 16);
-    OleScratch c{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t r = o; o = align256(o + bytes); return r; };
-    c.C1 = take(rows * OL_C * OL_CONV_K * es);
-    c.R2 = take(rows * OL_C * 64 * 4);
-    c.H0 = take(rows * 768 * es);
-    c.H1 = take(rows * 512 * es);
-    c.total = o;
-    return c;
-}
-
-extern "C" size_t cp_online_enroll_scratch_bytes(int64_t n_windows, int32_t dtype) {
-    if (n_windows < 1) n_windows = 1;
-    return ole_carve(n_windows, dtype).total;
-}
-
-// what the four accumulate entries check alike; n_windows == 0 is a valid empty call (the caller returns 0)
-static int ole_check(const char* who, const float* windows, int64_t n_windows, const int32_t* slots, int32_t n_classes, double* acc,
-                     void* scratch, size_t scratch_bytes, int dtype, OleScratch* out) {
-    char msg[160];
-    auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", who, what); return fail(CP_ERR_ARG, msg); };
-    if (n_windows < 0 || n_windows > (int64_t)1 << 24) return bad("n_windows outside 0..2**24");
-    if (n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return bad("1..64 classes");
-    if (!acc) return bad("acc is required");
-    if ((uintptr_t)acc % 8) return bad("misaligned acc");
-    if (n_windows == 0) return 0;
-    if (!windows || !slots || !scratch) return bad("windows, slots and scratch are required");
-    if ((uintptr_t)windows % 4 || (uintptr_t)slots % 4 || (uintptr_t)scratch % 256) return bad("misaligned input or scratch");
-    *out = ole_carve(n_windows, dtype);
-    if (scratch_bytes < out->total) {
-        snprintf(msg, sizeof msg, "%s: scratch too small", who);
-        return fail(CP_ERR_WORKSPACE, msg);
-    }
-    return 0;
-}
-
-template <typename T>
-static int ole_accumulate(const void* act, const void* pw, const float* pb, const int32_t* slots, int m, int n_classes, double* acc,
-                          hipStream_t st) {
-    OleAccArgs a{};
-    a.proj.act = act; a.proj.w = pw; a.proj.bias = pb; a.proj.K = 512; a.proj.F = CP_D_E;
-    a.slots = slots; a.acc = acc; a.M = m; a.n_classes = n_classes;
-    hipLaunchKernelGGL((ole_accumulate_kernel<T>), dim3(1), dim3(OL_THREADS), 0, st, a);
-    CKL("ole_accumulate_kernel");
-    return 0;
-}
-
-// the folded encoder of online_push_t over the caller's windows, chunk by chunk
-template <typename T>
-static int online_enroll_t(unsigned char* base, const OlWS& w, const float* x, int64_t N, const int32_t* slots, int n_classes,
-                           double* acc, unsigned char* sc, const OleScratch& k, hipStream_t st) {
-    for (int64_t r0 = 0; r0 < N; r0 += OL_MAXM) {
-        const int m = (int)(N - r0 < OL_MAXM ? N - r0 : OL_MAXM);
-        OlLayerArgs la{};
-        la.x = x + r0 * OL_C; la.c1w = (const float*)(base + w.c1w); la.c1b = (const float*)(base + w.c1b);
-        la.w = base + w.c2w; la.bias = (const float*)(base + w.c2b); la.out = sc + k.H0; la.K = OL_CONV_K; la.F = 64; la.ldo = 768;
-        la.out_pos = 64;
-        hipLaunchKernelGGL((ole_layer_kernel<T, true>), dim3(4, OL_C), dim3(OL_THREADS), 0, st, la, m);
-        CKL("ole_layer_kernel<conv>");
-        for (int i = 0; i < CP_N_FC; ++i) {               // H0 -> H1 -> H0 ...: fc7 leaves its output in H1
-            la.act = sc + (i % 2 == 0 ? k.H0 : k.H1);
-            la.out = sc + (i % 2 == 0 ? k.H1 : k.H0);
-            la.w = base + w.fcw[i]; la.bias = (const float*)(base + w.fcb[i]); la.K = fcK(i); la.F = 512; la.ldo = 512; la.out_pos = 0;
-            hipLaunchKernelGGL((ole_layer_kernel<T, false>), dim3(512 / 16), dim3(OL_THREADS), 0, st, la, m);
-            CKL("ole_layer_kernel<fc>");
-        }
-        if (int e = ole_accumulate<T>(sc + k.H1, base + w.pw, (const float*)(base + w.pb), slots + r0, m, n_classes, acc, st)) return e;
-    }
-    return 0;
-}
-
-// the unfolded encoder with the statistics frozen (the OLA_FROZEN pass of online_adapt_calibrate_t), chunk by chunk
-template <typename T>
-static int online_adapt_enroll_t(unsigned char* base, const OlaWS& w, const float* x, int64_t N, const int32_t* slots, int n_classes,
-                                 double* acc, unsigned char* sc, const OleScratch& k, hipStream_t st) {
-    const OlState* state = (const OlState*)(base + w.state);
-    for (int64_t r0 = 0; r0 < N; r0 += OL_MAXM) {
-        const int m = (int)(N - r0 < OL_MAXM ? N - r0 : OL_MAXM);
-        if (int e = ola_conv_chain<T>(base, w, state, x + r0 * OL_C, m, m, sc + k.C1, (float*)(sc + k.R2), sc + k.H0,
-                                      ola_bn(base, w, 0, OLA_FROZEN, nullptr, 0, 0), ola_bn(base, w, 1, OLA_FROZEN, nullptr, 0, 0), st))
-            return e;
-        for (int i = 0; i < CP_N_FC; ++i)                 // H0 -> H1 -> H0 ...: fc7 leaves its output in H1
-            if (int e = ola_fc<T>(base, w, state, i, sc + (i % 2 == 0 ? k.H0 : k.H1), sc + (i % 2 == 0 ? k.H1 : k.H0), m,
-                                  ola_bn(base, w, i + 2, OLA_FROZEN, nullptr, 0, 0), st))
-                return e;
-        if (int e = ole_accumulate<T>(sc + k.H1, base + w.pw, (const float*)(base + w.pb), slots + r0, m, n_classes, acc, st)) return e;
-    }
-    return 0;
-}
-
-extern "C" int cp_online_enroll(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* windows, int64_t n_windows,
-                                const int32_t* slots, int32_t n_classes, double* acc, void* scratch, size_t scratch_bytes, void* stream) {
-    OlWS w;
-    if (int e = ol_check(cfg, ws, ws_bytes, &w)) return e;
-    OleScratch k;
-    if (int e = ole_check("cp_online_enroll", windows, n_windows, slots, n_classes, acc, scratch, scratch_bytes, cfg->dtype, &k)) return e;
-    if (n_windows == 0) return 0;
-    unsigned char* base = (unsigned char*)ws;
-    if (cfg->dtype == CP_BF16)
-        return online_enroll_t<bf16_t>(base, w, windows, n_windows, slots, n_classes, acc, (unsigned char*)scratch, k, (hipStream_t)stream);
-    return online_enroll_t<float>(base, w, windows, n_windows, slots, n_classes, acc, (unsigned char*)scratch, k, (hipStream_t)stream);
-}
-
-extern "C" int cp_online_adapt_enroll(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* windows, int64_t n_windows,
-                                      const int32_t* slots, int32_t n_classes, double* acc, void* scratch, size_t scratch_bytes,
-                                      void* stream) {
-    OlaWS w;
-    if (int e = ola_check(cfg, ws, ws_bytes, &w)) return e;
-    OleScratch k;
-    if (int e = ole_check("cp_online_adapt_enroll", windows, n_windows, slots, n_classes, acc, scratch, scratch_bytes, cfg->dtype, &k))
-        return e;
-    if (n_windows == 0) return 0;
-    unsigned char* base = (unsigned char*)ws;
-    if (cfg->dtype == CP_BF16)
-        return online_adapt_enroll_t<bf16_t>(base, w, windows, n_windows, slots, n_classes, acc, (unsigned char*)scratch, k,
-                                             (hipStream_t)stream);
-    return online_adapt_enroll_t<float>(base, w, windows, n_windows, slots, n_classes, acc, (unsigned char*)scratch, k, (hipStream_t)stream);
-}
-
-extern "C" int cp_online_multi_enroll(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
-                                      const float* windows, int64_t n_windows, const int32_t* slots, int32_t n_classes, double* acc,
-                                      void* scratch, size_t scratch_bytes, void* stream) {
-    OlmWS m;
-    if (int e = olm_check(cfg, n_streams, max_rows, ws, ws_bytes, &m)) return e;
-    OleScratch k;
-    if (int e = ole_check("cp_online_multi_enroll", windows, n_windows, slots, n_classes, acc, scratch, scratch_bytes, cfg->dtype, &k))
-        return e;
-    if (n_windows == 0) return 0;
-    unsigned char* base = (unsigned char*)ws;
-    if (cfg->dtype == CP_BF16)
-        return online_enroll_t<bf16_t>(base, m.w, windows, n_windows, slots, n_classes, acc, (unsigned char*)scratch, k, (hipStream_t)stream);
-    return online_enroll_t<float>(base, m.w, windows, n_windows, slots, n_classes, acc, (unsigned char*)scratch, k, (hipStream_t)stream);
-}
-
-extern "C" int cp_online_multi_adapt_enroll(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
-                                            int32_t index, const float* windows, int64_t n_windows, const int32_t* slots,
-                                            int32_t n_classes, double* acc, void* scratch, size_t scratch_bytes, void* stream) {
-    OlamWS m;
-    if (int e = olam_check(cfg, n_streams, max_rows, ws, ws_bytes, &m)) return e;
-    if (int e = olam_index(index, n_streams, "cp_online_multi_adapt_enroll")) return e;
-    OleScratch k;
-    if (int e = ole_check("cp_online_multi_adapt_enroll", windows, n_windows, slots, n_classes, acc, scratch, scratch_bytes, cfg->dtype, &k))
-        return e;
-    if (n_windows == 0) return 0;
-    unsigned char* base = (unsigned char*)ws;
-    const OlaWS w = olam_stream(m, index);
-    if (cfg->dtype == CP_BF16)
-        return online_adapt_enroll_t<bf16_t>(base, w, windows, n_windows, slots, n_classes, acc, (unsigned char*)scratch, k,
-                                             (hipStream_t)stream);
-    return online_adapt_enroll_t<float>(base, w, windows, n_windows, slots, n_classes, acc, (unsigned char*)scratch, k, (hipStream_t)stream);
-}
-
-extern "C" int cp_online_enroll_table(const double* acc, int32_t n_classes, const float* prior, double mix, int32_t min_windows,
-                                      float* table, void* stream) {
-    if (!acc || !prior || !table) return fail(CP_ERR_ARG, "cp_online_enroll_table: acc, prior and table are required");
-    if ((uintptr_t)acc % 8 || (uintptr_t)prior % 4 || (uintptr_t)table % 4) return fail(CP_ERR_ARG, "cp_online_enroll_table: misaligned input");
-    if (n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return fail(CP_ERR_ARG, "cp_online_enroll_table: 1..64 classes");
-    if (!(mix >= 0.0 && mix <= 1.0)) return fail(CP_ERR_ARG, "cp_online_enroll_table: mix outside [0, 1]");
-    if (min_windows < 1) return fail(CP_ERR_ARG, "cp_online_enroll_table: min_windows must be at least 1");
-    hipLaunchKernelGGL(ole_table_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, acc, (int)n_classes, prior, mix, (double)min_windows,
-                       table);
-    CKL("ole_table_kernel");
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------
-// grasp command gate (csrc/online_gate.cuh): one OgState per stream in a workspace of its own, behind any decoder's logits
-// ---------------------------------------------------------------------------------------
-static_assert(OG_MAXK == CP_ONLINE_MAX_CLASSES && OG_MAXVOTE == CP_ONLINE_MAX_VOTE && OG_MAXM == CP_ONLINE_MAX_WINDOWS, "gate limits");
-static_assert(sizeof(OgState) == 4 * (8 + 2 * OG_MAXK + 2 * OG_MAXVOTE), "OgState is 648 words (CommandGate.state reads it back)");
-
-static int og_check(const char* who, const cp_online_gate_config* c, int32_t n_streams, void* ws, size_t ws_bytes) {
-    static char msg[160];
-    auto bad = [&](const char* what) {
-        snprintf(msg, sizeof(msg), "%s: %s", who, what);
-        return fail(CP_ERR_ARG, msg);
-    };
-    if (!c || !ws) return bad("config and workspace are required");
-    if (n_streams < 1 || n_streams > CP_ONLINE_MULTI_MAX_STREAMS) return bad("n_streams outside 1..256");
-    if (c->vote < 1 || c->vote > CP_ONLINE_MAX_VOTE) return bad("vote outside 1..256");
-    if (c->min_votes < 1) return bad("min_votes must be at least 1");
-    if (c->dwell < 1) return bad("dwell must be at least 1");
-    if (c->release < 0) return bad("release must not be negative");
-    if (c->weight != 0 && c->weight != 1) return bad("weight must be 0 (count) or 1 (margin)");
-    if (!(c->min_margin >= 0.f) || std::isinf(c->min_margin)) return bad("min_margin must be finite and >= 0");
-    if ((uintptr_t)ws % 256) return bad("workspace not 256-byte aligned");
-    if (ws_bytes < (size_t)n_streams * sizeof(OgState)) return bad("workspace too small");
-    return 0;
-}
-
-extern "C" size_t cp_online_gate_workspace_bytes(int32_t n_streams) {
-    if (n_streams < 1) n_streams = 1;
-    return align256((size_t)n_streams * sizeof(OgState));
-}
-
-extern "C" int cp_online_gate_set_classes(const cp_online_gate_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index,
-                                          const int32_t* ids, const float* min_cosine, int32_t n_classes, void* stream) {
-    if (int e = og_check("cp_online_gate_set_classes", cfg, n_streams, ws, ws_bytes)) return e;
-    if (index < 0 || index >= n_streams) return fail(CP_ERR_ARG, "cp_online_gate_set_classes: stream index outside 0..n_streams-1");
-    if (!ids || !min_cosine || n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES)
-        return fail(CP_ERR_ARG, "cp_online_gate_set_classes: 1..64 classes, with ids and min_cosine");
-    OgClassArgs c{};
-    c.K = n_classes;
-    for (int k = 0; k < n_classes; ++k) {
-        if (ids[k] < 0 || ids[k] == INT32_MAX || (k > 0 && ids[k] <= ids[k - 1]))
-            return fail(CP_ERR_ARG, "cp_online_gate_set_classes: ids must be ascending, distinct and in 0..2^31-2");
-        if (std::isnan(min_cosine[k])) return fail(CP_ERR_ARG, "cp_online_gate_set_classes: min_cosine must not be NaN");
-        c.ids[k] = ids[k];
-        c.min_cosine[k] = min_cosine[k];
-    }
-    hipLaunchKernelGGL(og_set_classes_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (OgState*)ws + index, c);
-    CKL("og_set_classes_kernel");
-    return 0;
-}
-
-extern "C" int cp_online_gate_reset(const cp_online_gate_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index,
-                                    void* stream) {
-    if (int e = og_check("cp_online_gate_reset", cfg, n_streams, ws, ws_bytes)) return e;
-    if (index < -1 || index >= n_streams) return fail(CP_ERR_ARG, "cp_online_gate_reset: stream index outside -1..n_streams-1");
-    hipLaunchKernelGGL(og_reset_kernel, dim3(index < 0 ? n_streams : 1), dim3(64), 0, (hipStream_t)stream, (OgState*)ws,
-                       index < 0 ? 0 : index);
-    CKL("og_reset_kernel");
-    return 0;
-}
-
-extern "C" int cp_online_gate_push(const cp_online_gate_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, const float* logits,
-                                   int32_t ldl, const int32_t* row0, const int32_t* m, int32_t total_rows, int32_t* command,
-                                   int32_t* accepted, float* conf, float* margin, void* stream) {
-    if (int e = og_check("cp_online_gate_push", cfg, n_streams, ws, ws_bytes)) return e;
-    if (total_rows < 0 || total_rows > CP_ONLINE_MULTI_MAX_ROWS) return fail(CP_ERR_ARG, "cp_online_gate_push: total_rows outside 0..65536");
-    if (total_rows == 0) return 0;
-    if (ldl < 1) return fail(CP_ERR_ARG, "cp_online_gate_push: ldl must be at least 1");
-    if (!logits || !row0 || !m || !command || !accepted)
-        return fail(CP_ERR_ARG, "cp_online_gate_push: logits, row0, m, command and accepted are required");
-    if ((uintptr_t)logits % 4 || (uintptr_t)row0 % 4 || (uintptr_t)m % 4 || (uintptr_t)command % 4 || (uintptr_t)accepted % 4 ||
-        (uintptr_t)conf % 4 || (uintptr_t)margin % 4)
-        return fail(CP_ERR_ARG, "cp_online_gate_push: misaligned argument");
-    OgPushArgs a{};
-    a.states = (OgState*)ws; a.logits = logits; a.row0 = row0; a.m = m; a.ldl = ldl; a.total_rows = total_rows;
-    a.command = command; a.accepted = accepted; a.conf = conf; a.margin = margin;
-    a.c.vote = cfg->vote; a.c.min_votes = cfg->min_votes; a.c.dwell = cfg->dwell; a.c.release = cfg->release; a.c.weight = cfg->weight;
-    a.c.min_margin = cfg->min_margin;
-    hipLaunchKernelGGL(og_push_kernel, dim3(n_streams), dim3(64), 0, (hipStream_t)stream, a);
-    CKL("og_push_kernel");
-    return 0;
-}
-
-// gate sweep: n_configs settings over one recording, one wave each, scored on the device (og_rows_kernel, og_sweep_kernel)
-static_assert(OG_SCORES == CP_ONLINE_GATE_SCORES && sizeof(OgRow) == 12, "gate sweep layout");
-static_assert(sizeof(OgConfig) == sizeof(cp_online_gate_config), "the sweep reads cp_online_gate_config from the device as OgConfig");
-
-extern "C" size_t cp_online_gate_sweep_scratch_bytes(int64_t n_rows) {
-    if (n_rows < 1) n_rows = 1;
-    return align256((size_t)n_rows * sizeof(OgRow));
-}
-
-extern "C" int cp_online_gate_sweep(const float* logits, int32_t ldl, int64_t n_rows, int32_t n_classes, const int32_t* expected_slot,
-                                    const cp_online_gate_config* configs, const float* min_cosine, int32_t n_configs, void* scratch,
-                                    size_t scratch_bytes, int64_t* scores, int32_t* commands, void* stream) {
-    if (n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return fail(CP_ERR_ARG, "cp_online_gate_sweep: n_classes outside 1..64");
-    if (ldl < n_classes) return fail(CP_ERR_ARG, "cp_online_gate_sweep: ldl must be at least n_classes");
-    if (n_configs < 1 || n_configs > CP_ONLINE_GATE_SWEEP_MAX_CONFIGS)
-        return fail(CP_ERR_ARG, "cp_online_gate_sweep: n_configs outside 1..65536");
-    if (n_rows < 1 || n_rows > INT32_MAX) return fail(CP_ERR_ARG, "cp_online_gate_sweep: n_rows outside 1..2^31-1");
-    if (!logits || !expected_slot || !configs || !min_cosine || !scratch || !scores)
-        return fail(CP_ERR_ARG, "cp_online_gate_sweep: logits, expected_slot, configs, min_cosine, scratch and scores are required");
-    if ((uintptr_t)logits % 4 || (uintptr_t)expected_slot % 4 || (uintptr_t)configs % 4 || (uintptr_t)min_cosine % 4 ||
-        (uintptr_t)scratch % 4 || (uintptr_t)scores % 8 || (uintptr_t)commands % 4)
-        return fail(CP_ERR_ARG, "cp_online_gate_sweep: misaligned argument");
-    if (scratch_bytes < (size_t)n_rows * sizeof(OgRow)) return fail(CP_ERR_ARG, "cp_online_gate_sweep: scratch too small");
-    const int rows_per_block = 4 * OG_ROWS_PER_WAVE;
-    hipLaunchKernelGGL(og_rows_kernel, dim3((unsigned)((n_rows + rows_per_block - 1) / rows_per_block)), dim3(256), 0, (hipStream_t)stream,
-                       logits, (int)ldl, (long long)n_rows, (int)n_classes, (OgRow*)scratch);
-    CKL("og_rows_kernel");
-    OgSweepArgs a{};
-    a.rows = (const OgRow*)scratch; a.expected = expected_slot; a.configs = (const OgConfig*)configs; a.min_cosine = min_cosine;
-    a.n_rows = n_rows; a.n_configs = n_configs; a.K = n_classes; a.scores = (long long*)scores; a.commands = commands;
-    hipLaunchKernelGGL(og_sweep_kernel, dim3((n_configs + OG_SWEEP_WAVES - 1) / OG_SWEEP_WAVES), dim3(64 * OG_SWEEP_WAVES), 0,
-                       (hipStream_t)stream, a);
-    CKL("og_sweep_kernel");
-    return 0;
-}
+#include "online_api.cuh"             // the cp_online_* entries: host layer of the online decoders, the gate and the gate sweep

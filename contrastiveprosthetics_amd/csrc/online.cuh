@@ -1,7 +1,7 @@
 // Online grasp decoding (include/cpnative.h, cp_online_*): consecutive chunks of a live 2 kHz, 12-channel sEMG stream ->
 // one predicted and one voted class per 10 ms window.  Everything a stream carries from one push to the next -- IIR state,
 // RMS history, sample count, vote ring, class table, folded weights -- lives in the caller's workspace (OlState and the
-// carve of ol_carve in api.hip); nothing is process-global.
+// carve of ol_carve in online_api.cuh); nothing is process-global.
 //
 // A push is a chain of ten launches on one stream:
 //   ol_frontend_kernel   one workgroup; 12 threads run the float64 recurrences of preprocess_kernel (csrc/preprocess.cuh)

@@ -1,0 +1,1032 @@
+// Host layer of the online decoders (include/cpnative.h, cp_online_*): workspace layout, argument checks, launch chains and
+// the extern "C" entries of the folded, adaptive, multi-stream and adaptive multi-stream decoders, class enrolment, the
+// command gate and the gate sweep.  Host code only; api.hip includes it behind its own helpers (fail, CK, CKL, align256, fcK),
+// so the library stays one translation unit.  The four decoders share one workspace description (OlWS, ol_carve), one
+// parameter check, one set of front-end arguments, one folded chain and one unfolded weight copy; what an entry adds is its
+// name in the refusals and the kernels it launches.
+#pragma once
+#include <type_traits>
+
+static_assert(OL_MAXM == CP_ONLINE_MAX_WINDOWS && OL_MAXVOTE == CP_ONLINE_MAX_VOTE && OL_MAXK == CP_ONLINE_MAX_CLASSES, "online limits");
+static_assert(OLM_MAXS == CP_ONLINE_MULTI_MAX_STREAMS && OL_MAXK == 64, "multi-stream limits");
+static_assert(OLAM_STATS == CP_N_BN * 2 * OLA_F, "one stream's statistics: mu and v of every BatchNorm");
+
+// "<who>: <what>" as cp_last_error reports a refusal of entry (or family) `who`
+static int ol_fail(int code, const char* who, const char* what) {
+    char msg[256];
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    return fail(code, msg);
+}
+
+// f(T()) with T the compute type of `dtype`; the *_t functions below take that value as their first argument
+template <typename F>
+static int ol_dispatch(int dtype, F f) {
+    return dtype == CP_BF16 ? f(bf16_t()) : f(float());
+}
+
+// ---------------------------------------------------------------------------------------
+// the workspace of all four decoders.  Members a form does not have are not taken (and stay 0).  Three things hold for every
+// form: `state` is at offset 0 (cp_online_set_classes / cp_online_reset take an adaptive workspace, the multi entries a
+// multi-adaptive one); in the multi forms the OlmMeta array follows the states directly; every block starts 256-aligned, so
+// the total does not depend on the order of the blocks.
+// ---------------------------------------------------------------------------------------
+struct OlWS {
+    size_t state, meta, head, stats;     // per stream: OlState; multi: OlmMeta; adaptive: OlaHead and the float64 statistics
+    size_t c1w, c1b, c2w, c2b, fcw[CP_N_FC], fcb[CP_N_FC], pw, pb, gb;     // the weights once; gb (adaptive): gamma and beta
+    size_t X, C1, R2, H0, H1;            // `rows` rows; C1, R2 (adaptive): conv2's operand, rows (window, position), and its f32 output
+    size_t total;
+};
+// rows: windows of one push (single forms: max_windows; multi forms: max_rows)
+static OlWS ol_carve(int64_t rows, int dtype, int n_streams, bool adaptive, bool multi) {
+    const size_t es = dtype == CP_BF16 ? 2 : 4, S = (size_t)n_streams;
+    const size_t R = (size_t)((rows + 15) / 16 * 16);
+    OlWS w{};
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t r = o; o = align256(o + bytes); return r; };
+    w.state = take(S * sizeof(OlState));
+    if (multi) w.meta = take(S * sizeof(OlmMeta));
+    if (adaptive) {
+        w.head = take(S * sizeof(OlaHead));
+        w.stats = take(S * OLAM_STATS * 8);
+    }
+    w.c1w = take(64 * 3 * 4);
+    w.c1b = take(64 * 4);
+    w.c2w = take(64 * OL_CONV_K * es);
+    w.c2b = take((adaptive ? 1 : OL_C) * 64 * 4);          // folded: BN1's shift depends on the position
+    for (int i = 0; i < CP_N_FC; ++i) {
+        w.fcw[i] = take((size_t)512 * fcK(i) * es);
+        w.fcb[i] = take(512 * 4);
+    }
+    w.pw = take(CP_D_E * 512 * es);
+    w.pb = take(CP_D_E * 4);                              // adaptive: zeros (the tail adds a bias the unfolded projection does not have)
+    if (adaptive) w.gb = take((size_t)CP_N_BN * 2 * OLA_F * 4);
+    w.X = take(R * OL_C * 4);
+    if (adaptive) {
+        w.C1 = take(R * OL_C * OL_CONV_K * es);
+        w.R2 = take(R * OL_C * 64 * 4);
+    }
+    w.H0 = take(R * 768 * es);
+    w.H1 = take(R * 512 * es);
+    w.total = o;
+    return w;
+}
+
+// the view of stream s of an adaptive multi-stream workspace: its state, head and statistics, the shared weights and buffers
+static OlWS ol_stream(OlWS w, int s) {
+    w.state += (size_t)s * sizeof(OlState);
+    w.head += (size_t)s * sizeof(OlaHead);
+    w.stats += (size_t)s * OLAM_STATS * 8;
+    return w;
+}
+
+static int ol_check_config(const cp_online_config* c, void* ws) {
+    if (!c || !ws) return fail(CP_ERR_ARG, "cp_online: config and workspace are required");
+    if (c->dtype != CP_F32 && c->dtype != CP_BF16) return fail(CP_ERR_ARG, "cp_online: dtype must be CP_F32 or CP_BF16 (no 8-bit path)");
+    if (c->max_windows < 1 || c->max_windows > CP_ONLINE_MAX_WINDOWS) return fail(CP_ERR_ARG, "cp_online: max_windows outside 1..256");
+    if (c->vote < 1 || c->vote > CP_ONLINE_MAX_VOTE) return fail(CP_ERR_ARG, "cp_online: vote outside 1..256");
+    if (c->phase < 0 || c->phase >= CP_ONLINE_STRIDE) return fail(CP_ERR_ARG, "cp_online: phase outside 0..19");
+    if (c->n_coef < 2 || c->n_coef > OL_MAXCOEF || c->a[0] == 0.0) return fail(CP_ERR_ARG, "cp_online: IIR coefficients");
+    if ((uintptr_t)ws % 256) return fail(CP_ERR_ARG, "cp_online: workspace not 256-byte aligned");
+    return 0;
+}
+
+// the single-stream forms.  An adaptive workspace too small even for the folded form is refused in the folded form's words.
+static int ol_check(const cp_online_config* c, void* ws, size_t ws_bytes, bool adaptive, OlWS* out) {
+    if (int e = ol_check_config(c, ws)) return e;
+    *out = ol_carve(c->max_windows, c->dtype, 1, false, false);
+    if (ws_bytes < out->total) return fail(CP_ERR_WORKSPACE, "cp_online: workspace too small");
+    if (!adaptive) return 0;
+    *out = ol_carve(c->max_windows, c->dtype, 1, true, false);
+    if (ws_bytes < out->total) return fail(CP_ERR_WORKSPACE, "cp_online_adapt: workspace too small");
+    return 0;
+}
+
+// the multi-stream forms; out: stream 0's view
+static int olm_check(const cp_online_config* c, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes, bool adaptive, OlWS* out) {
+    const char* who = adaptive ? "cp_online_multi_adapt" : "cp_online_multi";
+    if (n_streams < 1 || n_streams > CP_ONLINE_MULTI_MAX_STREAMS) return ol_fail(CP_ERR_ARG, who, "n_streams outside 1..256");
+    if (max_rows < 1 || max_rows > CP_ONLINE_MULTI_MAX_ROWS) return ol_fail(CP_ERR_ARG, who, "max_rows outside 1..65536");
+    if (int e = ol_check_config(c, ws)) return e;
+    *out = ol_carve(max_rows, c->dtype, n_streams, adaptive, true);
+    if (ws_bytes < out->total) return ol_fail(CP_ERR_WORKSPACE, who, "workspace too small");
+    return 0;
+}
+
+static int ol_check_index(const char* who, int32_t index, int32_t n_streams) {
+    if (index < 0 || index >= n_streams) return ol_fail(CP_ERR_ARG, who, "stream index outside 0..n_streams-1");
+    return 0;
+}
+
+// an entry of the adaptive multi-stream form that works on one stream; out: that stream's view
+static int olam_check_stream(const char* who, const cp_online_config* c, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                             int32_t index, OlWS* out) {
+    if (int e = olm_check(c, n_streams, max_rows, ws, ws_bytes, true, out)) return e;
+    if (int e = ol_check_index(who, index, n_streams)) return e;
+    *out = ol_stream(*out, index);
+    return 0;
+}
+
+// the model a prepare entry takes.  running_required: the folded forms (stock BatchNorm only); else bn may be NULL
+static int ol_check_params(const char* who, const cp_params* p, const cp_bn_buffers* bn, bool running_required) {
+    const char* stock = "stock BatchNorm with running statistics required (AdaBN has none)";
+    bool layers = p && p->conv1_w && p->conv1_b && p->conv2_w && p->conv2_b && p->last_w;
+    for (int i = 0; layers && i < CP_N_FC; ++i) layers = p->fc_w[i] && p->fc_b[i];
+    if (!layers) return ol_fail(CP_ERR_ARG, who, "parameters");
+    if (running_required && !bn) return ol_fail(CP_ERR_ARG, who, stock);
+    for (int l = 0; l < CP_N_BN; ++l) {
+        if (!p->bn_g[l] || !p->bn_b[l]) return ol_fail(CP_ERR_ARG, who, running_required ? stock : "parameters");
+        if (bn && (!bn->running_mean[l] || !bn->running_var[l])) return ol_fail(CP_ERR_ARG, who, running_required ? stock : "running statistics");
+    }
+    return 0;
+}
+
+// what the pushes of the single-stream forms check alike; n == 0 is a valid empty call (the caller returns 0)
+static int ol_check_push(const char* who, const cp_online_config* c, int64_t n, const float* raw, const float* mean_std,
+                         const int32_t* pred, const int32_t* voted) {
+    if (n < 0 || n > (int64_t)CP_ONLINE_STRIDE * c->max_windows) return ol_fail(CP_ERR_ARG, who, "a push takes at most 20 * max_windows samples");
+    if (n == 0) return 0;
+    if (!raw || !mean_std || !pred || !voted) return ol_fail(CP_ERR_ARG, who, "raw, mean_std, pred and voted are required");
+    if ((uintptr_t)raw % 4 || (uintptr_t)mean_std % 4) return ol_fail(CP_ERR_ARG, who, "misaligned input");
+    return 0;
+}
+
+// the same for the multi-stream forms; total_samples == 0 is a valid empty call
+static int olm_check_push(const char* who, int32_t max_rows, const float* raw, const int32_t* counts, int64_t total_samples,
+                          int32_t total_windows, const float* mean_std, const int32_t* pred, const int32_t* voted) {
+    if (total_windows < 0 || total_windows > max_rows) return ol_fail(CP_ERR_ARG, who, "total_windows outside 0..max_rows");
+    if (total_samples < 0) return ol_fail(CP_ERR_ARG, who, "negative total_samples");
+    if (total_samples == 0) return 0;
+    if (!raw || !counts || !mean_std) return ol_fail(CP_ERR_ARG, who, "raw, counts and mean_std are required");
+    if (total_windows > 0 && (!pred || !voted)) return ol_fail(CP_ERR_ARG, who, "pred and voted are required");
+    if ((uintptr_t)raw % 4 || (uintptr_t)mean_std % 4 || (uintptr_t)counts % 4) return ol_fail(CP_ERR_ARG, who, "misaligned input");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// pieces of the launch chains
+// ---------------------------------------------------------------------------------------
+// what every front end takes from the configuration: the IIR normalised to a[0] == 1, phase and gain
+static OlFrontArgs ol_front_args(const cp_online_config* c) {
+    OlFrontArgs fa{};
+    fa.n_coef = c->n_coef; fa.phase = c->phase; fa.gain = 1024.f;            // code/load.py:105, 2**10
+    for (int i = 0; i < c->n_coef; ++i) { fa.b[i] = c->b[i] / c->a[0]; fa.a[i] = c->a[i] / c->a[0]; }
+    return fa;
+}
+
+static int ol_launch_frontend(const cp_online_config* c, OlState* state, float* X, const float* raw, int64_t n, const float* mean_std,
+                              float* windows, hipStream_t st) {
+    OlFrontArgs fa = ol_front_args(c);
+    fa.raw = raw; fa.n = n; fa.st = state; fa.X = X; fa.windows = windows; fa.mean_std = mean_std;
+    if (c->n_coef == 9) hipLaunchKernelGGL((ol_frontend_kernel<9>), dim3(1), dim3(256), 0, st, fa);
+    else hipLaunchKernelGGL((ol_frontend_kernel<0>), dim3(1), dim3(256), 0, st, fa);
+    CKL("ol_frontend_kernel");
+    return 0;
+}
+
+static int olm_launch_frontend(const cp_online_config* c, int n_streams, unsigned char* base, const OlWS& w, const float* raw,
+                               const int32_t* counts, int64_t total, int rows, const float* mean_std, float* windows, hipStream_t st) {
+    OlmFrontArgs fa{};
+    fa.f = ol_front_args(c);
+    fa.f.raw = raw; fa.f.X = (float*)(base + w.X); fa.f.windows = windows; fa.f.mean_std = mean_std;
+    fa.states = (OlState*)(base + w.state); fa.meta = (OlmMeta*)(base + w.meta); fa.counts = counts; fa.total_samples = total;
+    fa.rows = rows; fa.max_m = c->max_windows;
+    if (c->n_coef == 9) hipLaunchKernelGGL((olm_frontend_kernel<9>), dim3(n_streams), dim3(256), 0, st, fa);
+    else hipLaunchKernelGGL((olm_frontend_kernel<0>), dim3(n_streams), dim3(256), 0, st, fa);
+    CKL("olm_frontend_kernel");
+    return 0;
+}
+
+// The arguments of layer i of the stored model, reading `in` and writing `out`.  i = 0: conv1 + conv2 over the windows `in`
+// (folded form only); 1..7: fc1..fc7, folded or unfolded; OL_PROJ: the projection as the tails and ole_accumulate take it
+constexpr int OL_PROJ = CP_N_FC + 1;
+static OlLayerArgs ol_layer_args(unsigned char* base, const OlWS& w, int i, const OlState* st, const void* in, void* out) {
+    OlLayerArgs l{};
+    l.st = st; l.out = out;
+    if (i == 0) {
+        l.x = (const float*)in; l.c1w = (const float*)(base + w.c1w); l.c1b = (const float*)(base + w.c1b);
+        l.w = base + w.c2w; l.bias = (const float*)(base + w.c2b); l.K = OL_CONV_K; l.F = 64; l.ldo = 768; l.out_pos = 64;
+    } else if (i < OL_PROJ) {
+        l.act = in; l.w = base + w.fcw[i - 1]; l.bias = (const float*)(base + w.fcb[i - 1]); l.K = fcK(i - 1); l.F = 512; l.ldo = 512;
+    } else {
+        l.act = in; l.w = base + w.pw; l.bias = (const float*)(base + w.pb); l.K = 512; l.F = CP_D_E;
+    }
+    return l;
+}
+
+// The folded encoder over the windows x: conv2 into h0, then fc1..fc7, h0 -> h1 -> h0 ...: fc7 leaves its output in h1.
+// launch(args, conv) enqueues one layer; conv is std::true_type for conv2
+template <typename Launch>
+static int ol_folded_chain(unsigned char* base, const OlWS& w, const OlState* st, const float* x, unsigned char* h0, unsigned char* h1,
+                           Launch launch) {
+    if (int e = launch(ol_layer_args(base, w, 0, st, x, h0), std::true_type())) return e;
+    for (int i = 0; i < CP_N_FC; ++i)
+        if (int e = launch(ol_layer_args(base, w, i + 1, st, i % 2 == 0 ? h0 : h1, i % 2 == 0 ? h1 : h0), std::false_type())) return e;
+    return 0;
+}
+
+template <typename T>
+static int ol_launch_tail(T, const cp_online_config* c, unsigned char* base, const OlWS& w, int32_t* pred, int32_t* voted, float* logits,
+                          hipStream_t st) {
+    OlTailArgs ta{};
+    ta.st = (OlState*)(base + w.state);
+    ta.proj = ol_layer_args(base, w, OL_PROJ, ta.st, base + w.H1, nullptr);
+    ta.vote = c->vote; ta.pred = pred; ta.voted = voted; ta.logits = logits;
+    hipLaunchKernelGGL((ol_tail_kernel<T>), dim3(1), dim3(OL_THREADS), 0, st, ta);
+    CKL("ol_tail_kernel");
+    return 0;
+}
+
+template <typename T>
+static int olm_launch_tail(T, const cp_online_config* c, int n_streams, unsigned char* base, const OlWS& w, int32_t* pred, int32_t* voted,
+                           float* logits, hipStream_t st) {
+    OlmTailArgs ta{};
+    ta.proj = ol_layer_args(base, w, OL_PROJ, nullptr, base + w.H1, nullptr);
+    ta.states = (OlState*)(base + w.state); ta.meta = (const OlmMeta*)(base + w.meta);
+    ta.vote = c->vote; ta.pred = pred; ta.voted = voted; ta.logits = logits;
+    hipLaunchKernelGGL((olm_tail_kernel<T>), dim3(n_streams), dim3(OL_THREADS), 0, st, ta);
+    CKL("olm_tail_kernel");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// online grasp decoding (csrc/online.cuh): per-stream state, folded weights and activations in the caller's workspace
+// ---------------------------------------------------------------------------------------
+extern "C" size_t cp_online_workspace_bytes(int32_t max_windows_per_push, int32_t dtype) {
+    if (max_windows_per_push < 1) max_windows_per_push = 1;
+    return ol_carve(max_windows_per_push, dtype, 1, false, false).total;
+}
+
+template <typename T>
+static int online_prepare_t(T, const cp_params* p, const cp_bn_buffers* bn, float eps, unsigned char* base, const OlWS& w, hipStream_t st) {
+    OlFoldArgs f{};
+    f.eps = eps;
+    auto set_bn = [&](int l) { f.g = p->bn_g[l]; f.beta = p->bn_b[l]; f.mean = bn->running_mean[l]; f.var = bn->running_var[l]; };
+    set_bn(0);                                            // BN1 -> conv2 (and conv1 copied as it is)
+    f.W = p->conv2_w; f.b = p->conv2_b; f.Wd = base + w.c2w; f.bd = (float*)(base + w.c2b); f.K = OL_CONV_K; f.mode = 2;
+    f.c1w_src = p->conv1_w; f.c1b_src = p->conv1_b; f.c1w = (float*)(base + w.c1w); f.c1b = (float*)(base + w.c1b);
+    hipLaunchKernelGGL((ol_fold_kernel<T>), dim3(64), dim3(256), 0, st, f);
+    CKL("ol_fold_kernel");
+    for (int i = 0; i < CP_N_FC; ++i) {                   // BN(i+1) -> fc(i+1); fc1's columns to the position-major layout
+        set_bn(i + 1);
+        f.W = p->fc_w[i]; f.b = p->fc_b[i]; f.Wd = base + w.fcw[i]; f.bd = (float*)(base + w.fcb[i]); f.K = fcK(i); f.mode = i == 0 ? 1 : 0;
+        hipLaunchKernelGGL((ol_fold_kernel<T>), dim3(512), dim3(256), 0, st, f);
+        CKL("ol_fold_kernel");
+    }
+    set_bn(CP_N_BN - 1);                                  // BN9 -> projection, which gains a bias
+    f.W = p->last_w; f.b = nullptr; f.Wd = base + w.pw; f.bd = (float*)(base + w.pb); f.K = 512; f.mode = 0;
+    hipLaunchKernelGGL((ol_fold_kernel<T>), dim3(CP_D_E), dim3(256), 0, st, f);
+    CKL("ol_fold_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_prepare(const cp_online_config* cfg, const cp_params* p, const cp_bn_buffers* bn, float bn_eps, void* ws,
+                                 size_t ws_bytes, void* stream) {
+    OlWS w;
+    if (int e = ol_check(cfg, ws, ws_bytes, false, &w)) return e;
+    if (int e = ol_check_params("cp_online_prepare", p, bn, true)) return e;
+    return ol_dispatch(cfg->dtype, [&](auto t) { return online_prepare_t(t, p, bn, bn_eps, (unsigned char*)ws, w, (hipStream_t)stream); });
+}
+
+extern "C" int cp_online_set_classes(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* table, const int32_t* ids,
+                                     int32_t n_classes, void* stream) {
+    OlWS w;
+    if (int e = ol_check(cfg, ws, ws_bytes, false, &w)) return e;
+    if (!table || !ids || n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return fail(CP_ERR_ARG, "cp_online_set_classes: 1..64 classes");
+    hipLaunchKernelGGL(ol_set_classes_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (OlState*)((unsigned char*)ws + w.state), table,
+                       ids, (int)n_classes);
+    CKL("ol_set_classes_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_reset(const cp_online_config* cfg, void* ws, size_t ws_bytes, void* stream) {
+    OlWS w;
+    if (int e = ol_check(cfg, ws, ws_bytes, false, &w)) return e;
+    CK(hipMemsetAsync((unsigned char*)ws + w.state, 0, offsetof(OlState, K), (hipStream_t)stream));
+    return 0;
+}
+
+template <typename T>
+static int online_push_t(T t, const cp_online_config* c, unsigned char* base, const OlWS& w, const float* raw, int64_t n,
+                         const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, hipStream_t st) {
+    OlState* state = (OlState*)(base + w.state);
+    if (int e = ol_launch_frontend(c, state, (float*)(base + w.X), raw, n, mean_std, windows, st)) return e;
+    auto layer = [&](const OlLayerArgs& la, auto conv) {
+        constexpr bool CONV = decltype(conv)::value;
+        hipLaunchKernelGGL((ol_layer_kernel<T, CONV>), CONV ? dim3(4, OL_C) : dim3(512 / 16), dim3(OL_THREADS), 0, st, la);
+        CKL(CONV ? "ol_layer_kernel<conv>" : "ol_layer_kernel<fc>");
+        return 0;
+    };
+    if (int e = ol_folded_chain(base, w, state, (const float*)(base + w.X), base + w.H0, base + w.H1, layer)) return e;
+    return ol_launch_tail(t, c, base, w, pred, voted, logits, st);
+}
+
+extern "C" int cp_online_push(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* raw, int64_t n_samples,
+                              const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, void* stream) {
+    OlWS w;
+    if (int e = ol_check(cfg, ws, ws_bytes, false, &w)) return e;
+    if (int e = ol_check_push("cp_online_push", cfg, n_samples, raw, mean_std, pred, voted)) return e;
+    if (n_samples == 0) return 0;
+    return ol_dispatch(cfg->dtype, [&](auto t) {
+        return online_push_t(t, cfg, (unsigned char*)ws, w, raw, n_samples, mean_std, pred, voted, logits, windows, (hipStream_t)stream);
+    });
+}
+
+// ---------------------------------------------------------------------------------------
+// adaptive online decoding (csrc/online_adapt.cuh): BatchNorm unfolded, float64 statistics per stream in the workspace
+// ---------------------------------------------------------------------------------------
+extern "C" size_t cp_online_adapt_workspace_bytes(int32_t max_windows_per_push, int32_t dtype) {
+    if (max_windows_per_push < 1) max_windows_per_push = 1;
+    return ol_carve(max_windows_per_push, dtype, 1, true, false).total;
+}
+
+// BatchNorm l of the stream whose view w is
+static OlaBn ola_bn(unsigned char* base, const OlWS& w, int l, int mode, double* acc, int first, int last) {
+    OlaBn b{};
+    b.stats = (double*)(base + w.stats) + (size_t)l * 2 * OLA_F;
+    b.acc = acc ? acc + (size_t)l * 3 * OLA_F : nullptr;
+    b.gamma = (const float*)(base + w.gb) + (size_t)l * 2 * OLA_F;
+    b.beta = b.gamma + OLA_F;
+    b.head = (const OlaHead*)(base + w.head);
+    b.mode = mode; b.first = first; b.last = last;
+    return b;
+}
+
+// the unfolded weights of conv2, fc1..fc7 and the projection (zero bias) into the workspace, in the layouts the folded form uses
+template <typename T>
+static int ola_copy_weights(T, const cp_params* p, unsigned char* base, const OlWS& w, hipStream_t st) {
+    OlaCopyArgs f{};
+    f.W = p->conv2_w; f.b = p->conv2_b; f.Wd = base + w.c2w; f.bd = (float*)(base + w.c2b); f.K = OL_CONV_K; f.mode = 2;
+    hipLaunchKernelGGL((ola_copy_kernel<T>), dim3(64), dim3(256), 0, st, f);
+    CKL("ola_copy_kernel");
+    for (int i = 0; i < CP_N_FC; ++i) {
+        f.W = p->fc_w[i]; f.b = p->fc_b[i]; f.Wd = base + w.fcw[i]; f.bd = (float*)(base + w.fcb[i]); f.K = fcK(i); f.mode = i == 0 ? 1 : 0;
+        hipLaunchKernelGGL((ola_copy_kernel<T>), dim3(512), dim3(256), 0, st, f);
+        CKL("ola_copy_kernel");
+    }
+    f.W = p->last_w; f.b = nullptr; f.Wd = base + w.pw; f.bd = (float*)(base + w.pb); f.K = 512; f.mode = 0;
+    hipLaunchKernelGGL((ola_copy_kernel<T>), dim3(CP_D_E), dim3(256), 0, st, f);
+    CKL("ola_copy_kernel");
+    return 0;
+}
+
+// what both adaptive prepares hand their init kernel: gamma, beta, the running statistics if there are any, conv1 and where they go
+template <typename InitArgs>
+static void ola_init_args(InitArgs& ia, const cp_params* p, const cp_bn_buffers* bn, float eps, unsigned char* base, const OlWS& w) {
+    for (int l = 0; l < CP_N_BN; ++l) {
+        ia.g[l] = p->bn_g[l]; ia.beta[l] = p->bn_b[l];
+        ia.mean[l] = bn ? bn->running_mean[l] : nullptr; ia.var[l] = bn ? bn->running_var[l] : nullptr;
+    }
+    ia.c1w = p->conv1_w; ia.c1b = p->conv1_b; ia.gb = (float*)(base + w.gb); ia.stats = (double*)(base + w.stats);
+    ia.c1w_d = (float*)(base + w.c1w); ia.c1b_d = (float*)(base + w.c1b);
+    ia.eps = eps;
+}
+
+extern "C" int cp_online_adapt_prepare(const cp_online_config* cfg, const cp_params* p, const cp_bn_buffers* bn, float bn_eps,
+                                       double alpha, void* ws, size_t ws_bytes, void* stream) {
+    if (!(alpha >= 0.0 && alpha < 1.0)) return fail(CP_ERR_ARG, "cp_online_adapt_prepare: alpha outside [0, 1)");
+    if (!(bn_eps > 0.f)) return fail(CP_ERR_ARG, "cp_online_adapt_prepare: bn_eps must be positive");
+    OlWS w;
+    if (int e = ol_check(cfg, ws, ws_bytes, true, &w)) return e;
+    if (int e = ol_check_params("cp_online_adapt_prepare", p, bn, false)) return e;
+    unsigned char* base = (unsigned char*)ws;
+    OlaBnInitArgs ia{};
+    ola_init_args(ia, p, bn, bn_eps, base, w);
+    ia.head = (OlaHead*)(base + w.head); ia.alpha = alpha;
+    hipLaunchKernelGGL(ola_bn_init_kernel, dim3(CP_N_BN), dim3(512), 0, (hipStream_t)stream, ia);
+    CKL("ola_bn_init_kernel");
+    return ol_dispatch(cfg->dtype, [&](auto t) { return ola_copy_weights(t, p, base, w, (hipStream_t)stream); });
+}
+
+// conv2 GEMM: row-tile groups per feature tile for `rows` rows
+static int ola_conv2_groups(int64_t rows) {
+    const int64_t tiles = (rows + 15) / 16;
+    return (int)(tiles < 16 ? tiles : 16);
+}
+
+// BN1 -> conv2 -> BN2 for M windows (m_fixed < 0: the push's count; max_rows bounds the row-tile groups)
+template <typename T>
+static int ola_conv_chain(T, unsigned char* base, const OlWS& w, const OlState* state, const float* x, int m_fixed, int64_t max_rows,
+                          void* c1, float* r2, void* out, const OlaBn& bn1, const OlaBn& bn2, hipStream_t st) {
+    OlaConvBnArgs cb{};
+    cb.x = x; cb.c1w = (const float*)(base + w.c1w); cb.c1b = (const float*)(base + w.c1b); cb.out = c1; cb.st = state;
+    cb.m_fixed = m_fixed; cb.conv1 = 1; cb.bn = bn1;
+    hipLaunchKernelGGL((ola_conv_bn_kernel<T>), dim3(1), dim3(64), 0, st, cb);
+    CKL("ola_conv_bn_kernel<BN1>");
+    OlaGemmArgs g{};
+    g.l.act = c1; g.l.w = base + w.c2w; g.l.bias = (const float*)(base + w.c2b); g.l.out = r2; g.l.st = state; g.l.K = OL_CONV_K;
+    g.l.F = 64; g.l.ldo = 64; g.m_fixed = m_fixed; g.rows_per_window = OL_C;
+    hipLaunchKernelGGL((ola_gemm_kernel<T>), dim3(64 / 16, ola_conv2_groups(max_rows * OL_C)), dim3(OL_THREADS), 0, st, g);
+    CKL("ola_gemm_kernel");
+    cb.pre = r2; cb.out = out; cb.conv1 = 0; cb.bn = bn2;
+    hipLaunchKernelGGL((ola_conv_bn_kernel<T>), dim3(1), dim3(64), 0, st, cb);
+    CKL("ola_conv_bn_kernel<BN2>");
+    return 0;
+}
+
+// fc layer i: act [M][K] -> out [M][512] (normalised; nothing under OLA_ACC)
+template <typename T>
+static int ola_fc(T, unsigned char* base, const OlWS& w, const OlState* state, int i, const void* act, void* out, int m_fixed,
+                  const OlaBn& bn, hipStream_t st) {
+    OlaGemmArgs g{};
+    g.l = ol_layer_args(base, w, i + 1, state, act, out);
+    g.m_fixed = m_fixed; g.rows_per_window = 1; g.bn = bn;
+    hipLaunchKernelGGL((ola_fc_kernel<T>), dim3(512 / 16), dim3(OL_THREADS), 0, st, g);
+    CKL("ola_fc_kernel");
+    return 0;
+}
+
+// The unfolded encoder over the windows x with every BatchNorm in `mode` (OLA_TRACK: a push; OLA_FROZEN: enrolment):
+// BN1 -> conv2 -> BN2 into h0, then fc1..fc7, h0 -> h1 -> h0 ...: fc7 leaves its output in h1
+template <typename T>
+static int ola_chain(T t, unsigned char* base, const OlWS& w, const float* x, int m_fixed, int64_t max_rows, int mode, unsigned char* c1,
+                     unsigned char* r2, unsigned char* h0, unsigned char* h1, hipStream_t st) {
+    const OlState* state = (const OlState*)(base + w.state);
+    auto bn = [&](int l) { return ola_bn(base, w, l, mode, nullptr, 0, 0); };
+    if (int e = ola_conv_chain(t, base, w, state, x, m_fixed, max_rows, c1, (float*)r2, h0, bn(0), bn(1), st)) return e;
+    for (int i = 0; i < CP_N_FC; ++i)
+        if (int e = ola_fc(t, base, w, state, i, i % 2 == 0 ? h0 : h1, i % 2 == 0 ? h1 : h0, m_fixed, bn(i + 2), st)) return e;
+    return 0;
+}
+
+template <typename T>
+static int online_adapt_push_t(T t, const cp_online_config* c, unsigned char* base, const OlWS& w, const float* raw, int64_t n,
+                               const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, hipStream_t st) {
+    if (int e = ol_launch_frontend(c, (OlState*)(base + w.state), (float*)(base + w.X), raw, n, mean_std, windows, st)) return e;
+    if (int e = ola_chain(t, base, w, (const float*)(base + w.X), -1, c->max_windows, OLA_TRACK, base + w.C1, base + w.R2, base + w.H0,
+                          base + w.H1, st))
+        return e;
+    return ol_launch_tail(t, c, base, w, pred, voted, logits, st);
+}
+
+extern "C" int cp_online_adapt_push(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* raw, int64_t n_samples,
+                                    const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, void* stream) {
+    OlWS w;
+    if (int e = ol_check(cfg, ws, ws_bytes, true, &w)) return e;
+    if (int e = ol_check_push("cp_online_adapt_push", cfg, n_samples, raw, mean_std, pred, voted)) return e;
+    if (n_samples == 0) return 0;
+    return ol_dispatch(cfg->dtype, [&](auto t) {
+        return online_adapt_push_t(t, cfg, (unsigned char*)ws, w, raw, n_samples, mean_std, pred, voted, logits, windows, (hipStream_t)stream);
+    });
+}
+
+// calibration scratch: the normalised activations of all windows (two buffers), one chunk of conv2 operand and output, and
+// the float64 accumulators
+struct OlaCalib {
+    size_t A0, A1, C1, R2, acc, total;
+};
+static OlaCalib ola_calib_carve(int64_t n_windows, int dtype) {
+    const size_t es = dtype == CP_BF16 ? 2 : 4;
+    OlaCalib c{};
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t r = o; o = align256(o + bytes); return r; };
+    c.A0 = take((size_t)n_windows * 768 * es);
+    c.A1 = take((size_t)n_windows * 512 * es);
+    c.C1 = take((size_t)OL_MAXM * OL_C * OL_CONV_K * es);
+    c.R2 = take((size_t)OL_MAXM * OL_C * 64 * 4);
+    c.acc = take((size_t)CP_N_BN * 3 * OLA_F * 8);
+    c.total = o;
+    return c;
+}
+
+extern "C" size_t cp_online_adapt_calibrate_scratch_bytes(int64_t n_windows, int32_t dtype) {
+    if (n_windows < 1) n_windows = 1;
+    return ola_calib_carve(n_windows, dtype).total;
+}
+
+template <typename T>
+static int online_adapt_calibrate_t(T t, unsigned char* base, const OlWS& w, const float* x, int64_t N, unsigned char* sc,
+                                    const OlaCalib& k, hipStream_t st) {
+    const OlState* state = (const OlState*)(base + w.state);
+    const size_t es = sizeof(T);
+    double* acc = (double*)(sc + k.acc);
+    const int64_t nch = (N + OL_MAXM - 1) / OL_MAXM;
+    auto rows_of = [&](int64_t ci) { return (int)(ci + 1 < nch ? OL_MAXM : N - ci * OL_MAXM); };
+    // BN1: conv1 of all windows, one launch
+    OlaConvBnArgs cb{};
+    cb.x = x; cb.c1w = (const float*)(base + w.c1w); cb.c1b = (const float*)(base + w.c1b); cb.st = state;
+    cb.m_fixed = (int)N; cb.conv1 = 1; cb.bn = ola_bn(base, w, 0, OLA_ACC, acc, 1, 1);
+    hipLaunchKernelGGL((ola_conv_bn_kernel<T>), dim3(1), dim3(64), 0, st, cb);
+    CKL("ola_conv_bn_kernel<BN1>");
+    // BN2: per chunk BN1 (frozen) -> conv2 -> accumulate; then again with BN2 frozen into A0
+    const OlaBn bn1 = ola_bn(base, w, 0, OLA_FROZEN, nullptr, 0, 0);
+    for (int pass = 0; pass < 2; ++pass)
+        for (int64_t ci = 0; ci < nch; ++ci) {
+            const OlaBn bn2 = pass == 0 ? ola_bn(base, w, 1, OLA_ACC, acc, ci == 0, ci + 1 == nch) : ola_bn(base, w, 1, OLA_FROZEN, nullptr, 0, 0);
+            if (int e = ola_conv_chain(t, base, w, state, x + ci * OL_MAXM * OL_C, rows_of(ci), OL_MAXM, sc + k.C1, (float*)(sc + k.R2),
+                                       sc + k.A0 + (size_t)ci * OL_MAXM * 768 * es, bn1, bn2, st))
+                return e;
+        }
+    // fc1..fc7: accumulate over the chunks, then (but for fc7) normalise them into the other buffer
+    for (int i = 0; i < CP_N_FC; ++i) {
+        const int K = fcK(i);
+        unsigned char* in = sc + (i % 2 == 0 ? k.A0 : k.A1);
+        unsigned char* out = sc + (i % 2 == 0 ? k.A1 : k.A0);
+        for (int pass = 0; pass < (i + 1 < CP_N_FC ? 2 : 1); ++pass)
+            for (int64_t ci = 0; ci < nch; ++ci) {
+                const OlaBn bn = pass == 0 ? ola_bn(base, w, i + 2, OLA_ACC, acc, ci == 0, ci + 1 == nch)
+                                           : ola_bn(base, w, i + 2, OLA_FROZEN, nullptr, 0, 0);
+                if (int e = ola_fc(t, base, w, state, i, in + (size_t)ci * OL_MAXM * K * es, out + (size_t)ci * OL_MAXM * 512 * es,
+                                   rows_of(ci), bn, st))
+                    return e;
+            }
+    }
+    return 0;
+}
+
+// both calibrate entries: check_ws(&w) checks the entry's workspace arguments and gives the view of the stream to calibrate
+template <typename CheckWs>
+static int ola_calibrate(const char* who, const cp_online_config* cfg, CheckWs check_ws, void* ws, const float* windows, int64_t n_windows,
+                         void* scratch, size_t scratch_bytes, void* stream) {
+    if (n_windows < 2) return ol_fail(CP_ERR_ARG, who, "calibration takes at least 2 windows");
+    if (n_windows > (int64_t)1 << 24) return ol_fail(CP_ERR_ARG, who, "at most 2**24 windows");
+    OlWS w;
+    if (int e = check_ws(&w)) return e;
+    if (!windows || !scratch) return ol_fail(CP_ERR_ARG, who, "windows and scratch are required");
+    if ((uintptr_t)windows % 4 || (uintptr_t)scratch % 256) return ol_fail(CP_ERR_ARG, who, "misaligned input or scratch");
+    const OlaCalib k = ola_calib_carve(n_windows, cfg->dtype);
+    if (scratch_bytes < k.total) return ol_fail(CP_ERR_WORKSPACE, who, "scratch too small");
+    return ol_dispatch(cfg->dtype, [&](auto t) {
+        return online_adapt_calibrate_t(t, (unsigned char*)ws, w, windows, n_windows, (unsigned char*)scratch, k, (hipStream_t)stream);
+    });
+}
+
+extern "C" int cp_online_adapt_calibrate(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* windows,
+                                         int64_t n_windows, void* scratch, size_t scratch_bytes, void* stream) {
+    return ola_calibrate("cp_online_adapt_calibrate", cfg, [&](OlWS* w) { return ol_check(cfg, ws, ws_bytes, true, w); }, ws, windows,
+                         n_windows, scratch, scratch_bytes, stream);
+}
+
+extern "C" int cp_online_adapt_statistics(const cp_online_config* cfg, void* ws, size_t ws_bytes, double* out, void* stream) {
+    OlWS w;
+    if (int e = ol_check(cfg, ws, ws_bytes, true, &w)) return e;
+    if (!out) return fail(CP_ERR_ARG, "cp_online_adapt_statistics: out is required");
+    CK(hipMemcpyAsync(out, (unsigned char*)ws + w.stats, (size_t)OLAM_STATS * 8, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// multi-stream online decoding (csrc/online_multi.cuh): S states, the folded weights once, rows of all streams packed
+// ---------------------------------------------------------------------------------------
+extern "C" size_t cp_online_multi_workspace_bytes(int32_t n_streams, int32_t max_rows, int32_t dtype) {
+    if (n_streams < 1) n_streams = 1;
+    if (max_rows < 1) max_rows = 1;
+    return ol_carve(max_rows, dtype, n_streams, false, true).total;
+}
+
+extern "C" int cp_online_multi_prepare(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, const cp_params* p,
+                                       const cp_bn_buffers* bn, float bn_eps, void* ws, size_t ws_bytes, void* stream) {
+    OlWS w;
+    if (int e = olm_check(cfg, n_streams, max_rows, ws, ws_bytes, false, &w)) return e;
+    if (int e = ol_check_params("cp_online_multi_prepare", p, bn, true)) return e;
+    return ol_dispatch(cfg->dtype, [&](auto t) { return online_prepare_t(t, p, bn, bn_eps, (unsigned char*)ws, w, (hipStream_t)stream); });
+}
+
+extern "C" int cp_online_multi_set_classes(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                           int32_t index, const float* table, const int32_t* ids, int32_t n_classes, void* stream) {
+    OlWS w;
+    if (int e = olm_check(cfg, n_streams, max_rows, ws, ws_bytes, false, &w)) return e;
+    if (int e = ol_check_index("cp_online_multi_set_classes", index, n_streams)) return e;
+    if (!table || !ids || n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return fail(CP_ERR_ARG, "cp_online_multi_set_classes: 1..64 classes");
+    OlState* states = (OlState*)((unsigned char*)ws + w.state);
+    hipLaunchKernelGGL(ol_set_classes_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, states + index, table, ids, (int)n_classes);
+    CKL("ol_set_classes_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_multi_reset(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                     int32_t index, void* stream) {
+    OlWS w;
+    if (int e = olm_check(cfg, n_streams, max_rows, ws, ws_bytes, false, &w)) return e;
+    if (index < -1 || index >= n_streams) return fail(CP_ERR_ARG, "cp_online_multi_reset: stream index outside -1..n_streams-1");
+    OlState* states = (OlState*)((unsigned char*)ws + w.state);
+    hipLaunchKernelGGL(olm_reset_kernel, dim3(index < 0 ? n_streams : 1), dim3(256), 0, (hipStream_t)stream, states, index < 0 ? 0 : index);
+    CKL("olm_reset_kernel");
+    return 0;
+}
+
+// row blocks of an encoder launch with `ftiles` workgroups per row block: about OLM_TARGET_WG workgroups when there are rows
+static void olm_row_blocks(int rows, int ftiles, int* blocks, int* tiles_per_block) {
+    const int tiles = (rows + 15) / 16;
+    int b = (OLM_TARGET_WG + ftiles - 1) / ftiles;
+    if (b > tiles) b = tiles;
+    *tiles_per_block = (tiles + b - 1) / b;
+    *blocks = (tiles + *tiles_per_block - 1) / *tiles_per_block;
+}
+
+template <typename T>
+static int online_multi_push_t(T t, const cp_online_config* c, int n_streams, unsigned char* base, const OlWS& w, const float* raw,
+                               const int32_t* counts, int64_t total, int rows, const float* mean_std, int32_t* pred,
+                               int32_t* voted, float* logits, float* windows, hipStream_t st) {
+    if (int e = olm_launch_frontend(c, n_streams, base, w, raw, counts, total, rows, mean_std, windows, st)) return e;
+    OlmLayerArgs la{};
+    la.rows = rows;
+    auto layer = [&](const OlLayerArgs& l, auto conv) {
+        constexpr bool CONV = decltype(conv)::value;
+        int blocks;
+        olm_row_blocks(rows, CONV ? 4 * OL_C : 512 / 16, &blocks, &la.tiles_per_block);
+        la.l = l;
+        hipLaunchKernelGGL((olm_layer_kernel<T, CONV>), CONV ? dim3(4, OL_C, blocks) : dim3(512 / 16, blocks), dim3(OL_THREADS), 0, st, la);
+        CKL(CONV ? "olm_layer_kernel<conv>" : "olm_layer_kernel<fc>");
+        return 0;
+    };
+    if (rows > 0)
+        if (int e = ol_folded_chain(base, w, nullptr, (const float*)(base + w.X), base + w.H0, base + w.H1, layer)) return e;
+    return olm_launch_tail(t, c, n_streams, base, w, pred, voted, logits, st);
+}
+
+extern "C" int cp_online_multi_push(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                    const float* raw, const int32_t* counts, int64_t total_samples, int32_t total_windows,
+                                    const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, void* stream) {
+    OlWS w;
+    if (int e = olm_check(cfg, n_streams, max_rows, ws, ws_bytes, false, &w)) return e;
+    if (int e = olm_check_push("cp_online_multi_push", max_rows, raw, counts, total_samples, total_windows, mean_std, pred, voted)) return e;
+    if (total_samples == 0) return 0;
+    return ol_dispatch(cfg->dtype, [&](auto t) {
+        return online_multi_push_t(t, cfg, n_streams, (unsigned char*)ws, w, raw, counts, total_samples, total_windows, mean_std, pred,
+                                   voted, logits, windows, (hipStream_t)stream);
+    });
+}
+
+// ---------------------------------------------------------------------------------------
+// adaptive multi-stream online decoding (csrc/online_multi_adapt.cuh): the unfolded weights once; per stream its OlState, head
+// and float64 statistics; rows of all streams packed.  The workspace begins as the folded multi-stream one (n_streams states,
+// then their OlmMeta), so cp_online_multi_set_classes and cp_online_multi_reset take it
+// ---------------------------------------------------------------------------------------
+extern "C" size_t cp_online_multi_adapt_workspace_bytes(int32_t n_streams, int32_t max_rows, int32_t dtype) {
+    if (n_streams < 1) n_streams = 1;
+    if (max_rows < 1) max_rows = 1;
+    return ol_carve(max_rows, dtype, n_streams, true, true).total;
+}
+
+extern "C" int cp_online_multi_adapt_prepare(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, const cp_params* p,
+                                             const cp_bn_buffers* bn, float bn_eps, const double* alpha, void* ws, size_t ws_bytes,
+                                             void* stream) {
+    if (!(bn_eps > 0.f)) return fail(CP_ERR_ARG, "cp_online_multi_adapt_prepare: bn_eps must be positive");
+    OlWS w;
+    if (int e = olm_check(cfg, n_streams, max_rows, ws, ws_bytes, true, &w)) return e;
+    for (int s = 0; alpha && s < n_streams; ++s)
+        if (!(alpha[s] >= 0.0 && alpha[s] < 1.0)) return fail(CP_ERR_ARG, "cp_online_multi_adapt_prepare: alpha outside [0, 1)");
+    if (int e = ol_check_params("cp_online_multi_adapt_prepare", p, bn, false)) return e;
+    unsigned char* base = (unsigned char*)ws;
+    OlamInitArgs ia{};
+    ola_init_args(ia, p, bn, bn_eps, base, w);
+    ia.heads = (OlaHead*)(base + w.head); ia.first = 0; ia.zero = 0; ia.set_alpha = alpha != nullptr;
+    for (int s = 0; alpha && s < n_streams; ++s) ia.alpha[s] = alpha[s];
+    hipLaunchKernelGGL(olam_init_kernel, dim3(CP_N_BN, n_streams), dim3(512), 0, (hipStream_t)stream, ia);
+    CKL("olam_init_kernel");
+    return ol_dispatch(cfg->dtype, [&](auto t) { return ola_copy_weights(t, p, base, w, (hipStream_t)stream); });
+}
+
+extern "C" int cp_online_multi_adapt_set_alpha(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
+                                               size_t ws_bytes, int32_t index, double alpha, void* stream) {
+    OlWS w;
+    if (int e = olam_check_stream("cp_online_multi_adapt_set_alpha", cfg, n_streams, max_rows, ws, ws_bytes, index, &w)) return e;
+    if (!(alpha >= 0.0 && alpha < 1.0)) return fail(CP_ERR_ARG, "cp_online_multi_adapt_set_alpha: alpha outside [0, 1)");
+    hipLaunchKernelGGL(olam_set_alpha_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (OlaHead*)((unsigned char*)ws + w.head), alpha);
+    CKL("olam_set_alpha_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_multi_adapt_reset_statistics(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
+                                                      size_t ws_bytes, int32_t index, const cp_bn_buffers* bn, void* stream) {
+    OlWS w;                                               // stream 0's view: the kernel finds stream `first` itself
+    if (int e = olm_check(cfg, n_streams, max_rows, ws, ws_bytes, true, &w)) return e;
+    if (int e = ol_check_index("cp_online_multi_adapt_reset_statistics", index, n_streams)) return e;
+    OlamInitArgs ia{};
+    for (int l = 0; l < CP_N_BN; ++l) {
+        if (bn && (!bn->running_mean[l] || !bn->running_var[l]))
+            return fail(CP_ERR_ARG, "cp_online_multi_adapt_reset_statistics: running statistics");
+        ia.mean[l] = bn ? bn->running_mean[l] : nullptr; ia.var[l] = bn ? bn->running_var[l] : nullptr;
+    }
+    ia.stats = (double*)((unsigned char*)ws + w.stats); ia.first = index; ia.zero = bn ? 0 : 1;
+    hipLaunchKernelGGL(olam_init_kernel, dim3(CP_N_BN, 1), dim3(512), 0, (hipStream_t)stream, ia);
+    CKL("olam_init_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_multi_adapt_calibrate(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
+                                               size_t ws_bytes, int32_t index, const float* windows, int64_t n_windows, void* scratch,
+                                               size_t scratch_bytes, void* stream) {
+    const char* who = "cp_online_multi_adapt_calibrate";
+    return ola_calibrate(who, cfg, [&](OlWS* w) { return olam_check_stream(who, cfg, n_streams, max_rows, ws, ws_bytes, index, w); }, ws,
+                         windows, n_windows, scratch, scratch_bytes, stream);
+}
+
+// row blocks of the fc launches: about OLM_TARGET_WG workgroups of 512 / 16 feature tiles when there are rows enough
+static void olam_fc_blocks(int rows, int* blocks, int* rows_per_block) {
+    int b = (OLM_TARGET_WG + 512 / 16 - 1) / (512 / 16);
+    if (b > rows) b = rows;
+    *rows_per_block = (rows + b - 1) / b;
+    *blocks = (rows + *rows_per_block - 1) / *rows_per_block;
+}
+
+template <typename T>
+static int online_multi_adapt_push_t(T t, const cp_online_config* c, int n_streams, unsigned char* base, const OlWS& w, const float* raw,
+                                     const int32_t* counts, int64_t total, int rows, const float* mean_std, int32_t* pred,
+                                     int32_t* voted, float* logits, float* windows, hipStream_t st) {
+    if (int e = olm_launch_frontend(c, n_streams, base, w, raw, counts, total, rows, mean_std, windows, st)) return e;
+    if (rows > 0) {
+        const OlmMeta* meta = (const OlmMeta*)(base + w.meta);
+        auto bn = [&](int l) { return ola_bn(base, w, l, OLA_TRACK, nullptr, 0, 0); };      // stream 0's: the kernels find their stream's
+        OlamConvBnArgs cb{};                              // BN1 -> conv2 -> BN2, as ola_conv_chain
+        cb.meta = meta;
+        cb.a.x = (const float*)(base + w.X); cb.a.c1w = (const float*)(base + w.c1w); cb.a.c1b = (const float*)(base + w.c1b);
+        cb.a.out = base + w.C1; cb.a.m_fixed = 0; cb.a.conv1 = 1; cb.a.bn = bn(0);
+        hipLaunchKernelGGL((olam_conv_bn_kernel<T>), dim3(n_streams), dim3(64), 0, st, cb);
+        CKL("olam_conv_bn_kernel<BN1>");
+        OlaGemmArgs g{};
+        g.l.act = base + w.C1; g.l.w = base + w.c2w; g.l.bias = (const float*)(base + w.c2b); g.l.out = base + w.R2; g.l.K = OL_CONV_K;
+        g.l.F = 64; g.l.ldo = 64; g.m_fixed = rows; g.rows_per_window = OL_C;
+        int blocks, tiles_per_block;
+        olm_row_blocks(rows * OL_C, 64 / 16, &blocks, &tiles_per_block);
+        hipLaunchKernelGGL((ola_gemm_kernel<T>), dim3(64 / 16, blocks), dim3(OL_THREADS), 0, st, g);
+        CKL("ola_gemm_kernel");
+        cb.a.pre = (const float*)(base + w.R2); cb.a.out = base + w.H0; cb.a.conv1 = 0; cb.a.bn = bn(1);
+        hipLaunchKernelGGL((olam_conv_bn_kernel<T>), dim3(n_streams), dim3(64), 0, st, cb);
+        CKL("olam_conv_bn_kernel<BN2>");
+        OlamFcArgs fc{};
+        fc.meta = meta; fc.n_streams = n_streams;
+        olam_fc_blocks(rows, &blocks, &fc.rows_per_block);
+        for (int i = 0; i < CP_N_FC; ++i) {               // H0 -> H1 -> H0 ...: fc7 leaves its output in H1
+            fc.g.l = ol_layer_args(base, w, i + 1, nullptr, base + (i % 2 == 0 ? w.H0 : w.H1), base + (i % 2 == 0 ? w.H1 : w.H0));
+            fc.g.rows_per_window = 1; fc.g.bn = bn(i + 2);
+            hipLaunchKernelGGL((olam_fc_kernel<T>), dim3(512 / 16, blocks), dim3(OL_THREADS), 0, st, fc);
+            CKL("olam_fc_kernel");
+        }
+    }
+    return olm_launch_tail(t, c, n_streams, base, w, pred, voted, logits, st);
+}
+
+extern "C" int cp_online_multi_adapt_push(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                          const float* raw, const int32_t* counts, int64_t total_samples, int32_t total_windows,
+                                          const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows,
+                                          void* stream) {
+    OlWS w;
+    if (int e = olm_check(cfg, n_streams, max_rows, ws, ws_bytes, true, &w)) return e;
+    if (int e = olm_check_push("cp_online_multi_adapt_push", max_rows, raw, counts, total_samples, total_windows, mean_std, pred, voted))
+        return e;
+    if (total_samples == 0) return 0;
+    return ol_dispatch(cfg->dtype, [&](auto t) {
+        return online_multi_adapt_push_t(t, cfg, n_streams, (unsigned char*)ws, w, raw, counts, total_samples, total_windows, mean_std, pred,
+                                         voted, logits, windows, (hipStream_t)stream);
+    });
+}
+
+extern "C" int cp_online_multi_adapt_statistics(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
+                                                size_t ws_bytes, int32_t index, double* out, void* stream) {
+    OlWS w;
+    if (int e = olam_check_stream("cp_online_multi_adapt_statistics", cfg, n_streams, max_rows, ws, ws_bytes, index, &w)) return e;
+    if (!out) return fail(CP_ERR_ARG, "cp_online_multi_adapt_statistics: out is required");
+    CK(hipMemcpyAsync(out, (unsigned char*)ws + w.stats, (size_t)OLAM_STATS * 8, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// class enrolment (csrc/online_enroll.cuh): the front end alone, per-class sums of z / |z| in the caller's float64
+// accumulator, and the blend of those directions with the rows a decoder has
+// ---------------------------------------------------------------------------------------
+extern "C" size_t cp_online_frontend_state_bytes(void) { return align256(offsetof(OlState, K)); }
+
+extern "C" int cp_online_windows(const cp_online_config* cfg, void* state, size_t state_bytes, const float* raw, int64_t n_samples,
+                                 const float* mean_std, float* windows, void* stream) {
+    if (!cfg || !state) return fail(CP_ERR_ARG, "cp_online_windows: config and state are required");
+    if (int e = ol_check_config(cfg, state)) return e;
+    if (state_bytes < cp_online_frontend_state_bytes()) return fail(CP_ERR_ARG, "cp_online_windows: state too small");
+    if (n_samples < 0 || n_samples > (int64_t)CP_ONLINE_STRIDE * cfg->max_windows)
+        return fail(CP_ERR_ARG, "cp_online_windows: a call takes at most 20 * max_windows samples");
+    if (n_samples == 0) return 0;
+    if (!raw || !mean_std || !windows) return fail(CP_ERR_ARG, "cp_online_windows: raw, mean_std and windows are required");
+    if ((uintptr_t)raw % 4 || (uintptr_t)mean_std % 4 || (uintptr_t)windows % 4) return fail(CP_ERR_ARG, "cp_online_windows: misaligned input");
+    OlFrontArgs fa = ol_front_args(cfg);
+    fa.raw = raw; fa.n = n_samples; fa.st = (OlState*)state; fa.X = windows; fa.windows = nullptr; fa.mean_std = mean_std;
+    if (cfg->n_coef == 9) hipLaunchKernelGGL((ole_windows_kernel<9>), dim3(1), dim3(256), 0, (hipStream_t)stream, fa);
+    else hipLaunchKernelGGL((ole_windows_kernel<0>), dim3(1), dim3(256), 0, (hipStream_t)stream, fa);
+    CKL("ole_windows_kernel");
+    return 0;
+}
+
+// enrolment scratch: the activations of one chunk of <= 256 windows (the adaptive form also conv2's operand and output)
+struct OleScratch {
+    size_t C1, R2, H0, H1, total;
+};
+static OleScratch ole_carve(int64_t n_windows, int dtype) {
+    const size_t es = dtype == CP_BF16 ? 2 : 4;
+    const size_t rows = (size_t)(((n_windows < OL_MAXM ? n_windows : OL_MAXM) + 15) / 16 * 16);
+    OleScratch c{};
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t r = o; o = align256(o + bytes); return r; };
+    c.C1 = take(rows * OL_C * OL_CONV_K * es);
+    c.R2 = take(rows * OL_C * 64 * 4);
+    c.H0 = take(rows * 768 * es);
+    c.H1 = take(rows * 512 * es);
+    c.total = o;
+    return c;
+}
+
+extern "C" size_t cp_online_enroll_scratch_bytes(int64_t n_windows, int32_t dtype) {
+    if (n_windows < 1) n_windows = 1;
+    return ole_carve(n_windows, dtype).total;
+}
+
+// The caller's windows through the encoder chunk by chunk, each chunk's z / |z| added to acc: the folded encoder as a push runs
+// it, or (adaptive) the unfolded one with the statistics frozen, the OLA_FROZEN pass of online_adapt_calibrate_t
+template <typename T>
+static int online_enroll_t(T t, bool adaptive, unsigned char* base, const OlWS& w, const float* x, int64_t N, const int32_t* slots,
+                           int n_classes, double* acc, unsigned char* sc, const OleScratch& k, hipStream_t st) {
+    for (int64_t r0 = 0; r0 < N; r0 += OL_MAXM) {
+        const int m = (int)(N - r0 < OL_MAXM ? N - r0 : OL_MAXM);
+        auto layer = [&](const OlLayerArgs& la, auto conv) {
+            constexpr bool CONV = decltype(conv)::value;
+            hipLaunchKernelGGL((ole_layer_kernel<T, CONV>), CONV ? dim3(4, OL_C) : dim3(512 / 16), dim3(OL_THREADS), 0, st, la, m);
+            CKL(CONV ? "ole_layer_kernel<conv>" : "ole_layer_kernel<fc>");
+            return 0;
+        };
+        if (int e = adaptive ? ola_chain(t, base, w, x + r0 * OL_C, m, m, OLA_FROZEN, sc + k.C1, sc + k.R2, sc + k.H0, sc + k.H1, st)
+                             : ol_folded_chain(base, w, nullptr, x + r0 * OL_C, sc + k.H0, sc + k.H1, layer))
+            return e;
+        OleAccArgs a{};
+        a.proj = ol_layer_args(base, w, OL_PROJ, nullptr, sc + k.H1, nullptr);
+        a.slots = slots + r0; a.acc = acc; a.M = m; a.n_classes = n_classes;
+        hipLaunchKernelGGL((ole_accumulate_kernel<T>), dim3(1), dim3(OL_THREADS), 0, st, a);
+        CKL("ole_accumulate_kernel");
+    }
+    return 0;
+}
+
+// the four accumulate entries: check_ws(&w) checks the entry's workspace arguments and gives the view of the stream to enrol
+// with.  n_windows == 0 is a valid empty call
+template <typename CheckWs>
+static int ole_enroll(const char* who, const cp_online_config* cfg, CheckWs check_ws, bool adaptive, void* ws, const float* windows,
+                      int64_t n_windows, const int32_t* slots, int32_t n_classes, double* acc, void* scratch, size_t scratch_bytes,
+                      void* stream) {
+    OlWS w;
+    if (int e = check_ws(&w)) return e;
+    if (n_windows < 0 || n_windows > (int64_t)1 << 24) return ol_fail(CP_ERR_ARG, who, "n_windows outside 0..2**24");
+    if (n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return ol_fail(CP_ERR_ARG, who, "1..64 classes");
+    if (!acc) return ol_fail(CP_ERR_ARG, who, "acc is required");
+    if ((uintptr_t)acc % 8) return ol_fail(CP_ERR_ARG, who, "misaligned acc");
+    if (n_windows == 0) return 0;
+    if (!windows || !slots || !scratch) return ol_fail(CP_ERR_ARG, who, "windows, slots and scratch are required");
+    if ((uintptr_t)windows % 4 || (uintptr_t)slots % 4 || (uintptr_t)scratch % 256) return ol_fail(CP_ERR_ARG, who, "misaligned input or scratch");
+    const OleScratch k = ole_carve(n_windows, cfg->dtype);
+    if (scratch_bytes < k.total) return ol_fail(CP_ERR_WORKSPACE, who, "scratch too small");
+    return ol_dispatch(cfg->dtype, [&](auto t) {
+        return online_enroll_t(t, adaptive, (unsigned char*)ws, w, windows, n_windows, slots, n_classes, acc, (unsigned char*)scratch, k,
+                               (hipStream_t)stream);
+    });
+}
+
+extern "C" int cp_online_enroll(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* windows, int64_t n_windows,
+                                const int32_t* slots, int32_t n_classes, double* acc, void* scratch, size_t scratch_bytes, void* stream) {
+    return ole_enroll("cp_online_enroll", cfg, [&](OlWS* w) { return ol_check(cfg, ws, ws_bytes, false, w); }, false, ws, windows,
+                      n_windows, slots, n_classes, acc, scratch, scratch_bytes, stream);
+}
+
+extern "C" int cp_online_adapt_enroll(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* windows, int64_t n_windows,
+                                      const int32_t* slots, int32_t n_classes, double* acc, void* scratch, size_t scratch_bytes,
+                                      void* stream) {
+    return ole_enroll("cp_online_adapt_enroll", cfg, [&](OlWS* w) { return ol_check(cfg, ws, ws_bytes, true, w); }, true, ws, windows,
+                      n_windows, slots, n_classes, acc, scratch, scratch_bytes, stream);
+}
+
+extern "C" int cp_online_multi_enroll(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                      const float* windows, int64_t n_windows, const int32_t* slots, int32_t n_classes, double* acc,
+                                      void* scratch, size_t scratch_bytes, void* stream) {
+    return ole_enroll("cp_online_multi_enroll", cfg, [&](OlWS* w) { return olm_check(cfg, n_streams, max_rows, ws, ws_bytes, false, w); },
+                      false, ws, windows, n_windows, slots, n_classes, acc, scratch, scratch_bytes, stream);
+}
+
+extern "C" int cp_online_multi_adapt_enroll(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                            int32_t index, const float* windows, int64_t n_windows, const int32_t* slots,
+                                            int32_t n_classes, double* acc, void* scratch, size_t scratch_bytes, void* stream) {
+    const char* who = "cp_online_multi_adapt_enroll";
+    return ole_enroll(who, cfg, [&](OlWS* w) { return olam_check_stream(who, cfg, n_streams, max_rows, ws, ws_bytes, index, w); }, true,
+                      ws, windows, n_windows, slots, n_classes, acc, scratch, scratch_bytes, stream);
+}
+
+extern "C" int cp_online_enroll_table(const double* acc, int32_t n_classes, const float* prior, double mix, int32_t min_windows,
+                                      float* table, void* stream) {
+    if (!acc || !prior || !table) return fail(CP_ERR_ARG, "cp_online_enroll_table: acc, prior and table are required");
+    if ((uintptr_t)acc % 8 || (uintptr_t)prior % 4 || (uintptr_t)table % 4) return fail(CP_ERR_ARG, "cp_online_enroll_table: misaligned input");
+    if (n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return fail(CP_ERR_ARG, "cp_online_enroll_table: 1..64 classes");
+    if (!(mix >= 0.0 && mix <= 1.0)) return fail(CP_ERR_ARG, "cp_online_enroll_table: mix outside [0, 1]");
+    if (min_windows < 1) return fail(CP_ERR_ARG, "cp_online_enroll_table: min_windows must be at least 1");
+    hipLaunchKernelGGL(ole_table_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, acc, (int)n_classes, prior, mix, (double)min_windows,
+                       table);
+    CKL("ole_table_kernel");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// grasp command gate (csrc/online_gate.cuh): one OgState per stream in a workspace of its own, behind any decoder's logits
+// ---------------------------------------------------------------------------------------
+static_assert(OG_MAXK == CP_ONLINE_MAX_CLASSES && OG_MAXVOTE == CP_ONLINE_MAX_VOTE && OG_MAXM == CP_ONLINE_MAX_WINDOWS, "gate limits");
+static_assert(sizeof(OgState) == 4 * (8 + 2 * OG_MAXK + 2 * OG_MAXVOTE), "OgState is 648 words (CommandGate.state reads it back)");
+
+static int og_check(const char* who, const cp_online_gate_config* c, int32_t n_streams, void* ws, size_t ws_bytes) {
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (!c || !ws) return bad("config and workspace are required");
+    if (n_streams < 1 || n_streams > CP_ONLINE_MULTI_MAX_STREAMS) return bad("n_streams outside 1..256");
+    if (c->vote < 1 || c->vote > CP_ONLINE_MAX_VOTE) return bad("vote outside 1..256");
+    if (c->min_votes < 1) return bad("min_votes must be at least 1");
+    if (c->dwell < 1) return bad("dwell must be at least 1");
+    if (c->release < 0) return bad("release must not be negative");
+    if (c->weight != 0 && c->weight != 1) return bad("weight must be 0 (count) or 1 (margin)");
+    if (!(c->min_margin >= 0.f) || std::isinf(c->min_margin)) return bad("min_margin must be finite and >= 0");
+    if ((uintptr_t)ws % 256) return bad("workspace not 256-byte aligned");
+    if (ws_bytes < (size_t)n_streams * sizeof(OgState)) return bad("workspace too small");
+    return 0;
+}
+
+extern "C" size_t cp_online_gate_workspace_bytes(int32_t n_streams) {
+    if (n_streams < 1) n_streams = 1;
+    return align256((size_t)n_streams * sizeof(OgState));
+}
+
+extern "C" int cp_online_gate_set_classes(const cp_online_gate_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index,
+                                          const int32_t* ids, const float* min_cosine, int32_t n_classes, void* stream) {
+    if (int e = og_check("cp_online_gate_set_classes", cfg, n_streams, ws, ws_bytes)) return e;
+    if (int e = ol_check_index("cp_online_gate_set_classes", index, n_streams)) return e;
+    if (!ids || !min_cosine || n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES)
+        return fail(CP_ERR_ARG, "cp_online_gate_set_classes: 1..64 classes, with ids and min_cosine");
+    OgClassArgs c{};
+    c.K = n_classes;
+    for (int k = 0; k < n_classes; ++k) {
+        if (ids[k] < 0 || ids[k] == INT32_MAX || (k > 0 && ids[k] <= ids[k - 1]))
+            return fail(CP_ERR_ARG, "cp_online_gate_set_classes: ids must be ascending, distinct and in 0..2^31-2");
+        if (std::isnan(min_cosine[k])) return fail(CP_ERR_ARG, "cp_online_gate_set_classes: min_cosine must not be NaN");
+        c.ids[k] = ids[k];
+        c.min_cosine[k] = min_cosine[k];
+    }
+    hipLaunchKernelGGL(og_set_classes_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (OgState*)ws + index, c);
+    CKL("og_set_classes_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_gate_reset(const cp_online_gate_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index,
+                                    void* stream) {
+    if (int e = og_check("cp_online_gate_reset", cfg, n_streams, ws, ws_bytes)) return e;
+    if (index < -1 || index >= n_streams) return fail(CP_ERR_ARG, "cp_online_gate_reset: stream index outside -1..n_streams-1");
+    hipLaunchKernelGGL(og_reset_kernel, dim3(index < 0 ? n_streams : 1), dim3(64), 0, (hipStream_t)stream, (OgState*)ws,
+                       index < 0 ? 0 : index);
+    CKL("og_reset_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_gate_push(const cp_online_gate_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, const float* logits,
+                                   int32_t ldl, const int32_t* row0, const int32_t* m, int32_t total_rows, int32_t* command,
+                                   int32_t* accepted, float* conf, float* margin, void* stream) {
+    if (int e = og_check("cp_online_gate_push", cfg, n_streams, ws, ws_bytes)) return e;
+    if (total_rows < 0 || total_rows > CP_ONLINE_MULTI_MAX_ROWS) return fail(CP_ERR_ARG, "cp_online_gate_push: total_rows outside 0..65536");
+    if (total_rows == 0) return 0;
+    if (ldl < 1) return fail(CP_ERR_ARG, "cp_online_gate_push: ldl must be at least 1");
+    if (!logits || !row0 || !m || !command || !accepted)
+        return fail(CP_ERR_ARG, "cp_online_gate_push: logits, row0, m, command and accepted are required");
+    if ((uintptr_t)logits % 4 || (uintptr_t)row0 % 4 || (uintptr_t)m % 4 || (uintptr_t)command % 4 || (uintptr_t)accepted % 4 ||
+        (uintptr_t)conf % 4 || (uintptr_t)margin % 4)
+        return fail(CP_ERR_ARG, "cp_online_gate_push: misaligned argument");
+    OgPushArgs a{};
+    a.states = (OgState*)ws; a.logits = logits; a.row0 = row0; a.m = m; a.ldl = ldl; a.total_rows = total_rows;
+    a.command = command; a.accepted = accepted; a.conf = conf; a.margin = margin;
+    a.c.vote = cfg->vote; a.c.min_votes = cfg->min_votes; a.c.dwell = cfg->dwell; a.c.release = cfg->release; a.c.weight = cfg->weight;
+    a.c.min_margin = cfg->min_margin;
+    hipLaunchKernelGGL(og_push_kernel, dim3(n_streams), dim3(64), 0, (hipStream_t)stream, a);
+    CKL("og_push_kernel");
+    return 0;
+}
+
+// gate sweep: n_configs settings over one recording, one wave each, scored on the device (og_rows_kernel, og_sweep_kernel)
+static_assert(OG_SCORES == CP_ONLINE_GATE_SCORES && sizeof(OgRow) == 12, "gate sweep layout");
+static_assert(sizeof(OgConfig) == sizeof(cp_online_gate_config), "the sweep reads cp_online_gate_config from the device as OgConfig");
+
+extern "C" size_t cp_online_gate_sweep_scratch_bytes(int64_t n_rows) {
+    if (n_rows < 1) n_rows = 1;
+    return align256((size_t)n_rows * sizeof(OgRow));
+}
+
+extern "C" int cp_online_gate_sweep(const float* logits, int32_t ldl, int64_t n_rows, int32_t n_classes, const int32_t* expected_slot,
+                                    const cp_online_gate_config* configs, const float* min_cosine, int32_t n_configs, void* scratch,
+                                    size_t scratch_bytes, int64_t* scores, int32_t* commands, void* stream) {
+    if (n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return fail(CP_ERR_ARG, "cp_online_gate_sweep: n_classes outside 1..64");
+    if (ldl < n_classes) return fail(CP_ERR_ARG, "cp_online_gate_sweep: ldl must be at least n_classes");
+    if (n_configs < 1 || n_configs > CP_ONLINE_GATE_SWEEP_MAX_CONFIGS)
+        return fail(CP_ERR_ARG, "cp_online_gate_sweep: n_configs outside 1..65536");
+    if (n_rows < 1 || n_rows > INT32_MAX) return fail(CP_ERR_ARG, "cp_online_gate_sweep: n_rows outside 1..2^31-1");
+    if (!logits || !expected_slot || !configs || !min_cosine || !scratch || !scores)
+        return fail(CP_ERR_ARG, "cp_online_gate_sweep: logits, expected_slot, configs, min_cosine, scratch and scores are required");
+    if ((uintptr_t)logits % 4 || (uintptr_t)expected_slot % 4 || (uintptr_t)configs % 4 || (uintptr_t)min_cosine % 4 ||
+        (uintptr_t)scratch % 4 || (uintptr_t)scores % 8 || (uintptr_t)commands % 4)
+        return fail(CP_ERR_ARG, "cp_online_gate_sweep: misaligned argument");
+    if (scratch_bytes < (size_t)n_rows * sizeof(OgRow)) return fail(CP_ERR_ARG, "cp_online_gate_sweep: scratch too small");
+    const int rows_per_block = 4 * OG_ROWS_PER_WAVE;
+    hipLaunchKernelGGL(og_rows_kernel, dim3((unsigned)((n_rows + rows_per_block - 1) / rows_per_block)), dim3(256), 0, (hipStream_t)stream,
+                       logits, (int)ldl, (long long)n_rows, (int)n_classes, (OgRow*)scratch);
+    CKL("og_rows_kernel");
+    OgSweepArgs a{};
+    a.rows = (const OgRow*)scratch; a.expected = expected_slot; a.configs = (const OgConfig*)configs; a.min_cosine = min_cosine;
+    a.n_rows = n_rows; a.n_configs = n_configs; a.K = n_classes; a.scores = (long long*)scores; a.commands = commands;
+    hipLaunchKernelGGL(og_sweep_kernel, dim3((n_configs + OG_SWEEP_WAVES - 1) / OG_SWEEP_WAVES), dim3(64 * OG_SWEEP_WAVES), 0,
+                       (hipStream_t)stream, a);
+    CKL("og_sweep_kernel");
+    return 0;
+}

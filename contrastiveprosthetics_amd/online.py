@@ -125,6 +125,19 @@ def _check_count(k: int):
         raise ValueError(f"at most {MAX_CLASSES} classes, got {k}")
 
 
+def _check_raw(t, what: str = "raw"):
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != torch.float32 or t.dim() != 2 \
+            or t.shape[1] != EMG_DIM:
+        raise ValueError(f"{what} must be an (n, 12) float32 tensor on the GPU")
+
+
+class _OnStream:
+    """a decoder or gate on `self.device`: its C entries run on torch's current stream there"""
+
+    def _stream(self) -> int:
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+
 def _class_table(e: Engine, classes=None, glove=None, table=None, ids=None):
     """The class table of `set_classes` (see OnlineDecoder.set_classes): (K, 16) f32 rows on the device, sorted by id, and the
     sorted ids (K,) int64.  Raises before anything is enqueued on a decoder."""
@@ -175,8 +188,7 @@ def _calibration_windows(raw: torch.Tensor, b, a, phase: int, mean_std: torch.Te
     recording as one segment, 256 kept positions per call.  Valid for a recording of any length: cp_preprocess_emg keeps
     its positions in 32 bits."""
     from .preprocess import normalize_, preprocess_segments
-    if raw.device.type != "cuda" or raw.dtype != torch.float32 or raw.dim() != 2 or raw.shape[1] != EMG_DIM:
-        raise ValueError("raw must be an (n, 12) float32 tensor on the GPU")
+    _check_raw(raw)
     k = windows_before(raw.shape[0], phase)
     if k < 2:
         raise ValueError("calibration takes at least 2 windows")
@@ -214,9 +226,7 @@ def recording_windows(raw: torch.Tensor, mean_std: torch.Tensor, b=None, a=None,
     of the stateful front end (cp_online_windows) over the recording, bit-identical to the offline path
     (`preprocess_segments` + `normalize_`), which filters the recording again for every 256 positions it keeps.  mean_std
     (2, 12) f32 on the GPU."""
-    if not isinstance(raw, torch.Tensor) or raw.device.type != "cuda" or raw.dtype != torch.float32 or raw.dim() != 2 \
-            or raw.shape[1] != EMG_DIM:
-        raise ValueError("raw must be an (n, 12) float32 tensor on the GPU")
+    _check_raw(raw)
     if not 0 <= int(phase) < STRIDE:
         raise ValueError(f"phase must lie in 0..{STRIDE - 1}")
     b, a = _filter(b, a)
@@ -263,7 +273,7 @@ def _sample_labels(labels, n: int) -> np.ndarray:
     return lab.astype(np.int64)
 
 
-class _EnrollMixin:
+class _EnrollMixin(_OnStream):
     """`enroll` of the online decoders.  `key` is None (OnlineDecoder) or a stream index; a decoder supplies _enroll_view,
     _enroll_call and _enroll_install."""
 
@@ -277,9 +287,7 @@ class _EnrollMixin:
             raise ValueError("mix must lie in [0, 1]")
         if int(min_windows) < 1:
             raise ValueError("min_windows must be at least 1")
-        if not isinstance(raw, torch.Tensor) or raw.device.type != "cuda" or raw.dtype != torch.float32 or raw.dim() != 2 \
-                or raw.shape[1] != EMG_DIM:
-            raise ValueError("raw must be an (n, 12) float32 tensor on the GPU")
+        _check_raw(raw)
         wl = window_labels(_sample_labels(labels, raw.shape[0]), self.phase)
         keep = np.nonzero(wl >= 0)[0]
         if keep.size == 0:
@@ -359,7 +367,7 @@ class OnlineDecoder(_EnrollMixin):
             raise ValueError("adapt (alpha) must lie in [0, 1)")
         dtype = _check_settings(e, dtype, vote, phase, max_windows_per_push, "OnlineDecoder")
         if classes is not None:
-            self._check_count(len(classes))
+            _check_count(len(classes))
         b, a = _filter(b, a)
         self.engine = e
         self.adapt = None if adapt is None else float(adapt)
@@ -373,7 +381,7 @@ class OnlineDecoder(_EnrollMixin):
         self.phase = int(phase)
         self.max_windows = int(max_windows_per_push)
         cfg = self._cfg = _config(dtype, self.max_windows, self.vote, self.phase, b, a)
-        self.mean_std = torch.stack([self._channels(mean), self._channels(std)]).contiguous()
+        self.mean_std = torch.stack([_channels(mean, self.device), _channels(std, self.device)]).contiguous()
         nbytes = (self.lib.cp_online_workspace_bytes if adapt is None else self.lib.cp_online_adapt_workspace_bytes)(self.max_windows, cfg.dtype)
         self.ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
         self.n_seen = 0
@@ -384,16 +392,6 @@ class OnlineDecoder(_EnrollMixin):
             self.set_classes(classes)
 
     # ------------------------------------------------------------------ helpers
-    def _channels(self, v) -> torch.Tensor:
-        return _channels(v, self.device)
-
-    @staticmethod
-    def _check_count(k: int):
-        _check_count(k)
-
-    def _stream(self) -> int:
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def _ws(self):
         return self.ws.data_ptr(), self.ws.numel()
 
@@ -446,8 +444,7 @@ class OnlineDecoder(_EnrollMixin):
             raise _lib.CpNativeError("set_classes() first")
         if not self.calibrated:
             raise _lib.CpNativeError("an AdaBN model has no BatchNorm statistics: calibrate() first")
-        if raw.device.type != "cuda" or raw.dtype != torch.float32 or raw.dim() != 2 or raw.shape[1] != EMG_DIM:
-            raise ValueError("raw must be an (n, 12) float32 tensor on the GPU")
+        _check_raw(raw)
         raw = raw.contiguous()
         K = self.class_ids.numel()
         step = STRIDE * self.max_windows
@@ -647,9 +644,6 @@ class _MultiStreamBase(_EnrollMixin):
         self._enroll_rec = {}
 
     # ------------------------------------------------------------------ helpers
-    def _stream(self) -> int:
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def _args(self):
         return (C.byref(self._cfg), self.n_streams, self.max_rows, self.ws.data_ptr(), self.ws.numel())
 
@@ -741,7 +735,7 @@ class _MultiStreamBase(_EnrollMixin):
             if c is None:
                 counts.append(0)
                 continue
-            self._check_raw(c, "each chunk")
+            _check_raw(c, "each chunk")
             counts.append(int(c.shape[0]))
             if c.shape[0]:
                 parts.append(c)
@@ -756,7 +750,7 @@ class _MultiStreamBase(_EnrollMixin):
     def push_packed(self, raw: torch.Tensor, counts, return_logits: bool = False, return_windows: bool = False):
         """As push, for samples already packed in stream order: raw (sum(counts), 12) float32 on the GPU, counts[s] >= 0 the
         samples of stream s."""
-        self._check_raw(raw, "raw")
+        _check_raw(raw)
         cnt = np.asarray(counts, dtype=np.int64).reshape(-1)
         if cnt.shape[0] != self.n_streams:
             raise ValueError(f"counts must hold {self.n_streams} entries")
@@ -768,12 +762,6 @@ class _MultiStreamBase(_EnrollMixin):
 
     def _check_push(self, counts: np.ndarray):
         """refusals of a subclass, before anything is enqueued"""
-
-    @staticmethod
-    def _check_raw(t, what: str):
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != torch.float32 or t.dim() != 2 \
-                or t.shape[1] != EMG_DIM:
-            raise ValueError(f"{what} must be an (n, 12) float32 tensor on the GPU")
 
     def _counts_on_device(self, take: np.ndarray) -> torch.Tensor:
         """take as int32 on the device.  A stream of pushes usually repeats its counts: the last device copy is reused (it is
@@ -1012,7 +1000,7 @@ def _gate_settings(new: dict):
     return mm, int(new["min_votes"]), int(new["dwell"]), int(new["release"]), _GATE_WEIGHTS[new["weight"]]
 
 
-class CommandGate:
+class CommandGate(_OnStream):
     """A command a hand can follow, from any of the four decoders: per stream one state machine on the device that reads the
     logits of every push (include/cpnative.h, cp_online_gate_*; one launch more per push, nothing is copied to the host).
 
@@ -1114,9 +1102,6 @@ class CommandGate:
         self._ids_seen[s] = None
 
     # ------------------------------------------------------------------ the device side (one method per C entry)
-    def _stream(self) -> int:
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def _args(self):
         if self.ws is None:
             self.lib = _lib.load()

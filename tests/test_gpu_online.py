@@ -243,3 +243,7 @@ def test_refusals(engine, recording):
         d1.set_classes([])
     x1, x2 = d1.push(rec[1000:3000]), d2.push(rec[1000:3000])
     assert torch.equal(x1[0], x2[0]) and torch.equal(x1[1], x2[1])
+    # raw that is not an (n, 12) float32 GPU tensor, a non-tensor included: the one refusal every entry point gives
+    for bad in (rec[:100].cpu(), rec[:100].double(), rec[:100, :11], rec[:100].cpu().numpy(), None):
+        with pytest.raises(ValueError, match="float32 tensor on the GPU"):
+            d1.push(bad)
