@@ -142,7 +142,7 @@ __device__ __forceinline__ uint32_t hash32(uint32_t x) {
 // index's top byte enters through its own multiply, and the second output word is drawn from another 24-bit window of the state.
 // tools/dropout_hash_check.py (numpy, bit for bit; a CPU test runs it): no two rows of a 167,936 x 512 or a 335,872 x 512 tensor share a
 // mask (round 3's form: 36,864 / 204,800 rows), drop rates 0.0634-0.0636 for p = 0.0635 in all four draws, cross-draw, lag-1, next-row,
-// 2^22 / 2^24 / 2^25-quad-lag and key-bit-flip mask correlations all below 0.004.  Limit: row * ld < 2^32 (api.hip checks n_windows).
+// 2^22 / 2^24 / 2^25-quad-lag and key-bit-flip mask correlations all below 0.004.  Limit: row * ld < 2^32 (encoder_api.cuh, check_cfg, checks n_windows).
 __device__ __forceinline__ uint2 dropout_quad(uint32_t key, uint32_t row, uint32_t ld, uint32_t col) {
     uint32_t x = ((__umul24(row, ld) + col) >> 2) ^ key;        // (rows and ld below 2^24, rows * ld below 2^32)
     const uint32_t hi = x >> 24;

@@ -1304,7 +1304,7 @@ __global__ __launch_bounds__(256) void bn_relu_bwd8_kernel(uint8_t* __restrict__
     };
     const int64_t step = (int64_t)gridDim.x * rpp;
     int64_t m = (int64_t)blockIdx.x * rpp + rr;
-    // four rows in flight per thread (two were, on four times the workgroups: round 4, third part -- api.hip CAP_BRB8)
+    // four rows in flight per thread (two were, on four times the workgroups: round 4, third part -- encoder_api.cuh CAP_BRB8)
     for (; m + 3 * step < rows; m += 4 * step) {
         const uint4 g0 = *(const uint4*)(g + m * C + cc * 16), r0 = *(const uint4*)(r + m * C + cc * 16);
         const uint4 g1 = *(const uint4*)(g + (m + step) * C + cc * 16), r1 = *(const uint4*)(r + (m + step) * C + cc * 16);

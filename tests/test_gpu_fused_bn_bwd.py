@@ -49,7 +49,7 @@ def test_bf16_fused_bn_backward_equals_separate_pass(dp):
 
 def test_paired_weight_gradients_equal_unpaired():
     """bf16 with dropout: the weight gradients of fc7/fc6 and fc5/fc4 run as two problems of one launch with 32 splits
-    each (api.hip, defer_wgrad) -- against one launch per layer with 64 splits (cp_config.options, CP_OPT_UNPAIRED_WGRAD).  Same products,
+    each (csrc/encoder_api.cuh, place_wgrad) -- against one launch per layer with 64 splits (cp_config.options, CP_OPT_UNPAIRED_WGRAD).  Same products,
     f32 partial sums grouped differently."""
     from contrastiveprosthetics_amd.engine import Engine
     n = 40000 - 40000 % T
