@@ -13,7 +13,8 @@ def __getattr__(name):
     # OnlineDecoder pulls in torch and the engine; importing the package stays light until it is asked for
     if name in ("OnlineDecoder", "MultiStreamDecoder", "AdaptiveMultiStreamDecoder", "recording_windows", "window_labels",
                 "CommandGate", "thresholds_from_logits", "REST", "IGNORE", "expected_commands", "score_commands", "pick_gate",
-                "sweep_gate", "gate_grid"):
+                "sweep_gate", "gate_grid", "SUBSET_SCORE_KEYS", "score_subset", "sweep_subsets", "rank_subsets",
+                "search_grasp_sets"):
         from . import online
         return getattr(online, name)
     raise AttributeError(name)

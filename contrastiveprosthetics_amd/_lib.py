@@ -86,6 +86,7 @@ class cp_online_gate_config(C.Structure):
 CP_ONLINE_MAX_CLASSES, CP_ONLINE_MAX_VOTE, CP_ONLINE_MAX_WINDOWS, CP_ONLINE_STRIDE = 64, 256, 256, 20
 CP_ONLINE_MULTI_MAX_STREAMS, CP_ONLINE_MULTI_MAX_ROWS = 256, 65536
 CP_ONLINE_GATE_SCORES, CP_ONLINE_GATE_SWEEP_MAX_CONFIGS = 10, 65536
+CP_ONLINE_SUBSET_SCORES, CP_ONLINE_SUBSET_SWEEP_MAX_SUBSETS = 7, 1048576
 
 SYMBOLS = {
     "cp_version": (C.c_int, []),
@@ -184,6 +185,9 @@ SYMBOLS = {
     "cp_online_gate_sweep_scratch_bytes": (C.c_size_t, [C.c_int64]),
     "cp_online_gate_sweep": (C.c_int, [_fp, C.c_int32, C.c_int64, C.c_int32, _fp, _fp, _fp, C.c_int32, _fp, C.c_size_t, _fp, _fp,
                                        _fp]),
+    "cp_online_subset_sweep_scratch_bytes": (C.c_size_t, [C.c_int64]),
+    "cp_online_subset_sweep": (C.c_int, [_fp, C.c_int32, C.c_int64, C.c_int32, _fp, _fp, C.c_int32, C.c_int32, _fp, C.c_size_t, _fp,
+                                         _fp, _fp]),
 }
 
 KERNEL_KINDS = ["gather", "prep", "conv1_fwd", "bn_finalize", "conv2_fwd", "fold", "fc_fwd", "dropout", "proj_fwd",

@@ -26,6 +26,7 @@
 #include "online_multi_adapt.cuh"
 #include "online_enroll.cuh"
 #include "online_gate.cuh"
+#include "online_subsets.cuh"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* what) {
@@ -749,4 +750,4 @@ extern "C" int cp_debug_gemm(int32_t dtype, int32_t kind, int64_t M, int32_t K, 
     return debug_gemm_t<float>(kind, M, K, F, A, W, C, bias, R, partials, (hipStream_t)stream);
 }
 
-#include "online_api.cuh"             // the cp_online_* entries: host layer of the online decoders, the gate and the gate sweep
+#include "online_api.cuh"             // the cp_online_* entries: host layer of the online decoders, the gate, the gate sweep and the subset sweep

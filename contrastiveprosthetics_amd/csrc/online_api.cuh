@@ -1,6 +1,6 @@
 // Host layer of the online decoders (include/cpnative.h, cp_online_*): workspace layout, argument checks, launch chains and
 // the extern "C" entries of the folded, adaptive, multi-stream and adaptive multi-stream decoders, class enrolment, the
-// command gate and the gate sweep.  Host code only; api.hip includes it behind its own helpers (fail, CK, CKL) and encoder_api.cuh's (align256, fcK),
+// command gate, the gate sweep and the subset sweep.  Host code only; api.hip includes it behind its own helpers (fail, CK, CKL) and encoder_api.cuh's (align256, fcK),
 // so the library stays one translation unit.  The four decoders share one workspace description (OlWS, ol_carve), one
 // parameter check, one set of front-end arguments, one folded chain and one unfolded weight copy; what an entry adds is its
 // name in the refusals and the kernels it launches.
@@ -1028,5 +1028,39 @@ extern "C" int cp_online_gate_sweep(const float* logits, int32_t ldl, int64_t n_
     hipLaunchKernelGGL(og_sweep_kernel, dim3((n_configs + OG_SWEEP_WAVES - 1) / OG_SWEEP_WAVES), dim3(64 * OG_SWEEP_WAVES), 0,
                        (hipStream_t)stream, a);
     CKL("og_sweep_kernel");
+    return 0;
+}
+
+// grasp-set search: n_subsets class subsets over one cued recording, one wave each, scored on the device (csrc/online_subsets.cuh)
+static_assert(OS_SCORES == CP_ONLINE_SUBSET_SCORES && OS_ORDER == CP_ONLINE_MAX_CLASSES, "subset sweep layout");
+
+extern "C" size_t cp_online_subset_sweep_scratch_bytes(int64_t n_rows) {
+    if (n_rows < 1) n_rows = 1;
+    return align256((size_t)n_rows * OS_ORDER);
+}
+
+extern "C" int cp_online_subset_sweep(const float* logits, int32_t ldl, int64_t n_rows, int32_t n_classes, const int32_t* expected_slot,
+                                      const uint64_t* subsets, int32_t n_subsets, int32_t vote, void* scratch, size_t scratch_bytes,
+                                      int64_t* scores, int32_t* class_hits, void* stream) {
+    if (n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return fail(CP_ERR_ARG, "cp_online_subset_sweep: n_classes outside 1..64");
+    if (ldl < n_classes) return fail(CP_ERR_ARG, "cp_online_subset_sweep: ldl must be at least n_classes");
+    if (n_subsets < 1 || n_subsets > CP_ONLINE_SUBSET_SWEEP_MAX_SUBSETS)
+        return fail(CP_ERR_ARG, "cp_online_subset_sweep: n_subsets outside 1..1048576");
+    if (vote < 1 || vote > CP_ONLINE_MAX_VOTE) return fail(CP_ERR_ARG, "cp_online_subset_sweep: vote outside 1..256");
+    if (n_rows < 1 || n_rows > INT32_MAX) return fail(CP_ERR_ARG, "cp_online_subset_sweep: n_rows outside 1..2^31-1");
+    if (!logits || !expected_slot || !subsets || !scratch || !scores)
+        return fail(CP_ERR_ARG, "cp_online_subset_sweep: logits, expected_slot, subsets, scratch and scores are required");
+    if ((uintptr_t)logits % 4 || (uintptr_t)expected_slot % 4 || (uintptr_t)subsets % 8 || (uintptr_t)scratch % 16 ||
+        (uintptr_t)scores % 8 || (uintptr_t)class_hits % 4)
+        return fail(CP_ERR_ARG, "cp_online_subset_sweep: misaligned argument");
+    if (scratch_bytes < (size_t)n_rows * OS_ORDER) return fail(CP_ERR_ARG, "cp_online_subset_sweep: scratch too small");
+    hipLaunchKernelGGL(os_rows_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, (int)ldl,
+                       (long long)n_rows, (int)n_classes, (unsigned char*)scratch);
+    CKL("os_rows_kernel");
+    OsSweepArgs a{};
+    a.order = (const unsigned char*)scratch; a.expected = expected_slot; a.subsets = (const unsigned long long*)subsets;
+    a.n_rows = n_rows; a.n_subsets = n_subsets; a.K = n_classes; a.vote = vote; a.scores = (long long*)scores; a.class_hits = class_hits;
+    hipLaunchKernelGGL(os_sweep_kernel, dim3((n_subsets + OS_WAVES - 1) / OS_WAVES), dim3(64 * OS_WAVES), 0, (hipStream_t)stream, a);
+    CKL("os_sweep_kernel");
     return 0;
 }

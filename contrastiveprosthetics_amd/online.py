@@ -26,7 +26,10 @@ own `OnlineDecoder(adapt=alpha)`.
 device (cp_online_gate_*, csrc/online_gate.cuh): rejection by cosine threshold and margin, a weighted vote ring, a dwell time
 before a new grasp and a release time before none.  `sweep_gate` chooses its settings: it runs many of them over the logits
 of a cued recording in one pass on the device (cp_online_gate_sweep) and returns each one's score against the cues
-(`expected_commands`, `score_commands`, `pick_gate`).
+(`expected_commands`, `score_commands`, `pick_gate`).  `search_grasp_sets` answers the question before that one, which grasps
+to keep: it scores many class subsets of the same recording in one pass on the device (`sweep_subsets`,
+cp_online_subset_sweep, csrc/online_subsets.cuh) as the decoders would decode it with that subset alone (`score_subset` is the
+definition), all subsets of a size where that is affordable and a beam beyond, and ranks them (`rank_subsets`).
 
 The number of windows a push emits follows from sample counts alone (`windows_emitted`), so a push never waits for the device:
 its outputs are device tensors on torch's current stream.
@@ -1430,6 +1433,21 @@ def _sweep_configs(configs, cid: np.ndarray):
     return cfg, thr
 
 
+def _cue_slots(logits, expected, cid: np.ndarray) -> np.ndarray:
+    """the checks of a cued recording's logits (M, K) and expected (M,) against the ids -> expected as (M,) int32 class slots
+    (REST and IGNORE as they are)"""
+    if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.dim() != 2 or logits.shape[1] != cid.shape[0]:
+        raise ValueError("logits must be an (M, K) float32 tensor with one column per id")
+    exp = np.asarray(expected.detach().cpu() if isinstance(expected, torch.Tensor) else expected)
+    if exp.shape != (logits.shape[0],) or exp.dtype.kind not in "iu":
+        raise ValueError(f"expected must hold one integer entry per window ({logits.shape[0]})")
+    exp = exp.astype(np.int64)
+    pos = np.minimum(np.searchsorted(cid, exp), cid.shape[0] - 1)
+    if ((exp >= 0) & (cid[pos] != exp)).any() or (exp < IGNORE).any():
+        raise ValueError("expected holds class ids among ids, REST or IGNORE")
+    return np.where(exp >= 0, pos, exp).astype(np.int32)
+
+
 def _sweep_dev(logits: torch.Tensor, slots: np.ndarray, k: int, cfg: np.ndarray, thr: np.ndarray, want_commands: bool):
     """the device side of `sweep_gate` (one call of cp_online_gate_sweep) -> scores (G, 10) int64 on the host, commands (G, M)
     int32 slots on the device or None"""
@@ -1460,16 +1478,7 @@ def sweep_gate(logits, expected, ids, configs, return_commands: bool = False):
     commands (G, M) int32 on the GPU, class ids or -1.  One host synchronisation: the copy of the score table."""
     cid = _ids_array(ids)
     cfg, thr = _sweep_configs(configs, cid)
-    if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.dim() != 2 or logits.shape[1] != cid.shape[0]:
-        raise ValueError("logits must be an (M, K) float32 tensor with one column per id")
-    exp = np.asarray(expected.detach().cpu() if isinstance(expected, torch.Tensor) else expected)
-    if exp.shape != (logits.shape[0],) or exp.dtype.kind not in "iu":
-        raise ValueError(f"expected must hold one integer entry per window ({logits.shape[0]})")
-    exp = exp.astype(np.int64)
-    pos = np.minimum(np.searchsorted(cid, exp), cid.shape[0] - 1)
-    if ((exp >= 0) & (cid[pos] != exp)).any() or (exp < IGNORE).any():
-        raise ValueError("expected holds class ids among ids, REST or IGNORE")
-    slots = np.where(exp >= 0, pos, exp).astype(np.int32)
+    slots = _cue_slots(logits, expected, cid)
     g, m = cfg.shape[0], int(logits.shape[0])
     if m == 0:
         scores = np.zeros((g, len(SCORE_KEYS)), dtype=np.int64)
@@ -1489,3 +1498,224 @@ def sweep_gate(logits, expected, ids, configs, return_commands: bool = False):
         for lo in range(0, g, step):
             commands[lo:lo + step] = table[(commands[lo:lo + step] + 1).long()]
     return out, commands
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# grasp-set search: many class subsets of one cued recording, scored on the device (cp_online_subset_sweep)
+# ---------------------------------------------------------------------------------------------------------------------------
+SUBSET_SCORE_KEYS = ("n_cue", "hit", "voted_hit", "classes_scored", "worst_class", "worst_hit", "worst_n")
+MAX_SUBSETS = _lib.CP_ONLINE_SUBSET_SWEEP_MAX_SUBSETS
+
+
+def _check_vote(vote) -> int:
+    if isinstance(vote, bool) or not isinstance(vote, (int, np.integer)) or not 1 <= int(vote) <= _lib.CP_ONLINE_MAX_VOTE:
+        raise ValueError(f"vote must lie in 1..{_lib.CP_ONLINE_MAX_VOTE}")
+    return int(vote)
+
+
+def _mask_sizes(masks: np.ndarray) -> np.ndarray:
+    return np.unpackbits(np.ascontiguousarray(masks).view(np.uint8).reshape(-1, 8), axis=1).sum(axis=1).astype(np.int64)
+
+
+def _subset_masks(subsets, cid: np.ndarray) -> np.ndarray:
+    """subsets (a sequence of collections of class ids, or a (G,) uint64 array of slot masks) -> (G,) uint64 slot masks, bit k =
+    slot k of ids; ValueError for an id that is not among ids, an empty subset, a bit at or above K, and G outside
+    1..MAX_SUBSETS"""
+    k = int(cid.shape[0])
+    if isinstance(subsets, np.ndarray) and subsets.dtype == np.uint64:
+        if subsets.ndim != 1:
+            raise ValueError("subsets as masks must be a (G,) uint64 array")
+        masks = subsets.copy()
+    else:
+        subsets = list(subsets)
+        masks = np.zeros(len(subsets), dtype=np.uint64)
+        slot = {int(c): i for i, c in enumerate(cid)}
+        for g, sub in enumerate(subsets):
+            m = 0
+            for c in (sub.tolist() if isinstance(sub, (np.ndarray, torch.Tensor)) else sub):
+                if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or int(c) not in slot:
+                    raise ValueError(f"subset {g} names {c!r}, which is not among ids")
+                m |= 1 << slot[int(c)]
+            masks[g] = m
+    if not 1 <= masks.shape[0] <= MAX_SUBSETS:
+        raise ValueError(f"sweep_subsets takes 1..{MAX_SUBSETS} subsets, got {masks.shape[0]}")
+    if (masks == 0).any():
+        raise ValueError(f"subset {int(np.nonzero(masks == 0)[0][0])} is empty")
+    if k < 64 and (masks >> np.uint64(k)).any():
+        raise ValueError(f"subset {int(np.nonzero(masks >> np.uint64(k))[0][0])} has a bit at or above the {k} class slots")
+    return masks
+
+
+def score_subset(logits, expected, ids, subset, vote: int = VOTE, per_class: bool = False):
+    """What a user who keeps only the classes of `subset` gets out of a cued recording; this function is the definition (the
+    subset sweep kernel restates it).  logits (M, K) f32 with one column per id; ids the K ascending class ids; expected (M,) as
+    `expected_commands` gives it; subset a non-empty collection of ids among `ids`, S its set of slots.
+    Kept rows: those with expected < 0 and those cued for a class of S.  Rows cued for another class are dropped, as though never
+    recorded; kept rows with expected < 0 feed the ring and are not scored.
+    Raw prediction of a kept row: the first maximum of its logits over the slots of S in ascending order (`>`, the lowest slot
+    wins ties), or none if any of the row's K logits is not finite.
+    Vote: the decoders' ring from an empty ring.  Every kept row's prediction enters (none takes a place without voting), the
+    oldest leaves once `vote` are in; the voted prediction is the slot with the most entries, the smallest among equals, none if
+    no slot has one.
+    Returns, all ints, the keys of SUBSET_SCORE_KEYS and `size` (the number of classes of S):
+    n_cue            kept rows cued for a class of S
+    hit              of those, rows whose raw prediction is the cued class
+    voted_hit        of those, rows whose voted prediction is the cued class
+    classes_scored   classes of S with at least one cue row
+    worst_class      the class id of S with the smallest voted recall voted_hit_c / n_c among those with n_c > 0 (fractions
+                     compared by cross-multiplication, the smallest slot among equals); -1 if there is none
+    worst_hit, worst_n   its voted_hit_c and n_c; 0, 0 if there is none
+    per_class=True: (scores, (K,) int64 voted_hit_c per slot, 0 outside S).  Host only (numpy)."""
+    cid = _ids_array(ids)
+    vote = _check_vote(vote)
+    lg = np.array(logits.detach().cpu() if isinstance(logits, torch.Tensor) else logits)
+    slots = _cue_slots(torch.from_numpy(lg), expected, cid).astype(np.int64)
+    mask = int(_subset_masks([subset], cid)[0])
+    k = int(cid.shape[0])
+    s_slots = np.array([i for i in range(k) if mask >> i & 1], dtype=np.int64)
+    in_s = np.zeros(k, dtype=bool)
+    in_s[s_slots] = True
+    keep = (slots < 0) | in_s[np.maximum(slots, 0)]
+    lg, e = lg[keep], slots[keep]
+    n = int(e.shape[0])
+    pred = np.where(np.isfinite(lg).all(axis=1), s_slots[np.argmax(lg[:, s_slots], axis=1)], -1) if n else np.zeros(0, np.int64)
+    entered = np.zeros((n, k), dtype=np.int64)
+    entered[np.nonzero(pred >= 0)[0], pred[pred >= 0]] = 1
+    in_ring = np.cumsum(entered, axis=0)                              # per slot, entries among the last `vote` kept rows
+    in_ring[vote:] -= in_ring[:-vote].copy()
+    voted = np.where(in_ring.max(axis=1) > 0, in_ring.argmax(axis=1), -1) if n else np.zeros(0, np.int64)
+    cue = e >= 0
+    n_c = np.bincount(e[cue], minlength=k)
+    hit_c = np.bincount(e[cue & (voted == e)], minlength=k)
+    worst = -1
+    for c in np.nonzero(n_c)[0].tolist():
+        if worst < 0 or int(hit_c[c]) * int(n_c[worst]) < int(hit_c[worst]) * int(n_c[c]):
+            worst = c
+    out = dict(n_cue=cue.sum(), hit=(cue & (pred == e)).sum(), voted_hit=hit_c.sum(), classes_scored=np.count_nonzero(n_c),
+               worst_class=cid[worst] if worst >= 0 else -1, worst_hit=hit_c[worst] if worst >= 0 else 0,
+               worst_n=n_c[worst] if worst >= 0 else 0)
+    assert tuple(out) == SUBSET_SCORE_KEYS
+    out = {key: int(v) for key, v in out.items()}
+    out["size"] = int(s_slots.shape[0])
+    return (out, hit_c.astype(np.int64)) if per_class else out
+
+
+def _subsets_dev(logits: torch.Tensor, slots: np.ndarray, k: int, masks: np.ndarray, vote: int, per_class: bool):
+    """the device side of `sweep_subsets` (one call of cp_online_subset_sweep) -> scores (G, 7) int64 on the host (worst_class
+    a slot), voted hits per class (G, 64) int32 on the device or None"""
+    lib = _lib.load()
+    dev, m, g = logits.device, int(logits.shape[0]), int(masks.shape[0])
+    with torch.cuda.device(dev):
+        exp_d = torch.from_numpy(slots).to(dev)
+        masks_d = torch.from_numpy(masks.view(np.int64)).to(dev)
+        scratch = torch.empty(lib.cp_online_subset_sweep_scratch_bytes(m), dtype=torch.uint8, device=dev)
+        scores = torch.empty(g, _lib.CP_ONLINE_SUBSET_SCORES, dtype=torch.int64, device=dev)
+        hits = torch.empty(g, MAX_CLASSES, dtype=torch.int32, device=dev) if per_class else None
+        _lib.check(lib.cp_online_subset_sweep(logits.data_ptr(), int(logits.stride(0)), m, k, exp_d.data_ptr(), masks_d.data_ptr(),
+                                              g, vote, scratch.data_ptr(), scratch.numel(), scores.data_ptr(),
+                                              hits.data_ptr() if per_class else None,
+                                              torch.cuda.current_stream(dev).cuda_stream), "cp_online_subset_sweep")
+        return scores.cpu().numpy(), hits
+
+
+def sweep_subsets(logits, expected, ids, subsets, vote: int = VOTE, per_class: bool = False):
+    """Score many class subsets of one cued recording in one pass on the device (cp_online_subset_sweep: one wave per subset).
+    logits (M, K) f32 on the GPU, what `push(..., return_logits=True)` returned for the recording; expected (M,) as
+    `expected_commands` gives it; ids the K ascending class ids of the columns; subsets a sequence of collections of class ids,
+    or a (G,) uint64 array of slot masks (bit k = ids[k]); vote the ring length.  Everything is checked before anything is
+    enqueued: an id that is not among ids, an empty subset and more than MAX_SUBSETS subsets are refused with a ValueError.
+    Returns {key: (G,) int64 array} with the keys of SUBSET_SCORE_KEYS and `size`: subset g's entry is `score_subset` of it
+    (worst_class a class id).  per_class=True: (scores, hits) with hits (G, K) int32 on the GPU, voted_hit_c per slot.  M = 0:
+    what `score_subset` gives for no rows (zeros, worst_class -1), without a launch.  One host synchronisation: the copy of the
+    score table."""
+    cid = _ids_array(ids)
+    vote = _check_vote(vote)
+    masks = _subset_masks(subsets, cid)
+    slots = _cue_slots(logits, expected, cid)
+    g, m, k = int(masks.shape[0]), int(logits.shape[0]), int(cid.shape[0])
+    if m == 0:
+        scores = np.zeros((g, len(SUBSET_SCORE_KEYS)), dtype=np.int64)
+        scores[:, SUBSET_SCORE_KEYS.index("worst_class")] = -1
+        hits = torch.zeros(g, MAX_CLASSES, dtype=torch.int32, device=logits.device) if per_class else None
+    else:
+        if logits.device.type != "cuda":
+            raise ValueError("logits must be on the GPU")
+        if logits.stride(1) != 1 or (m > 1 and logits.stride(0) < logits.shape[1]):
+            logits = logits.contiguous()
+        scores, hits = _subsets_dev(logits, slots, k, masks, vote, per_class)
+    out = {key: scores[:, i].copy() for i, key in enumerate(SUBSET_SCORE_KEYS)}
+    out["worst_class"] = np.where(out["worst_class"] >= 0, cid[np.clip(out["worst_class"], 0, k - 1)], -1)
+    out["size"] = _mask_sizes(masks)
+    return (out, hits[:, :k]) if per_class else out
+
+
+def rank_subsets(scores) -> np.ndarray:
+    """The order in which to prefer the subsets of one `sweep_subsets` table; this function is the policy's definition.  First
+    the subsets every class of which has a cue row (classes_scored == size), then by larger worst_hit / max(worst_n, 1), then
+    by larger voted_hit / max(n_cue, 1), then by larger hit / max(n_cue, 1) (float64 ratios), then by smaller index.
+    Returns the (G,) int64 indices, best first.  Host only (numpy)."""
+    sc = {key: np.asarray(scores[key], dtype=np.int64).reshape(-1) for key in SUBSET_SCORE_KEYS + ("size",)}
+    cues = np.maximum(sc["n_cue"], 1)
+    complete = sc["classes_scored"] == sc["size"]
+    keys = (sc["hit"] / cues, sc["voted_hit"] / cues, sc["worst_hit"] / np.maximum(sc["worst_n"], 1), complete.astype(np.float64))
+    # (lexsort: the last key first; it is stable, so equal subsets stay in index order)
+    return np.lexsort(tuple(-key for key in keys)).astype(np.int64)
+
+
+def _search_masks(k: int, score, min_size: int = 2, max_size=None, require: int = 0, exhaustive: int = 200_000, beam: int = 256,
+                  keep: int = 8, max_call: int = MAX_SUBSETS) -> list:
+    """The candidate generation of `search_grasp_sets` over slot masks of k slots; `score(masks (G,) uint64) -> scores` is what
+    `sweep_subsets` returns for them and is called with at most max_call masks; require is a mask.  One record per size:
+    dict(size, exhaustive, n_candidates, best=[(mask, {key: int})] in `rank_subsets` order)."""
+    import itertools
+    import math
+    max_size = k if max_size is None else max_size
+    for name, v in (("min_size", min_size), ("max_size", max_size), ("exhaustive", exhaustive), ("beam", beam), ("keep", keep)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(f"{name} must be an int >= 1")
+    n_req = bin(require).count("1")
+    if not min_size <= max_size <= k:
+        raise ValueError(f"sizes must satisfy min_size <= max_size <= {k} classes")
+    if min_size < n_req:
+        raise ValueError(f"min_size must be at least the {n_req} required classes")
+    free = [i for i in range(k) if not require >> i & 1]
+    bits = np.left_shift(np.uint64(1), np.arange(k, dtype=np.uint64))
+    out, prev = [], None
+    for size in range(int(min_size), int(max_size) + 1):
+        complete = math.comb(k - n_req, size - n_req) <= exhaustive
+        if complete:
+            combos = list(itertools.combinations(free, size - n_req))
+            combos = np.array(combos, dtype=np.uint64).reshape(len(combos), size - n_req)
+            masks = np.left_shift(np.uint64(1), combos).sum(axis=1, dtype=np.uint64) | np.uint64(require)
+        elif prev is None:
+            raise ValueError(f"size {size} has more than exhaustive={exhaustive} candidates and there is no smaller size to extend")
+        else:
+            grown = prev[:beam, None] | bits[None, :]
+            masks = np.unique(grown[(prev[:beam, None] & bits[None, :]) == 0])       # (ascending, each once)
+        parts = [score(masks[lo:lo + max_call]) for lo in range(0, masks.shape[0], max_call)]
+        sc = {key: np.concatenate([np.asarray(p[key]) for p in parts]) for key in SUBSET_SCORE_KEYS + ("size",)}
+        order = rank_subsets(sc)
+        out.append(dict(size=size, exhaustive=bool(complete), n_candidates=int(masks.shape[0]),
+                        best=[(int(masks[g]), {key: int(sc[key][g]) for key in sc}) for g in order[:keep]]))
+        prev = masks[order]
+    return out
+
+
+def search_grasp_sets(logits, expected, ids, min_size: int = 2, max_size=None, vote: int = VOTE, require=(),
+                      exhaustive: int = 200_000, beam: int = 256, keep: int = 8) -> list:
+    """Which grasps to keep: the best class subsets of every size min_size..max_size (None: all K) for a cued recording, by
+    `rank_subsets` over `sweep_subsets`.  Sizes go in ascending order.  A size with at most `exhaustive` subsets that contain
+    the ids of `require` is enumerated completely (in itertools.combinations order of slots); a larger size takes the one-class
+    extensions of the previous size's best `beam` subsets, each once, in ascending mask order; ValueError if the first size is
+    already too large.  Returns one record per size: dict(size, exhaustive (bool), n_candidates, best) with best the `keep`
+    best as (ids tuple, scores dict) in rank order; the ids of a result are what `set_classes(ids=...)` takes."""
+    cid = _ids_array(ids)
+    vote = _check_vote(vote)
+    _cue_slots(logits, expected, cid)
+    require = tuple(require)
+    need = int(_subset_masks([require], cid)[0]) if require else 0
+    found = _search_masks(int(cid.shape[0]), lambda masks: sweep_subsets(logits, expected, cid, masks, vote), min_size, max_size,
+                          need, exhaustive, beam, keep)
+    for rec in found:
+        rec["best"] = [(tuple(int(cid[i]) for i in range(cid.shape[0]) if mask >> i & 1), sc) for mask, sc in rec["best"]]
+    return found

@@ -700,6 +700,47 @@ int cp_online_gate_sweep(const float* logits, int32_t ldl, int64_t n_rows, int32
                          int32_t* commands,                     /* optional (n_configs, n_rows): slot or -1 */
                          void* stream);
 
+/* ---- grasp-set search: many class subsets of one cued recording, scored on the device --------------------------------------
+ * Which grasps to keep is a search over subsets of the K class slots, and a subset's score is an independent exact integer
+ * walk over the same logits.  The sweep runs n_subsets of them in one pair of launches (os_rows_kernel: a row's slots in
+ * descending logit order, once per row; os_sweep_kernel: one wave per subset) and only a table of integer counters leaves the
+ * device.  score_subset of contrastiveprosthetics_amd/online.py is the definition.  For the subset S given by the bits of
+ * subsets[g] (bit k = slot k):
+ * - Kept rows.  Row j is kept if expected_slot[j] is negative or a slot of S.  A row cued for a slot outside S is dropped, as
+ *   though it had not been recorded; a kept row with a negative expected_slot, or one >= n_classes, feeds the ring and is not
+ *   scored.
+ * - Raw prediction of a kept row: the first maximum of its logits over the slots of S in ascending slot order (compared with >,
+ *   the lowest slot wins a tie: the rule of the decoders and the gate), or none (-1) if any of the row's n_classes logits is not
+ *   finite.
+ * - Vote: the decoders' ring from an empty ring.  Every kept row's prediction enters, none included (it takes a place and does
+ *   not vote); the oldest entry leaves once `vote` entries are in.  The voted prediction is the slot with the most entries in
+ *   the ring, the smallest slot among equals, none if no slot has an entry.  For finite logits that is cp_online_gate_push with
+ *   every gate open over the kept rows and the columns of S.
+ * - scores[g], in this order: n_cue (kept rows with expected_slot in S), hit (of those, raw prediction == expected_slot),
+ *   voted_hit (of those, voted prediction == expected_slot), classes_scored (slots of S with a cue row), worst_class,
+ *   worst_hit, worst_n: the slot of S, among those with n_c > 0 cue rows, with the smallest voted recall voted_hit_c / n_c
+ *   (fractions compared by cross-multiplication in 64 bits, the smallest slot among equals), its voted_hit_c and its n_c;
+ *   -1, 0, 0 if no slot of S has a cue row.  class_hits[g][k], if given, is voted_hit_k for all 64 k (0 outside S).
+ * - A subset's results do not depend on the other subsets in the call.
+ * - The host checks n_classes in 1..64 and <= ldl, n_subsets in 1..CP_ONLINE_SUBSET_SWEEP_MAX_SUBSETS, vote in
+ *   1..CP_ONLINE_MAX_VOTE, n_rows in 1..2^31-1, the size and 16-byte alignment of scratch and the pointers (class_hits may be
+ *   NULL), and returns CP_ERR_ARG with a cp_last_error that names the entry before anything is enqueued.  It never allocates
+ *   and never synchronises.
+ * - `subsets` and `expected_slot` lie on the device, where the host cannot check them, and the kernel checks a value before it
+ *   indexes with it: a mask that is 0 or has a bit at or above n_classes gets all seven scores -1 and its row of class_hits
+ *   is not written. */
+#define CP_ONLINE_SUBSET_SCORES 7
+#define CP_ONLINE_SUBSET_SWEEP_MAX_SUBSETS 1048576
+/* bytes of the sweep's scratch (256-byte aligned): 64 per row */
+size_t cp_online_subset_sweep_scratch_bytes(int64_t n_rows);
+int cp_online_subset_sweep(const float* logits, int32_t ldl, int64_t n_rows, int32_t n_classes,
+                           const int32_t* expected_slot,   /* (n_rows) device: slot, or negative = kept, unscored */
+                           const uint64_t* subsets,        /* (n_subsets) device: bit k = slot k */
+                           int32_t n_subsets, int32_t vote, void* scratch, size_t scratch_bytes,
+                           int64_t* scores,                /* (n_subsets, CP_ONLINE_SUBSET_SCORES) device */
+                           int32_t* class_hits,            /* optional (n_subsets, 64) device */
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

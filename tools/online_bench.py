@@ -23,6 +23,10 @@ the gate's launch alone (CommandGate.apply on the logits of one push).
 With --gate-sweep the gate sweep (sweep_gate, csrc/online_gate.cuh og_sweep_kernel) is timed against the way without it: G
 CommandGate.apply calls one after another over the same logits plus the copy of each one's commands to the host; synthetic
 cued logits of 8 classes, 6,000 and 60,000 windows, G = 64, 256 and 1,024 configs, every timed case under a time limit of its own.
+With --subset-sweep the grasp-set search's sweep (sweep_subsets, csrc/online_subsets.cuh) is timed on synthetic cued logits of
+41 classes, 6,000 and 20,500 windows, G = 64, 1,024, 10,660 (all triples) and 112,750 (all pairs, triples and quadruples)
+subsets at vote 25; for G = 64 the same scores are also computed the way without it (per subset a row and column select plus
+a one-config sweep_gate), must be equal, and the ratio of the two times is stated.
 Each push is timed from the host with a synchronisation behind it (the latency a control loop sees); kernels per push are
 counted with torch.profiler over a few pushes.  One JSON line per case, and a table with --out.
 
@@ -33,6 +37,7 @@ counted with torch.profiler over a few pushes.  One JSON line per case, and a ta
     python tools/online_bench.py --enroll --iters 10 --out profiles/online_enroll.txt
     python tools/online_bench.py --gate --iters 200 --out profiles/online_gate_latency.txt
     python tools/online_bench.py --gate-sweep --iters 20 --out profiles/online_gate_sweep.txt
+    python tools/online_bench.py --subset-sweep --iters 20 --out profiles/online_subset_sweep.txt
 """
 import argparse
 import json
@@ -87,12 +92,15 @@ def main():
     ap.add_argument("--enroll", action="store_true", help="class enrolment: time, one-pass windows, accuracy on a synthetic person")
     ap.add_argument("--gate", action="store_true", help="the command gate against the ungated push with logits")
     ap.add_argument("--gate-sweep", action="store_true", help="sweep_gate against G CommandGate.apply calls in turn")
+    ap.add_argument("--subset-sweep", action="store_true", help="sweep_subsets, and for 64 subsets a select + sweep_gate per subset")
     ap.add_argument("--case-seconds", type=float, default=150.0, help="--gate-sweep: time limit of each timed case")
     a = ap.parse_args()
     if a.enroll:
         return enroll_main(a)
     if a.gate_sweep:
         return gate_sweep_main(a)
+    if a.subset_sweep:
+        return subset_sweep_main(a)
     torch.manual_seed(0)
     e = Engine(adabn=False, dtype="f32", device="cuda:0")
     e.init_parameters(1)
@@ -519,6 +527,68 @@ def gate_sweep_main(a):
             for r in rows:
                 f.write(f"{r['windows']:>7} {r['configs']:>7} {r['sweep_ms']:>9.3f} {r['sweep_reps']:>5} {r['sequential_ms']:>14.1f} "
                         f"{r['sequential_reps']:>5} {r['sequential_configs_done']:>6} {r['ratio']:>8.1f}\n")
+
+
+def subset_sweep_main(a):
+    """one sweep_subsets call (score table on the host) for growing numbers of subsets of 41 classes; for 64 subsets also the
+    composition: per subset a row and column select plus a one-config sweep_gate, whose hit and n_cue must equal the sweep's
+    voted_hit and n_cue.  Every timed case has its own time limit (--case-seconds): repetitions stop when it is used up."""
+    import itertools
+    from contrastiveprosthetics_amd.online import sweep_gate, sweep_subsets
+    K, vote = 41, 25
+    ids = np.arange(K)
+    sets = {n: np.array([sum(1 << i for i in c) for c in itertools.combinations(range(K), n)], dtype=np.uint64) for n in (2, 3, 4)}
+    rng = np.random.default_rng(0)
+    cases = {64: rng.choice(sets[3], 64, replace=False), 1024: rng.choice(sets[3], 1024, replace=False), 10660: sets[3],
+             112750: np.concatenate([sets[2], sets[3], sets[4]])}
+    assert [len(v) for v in cases.values()] == list(cases)
+    rows = []
+
+    def timed(fn, reps):
+        fn()                                                     # (returns host arrays: it has synchronised)
+        ts, t_case = [], time.perf_counter()
+        while len(ts) < reps and (not ts or time.perf_counter() - t_case < a.case_seconds):
+            t0 = time.perf_counter()
+            fn()
+            ts.append(time.perf_counter() - t0)
+        return float(np.median(ts)) * 1e3, len(ts)
+
+    for m in (6000, 20500):
+        logits, exp = _cued_logits(m, K)
+        for G, masks in cases.items():
+            ms, reps = timed(lambda: sweep_subsets(logits, exp, ids, masks, vote=vote), a.iters)
+            r = dict(windows=m, subsets=G, sweep_ms=round(ms, 3), sweep_reps=reps)
+            if G == 64:
+                members = [np.array([i for i in range(K) if int(mk) >> i & 1]) for mk in masks]
+
+                def composed():
+                    out = []
+                    for s in members:
+                        keep = (exp < 0) | np.isin(exp, s)
+                        sub = logits[torch.from_numpy(keep).to(logits.device)][:, torch.from_numpy(s).to(logits.device)].contiguous()
+                        sc = sweep_gate(sub, exp[keep], s, [dict(vote=vote)])
+                        out.append((int(sc["n_cue"][0]), int(sc["hit"][0])))
+                    return out
+
+                got = sweep_subsets(logits, exp, ids, masks, vote=vote)
+                if composed() != list(zip(got["n_cue"].tolist(), got["voted_hit"].tolist())):
+                    raise SystemExit(f"the composition's scores differ from the sweep's at {m} windows")
+                cms, creps = timed(composed, min(a.iters, 5))
+                r.update(composed_ms=round(cms, 1), composed_reps=creps, ratio=round(cms / ms, 1), scores_equal=True)
+            print(json.dumps(r), flush=True)
+            rows.append(r)
+    if a.out:
+        dev = torch.cuda.get_device_name(0)
+        with open(a.out, "w") as f:
+            f.write(f"# tools/online_bench.py --subset-sweep --iters {a.iters} --case-seconds {a.case_seconds:g} on {dev}\n")
+            f.write("# synthetic cued logits, 41 classes, vote 25; sweep = one sweep_subsets call (masks in, score table on the host),\n"
+                    "# wall time, median over reps; 10660 = all triples, 112750 = all pairs, triples and quadruples.  composed (64\n"
+                    "# subsets only) = per subset a row and column select plus a one-config sweep_gate; its n_cue and hit equal the\n"
+                    "# sweep's n_cue and voted_hit (checked in this run); ratio = composed / sweep\n")
+            f.write(f"{'windows':>7} {'subsets':>7} {'sweep_ms':>9} {'reps':>5} {'composed_ms':>12} {'reps':>5} {'ratio':>8}\n")
+            for r in rows:
+                tail = f"{r['composed_ms']:>12.1f} {r['composed_reps']:>5} {r['ratio']:>8.1f}" if "ratio" in r else f"{'-':>12} {'-':>5} {'-':>8}"
+                f.write(f"{r['windows']:>7} {r['subsets']:>7} {r['sweep_ms']:>9.3f} {r['sweep_reps']:>5} {tail}\n")
 
 
 def streams_main(a, e, stream, mean, std, classes):
