@@ -83,10 +83,16 @@ class cp_online_gate_config(C.Structure):
                 ("weight", C.c_int32), ("min_margin", C.c_float)]
 
 
+class cp_online_drive_config(C.Structure):
+    _fields_ = [("smooth", C.c_int32), ("on_level", C.c_int32), ("off_level", C.c_int32), ("rise", C.c_int32), ("fall", C.c_int32),
+                ("bad_after", C.c_int32), ("good_after", C.c_int32)]
+
+
 CP_ONLINE_MAX_CLASSES, CP_ONLINE_MAX_VOTE, CP_ONLINE_MAX_WINDOWS, CP_ONLINE_STRIDE = 64, 256, 256, 20
 CP_ONLINE_MULTI_MAX_STREAMS, CP_ONLINE_MULTI_MAX_ROWS = 256, 65536
 CP_ONLINE_GATE_SCORES, CP_ONLINE_GATE_SWEEP_MAX_CONFIGS = 10, 65536
 CP_ONLINE_SUBSET_SCORES, CP_ONLINE_SUBSET_SWEEP_MAX_SUBSETS = 7, 1048576
+CP_ONLINE_DRIVE_ONE, CP_ONLINE_DRIVE_MAX_SMOOTH = 4096, 256
 
 SYMBOLS = {
     "cp_version": (C.c_int, []),
@@ -182,6 +188,13 @@ SYMBOLS = {
     "cp_online_gate_reset": (C.c_int, [_P(cp_online_gate_config), C.c_int32, _fp, C.c_size_t, C.c_int32, _fp]),
     "cp_online_gate_push": (C.c_int, [_P(cp_online_gate_config), C.c_int32, _fp, C.c_size_t, _fp, C.c_int32, _fp, _fp, C.c_int32,
                                       _fp, _fp, _fp, _fp, _fp]),
+    "cp_online_drive_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "cp_online_drive_set_profile": (C.c_int, [_P(cp_online_drive_config), C.c_int32, _fp, C.c_size_t, C.c_int32, _P(C.c_int32),
+                                              C.c_int32, _P(C.c_float), _P(C.c_float), _P(C.c_int32), _P(C.c_float), _P(C.c_float),
+                                              _fp]),
+    "cp_online_drive_reset": (C.c_int, [_P(cp_online_drive_config), C.c_int32, _fp, C.c_size_t, C.c_int32, _fp]),
+    "cp_online_drive_push": (C.c_int, [_P(cp_online_drive_config), C.c_int32, _fp, C.c_size_t, _fp, C.c_int32, _fp, _fp, _fp,
+                                       C.c_int32, _fp, _fp, _fp, _fp]),
     "cp_online_gate_sweep_scratch_bytes": (C.c_size_t, [C.c_int64]),
     "cp_online_gate_sweep": (C.c_int, [_fp, C.c_int32, C.c_int64, C.c_int32, _fp, _fp, _fp, C.c_int32, _fp, C.c_size_t, _fp, _fp,
                                        _fp]),

@@ -26,6 +26,7 @@
 #include "online_multi_adapt.cuh"
 #include "online_enroll.cuh"
 #include "online_gate.cuh"
+#include "online_drive.cuh"
 #include "online_subsets.cuh"
 
 static thread_local char g_err[512] = "";

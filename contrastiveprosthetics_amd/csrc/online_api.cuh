@@ -1,6 +1,6 @@
 // Host layer of the online decoders (include/cpnative.h, cp_online_*): workspace layout, argument checks, launch chains and
 // the extern "C" entries of the folded, adaptive, multi-stream and adaptive multi-stream decoders, class enrolment, the
-// command gate, the gate sweep and the subset sweep.  Host code only; api.hip includes it behind its own helpers (fail, CK, CKL) and encoder_api.cuh's (align256, fcK),
+// command gate, the grasp drive, the gate sweep and the subset sweep.  Host code only; api.hip includes it behind its own helpers (fail, CK, CKL) and encoder_api.cuh's (align256, fcK),
 // so the library stays one translation unit.  The four decoders share one workspace description (OlWS, ol_carve), one
 // parameter check, one set of front-end arguments, one folded chain and one unfolded weight copy; what an entry adds is its
 // name in the refusals and the kernels it launches.
@@ -1062,5 +1062,112 @@ extern "C" int cp_online_subset_sweep(const float* logits, int32_t ldl, int64_t 
     a.n_rows = n_rows; a.n_subsets = n_subsets; a.K = n_classes; a.vote = vote; a.scores = (long long*)scores; a.class_hits = class_hits;
     hipLaunchKernelGGL(os_sweep_kernel, dim3((n_subsets + OS_WAVES - 1) / OS_WAVES), dim3(64 * OS_WAVES), 0, (hipStream_t)stream, a);
     CKL("os_sweep_kernel");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// grasp drive (csrc/online_drive.cuh): one OdState per stream in a workspace of its own, behind any decoder's windows and the
+// class the hand follows
+// ---------------------------------------------------------------------------------------
+static_assert(OD_MAXK == CP_ONLINE_MAX_CLASSES && OD_MAXSMOOTH == CP_ONLINE_DRIVE_MAX_SMOOTH && OD_MAXM == CP_ONLINE_MAX_WINDOWS &&
+              OD_ONE == CP_ONLINE_DRIVE_ONE && OD_C == CP_EMG_DIM, "drive limits");
+static_assert(sizeof(OdState) == 4 * (8 + 16 + OD_MAXK + 48 + OD_MAXK * OD_C + OD_MAXK * OD_C / 4 + OD_MAXSMOOTH),
+              "OdState is 1352 words (GraspDrive.state reads it back)");
+static_assert(sizeof(OdConfig) == sizeof(cp_online_drive_config) && sizeof(OdProfileArgs) <= 4096, "drive arguments");
+
+static int od_check(const char* who, const cp_online_drive_config* c, int32_t n_streams, void* ws, size_t ws_bytes) {
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (!c || !ws) return bad("config and workspace are required");
+    if (n_streams < 1 || n_streams > CP_ONLINE_MULTI_MAX_STREAMS) return bad("n_streams outside 1..256");
+    if (c->smooth < 1 || c->smooth > CP_ONLINE_DRIVE_MAX_SMOOTH) return bad("smooth outside 1..256");
+    if (c->on_level < 0 || c->on_level > CP_ONLINE_DRIVE_ONE) return bad("on_level outside 0..4096");
+    if (c->off_level < 0 || c->off_level > CP_ONLINE_DRIVE_ONE) return bad("off_level outside 0..4096");
+    if (c->off_level > c->on_level) return bad("off_level must not exceed on_level");
+    if (c->rise < 1 || c->rise > CP_ONLINE_DRIVE_ONE) return bad("rise outside 1..4096");
+    if (c->fall < 1 || c->fall > CP_ONLINE_DRIVE_ONE) return bad("fall outside 1..4096");
+    if (c->bad_after < 1 || c->bad_after > 65535) return bad("bad_after outside 1..65535");
+    if (c->good_after < 1 || c->good_after > 65535) return bad("good_after outside 1..65535");
+    if ((uintptr_t)ws % 256) return bad("workspace not 256-byte aligned");
+    if (ws_bytes < (size_t)n_streams * sizeof(OdState)) return bad("workspace too small");
+    return 0;
+}
+
+static OdConfig od_config(const cp_online_drive_config* c) {
+    OdConfig o;
+    o.smooth = c->smooth; o.on_level = c->on_level; o.off_level = c->off_level; o.rise = c->rise; o.fall = c->fall;
+    o.bad_after = c->bad_after; o.good_after = c->good_after;
+    return o;
+}
+
+extern "C" size_t cp_online_drive_workspace_bytes(int32_t n_streams) {
+    if (n_streams < 1) n_streams = 1;
+    return align256((size_t)n_streams * sizeof(OdState));
+}
+
+extern "C" int cp_online_drive_set_profile(const cp_online_drive_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index,
+                                           const int32_t* ids, int32_t n_classes, const float* rest, const float* span,
+                                           const int32_t* weight, const float* low, const float* high, void* stream) {
+    const char* who = "cp_online_drive_set_profile";
+    if (int e = od_check(who, cfg, n_streams, ws, ws_bytes)) return e;
+    if (int e = ol_check_index(who, index, n_streams)) return e;
+    if (!ids || !rest || !span || !weight || !low || !high || n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES)
+        return ol_fail(CP_ERR_ARG, who, "1..64 classes, with ids, rest, span, weight, low and high");
+    for (int k = 0; k < n_classes; ++k)
+        if (ids[k] < 0 || ids[k] == INT32_MAX || (k > 0 && ids[k] <= ids[k - 1]))
+            return ol_fail(CP_ERR_ARG, who, "ids must be ascending, distinct and in 0..2^31-2");
+    for (int c = 0; c < OD_C; ++c) {
+        if (!std::isfinite(rest[c])) return ol_fail(CP_ERR_ARG, who, "rest must be finite");
+        if (std::isnan(low[c]) || std::isnan(high[c]) || low[c] > high[c]) return ol_fail(CP_ERR_ARG, who, "low and high must not be NaN, low <= high");
+    }
+    for (int i = 0; i < n_classes * OD_C; ++i)
+        if (weight[i] < 0 || weight[i] > 255) return ol_fail(CP_ERR_ARG, who, "weight outside 0..255");
+    OdProfileArgs p{};
+    p.K = n_classes;
+    for (int k = 0; k < n_classes; ++k) p.ids[k] = ids[k];
+    for (int c = 0; c < OD_C; ++c) {
+        p.par[c] = rest[c];
+        p.par[16 + c] = low[c];
+        p.par[32 + c] = high[c];
+    }
+    for (int first = 0; first < OD_MAXK; first += OD_PROFILE_SLOTS) {
+        p.first = first;
+        for (int i = 0; i < OD_PROFILE_SLOTS * OD_C; ++i) {
+            const bool on = first * OD_C + i < n_classes * OD_C;
+            p.span[i] = on ? span[first * OD_C + i] : 0.f;
+            p.weight[i] = on ? (unsigned char)weight[first * OD_C + i] : (unsigned char)0;
+        }
+        hipLaunchKernelGGL(od_set_profile_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (OdState*)ws + index, p);
+        CKL("od_set_profile_kernel");
+    }
+    return 0;
+}
+
+extern "C" int cp_online_drive_reset(const cp_online_drive_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index,
+                                     void* stream) {
+    if (int e = od_check("cp_online_drive_reset", cfg, n_streams, ws, ws_bytes)) return e;
+    if (index < -1 || index >= n_streams) return fail(CP_ERR_ARG, "cp_online_drive_reset: stream index outside -1..n_streams-1");
+    hipLaunchKernelGGL(od_reset_kernel, dim3(index < 0 ? n_streams : 1), dim3(64), 0, (hipStream_t)stream, (OdState*)ws,
+                       index < 0 ? 0 : index);
+    CKL("od_reset_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_drive_push(const cp_online_drive_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, const float* windows,
+                                    int32_t ldw, const int32_t* cls, const int32_t* row0, const int32_t* m, int32_t total_rows,
+                                    float* drive, int32_t* active, int32_t* bad, void* stream) {
+    if (int e = od_check("cp_online_drive_push", cfg, n_streams, ws, ws_bytes)) return e;
+    if (total_rows < 0 || total_rows > CP_ONLINE_MULTI_MAX_ROWS) return fail(CP_ERR_ARG, "cp_online_drive_push: total_rows outside 0..65536");
+    if (total_rows == 0) return 0;
+    if (ldw < CP_EMG_DIM) return fail(CP_ERR_ARG, "cp_online_drive_push: ldw must be at least 12");
+    if (!windows || !cls || !row0 || !m || !drive || !active || !bad)
+        return fail(CP_ERR_ARG, "cp_online_drive_push: windows, cls, row0, m, drive, active and bad are required");
+    if ((uintptr_t)windows % 4 || (uintptr_t)cls % 4 || (uintptr_t)row0 % 4 || (uintptr_t)m % 4 || (uintptr_t)drive % 4 ||
+        (uintptr_t)active % 4 || (uintptr_t)bad % 4)
+        return fail(CP_ERR_ARG, "cp_online_drive_push: misaligned argument");
+    OdPushArgs a{};
+    a.states = (OdState*)ws; a.windows = windows; a.cls = cls; a.row0 = row0; a.m = m; a.ldw = ldw; a.total_rows = total_rows;
+    a.drive = drive; a.active = active; a.bad = bad; a.c = od_config(cfg);
+    hipLaunchKernelGGL(od_push_kernel, dim3(n_streams), dim3(64), 0, (hipStream_t)stream, a);
+    CKL("od_push_kernel");
     return 0;
 }

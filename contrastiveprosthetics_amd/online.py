@@ -31,6 +31,10 @@ to keep: it scores many class subsets of the same recording in one pass on the d
 cp_online_subset_sweep, csrc/online_subsets.cuh) as the decoders would decode it with that subset alone (`score_subset` is the
 definition), all subsets of a size where that is affordable and a beam beyond, and ranks them (`rank_subsets`).
 
+`GraspDrive` adds what a hand needs besides the class: a proportional level per window from the normalised windows the
+decoders already emit, and the health of every electrode, on the device behind a gate or a decoder (cp_online_drive_*,
+csrc/online_drive.cuh); `drive_profile` makes its profile from the cued recording enrolment already has.
+
 The number of windows a push emits follows from sample counts alone (`windows_emitted`), so a push never waits for the device:
 its outputs are device tensors on torch's current stream.
 """
@@ -985,6 +989,40 @@ def thresholds_from_logits(logits, labels, ids, keep: float = 0.95) -> dict:
     return out
 
 
+def _packed_rows(views, row0, trusted: bool, width: int):
+    """the rows of one launch as (tensor whose data_ptr is row 0, leading dimension): the (M_s, <= width) views as they lie if
+    they are the packed output of a push (one buffer, stream order, one row stride), else a packed (rows, width) copy.
+    Every view is checked; of a push's own output (trusted) only the first and the last one, which tell its one packed
+    buffer from the per-stream concatenations of a push that had to be split."""
+    live = [(s, v) for s, v in enumerate(views) if v is not None]
+    s0, v0 = live[0]
+    ld = int(v0.stride(0)) if v0.shape[0] > 1 or len(live) > 1 else max(int(v0.shape[1]), 1)
+    ok = ld >= 1
+    for s, v in ((live[0], live[-1]) if trusted else live):
+        ok = ok and v.stride(1) == 1 and (v.shape[0] == 1 or v.stride(0) == ld) and ld >= v.shape[1] \
+            and v.untyped_storage().data_ptr() == v0.untyped_storage().data_ptr() \
+            and v.data_ptr() == v0.data_ptr() + v0.element_size() * ld * int(row0[s] - row0[s0])
+    if ok:
+        return v0, ld
+    buf = torch.zeros(int(sum(v.shape[0] for _, v in live)), width, dtype=v0.dtype, device=v0.device)
+    for s, v in live:
+        buf[int(row0[s]):int(row0[s]) + v.shape[0], :v.shape[1]] = v
+    return buf, width
+
+
+def _rows_on_device(cache: dict, row0: np.ndarray, m: np.ndarray, stream: int, device) -> torch.Tensor:
+    """(row0, m) of one launch as a (2, n_streams) int32 device tensor.  A stream of pushes usually repeats its row counts:
+    device copies are kept (they are only ever read), a fresh one goes through pinned memory."""
+    key = (row0.tobytes(), m.tobytes(), stream)
+    rm = cache.get(key)
+    if rm is None:
+        if len(cache) >= 16:
+            cache.clear()
+        rm = torch.from_numpy(np.stack([row0, m]).astype(np.int32)).pin_memory().to(device, non_blocking=True)
+        cache[key] = rm
+    return rm
+
+
 _GATE_WEIGHTS = {"count": 0, "margin": 1}
 _GATE_KEYS = ("min_cosine", "default", "min_margin", "min_votes", "dwell", "release", "weight", "vote")
 
@@ -1124,13 +1162,7 @@ class CommandGate(_OnStream):
     def _dev_push(self, logits_ptr: int, ldl: int, row0: np.ndarray, m: np.ndarray, rows: int):
         """one launch over `rows` packed rows -> (command, accepted) (2, rows) int32 and (conf, margin) (2, rows) f32"""
         args = self._args()
-        key = (row0.tobytes(), m.tobytes(), self._stream())
-        rm = self._rows_cache.get(key)
-        if rm is None:
-            if len(self._rows_cache) >= 16:
-                self._rows_cache.clear()
-            rm = torch.from_numpy(np.stack([row0, m]).astype(np.int32)).pin_memory().to(self.device, non_blocking=True)
-            self._rows_cache[key] = rm
+        rm = _rows_on_device(self._rows_cache, row0, m, self._stream(), self.device)
         ca = torch.empty(2, rows, dtype=torch.int32, device=self.device)
         cm = torch.empty(2, rows, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.cp_online_gate_push(*args, logits_ptr, ldl, rm[0].data_ptr(), rm[1].data_ptr(), rows, ca[0].data_ptr(),
@@ -1210,24 +1242,8 @@ class CommandGate(_OnStream):
 
     @staticmethod
     def _packed(views, row0, trusted: bool = False):
-        """the rows of one launch as (tensor whose data_ptr is row 0, leading dimension): the views as they lie if they are
-        the packed output of a decoder's push (one buffer, stream order, one row stride), else a packed (rows, 64) copy.
-        Every view is checked; of a decoder's own output (trusted) only the first and the last one, which tell its one
-        packed buffer from the per-stream concatenations of a push it had to split."""
-        live = [(s, v) for s, v in enumerate(views) if v is not None]
-        s0, v0 = live[0]
-        ldl = int(v0.stride(0)) if v0.shape[0] > 1 or len(live) > 1 else max(int(v0.shape[1]), 1)
-        ok = ldl >= 1
-        for s, v in ((live[0], live[-1]) if trusted else live):
-            ok = ok and v.stride(1) == 1 and (v.shape[0] == 1 or v.stride(0) == ldl) and ldl >= v.shape[1] \
-                and v.untyped_storage().data_ptr() == v0.untyped_storage().data_ptr() \
-                and v.data_ptr() == v0.data_ptr() + 4 * ldl * int(row0[s] - row0[s0])
-        if ok:
-            return v0, ldl
-        buf = torch.zeros(int(sum(v.shape[0] for _, v in live)), MAX_CLASSES, dtype=torch.float32, device=v0.device)
-        for s, v in live:
-            buf[int(row0[s]):int(row0[s]) + v.shape[0], :v.shape[1]] = v
-        return buf, MAX_CLASSES
+        """the logits of one launch as (tensor whose data_ptr is row 0, leading dimension), see _packed_rows"""
+        return _packed_rows(views, row0, trusted, MAX_CLASSES)
 
     # ------------------------------------------------------------------ API
     def apply(self, logits):
@@ -1301,6 +1317,369 @@ class CommandGate(_OnStream):
             self.decoder.reset()
             self._dev_reset(-1)
         self._left = self._seen_now()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# grasp drive: a proportional level and the electrodes' health per window (cp_online_drive_*)
+# ---------------------------------------------------------------------------------------------------------------------------
+DRIVE_ONE = _lib.CP_ONLINE_DRIVE_ONE    # full level: levels are integers out of 4096
+_DRIVE_LEVELS = ("on_level", "off_level", "rise", "fall")
+_DRIVE_COUNTS = ("bad_after", "good_after")
+_DRIVE_FOLLOW = ("pred", "voted", "command")
+_OD_WORDS = 8 + 16 + MAX_CLASSES + 48 + MAX_CLASSES * EMG_DIM + MAX_CLASSES * EMG_DIM // 4 + _lib.CP_ONLINE_DRIVE_MAX_SMOOTH
+_OD_RING = _OD_WORDS - _lib.CP_ONLINE_DRIVE_MAX_SMOOTH
+
+
+def _drive_settings(new: dict):
+    """on_level, off_level, rise, fall (fractions of full level) and bad_after, good_after as the C config takes them, or
+    ValueError"""
+    out = []
+    for k in _DRIVE_LEVELS:
+        v = new[k]
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) <= 1.0:
+            raise ValueError(f"{k} must be a fraction in 0..1")
+        out.append(int(np.rint(float(v) * DRIVE_ONE)))
+    if out[1] > out[0]:
+        raise ValueError("off_level must not exceed on_level")
+    if out[2] < 1 or out[3] < 1:
+        raise ValueError(f"rise and fall must be at least 1/{DRIVE_ONE}")
+    for k in _DRIVE_COUNTS:
+        v = new[k]
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= 65535:
+            raise ValueError(f"{k} must be an int in 1..65535")
+        out.append(int(v))
+    return out
+
+
+def _check_profile(profile: dict) -> dict:
+    """a profile (see drive_profile) as the arrays cp_online_drive_set_profile takes, or ValueError"""
+    missing = [k for k in ("ids", "rest", "span", "weight", "low", "high") if k not in profile]
+    if missing:
+        raise ValueError(f"a drive profile holds ids, rest, span, weight, low and high; {missing[0]!r} is missing")
+    ids = _ids_array(profile["ids"])
+    k = ids.shape[0]
+    chan = {n: np.ascontiguousarray(np.asarray(profile[n], dtype=np.float32).reshape(-1)) for n in ("rest", "low", "high")}
+    span = np.ascontiguousarray(np.asarray(profile["span"], dtype=np.float32))
+    weight = np.asarray(profile["weight"])
+    if any(v.shape != (EMG_DIM,) for v in chan.values()) or span.shape != (k, EMG_DIM) or weight.shape != (k, EMG_DIM):
+        raise ValueError(f"rest, low, high: ({EMG_DIM},); span, weight: ({k}, {EMG_DIM})")
+    if not np.isfinite(chan["rest"]).all():
+        raise ValueError("rest must be finite")
+    if np.isnan(chan["low"]).any() or np.isnan(chan["high"]).any() or (chan["low"] > chan["high"]).any():
+        raise ValueError("low and high must not be NaN, low <= high")
+    if weight.dtype.kind not in "iu" or (weight < 0).any() or (weight > 255).any():
+        raise ValueError("weight must hold integers in 0..255")
+    return dict(ids=ids.astype(np.int32), span=span, weight=np.ascontiguousarray(weight.astype(np.int32)), **chan)
+
+
+class GraspDrive(_OnStream):
+    """How hard, next to which grasp: per stream one state machine on the device that reads the normalised windows of every
+    push and the class the hand follows (include/cpnative.h, cp_online_drive_*; one launch more per push, nothing is copied to
+    the host), and reports per window a proportional level `drive` in 0..1, whether the stream is `active`, and `bad`, the mask
+    of electrodes whose windows have left their plausible range.
+
+    source: a `CommandGate` (the drive follows its `command`) or any of the four decoders (it follows `voted`);
+    follow='pred' | 'voted' | 'command' overrides that.  The level of a window is the weighted mean over the class's channels
+    of (x - rest) / span, clamped to 0..1, over the channels that are good; it is averaged over the last `smooth` windows,
+    switches the stream on at `on_level` and off below `off_level`, and moves by at most `rise` up and `fall` down per window.
+    A channel is bad after `bad_after` windows in a row outside [low, high] and good again after `good_after` inside.  Levels
+    are fractions of full level and are kept as integers out of 4096.  With smooth=1, on_level=off_level=0, rise=fall=1 and an
+    open range `drive` is the level of each window on its own.
+
+    profile: what `drive_profile` returns (a dict with ids, rest, span, weight, low, high); on a multi-stream source one for
+    every stream, or a list with one (or None) per stream.  A class id that is not in the profile drives nothing.  A push or
+    reset of the source behind the drive's back makes the next `push` raise `CpNativeError` before anything is enqueued."""
+
+    def __init__(self, source, profile=None, smooth: int = 10, on_level: float = 0.08, off_level: float = 0.04, rise: float = 1.0,
+                 fall: float = 1.0, bad_after: int = 20, good_after: int = 100, follow: Optional[str] = None):
+        self.gate = source if isinstance(source, CommandGate) else None
+        self.source = source
+        self.decoder = source.decoder if self.gate is not None else source
+        for name in ("class_ids", "n_seen", "push"):
+            if not hasattr(self.decoder, name):
+                raise TypeError("GraspDrive wraps a CommandGate, an OnlineDecoder, MultiStreamDecoder or AdaptiveMultiStreamDecoder")
+        if follow is None:
+            follow = "command" if self.gate is not None else "voted"
+        if follow not in _DRIVE_FOLLOW:
+            raise ValueError("follow must be 'pred', 'voted' or 'command'")
+        if follow == "command" and self.gate is None:
+            raise ValueError("follow='command' takes a CommandGate as the source")
+        self.follow = follow
+        self.multi = isinstance(self.decoder.class_ids, (list, tuple))
+        self.n_streams = len(self.decoder.class_ids) if self.multi else 1
+        if isinstance(smooth, bool) or not isinstance(smooth, (int, np.integer)) or not 1 <= int(smooth) <= _lib.CP_ONLINE_DRIVE_MAX_SMOOTH:
+            raise ValueError(f"smooth must be an int in 1..{_lib.CP_ONLINE_DRIVE_MAX_SMOOTH}")
+        self.smooth = int(smooth)
+        self._cfg = _lib.cp_online_drive_config()
+        self._cfg.smooth = self.smooth
+        self._cfg.on_level = self._cfg.off_level = 0
+        self._cfg.rise = self._cfg.fall = DRIVE_ONE
+        self._cfg.bad_after = self._cfg.good_after = 1
+        self.set(on_level=on_level, off_level=off_level, rise=rise, fall=fall, bad_after=bad_after, good_after=good_after)
+        self.device = getattr(self.decoder, "device", None)
+        self.ws = None                                      # allocated with the first launch
+        self._rows_cache = {}
+        self._profile = [None] * self.n_streams
+        self._left = self._seen_now()
+        if profile is not None:
+            each = list(profile) if isinstance(profile, (list, tuple)) else [profile] * self.n_streams
+            if len(each) != self.n_streams:
+                raise ValueError(f"profile: one dict, or a list of {self.n_streams} (None: no profile yet)")
+            for s, p in enumerate(each):
+                if p is not None:
+                    self._install(s, p)
+
+    # ------------------------------------------------------------------ settings
+    def set(self, **kw):
+        """Change on_level, off_level, rise, fall, bad_after or good_after from the next window on (smooth is fixed at
+        construction)."""
+        c = self._cfg
+        new = dict(on_level=c.on_level / DRIVE_ONE, off_level=c.off_level / DRIVE_ONE, rise=c.rise / DRIVE_ONE, fall=c.fall / DRIVE_ONE,
+                   bad_after=c.bad_after, good_after=c.good_after)
+        for k, v in kw.items():
+            if k == "smooth":
+                raise ValueError("smooth is fixed at construction: the ring is laid out by it")
+            if k not in new:
+                raise TypeError(f"set() takes on_level, off_level, rise, fall, bad_after and good_after, not {k!r}")
+            new[k] = v
+        c.on_level, c.off_level, c.rise, c.fall, c.bad_after, c.good_after = _drive_settings(new)
+
+    def _index(self, stream) -> int:
+        if isinstance(stream, bool) or not isinstance(stream, (int, np.integer)) or not 0 <= int(stream) < self.n_streams:
+            raise IndexError(f"stream index must be an int in 0..{self.n_streams - 1}, got {stream!r}")
+        return int(stream)
+
+    def set_profile(self, *args):
+        """set_profile(profile) on a single-stream source, set_profile(stream, profile) on a multi-stream one.  That stream
+        starts again: every channel good, the ring empty, inactive, drive 0."""
+        if len(args) != (2 if self.multi else 1):
+            raise TypeError("set_profile(stream, profile) on a multi-stream source, set_profile(profile) otherwise")
+        self._install(self._index(args[0]) if self.multi else 0, args[-1])
+
+    def _install(self, s: int, profile: dict):
+        p = _check_profile(profile)
+        self._dev_set_profile(s, p)
+        self._profile[s] = p
+
+    # ------------------------------------------------------------------ the device side (one method per C entry)
+    def _args(self):
+        if self.ws is None:
+            self.lib = _lib.load()
+            self.ws = torch.zeros(self.lib.cp_online_drive_workspace_bytes(self.n_streams), dtype=torch.uint8, device=self.device)
+        return C.byref(self._cfg), self.n_streams, self.ws.data_ptr(), self.ws.numel()
+
+    def _dev_set_profile(self, s: int, p: dict):
+        args = self._args()
+        f, i = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        _lib.check(self.lib.cp_online_drive_set_profile(
+            *args, s, p["ids"].ctypes.data_as(i), int(p["ids"].shape[0]), p["rest"].ctypes.data_as(f), p["span"].ctypes.data_as(f),
+            p["weight"].ctypes.data_as(i), p["low"].ctypes.data_as(f), p["high"].ctypes.data_as(f), self._stream()),
+            "cp_online_drive_set_profile")
+
+    def _dev_reset(self, s: int):
+        args = self._args()
+        _lib.check(self.lib.cp_online_drive_reset(*args, s, self._stream()), "cp_online_drive_reset")
+
+    def _dev_push(self, windows_ptr: int, ldw: int, cls_ptr: int, row0: np.ndarray, m: np.ndarray, rows: int):
+        """one launch over `rows` packed rows -> drive (rows,) f32 and (active, bad) (2, rows) int32"""
+        args = self._args()
+        rm = _rows_on_device(self._rows_cache, row0, m, self._stream(), self.device)
+        drive = torch.empty(rows, dtype=torch.float32, device=self.device)
+        ab = torch.empty(2, rows, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.cp_online_drive_push(*args, windows_ptr, ldw, cls_ptr, rm[0].data_ptr(), rm[1].data_ptr(), rows,
+                                                 drive.data_ptr(), ab[0].data_ptr(), ab[1].data_ptr(), self._stream()),
+                   "cp_online_drive_push")
+        return drive, ab
+
+    # ------------------------------------------------------------------ staying in step with the source
+    def _seen_now(self) -> np.ndarray:
+        return np.array(self.decoder.n_seen, dtype=np.int64).reshape(-1).copy()
+
+    def _check_in_step(self):
+        if not np.array_equal(self._seen_now(), self._left):
+            raise _lib.CpNativeError("the source was pushed or reset behind the drive (its n_seen is not what the drive left): the "
+                                     "drive's ring no longer follows the stream; push and reset through the drive, or reset() it")
+
+    def _check_profiles(self, has_rows):
+        for s, rows in enumerate(has_rows):
+            if rows and self._profile[s] is None:
+                raise _lib.CpNativeError(f"stream {s} has windows but no drive profile: set_profile first")
+
+    # ------------------------------------------------------------------ the drive over per-stream windows and classes
+    def _drive(self, wins, cls, trusted: bool = False):
+        """wins, cls: n_streams entries, None or (M_s, 12) f32 windows and (M_s,) int32 class ids -> per stream (drive,
+        active, bad).  trusted: the entries are what the source's own push just returned (their layout is known)."""
+        step = _lib.CP_ONLINE_MAX_WINDOWS
+        ms = []
+        for s, (w, c) in enumerate(zip(wins, cls)):
+            if w is None or c is None:
+                if w is not None or c is not None:
+                    raise ValueError(f"stream {s}: windows and cls go together")
+                ms.append(0)
+                continue
+            if not trusted:
+                if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or w.dim() != 2 or w.shape[1] != EMG_DIM \
+                        or w.device.type != "cuda":
+                    raise ValueError("windows must be (M, 12) float32 tensors on the GPU")
+                if not isinstance(c, torch.Tensor) or c.dtype != torch.int32 or c.dim() != 1 or c.shape[0] != w.shape[0] \
+                        or c.device != w.device:
+                    raise ValueError("cls must be (M,) int32 tensors next to their windows")
+            ms.append(int(w.shape[0]))
+        self._check_profiles(ms)
+        outs = []                                              # per round: per stream (drive, active, bad)
+        for lo in range(0, max(max(ms), 1), step):
+            m = np.array([min(max(n - lo, 0), step) for n in ms], dtype=np.int64)
+            rows = int(m.sum())
+            row0 = np.zeros_like(m)
+            np.cumsum(m[:-1], out=row0[1:])
+            if rows == 0:
+                dev = next((t.device for t in wins if t is not None), self.device)
+                drive, ab = torch.empty(0, dtype=torch.float32, device=dev), torch.empty(2, 0, dtype=torch.int32, device=dev)
+            else:
+                whole = lo == 0 and max(ms) <= step
+                ml = m.tolist()
+                wv = [None if n == 0 else (wins[s] if whole else wins[s][lo:lo + n]) for s, n in enumerate(ml)]
+                cv = [None if n == 0 else (cls[s] if whole else cls[s][lo:lo + n]).unsqueeze(1) for s, n in enumerate(ml)]
+                wbase, ldw = _packed_rows(wv, row0, trusted, EMG_DIM)
+                cbase, ldc = _packed_rows(cv, row0, trusted, 1)
+                if ldc != 1:                                   # (a class id every ldc words: not what the entry takes)
+                    cbase = torch.cat([v for v in cv if v is not None])
+                drive, ab = self._dev_push(wbase.data_ptr(), ldw, cbase.data_ptr(), row0, m, rows)
+            if self.n_streams == 1:
+                outs.append([(drive, ab[0], ab[1])])
+                continue
+            ml = m.tolist()
+            outs.append(list(zip(drive.split(ml), ab[0].split(ml), ab[1].split(ml))))
+        if len(outs) == 1:
+            return outs[0]
+        return [tuple(torch.cat([o[s][i] for o in outs]) for i in range(3)) for s in range(self.n_streams)]
+
+    # ------------------------------------------------------------------ API
+    def apply(self, windows, cls):
+        """The drive alone on tensors the caller already has (of the source's next windows, in order): windows (M, 12) f32 and
+        cls (M,) int32 (class ids, -1: none) on the GPU -> (drive, active, bad); on a multi-stream source lists with one entry
+        per stream (None: no windows) -> one such tuple per stream.  drive (M,) f32 in 0..1, active (M,) int32 0/1, bad (M,)
+        int32, bit c set while channel c is bad."""
+        if self.multi:
+            if isinstance(windows, torch.Tensor) or isinstance(cls, torch.Tensor) or len(windows) != self.n_streams \
+                    or len(cls) != self.n_streams:
+                raise ValueError(f"windows and cls must be sequences of {self.n_streams} entries (None or tensors)")
+            out = self._drive(list(windows), list(cls))
+        else:
+            out = self._drive([windows], [cls])[0]
+        self._left = self._seen_now()
+        return out
+
+    def _class_index(self, return_logits: bool) -> int:
+        """where the class the drive follows sits in the source's tuple (windows asked for)"""
+        return {"pred": 0, "voted": 1, "command": 3 + int(return_logits)}[self.follow]
+
+    def _strip(self, res, driven, return_logits: bool, return_windows: bool):
+        at = 2 + int(return_logits)                            # where the windows sit
+        keep = [x for i, x in enumerate(res) if i != at or return_windows]
+        return tuple(keep) + tuple(driven)
+
+    def push(self, raw, return_logits: bool = False, return_windows: bool = False):
+        """What the source's `push` takes (raw (n, 12), or one chunk per stream) -> the source's tuple(s) extended by drive,
+        active, bad: behind a gate (pred, voted[, logits][, windows], command, accepted, conf, margin, drive, active, bad)."""
+        self._check_in_step()
+        if self.multi:
+            if isinstance(raw, torch.Tensor) or len(raw) != self.n_streams:
+                raise ValueError(f"chunks must be a sequence of {self.n_streams} entries (None or (n, 12) tensors)")
+            self._check_profiles([c is not None and c.shape[0] > 0 for c in raw])
+        else:
+            self._check_profiles([True])
+        res = self.source.push(raw, return_logits=return_logits, return_windows=True)
+        return self._finish(res, return_logits, return_windows)
+
+    def push_packed(self, raw, counts, return_logits: bool = False, return_windows: bool = False):
+        """`push` for samples packed in stream order, as the multi-stream decoders' `push_packed`."""
+        if not self.multi:
+            raise TypeError("push_packed belongs to the multi-stream decoders")
+        self._check_in_step()
+        cnt = np.asarray(counts).reshape(-1)
+        if cnt.shape[0] == self.n_streams:
+            self._check_profiles((cnt > 0).tolist())
+        res = self.source.push_packed(raw, counts, return_logits=return_logits, return_windows=True)
+        return self._finish(res, return_logits, return_windows)
+
+    def _finish(self, res, return_logits: bool, return_windows: bool):
+        self._left = self._seen_now()
+        at, ci = 2 + int(return_logits), self._class_index(return_logits)
+        if self.multi:
+            driven = self._drive([r[at] for r in res], [r[ci] for r in res], trusted=True)
+            return [self._strip(r, d, return_logits, return_windows) for r, d in zip(res, driven)]
+        return self._strip(res, self._drive([res[at]], [res[ci]], trusted=True)[0], return_logits, return_windows)
+
+    def state(self, stream: int = 0) -> dict:
+        """One stream's state as the device holds it, read back (this waits for the device; a test and debugging aid): out
+        (the level, an integer out of 4096), active (0 / 1), bad (the mask), run (the 12 run counters) and ring, the raw
+        levels from the oldest to the newest.  The layout is that of OdState (csrc/online_drive.cuh): int32 K, head, len,
+        active, out, bad, 2 unused, run[16], ids[64], f32 rest[16], low[16], high[16], span[64][12], uint8 weight[64][12],
+        int32 ring[256]."""
+        s = self._index(stream)
+        if self.ws is None:
+            return dict(out=0, active=0, bad=0, run=[0] * EMG_DIM, ring=[])
+        w = self.ws[:self.n_streams * _OD_WORDS * 4].view(torch.int32).reshape(self.n_streams, _OD_WORDS)[s].cpu().numpy()
+        head, n = int(w[1]), int(w[2])
+        ring = w[_OD_RING:]
+        return dict(out=int(w[4]), active=int(w[3]), bad=int(w[5]), run=[int(x) for x in w[8:8 + EMG_DIM]],
+                    ring=[int(ring[(head - n + i) % self.smooth]) for i in range(n)])
+
+    def reset(self, streams=None):
+        """Reset the source (a gate resets its decoder) and the drive (every channel good, ring empty, inactive, drive 0;
+        the profiles stay); on a multi-stream source the listed streams, default all."""
+        if self.multi and streams is not None:
+            idx = sorted({self._index(s) for s in streams})
+            self.source.reset(idx)
+            for s in idx:
+                self._dev_reset(s)
+        else:
+            self.source.reset()
+            self._dev_reset(-1)
+        self._left = self._seen_now()
+
+
+def drive_profile(windows, expected, ids, level: float = 0.9, floor=None, min_windows: int = 25, headroom: float = 4.0) -> dict:
+    """The profile of a `GraspDrive` from a cued recording: windows (N, 12), the normalised windows of the recording
+    (`recording_windows`), and expected (N,), what the cue asked of each (`expected_commands`: a class id, REST or IGNORE).
+    Host only (numpy).  Returns a dict of
+      ids     the class ids, ascending;
+      rest    (12,) the per-channel median over the REST windows;
+      span    (K, 12) the per-channel `level` quantile over the windows cued for class k, minus rest; 0 for a class with fewer
+              than `min_windows` windows (it drives nothing);
+      weight  (K, 12) int32 rint(255 max(span, 0) / max_c span): how much of the class's effort a channel carries;
+      high    (12,) rest + headroom (max seen - rest): above this a channel is not plausible;
+      low     (12,) halfway between `floor` and the lowest value seen; floor is the value of a silent electrode, -mean / std
+              per channel (one value or 12); None: -inf, the range is open below."""
+    cid = _ids_array(ids)
+    w = np.asarray(windows.detach().cpu() if isinstance(windows, torch.Tensor) else windows, dtype=np.float64)
+    e = np.asarray(expected.detach().cpu() if isinstance(expected, torch.Tensor) else expected).reshape(-1)
+    if w.ndim != 2 or w.shape[1] != EMG_DIM or e.shape[0] != w.shape[0]:
+        raise ValueError(f"windows (N, {EMG_DIM}) and expected (N,) go together")
+    if not 0.0 < float(level) <= 1.0:
+        raise ValueError("level must lie in (0, 1]")
+    if not float(headroom) >= 1.0:
+        raise ValueError("headroom must be at least 1")
+    at_rest = w[e == REST]
+    if at_rest.shape[0] == 0:
+        raise ValueError("the recording has no REST windows: the resting level is taken from them")
+    rest = np.median(at_rest, axis=0)
+    span = np.zeros((cid.shape[0], EMG_DIM))
+    for k, c in enumerate(cid):
+        rows = w[e == c]
+        if rows.shape[0] >= max(int(min_windows), 1):
+            span[k] = np.quantile(rows, float(level), axis=0) - rest
+    top = span.max(axis=1, keepdims=True)
+    weight = np.where(top > 0, np.rint(255.0 * np.maximum(span, 0.0) / np.where(top > 0, top, 1.0)), 0.0).astype(np.int32)
+    seen = w[e != IGNORE] if (e != IGNORE).any() else w
+    high = rest + float(headroom) * (seen.max(axis=0) - rest)
+    if floor is None:
+        low = np.full(EMG_DIM, -np.inf)
+    else:
+        low = 0.5 * (np.broadcast_to(np.asarray(floor, dtype=np.float64).reshape(-1), (EMG_DIM,)) + seen.min(axis=0))
+    f = np.float32
+    return dict(ids=cid, rest=rest.astype(f), span=span.astype(f), weight=weight, low=low.astype(f), high=high.astype(f))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

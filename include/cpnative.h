@@ -663,6 +663,61 @@ int cp_online_gate_push(const cp_online_gate_config* cfg, int32_t n_streams, voi
                         int32_t ldl, const int32_t* row0, const int32_t* m, int32_t total_rows, int32_t* command,
                         int32_t* accepted, float* conf, float* margin, void* stream);
 
+/* ---- grasp drive: a proportional level and the electrodes' health per window, behind the decoders and the gate ------------
+ * The gate says which grasp; a hand also needs how hard.  The drive is a stage behind the decoders that reads the normalised
+ * windows a push emits (the per-channel amplitude) and a class id per window (the gate's command, or a decoder's voted or
+ * pred), and keeps one state machine per stream in a workspace of its own: one launch per push for any n_streams <= 256 (one
+ * wave per stream).  The decoders' and the gate's kernels and outputs do not change.  A zeroed workspace is a valid start (no
+ * profile, every channel good, empty ring, inactive, out 0).  cfg.smooth is the same on every call of a workspace.
+ * The profile of a stream (cp_online_drive_set_profile; it survives a reset): ids[K] ascending; rest[12], the resting level
+ * of each channel in window units; span[K][12], full effort minus rest (<= 0 or NaN: the channel is not used for that class);
+ * weight[K][12] in 0..255; low[12], high[12], the plausible range of a channel (-inf / +inf: open).
+ * Per window x[12] with class id g (-1: none), in window order; levels are integers out of CP_ONLINE_DRIVE_ONE; every f32
+ * operation is a single one without contraction, the division the correctly rounded one:
+ *   health     inside_c = isfinite(x_c) && x_c >= low_c && x_c <= high_c.  A good channel that is not inside, or a bad one that
+ *              is, adds 1 to its run counter; otherwise the counter becomes 0.  A counter that reaches bad_after (good -> bad) or
+ *              good_after (bad -> good) flips the status and becomes 0.  bad = the 12-bit mask of bad channels after that.
+ *   raw        k = the slot of g in ids; g == -1 or not in ids: raw = 0.  Otherwise, over the channels with weight[k][c] > 0,
+ *              span[k][c] > 0 and status good: a = fminf(fmaxf((x_c - rest_c) / span[k][c], 0), 1) (NaN -> 0),
+ *              q = (int32) rintf(a * 4096), raw = floor(sum w q / sum w), 0 if no channel counts.
+ *   smooth     raw enters a ring of the last `smooth` values; s = floor(sum of the ring / entries in it).
+ *   hysteresis inactive and s >= on_level: active.  Active and s < off_level: inactive.
+ *   slew       target = active ? s : 0; out moves towards target by at most `rise` upwards or `fall` downwards.
+ *   outputs    drive = (float) out / 4096.f (exact), active (0 / 1), bad (the mask).
+ * So a stream's outputs depend neither on how its rows are cut into calls nor on the streams that share a launch, and with
+ * smooth 1, on_level = off_level = 0, rise = fall = 4096 and an open range drive equals raw / 4096 in every window.
+ * The entries keep no state in the library and validate on the host: a bad argument -- a short workspace included -- returns
+ * CP_ERR_ARG with a cp_last_error that names the entry, before anything is enqueued. */
+#define CP_ONLINE_DRIVE_ONE 4096          /* full level */
+#define CP_ONLINE_DRIVE_MAX_SMOOTH 256    /* ring length */
+typedef struct cp_online_drive_config {
+    int32_t smooth;          /* ring length, 1..256 */
+    int32_t on_level;        /* 0..4096: an inactive stream becomes active at s >= on_level */
+    int32_t off_level;       /* 0..on_level: an active stream becomes inactive at s < off_level */
+    int32_t rise;            /* 1..4096: the most `out` grows in one window */
+    int32_t fall;            /* 1..4096: the most `out` shrinks in one window */
+    int32_t bad_after;       /* 1..65535: windows in a row outside its range before a channel is bad */
+    int32_t good_after;      /* 1..65535: windows in a row inside its range before a bad channel is good again */
+} cp_online_drive_config;
+/* bytes of the drive's workspace (256-byte aligned) for n_streams streams; zero it before the first call */
+size_t cp_online_drive_workspace_bytes(int32_t n_streams);
+/* ids (n_classes) int32 ascending, distinct, >= 0; rest, low, high (12) f32 (rest finite; low, high not NaN, low <= high);
+ * span (n_classes, 12) f32; weight (n_classes, 12) int32 in 0..255: all on the HOST (they travel as kernel arguments).
+ * Installs them for stream `index` and restarts that stream (every channel good, empty ring, inactive, out 0). */
+int cp_online_drive_set_profile(const cp_online_drive_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index,
+                                const int32_t* ids, int32_t n_classes, const float* rest, const float* span,
+                                const int32_t* weight, const float* low, const float* high, void* stream);
+/* restarts stream `index` (every stream for index -1); the profiles stay */
+int cp_online_drive_reset(const cp_online_drive_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index, void* stream);
+/* windows (total_rows, ldw) f32 as a decoder's push emits them (ldw >= 12) and cls (total_rows) int32, a class id or -1 per
+ * row; row0, m (n_streams) int32 on the device: stream s owns the rows row0[s] .. row0[s] + m[s] - 1, m[s] <=
+ * CP_ONLINE_MAX_WINDOWS, total_rows <= CP_ONLINE_MULTI_MAX_ROWS.  drive (total_rows) f32 and active, bad (total_rows) int32
+ * receive the rows' outputs.  A stream with m[s] = 0, without a profile, or whose rows do not lie inside 0..total_rows-1 is
+ * left untouched (its outputs are not written).  Nothing is enqueued for total_rows = 0. */
+int cp_online_drive_push(const cp_online_drive_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, const float* windows,
+                         int32_t ldw, const int32_t* cls, const int32_t* row0, const int32_t* m, int32_t total_rows,
+                         float* drive, int32_t* active, int32_t* bad, void* stream);
+
 /* ---- gate sweep: many gate settings over one cued recording, scored on the device ------------------------------------------
  * A search over the gate's settings is a set of independent runs of the state machine over the same logits.  The sweep runs
  * n_configs of them in one pair of launches (og_rows_kernel: the part of a row no setting enters, once per row; og_sweep_kernel:

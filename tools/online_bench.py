@@ -27,6 +27,10 @@ With --subset-sweep the grasp-set search's sweep (sweep_subsets, csrc/online_sub
 41 classes, 6,000 and 20,500 windows, G = 64, 1,024, 10,660 (all triples) and 112,750 (all pairs, triples and quadruples)
 subsets at vote 25; for G = 64 the same scores are also computed the way without it (per subset a row and column select plus
 a one-config sweep_gate), must be equal, and the ratio of the two times is stated.
+With --drive the grasp drive (GraspDrive.push, csrc/online_drive.cuh) is timed behind gate-wrapped decoders next to the gate
+itself in the same run: ungated, gated and driven pushes of 1 and 25 windows on OnlineDecoder and of 256 streams x 1 window on
+MultiStreamDecoder, plus the drive's launch alone (GraspDrive.apply on the windows and commands of one push).  A driven push
+must launch one kernel more than a gated one.
 Each push is timed from the host with a synchronisation behind it (the latency a control loop sees); kernels per push are
 counted with torch.profiler over a few pushes.  One JSON line per case, and a table with --out.
 
@@ -36,6 +40,7 @@ counted with torch.profiler over a few pushes.  One JSON line per case, and a ta
     python tools/online_bench.py --streams --adapt --iters 100 --out profiles/online_multi_adapt_latency.txt
     python tools/online_bench.py --enroll --iters 10 --out profiles/online_enroll.txt
     python tools/online_bench.py --gate --iters 200 --out profiles/online_gate_latency.txt
+    python tools/online_bench.py --drive --iters 200 --out profiles/online_drive_latency.txt
     python tools/online_bench.py --gate-sweep --iters 20 --out profiles/online_gate_sweep.txt
     python tools/online_bench.py --subset-sweep --iters 20 --out profiles/online_subset_sweep.txt
 """
@@ -50,7 +55,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from contrastiveprosthetics_amd import AdaptiveMultiStreamDecoder, CommandGate, MultiStreamDecoder, OnlineDecoder  # noqa: E402
+from contrastiveprosthetics_amd import (AdaptiveMultiStreamDecoder, CommandGate, GraspDrive, MultiStreamDecoder,  # noqa: E402
+                                        OnlineDecoder)
 from contrastiveprosthetics_amd.engine import Engine                       # noqa: E402
 from contrastiveprosthetics_amd.preprocess import normalize_, preprocess_segments   # noqa: E402
 
@@ -91,6 +97,7 @@ def main():
     ap.add_argument("--counts", default="1,8,64,256", help="--streams: stream counts")
     ap.add_argument("--enroll", action="store_true", help="class enrolment: time, one-pass windows, accuracy on a synthetic person")
     ap.add_argument("--gate", action="store_true", help="the command gate against the ungated push with logits")
+    ap.add_argument("--drive", action="store_true", help="the grasp drive behind gate-wrapped decoders, next to the gate's own cost")
     ap.add_argument("--gate-sweep", action="store_true", help="sweep_gate against G CommandGate.apply calls in turn")
     ap.add_argument("--subset-sweep", action="store_true", help="sweep_subsets, and for 64 subsets a select + sweep_gate per subset")
     ap.add_argument("--case-seconds", type=float, default=150.0, help="--gate-sweep: time limit of each timed case")
@@ -112,6 +119,8 @@ def main():
     rows = []
     if a.gate:
         return gate_main(a, e, stream, mean, std, classes)
+    if a.drive:
+        return drive_main(a, e, stream, mean, std, classes)
     if a.adapt and a.streams:
         return streams_adapt_main(a, e, stream, mean, std, classes)
     if a.adapt:
@@ -429,6 +438,87 @@ def gate_main(a, e, stream, mean, std, classes):
             for r in rows:
                 f.write(f"{r['kind']:<11} {r['dtype']:<5} {r['streams']:>7} {r['windows']:>7} {r['median_us']:>10.1f} {r['p90_us']:>9.1f} "
                         f"{r['kernels_per_push']:>8.1f} {r['gated_minus_ungated_us']:>9.1f}\n")
+
+
+def drive_main(a, e, stream, mean, std, classes):
+    """ungated, gated and driven pushes, interleaved case by case in one run, each on a decoder of its own; the profile uses
+    every channel of every class, and its range lies off the stream's windows, so that every channel goes bad (bad_mask_seen in
+    the JSON lines): the health part of the walk does all it can do"""
+    rows = []
+    settings = dict(min_cosine=0.2, min_margin=0.02, min_votes=3, dwell=5, release=10, weight="margin")
+    rng = np.random.default_rng(0)
+    K = len(classes)
+    profile = dict(ids=np.asarray(classes), rest=np.full(12, -4.2, np.float32), span=rng.uniform(0.2, 1.0, (K, 12)).astype(np.float32),
+                   weight=rng.integers(1, 256, (K, 12)).astype(np.int32), low=np.full(12, -3.95, np.float32),
+                   high=np.full(12, -3.75, np.float32))
+    for dtype in ("f32", "bf16"):
+        for S, n in ((1, 20), (1, 500), (256, 20)):
+            m = n // 20
+
+            def decoder():
+                if S == 1:
+                    return OnlineDecoder(e, mean, std, classes=classes, dtype=dtype)
+                d = MultiStreamDecoder(e, mean, std, S, dtype=dtype, max_rows=S * m)
+                for s in range(S):
+                    d.set_classes(s, classes=classes)
+                return d
+
+            plain, gate, under = decoder(), CommandGate(decoder(), **settings), CommandGate(decoder(), **settings)
+            drive = GraspDrive(under, profile=profile)
+            pos = [0]
+            span = stream.shape[0] - S * n
+
+            def chunk():
+                base = pos[0] % span
+                pos[0] += S * n
+                return stream[base:base + S * n]
+
+            if S == 1:
+                fns = (("ungated", lambda: plain.push(chunk(), return_logits=True)), ("gated", lambda: gate.push(chunk())),
+                       ("driven", lambda: drive.push(chunk())))
+            else:
+                fns = (("ungated", lambda: plain.push_packed(chunk(), [n] * S, return_logits=True)),
+                       ("gated", lambda: gate.push_packed(chunk(), [n] * S)), ("driven", lambda: drive.push_packed(chunk(), [n] * S)))
+            res, kernels = {}, {}
+            for name, fn in fns:
+                med, p90 = time_pushes(fn, a.iters, a.warmup)
+                res[name], kernels[name] = med, count_kernels(fn, pushes=3)
+                rows.append(dict(kind=name, dtype=dtype, streams=S, windows=m, median_us=round(med, 1), p90_us=round(p90, 1),
+                                 kernels_per_push=kernels[name]))
+            if kernels["driven"] != kernels["gated"] + 1:
+                raise SystemExit(f"a driven push launches {kernels['driven']} kernels, a gated one {kernels['gated']}: not one more")
+            if S > 1:
+                out = gate.push_packed(chunk(), [n] * S, return_windows=True)
+                wins, cmd = [r[2] for r in out], [r[3] for r in out]
+            else:
+                out = gate.push(chunk(), return_windows=True)
+                wins, cmd = out[2], out[3]
+            alone = GraspDrive(plain, profile=profile, follow="voted")
+            med, p90 = time_pushes(lambda: alone.apply(wins, cmd), a.iters, a.warmup)
+            rows.append(dict(kind="drive alone", dtype=dtype, streams=S, windows=m, median_us=round(med, 1), p90_us=round(p90, 1),
+                             kernels_per_push=count_kernels(lambda: alone.apply(wins, cmd), pushes=3)))
+            bad = drive.push_packed(chunk(), [n] * S)[0][-1] if S > 1 else drive.push(chunk())[-1]
+            for r in rows[-4:]:
+                r["gate_adds_us"] = round(res["gated"] - res["ungated"], 1)
+                r["drive_adds_us"] = round(res["driven"] - res["gated"], 1)
+                r["bad_mask_seen"] = int(bad.max()) if bad.numel() else 0
+                print(json.dumps(r), flush=True)
+            del plain, gate, under, drive, alone
+            torch.cuda.empty_cache()
+    if a.out:
+        dev = torch.cuda.get_device_name(0)
+        with open(a.out, "w") as f:
+            f.write(f"# tools/online_bench.py --drive --iters {a.iters} --warmup {a.warmup} on {dev}\n")
+            f.write("# ungated = decoder.push(return_logits=True), gated = CommandGate.push, driven = GraspDrive.push on a CommandGate, each\n"
+                    "# on a decoder of its own; drive alone = GraspDrive.apply on the windows and commands of one push; per-push wall\n"
+                    "# time, host-synchronised (median, p90), kernels per push (torch.profiler: library kernels plus torch's own);\n"
+                    "# gate_adds = gated - ungated median, drive_adds = driven - gated median, of the same run\n"
+                    "# the profile's range lies off the stream's windows: all twelve channels go bad, the worst case for the health part of the walk\n")
+            f.write(f"{'kind':<11} {'dtype':<5} {'streams':>7} {'windows':>7} {'median_us':>10} {'p90_us':>9} {'kernels':>8} {'gate_adds':>10} "
+                    f"{'drive_adds':>10}\n")
+            for r in rows:
+                f.write(f"{r['kind']:<11} {r['dtype']:<5} {r['streams']:>7} {r['windows']:>7} {r['median_us']:>10.1f} {r['p90_us']:>9.1f} "
+                        f"{r['kernels_per_push']:>8.1f} {r['gate_adds_us']:>10.1f} {r['drive_adds_us']:>10.1f}\n")
 
 
 class _Ids:
