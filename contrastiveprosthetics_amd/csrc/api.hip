@@ -479,6 +479,9 @@ extern "C" int cp_glove_forward(const cp_config* cfg, const cp_glove_params* gp,
     GWS w;
     if (int e = check_glove(cfg, rows, gws, gws_bytes, &w)) return e;
     if (!gp || !gp->w1 || !gp->bn_g || !gp->bn_b || !gp->last_w || !glove || !zg) return fail(CP_ERR_ARG, "cp_glove_forward args");
+    // (the fused kernels read glove rows and store zg rows in 16-byte pieces; rows are 80 and 64 bytes)
+    if (((uintptr_t)glove & 15) != 0) return fail(CP_ERR_ARG, "cp_glove_forward: glove must be 16-byte aligned");
+    if (((uintptr_t)zg & 15) != 0) return fail(CP_ERR_ARG, "cp_glove_forward: zg must be 16-byte aligned");
     if (cfg->dtype != CP_F32) return glove_forward_t<bf16_t>(cfg, gp, glove, rows, (unsigned char*)gws, w, zg, (hipStream_t)stream);
     return glove_forward_t<float>(cfg, gp, glove, rows, (unsigned char*)gws, w, zg, (hipStream_t)stream);
 }
@@ -491,6 +494,8 @@ extern "C" int cp_head_glove(const cp_config* cfg, const float* z, const float* 
     if (!z || !zg || !labels || !loss_correct || !pred || V <= 0 || n_groups * CP_TASKS != cfg->n_windows || n_groups % V != 0)
         return fail(CP_ERR_ARG, "cp_head_glove args");
     if (want_grad && V != 1) return fail(CP_ERR_ARG, "cp_head_glove: gradients need V == 1 (training batches)");
+    if (((uintptr_t)z & 15) != 0) return fail(CP_ERR_ARG, "cp_head_glove: z must be 16-byte aligned");        // (head_kernel reads rows in 16-byte pieces)
+    if (((uintptr_t)zg & 15) != 0) return fail(CP_ERR_ARG, "cp_head_glove: zg must be 16-byte aligned");
     const int64_t R = n_groups / V * CP_TASKS;
     GWS gw;
     if (int e = check_glove(cfg, R, gws, gws_bytes, &gw)) return e;

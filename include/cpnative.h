@@ -320,12 +320,13 @@ typedef struct cp_glove_params {
 size_t cp_glove_workspace_bytes(int64_t max_rows, int32_t dtype);
 
 /* GLOVENet.forward, glove branch.  glove (rows,20) f32, rows = B*41; zg (rows,16) f32.  cfg supplies dtype, adabn,
- * training, bn_momentum, bn_eps (n_windows and the dropout fields are not used).  Saves what backward needs in gws. */
+ * training, bn_momentum, bn_eps (n_windows and the dropout fields are not used).  Saves what backward needs in gws.
+ * glove and zg must be 16-byte aligned (CP_ERR_ARG otherwise). */
 int cp_glove_forward(const cp_config* cfg, const cp_glove_params* gp, const float* glove, int64_t rows,
                      void* gws, size_t gws_bytes, float* zg, void* stream);
 
 /* cp_head with per-group class embeddings: same outputs; want_grad (V must be 1) leaves dL/dz in ws for
- * cp_encoder_backward and dL/dzg in gws for cp_glove_backward. */
+ * cp_encoder_backward and dL/dzg in gws for cp_glove_backward.  z and zg must be 16-byte aligned (CP_ERR_ARG otherwise). */
 int cp_head_glove(const cp_config* cfg, const float* z, const float* zg, const int64_t* labels, int64_t n_groups,
                   int32_t V, int32_t want_grad, void* ws, size_t ws_bytes, void* gws, size_t gws_bytes,
                   float* loss_correct, int32_t* pred, float* logits, void* stream);

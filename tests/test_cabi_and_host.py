@@ -103,6 +103,39 @@ def test_preprocess_entry_validates_long_segments_before_it_launches(lib):
         assert b"cp_preprocess_emg" in lib.cp_last_error(), name
 
 
+def test_glove_entries_refuse_misaligned_pointers_before_they_launch(lib):
+    """cp_glove_forward reads `glove` and stores `zg` in 16-byte pieces, cp_head_glove reads `z` and `zg` so: a pointer 4 bytes
+    off is refused with CP_ERR_ARG and a message that names the entry and the argument, before any launch (every pointer is
+    a dummy address that is never dereferenced; sizes and workspaces are valid, so the alignment check is what refuses)"""
+    from contrastiveprosthetics_amd import _lib
+    B, T = 3, 41
+    rows = B * T
+    ok, ws, gws = 0x100000, 0x200000, 0x40000000                  # 256-byte aligned addresses
+    for dtype in (0, 1):                                          # CP_F32, CP_BF16
+        cfg = _lib.cp_config()
+        cfg.n_windows, cfg.dtype, cfg.training, cfg.bn_momentum, cfg.bn_eps = rows, dtype, 1, 0.1, 1e-5
+        nb, gnb = lib.cp_workspace_bytes(rows, dtype, 0.0), lib.cp_glove_workspace_bytes(rows, dtype)
+        assert nb > 0 and gnb > 0
+        gp = _lib.cp_glove_params(ok, ok, ok, ok, ok, ok)
+
+        def forward(glove, zg):
+            return lib.cp_glove_forward(ctypes.byref(cfg), ctypes.byref(gp), glove, rows, gws, gnb, zg, None)
+
+        def head(z, zg):
+            return lib.cp_head_glove(ctypes.byref(cfg), z, zg, ok, B, 1, 1, ws, nb, gws, gnb, ok, ok, None, None)
+
+        for entry, arg, call, ptrs in (("cp_glove_forward", "glove", forward, (ok + 4, ok)),
+                                       ("cp_glove_forward", "zg", forward, (ok, ok + 4)),
+                                       ("cp_glove_forward", "glove", forward, (ok + 8, ok + 8)),
+                                       ("cp_head_glove", "z", head, (ok + 4, ok)),
+                                       ("cp_head_glove", "zg", head, (ok, ok + 4)),
+                                       ("cp_head_glove", "z", head, (ok + 12, ok + 12))):
+            rc = call(*ptrs)
+            msg = lib.cp_last_error()
+            assert rc == 10001, (entry, arg, dtype, rc, msg)
+            assert entry.encode() in msg and (b" " + arg.encode() + b" must be 16-byte aligned") in msg, (entry, arg, msg)
+
+
 def test_missing_library_is_an_error(monkeypatch):
     from contrastiveprosthetics_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)
