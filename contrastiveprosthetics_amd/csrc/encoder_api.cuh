@@ -635,8 +635,7 @@ static int encoder_forward_fp8(const cp_config* c, const cp_params* p, const cp_
 // small batches (csrc/small.cuh): N <= 64 groups, batch statistics, f32 or bf16
 // ---------------------------------------------------------------------------------------
 static bool use_small(const cp_config* c) {
-    return c->n_windows <= SM_MAX_WINDOWS && (c->training || c->adabn) && c->dtype != CP_FP8 && !c->stats_allreduce && !c->grad_tap &&
-           !opt(c, CP_OPT_NO_SMALL);
+    return c->n_windows <= SM_MAX_WINDOWS && (c->training || c->adabn) && c->dtype != CP_FP8 && !c->stats_allreduce && !opt(c, CP_OPT_NO_SMALL);
 }
 
 template <typename T>
@@ -742,13 +741,22 @@ extern "C" int cp_encoder_forward(const cp_config* cfg, const cp_params* p, cons
 // ---------------------------------------------------------------------------------------
 // encoder backward: the pieces the forms share
 // ---------------------------------------------------------------------------------------
-// test aid (cp_config.grad_tap): device buffer of 9 slots x n_windows x 768 elements of the compute dtype that receives a
+// test aid (cp_config.grad_tap): device buffer of 9 slots x n_windows x 768 elements of the compute dtype (CP_FP8: bf16) that receives a
 // copy of every intermediate gradient of the backward pass, so that each backward kernel can be checked on its own
-// inputs at full batch size (tests/test_gpu_fullsize.py).  nullptr (the default) = no copies.
+// inputs at full batch size (tests/test_gpu_fullsize.py).  nullptr (the default) = no copies.  A tap never changes which kernels compute
+// the step: it adds copies and one stand-alone conv2 data-gradient launch for slot 0 (conv_backward_tail), and keeps the second stream
+// off (make_aux).
+// The small-batch form fills 11 slots (tests/test_gpu_small_recompute.py; the slots' meaning on that path: include/cpnative.h).
+// check_tap(): the whole buffer is checked once, before the first launch of a backward pass -- a short one enqueues nothing.
+static int check_tap(const cp_config* c, bool small) {
+    if (!c->grad_tap) return 0;
+    const size_t slot_bytes = (size_t)c->n_windows * 768 * (c->dtype == CP_F32 ? 4 : 2);
+    if ((size_t)(small ? 11 : 9) * slot_bytes > c->grad_tap_bytes) return fail(CP_ERR_ARG, "gradient tap buffer too small");
+    return 0;
+}
 static int tap_gradient(const cp_config* c, int slot, const void* src, int64_t n_windows, int width, size_t es, hipStream_t st) {
     if (!c->grad_tap) return 0;
     const size_t slot_bytes = (size_t)n_windows * 768 * es, bytes = (size_t)n_windows * width * es;
-    if ((size_t)(slot + 1) * slot_bytes > c->grad_tap_bytes) return fail(CP_ERR_ARG, "gradient tap buffer too small");
     CK(hipMemcpyAsync((unsigned char*)c->grad_tap + slot * slot_bytes, src, bytes, hipMemcpyDeviceToDevice, st));
     return 0;
 }
@@ -923,7 +931,6 @@ static int conv_backward_tail(const cp_config* c, const cp_params* p, const floa
         if (gcol_rows <= 0 || sizeof(T) != 2) return fail(CP_ERR_ARG, "conv_backward_tail: 8-bit gradient without its column sums");
         if (c->grad_tap) {
             const size_t slot_bytes = (size_t)N * 768 * 2;
-            if (2 * slot_bytes > c->grad_tap_bytes) return fail(CP_ERR_ARG, "gradient tap buffer too small");
             hipLaunchKernelGGL(dequant5_bf16_kernel, dim3(1024), dim3(256), 0, st, (const uint8_t*)cur, (bf16_t*)((unsigned char*)c->grad_tap + slot_bytes),
                                N * 192, g8, F8_T_GRAD + 1);
             CKL("dequant5_bf16_kernel(conv2 gradient)");
@@ -1035,6 +1042,12 @@ static int encoder_backward_small_t(const cp_config* c, const cp_params* p, cons
         else hipLaunchKernelGGL((sm_fc_bwd_kernel<T, true>), dim3(a.n_dgrad + 8 * splits), dim3(256), 0, st, a);
         CKL("sm_fc_bwd_kernel<proj>");
     }
+    // gradient tap: every launch's stored data gradient, copied directly behind the launch that wrote it.  Gout is the masked
+    // dL/d(BN_L output) -- the NEXT launch applies layer L's BatchNorm + ReLU backward while staging -- so slot L = 2..8 holds that,
+    // and fc1's [N][768] goes to slot 9 before conv_backward_tail transforms it in place (slots 1 and 0 are filled there).  Slot 10: the
+    // projection launch's own input, dz as the head stored it ([N][64], 16 live columns)
+    if (int e = tap_gradient(c, 10, base + w.dz, N, 64, sizeof(T), st)) return e;
+    if (int e = tap_gradient(c, 8, gb[cur], N, 512, sizeof(T), st)) return e;
     for (int L = 8; L >= 2; --L) {
         const int i = L - 2, Lp = L - 1, K = fcK(i);
         SmBwdArgs a{};
@@ -1052,6 +1065,7 @@ static int encoder_backward_small_t(const cp_config* c, const cp_params* p, cons
         else hipLaunchKernelGGL((sm_fc_bwd_kernel<T, false>), dim3(a.n_dgrad + 8 * (K / 64) * splits), dim3(256), 0, st, a);
         CKL("sm_fc_bwd_kernel");
         cur ^= 1;
+        if (int e = tap_gradient(c, Lp == 1 ? 9 : Lp, gb[cur], N, K, sizeof(T), st)) return e;
     }
     if (splits > 1) {
         ProfScope ps(CP_K_REDUCE_SLABS, st);
@@ -1290,7 +1304,6 @@ static int encoder_backward_fp8(const cp_config* c, const cp_params* p, const fl
     auto tap8 = [&](int slot, const uint8_t* src, int t) -> int {          // test aid: the e5m2 gradient expanded into the bf16 tap
         if (!c->grad_tap) return 0;
         const size_t slot_bytes = (size_t)N * 768 * 2;
-        if ((size_t)(slot + 1) * slot_bytes > c->grad_tap_bytes) return fail(CP_ERR_ARG, "gradient tap buffer too small");
         hipLaunchKernelGGL(dequant5_bf16_kernel, dim3(1024), dim3(256), 0, st, src, (bf16_t*)((unsigned char*)c->grad_tap + slot * slot_bytes), N * 128, fs, t);
         CKL("dequant5_bf16_kernel");
         return 0;
@@ -1481,6 +1494,7 @@ extern "C" int cp_encoder_backward_ev(const cp_config* cfg, const cp_params* p, 
     // the path is the FORWARD's: use_small() ignores `training`, which a backward call may not carry, only through (training || adabn)
     if (r->n_windows != cfg->n_windows || r->path != forward_path(cfg))
         return fail(CP_ERR_ARG, "cp_encoder_backward: n_windows or the kernel path differs from the forward pass that filled cfg->record");
+    if (int e = check_tap(cfg, r->path == PATH_SMALL)) return e;
     unsigned char* base = (unsigned char*)ws;
     const hipStream_t st = (hipStream_t)stream;
     const hipEvent_t ready = (hipEvent_t)fc_grads_ready;

@@ -139,7 +139,16 @@ typedef struct cp_config {
      * BatchNorm + ReLU backward, n_windows x 512; slot 1: dL/d(conv2 pre-activation), slot 0: dL/d(BN1 output), both
      * n_windows x [12 positions][64 channels].  grad_tap_bytes = size of the buffer.  (Slot 0 is no tensor of the step since round 4 --
      * conv2's data gradient is consumed in the accumulators of conv2_dgrad_conv1_kernel -- so with a tap the call runs the stand-alone
-     * data-gradient kernel once more to fill it; CP_FP8: slots 0 and 1 hold the bf16 expansion of the e5m2 gradient.) */
+     * data-gradient kernel once more to fill it; CP_FP8: slots 0 and 1 hold the bf16 expansion of the e5m2 gradient.)
+     * The small-batch form (n_windows <= 2,624 with batch statistics) stores other tensors -- each launch applies the BatchNorm + ReLU
+     * backward of ITS layer while staging its input -- and fills 11 slots: slot L = 2..8: the masked dL/d(BN_L output) (BN_L = the
+     * BatchNorm behind fc layer L-1; dropout mask and 1 / (1 - p) applied, rounded to the compute dtype), n_windows x 512, i.e. the
+     * gradient BEFORE layer L's BatchNorm + ReLU backward; slot 9: the same for conv2's BatchNorm, n_windows x 768 as fc1's launch
+     * wrote it ([position][channel]); slot 1: dL/d(conv2 pre-activation), which conv2's weight-gradient launch writes over that
+     * tensor in place; slot 0 as above; slot 10: dL/dz as cp_head stored it, n_windows x 64 with 16 live columns.
+     * A tap never changes which kernels compute the step: it adds the copies and slot 0's stand-alone launch, and the second stream
+     * (below) stays off.  The buffer's size is checked before the first launch (9 slots, small-batch form 11; CP_FP8 slots are
+     * bf16): a short one returns CP_ERR_ARG with nothing enqueued. */
     void* grad_tap;
     size_t grad_tap_bytes;
     /* ---- a second stream for the work of cp_encoder_backward that nothing in the step waits for (round 4; all three NULL = one

@@ -136,6 +136,33 @@ def test_glove_entries_refuse_misaligned_pointers_before_they_launch(lib):
             assert entry.encode() in msg and (b" " + arg.encode() + b" must be 16-byte aligned") in msg, (entry, arg, msg)
 
 
+def test_backward_refuses_a_short_gradient_tap_before_it_launches(lib):
+    """cp_config.grad_tap: cp_encoder_backward checks the whole buffer once, before its first launch -- 9 slots of n_windows x 768
+    elements on the large-batch paths (CP_FP8: bf16 elements), 11 on the small-batch path (slot 9: fc1's data gradient before conv2's
+    weight-gradient launch overwrites it).  One byte short returns CP_ERR_ARG and leaves the forward record untouched (every pointer
+    is a dummy address that is never dereferenced: there is no GPU here, so a launch or a copy would fail with another code).  That a buffer
+    of exactly the stated size is accepted is shown on the GPU: tests/test_gpu_small_recompute.py and tests/test_gpu_fullsize.py allocate
+    exactly 11 and 9 slots."""
+    from contrastiveprosthetics_amd import _lib
+    ok, ws = 0x100000, 0x40000000
+    #            groups, dtype, record path (PATH_LARGE 0, PATH_SMALL 1, PATH_FP8 2), slots, element bytes
+    for groups, dtype, path, slots, es in ((8, 1, 1, 11, 2), (64, 0, 1, 11, 4), (65, 1, 0, 9, 2), (65, 0, 0, 9, 4), (8, 2, 2, 9, 2)):
+        n = 41 * groups
+        cfg = _lib.cp_config()
+        cfg.n_windows, cfg.dtype, cfg.training, cfg.bn_momentum, cfg.bn_eps = n, dtype, 1, 0.1, 1e-5
+        rec = _lib.cp_forward_record(n, path, 0, 0, 0, None)
+        cfg.record = ctypes.pointer(rec)
+        nb = lib.cp_workspace_bytes(n, dtype, 0.0)
+        need = slots * n * 768 * es
+        cfg.grad_tap = ok
+        pp, gg = _lib.cp_params(), _lib.cp_params()
+        for short in (need - 1, (slots - 1) * n * 768 * es, 0):
+            cfg.grad_tap_bytes = short
+            rc = lib.cp_encoder_backward_ev(ctypes.byref(cfg), ctypes.byref(pp), ok, ws, nb, ctypes.byref(gg), None, None)
+            assert rc == 10001 and b"gradient tap buffer too small" in lib.cp_last_error(), (groups, dtype, short, rc, lib.cp_last_error())
+            assert rec.backwards == 0
+
+
 def test_missing_library_is_an_error(monkeypatch):
     from contrastiveprosthetics_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)

@@ -16,7 +16,9 @@ are two-tier: tight on what no ReLU precedes in the backward pass (the projectio
 loose below, and the flip rate itself is measured and bounded.  8 groups = 328 rows (the reference's smallest), 33 groups = 1353 rows (ragged 32-row tiles, 6 splits),
 64 groups = 2624 rows (the dispatch limit).  The parity tests against the oracle at B <= 64 (tests/test_gpu_parity.py,
 test_gpu_api.py) run through the small path too; this file pins the two device paths to each other and the small path's
-run-to-run bit-exactness (its reductions are order-independent by construction)."""
+run-to-run bit-exactness (its reductions are order-independent by construction).  The bf16 ARITHMETIC of the small path -- each launch
+against a float64 recomputation at its own rounding points, at the ragged sizes where the path changes shape -- is held in
+tests/test_gpu_small_recompute.py; the bf16 bars here say only how far two bf16 pipelines may drift apart."""
 import pytest
 import torch
 
