@@ -14,7 +14,8 @@ def __getattr__(name):
     if name in ("OnlineDecoder", "MultiStreamDecoder", "AdaptiveMultiStreamDecoder", "recording_windows", "window_labels",
                 "CommandGate", "thresholds_from_logits", "REST", "IGNORE", "expected_commands", "score_commands", "pick_gate",
                 "sweep_gate", "gate_grid", "SUBSET_SCORE_KEYS", "score_subset", "sweep_subsets", "rank_subsets",
-                "search_grasp_sets", "GraspDrive", "drive_profile"):
+                "search_grasp_sets", "GraspDrive", "drive_profile", "rotations", "leave_one_out", "score_channel_maps",
+                "pick_channel_map"):
         from . import online
         return getattr(online, name)
     raise AttributeError(name)

@@ -93,6 +93,11 @@ CP_ONLINE_MULTI_MAX_STREAMS, CP_ONLINE_MULTI_MAX_ROWS = 256, 65536
 CP_ONLINE_GATE_SCORES, CP_ONLINE_GATE_SWEEP_MAX_CONFIGS = 10, 65536
 CP_ONLINE_SUBSET_SCORES, CP_ONLINE_SUBSET_SWEEP_MAX_SUBSETS = 7, 1048576
 CP_ONLINE_DRIVE_ONE, CP_ONLINE_DRIVE_MAX_SMOOTH = 4096, 256
+CP_ONLINE_MAP_SCORES, CP_ONLINE_MAP_SWEEP_MAX_MAPS = 3, 65536
+
+# what the four map sweep entries take behind their workspace: rms, n_windows, mean_std, map_src, map_fill, n_maps, n_classes,
+# expected_slot, chunk_rows, scratch, scratch_bytes, pred, voted, scores, class_hits, stream
+_MAP_SWEEP_TAIL = [_fp, C.c_int64, _fp, _fp, _fp, C.c_int32, C.c_int32, _fp, C.c_int64, _fp, C.c_size_t, _fp, _fp, _fp, _fp, _fp]
 
 SYMBOLS = {
     "cp_version": (C.c_int, []),
@@ -201,6 +206,21 @@ SYMBOLS = {
     "cp_online_subset_sweep_scratch_bytes": (C.c_size_t, [C.c_int64]),
     "cp_online_subset_sweep": (C.c_int, [_fp, C.c_int32, C.c_int64, C.c_int32, _fp, _fp, C.c_int32, C.c_int32, _fp, C.c_size_t, _fp,
                                          _fp, _fp]),
+    "cp_online_push_mapped": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
+                                        _fp]),
+    "cp_online_adapt_push_mapped": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
+                                              _fp]),
+    "cp_online_multi_push_mapped": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, _fp, _fp, C.c_int64,
+                                              C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "cp_online_multi_adapt_push_mapped": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, _fp, _fp, C.c_int64,
+                                                    C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "cp_online_windows_mapped": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp]),
+    "cp_online_map_sweep_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "cp_online_map_sweep": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t] + _MAP_SWEEP_TAIL),
+    "cp_online_adapt_map_sweep": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t] + _MAP_SWEEP_TAIL),
+    "cp_online_multi_map_sweep": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, C.c_int32] + _MAP_SWEEP_TAIL),
+    "cp_online_multi_adapt_map_sweep": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, C.c_int32]
+                                        + _MAP_SWEEP_TAIL),
 }
 
 KERNEL_KINDS = ["gather", "prep", "conv1_fwd", "bn_finalize", "conv2_fwd", "fold", "fc_fwd", "dropout", "proj_fwd",

@@ -28,6 +28,7 @@
 #include "online_gate.cuh"
 #include "online_drive.cuh"
 #include "online_subsets.cuh"
+#include "online_maps.cuh"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* what) {

@@ -57,6 +57,8 @@ struct OlFrontArgs {
     float* X;                            // [max windows][12] normalised windows
     float* windows;                      // optional copy for the caller
     const float* mean_std;               // [2][12]
+    const int32_t* map_src;              // optional electrode map [streams][12]: the raw column of each model channel, < 0: masked
+    const float* map_fill;               // [streams][12]: what a masked channel emits (NULL with map_src == NULL: the identity)
     int n_coef, phase;
     float gain;
     double b[OL_MAXCOEF], a[OL_MAXCOEF]; // normalised (a[0] == 1)
@@ -73,9 +75,14 @@ __device__ __forceinline__ long long ol_windows_before(long long N, int phase) {
 // One workgroup of 256 threads runs one stream: n samples of raw from the stream's state st (n0 samples seen so far), the
 // windows to X and windows (if not NULL) from row 0.  Updates the filter and RMS state, not n_seen; returns the number
 // of windows on thread 0.  Behind a barrier on return.
+// Electrode map (row map_row of p.map_src / p.map_fill; none: the identity): thread c is model channel c.  It filters raw
+// column src[c], keeps that filter's state in its own slots of st, normalises with its own mean and std and writes column c.
+// A masked channel (src < 0) runs the recurrences on input 0 and emits fill[c] in every window.  The map is read once, in
+// front of the sample loop; a value the host could not see is clamped here: src above 11 reads column 11, a fill that is
+// not finite reads as 0.
 template <int NB>
 __device__ __forceinline__ int ol_frontend_run(const OlFrontArgs& p, OlState* st, const float* raw, long long n, long long n0,
-                                               float* X, float* windows, float* xs) {
+                                               float* X, float* windows, float* xs, int map_row = 0) {
 #pragma clang fp contract(off)
     const int c = threadIdx.x;
     const bool on = c < OL_C;
@@ -97,6 +104,16 @@ __device__ __forceinline__ int ol_frontend_run(const OlFrontArgs& p, OlState* st
         mean = p.mean_std[c];
         sd = p.mean_std[OL_C + c];
     }
+    int col = on ? c : 0;                                  // raw column of this model channel
+    bool masked = false;
+    float fill = 0.f;
+    if (on && p.map_src) {
+        const int s = p.map_src[map_row * OL_C + c];
+        masked = s < 0;
+        col = masked ? c : (s < OL_C ? s : OL_C - 1);
+        const float f = p.map_fill[map_row * OL_C + c];
+        fill = isfinite(f) ? f : 0.f;
+    }
     int j = 0;
     for (long long base = 0; base < n; base += OL_FRONT_PIECE) {
         const int len = (int)((n - base) < OL_FRONT_PIECE ? (n - base) : OL_FRONT_PIECE);
@@ -106,7 +123,7 @@ __device__ __forceinline__ int ol_frontend_run(const OlFrontArgs& p, OlState* st
         if (!on) continue;
         for (int tl = 0; tl < len; ++tl) {
             const long long t = n0 + base + tl;
-            const float xin = xs[tl * OL_C + c] * p.gain;
+            const float xin = masked ? 0.f : xs[tl * OL_C + col] * p.gain;
             const double xt = (double)xin;
             const double y = z[0] + p.b[0] * xt;
 #pragma unroll
@@ -133,7 +150,7 @@ __device__ __forceinline__ int ol_frontend_run(const OlFrontArgs& p, OlState* st
                 const long long i = l - half;
                 if (i >= p.phase && (i - p.phase) % OL_STRIDE == 0) {
                     const float r = sqrtf((float)(tmp / dwin));
-                    const float v = (r - mean) / sd;                  // emg_normalize_kernel
+                    const float v = masked ? fill : (r - mean) / sd;  // emg_normalize_kernel
                     X[j * OL_C + c] = v;
                     if (windows) windows[j * OL_C + c] = v;
                     ++j;
@@ -326,54 +343,78 @@ struct OlTailLds {
     int ring[OL_MAXVOTE];
 };
 
-// projection -> z, z / |z|, logits against the table, argmax (first maximum), then one wave runs the vote ring over the
-// push's windows in order: mode of the last `vote` predictions, ties to the smallest class id (the table is sorted by id).
-// M (1..OL_MAXM) rows of proj.act; row j's outputs go to pred[j], voted[j] and logits[j * ldl ..] (columns 0..K-1).
+// One 16-row tile of the tail, rows m0..m0+15 of the M rows of proj.act: projection -> z, z / |z|, logits against the table,
+// argmax (first maximum).  Row j's slot (its index into the sorted table) goes to pidx[j], in LDS or in global memory, its
+// logits to logits[j * ldl ..] (columns 0..K-1) if logits is given.  wf: the projection's fragments (ol_load_weights).  Ends
+// behind a barrier.
 template <typename T>
-__device__ __forceinline__ void ol_tail_run(const OlLayerArgs& proj, OlState* st, int M, int vote, int32_t* pred, int32_t* voted,
-                                            float* logits, int ldl, OlTailLds<T>& S) {
+__device__ __forceinline__ void ol_tail_tile(const OlLayerArgs& proj, const OlState* st, int K, int m0, int M, float* logits, int ldl,
+                                             int* pidx, OlTailLds<T>& S, const uint4 (&wf)[OL_MAXCH][OL_KC * (int)sizeof(T) / 64]) {
 #pragma clang fp contract(off)
     OlTileLds<T>& L = S.L;
     auto& zn = S.zn;
     auto& lg = S.lg;
+    const int tid = threadIdx.x;
+    ol_tile<T, false>(proj, L, 512, 0, m0, M, wf);
+    if (tid < 16) {
+        float z[16], ss = 0.f;
+#pragma unroll
+        for (int d = 0; d < 16; ++d) {
+            z[d] = L.red[0][tid][d] + proj.bias[d];
+            ss += z[d] * z[d];
+        }
+        const float nrm = sqrtf(ss);
+#pragma unroll
+        for (int d = 0; d < 16; ++d) zn[tid][d] = z[d] / nrm;
+    }
+    __syncthreads();
+    for (int e = tid; e < 16 * K; e += OL_THREADS) {
+        const int row = e / K, k = e % K;
+        float s = 0.f;
+#pragma unroll
+        for (int d = 0; d < 16; ++d) s += zn[row][d] * st->table[k][d];
+        lg[row][k] = s;
+        if (logits && m0 + row < M) logits[(size_t)(m0 + row) * ldl + k] = s;
+    }
+    __syncthreads();
+    if (tid < 16 && m0 + tid < M) {
+        int best = 0;
+        float bv = lg[tid][0];
+        for (int k = 1; k < K; ++k)
+            if (lg[tid][k] > bv) { bv = lg[tid][k]; best = k; }
+        pidx[m0 + tid] = best;
+    }
+    __syncthreads();
+}
+
+// The vote ring, one wave: lane k keeps the count of slot k over the ring (cnt).  Slot pj enters at `head`, the oldest entry
+// leaves once V are in; returns the slot with the most entries, the smallest among equals, on every lane.
+__device__ __forceinline__ int ol_vote_step(int* ring, int& head, int& len, int& cnt, int V, int pj, int lane) {
+    if (len == V) cnt -= ring[head] == lane;
+    else ++len;
+    cnt += pj == lane;
+    __builtin_amdgcn_wave_barrier();
+    if (lane == 0) ring[head] = pj;
+    head = head + 1 == V ? 0 : head + 1;
+    int key = (cnt << 8) | (255 - lane);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) key = max(key, __shfl_xor(key, o, 64));
+    return 255 - (key & 255);
+}
+
+// ol_tail_tile over the M (1..OL_MAXM) rows of proj.act, then one wave runs the vote ring over the push's windows in order:
+// mode of the last `vote` predictions, ties to the smallest class id (the table is sorted by id).
+// Row j's outputs go to pred[j], voted[j] and logits[j * ldl ..] (columns 0..K-1).
+template <typename T>
+__device__ __forceinline__ void ol_tail_run(const OlLayerArgs& proj, OlState* st, int M, int vote, int32_t* pred, int32_t* voted,
+                                            float* logits, int ldl, OlTailLds<T>& S) {
     auto& pidx = S.pidx;
     auto& ring = S.ring;
     const int K = st->K;
     const int tid = threadIdx.x;
     uint4 wf[OL_MAXCH][OL_KC * (int)sizeof(T) / 64];
     ol_load_weights<T>((const T*)proj.w, 512, 0, wf);
-    for (int m0 = 0; m0 < M; m0 += 16) {
-        ol_tile<T, false>(proj, L, 512, 0, m0, M, wf);
-        if (tid < 16) {
-            float z[16], ss = 0.f;
-#pragma unroll
-            for (int d = 0; d < 16; ++d) {
-                z[d] = L.red[0][tid][d] + proj.bias[d];
-                ss += z[d] * z[d];
-            }
-            const float nrm = sqrtf(ss);
-#pragma unroll
-            for (int d = 0; d < 16; ++d) zn[tid][d] = z[d] / nrm;
-        }
-        __syncthreads();
-        for (int e = tid; e < 16 * K; e += OL_THREADS) {
-            const int row = e / K, k = e % K;
-            float s = 0.f;
-#pragma unroll
-            for (int d = 0; d < 16; ++d) s += zn[row][d] * st->table[k][d];
-            lg[row][k] = s;
-            if (logits && m0 + row < M) logits[(size_t)(m0 + row) * ldl + k] = s;
-        }
-        __syncthreads();
-        if (tid < 16 && m0 + tid < M) {
-            int best = 0;
-            float bv = lg[tid][0];
-            for (int k = 1; k < K; ++k)
-                if (lg[tid][k] > bv) { bv = lg[tid][k]; best = k; }
-            pidx[m0 + tid] = best;
-        }
-        __syncthreads();
-    }
+    for (int m0 = 0; m0 < M; m0 += 16) ol_tail_tile<T>(proj, st, K, m0, M, logits, ldl, pidx, S, wf);
     if (tid < 64) {
         const int lane = tid, V = vote;
         int head = st->vote_head, len = st->vote_len;
@@ -383,18 +424,10 @@ __device__ __forceinline__ void ol_tail_run(const OlLayerArgs& proj, OlState* st
         for (int i = 0; i < len; ++i) cnt += ring[(head + V - len + i) % V] == lane;
         for (int j = 0; j < M; ++j) {
             const int pj = pidx[j];
-            if (len == V) cnt -= ring[head] == lane;
-            else ++len;
-            cnt += pj == lane;
-            __builtin_amdgcn_wave_barrier();
-            if (lane == 0) ring[head] = pj;
-            head = head + 1 == V ? 0 : head + 1;
-            int key = (cnt << 8) | (255 - lane);
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) key = max(key, __shfl_xor(key, o, 64));
+            const int vj = ol_vote_step(ring, head, len, cnt, V, pj, lane);
             if (lane == 0) {
                 pred[j] = st->ids[pj];
-                voted[j] = st->ids[255 - (key & 255)];
+                voted[j] = st->ids[vj];
             }
         }
         __builtin_amdgcn_wave_barrier();

@@ -1,6 +1,6 @@
 // Host layer of the online decoders (include/cpnative.h, cp_online_*): workspace layout, argument checks, launch chains and
 // the extern "C" entries of the folded, adaptive, multi-stream and adaptive multi-stream decoders, class enrolment, the
-// command gate, the grasp drive, the gate sweep and the subset sweep.  Host code only; api.hip includes it behind its own helpers (fail, CK, CKL) and encoder_api.cuh's (align256, fcK),
+// command gate, the grasp drive, the gate sweep, the subset sweep and the electrode-map sweep.  Host code only; api.hip includes it behind its own helpers (fail, CK, CKL) and encoder_api.cuh's (align256, fcK),
 // so the library stays one translation unit.  The four decoders share one workspace description (OlWS, ol_carve), one
 // parameter check, one set of front-end arguments, one folded chain and one unfolded weight copy; what an entry adds is its
 // name in the refusals and the kernels it launches.
@@ -162,6 +162,28 @@ static int olm_check_push(const char* who, int32_t max_rows, const float* raw, c
     return 0;
 }
 
+// An electrode map (include/cpnative.h): `rows` rows of 12 sources and 12 fills in memory the device reads, both pointers or
+// neither (the identity).  Pinned host memory is checked here: src in -1..11, fill finite.  Device memory the host cannot
+// see, so the kernels clamp what they read (ol_frontend_run).
+static int ol_check_map(const char* who, const int32_t* src, const float* fill, int64_t rows) {
+    if (!src && !fill) return 0;
+    if (!src || !fill) return ol_fail(CP_ERR_ARG, who, "map_src and map_fill go together (both NULL: the identity)");
+    if ((uintptr_t)src % 4 || (uintptr_t)fill % 4) return ol_fail(CP_ERR_ARG, who, "misaligned map");
+    hipPointerAttribute_t as{}, af{};
+    if (hipPointerGetAttributes(&as, src) != hipSuccess || hipPointerGetAttributes(&af, fill) != hipSuccess ||
+        as.type == hipMemoryTypeUnregistered || af.type == hipMemoryTypeUnregistered) {
+        (void)hipGetLastError();
+        return ol_fail(CP_ERR_ARG, who, "the map must lie in memory the device reads (device or pinned host memory)");
+    }
+    if (as.type == hipMemoryTypeHost)
+        for (int64_t i = 0; i < rows * OL_C; ++i)
+            if (src[i] < -1 || src[i] >= OL_C) return ol_fail(CP_ERR_ARG, who, "map_src outside -1..11");
+    if (af.type == hipMemoryTypeHost)
+        for (int64_t i = 0; i < rows * OL_C; ++i)
+            if (!std::isfinite(fill[i])) return ol_fail(CP_ERR_ARG, who, "map_fill must be finite");
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------
 // pieces of the launch chains
 // ---------------------------------------------------------------------------------------
@@ -173,10 +195,16 @@ static OlFrontArgs ol_front_args(const cp_online_config* c) {
     return fa;
 }
 
+struct OlMap {                           // an electrode map as the entries take it: one row per stream, or none (the identity)
+    const int32_t* src;
+    const float* fill;
+};
+
 static int ol_launch_frontend(const cp_online_config* c, OlState* state, float* X, const float* raw, int64_t n, const float* mean_std,
-                              float* windows, hipStream_t st) {
+                              float* windows, const OlMap& map, hipStream_t st) {
     OlFrontArgs fa = ol_front_args(c);
     fa.raw = raw; fa.n = n; fa.st = state; fa.X = X; fa.windows = windows; fa.mean_std = mean_std;
+    fa.map_src = map.src; fa.map_fill = map.fill;
     if (c->n_coef == 9) hipLaunchKernelGGL((ol_frontend_kernel<9>), dim3(1), dim3(256), 0, st, fa);
     else hipLaunchKernelGGL((ol_frontend_kernel<0>), dim3(1), dim3(256), 0, st, fa);
     CKL("ol_frontend_kernel");
@@ -184,10 +212,12 @@ static int ol_launch_frontend(const cp_online_config* c, OlState* state, float* 
 }
 
 static int olm_launch_frontend(const cp_online_config* c, int n_streams, unsigned char* base, const OlWS& w, const float* raw,
-                               const int32_t* counts, int64_t total, int rows, const float* mean_std, float* windows, hipStream_t st) {
+                               const int32_t* counts, int64_t total, int rows, const float* mean_std, float* windows, const OlMap& map,
+                               hipStream_t st) {
     OlmFrontArgs fa{};
     fa.f = ol_front_args(c);
     fa.f.raw = raw; fa.f.X = (float*)(base + w.X); fa.f.windows = windows; fa.f.mean_std = mean_std;
+    fa.f.map_src = map.src; fa.f.map_fill = map.fill;
     fa.states = (OlState*)(base + w.state); fa.meta = (OlmMeta*)(base + w.meta); fa.counts = counts; fa.total_samples = total;
     fa.rows = rows; fa.max_m = c->max_windows;
     if (c->n_coef == 9) hipLaunchKernelGGL((olm_frontend_kernel<9>), dim3(n_streams), dim3(256), 0, st, fa);
@@ -307,9 +337,10 @@ extern "C" int cp_online_reset(const cp_online_config* cfg, void* ws, size_t ws_
 
 template <typename T>
 static int online_push_t(T t, const cp_online_config* c, unsigned char* base, const OlWS& w, const float* raw, int64_t n,
-                         const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, hipStream_t st) {
+                         const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, const OlMap& map,
+                         hipStream_t st) {
     OlState* state = (OlState*)(base + w.state);
-    if (int e = ol_launch_frontend(c, state, (float*)(base + w.X), raw, n, mean_std, windows, st)) return e;
+    if (int e = ol_launch_frontend(c, state, (float*)(base + w.X), raw, n, mean_std, windows, map, st)) return e;
     auto layer = [&](const OlLayerArgs& la, auto conv) {
         constexpr bool CONV = decltype(conv)::value;
         hipLaunchKernelGGL((ol_layer_kernel<T, CONV>), CONV ? dim3(4, OL_C) : dim3(512 / 16), dim3(OL_THREADS), 0, st, la);
@@ -320,15 +351,38 @@ static int online_push_t(T t, const cp_online_config* c, unsigned char* base, co
     return ol_launch_tail(t, c, base, w, pred, voted, logits, st);
 }
 
-extern "C" int cp_online_push(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* raw, int64_t n_samples,
-                              const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, void* stream) {
+// cp_online_push, cp_online_adapt_push and their mapped forms
+template <typename T>
+static int online_adapt_push_t(T t, const cp_online_config* c, unsigned char* base, const OlWS& w, const float* raw, int64_t n,
+                               const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, const OlMap& map,
+                               hipStream_t st);
+
+static int ol_push(const char* who, bool adaptive, const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* raw,
+                   int64_t n_samples, const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows,
+                   const OlMap& map, void* stream) {
     OlWS w;
-    if (int e = ol_check(cfg, ws, ws_bytes, false, &w)) return e;
-    if (int e = ol_check_push("cp_online_push", cfg, n_samples, raw, mean_std, pred, voted)) return e;
+    if (int e = ol_check(cfg, ws, ws_bytes, adaptive, &w)) return e;
+    if (int e = ol_check_push(who, cfg, n_samples, raw, mean_std, pred, voted)) return e;
+    if (int e = ol_check_map(who, map.src, map.fill, 1)) return e;
     if (n_samples == 0) return 0;
     return ol_dispatch(cfg->dtype, [&](auto t) {
-        return online_push_t(t, cfg, (unsigned char*)ws, w, raw, n_samples, mean_std, pred, voted, logits, windows, (hipStream_t)stream);
+        return adaptive ? online_adapt_push_t(t, cfg, (unsigned char*)ws, w, raw, n_samples, mean_std, pred, voted, logits, windows, map,
+                                              (hipStream_t)stream)
+                        : online_push_t(t, cfg, (unsigned char*)ws, w, raw, n_samples, mean_std, pred, voted, logits, windows, map,
+                                        (hipStream_t)stream);
     });
+}
+
+extern "C" int cp_online_push(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* raw, int64_t n_samples,
+                              const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, void* stream) {
+    return ol_push("cp_online_push", false, cfg, ws, ws_bytes, raw, n_samples, mean_std, pred, voted, logits, windows, OlMap{}, stream);
+}
+
+extern "C" int cp_online_push_mapped(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* raw, int64_t n_samples,
+                                     const float* mean_std, const int32_t* map_src, const float* map_fill, int32_t* pred,
+                                     int32_t* voted, float* logits, float* windows, void* stream) {
+    return ol_push("cp_online_push_mapped", false, cfg, ws, ws_bytes, raw, n_samples, mean_std, pred, voted, logits, windows,
+                   OlMap{map_src, map_fill}, stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -450,8 +504,9 @@ static int ola_chain(T t, unsigned char* base, const OlWS& w, const float* x, in
 
 template <typename T>
 static int online_adapt_push_t(T t, const cp_online_config* c, unsigned char* base, const OlWS& w, const float* raw, int64_t n,
-                               const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, hipStream_t st) {
-    if (int e = ol_launch_frontend(c, (OlState*)(base + w.state), (float*)(base + w.X), raw, n, mean_std, windows, st)) return e;
+                               const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, const OlMap& map,
+                               hipStream_t st) {
+    if (int e = ol_launch_frontend(c, (OlState*)(base + w.state), (float*)(base + w.X), raw, n, mean_std, windows, map, st)) return e;
     if (int e = ola_chain(t, base, w, (const float*)(base + w.X), -1, c->max_windows, OLA_TRACK, base + w.C1, base + w.R2, base + w.H0,
                           base + w.H1, st))
         return e;
@@ -460,13 +515,14 @@ static int online_adapt_push_t(T t, const cp_online_config* c, unsigned char* ba
 
 extern "C" int cp_online_adapt_push(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* raw, int64_t n_samples,
                                     const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, void* stream) {
-    OlWS w;
-    if (int e = ol_check(cfg, ws, ws_bytes, true, &w)) return e;
-    if (int e = ol_check_push("cp_online_adapt_push", cfg, n_samples, raw, mean_std, pred, voted)) return e;
-    if (n_samples == 0) return 0;
-    return ol_dispatch(cfg->dtype, [&](auto t) {
-        return online_adapt_push_t(t, cfg, (unsigned char*)ws, w, raw, n_samples, mean_std, pred, voted, logits, windows, (hipStream_t)stream);
-    });
+    return ol_push("cp_online_adapt_push", true, cfg, ws, ws_bytes, raw, n_samples, mean_std, pred, voted, logits, windows, OlMap{}, stream);
+}
+
+extern "C" int cp_online_adapt_push_mapped(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* raw, int64_t n_samples,
+                                           const float* mean_std, const int32_t* map_src, const float* map_fill, int32_t* pred,
+                                           int32_t* voted, float* logits, float* windows, void* stream) {
+    return ol_push("cp_online_adapt_push_mapped", true, cfg, ws, ws_bytes, raw, n_samples, mean_std, pred, voted, logits, windows,
+                   OlMap{map_src, map_fill}, stream);
 }
 
 // calibration scratch: the normalised activations of all windows (two buffers), one chunk of conv2 operand and output, and
@@ -616,8 +672,8 @@ static void olm_row_blocks(int rows, int ftiles, int* blocks, int* tiles_per_blo
 template <typename T>
 static int online_multi_push_t(T t, const cp_online_config* c, int n_streams, unsigned char* base, const OlWS& w, const float* raw,
                                const int32_t* counts, int64_t total, int rows, const float* mean_std, int32_t* pred,
-                               int32_t* voted, float* logits, float* windows, hipStream_t st) {
-    if (int e = olm_launch_frontend(c, n_streams, base, w, raw, counts, total, rows, mean_std, windows, st)) return e;
+                               int32_t* voted, float* logits, float* windows, const OlMap& map, hipStream_t st) {
+    if (int e = olm_launch_frontend(c, n_streams, base, w, raw, counts, total, rows, mean_std, windows, map, st)) return e;
     OlmLayerArgs la{};
     la.rows = rows;
     auto layer = [&](const OlLayerArgs& l, auto conv) {
@@ -634,17 +690,41 @@ static int online_multi_push_t(T t, const cp_online_config* c, int n_streams, un
     return olm_launch_tail(t, c, n_streams, base, w, pred, voted, logits, st);
 }
 
+// cp_online_multi_push, cp_online_multi_adapt_push and their mapped forms
+template <typename T>
+static int online_multi_adapt_push_t(T t, const cp_online_config* c, int n_streams, unsigned char* base, const OlWS& w, const float* raw,
+                                     const int32_t* counts, int64_t total, int rows, const float* mean_std, int32_t* pred,
+                                     int32_t* voted, float* logits, float* windows, const OlMap& map, hipStream_t st);
+
+static int olm_push(const char* who, bool adaptive, const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
+                    size_t ws_bytes, const float* raw, const int32_t* counts, int64_t total_samples, int32_t total_windows,
+                    const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, const OlMap& map, void* stream) {
+    OlWS w;
+    if (int e = olm_check(cfg, n_streams, max_rows, ws, ws_bytes, adaptive, &w)) return e;
+    if (int e = olm_check_push(who, max_rows, raw, counts, total_samples, total_windows, mean_std, pred, voted)) return e;
+    if (int e = ol_check_map(who, map.src, map.fill, n_streams)) return e;
+    if (total_samples == 0) return 0;
+    return ol_dispatch(cfg->dtype, [&](auto t) {
+        return adaptive ? online_multi_adapt_push_t(t, cfg, n_streams, (unsigned char*)ws, w, raw, counts, total_samples, total_windows,
+                                                    mean_std, pred, voted, logits, windows, map, (hipStream_t)stream)
+                        : online_multi_push_t(t, cfg, n_streams, (unsigned char*)ws, w, raw, counts, total_samples, total_windows,
+                                              mean_std, pred, voted, logits, windows, map, (hipStream_t)stream);
+    });
+}
+
 extern "C" int cp_online_multi_push(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
                                     const float* raw, const int32_t* counts, int64_t total_samples, int32_t total_windows,
                                     const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows, void* stream) {
-    OlWS w;
-    if (int e = olm_check(cfg, n_streams, max_rows, ws, ws_bytes, false, &w)) return e;
-    if (int e = olm_check_push("cp_online_multi_push", max_rows, raw, counts, total_samples, total_windows, mean_std, pred, voted)) return e;
-    if (total_samples == 0) return 0;
-    return ol_dispatch(cfg->dtype, [&](auto t) {
-        return online_multi_push_t(t, cfg, n_streams, (unsigned char*)ws, w, raw, counts, total_samples, total_windows, mean_std, pred,
-                                   voted, logits, windows, (hipStream_t)stream);
-    });
+    return olm_push("cp_online_multi_push", false, cfg, n_streams, max_rows, ws, ws_bytes, raw, counts, total_samples, total_windows,
+                    mean_std, pred, voted, logits, windows, OlMap{}, stream);
+}
+
+extern "C" int cp_online_multi_push_mapped(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                           const float* raw, const int32_t* counts, int64_t total_samples, int32_t total_windows,
+                                           const float* mean_std, const int32_t* map_src, const float* map_fill, int32_t* pred,
+                                           int32_t* voted, float* logits, float* windows, void* stream) {
+    return olm_push("cp_online_multi_push_mapped", false, cfg, n_streams, max_rows, ws, ws_bytes, raw, counts, total_samples,
+                    total_windows, mean_std, pred, voted, logits, windows, OlMap{map_src, map_fill}, stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -723,8 +803,8 @@ static void olam_fc_blocks(int rows, int* blocks, int* rows_per_block) {
 template <typename T>
 static int online_multi_adapt_push_t(T t, const cp_online_config* c, int n_streams, unsigned char* base, const OlWS& w, const float* raw,
                                      const int32_t* counts, int64_t total, int rows, const float* mean_std, int32_t* pred,
-                                     int32_t* voted, float* logits, float* windows, hipStream_t st) {
-    if (int e = olm_launch_frontend(c, n_streams, base, w, raw, counts, total, rows, mean_std, windows, st)) return e;
+                                     int32_t* voted, float* logits, float* windows, const OlMap& map, hipStream_t st) {
+    if (int e = olm_launch_frontend(c, n_streams, base, w, raw, counts, total, rows, mean_std, windows, map, st)) return e;
     if (rows > 0) {
         const OlmMeta* meta = (const OlmMeta*)(base + w.meta);
         auto bn = [&](int l) { return ola_bn(base, w, l, OLA_TRACK, nullptr, 0, 0); };      // stream 0's: the kernels find their stream's
@@ -761,15 +841,17 @@ extern "C" int cp_online_multi_adapt_push(const cp_online_config* cfg, int32_t n
                                           const float* raw, const int32_t* counts, int64_t total_samples, int32_t total_windows,
                                           const float* mean_std, int32_t* pred, int32_t* voted, float* logits, float* windows,
                                           void* stream) {
-    OlWS w;
-    if (int e = olm_check(cfg, n_streams, max_rows, ws, ws_bytes, true, &w)) return e;
-    if (int e = olm_check_push("cp_online_multi_adapt_push", max_rows, raw, counts, total_samples, total_windows, mean_std, pred, voted))
-        return e;
-    if (total_samples == 0) return 0;
-    return ol_dispatch(cfg->dtype, [&](auto t) {
-        return online_multi_adapt_push_t(t, cfg, n_streams, (unsigned char*)ws, w, raw, counts, total_samples, total_windows, mean_std, pred,
-                                         voted, logits, windows, (hipStream_t)stream);
-    });
+    return olm_push("cp_online_multi_adapt_push", true, cfg, n_streams, max_rows, ws, ws_bytes, raw, counts, total_samples, total_windows,
+                    mean_std, pred, voted, logits, windows, OlMap{}, stream);
+}
+
+extern "C" int cp_online_multi_adapt_push_mapped(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
+                                                 size_t ws_bytes, const float* raw, const int32_t* counts, int64_t total_samples,
+                                                 int32_t total_windows, const float* mean_std, const int32_t* map_src,
+                                                 const float* map_fill, int32_t* pred, int32_t* voted, float* logits, float* windows,
+                                                 void* stream) {
+    return olm_push("cp_online_multi_adapt_push_mapped", true, cfg, n_streams, max_rows, ws, ws_bytes, raw, counts, total_samples,
+                    total_windows, mean_std, pred, voted, logits, windows, OlMap{map_src, map_fill}, stream);
 }
 
 extern "C" int cp_online_multi_adapt_statistics(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
@@ -787,22 +869,36 @@ extern "C" int cp_online_multi_adapt_statistics(const cp_online_config* cfg, int
 // ---------------------------------------------------------------------------------------
 extern "C" size_t cp_online_frontend_state_bytes(void) { return align256(offsetof(OlState, K)); }
 
-extern "C" int cp_online_windows(const cp_online_config* cfg, void* state, size_t state_bytes, const float* raw, int64_t n_samples,
-                                 const float* mean_std, float* windows, void* stream) {
-    if (!cfg || !state) return fail(CP_ERR_ARG, "cp_online_windows: config and state are required");
+static int ol_windows(const char* who, const cp_online_config* cfg, void* state, size_t state_bytes, const float* raw, int64_t n_samples,
+                      const float* mean_std, const OlMap& map, float* windows, void* stream) {
+    if (!cfg || !state) return ol_fail(CP_ERR_ARG, who, "config and state are required");
     if (int e = ol_check_config(cfg, state)) return e;
-    if (state_bytes < cp_online_frontend_state_bytes()) return fail(CP_ERR_ARG, "cp_online_windows: state too small");
+    if (state_bytes < cp_online_frontend_state_bytes()) return ol_fail(CP_ERR_ARG, who, "state too small");
     if (n_samples < 0 || n_samples > (int64_t)CP_ONLINE_STRIDE * cfg->max_windows)
-        return fail(CP_ERR_ARG, "cp_online_windows: a call takes at most 20 * max_windows samples");
+        return ol_fail(CP_ERR_ARG, who, "a call takes at most 20 * max_windows samples");
+    if (int e = ol_check_map(who, map.src, map.fill, 1)) return e;
     if (n_samples == 0) return 0;
-    if (!raw || !mean_std || !windows) return fail(CP_ERR_ARG, "cp_online_windows: raw, mean_std and windows are required");
-    if ((uintptr_t)raw % 4 || (uintptr_t)mean_std % 4 || (uintptr_t)windows % 4) return fail(CP_ERR_ARG, "cp_online_windows: misaligned input");
+    if (!raw || !mean_std || !windows) return ol_fail(CP_ERR_ARG, who, "raw, mean_std and windows are required");
+    if ((uintptr_t)raw % 4 || (uintptr_t)mean_std % 4 || (uintptr_t)windows % 4) return ol_fail(CP_ERR_ARG, who, "misaligned input");
     OlFrontArgs fa = ol_front_args(cfg);
     fa.raw = raw; fa.n = n_samples; fa.st = (OlState*)state; fa.X = windows; fa.windows = nullptr; fa.mean_std = mean_std;
+    fa.map_src = map.src; fa.map_fill = map.fill;
     if (cfg->n_coef == 9) hipLaunchKernelGGL((ole_windows_kernel<9>), dim3(1), dim3(256), 0, (hipStream_t)stream, fa);
     else hipLaunchKernelGGL((ole_windows_kernel<0>), dim3(1), dim3(256), 0, (hipStream_t)stream, fa);
     CKL("ole_windows_kernel");
     return 0;
+}
+
+extern "C" int cp_online_windows(const cp_online_config* cfg, void* state, size_t state_bytes, const float* raw, int64_t n_samples,
+                                 const float* mean_std, float* windows, void* stream) {
+    return ol_windows("cp_online_windows", cfg, state, state_bytes, raw, n_samples, mean_std, OlMap{}, windows, stream);
+}
+
+extern "C" int cp_online_windows_mapped(const cp_online_config* cfg, void* state, size_t state_bytes, const float* raw,
+                                        int64_t n_samples, const float* mean_std, const int32_t* map_src, const float* map_fill,
+                                        float* windows, void* stream) {
+    return ol_windows("cp_online_windows_mapped", cfg, state, state_bytes, raw, n_samples, mean_std, OlMap{map_src, map_fill}, windows,
+                      stream);
 }
 
 // enrolment scratch: the activations of one chunk of <= 256 windows (the adaptive form also conv2's operand and output)
@@ -1170,4 +1266,185 @@ extern "C" int cp_online_drive_push(const cp_online_drive_config* cfg, int32_t n
     hipLaunchKernelGGL(od_push_kernel, dim3(n_streams), dim3(64), 0, (hipStream_t)stream, a);
     CKL("od_push_kernel");
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// electrode-map sweep (csrc/online_maps.cuh): n_maps maps over one cued recording's RMS series, rows (map, window) through the
+// decoder's own encoder in chunks that fill the chip, then one wave per map through the vote ring
+// ---------------------------------------------------------------------------------------
+static_assert(OLMAP_SCORES == CP_ONLINE_MAP_SCORES, "map sweep layout");
+constexpr int64_t OLMAP_DEFAULT_CHUNK = 16384;           // rows: 1024 tiles, two per workgroup slot of a 512-workgroup fc launch x 32
+
+// sweep scratch: the windows and activations of one chunk (the adaptive forms also conv2's operand and output for a piece of
+// <= 256 rows)
+struct OlMapScratch {
+    size_t X, C1, R2, H0, H1, total;
+    int64_t chunk;
+};
+static OlMapScratch olmap_carve(int64_t n_rows, int64_t chunk_rows, int dtype, bool adaptive) {
+    const size_t es = dtype == CP_BF16 ? 2 : 4;
+    if (n_rows < 1) n_rows = 1;
+    int64_t chunk = chunk_rows > 0 ? chunk_rows : OLMAP_DEFAULT_CHUNK;
+    if (chunk > CP_ONLINE_MULTI_MAX_ROWS) chunk = CP_ONLINE_MULTI_MAX_ROWS;
+    if (chunk > n_rows) chunk = n_rows;
+    const size_t R = (size_t)((chunk + 15) / 16 * 16);
+    OlMapScratch c{};
+    c.chunk = chunk;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t r = o; o = align256(o + bytes); return r; };
+    c.X = take(R * OL_C * 4);
+    if (adaptive) {
+        c.C1 = take((size_t)OL_MAXM * OL_C * OL_CONV_K * es);
+        c.R2 = take((size_t)OL_MAXM * OL_C * 64 * 4);
+    }
+    c.H0 = take(R * 768 * es);
+    c.H1 = take(R * 512 * es);
+    c.total = o;
+    return c;
+}
+
+extern "C" size_t cp_online_map_sweep_scratch_bytes(int64_t n_rows, int64_t chunk_rows, int32_t dtype, int32_t adaptive) {
+    return olmap_carve(n_rows, chunk_rows, dtype, adaptive != 0).total;
+}
+
+struct OlMapSweep {                      // what the four sweep entries share
+    const float* rms;                    // (M, 12) device
+    int64_t n_windows;
+    const float* mean_std;
+    const int32_t* map_src;              // (n_maps, 12)
+    const float* map_fill;
+    int32_t n_maps, n_classes;
+    const int32_t* expected_slot;        // (M) device
+    int64_t chunk_rows;
+    void* scratch;
+    size_t scratch_bytes;
+    int32_t *pred, *voted;               // (n_maps, M)
+    int64_t* scores;
+    int32_t* class_hits;
+};
+
+template <typename T>
+static int online_map_sweep_t(T t, bool adaptive, const cp_online_config* c, unsigned char* base, const OlWS& w, const OlMapSweep& a,
+                              const OlMapScratch& k, hipStream_t st) {
+    unsigned char* sc = (unsigned char*)a.scratch;
+    const size_t es = sizeof(T);
+    const OlState* state = (const OlState*)(base + w.state);
+    const int M = (int)a.n_windows;
+    const int64_t total = (int64_t)a.n_maps * M;
+    for (int64_t r0 = 0; r0 < total; r0 += k.chunk) {
+        const int rows = (int)(total - r0 < k.chunk ? total - r0 : k.chunk);
+        OlMapBuildArgs b{};
+        b.R = a.rms; b.mean_std = a.mean_std; b.src = a.map_src; b.fill = a.map_fill; b.X = (float*)(sc + k.X); b.row0 = r0; b.rows = rows;
+        b.M = M;
+        hipLaunchKernelGGL(olmap_build_kernel, dim3((unsigned)(((int64_t)rows * OL_C + 255) / 256)), dim3(256), 0, st, b);
+        CKL("olmap_build_kernel");
+        if (adaptive) {
+            for (int p0 = 0; p0 < rows; p0 += OL_MAXM) {
+                const int m = rows - p0 < OL_MAXM ? rows - p0 : OL_MAXM;
+                if (int e = ola_chain(t, base, w, (const float*)(sc + k.X) + (size_t)p0 * OL_C, m, m, OLA_FROZEN, sc + k.C1, sc + k.R2,
+                                      sc + k.H0 + (size_t)p0 * 768 * es, sc + k.H1 + (size_t)p0 * 512 * es, st))
+                    return e;
+            }
+        } else {
+            OlmLayerArgs la{};
+            la.rows = rows;
+            auto layer = [&](const OlLayerArgs& l, auto conv) {
+                constexpr bool CONV = decltype(conv)::value;
+                int blocks;
+                olm_row_blocks(rows, CONV ? 4 * OL_C : 512 / 16, &blocks, &la.tiles_per_block);
+                la.l = l;
+                hipLaunchKernelGGL((olm_layer_kernel<T, CONV>), CONV ? dim3(4, OL_C, blocks) : dim3(512 / 16, blocks), dim3(OL_THREADS), 0, st,
+                                   la);
+                CKL(CONV ? "olm_layer_kernel<conv>" : "olm_layer_kernel<fc>");
+                return 0;
+            };
+            if (int e = ol_folded_chain(base, w, nullptr, (const float*)(sc + k.X), sc + k.H0, sc + k.H1, layer)) return e;
+        }
+        OlMapTailArgs ta{};
+        ta.proj = ol_layer_args(base, w, OL_PROJ, nullptr, sc + k.H1, nullptr);
+        ta.st = state; ta.slot = a.pred + r0; ta.rows = rows;
+        int blocks;
+        olm_row_blocks(rows, 1, &blocks, &ta.tiles_per_block);
+        hipLaunchKernelGGL((olmap_tail_kernel<T>), dim3(blocks), dim3(OL_THREADS), 0, st, ta);
+        CKL("olmap_tail_kernel");
+    }
+    OlMapVoteArgs v{};
+    v.st = state; v.expected = a.expected_slot; v.pred = a.pred; v.voted = a.voted; v.scores = (long long*)a.scores;
+    v.class_hits = a.class_hits; v.n_maps = a.n_maps; v.M = M; v.vote = c->vote;
+    hipLaunchKernelGGL(olmap_vote_kernel, dim3((a.n_maps + OLMAP_WAVES - 1) / OLMAP_WAVES), dim3(64 * OLMAP_WAVES), 0, st, v);
+    CKL("olmap_vote_kernel");
+    return 0;
+}
+
+// the four sweep entries: check_ws(&w) checks the entry's workspace arguments and gives the view of the stream to sweep with
+template <typename CheckWs>
+static int olmap_sweep(const char* who, const cp_online_config* cfg, CheckWs check_ws, bool adaptive, void* ws, const OlMapSweep& a,
+                       void* stream) {
+    if (a.n_maps < 1 || a.n_maps > CP_ONLINE_MAP_SWEEP_MAX_MAPS) return ol_fail(CP_ERR_ARG, who, "n_maps outside 1..65536");
+    if (a.n_classes < 1 || a.n_classes > CP_ONLINE_MAX_CLASSES) return ol_fail(CP_ERR_ARG, who, "n_classes outside 1..64");
+    if (a.n_windows < 1 || (int64_t)a.n_maps * a.n_windows > INT32_MAX) return ol_fail(CP_ERR_ARG, who, "n_windows < 1, or n_maps * n_windows >= 2^31");
+    if (a.chunk_rows < 0) return ol_fail(CP_ERR_ARG, who, "chunk_rows must not be negative (0: the default)");
+    OlWS w;
+    if (int e = check_ws(&w)) return e;
+    if (!a.rms || !a.mean_std || !a.map_src || !a.map_fill || !a.expected_slot || !a.scratch || !a.pred || !a.scores)
+        return ol_fail(CP_ERR_ARG, who, "rms, mean_std, map_src, map_fill, expected_slot, scratch, pred and scores are required");
+    if ((uintptr_t)a.rms % 4 || (uintptr_t)a.mean_std % 4 || (uintptr_t)a.expected_slot % 4 || (uintptr_t)a.scratch % 256 ||
+        (uintptr_t)a.pred % 4 || (uintptr_t)a.voted % 4 || (uintptr_t)a.scores % 8 || (uintptr_t)a.class_hits % 4)
+        return ol_fail(CP_ERR_ARG, who, "misaligned argument");
+    if (int e = ol_check_map(who, a.map_src, a.map_fill, a.n_maps)) return e;
+    const OlMapScratch k = olmap_carve((int64_t)a.n_maps * a.n_windows, a.chunk_rows, cfg->dtype, adaptive);
+    if (a.scratch_bytes < k.total) return ol_fail(CP_ERR_WORKSPACE, who, "scratch too small");
+    return ol_dispatch(cfg->dtype, [&](auto t) {
+        return online_map_sweep_t(t, adaptive, cfg, (unsigned char*)ws, w, a, k, (hipStream_t)stream);
+    });
+}
+
+extern "C" int cp_online_map_sweep(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* rms, int64_t n_windows,
+                                   const float* mean_std, const int32_t* map_src, const float* map_fill, int32_t n_maps,
+                                   int32_t n_classes, const int32_t* expected_slot, int64_t chunk_rows, void* scratch,
+                                   size_t scratch_bytes, int32_t* pred, int32_t* voted, int64_t* scores, int32_t* class_hits,
+                                   void* stream) {
+    const OlMapSweep a{rms, n_windows, mean_std, map_src, map_fill, n_maps, n_classes, expected_slot, chunk_rows, scratch, scratch_bytes,
+                       pred, voted, scores, class_hits};
+    return olmap_sweep("cp_online_map_sweep", cfg, [&](OlWS* w) { return ol_check(cfg, ws, ws_bytes, false, w); }, false, ws, a, stream);
+}
+
+extern "C" int cp_online_adapt_map_sweep(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* rms, int64_t n_windows,
+                                         const float* mean_std, const int32_t* map_src, const float* map_fill, int32_t n_maps,
+                                         int32_t n_classes, const int32_t* expected_slot, int64_t chunk_rows, void* scratch,
+                                         size_t scratch_bytes, int32_t* pred, int32_t* voted, int64_t* scores, int32_t* class_hits,
+                                         void* stream) {
+    const OlMapSweep a{rms, n_windows, mean_std, map_src, map_fill, n_maps, n_classes, expected_slot, chunk_rows, scratch, scratch_bytes,
+                       pred, voted, scores, class_hits};
+    return olmap_sweep("cp_online_adapt_map_sweep", cfg, [&](OlWS* w) { return ol_check(cfg, ws, ws_bytes, true, w); }, true, ws, a, stream);
+}
+
+extern "C" int cp_online_multi_map_sweep(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                         int32_t index, const float* rms, int64_t n_windows, const float* mean_std,
+                                         const int32_t* map_src, const float* map_fill, int32_t n_maps, int32_t n_classes,
+                                         const int32_t* expected_slot, int64_t chunk_rows, void* scratch, size_t scratch_bytes,
+                                         int32_t* pred, int32_t* voted, int64_t* scores, int32_t* class_hits, void* stream) {
+    const char* who = "cp_online_multi_map_sweep";
+    const OlMapSweep a{rms, n_windows, mean_std, map_src, map_fill, n_maps, n_classes, expected_slot, chunk_rows, scratch, scratch_bytes,
+                       pred, voted, scores, class_hits};
+    auto check_ws = [&](OlWS* w) {
+        if (int e = olm_check(cfg, n_streams, max_rows, ws, ws_bytes, false, w)) return e;
+        if (int e = ol_check_index(who, index, n_streams)) return e;
+        w->state += (size_t)index * sizeof(OlState);       // the stream's class table; the folded weights are shared
+        return 0;
+    };
+    return olmap_sweep(who, cfg, check_ws, false, ws, a, stream);
+}
+
+extern "C" int cp_online_multi_adapt_map_sweep(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
+                                               size_t ws_bytes, int32_t index, const float* rms, int64_t n_windows,
+                                               const float* mean_std, const int32_t* map_src, const float* map_fill, int32_t n_maps,
+                                               int32_t n_classes, const int32_t* expected_slot, int64_t chunk_rows, void* scratch,
+                                               size_t scratch_bytes, int32_t* pred, int32_t* voted, int64_t* scores,
+                                               int32_t* class_hits, void* stream) {
+    const char* who = "cp_online_multi_adapt_map_sweep";
+    const OlMapSweep a{rms, n_windows, mean_std, map_src, map_fill, n_maps, n_classes, expected_slot, chunk_rows, scratch, scratch_bytes,
+                       pred, voted, scores, class_hits};
+    return olmap_sweep(who, cfg, [&](OlWS* w) { return olam_check_stream(who, cfg, n_streams, max_rows, ws, ws_bytes, index, w); }, true,
+                       ws, a, stream);
 }

@@ -23,7 +23,8 @@ struct OlmMeta {                         // what the front end leaves for the ta
 };
 
 struct OlmFrontArgs {
-    OlFrontArgs f;                       // raw: packed samples; X, windows: packed rows (f.st and f.n are unused)
+    OlFrontArgs f;                       // raw: packed samples; X, windows: packed rows; map_src, map_fill: one row per stream
+                                         // (f.st and f.n are unused)
     OlState* states;                     // [S]
     OlmMeta* meta;                       // [S]
     const int32_t* counts;               // [S] samples of each stream in this push
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(256) void olm_frontend_kernel(OlmFrontArgs p) {
     }
     if (n > 0)
         ol_frontend_run<NB>(p.f, st, p.f.raw + soff * OL_C, n, n0, p.f.X + (size_t)row0 * OL_C,
-                            p.f.windows ? p.f.windows + (size_t)row0 * OL_C : nullptr, xs);
+                            p.f.windows ? p.f.windows + (size_t)row0 * OL_C : nullptr, xs, s);
     if (tid == 0) {
         p.meta[s].n_seen = n0 + n;
         p.meta[s].row0 = row0;

@@ -35,6 +35,13 @@ definition), all subsets of a size where that is affordable and a beam beyond, a
 decoders already emit, and the health of every electrode, on the device behind a gate or a decoder (cp_online_drive_*,
 csrc/online_drive.cuh); `drive_profile` makes its profile from the cued recording enrolment already has.
 
+`set_channel_map` tells a decoder which physical electrode feeds each model channel, or that a channel is masked (a sleeve
+that went back on rotated, a dead electrode): the front end reads the map in its own launch (cp_online_*_mapped), and
+everything behind it -- encoder, gate, drive, enrolment, calibration -- sees model channels.  `score_channel_maps` finds the
+map: it scores many candidates (`rotations`, `leave_one_out`) over a cued recording in one pass on the device
+(cp_online_*map_sweep, csrc/online_maps.cuh) exactly as fresh mapped decoders would decode it, and `pick_channel_map` takes
+the best.
+
 The number of windows a push emits follows from sample counts alone (`windows_emitted`), so a push never waits for the device:
 its outputs are device tensors on torch's current stream.
 """
@@ -138,6 +145,44 @@ def _check_raw(t, what: str = "raw"):
         raise ValueError(f"{what} must be an (n, 12) float32 tensor on the GPU")
 
 
+def _check_map(src, fill=None):
+    """An electrode map as `set_channel_map` takes it -> (src (12,) int32, fill (12,) float32) numpy arrays, or None for
+    src=None.  src[d] in -1..11: the physical channel that feeds model channel d, -1 masked; fill: one value or 12, finite."""
+    if src is None:
+        if fill is not None:
+            raise ValueError("fill goes with a map: src=None clears the map")
+        return None
+    a = np.asarray(src)
+    if a.ndim != 1 or a.shape[0] != EMG_DIM:
+        raise ValueError(f"src must hold {EMG_DIM} entries: the physical channel of each model channel, or -1")
+    if a.dtype.kind not in "iu":
+        raise ValueError("src must be integers")
+    a = a.astype(np.int64)
+    if a.min() < -1 or a.max() >= EMG_DIM:
+        raise ValueError(f"src must lie in -1..{EMG_DIM - 1}")
+    f = np.zeros(EMG_DIM, dtype=np.float32) if fill is None else np.asarray(fill, dtype=np.float32).reshape(-1)
+    if f.shape[0] == 1:
+        f = np.repeat(f, EMG_DIM)
+    if f.shape[0] != EMG_DIM:
+        raise ValueError(f"fill: one value or one per model channel ({EMG_DIM})")
+    if not np.isfinite(f).all():
+        raise ValueError("fill must be finite")
+    return a.astype(np.int32), f.astype(np.float32)
+
+
+def _map_on_device(m, device):
+    """(src, fill) of `_check_map` as one (12,) int32 and one (12,) float32 device tensor"""
+    return torch.as_tensor(m[0]).to(device), torch.as_tensor(m[1]).to(device)
+
+
+def _map_windows(w: torch.Tensor, m) -> torch.Tensor:
+    """the masked columns of the windows w (K, 12) overwritten with the map's fill"""
+    masked = np.nonzero(m[0] < 0)[0]
+    if masked.size:
+        w[:, torch.as_tensor(masked, device=w.device)] = torch.as_tensor(m[1][masked], device=w.device)
+    return w
+
+
 class _OnStream:
     """a decoder or gate on `self.device`: its C entries run on torch's current stream there"""
 
@@ -190,12 +235,16 @@ def _class_table(e: Engine, classes=None, glove=None, table=None, ids=None):
     return tab.to(torch.float32).contiguous(), ids_t
 
 
-def _calibration_windows(raw: torch.Tensor, b, a, phase: int, mean_std: torch.Tensor) -> torch.Tensor:
+def _calibration_windows(raw: torch.Tensor, b, a, phase: int, mean_std: torch.Tensor, channel_map=None) -> torch.Tensor:
     """The windows a fresh stream emits for `raw` (n, 12), by the offline path (preprocess_segments + normalize_): the whole
     recording as one segment, 256 kept positions per call.  Valid for a recording of any length: cp_preprocess_emg keeps
-    its positions in 32 bits."""
+    its positions in 32 bits.  channel_map (src, fill of `_check_map`): the windows in model channels -- the raw columns
+    permuted by src first, the masked columns overwritten with fill last."""
     from .preprocess import normalize_, preprocess_segments
     _check_raw(raw)
+    if channel_map is not None:
+        cols = np.where(channel_map[0] < 0, np.arange(EMG_DIM), channel_map[0])
+        raw = raw[:, torch.as_tensor(cols, dtype=torch.long, device=raw.device)]
     k = windows_before(raw.shape[0], phase)
     if k < 2:
         raise ValueError("calibration takes at least 2 windows")
@@ -203,7 +252,8 @@ def _calibration_windows(raw: torch.Tensor, b, a, phase: int, mean_std: torch.Te
     keep = phase + STRIDE * np.arange(k)
     step = _lib.CP_ONLINE_MAX_WINDOWS                      # positions one call of the offline transform keeps
     w = torch.cat([preprocess_segments(raw, b=b, a=a, keep=keep[i:i + step]) for i in range(0, k, step)], dim=1)
-    return normalize_(w.contiguous(), mean_std[0], mean_std[1])[0]
+    w = normalize_(w.contiguous(), mean_std[0], mean_std[1])[0]
+    return w if channel_map is None else _map_windows(w, channel_map)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -228,12 +278,14 @@ def window_labels(labels, phase: int = 0) -> np.ndarray:
     return np.where(same, span[:, 0], -1)
 
 
-def recording_windows(raw: torch.Tensor, mean_std: torch.Tensor, b=None, a=None, phase: int = 0) -> torch.Tensor:
+def recording_windows(raw: torch.Tensor, mean_std: torch.Tensor, b=None, a=None, phase: int = 0, channel_map=None) -> torch.Tensor:
     """The windows a fresh stream emits for `raw` (n, 12) f32 on the GPU, (K, 12) with K = windows_before(n, phase): one pass
     of the stateful front end (cp_online_windows) over the recording, bit-identical to the offline path
     (`preprocess_segments` + `normalize_`), which filters the recording again for every 256 positions it keeps.  mean_std
-    (2, 12) f32 on the GPU."""
+    (2, 12) f32 on the GPU.  channel_map: None, or (src, fill) as `set_channel_map` takes them -- the windows in model
+    channels, as a decoder with that map emits them (cp_online_windows_mapped)."""
     _check_raw(raw)
+    cmap = None if channel_map is None else _check_map(*channel_map)
     if not 0 <= int(phase) < STRIDE:
         raise ValueError(f"phase must lie in 0..{STRIDE - 1}")
     b, a = _filter(b, a)
@@ -248,12 +300,18 @@ def recording_windows(raw: torch.Tensor, mean_std: torch.Tensor, b=None, a=None,
     state = torch.zeros(lib.cp_online_frontend_state_bytes(), dtype=torch.uint8, device=raw.device)
     stream = torch.cuda.current_stream(raw.device).cuda_stream
     step = STRIDE * _lib.CP_ONLINE_MAX_WINDOWS
+    dev_map = None if cmap is None else _map_on_device(cmap, raw.device)
     for s in range(0, n, step):
         m = min(step, n - s)
         row = windows_before(s, phase)                         # 20 W samples complete at most W windows: out has the room
-        _lib.check(lib.cp_online_windows(C.byref(cfg), state.data_ptr(), state.numel(), raw[s:].data_ptr(), m, mean_std.data_ptr(),
-                                         out[row:].data_ptr() if row < out.shape[0] else out.data_ptr(), stream),
-                   "cp_online_windows")
+        dst = out[row:].data_ptr() if row < out.shape[0] else out.data_ptr()
+        if dev_map is None:
+            _lib.check(lib.cp_online_windows(C.byref(cfg), state.data_ptr(), state.numel(), raw[s:].data_ptr(), m, mean_std.data_ptr(),
+                                             dst, stream), "cp_online_windows")
+        else:
+            _lib.check(lib.cp_online_windows_mapped(C.byref(cfg), state.data_ptr(), state.numel(), raw[s:].data_ptr(), m,
+                                                    mean_std.data_ptr(), dev_map[0].data_ptr(), dev_map[1].data_ptr(), dst, stream),
+                       "cp_online_windows_mapped")
     return out[:windows_before(n, phase)]
 
 
@@ -328,7 +386,7 @@ class _EnrollMixin(_OnStream):
             rec.acc, rec.ids = acc, ids
         rec.counts = counts
         self._enroll_rec[key] = rec
-        w = recording_windows(raw, self.mean_std, self._b, self._a, self.phase)
+        w = recording_windows(raw, self.mean_std, self._b, self._a, self.phase, channel_map=self._map_of(key))
         w = w[torch.as_tensor(keep, device=self.device)].contiguous()
         slots_dev = torch.as_tensor(slots.astype(np.int32), device=self.device)
         scratch = torch.empty(self.lib.cp_online_enroll_scratch_bytes(w.shape[0], self._cfg.dtype), dtype=torch.uint8, device=self.device)
@@ -394,6 +452,8 @@ class OnlineDecoder(_EnrollMixin):
         self.n_seen = 0
         self.class_ids: Optional[torch.Tensor] = None
         self._enroll_rec = {}
+        self._map = None                                   # electrode map: (src, fill) numpy, and its device copy
+        self._map_dev = None
         self.refresh()
         if classes is not None:
             self.set_classes(classes)
@@ -443,6 +503,29 @@ class OnlineDecoder(_EnrollMixin):
         _lib.check(self.lib.cp_online_reset(C.byref(self._cfg), *self._ws(), self._stream()), "cp_online_reset")
         self.n_seen = 0
 
+    def set_channel_map(self, src=None, fill=None):
+        """Which physical electrode feeds each model channel.  src: 12 integers, src[d] the raw column 0..11 that model channel d
+        reads, or -1: masked; it need not be a permutation (a dead electrode may be replaced by a neighbour).  fill: what a
+        masked channel emits in normalised units, one value or 12 (default 0.0, the training mean); read only where src is -1.
+        src=None clears the map; the identity map decodes as no map does.
+
+        With a map model channel d filters raw column src[d] with its own filter state, normalises with mean[d] and std[d] and
+        fills column d of the windows, so a mapped decoder fed `raw` equals an unmapped one fed `raw[:, src]` bit for bit, and
+        everything behind the front end -- the encoder, a `CommandGate`, a `GraspDrive` and its `bad` electrodes, `enroll`,
+        `calibrate` -- sees model channels.  A masked channel emits `fill` exactly; its filter keeps running on zeros.
+        Changing the map in mid-stream leaves a filter transient on the changed channels, as plugging a cable would;
+        `reset()` clears it.  The map survives `reset()`, `refresh()` and `set_classes()`."""
+        m = _check_map(src, fill)
+        self._map = m
+        self._map_dev = None if m is None else _map_on_device(m, self.device)
+
+    def channel_map(self):
+        """None, or (src (12,) int32, fill (12,) float32) numpy arrays as `set_channel_map` took them."""
+        return None if self._map is None else (self._map[0].copy(), self._map[1].copy())
+
+    def _map_of(self, key):
+        return self._map
+
     def push(self, raw: torch.Tensor, return_logits: bool = False, return_windows: bool = False):
         """raw (n, 12) f32 on the GPU: the next n samples of the stream.  Returns (pred, voted[, logits][, windows]) for the
         M = windows_emitted(n_seen, n, phase) windows the chunk completes: pred, voted (M,) int32 class ids, logits (M, K) f32,
@@ -466,10 +549,12 @@ class OnlineDecoder(_EnrollMixin):
             pred, voted = pv[0, :M], pv[1, :M]
             logits = torch.empty(M, K, dtype=torch.float32, device=self.device) if return_logits else None
             wins = torch.empty(M, EMG_DIM, dtype=torch.float32, device=self.device) if return_windows else None
-            fn = self.lib.cp_online_push if self.adapt is None else self.lib.cp_online_adapt_push
-            _lib.check(fn(C.byref(self._cfg), *self._ws(), piece.data_ptr(), n, self.mean_std.data_ptr(),
+            name = "cp_online_push" if self.adapt is None else "cp_online_adapt_push"
+            cmap = () if self._map_dev is None else (self._map_dev[0].data_ptr(), self._map_dev[1].data_ptr())
+            fn = getattr(self.lib, name + "_mapped" if cmap else name)
+            _lib.check(fn(C.byref(self._cfg), *self._ws(), piece.data_ptr(), n, self.mean_std.data_ptr(), *cmap,
                           pv[0].data_ptr(), pv[1].data_ptr(), logits.data_ptr() if logits is not None else None,
-                          wins.data_ptr() if wins is not None else None, self._stream()), "cp_online_push")
+                          wins.data_ptr() if wins is not None else None, self._stream()), name)
             self.n_seen += n
             outs.append((pred, voted, logits, wins))
         if not outs:
@@ -505,7 +590,8 @@ class OnlineDecoder(_EnrollMixin):
         `enroll_reset()` or the next `set_classes()`.  Returns {class id: windows accumulated so far}.
 
         Prototypes belong to the weights and statistics they were taken with: enrol after `calibrate()`, and again (after
-        `enroll_reset()`) after a `refresh()` that changed the weights."""
+        `enroll_reset()`) after a `refresh()` that changed the weights.  Under an electrode map (`set_channel_map`) the
+        recording is read through the map, so the prototypes are taken in model channels."""
         return self._enroll(None, raw, labels, mix, min_windows, add, accumulate)
 
     def enroll_reset(self):
@@ -540,12 +626,13 @@ class OnlineDecoder(_EnrollMixin):
 
     def calibration_windows(self, raw: torch.Tensor) -> torch.Tensor:
         """The windows a fresh stream would emit for `raw` (n, 12), by the offline path: preprocess_segments + normalize_ with
-        this decoder's filter, phase, mean and std."""
-        return _calibration_windows(raw, self._b, self._a, self.phase, self.mean_std)
+        this decoder's filter, phase, mean and std, in model channels under the decoder's electrode map."""
+        return _calibration_windows(raw, self._b, self._a, self.phase, self.mean_std, self._map)
 
     def calibrate(self, raw: torch.Tensor):
         """AdaBN calibration from a recording raw (n, 12) f32 on the GPU: every BatchNorm's statistics become the batch
-        statistics of the recording's windows, layer by layer (include/cpnative.h).  Stream state, vote ring and classes stay."""
+        statistics of the recording's windows, layer by layer (include/cpnative.h).  Stream state, vote ring and classes stay.
+        Under an electrode map the windows, and so the statistics, are taken in model channels."""
         self._need_adapt("calibrate()")
         if raw.dim() != 2 or windows_before(raw.shape[0], self.phase) < 2:
             raise ValueError("calibration takes at least 2 windows")
@@ -649,6 +736,9 @@ class _MultiStreamBase(_EnrollMixin):
         self._k = [0] * self.n_streams                     # classes per stream
         self._counts_cache = None
         self._enroll_rec = {}
+        self._maps = [None] * self.n_streams               # electrode maps: (src, fill) numpy per stream, None: the identity
+        self._map_src = torch.arange(EMG_DIM, dtype=torch.int32, device=self.device).repeat(self.n_streams, 1).contiguous()
+        self._map_fill = torch.zeros(self.n_streams, EMG_DIM, dtype=torch.float32, device=self.device)
 
     # ------------------------------------------------------------------ helpers
     def _args(self):
@@ -687,6 +777,27 @@ class _MultiStreamBase(_EnrollMixin):
         self._has_table[s] = True
         self._k[s] = int(ids32.numel())
         self._enroll_rec.pop(s, None)                          # the accumulator is laid out by the id list
+
+    def set_channel_map(self, stream: int, src=None, fill=None):
+        """The electrode map of one stream, as `OnlineDecoder.set_channel_map`: src[d] the raw column that feeds model channel
+        d or -1 (masked, emits fill[d]); src=None clears it.  The maps of all streams live in one small device array that a
+        push reads in its front-end launch; the other streams, and this stream's state, are not touched.  The map survives
+        `reset()`, `refresh()` and `set_classes()`; under it `enroll` and `calibrate` of the stream work in model channels."""
+        s = self._index(stream)
+        m = _check_map(src, fill)
+        self._maps[s] = m
+        ident = (np.arange(EMG_DIM, dtype=np.int32), np.zeros(EMG_DIM, dtype=np.float32))
+        src_dev, fill_dev = _map_on_device(m if m is not None else ident, self.device)
+        self._map_src[s].copy_(src_dev)
+        self._map_fill[s].copy_(fill_dev)
+
+    def channel_map(self, stream: int):
+        """None, or (src (12,) int32, fill (12,) float32) numpy arrays of one stream."""
+        m = self._maps[self._index(stream)]
+        return None if m is None else (m[0].copy(), m[1].copy())
+
+    def _map_of(self, s):
+        return self._maps[s]
 
     def enroll(self, stream: int, raw: torch.Tensor, labels, *, mix: float = 1.0, min_windows: int = 25, add: bool = False,
                accumulate: bool = False) -> dict:
@@ -807,10 +918,12 @@ class _MultiStreamBase(_EnrollMixin):
             logits = torch.empty(R, MAX_CLASSES, dtype=torch.float32, device=self.device) if return_logits else None
             wins = torch.empty(R, EMG_DIM, dtype=torch.float32, device=self.device) if return_windows else None
             if piece.shape[0]:
-                _lib.check(getattr(self.lib, self._ENTRY + "_push")(
+                cmap = (self._map_src.data_ptr(), self._map_fill.data_ptr()) if any(m is not None for m in self._maps) else ()
+                _lib.check(getattr(self.lib, self._ENTRY + ("_push_mapped" if cmap else "_push"))(
                     *self._args(), piece.data_ptr(), self._counts_on_device(take).data_ptr(), int(piece.shape[0]), R,
-                    self.mean_std.data_ptr(), pv[0].data_ptr(), pv[1].data_ptr(), logits.data_ptr() if logits is not None else None,
-                    wins.data_ptr() if wins is not None else None, self._stream()), self._ENTRY + "_push")
+                    self.mean_std.data_ptr(), *cmap, pv[0].data_ptr(), pv[1].data_ptr(),
+                    logits.data_ptr() if logits is not None else None, wins.data_ptr() if wins is not None else None,
+                    self._stream()), self._ENTRY + "_push")
             self._seen += take
             ml = m.tolist()
             cols = [pv[0, :R].split(ml), pv[1, :R].split(ml)]
@@ -928,12 +1041,13 @@ class AdaptiveMultiStreamDecoder(_MultiStreamBase):
         self.alpha[s] = float(alpha)
 
     def calibrate(self, stream: int, raw: torch.Tensor):
-        """AdaBN calibration of one stream from a recording raw (n, 12) f32 on the GPU, as OnlineDecoder.calibrate.  No other
-        stream's statistics, and no stream's filter state, vote ring or class table, change."""
+        """AdaBN calibration of one stream from a recording raw (n, 12) f32 on the GPU, as OnlineDecoder.calibrate (in model
+        channels under the stream's electrode map).  No other stream's statistics, and no stream's filter state, vote ring or
+        class table, change."""
         s = self._index(stream)
         if raw.dim() != 2 or windows_before(raw.shape[0], self.phase) < 2:
             raise ValueError("calibration takes at least 2 windows")
-        w = _calibration_windows(raw, self._b, self._a, self.phase, self.mean_std).contiguous()
+        w = _calibration_windows(raw, self._b, self._a, self.phase, self.mean_std, self._maps[s]).contiguous()
         scratch = torch.empty(self.lib.cp_online_adapt_calibrate_scratch_bytes(w.shape[0], self._cfg.dtype), dtype=torch.uint8,
                               device=self.device)
         _lib.check(self.lib.cp_online_multi_adapt_calibrate(*self._args(), s, w.data_ptr(), w.shape[0], scratch.data_ptr(),
@@ -2098,3 +2212,137 @@ def search_grasp_sets(logits, expected, ids, min_size: int = 2, max_size=None, v
     for rec in found:
         rec["best"] = [(tuple(int(cid[i]) for i in range(cid.shape[0]) if mask >> i & 1), sc) for mask, sc in rec["best"]]
     return found
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# electrode maps: candidates, the sweep that scores them on the device (cp_online_*map_sweep, csrc/online_maps.cuh), the pick
+# ---------------------------------------------------------------------------------------------------------------------------
+MAP_SCORE_KEYS = ("rows", "raw_hits", "voted_hits")
+MAX_MAPS = _lib.CP_ONLINE_MAP_SWEEP_MAX_MAPS
+
+
+def rotations(ring=(0, 1, 2, 3, 4, 5, 6, 7), reflect: bool = False) -> np.ndarray:
+    """The maps of a sleeve that went back on turned around the forearm: (8, 12) int32, row s the ring shifted by s electrode
+    positions (src[ring[i]] = ring[(i + s) % n]; row 0 is the identity), the other channels in place.  reflect=True adds the
+    n mirrored ones (src[ring[i]] = ring[(s - i) % n]: the sleeve inside out or on the other arm), 16 rows.  The default ring
+    is the Ninapro DB2 layout: electrodes 1-8 equally spaced around the forearm, 9-10 on flexor / extensor digitorum, 11-12
+    on biceps / triceps; other sleeves pass their own ring, in order around the arm."""
+    r = np.asarray(ring, dtype=np.int64).reshape(-1)
+    n = r.shape[0]
+    if n < 2 or len(set(r.tolist())) != n or r.min() < 0 or r.max() >= EMG_DIM:
+        raise ValueError(f"ring: at least 2 distinct channels in 0..{EMG_DIM - 1}, in order around the arm")
+    maps = []
+    for mirror in ((False, True) if reflect else (False,)):
+        for s in range(n):
+            m = np.arange(EMG_DIM, dtype=np.int32)
+            for i in range(n):
+                m[r[i]] = r[(s - i) % n] if mirror else r[(i + s) % n]
+            maps.append(m)
+    return np.stack(maps)
+
+
+def leave_one_out() -> np.ndarray:
+    """The 12 maps that mask one electrode each: (12, 12) int32, row d the identity with src[d] = -1.  Scored with
+    `score_channel_maps` they price a dead electrode before anything is masked."""
+    m = np.tile(np.arange(EMG_DIM, dtype=np.int32), (EMG_DIM, 1))
+    m[np.arange(EMG_DIM), np.arange(EMG_DIM)] = -1
+    return m
+
+
+def _sweep_target(decoder, stream):
+    """(entry name, leading arguments, class ids (K,) int64, adaptive, calibrated) of the decoder (and stream) a sweep runs on"""
+    if isinstance(decoder, _MultiStreamBase):
+        if stream is None:
+            raise ValueError("a multi-stream decoder needs stream=")
+        s = decoder._index(stream)
+        if not decoder._has_table[s]:
+            raise _lib.CpNativeError(f"stream {s} has no class table: set_classes({s}, ...) first")
+        return (decoder._ENTRY + "_map_sweep", (*decoder._args(), s), decoder.class_ids[s].numpy().astype(np.int64),
+                decoder._ENTRY.endswith("adapt"), decoder._enroll_calibrated(s))
+    if isinstance(decoder, OnlineDecoder):
+        if stream is not None:
+            raise ValueError("stream= goes with a multi-stream decoder")
+        if decoder.class_ids is None:
+            raise _lib.CpNativeError("set_classes() first")
+        adaptive = decoder.adapt is not None
+        return ("cp_online_adapt_map_sweep" if adaptive else "cp_online_map_sweep", (C.byref(decoder._cfg), *decoder._ws()),
+                decoder.class_ids.numpy().astype(np.int64), adaptive, decoder.calibrated)
+    raise TypeError("score_channel_maps takes an OnlineDecoder, a MultiStreamDecoder or an AdaptiveMultiStreamDecoder")
+
+
+def score_channel_maps(decoder, raw: torch.Tensor, labels, maps, fills=None, stream=None, return_pred: bool = False,
+                       chunk_rows=None, per_class: bool = False):
+    """Score many electrode maps over one cued recording in one pass on the device.  raw (n, 12) f32 on the GPU and labels (n,)
+    are the recording `enroll` takes; maps (n_maps, 12) integers, one `set_channel_map` src per row (`rotations()`,
+    `leave_one_out()`, your own); fills None (0.0) or (n_maps, 12).
+
+    The definition, for map g: take a fresh stream of the same decoder -- same weights and class table, the vote ring empty,
+    on the adaptive forms the current statistics frozen as `enroll` freezes them --, `set_channel_map(maps[g], fills[g])`,
+    push the whole recording and count.  Returns one dict per map: rows (the windows whose `window_labels` class is in the
+    decoder's table), raw_hits and voted_hits (of those, the windows whose pred / voted equals the cue), and with
+    per_class=True per_class_voted_hits (K,) in the order of the decoder's class ids.  With return_pred=True returns
+    (scores, pred, voted), pred and voted (n_maps, M) int32 class ids on the GPU.  The device pass reproduces the
+    definition's pred and voted exactly; the decoder's live stream is not touched.
+
+    The front end runs once for all maps (the un-normalised RMS series of the recording); rows (map, window) then run through
+    the encoder in chunks of chunk_rows rows (default: sized to fill the chip), which the results do not depend on."""
+    name, lead, ids, adaptive, calibrated = _sweep_target(decoder, stream)
+    if not calibrated:
+        raise _lib.CpNativeError("an AdaBN model has no BatchNorm statistics: calibrate() first")
+    _check_raw(raw)
+    lab = _sample_labels(labels, raw.shape[0])
+    src = np.asarray(maps)
+    if src.ndim != 2 or src.shape[1] != EMG_DIM or src.shape[0] < 1:
+        raise ValueError(f"maps must be (n_maps, {EMG_DIM})")
+    n_maps = src.shape[0]
+    if n_maps > MAX_MAPS:
+        raise ValueError(f"at most {MAX_MAPS} maps")
+    fl = np.zeros((n_maps, EMG_DIM), dtype=np.float32) if fills is None else np.asarray(fills, dtype=np.float32)
+    if fl.shape != (n_maps, EMG_DIM):
+        raise ValueError(f"fills must be (n_maps, {EMG_DIM})")
+    checked = [_check_map(src[g], fl[g]) for g in range(n_maps)]
+    src32 = np.stack([c[0] for c in checked])
+    fl32 = np.stack([c[1] for c in checked])
+    if chunk_rows is not None and int(chunk_rows) < 1:
+        raise ValueError("chunk_rows must be at least 1")
+    wl = window_labels(lab, decoder.phase)
+    M = wl.shape[0]
+    if M < 1:
+        raise ValueError("the recording completes no window")
+    if n_maps * M >= 2 ** 31:
+        raise ValueError("n_maps * windows must stay below 2**31")
+    slot = np.searchsorted(ids, wl)
+    slot = np.where((slot < ids.size) & (ids[np.minimum(slot, ids.size - 1)] == wl), slot, -1).astype(np.int32)
+    # ---- everything is checked: from here on work is enqueued
+    dev, lib = decoder.device, decoder.lib
+    unit = torch.stack([torch.zeros(EMG_DIM, device=dev), torch.ones(EMG_DIM, device=dev)])
+    rms = recording_windows(raw, unit, decoder._b, decoder._a, decoder.phase).contiguous()
+    src_d, fill_d, slot_d = torch.as_tensor(src32).to(dev), torch.as_tensor(fl32).to(dev), torch.as_tensor(slot).to(dev)
+    pred = torch.empty(n_maps, M, dtype=torch.int32, device=dev)
+    voted = torch.empty(n_maps, M, dtype=torch.int32, device=dev) if return_pred else None
+    scores = torch.zeros(n_maps, len(MAP_SCORE_KEYS), dtype=torch.int64, device=dev)
+    hits = torch.zeros(n_maps, MAX_CLASSES, dtype=torch.int32, device=dev) if per_class else None
+    chunk = 0 if chunk_rows is None else int(chunk_rows)
+    scratch = torch.empty(lib.cp_online_map_sweep_scratch_bytes(n_maps * M, chunk, decoder._cfg.dtype, int(adaptive)),
+                          dtype=torch.uint8, device=dev)
+    _lib.check(getattr(lib, name)(*lead, rms.data_ptr(), M, decoder.mean_std.data_ptr(), src_d.data_ptr(), fill_d.data_ptr(), n_maps,
+                                  int(ids.size), slot_d.data_ptr(), chunk, scratch.data_ptr(), scratch.numel(), pred.data_ptr(),
+                                  voted.data_ptr() if voted is not None else None, scores.data_ptr(),
+                                  hits.data_ptr() if hits is not None else None, decoder._stream()), name)
+    sc = scores.cpu().numpy()
+    hc = hits.cpu().numpy() if hits is not None else None
+    out = []
+    for g in range(n_maps):
+        d = {k: int(v) for k, v in zip(MAP_SCORE_KEYS, sc[g])}
+        if per_class:
+            d["per_class_voted_hits"] = hc[g, :ids.size].astype(np.int64)
+        out.append(d)
+    return (out, pred, voted) if return_pred else out
+
+
+def pick_channel_map(scores) -> int:
+    """The index of the best map of `score_channel_maps`: the most voted hits, then the most raw hits, then the lowest index.
+    The caller then calls `set_channel_map(maps[index], fills[index])`."""
+    if len(scores) == 0:
+        raise ValueError("no scores")
+    return max(range(len(scores)), key=lambda g: (scores[g]["voted_hits"], scores[g]["raw_hits"], -g))

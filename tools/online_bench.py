@@ -31,6 +31,11 @@ With --drive the grasp drive (GraspDrive.push, csrc/online_drive.cuh) is timed b
 itself in the same run: ungated, gated and driven pushes of 1 and 25 windows on OnlineDecoder and of 256 streams x 1 window on
 MultiStreamDecoder, plus the drive's launch alone (GraspDrive.apply on the windows and commands of one push).  A driven push
 must launch one kernel more than a gated one.
+With --map-sweep the electrode-map sweep (score_channel_maps, csrc/online_maps.cuh) is measured: (a) 16 and 64 maps over a
+recording of 41 classes x 500 windows in f32 and bf16 against the way without it, a decoder that is reset, given each map in
+turn and pushed the recording in 256-window pushes, its pred and voted copied to the host and counted there (both must give
+the same counts); (b) a mapped against an unmapped push of 1 and 25 windows on OnlineDecoder and of 256 streams x 1 window
+on MultiStreamDecoder, alternating in the same run, with the run-to-run spread of the unmapped medians next to the difference.
 Each push is timed from the host with a synchronisation behind it (the latency a control loop sees); kernels per push are
 counted with torch.profiler over a few pushes.  One JSON line per case, and a table with --out.
 
@@ -43,6 +48,7 @@ counted with torch.profiler over a few pushes.  One JSON line per case, and a ta
     python tools/online_bench.py --drive --iters 200 --out profiles/online_drive_latency.txt
     python tools/online_bench.py --gate-sweep --iters 20 --out profiles/online_gate_sweep.txt
     python tools/online_bench.py --subset-sweep --iters 20 --out profiles/online_subset_sweep.txt
+    python tools/online_bench.py --map-sweep --iters 5 --out profiles/online_map_sweep.txt
 """
 import argparse
 import json
@@ -100,6 +106,8 @@ def main():
     ap.add_argument("--drive", action="store_true", help="the grasp drive behind gate-wrapped decoders, next to the gate's own cost")
     ap.add_argument("--gate-sweep", action="store_true", help="sweep_gate against G CommandGate.apply calls in turn")
     ap.add_argument("--subset-sweep", action="store_true", help="sweep_subsets, and for 64 subsets a select + sweep_gate per subset")
+    ap.add_argument("--map-sweep", action="store_true", help="score_channel_maps against a reset / set_channel_map / push loop, and "
+                    "a mapped against an unmapped push")
     ap.add_argument("--case-seconds", type=float, default=150.0, help="--gate-sweep: time limit of each timed case")
     a = ap.parse_args()
     if a.enroll:
@@ -108,6 +116,8 @@ def main():
         return gate_sweep_main(a)
     if a.subset_sweep:
         return subset_sweep_main(a)
+    if a.map_sweep:
+        return map_sweep_main(a)
     torch.manual_seed(0)
     e = Engine(adabn=False, dtype="f32", device="cuda:0")
     e.init_parameters(1)
@@ -679,6 +689,111 @@ def subset_sweep_main(a):
             for r in rows:
                 tail = f"{r['composed_ms']:>12.1f} {r['composed_reps']:>5} {r['ratio']:>8.1f}" if "ratio" in r else f"{'-':>12} {'-':>5} {'-':>8}"
                 f.write(f"{r['windows']:>7} {r['subsets']:>7} {r['sweep_ms']:>9.3f} {r['sweep_reps']:>5} {tail}\n")
+
+
+def map_sweep_main(a):
+    from contrastiveprosthetics_amd.online import leave_one_out, recording_windows, rotations, score_channel_maps, window_labels
+    torch.manual_seed(0)
+    rng = np.random.default_rng(0)
+    classes = list(range(41))
+    pattern = rng.uniform(0.4, 3.0, (41, 12))
+    e = Engine(adabn=False, dtype="f32", device="cuda:0")
+    e.init_parameters(1)
+    raw, lab = _cue_recording(rng, pattern, np.ones(12), 500, classes)
+    ident = torch.stack([torch.zeros(12), torch.ones(12)]).cuda()
+    w0 = recording_windows(raw[:200000], ident)
+    mean, std = w0.mean(0), w0.std(0)
+    wl = window_labels(lab, 0)
+    scored = wl >= 0
+    cand = np.concatenate([rotations(reflect=True), leave_one_out()])
+    cand = np.concatenate([cand, cand[:, rotations()[1]], cand[:, rotations()[2]], cand[:, rotations()[3]]])[:64]   # 64 distinct-ish maps
+    lines = []
+
+    def out(r):
+        print(json.dumps(r), flush=True)
+        lines.append(r)
+
+    # ---- (a) the sweep against the push loop
+    for dtype in ("f32", "bf16"):
+        dec = OnlineDecoder(e, mean, std, classes=classes, dtype=dtype)
+        for G in (16, 64):
+            maps = cand[:G]
+            got = {}
+
+            def sweep():
+                got["sweep"] = [(s["rows"], s["raw_hits"], s["voted_hits"]) for s in score_channel_maps(dec, raw, lab, maps)]
+
+            def loop():
+                res = []
+                for g in range(G):
+                    dec.reset()
+                    dec.set_channel_map(maps[g])
+                    p, v = dec.push(raw)                          # split into pushes of 256 windows
+                    p, v = p.cpu().numpy(), v.cpu().numpy()
+                    res.append((int(scored.sum()), int((p == wl)[scored].sum()), int((v == wl)[scored].sum())))
+                dec.set_channel_map(None)
+                got["loop"] = res
+
+            t_sweep = _wall(sweep, a.iters, warmup=1)
+            t_loop = _wall(loop, max(1, a.iters // 2), warmup=1)
+            assert got["sweep"] == got["loop"], "the sweep and the push loop disagree"
+            out(dict(kind="map_sweep", dtype=dtype, maps=G, windows=int(wl.shape[0]), rows=G * int(wl.shape[0]),
+                     sweep_ms=round(t_sweep, 2), push_loop_ms=round(t_loop, 2), ratio=round(t_loop / t_sweep, 1)))
+    # ---- (b) a mapped against an unmapped push, alternating
+    perm = rotations()[3]
+    stream = (torch.randn(200000, 12) * 2e-3).cuda()
+    cases = []
+    for n in (20, 500):
+        plain = OnlineDecoder(e, mean, std, classes=classes, dtype="f32")
+        mapped = OnlineDecoder(e, mean, std, classes=classes, dtype="f32")
+        mapped.set_channel_map(perm)
+        cases.append((f"single {n // 20} windows", plain, mapped, lambda d, s, n=n: d.push(stream[s:s + n]), n))
+    S = 256
+    plain = MultiStreamDecoder(e, mean, std, S, dtype="f32")
+    mapped = MultiStreamDecoder(e, mean, std, S, dtype="f32")
+    for s_ in range(S):
+        plain.set_classes(s_, classes)
+        mapped.set_classes(s_, classes)
+        mapped.set_channel_map(s_, rotations()[s_ % 8] if s_ % 8 else perm)
+    counts = np.full(S, 20)
+    cases.append((f"{S} streams x 1 window", plain, mapped, lambda d, s: d.push_packed(stream[s:s + 20 * S], counts), 20 * S))
+    for name, plain, mapped, fn, n in cases:
+        pos = {id(plain): 0, id(mapped): 0}
+
+        def push(d):
+            s = pos[id(d)] % (stream.shape[0] - n)
+            pos[id(d)] += n
+            return fn(d, s)
+
+        meds = {"unmapped": [], "mapped": []}
+        for _ in range(5):                                       # alternate, so that a drift of the machine hits both
+            for key, d in (("unmapped", plain), ("mapped", mapped)):
+                meds[key].append(time_pushes(lambda: push(d), a.iters * 20, a.warmup)[0])
+        u, m = np.array(meds["unmapped"]), np.array(meds["mapped"])
+        out(dict(kind="mapped_push", case=name, unmapped_us=round(float(np.median(u)), 1), mapped_us=round(float(np.median(m)), 1),
+                 difference_us=round(float(np.median(m) - np.median(u)), 1), unmapped_spread_us=round(float(u.max() - u.min()), 1),
+                 mapped_spread_us=round(float(m.max() - m.min()), 1),
+                 kernels_unmapped=count_kernels(lambda: push(plain)), kernels_mapped=count_kernels(lambda: push(mapped))))
+    if a.out:
+        dev = torch.cuda.get_device_name(0)
+        with open(a.out, "w") as f:
+            f.write(f"# tools/online_bench.py --map-sweep --iters {a.iters} --warmup {a.warmup} on {dev}\n")
+            f.write("# (a) score_channel_maps against reset / set_channel_map / push (256-window pushes) / count per map, one decoder;\n")
+            f.write("#     wall time of the whole call, host-synchronised, median; both sides in the same run and with equal counts\n")
+            f.write(f"{'dtype':<5} {'maps':>5} {'windows':>8} {'rows':>9} {'sweep_ms':>10} {'push_loop_ms':>13} {'ratio':>7}\n")
+            for r in lines:
+                if r["kind"] == "map_sweep":
+                    f.write(f"{r['dtype']:<5} {r['maps']:>5} {r['windows']:>8} {r['rows']:>9} {r['sweep_ms']:>10.2f} "
+                            f"{r['push_loop_ms']:>13.2f} {r['ratio']:>7.1f}\n")
+            f.write("# (b) a mapped against an unmapped push, f32: 5 alternating rounds of host-synchronised medians; spread = max - min\n")
+            f.write("#     of the 5 medians of one side\n")
+            f.write(f"{'case':<24} {'unmapped_us':>12} {'mapped_us':>10} {'difference_us':>14} {'unmapped_spread_us':>19} "
+                    f"{'mapped_spread_us':>17} {'kernels':>12}\n")
+            for r in lines:
+                if r["kind"] == "mapped_push":
+                    f.write(f"{r['case']:<24} {r['unmapped_us']:>12.1f} {r['mapped_us']:>10.1f} {r['difference_us']:>14.1f} "
+                            f"{r['unmapped_spread_us']:>19.1f} {r['mapped_spread_us']:>17.1f} "
+                            f"{r['kernels_unmapped']:>5.1f} /{r['kernels_mapped']:>5.1f}\n")
 
 
 def streams_main(a, e, stream, mean, std, classes):
