@@ -142,6 +142,8 @@ SYMBOLS = {
     "cp_profile_summary": (C.c_int, [C.c_int32, _P(C.c_double), _P(C.c_int64)]),
     "cp_debug_activation": (C.c_int, [_P(cp_config), _P(cp_params), _fp, _fp, C.c_size_t, C.c_int32, _fp, _fp]),
     "cp_debug_bn_stats": (C.c_int, [_P(cp_config), _fp, C.c_size_t, C.c_int32, _fp, _fp]),
+    "cp_debug_head_grad": (C.c_int, [_P(cp_config), _fp, C.c_size_t, _fp, _fp]),
+    "cp_debug_glove_head_grad": (C.c_int, [_P(cp_config), _fp, C.c_size_t, C.c_int64, _fp, _fp]),
     "cp_debug_gemm": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "cp_online_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "cp_online_prepare": (C.c_int, [_P(cp_online_config), _P(cp_params), _P(cp_bn_buffers), C.c_float, _fp, C.c_size_t, _fp]),

@@ -228,9 +228,12 @@ static int head_impl(const cp_config* cfg, const cp_params* p, const float* z, c
                      float* logits, cp_params* grads, const float* gneg, void* stream) {
     WS w;
     if (int e = check_cfg(cfg, ws, ws_bytes, &w)) return e;
-    if (!p || !z || !labels || !loss_correct || !pred || V <= 0 || n_groups * CP_TASKS != cfg->n_windows)
-        return fail(CP_ERR_ARG, "cp_head args");
-    if (want_grad && (!grads || !grads->easy_w || !grads->easy_b)) return fail(CP_ERR_ARG, "cp_head grads");
+    // (n_groups % V: group g reads the z rows of batch entry g / V, V to a position -- a remainder would reach past n_windows)
+    if (!p || !z || !labels || !loss_correct || !pred || V <= 0 || n_groups * CP_TASKS != cfg->n_windows || n_groups % V != 0)
+        return fail(CP_ERR_ARG, gneg ? "cp_head_gneg args" : "cp_head args");
+    if (want_grad && (!grads || !grads->easy_w || !grads->easy_b)) return fail(CP_ERR_ARG, gneg ? "cp_head_gneg grads" : "cp_head grads");
+    if (((uintptr_t)z & 15) != 0)                                                                              // (head_kernel reads rows in 16-byte pieces)
+        return fail(CP_ERR_ARG, gneg ? "cp_head_gneg: z must be 16-byte aligned" : "cp_head: z must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     unsigned char* base = (unsigned char*)ws;
     const size_t es = cfg->dtype == CP_F32 ? 4 : 2;
@@ -264,6 +267,22 @@ static int head_impl(const cp_config* cfg, const cp_params* p, const float* z, c
                        want_grad, loss_correct, want_grad ? grads->easy_w : nullptr, want_grad ? grads->easy_b : nullptr);
     CKL("head_finalize_kernel");
     return 0;
+}
+
+// debug access: the dL/dz rows the last cp_head / cp_head_gneg / cp_head_glove call with want_grad left in ws, all 64 columns, as f32
+extern "C" int cp_debug_head_grad(const cp_config* cfg, void* ws, size_t ws_bytes, float* out, void* stream) {
+    WS w;
+    if (int e = check_cfg(cfg, ws, ws_bytes, &w)) return e;
+    if (!out) return fail(CP_ERR_ARG, "cp_debug_head_grad args");
+    const int64_t n = cfg->n_windows * HEAD_LD;
+    unsigned char* base = (unsigned char*)ws;
+    const hipStream_t st = (hipStream_t)stream;
+    return by_dtype(cfg->dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((to_f32_kernel<T>), dim3(1024), dim3(256), 0, st, (const T*)(base + w.dz), out, n);
+        CKL("to_f32_kernel");
+        return 0;
+    });
 }
 
 extern "C" int cp_vote(const int32_t* pred, const int64_t* labels, int64_t B, int32_t V, float* curve, int32_t* y_pred,
@@ -522,6 +541,22 @@ extern "C" int cp_head_glove(const cp_config* cfg, const float* z, const float* 
                        0, loss_correct, (float*)nullptr, (float*)nullptr);
     CKL("head_finalize_kernel");
     return 0;
+}
+
+// debug access: the dL/dzg rows the last cp_head_glove call with want_grad left in gws, all 64 columns, as f32
+extern "C" int cp_debug_glove_head_grad(const cp_config* cfg, void* gws, size_t gws_bytes, int64_t rows, float* out, void* stream) {
+    GWS w;
+    if (int e = check_glove(cfg, rows, gws, gws_bytes, &w)) return e;
+    if (!out) return fail(CP_ERR_ARG, "cp_debug_glove_head_grad args");
+    const int64_t n = rows * HEAD_LD;
+    unsigned char* base = (unsigned char*)gws;
+    const hipStream_t st = (hipStream_t)stream;
+    return by_dtype(cfg->dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((to_f32_kernel<T>), dim3(1024), dim3(256), 0, st, (const T*)(base + w.dzg), out, n);
+        CKL("to_f32_kernel");
+        return 0;
+    });
 }
 
 template <typename T>

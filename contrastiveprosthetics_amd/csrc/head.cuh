@@ -60,6 +60,13 @@ struct HeadArgs {
 __device__ __forceinline__ f32x4 head_mfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ float head_qsum(float v) { v += __shfl_xor(v, 16, 64); return v + __shfl_xor(v, 32, 64); }
 __device__ __forceinline__ float head_qmax(float v) { v = fmaxf(v, __shfl_xor(v, 16, 64)); return fmaxf(v, __shfl_xor(v, 32, 64)); }
+// sum over the 16 lanes c of one q (a DPP row), in every lane: two quad permutes, row_half_mirror, row_mirror
+__device__ __forceinline__ float head_row16_sum(float v) {
+    v += dpp_quad<0xB1>(v);
+    v += dpp_quad<0x4E>(v);
+    v += dpp_quad<0x141>(v);
+    return v + dpp_quad<0x140>(v);
+}
 __device__ __forceinline__ float head_exp2(float x) { return __builtin_amdgcn_exp2f(x); }      // v_exp_f32 (arguments <= 0 here, or tiny)
 __device__ __forceinline__ float head_log2(float x) { return __builtin_amdgcn_logf(x); }       // v_log_f32 (arguments in [1, 48])
 
@@ -336,15 +343,26 @@ __global__ __launch_bounds__(256, 2) void head_kernel(HeadArgs a) {
 #pragma unroll
                 for (int ti = 0; ti < 3; ++ti) {
                     const float dl = (tj == 2 && !jok) ? 0.f : dlt[ti][r];      // (columns 41..47 of the tile hold the padded columns' dl)
-                    dotz[ti] = fmaf(dl, Lt[tj][ti][r], dotz[ti]);
+                    if constexpr (!F8L) dotz[ti] = fmaf(dl, Lt[tj][ti][r], dotz[ti]);
                     dzh[ti] = head_mfma(dl, eB, dzh[ti]);
                 }
             }
         }
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
-            const float dz = head_qsum(dotz[t]) * HEAD_LN2;
-            if (q == 0) Dz[wave][16 * t + c] = dz;
+            if constexpr (F8L) {
+                // the 8-bit logits are not the products of the f32 unit vectors that dz_hat is made of (straight-through), so
+                // sum_j dl l is not z_hat_i . dz_hat_i here: it would leave dz a component along z, 3-9 % of a row's largest entry
+                // (tests/test_gpu_head.py, the fp8 cases).  The product itself: row i = 16t + 4q + r of dzh, dims c on 16 lanes
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float dz = head_row16_sum(dzh[t][r] * Zs[wave][16 * t + 4 * q + r][c]);
+                    if (c == 0) Dz[wave][16 * t + 4 * q + r] = dz;
+                }
+            } else {
+                const float dz = head_qsum(dotz[t]) * HEAD_LN2;
+                if (q == 0) Dz[wave][16 * t + c] = dz;
+            }
             if constexpr (GLOVE) {
                 const float de = head_qsum(dote[t]) * HEAD_LN2;
                 if (q == 0) De[wave][16 * t + c] = de;

@@ -320,6 +320,11 @@ class Engine:
             self._ws_windows = n_windows
         return self._ws
 
+    def _training(self) -> bool:
+        # mode of the last encoder_forward; the head does not depend on it, so a head called on its own (no forward yet) is an evaluation
+        last = getattr(self, "_last", None)
+        return bool(last[1]) if last is not None else False
+
     def _ws_args(self, cfg: _lib.cp_config):
         # the carve depends on n_windows, so a call always passes the size for ITS n_windows; the record goes with the buffer
         ws = self.workspace(cfg.n_windows)
@@ -373,7 +378,8 @@ class Engine:
         n = z.shape[0]
         G = n // CP_TASKS
         assert labels.dtype == torch.int64 and labels.numel() * V == n
-        cfg = self._cfg(n, self._last[1])
+        cfg = self._cfg(n, self._training())
+        self._last_head = n
         out = torch.empty(2, dtype=torch.float32, device=self.device)
         pred = torch.empty(G, CP_TASKS, dtype=torch.int32, device=self.device)
         logits = torch.empty(G, CP_TASKS, CP_TASKS, dtype=torch.float32, device=self.device) if want_logits else None
@@ -477,7 +483,8 @@ class Engine:
         n = z.shape[0]
         G = n // CP_TASKS
         assert labels.dtype == torch.int64 and labels.numel() * V == n and zg.shape[0] * V == n
-        cfg = self._cfg(n, self._last[1])
+        cfg = self._cfg(n, self._training())
+        self._last_head, self._last_head_glove_rows = n, zg.shape[0]
         out = torch.empty(2, dtype=torch.float32, device=self.device)
         pred = torch.empty(G, CP_TASKS, dtype=torch.int32, device=self.device)
         logits = torch.empty(G, CP_TASKS, CP_TASKS, dtype=torch.float32, device=self.device) if want_logits else None
@@ -571,6 +578,26 @@ class Engine:
         ws, nb = self._ws_args(cfg)
         _lib.check(self.lib.cp_debug_bn_stats(C.byref(cfg), ws, nb, layer, out.data_ptr(), self._stream()),
                    "cp_debug_bn_stats")
+        return out
+
+    def debug_head_grad(self) -> torch.Tensor:
+        """dL/dz as the last head() / head_glove() call with want_grad left it in the workspace: (n_windows, 64) f32, window order
+        as z, columns 16..63 the zeros the projection's backward kernels contract over."""
+        n = self._last_head
+        out = torch.empty(n, 64, dtype=torch.float32, device=self.device)
+        cfg = self._cfg(n, self._training())
+        ws, nb = self._ws_args(cfg)
+        _lib.check(self.lib.cp_debug_head_grad(C.byref(cfg), ws, nb, out.data_ptr(), self._stream()), "cp_debug_head_grad")
+        return out
+
+    def debug_glove_head_grad(self) -> torch.Tensor:
+        """dL/dzg as the last head_glove() call with want_grad left it in the glove workspace: (rows, 64) f32."""
+        rows = self._last_head_glove_rows
+        out = torch.empty(rows, 64, dtype=torch.float32, device=self.device)
+        cfg = self._cfg(self._last_head, self._training())
+        gws, nb = self._gws_args(rows)
+        _lib.check(self.lib.cp_debug_glove_head_grad(C.byref(cfg), gws, nb, rows, out.data_ptr(), self._stream()),
+                   "cp_debug_glove_head_grad")
         return out
 
     def fp8_scale_exponents(self) -> torch.Tensor:

@@ -218,7 +218,10 @@ int cp_encoder_forward(const cp_config* cfg, const cp_params* p, const cp_bn_buf
  * labels (B*41) int64; n_groups = B*V; loss_correct[0] = loss, [1] = number of rows whose
  * argmax equals its label; pred (n_groups,41) int32; logits optional (n_groups,41,41) f32.
  * want_grad: also writes dL/dz into ws (consumed by cp_encoder_backward) and the class-encoder
- * gradients grads->easy_w / easy_b. */
+ * gradients grads->easy_w / easy_b.
+ * Position j of group g carries the class embedding of labels[(g / V)*41 + j]; the targets of both loss directions and
+ * of loss_correct[1] are labels[0..40] for every group (code/models.py:147), which need not be a permutation.
+ * n_groups must be a multiple of V and z 16-byte aligned (CP_ERR_ARG otherwise, as in cp_head_gneg). */
 int cp_head(const cp_config* cfg, const cp_params* p, const float* z, const int64_t* labels,
             int64_t n_groups, int32_t V, int32_t want_grad, void* ws, size_t ws_bytes,
             float* loss_correct, int32_t* pred, float* logits, cp_params* grads, void* stream);
@@ -233,7 +236,9 @@ int cp_head(const cp_config* cfg, const cp_params* p, const float* z, const int6
  * gh_out: 128 device floats {G[64], H[64]} (41 used each; H[k] = sum over all groups of 1/(exp(pos) + G[k]) carries the
  * gradient into the negatives).  scratch: cp_global_negatives_scratch_floats(n_all_windows) device floats.
  * cp_head_gneg = cp_head with that table: row direction unchanged, column direction as above; gradients are those of
- * this rank's windows (the data-parallel gradient sum adds the ranks' parts).  One-hot class table, training batches. */
+ * this rank's windows (the data-parallel gradient sum adds the ranks' parts).  One-hot class table, training batches.
+ * The extension is defined for the identity layout, labels[t] = t: under another layout the table's kernels and the head
+ * mean different rows by a column's "positive". */
 size_t cp_global_negatives_scratch_floats(int64_t n_all_windows);
 int cp_global_negatives(const cp_params* p, const float* z_all, int64_t n_all_windows, const int64_t* labels,
                         float* scratch, float* gh_out, void* stream);
@@ -414,6 +419,14 @@ int cp_debug_gemm(int32_t dtype, int32_t kind, int64_t M, int32_t K, int32_t F, 
 /* BN statistics of `layer` as computed by the last forward: out[4][C] = mean, invstd, scale, shift */
 int cp_debug_bn_stats(const cp_config* cfg, void* ws, size_t ws_bytes, int32_t layer, float* out,
                       void* stream);
+
+/* debug/test access to the head's data gradients.  cp_debug_head_grad: the n_windows x 64 rows of dL/dz that the last
+ * cp_head / cp_head_gneg / cp_head_glove call with want_grad left in ws (window order as z; columns 0..15 live, 16..63 the zeros
+ * the projection's backward kernels contract over), widened to f32 into out (n_windows*64 floats).  cp_debug_glove_head_grad:
+ * the rows x 64 rows of dL/dzg that cp_head_glove left in gws, likewise.  cfg / ws / gws as for those calls; a NULL out is
+ * CP_ERR_ARG, a short workspace CP_ERR_WORKSPACE.  One conversion launch each; nothing in the workspace changes. */
+int cp_debug_head_grad(const cp_config* cfg, void* ws, size_t ws_bytes, float* out, void* stream);
+int cp_debug_glove_head_grad(const cp_config* cfg, void* gws, size_t gws_bytes, int64_t rows, float* out, void* stream);
 
 /* ---- online grasp decoding (README.md:11-19 of the reference: a prosthetic hand reads a live sEMG stream) ----------------
  * Consecutive chunks of raw 2 kHz, 12-channel sEMG -> for every 10 ms window a chunk completes, the predicted class and the

@@ -136,6 +136,66 @@ def test_glove_entries_refuse_misaligned_pointers_before_they_launch(lib):
             assert entry.encode() in msg and (b" " + arg.encode() + b" must be 16-byte aligned") in msg, (entry, arg, msg)
 
 
+def test_onehot_heads_refuse_ragged_views_and_misaligned_z_before_they_launch(lib):
+    """cp_head and cp_head_gneg run the kernel that cp_head_glove runs: group g reads the z rows of batch entry g / V in 16-byte
+    pieces.  An n_groups that is no multiple of V (the last batch entry's rows would lie past n_windows) and a z that is 4, 8 or 12
+    bytes off are refused with CP_ERR_ARG and a message that names the entry, before any launch (every pointer is a dummy address
+    that is never dereferenced; sizes and the workspace are valid, so the check under test is what refuses)"""
+    from contrastiveprosthetics_amd import _lib
+    ok, ws = 0x100000, 0x40000000
+    pp = _lib.cp_params()
+    pp.easy_w = pp.easy_b = ok
+    for dtype in (0, 1, 2):                                       # CP_F32, CP_BF16, CP_FP8
+        for groups, V in ((3, 2), (25, 3), (26, 25)):
+            cfg = _lib.cp_config()
+            cfg.n_windows, cfg.dtype = 41 * groups, dtype
+            nb = lib.cp_workspace_bytes(cfg.n_windows, dtype, 0.0)
+
+            def head(z, v, want_grad=0):
+                return lib.cp_head(ctypes.byref(cfg), ctypes.byref(pp), z, ok, groups, v, want_grad, ws, nb, ok, ok, None,
+                                   ctypes.byref(pp), None)
+
+            def gneg(z, v, want_grad=0):
+                return lib.cp_head_gneg(ctypes.byref(cfg), ctypes.byref(pp), z, ok, groups, v, want_grad, ws, nb, ok, ok, None,
+                                        ctypes.byref(pp), ok, None)
+
+            for want_grad in (0, 1):
+                rc = head(ok, V, want_grad)
+                assert rc == 10001 and b"cp_head args" in lib.cp_last_error(), (dtype, groups, V, rc, lib.cp_last_error())
+                rc = gneg(ok, V, want_grad)                       # (the extension takes training batches, V == 1: no ragged view exists)
+                assert rc == 10001 and b"cp_head_gneg" in lib.cp_last_error(), (dtype, groups, V, rc, lib.cp_last_error())
+            for entry, call in (("cp_head", head), ("cp_head_gneg", gneg)):
+                for off in (4, 8, 12):
+                    rc = call(ok + off, 1)
+                    msg = lib.cp_last_error()
+                    assert rc == 10001, (entry, dtype, off, rc, msg)
+                    assert entry.encode() + b": z must be 16-byte aligned" in msg, (entry, msg)
+
+
+def test_head_grad_readback_refuses_null_out_and_short_workspaces_before_it_launches(lib):
+    """cp_debug_head_grad / cp_debug_glove_head_grad validate as the calls whose rows they read: a NULL `out` is CP_ERR_ARG with the
+    entry's name, a workspace one byte short CP_ERR_WORKSPACE (10002), a row count that is no multiple of 41 CP_ERR_ARG -- all
+    before the conversion launch (dummy addresses, no GPU here)"""
+    from contrastiveprosthetics_amd import _lib
+    ok, ws, gws = 0x100000, 0x40000000, 0x200000
+    for dtype in (0, 1, 2):
+        rows = 41 * 5
+        cfg = _lib.cp_config()
+        cfg.n_windows, cfg.dtype = rows, dtype
+        nb, gnb = lib.cp_workspace_bytes(rows, dtype, 0.0), lib.cp_glove_workspace_bytes(rows, dtype)
+        rc = lib.cp_debug_head_grad(ctypes.byref(cfg), ws, nb, None, None)
+        assert rc == 10001 and b"cp_debug_head_grad" in lib.cp_last_error(), (dtype, rc, lib.cp_last_error())
+        rc = lib.cp_debug_glove_head_grad(ctypes.byref(cfg), gws, gnb, rows, None, None)
+        assert rc == 10001 and b"cp_debug_glove_head_grad" in lib.cp_last_error(), (dtype, rc, lib.cp_last_error())
+        rc = lib.cp_debug_head_grad(ctypes.byref(cfg), ws, nb - 1, ok, None)
+        assert rc == 10002 and b"workspace too small" in lib.cp_last_error(), (dtype, rc, lib.cp_last_error())
+        rc = lib.cp_debug_glove_head_grad(ctypes.byref(cfg), gws, gnb - 1, rows, ok, None)
+        assert rc == 10002 and b"glove workspace too small" in lib.cp_last_error(), (dtype, rc, lib.cp_last_error())
+        assert lib.cp_debug_head_grad(ctypes.byref(cfg), None, nb, ok, None) == 10001
+        assert lib.cp_debug_glove_head_grad(ctypes.byref(cfg), gws, gnb, rows + 1, ok, None) == 10001
+        assert lib.cp_debug_glove_head_grad(ctypes.byref(cfg), None, gnb, rows, ok, None) == 10001
+
+
 def test_backward_refuses_a_short_gradient_tap_before_it_launches(lib):
     """cp_config.grad_tap: cp_encoder_backward checks the whole buffer once, before its first launch -- 9 slots of n_windows x 768
     elements on the large-batch paths (CP_FP8: bf16 elements), 11 on the small-batch path (slot 9: fc1's data gradient before conv2's
