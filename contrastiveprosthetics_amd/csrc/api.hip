@@ -654,20 +654,40 @@ extern "C" int cp_glove_backward(const cp_config* cfg, const cp_glove_params* gp
 // ---------------------------------------------------------------------------------------
 // optimiser
 // ---------------------------------------------------------------------------------------
-static int build_opt(OptArgs* a, const int64_t* off, const int64_t* numel, const int32_t* group, const int32_t* l2, int n) {
-    if (n <= 0 || n > CP_MAX_TENSORS || !off || !numel || !group || !l2) return fail(CP_ERR_ARG, "tensor table");
-    int chunk = 0;
+// the table as the kernels take it.  Refused here, before any launch: a negative numel (a negative chunk count, and a grid that no
+// longer matches the table) and a negative offset (an index in front of the buffers)
+static int build_opt(const char* who, OptArgs* a, const int64_t* off, const int64_t* numel, const int32_t* group, const int32_t* l2, int n) {
+    char msg[160];
+    if (n <= 0 || n > CP_MAX_TENSORS || !off || !numel || !group || !l2) {
+        snprintf(msg, sizeof(msg), "%s: tensor table (n = %d, 1..%d entries)", who, n, CP_MAX_TENSORS);
+        return fail(CP_ERR_ARG, msg);
+    }
+    int64_t chunk = 0;
     for (int i = 0; i < n; ++i) {
+        if (off[i] < 0 || numel[i] < 0) {
+            snprintf(msg, sizeof(msg), "%s: tensor table entry %d has a negative %s (%lld)", who, i, off[i] < 0 ? "offset" : "numel",
+                     (long long)(off[i] < 0 ? off[i] : numel[i]));
+            return fail(CP_ERR_ARG, msg);
+        }
+        const int64_t nchunks = numel[i] / OPT_CHUNK + (numel[i] % OPT_CHUNK != 0);
+        if (chunk + nchunks > INT32_MAX) {
+            snprintf(msg, sizeof(msg), "%s: tensor table entry %d takes the table past 2^31 chunks", who, i);
+            return fail(CP_ERR_ARG, msg);
+        }
         a->t[i].offset = off[i];
         a->t[i].numel = numel[i];
-        a->t[i].chunk0 = chunk;
-        a->t[i].nchunks = (int)((numel[i] + OPT_CHUNK - 1) / OPT_CHUNK);
+        a->t[i].chunk0 = (int)chunk;
+        a->t[i].nchunks = (int)nchunks;
         a->t[i].group = group[i] ? 1 : 0;
         a->t[i].l2 = l2[i] ? 1 : 0;
-        chunk += a->t[i].nchunks;
+        chunk += nchunks;
+    }
+    if (chunk == 0) {                                    // (an empty grid is no launch)
+        snprintf(msg, sizeof(msg), "%s: tensor table without an element", who);
+        return fail(CP_ERR_ARG, msg);
     }
     a->n_tensors = n;
-    a->total_chunks = chunk;
+    a->total_chunks = (int)chunk;
     return 0;
 }
 
@@ -692,7 +712,7 @@ extern "C" int cp_l2_norms(const float* params_flat, const int64_t* offset_host,
                            float* scratch, float* l2_out, void* stream) {
     if (!params_flat || !h || !scratch || !l2_out) return fail(CP_ERR_ARG, "cp_l2_norms args");
     OptArgs a{};
-    if (int e = build_opt(&a, offset_host, numel_host, group_host, l2_host, n)) return e;
+    if (int e = build_opt("cp_l2_norms", &a, offset_host, numel_host, group_host, l2_host, n)) return e;
     a.p = const_cast<float*>(params_flat);
     a.reg[0] = h->reg_emg; a.reg[1] = h->reg_glove;
     return launch_norms(a, scratch, l2_out, (hipStream_t)stream);
@@ -705,7 +725,7 @@ extern "C" int cp_l2_adam_step(float* params_flat, const float* grads_flat, floa
     if (!params_flat || !grads_flat || !exp_avg || !exp_avg_sq || !h || !scratch || !l2_out || step_index < 1)
         return fail(CP_ERR_ARG, "cp_l2_adam_step args");
     OptArgs a{};
-    if (int e = build_opt(&a, offset_host, numel_host, group_host, l2_host, n)) return e;
+    if (int e = build_opt("cp_l2_adam_step", &a, offset_host, numel_host, group_host, l2_host, n)) return e;
     a.p = params_flat; a.g = grads_flat; a.m = exp_avg; a.v = exp_avg_sq;
     a.lr[0] = h->lr_emg; a.lr[1] = h->lr_glove; a.reg[0] = h->reg_emg; a.reg[1] = h->reg_glove;
     a.beta1 = h->beta1; a.beta2 = h->beta2; a.eps = h->eps; a.grad_scale = h->grad_scale;
@@ -726,7 +746,7 @@ extern "C" int cp_l2_adam_step_graph(float* params_flat, const float* grads_flat
     if (!params_flat || !grads_flat || !exp_avg || !exp_avg_sq || !h || !scratch || !l2_out || !state_dev)
         return fail(CP_ERR_ARG, "cp_l2_adam_step_graph args");
     OptArgs a{};
-    if (int e = build_opt(&a, offset_host, numel_host, group_host, l2_host, n)) return e;
+    if (int e = build_opt("cp_l2_adam_step_graph", &a, offset_host, numel_host, group_host, l2_host, n)) return e;
     a.p = params_flat; a.g = grads_flat; a.m = exp_avg; a.v = exp_avg_sq;
     a.lr[0] = h->lr_emg; a.lr[1] = h->lr_glove; a.reg[0] = h->reg_emg; a.reg[1] = h->reg_glove;
     a.beta1 = h->beta1; a.beta2 = h->beta2; a.eps = h->eps; a.grad_scale = h->grad_scale;

@@ -150,18 +150,23 @@ __global__ __launch_bounds__(256) void adam_kernel(OptArgs a) {
         norm = a.norms[ti];
     }
     const float lr = a.state ? a.state[3 + t.group] : a.lr[t.group];
-    const float l2c = t.l2 ? a.reg[t.group] / norm : 0.f;
+    // a member whose norm is 0 takes no regulariser gradient (torch.norm's gradient at the zero tensor is 0): reg / 0 is inf, or NaN
+    // at reg = 0, and its product with p = 0 would leave NaN in the parameter and both moments for good
+    const float l2c = (t.l2 && norm > 0.f) ? a.reg[t.group] / norm : 0.f;
     const float step = lr / (a.state ? a.state[1] : a.bc1);
     const float rs2 = 1.0f / sqrtf(a.state ? a.state[2] : a.bc2);
+    // every fused multiply-add is written out: left to the compiler's contraction the two branches below were given different ones
+    // (the vector branch fmaf(beta, m, (1 - beta) g), the scalar branch fmaf(1 - beta1, g, beta1 m) and an unfused second moment), and a
+    // tensor's numbers depended on its alignment.  This is the vector branch's form, the one every tensor of the model takes.
     auto upd = [&](float p, float gr, float& m, float& v) -> float {
         float g = gr * a.grad_scale;
         if (t.l2) g = fmaf(l2c, p, g);
-        m = a.beta1 * m + (1.f - a.beta1) * g;
-        v = a.beta2 * v + (1.f - a.beta2) * g * g;
-        return p - step * (m / (sqrtf(v) * rs2 + a.eps));
+        m = fmaf(a.beta1, m, (1.f - a.beta1) * g);
+        v = fmaf(a.beta2, v, ((1.f - a.beta2) * g) * g);
+        return fmaf(-step, m / fmaf(sqrtf(v), rs2, a.eps), p);
     };
     if (((t.offset | t.numel) & 3) == 0 && ((((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)a.m | (uintptr_t)a.v)) & 15) == 0) {
-        // four elements per thread and load (element-wise: the same numbers as the scalar form)
+        // four elements per thread and load (element-wise: the same numbers as the scalar form -- upd above; tests/test_gpu_optim.py)
         for (int i = threadIdx.x * 4; i < OPT_CHUNK; i += 1024) {
             const int64_t e = base + i;
             if (e >= t.numel) break;

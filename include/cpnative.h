@@ -355,7 +355,18 @@ int cp_glove_backward(const cp_config* cfg, const cp_glove_params* gp, int64_t r
  * 1 glove_net), l2 (1 if the tensor's name contains neither 'bn' nor 'bias').
  * step_index: 1-based Adam step.  grad_scale multiplies the data gradient (1/world_size after an
  * all-reduce sum).  l2_out: device scalar receiving the regulariser value.  scratch: device floats,
- * at least cp_optimizer_scratch_floats(...) long. */
+ * at least cp_optimizer_scratch_floats(...) long.
+ * Per element, with n = |p| the Frobenius norm of the element's tensor:
+ *     g' = grad_scale * g + reg * p / n        (members of the regulariser; the second term is 0 where n = 0)
+ *     m  = beta1 * m + (1 - beta1) * g',   v = beta2 * v + (1 - beta2) * g'^2
+ *     p  = p - lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ * A member whose norm is 0 (a zero-initialised or pruned tensor) takes no regulariser gradient -- torch.norm's gradient at the
+ * zero tensor is 0 -- and follows its data gradient; it adds 0 to the regulariser value.
+ * Any table of 1..64 entries that do not overlap is taken, entries of no element included; the flat buffers need no alignment
+ * (a tensor whose offset and numel are multiples of 4 is read in 16-byte pieces where the four base pointers are 16-byte
+ * aligned, every other tensor element by element: the same numbers either way).  Nothing outside the table's elements is written.
+ * Refused with CP_ERR_ARG and a cp_last_error that names the entry, before any launch: n outside 1..64, a negative offset or
+ * numel, a table without an element, a NULL pointer, step_index < 1. */
 typedef struct cp_adam_hyper {
     float lr_emg, lr_glove, reg_emg, reg_glove;
     float beta1, beta2, eps, grad_scale;

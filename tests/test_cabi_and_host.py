@@ -223,6 +223,55 @@ def test_backward_refuses_a_short_gradient_tap_before_it_launches(lib):
             assert rec.backwards == 0
 
 
+def test_optimiser_entries_refuse_bad_tables_before_they_launch(lib):
+    """cp_l2_norms, cp_l2_adam_step and cp_l2_adam_step_graph take any tensor table of 1..64 entries; what the kernels cannot
+    index is refused with CP_ERR_ARG and a message that names the entry, before any launch: no entry or 65, a negative numel
+    (a negative chunk count: the grid would no longer match the table), a negative offset (an index in front of the buffers), a
+    table without an element (an empty grid), and a step index of 0 (every pointer is a dummy address that is never
+    dereferenced: there is no GPU here, so a launch would fail with another code)"""
+    from contrastiveprosthetics_amd import _lib
+    ok = 0x100000
+    h = _lib.cp_adam_hyper(1e-3, 3e-2, 1e-3, 2e-2, 0.9, 0.999, 1e-8, 1.0)
+
+    def arrays(off, numel):
+        n = len(off)
+        return ((ctypes.c_int64 * n)(*off), (ctypes.c_int64 * n)(*numel), (ctypes.c_int32 * n)(*([0, 1] * n)[:n]),
+                (ctypes.c_int32 * n)(*([1, 0] * n)[:n]))
+
+    def norms(tab, n, step=1):
+        return lib.cp_l2_norms(ok, *tab, n, ctypes.byref(h), ok, ok, None)
+
+    def plain(tab, n, step=1):
+        return lib.cp_l2_adam_step(ok, ok, ok, ok, *tab, n, ctypes.byref(h), step, ok, ok, None)
+
+    def graph(tab, n, step=1):
+        return lib.cp_l2_adam_step_graph(ok, ok, ok, ok, *tab, n, ctypes.byref(h), ok, ok, ok, None)
+
+    good = arrays([0, 64, 4160], [5, 4096, 1])
+    many = arrays([64 * i for i in range(65)], [7] * 65)
+    for entry, call in (("cp_l2_norms", norms), ("cp_l2_adam_step", plain), ("cp_l2_adam_step_graph", graph)):
+        for what, tab, n, says in (("n = 0", good, 0, b"n = 0"),
+                                   ("n = -1", good, -1, b"n = -1"),
+                                   ("n = 65", many, 65, b"n = 65"),
+                                   ("numel[1] = -1", arrays([0, 64, 4160], [5, -1, 1]), 3, b"entry 1 has a negative numel"),
+                                   ("numel[2] = -4096", arrays([0, 64, 4160], [5, 4096, -4096]), 3, b"entry 2 has a negative numel"),
+                                   ("offset[0] = -1", arrays([-1, 64, 4160], [5, 4096, 1]), 3, b"entry 0 has a negative offset"),
+                                   ("offset[2] = -4", arrays([0, 64, -4], [5, 4096, 1]), 3, b"entry 2 has a negative offset"),
+                                   ("no element", arrays([0, 64], [0, 0]), 2, b"without an element")):
+            rc = call(tab, n)
+            msg = lib.cp_last_error()
+            assert rc == 10001, (entry, what, rc, msg)
+            assert msg.startswith(entry.encode() + b":") and says in msg, (entry, what, msg)
+        rc = lib.cp_l2_adam_step(ok, ok, ok, ok, None, good[1], good[2], good[3], 3, ctypes.byref(h), 1, ok, ok, None)
+        assert rc == 10001 and b"cp_l2_adam_step: tensor table" in lib.cp_last_error()
+    for step in (0, -1):
+        rc = plain(good, 3, step=step)
+        assert rc == 10001 and b"cp_l2_adam_step args" in lib.cp_last_error(), (step, rc, lib.cp_last_error())
+    # (the graph form takes its step from the device state, the norms take none: a missing state is what they refuse)
+    rc = lib.cp_l2_adam_step_graph(ok, ok, ok, ok, *good, 3, ctypes.byref(h), None, ok, ok, None)
+    assert rc == 10001 and b"cp_l2_adam_step_graph args" in lib.cp_last_error()
+
+
 def test_missing_library_is_an_error(monkeypatch):
     from contrastiveprosthetics_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)
