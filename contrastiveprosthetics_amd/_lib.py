@@ -88,6 +88,20 @@ class cp_online_drive_config(C.Structure):
                 ("bad_after", C.c_int32), ("good_after", C.c_int32)]
 
 
+class cp_augment(C.Structure):
+    """Settings of one cp_gather_groups_aug launch (include/cpnative.h)."""
+    _fields_ = [("seed", C.c_uint32), ("salt", C.c_uint32), ("salt_state_lo", C.c_uint32), ("salt_state_hi", C.c_uint32),
+                ("shift_min", C.c_int32), ("shift_max", C.c_int32), ("dead_mask", C.c_uint32),
+                ("p_drop", C.c_float), ("gain_sigma", C.c_float), ("amp_sigma", C.c_float), ("noise_sigma", C.c_float),
+                ("fill", C.c_float), ("mean_std", C.c_void_p), ("item_offset", C.c_int64)]
+
+
+class cp_step_state(C.Structure):
+    """The 32 device bytes a captured step reads its per-step values from (include/cpnative.h)."""
+    _fields_ = [("dp_salt", C.c_uint32), ("bc1", C.c_float), ("bc2", C.c_float), ("lr_emg", C.c_float), ("lr_glove", C.c_float),
+                ("aug_salt", C.c_uint32), ("pad", C.c_float * 2)]
+
+
 CP_ONLINE_MAX_CLASSES, CP_ONLINE_MAX_VOTE, CP_ONLINE_MAX_WINDOWS, CP_ONLINE_STRIDE = 64, 256, 256, 20
 CP_ONLINE_MULTI_MAX_STREAMS, CP_ONLINE_MULTI_MAX_ROWS = 256, 65536
 CP_ONLINE_GATE_SCORES, CP_ONLINE_GATE_SWEEP_MAX_CONFIGS = 10, 65536
@@ -105,6 +119,7 @@ SYMBOLS = {
     "cp_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_float]),
     "cp_gather_groups": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, C.c_int32, _fp, _fp]),
     "cp_gather_oob_count": (C.c_int, [_fp, C.c_int32, _fp]),
+    "cp_gather_groups_aug": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, C.c_int32, _fp, _P(cp_augment), _fp]),
     "cp_encoder_forward": (C.c_int, [_P(cp_config), _P(cp_params), _P(cp_bn_buffers), _fp, _fp, C.c_size_t, _fp, _fp]),
     "cp_head": (C.c_int, [_P(cp_config), _P(cp_params), _fp, _fp, C.c_int64, C.c_int32, C.c_int32, _fp, C.c_size_t,
                           _fp, _fp, _fp, _P(cp_params), _fp]),

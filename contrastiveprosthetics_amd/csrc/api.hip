@@ -153,6 +153,47 @@ extern "C" int cp_gather_groups(const float* table, int64_t table_rows, const in
     return 0;
 }
 
+// sEMG augmentation in the gather's launch (an opt-in EXTENSION, no reference counterpart: include/cpnative.h, cp_augment).
+// Everything is validated here, on the host, before the launch; nothing is allocated, synchronised or read.
+extern "C" int cp_gather_groups_aug(const float* table, int64_t table_rows, const int64_t* emg_rand, int64_t D,
+                                    const int64_t* perm, int64_t B, int32_t V, float* x_out, const cp_augment* aug, void* stream) {
+    if (!table || !emg_rand || !perm || !x_out || B <= 0 || V <= 0) return fail(CP_ERR_ARG, "cp_gather_groups_aug args");
+    if (!aug) return fail(CP_ERR_ARG, "cp_gather_groups_aug: aug is NULL");
+    if ((((uintptr_t)table | (uintptr_t)x_out) & 15) != 0)                     // (rows are read and stored in 16-byte pieces)
+        return fail(CP_ERR_ARG, "cp_gather_groups_aug: table and x_out must be 16-byte aligned");
+    if (aug->shift_min < -7 || aug->shift_max > 7 || aug->shift_min > aug->shift_max)
+        return fail(CP_ERR_ARG, "cp_gather_groups_aug: shift bounds must satisfy -7 <= shift_min <= shift_max <= 7");
+    if (!(aug->p_drop >= 0.f && aug->p_drop <= 1.f)) return fail(CP_ERR_ARG, "cp_gather_groups_aug: p_drop outside [0, 1]");
+    const float sig[3] = {aug->gain_sigma, aug->amp_sigma, aug->noise_sigma};
+    for (int i = 0; i < 3; ++i)
+        if (!(sig[i] >= 0.f && sig[i] <= 2.f))            // (a NaN fails both comparisons)
+            return fail(CP_ERR_ARG, "cp_gather_groups_aug: gain_sigma, amp_sigma and noise_sigma must be finite and in [0, 2]");
+    if (!std::isfinite(aug->fill)) return fail(CP_ERR_ARG, "cp_gather_groups_aug: fill must be finite");
+    if (aug->dead_mask > 0xFFFu) return fail(CP_ERR_ARG, "cp_gather_groups_aug: dead_mask has bits above channel 11");
+    const int64_t item_limit = (int64_t)1 << 32;
+    if (aug->item_offset < 0 || aug->item_offset > item_limit || B > (item_limit - aug->item_offset) / CP_TASKS)
+        return fail(CP_ERR_ARG, "cp_gather_groups_aug: item_offset + B * 41 must not exceed 2^32");
+    GatherAugArgs a{};
+    a.table = table; a.emg_rand = emg_rand; a.perm = perm; a.out = x_out; a.mean_std = aug->mean_std;
+    a.salt_state = nullptr;
+    if (aug->salt_state_lo || aug->salt_state_hi) {
+        const uintptr_t st = ((uintptr_t)aug->salt_state_hi << 32) | aug->salt_state_lo;
+        a.salt_state = &((const cp_step_state*)st)->aug_salt;
+    }
+    a.B = B; a.D = D; a.table_rows = table_rows; a.T = CP_TASKS; a.V = (int)V;
+    a.seed = aug->seed; a.salt = aug->salt; a.item_offset = (uint32_t)aug->item_offset;
+    a.drop_thresh = (uint32_t)floor((double)aug->p_drop * 65536.0 + 0.5);
+    a.dead_mask = aug->dead_mask;
+    a.shift_min = aug->shift_min; a.shift_span = aug->shift_max - aug->shift_min + 1;
+    a.gain_sigma = aug->gain_sigma; a.amp_sigma = aug->amp_sigma; a.noise_sigma = aug->noise_sigma; a.fill = aug->fill;
+    const int64_t total = B * CP_TASKS * V;               // one thread per window
+    const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
+    ProfScope ps(CP_K_GATHER, (hipStream_t)stream);
+    hipLaunchKernelGGL(gather_groups_aug_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+    CKL("gather_groups_aug_kernel");
+    return 0;
+}
+
 extern "C" int cp_gather_oob_count(uint32_t* count_out, int32_t reset, void* stream) {
     if (!count_out) return fail(CP_ERR_ARG, "cp_gather_oob_count args");
     unsigned int* ctr = nullptr;

@@ -38,6 +38,127 @@ __global__ void gather_groups_kernel(const float* __restrict__ table, const int6
 }
 
 // ------------------------------------------------------------------------------------
+// gather with sEMG augmentation (cp_gather_groups_aug, include/cpnative.h; an opt-in EXTENSION, no reference counterpart):
+// the source row of gather_groups_kernel (same emg_rand / perm / V indexing, same out-of-range rule and counter), then the
+// 12 values of the window perturbed in registers before the launch's only store of them: ring shift of channels 0..7, per-channel
+// and per-item gain on the raw RMS value, additive noise, dead electrodes.  One thread per window: three 16-byte loads, three
+// 16-byte stores.  Shift, gains and the dead mask belong to the ITEM i = item_offset + b*41 + t (the V windows of an
+// evaluation item share them); noise is per (item, v, channel).
+// Draws are counter-based, a function of (seed, salt, i, v, d) alone -- never of B, the grid or the launch:
+//     k0 = h(seed ^ h(salt + 0x9E3779B9)),  k = h(k0 + i),  word(j) = h(k ^ (j*0x85EBCA6B + 0xC2B2AE35)),   h = hash32
+//     shift   = shift_min + ((word(0) * (shift_max - shift_min + 1)) >> 32)
+//     dead(d) = 16-bit half d & 1 (low first) of word(1 + d/2) < drop_thresh
+//     normals: n = (h0 + h1 + h2 + h3 - 131070) * AUG_NORM_C, the four halves of two words (Irwin-Hall, |n| < 3.47):
+//              gain g_d words 8 + 2d, 9 + 2d;  item gain a_i words 32, 33;  noise(v, d) words 34 + 2(12v + d) and the next
+// Arithmetic is single f32 operations in the order written, contraction off; contrastiveprosthetics_amd/augment.py restates it
+// in numpy.  A draw whose setting is off is not computed, and with everything off the row is copied as gather_groups_kernel does.
+// ------------------------------------------------------------------------------------
+#define AUG_NORM_C 0x1.bb67aep-16f           // f32 nearest to 1 / sqrt((65536^2 - 1) / 3): unit variance of the sum of four 16-bit draws
+struct GatherAugArgs {
+    const float* table;
+    const int64_t* emg_rand;
+    const int64_t* perm;
+    float* out;
+    const float* mean_std;               // [24]: mean[d], std[12 + d] of the raw RMS value, or nullptr (gain acts on x itself)
+    const uint32_t* salt_state;          // word 5 of a device cp_step_state (graph replay), or nullptr: `salt` below
+    int64_t B, D, table_rows;
+    int T, V;
+    uint32_t seed, salt, item_offset, drop_thresh, dead_mask;
+    int shift_min, shift_span;           // span = shift_max - shift_min + 1
+    float gain_sigma, amp_sigma, noise_sigma, fill;
+};
+__device__ __forceinline__ uint32_t aug_word(uint32_t k, uint32_t j) { return hash32(k ^ (j * 0x85EBCA6BU + 0xC2B2AE35U)); }
+__device__ __forceinline__ float aug_normal(uint32_t k, uint32_t j) {
+    const uint32_t a = aug_word(k, j), b = aug_word(k, j + 1);
+    const int s = (int)((a & 0xFFFFu) + (a >> 16) + (b & 0xFFFFu) + (b >> 16)) - 131070;
+    return (float)s * AUG_NORM_C;
+}
+// y[d] = x[(d + s) & 7] for the ring channels d = 0..7 by three conditional stages: no register is indexed at run time
+__device__ __forceinline__ void aug_rotate8(float (&x)[12], int s) {
+#pragma unroll
+    for (int bit = 1; bit < 8; bit <<= 1) {
+        const bool on = (s & bit) != 0;
+        float t[8];
+#pragma unroll
+        for (int d = 0; d < 8; ++d) t[d] = x[(d + bit) & 7];
+#pragma unroll
+        for (int d = 0; d < 8; ++d) x[d] = on ? t[d] : x[d];
+    }
+}
+__global__ __launch_bounds__(256) void gather_groups_aug_kernel(GatherAugArgs a) {
+#pragma clang fp contract(off)
+    const int64_t total = a.B * a.T * a.V;
+    const uint32_t salt = a.salt_state ? *a.salt_state : a.salt;
+    const uint32_t k0 = hash32(a.seed ^ hash32(salt + 0x9E3779B9U));
+    const bool norm = a.mean_std != nullptr;
+    for (int64_t win = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; win < total; win += (int64_t)gridDim.x * blockDim.x) {
+        const int v = (int)(win % a.V);
+        const int64_t bt = win / a.V;
+        const int t = (int)(bt % a.T);
+        const int64_t b = bt / a.T;
+        int64_t src = a.emg_rand[(int64_t)t * a.D + a.perm[b]] * a.V + v;      // row of the (rows,12) table
+        if (src < 0 || src >= a.table_rows) {
+            atomicAdd(&g_gather_oob, 1u);
+            src = 0;
+        }
+        const float4* in = (const float4*)(a.table + src * 12);
+        const float4 q0 = in[0], q1 = in[1], q2 = in[2];
+        float x[12] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w};
+        const uint32_t k = hash32(k0 + (a.item_offset + (uint32_t)bt));
+        int s = 0;
+        if (a.shift_span > 1) s = a.shift_min + (int)(((uint64_t)aug_word(k, 0) * (uint32_t)a.shift_span) >> 32);
+        else s = a.shift_min;
+        s &= 7;
+        // the source channel's constants travel with its value: mc[d] = mean[c], sc[d] = std[c] for c = (d + s) & 7
+        float mc[12], sc[12], md[12], sd[12];
+        if (norm) {
+#pragma unroll
+            for (int d = 0; d < 12; ++d) { md[d] = mc[d] = a.mean_std[d]; sd[d] = sc[d] = a.mean_std[12 + d]; }
+        }
+        if (s != 0) {
+            aug_rotate8(x, s);
+            if (norm) { aug_rotate8(mc, s); aug_rotate8(sc, s); }
+        }
+        const bool gains = a.gain_sigma > 0.f || a.amp_sigma > 0.f;
+        if (gains || (norm && s != 0)) {
+            const float amp = a.amp_sigma > 0.f ? expf(a.amp_sigma * aug_normal(k, 32)) : 1.f;
+#pragma unroll
+            for (int d = 0; d < 12; ++d) {
+                const float g = a.gain_sigma > 0.f ? expf(a.gain_sigma * aug_normal(k, 8 + 2 * d)) : 1.f;
+                const float G = g * amp;
+                if (norm) {
+                    const bool same = (d >= 8 || s == 0) && G == 1.0f;      // c == d and no gain: the value itself, no round trip
+                    const float r = x[d] * sc[d] + mc[d];
+                    const float y = (r * G - md[d]) / sd[d];
+                    x[d] = same ? x[d] : y;
+                } else {
+                    x[d] = x[d] * G;
+                }
+            }
+        }
+        if (a.noise_sigma > 0.f) {
+#pragma unroll
+            for (int d = 0; d < 12; ++d) x[d] = x[d] + a.noise_sigma * aug_normal(k, 34 + 2 * (12 * v + d));
+        }
+        uint32_t dead = a.dead_mask;
+        if (a.drop_thresh != 0) {
+#pragma unroll
+            for (int j = 0; j < 6; ++j) {
+                const uint32_t w = aug_word(k, 1 + j);
+                if ((w & 0xFFFFu) < a.drop_thresh) dead |= 1u << (2 * j);
+                if ((w >> 16) < a.drop_thresh) dead |= 2u << (2 * j);
+            }
+        }
+#pragma unroll
+        for (int d = 0; d < 12; ++d) x[d] = ((dead >> d) & 1u) ? a.fill : x[d];
+        float4* o = (float4*)(a.out + win * 12);
+        o[0] = make_float4(x[0], x[1], x[2], x[3]);
+        o[1] = make_float4(x[4], x[5], x[6], x[7]);
+        o[2] = make_float4(x[8], x[9], x[10], x[11]);
+    }
+}
+
+// ------------------------------------------------------------------------------------
 // BatchNorm statistics -> affine (train: batch stats, biased variance, eps 1e-5; running
 // stats updated with momentum and the unbiased variance, as nn.BatchNorm does).
 // partials: [nrows][2][C] (sum, sum of squares).  use_running: eval with stock BN.

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import augment as _augment
 from ._lib import CP_BF16, CP_D_E, CP_F32, CP_FP8, CP_N_BN, CP_N_FC, CP_TASKS
 
 LINEAR_IDX = (0, 3, 6, 9, 13, 17, 21)           # code/models.py:266-298
@@ -113,16 +114,31 @@ def _params_struct(store: FlatStore, adabn: bool) -> _lib.cp_params:
     return p
 
 
-def gather_groups(table: torch.Tensor, emg_rand: torch.Tensor, perm: torch.Tensor, V: int) -> torch.Tensor:
-    """cp_gather_groups: (B,41,V,12) f32 = table[(emg_rand[t, perm[b]] * V + v)]  (code/utils.py:51-64)."""
+def _gather_aug(lib, table, emg_rand, perm, B, V, out, augment, item_offset, stream, state_addr=0):
+    """cp_gather_groups_aug with the next salt of `augment`'s stream (a captured step reads it from the device state instead,
+    and GraphStep.step advances the stream)."""
+    salt = 0 if state_addr else augment.next_salt()
+    a = augment.struct(salt, item_offset, table.device, state_addr)
+    _lib.check(lib.cp_gather_groups_aug(table.data_ptr(), table.shape[0], emg_rand.data_ptr(), emg_rand.shape[1],
+                                        perm.data_ptr(), B, V, out.data_ptr(), C.byref(a), stream), "cp_gather_groups_aug")
+
+
+def gather_groups(table: torch.Tensor, emg_rand: torch.Tensor, perm: torch.Tensor, V: int, augment=None,
+                  item_offset: int = 0) -> torch.Tensor:
+    """cp_gather_groups: (B,41,V,12) f32 = table[(emg_rand[t, perm[b]] * V + v)]  (code/utils.py:51-64).
+    augment (an active augment.Augment): the same rows perturbed in the same launch (cp_gather_groups_aug); item b*41 + t of
+    this call is item item_offset + b*41 + t of the augmentation's counter."""
     lib = _lib.load()
     assert table.dtype == torch.float32 and table.is_contiguous() and table.shape[1] == 12
     assert emg_rand.dtype == torch.int64 and emg_rand.is_contiguous() and perm.dtype == torch.int64
     B = perm.numel()
     out = torch.empty(B, CP_TASKS, V, 12, dtype=torch.float32, device=table.device)
+    stream = torch.cuda.current_stream(table.device).cuda_stream
+    if augment is not None and augment.active:
+        _gather_aug(lib, table, emg_rand, perm.contiguous(), B, V, out, augment, item_offset, stream)
+        return out
     _lib.check(lib.cp_gather_groups(table.data_ptr(), table.shape[0], emg_rand.data_ptr(), emg_rand.shape[1],
-                                    perm.contiguous().data_ptr(), B, V, out.data_ptr(),
-                                    torch.cuda.current_stream(table.device).cuda_stream), "cp_gather_groups")
+                                    perm.contiguous().data_ptr(), B, V, out.data_ptr(), stream), "cp_gather_groups")
     return out
 
 
@@ -332,9 +348,14 @@ class Engine:
         return ws.data_ptr(), ws.numel()
 
     # ------------------------------------------------------------------ stages
-    def gather(self, table: torch.Tensor, emg_rand: torch.Tensor, perm: torch.Tensor, V: int) -> torch.Tensor:
+    def gather(self, table: torch.Tensor, emg_rand: torch.Tensor, perm: torch.Tensor, V: int, augment=None,
+               item_offset: int = 0) -> torch.Tensor:
         B = perm.numel()
         out = torch.empty(B, CP_TASKS, V, 12, dtype=torch.float32, device=self.device)
+        if augment is not None and augment.active:
+            state = self._graph_state.data_ptr() if self._graph_state is not None else 0
+            _gather_aug(self.lib, table, emg_rand, perm, B, V, out, augment, item_offset, self._stream(), state)
+            return out
         _lib.check(self.lib.cp_gather_groups(table.data_ptr(), table.shape[0], emg_rand.data_ptr(), emg_rand.shape[1],
                                              perm.data_ptr(), B, V, out.data_ptr(), self._stream()), "cp_gather_groups")
         return out
@@ -669,11 +690,14 @@ class GraphStep:
     launch-latency-bound, so this is where its wall time goes.  What changes from step to step is not baked into
     the graph: the batch indices live in a fixed device buffer, and the dropout salt, Adam's bias corrections and
     the (scheduled) learning rates in a 32-byte device `cp_step_state` refreshed by one async copy per step.
+    `augment` (an active augment.Augment): the captured gather is cp_gather_groups_aug reading its salt from the same state,
+    so a replayed step and a call-by-call step of one stream draw the same perturbation.
     One instance per (engine, batch size); the class encoder is the one-hot table or, with `glove_table`, the glove one."""
 
     def __init__(self, engine: "Engine", table: torch.Tensor, emg_rand: torch.Tensor, batch: int, params: dict,
-                 grad_scale: float = 1.0, glove=None):
+                 grad_scale: float = 1.0, glove=None, augment=None):
         self.e = engine
+        self.augment = augment if (augment is not None and augment.active) else None    # its salt travels in the state's aug_salt word
         self.params = dict(params)
         self.B = int(batch)
         dev = engine.device
@@ -723,7 +747,7 @@ class GraphStep:
 
     def _body(self, grad_scale):
         e = self.e
-        x = e.gather(self.table, self.emg_rand, self.perm, 1)
+        x = e.gather(self.table, self.emg_rand, self.perm, 1, augment=self.augment)
         z = e.encoder_forward(x, training=True)
         if self.glove is not None:
             zg = e.glove_forward(self.glove(self.perm), training=True)
@@ -753,6 +777,9 @@ class GraphStep:
         h[2] = 1.0 - b2 ** t
         h[3] = float(self.params.get("lr_emg", 0.0)) * self.lr_scale[0]
         h[4] = float(self.params.get("lr_glove", 0.0)) * self.lr_scale[1]
+        if self.augment is not None:
+            asalt = _augment.salt_of(self.augment.count + 1)
+            h.view(torch.int32)[5] = asalt - (1 << 32) if asalt >= (1 << 31) else asalt
         self.state.copy_(h, non_blocking=True)
         if self._host_ev[i] is None:
             self._host_ev[i] = torch.cuda.Event()
@@ -772,6 +799,8 @@ class GraphStep:
         e = self.e
         e.step_count += 1
         e.adam_steps += 1
+        if self.augment is not None:
+            self.augment.count += 1
         if not e.adabn:
             e.num_batches_tracked += 1
         return self.out

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import engine as _engine
+from .augment import Augment
 from .constants import MAX_TASKS
 from .load import DB23
 from .models import Model
@@ -109,6 +110,50 @@ def test(model, dataset, save="../data/", sweep_trials: int = 0):
     return mean_loss, acc
 
 
+def robustness(model, dataset, shifts=range(-3, 4), dead=(None, *range(12)), gain_sigma: float = 0.0, mean_std=None,
+               seed: int = 0) -> np.ndarray:
+    """What a checkpoint loses under a turned sleeve or a dead electrode (an extension): the test split once per
+    setting (ring shift s, dead channel d or None), perturbed in the gather's launch through `dataset.perturb` -- a fixed shift,
+    a dead_mask, and, with gain_sigma > 0, a log-normal channel gain drawn per item.  Every setting sees the same batches (one
+    sampler table, one order).  Returns (len(shifts), len(dead), 2): per-window accuracy and the 25-sample voted accuracy (the
+    mean over batches that `test` reports).  The (0, None) cell with gain_sigma = 0 is the unperturbed test pass."""
+    shifts, dead = [int(s) for s in shifts], list(dead)
+    table = np.zeros((len(shifts), len(dead), 2), dtype=np.float64)
+    dataset.set_test()
+    n = len(dataset)
+    order = (torch.randperm(n) if shuff else torch.arange(n)).to(dataset.device)
+    bs = args.batch_size if args is not None else 8
+    keep = dataset.perturb
+    try:
+        for i, s in enumerate(shifts):
+            for j, d in enumerate(dead):
+                aug = Augment(shift=s, dead=() if d is None else (int(d),), gain_sigma=gain_sigma, mean_std=mean_std, seed=seed)
+                dataset.perturb = aug if aug.active else None
+                model.set_test()
+                hits, windows = [], 0
+                for k in range(0, n, bs):
+                    EMG, GLOVE, label = dataset.batch(order[k:k + bs])
+                    label = label.reshape(-1)
+                    with torch.no_grad():
+                        logits = model.forward(EMG, GLOVE, label)
+                        model.loss(logits, label)
+                    hits.append(model._pending["out"][1:2])            # rows whose argmax is their label (cp_head)
+                    windows += logits.shape[0] * N_TASKS
+                table[i, j, 0] = float(torch.cat(hits).sum().item()) / windows
+                table[i, j, 1] = model.correct()
+    finally:
+        dataset.perturb = keep
+    return table
+
+
+def print_robustness(table: np.ndarray, shifts, dead):
+    for which, name in enumerate(("per-window accuracy", "voted accuracy (25 samples)")):
+        print(f"robustness, {name}: rows = ring shift, columns = dead channel")
+        print("shift " + " ".join(f"{'none' if d is None else d:>6}" for d in dead))
+        for s, row in zip(shifts, table[:, :, which]):
+            print(f"{s:5d} " + " ".join(f"{v:6.4f}" for v in row))
+
+
 def main(a):
     global args
     args = a
@@ -143,6 +188,11 @@ def main(a):
     final_stats = test(model, dataset23, save=args.save, sweep_trials=args.subset_trials)
     print("loss,\t\t\tcorrect")
     print(final_stats)
+    if args.robustness:
+        shifts, dead = list(range(-3, 4)), [None] + list(range(12))
+        table = robustness(model, dataset23, shifts, dead)
+        print_robustness(table, shifts, dead)
+        np.save(os.path.join(args.save, "robustness.npy"), table)
 
 
 def build_parser():
@@ -167,6 +217,8 @@ def build_parser():
     parser.add_argument("--checkpoint_dir", default="../checkpoints")
     parser.add_argument("--save", default="../data/")
     parser.add_argument("--subset_trials", type=int, default=0, help="random subsets per size for the README curve (144)")
+    parser.add_argument("--robustness", action="store_true",
+                        help="also evaluate the test split under ring shifts -3..3 x one dead electrode (robustness.npy, (7, 13, 2))")
     return parser
 
 

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import dist as cpdist
+from .augment import Augment
 from .load import DB23
 from .engine import GraphStep
 from .models import Model
@@ -77,6 +78,16 @@ def _sync_bn_buffers(model, world):
         cpdist.broadcast_buffers_([v for k, v in model.engine.running.items() if v.dtype.is_floating_point])
 
 
+def build_augment(a, rank: int = 0):
+    """The training-time augmentation of the --aug_* flags (all off: None).  Data-parallel ranks key their own stream
+    (seed + rank), so the shards of one global batch do not share draws."""
+    n = int(getattr(a, "aug_shift", 0))
+    aug = Augment(shift=(-n, n), p_drop=getattr(a, "aug_drop", 0.0), gain_sigma=getattr(a, "aug_gain", 0.0),
+                  amp_sigma=getattr(a, "aug_amp", 0.0), noise_sigma=getattr(a, "aug_noise", 0.0),
+                  seed=int(getattr(a, "aug_seed", 0)) + rank)
+    return aug if aug.active else None
+
+
 def train_loop(dataset, params, checkpoint=False, checkpoint_dir="../checkpoints/model", annealing=False, load=None,
                verbose=False, solo=False):
     """code/train.py:65-138.  solo: this process trains the model alone even inside a multi-process job (packed sweep)."""
@@ -95,6 +106,8 @@ def train_loop(dataset, params, checkpoint=False, checkpoint_dir="../checkpoints
         cpdist.broadcast_(model.engine.values.flat)
         reduce_grads = cpdist.GradAllReduce(model.engine)     # two buckets, the large one beside the conv backward
     epochs = params["epochs"]
+    augment = build_augment(args, rank)
+    dataset.augment = augment                 # TaskWrapper.batch applies it in train mode only: validate / test are untouched
     dataset.set_train()
     model.set_train()
     gen = torch.Generator().manual_seed(42)
@@ -114,7 +127,8 @@ def train_loop(dataset, params, checkpoint=False, checkpoint_dir="../checkpoints
             # the whole step as ONE graph launch (engine.GraphStep): at these batch sizes a step is ~110 launches of a few
             # microseconds each.  The loader's order is kept; a short last batch goes through the call-by-call path.
             if graph_step is None:
-                graph_step = GraphStep(model.engine, dataset.EMG_use, dataset.emg_rand, args.batch_size, model.params)
+                graph_step = GraphStep(model.engine, dataset.EMG_use, dataset.emg_rand, args.batch_size, model.params,
+                                       augment=augment)
             graph_step.set_sampler(dataset.emg_rand)
             graph_step.lr_scale = list(model.lr_scale)
             order = torch.randperm(len(dataset), generator=gen).to(model.device)
@@ -292,6 +306,14 @@ def build_parser():
                              "per step); off = every rank uses its shard's statistics, the reference at B_local")
     parser.add_argument("--graph", action="store_true",
                         help="replay each training step as one captured HIP graph (single process, one-hot class encoder)")
+    parser.add_argument("--aug_shift", type=int, default=0,
+                        help="extension (DESIGN 7w): training windows read the electrode ring turned by a shift drawn per item from "
+                             "-N..N; 0 = off")
+    parser.add_argument("--aug_drop", type=float, default=0.0, help="probability that a channel of a training item is dead (stores 0)")
+    parser.add_argument("--aug_gain", type=float, default=0.0, help="sigma of the log-normal gain per (item, channel)")
+    parser.add_argument("--aug_amp", type=float, default=0.0, help="sigma of the log-normal gain per item")
+    parser.add_argument("--aug_noise", type=float, default=0.0, help="sigma of the additive noise per element, normalised units")
+    parser.add_argument("--aug_seed", type=int, default=0, help="seed of the augmentation's draws (data-parallel rank r uses seed + r)")
     parser.add_argument("--hpo_pack", action="store_true",
                         help="packed random search: every rank trains its share of the --crossval_size configurations alone "
                              "(any number of ranks per GPU, results gathered over gloo); rank 0 then trains the final model")

@@ -47,7 +47,13 @@ class Glover:
 class TaskWrapper:
     """code/utils.py:21-76.  ``__getitem__`` keeps the reference's per-item contract (one group of 41
     windows, one per class); ``batch(perm)`` is the fused path: the B items of a DataLoader batch and
-    their default_collate in ONE cp_gather_groups launch."""
+    their default_collate in ONE cp_gather_groups launch.
+    `augment` / `perturb` (augment.Augment or None, both off by default; an extension): `batch` perturbs the
+    windows in that same launch -- `augment` in train mode only (training-time augmentation), `perturb` in val / test mode
+    only (what a checkpoint loses under a turned sleeve or a dead electrode: results.robustness)."""
+
+    augment = None
+    perturb = None
 
     def __init__(self, dataset):
         self.dataset = dataset
@@ -82,7 +88,8 @@ class TaskWrapper:
         ds = self.dataset
         B = perm.numel()
         V = 1 if ds.train else ds.OUTPUT_DIM
-        EMG = gather_groups(ds.EMG_use, self.emg_rand, perm, V).reshape(B, ds.TASKS, V, 1, 12)
+        aug = self.augment if ds.train else self.perturb
+        EMG = gather_groups(ds.EMG_use, self.emg_rand, perm, V, augment=aug).reshape(B, ds.TASKS, V, 1, 12)
         GLOVE = None
         if with_glove:
             gidx = self.glove_rand[:, perm % ds.glover.D].t()               # (B,41)

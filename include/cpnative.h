@@ -183,7 +183,8 @@ typedef struct cp_step_state {
     uint32_t dp_salt;     /* any function of the step index, e.g. a hash of it */
     float bc1, bc2;       /* 1 - beta1^t, 1 - beta2^t */
     float lr_emg, lr_glove;
-    float pad[3];
+    uint32_t aug_salt;    /* the salt of this step's cp_gather_groups_aug, when its cp_augment names this state */
+    float pad[2];
 } cp_step_state;
 
 int cp_version(void);
@@ -204,6 +205,41 @@ int cp_gather_groups(const float* table, int64_t table_rows, const int64_t* emg_
  * word count_out (stream-ordered) and, with reset != 0, zeroes it afterwards.  Non-zero = emg_rand, V and the table
  * do not belong together. */
 int cp_gather_oob_count(uint32_t* count_out, int32_t reset, void* stream);
+
+/* ---- sEMG augmentation in the gather (an opt-in EXTENSION of the data path, no reference counterpart) ---------------
+ * cp_gather_groups_aug is cp_gather_groups -- same source rows, same out-of-range rule and counter, same single launch --
+ * whose windows are perturbed before they are stored, in this order, for item i = item_offset + b*41 + t, sample v,
+ * model channel d:
+ *   1. ring shift: s uniform in shift_min..shift_max; channels 0..7 read source channel c = (d + s) mod 8, channels 8..11
+ *      c = d (the map cp_online_*push_mapped takes for a sleeve turned by s positions);
+ *   2. gain: G = exp(gain_sigma n_d) exp(amp_sigma n_i).  With mean_std the gain acts on the raw RMS value and the result
+ *      is normalised with the model channel's constants, as a mapped push does: r = x[c] std[c] + mean[c],
+ *      y = (r G - mean[d]) / std[d]; a channel with c == d and G == 1 keeps x[d] itself.  Without (NULL): y = x[c] G;
+ *   3. noise: y += noise_sigma n per element, in normalised units;
+ *   4. dead electrodes: channel d stores `fill` for the whole item with probability p_drop, or always if bit d of
+ *      dead_mask is set.
+ * Shift, gains and the dead set are drawn per item: the V windows of an evaluation item share them.  Every draw is a
+ * counter-based function of (seed, salt, i, v, d) -- csrc/kernels_misc.cuh states the chain, and
+ * contrastiveprosthetics_amd/augment.py restates it in numpy -- so a window's perturbation does not depend on B, the
+ * grid or the launch.  f32 arithmetic in the order above, contraction off.  A setting that is off draws nothing; with
+ * everything off x_out is cp_gather_groups' output bit for bit.
+ * salt: per gather, any function of a step counter.  salt_state_{lo,hi}: the DEVICE address of a cp_step_state, or 0/0;
+ * when set, the kernel reads the salt from its aug_salt word instead (graph replay).
+ * Refused with CP_ERR_ARG before anything is enqueued: what cp_gather_groups refuses, a table or x_out that is not 16-byte aligned, a NULL aug, shift bounds outside
+ * -7..7 or min > max, p_drop outside [0, 1], a sigma that is negative, not finite or above 2, a `fill` that is not
+ * finite, dead_mask above 0xFFF, item_offset below 0 or item_offset + B*41 above 2^32.  Allocates, synchronises and
+ * reads nothing. */
+typedef struct cp_augment {
+    uint32_t seed, salt;
+    uint32_t salt_state_lo, salt_state_hi;
+    int32_t shift_min, shift_max;
+    uint32_t dead_mask;
+    float p_drop, gain_sigma, amp_sigma, noise_sigma, fill;
+    const float* mean_std;      /* (24) device floats: [d] mean, [12 + d] std of the raw RMS value; or NULL */
+    int64_t item_offset;
+} cp_augment;
+int cp_gather_groups_aug(const float* table, int64_t table_rows, const int64_t* emg_rand, int64_t D,
+                         const int64_t* perm, int64_t B, int32_t V, float* x_out, const cp_augment* aug, void* stream);
 
 /* EMGNet.forward (code/models.py:319-342): conv_emg -> linear -> last.
  * x (n_windows,12) f32, 16-byte aligned (a window's 12 values are read as three 16-byte loads; cp_gather_groups'
