@@ -102,6 +102,16 @@ class cp_step_state(C.Structure):
                 ("aug_salt", C.c_uint32), ("pad", C.c_float * 2)]
 
 
+class cp_debug_fc_gemm_args(C.Structure):
+    """One fc-layer GEMM launch on caller buffers (include/cpnative.h): what cp_debug_fc_gemm takes."""
+    _fields_ = [("dtype", C.c_int32), ("kind", C.c_int32), ("M", C.c_int64), ("K", C.c_int32), ("F", C.c_int32),
+                ("tile_schedule", C.c_int32), ("coef_mod", C.c_int32),
+                ("A", C.c_void_p), ("W", C.c_void_p), ("C", C.c_void_p), ("bias", C.c_void_p), ("R", C.c_void_p),
+                ("partials", C.c_void_p), ("coef", C.c_void_p),
+                ("dp_thresh", C.c_uint32), ("dp_key", C.c_uint32), ("dp_inv_keep", C.c_float), ("reserved0", C.c_int32),
+                ("stat_rows_out", C.POINTER(C.c_int32))]
+
+
 CP_ONLINE_MAX_CLASSES, CP_ONLINE_MAX_VOTE, CP_ONLINE_MAX_WINDOWS, CP_ONLINE_STRIDE = 64, 256, 256, 20
 CP_ONLINE_MULTI_MAX_STREAMS, CP_ONLINE_MULTI_MAX_ROWS = 256, 65536
 CP_ONLINE_GATE_SCORES, CP_ONLINE_GATE_SWEEP_MAX_CONFIGS = 10, 65536
@@ -160,6 +170,7 @@ SYMBOLS = {
     "cp_debug_head_grad": (C.c_int, [_P(cp_config), _fp, C.c_size_t, _fp, _fp]),
     "cp_debug_glove_head_grad": (C.c_int, [_P(cp_config), _fp, C.c_size_t, C.c_int64, _fp, _fp]),
     "cp_debug_gemm": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "cp_debug_fc_gemm": (C.c_int, [_P(cp_debug_fc_gemm_args), _fp]),
     "cp_online_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "cp_online_prepare": (C.c_int, [_P(cp_online_config), _P(cp_params), _P(cp_bn_buffers), C.c_float, _fp, C.c_size_t, _fp]),
     "cp_online_set_classes": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, _fp, C.c_int32, _fp]),

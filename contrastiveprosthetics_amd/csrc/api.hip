@@ -805,30 +805,71 @@ extern "C" int cp_l2_adam_step_graph(float* params_flat, const float* grads_flat
 // debug access
 // ---------------------------------------------------------------------------------------
 template <typename T>
-static int debug_gemm_t(int kind, int64_t M, int K, int F, const void* A, const void* W, void* C, const float* bias,
-                        const void* R, float* partials, hipStream_t st) {
-    if (kind == 2) {
+static int debug_fc_gemm_t(const cp_debug_fc_gemm_args* d, hipStream_t st) {
+    const int64_t M = d->M;
+    const int K = d->K, F = d->F;
+    int rows = 0;
+    if (d->kind == 2) {
         int S;
         if constexpr (sizeof(T) == 2) {
             GemmTN256Args ta{};
-            ta.X = (const bf16_t*)A; ta.ldx = K; ta.Y = (const bf16_t*)W; ta.ldy = F; ta.slabs = (float*)C; ta.M = M; ta.P = K; ta.Q = F;
+            ta.X = (const bf16_t*)d->A; ta.ldx = K; ta.Y = (const bf16_t*)d->W; ta.ldy = F; ta.slabs = (float*)d->C; ta.M = M; ta.P = K; ta.Q = F;
             split_rows(M, F == 512 ? 64 : 40, &S, &ta.rows_per_split);
             ta.splits = S;
             CK(launch_gemm_tn256(ta, st));
         } else {
             GemmTNArgs ta{};
-            ta.X = A; ta.ldx = K; ta.Y = W; ta.ldy = F; ta.slabs = (float*)C; ta.M = M; ta.P = K; ta.Q = F;
+            ta.X = d->A; ta.ldx = K; ta.Y = d->W; ta.ldy = F; ta.slabs = (float*)d->C; ta.M = M; ta.P = K; ta.Q = F;
             split_rows(M, 32, &S, &ta.rows_per_split);
             CK((launch_gemm_tn<T, 128, 128, YLOAD_PLAIN>(ta, S, st)));
         }
+        if (d->stat_rows_out) *d->stat_rows_out = S;
         return 0;
     }
     GemmNTArgs a{};
-    a.A = A; a.lda = K; a.M = M; a.K = K; a.W = W; a.F = F; a.C = C; a.ldc = F; a.bias = bias; a.relu = 1;
-    a.R = R; a.ldr = F; a.partials = partials;
-    if (kind == 0) CK((launch_fc_gemm<T, EPI_FWD>(a, st)));
-    else CK((launch_fc_gemm<T, EPI_DGRAD>(a, st)));
+    a.A = d->A; a.lda = K; a.M = M; a.K = K; a.W = d->W; a.F = F; a.C = d->C; a.ldc = F; a.bias = d->bias; a.relu = 1;
+    a.R = d->R; a.ldr = F; a.partials = d->partials;
+    a.coef = d->coef; a.coef_mod = d->coef ? d->coef_mod : 0;
+    a.dp_thresh = d->dp_thresh; a.dp_key = d->dp_key; a.dp_inv_keep = d->dp_inv_keep;
+    const bool dyn = d->tile_schedule == CP_TILES_DYNAMIC;
+    if (d->kind == 0) CK((launch_fc_gemm<T, EPI_FWD>(a, st, &rows, dyn)));
+    else CK((launch_fc_gemm<T, EPI_DGRAD>(a, st, &rows, dyn)));
+    if (d->kind == 1 && !d->R) rows = 0;                  // a data gradient without a saved activation carries no sums
+    if (d->stat_rows_out) *d->stat_rows_out = rows;
     return 0;
+}
+
+// everything a launcher would refuse, or a kernel would read or write out of bounds, before anything launches
+static int check_debug_fc_gemm(const cp_debug_fc_gemm_args* d) {
+    if (!d) return fail(CP_ERR_ARG, "cp_debug_fc_gemm args");
+    if (d->dtype != CP_F32 && d->dtype != CP_BF16) return fail(CP_ERR_ARG, "cp_debug_fc_gemm: dtype must be CP_F32 or CP_BF16");
+    if (d->kind < 0 || d->kind > 2) return fail(CP_ERR_ARG, "cp_debug_fc_gemm: kind must be 0, 1 or 2");
+    if (d->tile_schedule != CP_TILES_STATIC && d->tile_schedule != CP_TILES_DYNAMIC) return fail(CP_ERR_ARG, "cp_debug_fc_gemm: tile_schedule");
+    if (!d->A || !d->W || !d->C) return fail(CP_ERR_ARG, "cp_debug_fc_gemm: A, W and C must not be NULL");
+    if (d->kind != 2 && !d->partials) return fail(CP_ERR_ARG, "cp_debug_fc_gemm: partials must not be NULL");
+    if (d->kind == 0 && !d->bias) return fail(CP_ERR_ARG, "cp_debug_fc_gemm: the forward needs a bias");
+    if (d->M <= 0 || d->K <= 0 || d->F <= 0 || d->K % 64 || d->F % 256) return fail(CP_ERR_ARG, "cp_debug_fc_gemm: M > 0, K % 64 == 0, F % 256 == 0");
+    const bool b16 = d->dtype == CP_BF16;
+    if (d->kind == 2 && d->K % (b16 ? 256 : 128)) return fail(CP_ERR_ARG, "cp_debug_fc_gemm: the weight gradient needs K % 256 == 0 (f32: 128)");
+    if (b16 && d->kind != 2 && d->F > 256 * NT256P_MAX_TILES_F) return fail(CP_ERR_ARG, "cp_debug_fc_gemm: F > 768");
+    // 32-bit byte offsets of the weight-stationary kernels' buffer loads and the dropout hash's 32-bit element index (check_cfg)
+    const int wide = d->K > d->F ? d->K : d->F;
+    if ((uint64_t)d->M * (uint64_t)wide * 2 >= 0xFFF00000ull) return fail(CP_ERR_ARG, "cp_debug_fc_gemm: M * max(K, F) * 2 must stay below 2^32");
+    const bool drop = d->dp_thresh != 0;
+    if (d->kind != 1 && (d->R || d->coef || drop)) return fail(CP_ERR_ARG, "cp_debug_fc_gemm: R, coef and dropout belong to kind 1");
+    if ((d->coef || drop) && (!d->R || !b16)) return fail(CP_ERR_ARG, "cp_debug_fc_gemm: coef and dropout need R and CP_BF16");
+    if (d->coef && drop) return fail(CP_ERR_ARG, "cp_debug_fc_gemm: coef and dropout exclude each other");
+    if (d->coef && d->coef_mod <= 0) return fail(CP_ERR_ARG, "cp_debug_fc_gemm: coef_mod must be positive");
+    if (drop && (d->dp_thresh > 65535u || !(d->dp_inv_keep > 0.f))) return fail(CP_ERR_ARG, "cp_debug_fc_gemm: dp_thresh in 1..65535, dp_inv_keep > 0");
+    if ((((uintptr_t)d->A | (uintptr_t)d->W | (uintptr_t)d->C | (uintptr_t)d->R) & 15) != 0)
+        return fail(CP_ERR_ARG, "cp_debug_fc_gemm: A, W, C and R must be 16-byte aligned");
+    return 0;
+}
+
+extern "C" int cp_debug_fc_gemm(const cp_debug_fc_gemm_args* args, void* stream) {
+    if (int e = check_debug_fc_gemm(args)) return e;
+    if (args->dtype == CP_BF16) return debug_fc_gemm_t<bf16_t>(args, (hipStream_t)stream);
+    return debug_fc_gemm_t<float>(args, (hipStream_t)stream);
 }
 
 __global__ __launch_bounds__(256) void hog_kernel(long long ticks, float* sink) {
@@ -849,8 +890,11 @@ extern "C" int cp_debug_gemm(int32_t dtype, int32_t kind, int64_t M, int32_t K, 
                              void* C, const float* bias, const void* R, float* partials, void* stream) {
     if (!A || !W || !C || !partials || M <= 0 || K % 64 || F % 256 || kind < 0 || kind > 2)
         return fail(CP_ERR_ARG, "cp_debug_gemm args");
-    if (dtype == CP_BF16) return debug_gemm_t<bf16_t>(kind, M, K, F, A, W, C, bias, R, partials, (hipStream_t)stream);
-    return debug_gemm_t<float>(kind, M, K, F, A, W, C, bias, R, partials, (hipStream_t)stream);
+    // the static schedule, no coefficients, no dropout.  (R and bias are read by the kinds that have them.)
+    cp_debug_fc_gemm_args d{};
+    d.dtype = dtype == CP_BF16 ? CP_BF16 : CP_F32; d.kind = kind; d.M = M; d.K = K; d.F = F; d.tile_schedule = CP_TILES_STATIC;
+    d.A = A; d.W = W; d.C = C; d.bias = kind == 0 ? bias : nullptr; d.R = kind == 1 ? R : nullptr; d.partials = partials;
+    return cp_debug_fc_gemm(&d, stream);
 }
 
 #include "online_api.cuh"             // the cp_online_* entries: host layer of the online decoders, the gate, the gate sweep and the subset sweep

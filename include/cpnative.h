@@ -461,7 +461,46 @@ int cp_debug_hog(int32_t blocks, int32_t microseconds, void* stream);
 int cp_debug_gemm(int32_t dtype, int32_t kind, int64_t M, int32_t K, int32_t F, const void* A,
                   const void* W, void* C, const float* bias, const void* R, float* partials,
                   void* stream);
-
+/* debug/test access (tests/test_gpu_fc_gemm_exact.py): every fc-layer GEMM launch on caller buffers, one at a time.  cp_debug_gemm
+ * is this entry with CP_TILES_STATIC and no coef / dropout.  lda = K, ldc = ldr = F.  What runs (CP_BF16; CP_F32 runs the 128-tile
+ * parity kernels under either schedule and takes neither coef nor dropout):
+ *   kind 0                        static: the weight-stationary forward (K = 512; K = 768 with F = 512), else the persistent kernel;
+ *                                 dynamic: the persistent kernel.  partials: rows of [2][F], column sums of C and C^2 as stored
+ *   kind 1, R NULL                the persistent kernel, plain product, no sums (*stat_rows_out = 0)
+ *   kind 1, R and coef            C = R > 0 ? ca (A W^T) + cb R + cz : 0 with ca / cb / cz[f] = coef[{0,1,2} * coef_mod + f % coef_mod];
+ *                                 partials: rows of [F], column sums of C.  Static: weight-stationary (K = 512), dynamic: persistent
+ *   kind 1, R without coef        C = mask (A W^T) dp_inv_keep (dp_thresh != 0: element (m, f) is kept when the 16-bit draw of the
+ *                                 dropout hash of (dp_key, m, F, f) is >= dp_thresh), partials: rows of [2][F], column sums of C and
+ *                                 C R.  Static: weight-stationary (K = 512), dynamic: persistent
+ *   kind 2                        slabs[S][K][F] = sum over the rows of split s of A[m][K]^T W[m][F] (*stat_rows_out = S)
+ * stat_rows_out (host, may be NULL): the number of partial rows written.  Under CP_TILES_DYNAMIC that is one row per 256-row
+ * sample tile, in tile order; otherwise one row per worker of the kernel that ran.
+ * Checked before anything launches, CP_ERR_ARG: NULL A / W / C (partials for kinds 0 and 1, bias for kind 0), M <= 0, K % 64, F % 256
+ * (kind 2: K % 256, CP_F32 128), CP_BF16 kinds 0 and 1 with F > 768, an unknown dtype / kind / tile_schedule, M max(K, F) 2 >= 2^32 - 2^20,
+ * R / coef / dropout outside kind 1, coef or dropout without R or outside CP_BF16, both at once, coef_mod <= 0 with coef,
+ * dp_thresh > 65535, dp_inv_keep <= 0 with dropout, A / W / C / R not 16-byte aligned. */
+typedef struct cp_debug_fc_gemm_args {
+    int32_t dtype;             /* CP_F32 | CP_BF16 */
+    int32_t kind;              /* 0 forward, 1 data gradient, 2 weight gradient */
+    int64_t M;
+    int32_t K;
+    int32_t F;
+    int32_t tile_schedule;     /* CP_TILES_STATIC | CP_TILES_DYNAMIC */
+    int32_t coef_mod;
+    const void* A;
+    const void* W;
+    void* C;
+    const float* bias;
+    const void* R;
+    float* partials;
+    const float* coef;         /* [3][coef_mod] or NULL */
+    uint32_t dp_thresh;        /* 0: no dropout */
+    uint32_t dp_key;
+    float dp_inv_keep;
+    int32_t reserved0;
+    int32_t* stat_rows_out;
+} cp_debug_fc_gemm_args;
+int cp_debug_fc_gemm(const cp_debug_fc_gemm_args* args, void* stream);
 
 /* BN statistics of `layer` as computed by the last forward: out[4][C] = mean, invstd, scale, shift */
 int cp_debug_bn_stats(const cp_config* cfg, void* ws, size_t ws_bytes, int32_t layer, float* out,

@@ -57,7 +57,8 @@ def test_struct_layouts_match_header_with_forward_record():
     assert ctypes.sizeof(_lib.cp_config) == (8 + 4 * 4 + 4 * 4 + 8 + 8) + 4 + 4 + 8 + 8 + 4 + 4 + 8 + 8 + 3 * 8 + 8
     assert ctypes.sizeof(_lib.cp_forward_record) == 8 + 4 * 4 + 8
     hdr = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    for struct in ("cp_config", "cp_forward_record"):
+    assert ctypes.sizeof(_lib.cp_debug_fc_gemm_args) == 8 + 8 + 4 * 4 + 7 * 8 + 4 * 4 + 8
+    for struct in ("cp_config", "cp_forward_record", "cp_debug_fc_gemm_args"):
         body = hdr[hdr.index("typedef struct %s {" % struct):hdr.index("} %s;" % struct)]
         fields = re.findall(r"\b(\w+)\s*;", body)
         assert fields == [f[0] for f in getattr(_lib, struct)._fields_], fields
@@ -194,6 +195,60 @@ def test_head_grad_readback_refuses_null_out_and_short_workspaces_before_it_laun
         assert lib.cp_debug_head_grad(ctypes.byref(cfg), None, nb, ok, None) == 10001
         assert lib.cp_debug_glove_head_grad(ctypes.byref(cfg), gws, gnb, rows + 1, ok, None) == 10001
         assert lib.cp_debug_glove_head_grad(ctypes.byref(cfg), None, gnb, rows, ok, None) == 10001
+
+
+def test_debug_fc_gemm_refuses_what_a_launcher_would_before_it_launches(lib):
+    """cp_debug_fc_gemm checks its arguments on the host: what a launcher would refuse, or a kernel would read or write out of
+    bounds, is CP_ERR_ARG with a message that names the entry, before any launch (every pointer is a dummy address that is never
+    dereferenced; each case differs from a valid call in the one field under test, so that check is what refuses.  That the valid
+    calls are accepted is shown on the GPU: tests/test_gpu_fc_gemm_exact.py).  cp_debug_gemm keeps refusing what it refused."""
+    from contrastiveprosthetics_amd import _lib
+    ok = 0x100000
+    rows = ctypes.c_int32(-7)
+
+    def call(**kw):
+        d = _lib.cp_debug_fc_gemm_args()
+        d.dtype, d.kind, d.M, d.K, d.F, d.tile_schedule = 1, 0, 1000, 512, 512, 0
+        d.A = d.W = d.C = d.partials = ok
+        d.stat_rows_out = ctypes.pointer(rows)
+        for k, v in kw.items():
+            setattr(d, k, v)
+        if d.kind == 0 and "bias" not in kw:
+            d.bias = ok
+        rc = lib.cp_debug_fc_gemm(ctypes.byref(d), None)
+        return rc, lib.cp_last_error()
+
+    bn = dict(kind=1, R=ok, coef=ok, coef_mod=512)
+    st = dict(kind=1, R=ok, dp_thresh=32768, dp_key=7, dp_inv_keep=2.0)
+    cases = [("A", dict(A=None)), ("W", dict(W=None)), ("C", dict(C=None)), ("partials", dict(partials=None)),
+             ("partials, kind 1", dict(kind=1, partials=None)), ("bias", dict(bias=None)),
+             ("M = 0", dict(M=0)), ("M < 0", dict(M=-5)), ("K % 64", dict(K=544)), ("K = 0", dict(K=0)), ("F % 256", dict(F=640)),
+             ("F = 0", dict(F=0)), ("F = 1024 forward", dict(F=1024)), ("F = 1024 plain dgrad", dict(kind=1, F=1024)),
+             ("F = 1024 BN", dict(bn, F=1024)), ("F = 1024 ST", dict(st, F=1024)),
+             ("kind 3", dict(kind=3)), ("kind -1", dict(kind=-1)), ("schedule 2", dict(tile_schedule=2)),
+             ("schedule -1", dict(tile_schedule=-1)), ("dtype 2", dict(dtype=2)), ("dtype -1", dict(dtype=-1)),
+             ("coef_mod 0", dict(bn, coef_mod=0)), ("coef_mod -64", dict(bn, coef_mod=-64)),
+             ("coef without R", dict(bn, R=None)), ("dropout without R", dict(st, R=None)), ("coef and dropout", dict(bn, **st)),
+             ("coef in f32", dict(bn, dtype=0)), ("dropout in f32", dict(st, dtype=0)),
+             ("R in the forward", dict(R=ok)), ("coef in the forward", dict(coef=ok, coef_mod=512)),
+             ("dropout in the weight gradient", dict(st, kind=2)),
+             ("dp_thresh 65536", dict(st, dp_thresh=65536)), ("dp_inv_keep 0", dict(st, dp_inv_keep=0.0)),
+             ("K = 64 weight gradient", dict(kind=2, K=64)), ("K = 384 weight gradient", dict(kind=2, K=384)),
+             ("K = 64 weight gradient, f32", dict(kind=2, K=64, dtype=0)),
+             ("2^32 bytes", dict(M=2796203, K=768)), ("A + 8", dict(A=ok + 8)), ("W + 2", dict(W=ok + 2)), ("C + 4", dict(C=ok + 4)),
+             ("R + 8", dict(bn, R=ok + 8))]
+    for what, kw in cases:
+        rc, msg = call(**kw)
+        assert rc == 10001 and msg.startswith(b"cp_debug_fc_gemm"), (what, rc, msg)
+        assert rows.value == -7, what
+    for what, says in (("coef_mod 0", b"coef_mod"), ("F = 1024 BN", b"F > 768"), ("schedule 2", b"tile_schedule"), ("kind 3", b"kind")):
+        assert says in call(**dict(cases)[what])[1], what
+    assert lib.cp_debug_fc_gemm(None, None) == 10001
+    for kw in (dict(A=None), dict(W=None), dict(C=None), dict(partials=None), dict(M=0), dict(K=544), dict(F=640), dict(kind=3)):
+        a = dict(dtype=1, kind=0, M=1000, K=512, F=512, A=ok, W=ok, C=ok, bias=ok, R=None, partials=ok)
+        a.update(kw)
+        rc = lib.cp_debug_gemm(a["dtype"], a["kind"], a["M"], a["K"], a["F"], a["A"], a["W"], a["C"], a["bias"], a["R"], a["partials"], None)
+        assert rc == 10001 and b"cp_debug_gemm args" in lib.cp_last_error(), (kw, rc, lib.cp_last_error())
 
 
 def test_backward_refuses_a_short_gradient_tap_before_it_launches(lib):

@@ -188,16 +188,19 @@ def _shift_w(t, d):
     return out
 
 
-def recompute_check(n_groups=B, p_drop=P_DROP, data_seed=6, dtype="bf16"):
+def recompute_check(n_groups=B, p_drop=P_DROP, data_seed=6, dtype="bf16", tile_schedule=None):
     """every kernel of one training step against a plain torch fp32 recomputation of ITS output from ITS OWN stored inputs, at
     n_groups groups, with or without dropout (p_drop = 0: every data gradient is the BatchNorm-fused kind).  Also run by
-    tests/test_gpu_ws_kernels.py at a size with ragged tiles."""
+    tests/test_gpu_ws_kernels.py at a size with ragged tiles, and by tests/test_gpu_tile_schedule.py with tile_schedule =
+    CP_TILES_DYNAMIC (None: the engine's default), where the persistent kernel runs every fc launch."""
     B, N, P_DROP = n_groups, T * n_groups, p_drop
     drop = p_drop > 0
     from contrastiveprosthetics_amd import _lib
     from contrastiveprosthetics_amd.engine import Engine
     adabn = False
     e = Engine(adabn=adabn, dtype=dtype, dp_emg=P_DROP, device="cuda", seed=1000)
+    if tile_schedule is not None:
+        e.tile_schedule = tile_schedule
     e.init_parameters(5)
     gen = torch.Generator().manual_seed(9)
     bnn = _bn_names(adabn)

@@ -1,8 +1,12 @@
-"""The two tile schedules of the persistent fc GEMM kernels (cp_config.tile_schedule, include/cpnative.h): the outputs of
-the GEMMs are identical (same tiles, same arithmetic, whichever workgroup computes them); the BatchNorm partial sums
-are grouped per sample tile (dynamic) or per workgroup (static) and then added in f64, so the statistics and everything
-downstream agree to fp32 rounding of the partial rows; each schedule is reproducible run to run -- the dynamic one
-although which workgroup runs which tile changes from launch to launch.
+"""The two tile schedules of the fc GEMM launches (cp_config.tile_schedule, include/cpnative.h).  Per schedule the outputs are
+identical from run to run -- under the dynamic one although which workgroup runs which tile changes from launch to launch, because
+its BatchNorm partial sums leave as one row per sample tile.  ACROSS schedules different kernels run: the static schedule sends the
+bf16 forward launches and every data gradient with a saved activation to the weight-stationary kernels (csrc/gemm_ws.cuh), the
+dynamic one runs the persistent kernel (csrc/gemm_nt256p.cuh) for all of them.  Both round the same tensors to the same type, but
+their float32 sums are grouped differently (the products' accumulation, partial rows per worker or per sample tile), so the
+embeddings and gradients of the two agree to float32 rounding carried through seven BatchNorm layers, not bit for bit.
+What each kernel computes on its own is held exactly by tests/test_gpu_fc_gemm_exact.py; here the whole step under the dynamic
+schedule is held to the kernel-by-kernel fp32 recomputation of tests/test_gpu_fullsize.py, at that test's unchanged bounds.
 40,000 rows = 157 sample tiles (ragged last tile), 167,936 rows = the bench size (656 tiles, more than one round)."""
 import pytest
 import torch
@@ -49,6 +53,17 @@ def test_schedules_agree(dp):
     a, b = gs.double(), gd.double()
     cos = float(a @ b / (a.norm() * b.norm()))
     assert cos > 0.9995, cos
+
+
+@pytest.mark.parametrize("dp", [0.0, 0.0635])
+def test_dynamic_schedule_against_fp32_recompute_ragged(dp):
+    """every kernel of one step under CP_TILES_DYNAMIC against the fp32 recomputation of its output from its own stored inputs, at
+    the ragged size of tests/test_gpu_ws_kernels.py (975 groups = 39,975 rows = 157 sample tiles: more than one round, the last
+    tile ragged).  What the isolated launches of tests/test_gpu_fc_gemm_exact.py cannot show: that EPI_DGRAD_ST's dropout mask is
+    the forward's, that the host layer sizes and reduces the per-sample-tile partial rows, and that the BatchNorm coefficients
+    reach EPI_DGRAD_BN in the layout it reads (dp = 0: every data gradient is the BatchNorm-fused kind)."""
+    from test_gpu_fullsize import recompute_check
+    recompute_check(975, dp, data_seed=3, tile_schedule=DYNAMIC)
 
 
 def test_unknown_mode_is_rejected():
