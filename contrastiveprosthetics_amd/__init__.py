@@ -18,4 +18,7 @@ def __getattr__(name):
                 "pick_channel_map"):
         from . import online
         return getattr(online, name)
+    if name == "finetune_reference":
+        from .finetune import finetune_reference
+        return finetune_reference
     raise AttributeError(name)

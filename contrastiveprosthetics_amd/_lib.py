@@ -118,6 +118,7 @@ CP_ONLINE_GATE_SCORES, CP_ONLINE_GATE_SWEEP_MAX_CONFIGS = 10, 65536
 CP_ONLINE_SUBSET_SCORES, CP_ONLINE_SUBSET_SWEEP_MAX_SUBSETS = 7, 1048576
 CP_ONLINE_DRIVE_ONE, CP_ONLINE_DRIVE_MAX_SMOOTH = 4096, 256
 CP_ONLINE_MAP_SCORES, CP_ONLINE_MAP_SWEEP_MAX_MAPS = 3, 65536
+CP_ONLINE_FINETUNE_CHUNK, CP_ONLINE_FINETUNE_PROJECTION, CP_ONLINE_FINETUNE_ROWS = 64, 1, 2
 
 # what the four map sweep entries take behind their workspace: rms, n_windows, mean_std, map_src, map_fill, n_maps, n_classes,
 # expected_slot, chunk_rows, scratch, scratch_bytes, pred, voted, scores, class_hits, stream
@@ -215,6 +216,23 @@ SYMBOLS = {
     "cp_online_multi_adapt_enroll": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, C.c_int32, _fp, C.c_int64,
                                                _fp, C.c_int32, _fp, _fp, C.c_size_t, _fp]),
     "cp_online_enroll_table": (C.c_int, [_fp, C.c_int32, _fp, C.c_double, C.c_int32, _fp, _fp]),
+    "cp_online_tail_inputs": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, C.c_int64, _fp, _fp, C.c_size_t, _fp]),
+    "cp_online_adapt_tail_inputs": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, C.c_int64, _fp, _fp, C.c_size_t, _fp]),
+    "cp_online_multi_tail_inputs": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, _fp, C.c_int64, _fp, _fp,
+                                              C.c_size_t, _fp]),
+    "cp_online_multi_adapt_tail_inputs": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, C.c_int32, _fp,
+                                                    C.c_int64, _fp, _fp, C.c_size_t, _fp]),
+    "cp_online_finetune_state_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "cp_online_finetune_init": (C.c_int, [_fp, C.c_size_t, C.c_int32, _fp, _fp, _fp, _fp, C.c_int64, C.c_int32, C.c_int32, _fp]),
+    "cp_online_finetune_steps": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, C.c_int64, C.c_int32, C.c_int32, C.c_double,
+                                           C.c_double, C.c_double, C.c_double, C.c_int32, _fp, _fp]),
+    "cp_online_finetune_read": (C.c_int, [_fp, C.c_size_t, C.c_int64, C.c_int32, _fp, _fp, _fp, _fp, _fp]),
+    "cp_online_set_projection": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, _fp, _fp]),
+    "cp_online_adapt_set_projection": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, _fp, _fp]),
+    "cp_online_projection": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, _fp, _fp]),
+    "cp_online_adapt_projection": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, _fp, _fp]),
+    "cp_online_multi_projection": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, _fp, _fp, _fp]),
+    "cp_online_multi_adapt_projection": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, _fp, _fp, _fp]),
     "cp_online_gate_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "cp_online_gate_set_classes": (C.c_int, [_P(cp_online_gate_config), C.c_int32, _fp, C.c_size_t, C.c_int32, _P(C.c_int32),
                                              _P(C.c_float), C.c_int32, _fp]),

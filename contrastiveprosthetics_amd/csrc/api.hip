@@ -25,6 +25,7 @@
 #include "online_multi.cuh"
 #include "online_multi_adapt.cuh"
 #include "online_enroll.cuh"
+#include "online_finetune.cuh"
 #include "online_gate.cuh"
 #include "online_drive.cuh"
 #include "online_subsets.cuh"

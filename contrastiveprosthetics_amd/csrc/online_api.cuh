@@ -1,6 +1,6 @@
 // Host layer of the online decoders (include/cpnative.h, cp_online_*): workspace layout, argument checks, launch chains and
-// the extern "C" entries of the folded, adaptive, multi-stream and adaptive multi-stream decoders, class enrolment, the
-// command gate, the grasp drive, the gate sweep, the subset sweep and the electrode-map sweep.  Host code only; api.hip includes it behind its own helpers (fail, CK, CKL) and encoder_api.cuh's (align256, fcK),
+// the extern "C" entries of the folded, adaptive, multi-stream and adaptive multi-stream decoders, class enrolment, head
+// fine-tuning, the command gate, the grasp drive, the gate sweep, the subset sweep and the electrode-map sweep.  Host code only; api.hip includes it behind its own helpers (fail, CK, CKL) and encoder_api.cuh's (align256, fcK),
 // so the library stays one translation unit.  The four decoders share one workspace description (OlWS, ol_carve), one
 // parameter check, one set of front-end arguments, one folded chain and one unfolded weight copy; what an entry adds is its
 // name in the refusals and the kernels it launches.
@@ -924,22 +924,29 @@ extern "C" size_t cp_online_enroll_scratch_bytes(int64_t n_windows, int32_t dtyp
     return ole_carve(n_windows, dtype).total;
 }
 
-// The caller's windows through the encoder chunk by chunk, each chunk's z / |z| added to acc: the folded encoder as a push runs
-// it, or (adaptive) the unfolded one with the statistics frozen, the OLA_FROZEN pass of online_adapt_calibrate_t
+// One chunk of m <= 256 windows x through the decoder's own encoder: the folded encoder as a push runs it, or (adaptive) the
+// unfolded one with the statistics frozen, the OLA_FROZEN pass of online_adapt_calibrate_t.  fc7's output goes to rows 0..m-1
+// of h1 (rows of 512 in the compute dtype); fc1's, fc3's and fc5's pass through the same rows
+template <typename T>
+static int ole_encode_chunk(T t, bool adaptive, unsigned char* base, const OlWS& w, const float* x, int m, unsigned char* sc,
+                            const OleScratch& k, unsigned char* h1, hipStream_t st) {
+    auto layer = [&](const OlLayerArgs& la, auto conv) {
+        constexpr bool CONV = decltype(conv)::value;
+        hipLaunchKernelGGL((ole_layer_kernel<T, CONV>), CONV ? dim3(4, OL_C) : dim3(512 / 16), dim3(OL_THREADS), 0, st, la, m);
+        CKL(CONV ? "ole_layer_kernel<conv>" : "ole_layer_kernel<fc>");
+        return 0;
+    };
+    return adaptive ? ola_chain(t, base, w, x, m, m, OLA_FROZEN, sc + k.C1, sc + k.R2, sc + k.H0, h1, st)
+                    : ol_folded_chain(base, w, nullptr, x, sc + k.H0, h1, layer);
+}
+
+// The caller's windows through the encoder chunk by chunk, each chunk's z / |z| added to acc
 template <typename T>
 static int online_enroll_t(T t, bool adaptive, unsigned char* base, const OlWS& w, const float* x, int64_t N, const int32_t* slots,
                            int n_classes, double* acc, unsigned char* sc, const OleScratch& k, hipStream_t st) {
     for (int64_t r0 = 0; r0 < N; r0 += OL_MAXM) {
         const int m = (int)(N - r0 < OL_MAXM ? N - r0 : OL_MAXM);
-        auto layer = [&](const OlLayerArgs& la, auto conv) {
-            constexpr bool CONV = decltype(conv)::value;
-            hipLaunchKernelGGL((ole_layer_kernel<T, CONV>), CONV ? dim3(4, OL_C) : dim3(512 / 16), dim3(OL_THREADS), 0, st, la, m);
-            CKL(CONV ? "ole_layer_kernel<conv>" : "ole_layer_kernel<fc>");
-            return 0;
-        };
-        if (int e = adaptive ? ola_chain(t, base, w, x + r0 * OL_C, m, m, OLA_FROZEN, sc + k.C1, sc + k.R2, sc + k.H0, sc + k.H1, st)
-                             : ol_folded_chain(base, w, nullptr, x + r0 * OL_C, sc + k.H0, sc + k.H1, layer))
-            return e;
+        if (int e = ole_encode_chunk(t, adaptive, base, w, x + r0 * OL_C, m, sc, k, sc + k.H1, st)) return e;
         OleAccArgs a{};
         a.proj = ol_layer_args(base, w, OL_PROJ, nullptr, sc + k.H1, nullptr);
         a.slots = slots + r0; a.acc = acc; a.M = m; a.n_classes = n_classes;
@@ -1011,6 +1018,278 @@ extern "C" int cp_online_enroll_table(const double* acc, int32_t n_classes, cons
                        table);
     CKL("ole_table_kernel");
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// head fine-tuning (csrc/online_finetune.cuh): the tail inputs of a labelled recording, a caller-owned state with the masters
+// of the projection and the class rows, steps of two launches each, and the tail's projection written and read
+// ---------------------------------------------------------------------------------------
+static_assert(OLF_CHUNK == CP_ONLINE_FINETUNE_CHUNK && OLF_TRAIN_PROJ == CP_ONLINE_FINETUNE_PROJECTION &&
+              OLF_TRAIN_ROWS == CP_ONLINE_FINETUNE_ROWS, "fine-tuning constants");
+
+// The workspace checks of the entries that read or write the tail's weights.  The four forms lay their weights out at
+// different offsets, and an entry cannot see which form prepared a workspace: these entries take ws_bytes as the form's own
+// cp_online_*workspace_bytes and refuse any other size, so a folded entry on an adaptive workspace (or the reverse) is an error
+// and not a write into the wrong block.
+static int olf_check_single(const char* who, const cp_online_config* c, void* ws, size_t ws_bytes, bool adaptive, OlWS* out) {
+    if (int e = ol_check(c, ws, ws_bytes, adaptive, out)) return e;
+    if (ws_bytes != out->total)
+        return ol_fail(CP_ERR_ARG, who, adaptive ? "ws_bytes is not cp_online_adapt_workspace_bytes: not an adaptive workspace of this configuration"
+                                                 : "ws_bytes is not cp_online_workspace_bytes: not a folded workspace of this configuration");
+    return 0;
+}
+static int olf_check_multi(const char* who, const cp_online_config* c, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                           bool adaptive, OlWS* out) {
+    if (int e = olm_check(c, n_streams, max_rows, ws, ws_bytes, adaptive, out)) return e;
+    if (ws_bytes != out->total) return ol_fail(CP_ERR_ARG, who, "ws_bytes is not this form's workspace size for n_streams, max_rows and dtype");
+    return 0;
+}
+
+template <typename T>
+static int online_tail_inputs_t(T t, bool adaptive, unsigned char* base, const OlWS& w, const float* x, int64_t N, unsigned char* out,
+                                unsigned char* sc, const OleScratch& k, hipStream_t st) {
+    for (int64_t r0 = 0; r0 < N; r0 += OL_MAXM) {
+        const int m = (int)(N - r0 < OL_MAXM ? N - r0 : OL_MAXM);
+        if (int e = ole_encode_chunk(t, adaptive, base, w, x + r0 * OL_C, m, sc, k, out + (size_t)r0 * 512 * sizeof(T), st)) return e;
+    }
+    return 0;
+}
+
+// the four tail-input entries: check_ws(&w) as for ole_enroll.  n_windows == 0 is a valid empty call
+template <typename CheckWs>
+static int olf_tail_inputs(const char* who, const cp_online_config* cfg, CheckWs check_ws, bool adaptive, void* ws, const float* windows,
+                           int64_t n_windows, void* out, void* scratch, size_t scratch_bytes, void* stream) {
+    OlWS w;
+    if (int e = check_ws(&w)) return e;
+    if (n_windows < 0 || n_windows > (int64_t)1 << 24) return ol_fail(CP_ERR_ARG, who, "n_windows outside 0..2**24");
+    if (n_windows == 0) return 0;
+    if (!windows || !out || !scratch) return ol_fail(CP_ERR_ARG, who, "windows, out and scratch are required");
+    if ((uintptr_t)windows % 4 || (uintptr_t)out % 16 || (uintptr_t)scratch % 256) return ol_fail(CP_ERR_ARG, who, "misaligned input, out or scratch");
+    const OleScratch k = ole_carve(n_windows, cfg->dtype);
+    if (scratch_bytes < k.total) return ol_fail(CP_ERR_WORKSPACE, who, "scratch too small");
+    return ol_dispatch(cfg->dtype, [&](auto t) {
+        return online_tail_inputs_t(t, adaptive, (unsigned char*)ws, w, windows, n_windows, (unsigned char*)out, (unsigned char*)scratch, k,
+                                    (hipStream_t)stream);
+    });
+}
+
+extern "C" int cp_online_tail_inputs(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* windows, int64_t n_windows,
+                                     void* out, void* scratch, size_t scratch_bytes, void* stream) {
+    const char* who = "cp_online_tail_inputs";
+    return olf_tail_inputs(who, cfg, [&](OlWS* w) { return olf_check_single(who, cfg, ws, ws_bytes, false, w); }, false, ws, windows,
+                           n_windows, out, scratch, scratch_bytes, stream);
+}
+
+extern "C" int cp_online_adapt_tail_inputs(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* windows,
+                                           int64_t n_windows, void* out, void* scratch, size_t scratch_bytes, void* stream) {
+    const char* who = "cp_online_adapt_tail_inputs";
+    return olf_tail_inputs(who, cfg, [&](OlWS* w) { return olf_check_single(who, cfg, ws, ws_bytes, true, w); }, true, ws, windows,
+                           n_windows, out, scratch, scratch_bytes, stream);
+}
+
+extern "C" int cp_online_multi_tail_inputs(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                           const float* windows, int64_t n_windows, void* out, void* scratch, size_t scratch_bytes,
+                                           void* stream) {
+    const char* who = "cp_online_multi_tail_inputs";
+    return olf_tail_inputs(who, cfg, [&](OlWS* w) { return olf_check_multi(who, cfg, n_streams, max_rows, ws, ws_bytes, false, w); }, false,
+                           ws, windows, n_windows, out, scratch, scratch_bytes, stream);
+}
+
+extern "C" int cp_online_multi_adapt_tail_inputs(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
+                                                 size_t ws_bytes, int32_t index, const float* windows, int64_t n_windows, void* out,
+                                                 void* scratch, size_t scratch_bytes, void* stream) {
+    const char* who = "cp_online_multi_adapt_tail_inputs";
+    auto check = [&](OlWS* w) {
+        if (int e = olf_check_multi(who, cfg, n_streams, max_rows, ws, ws_bytes, true, w)) return e;
+        if (int e = ol_check_index(who, index, n_streams)) return e;
+        *w = ol_stream(*w, index);
+        return 0;
+    };
+    return olf_tail_inputs(who, cfg, check, true, ws, windows, n_windows, out, scratch, scratch_bytes, stream);
+}
+
+// the state of a fine-tuning run: OlfHead, the masters theta = (W, b, E), their initial values and Adam moments (f32, OLF_P
+// each), the copy of W in the compute dtype (sized for f32), the step's reduced gradient (float64), the slots and one slab per
+// chunk of OLF_CHUNK windows
+struct OlfState {
+    size_t head, theta, theta0, m, v, wT, grad, slots, slabs, total;
+};
+static OlfState olf_carve(int64_t n_windows) {
+    OlfState c{};
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t r = o; o = align256(o + bytes); return r; };
+    const size_t chunks = (size_t)((n_windows + OLF_CHUNK - 1) / OLF_CHUNK);
+    c.head = take(sizeof(OlfHead));
+    c.theta = take((size_t)OLF_P * 4);
+    c.theta0 = take((size_t)OLF_P * 4);
+    c.m = take((size_t)OLF_P * 4);
+    c.v = take((size_t)OLF_P * 4);
+    c.wT = take((size_t)OLF_W * 4);
+    c.grad = take((size_t)OLF_P * 8);
+    c.slots = take((size_t)n_windows * 4);
+    c.slabs = take(chunks * OLF_SLAB * 4);
+    c.total = o;
+    return c;
+}
+
+extern "C" size_t cp_online_finetune_state_bytes(int64_t n_windows, int32_t n_classes) {
+    (void)n_classes;                                         // the state holds 64 rows whatever K is
+    if (n_windows < 1) n_windows = 1;
+    return olf_carve(n_windows).total;
+}
+
+// what init, steps and read check alike
+static int olf_check_state(const char* who, void* state, size_t state_bytes, int64_t n_windows, int32_t n_classes, OlfState* out) {
+    if (!state) return ol_fail(CP_ERR_ARG, who, "state is required");
+    if ((uintptr_t)state % 256) return ol_fail(CP_ERR_ARG, who, "state not 256-byte aligned");
+    if (n_windows < 1 || n_windows > (int64_t)1 << 24) return ol_fail(CP_ERR_ARG, who, "n_windows outside 1..2**24");
+    if (n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return ol_fail(CP_ERR_ARG, who, "1..64 classes");
+    *out = olf_carve(n_windows);
+    if (state_bytes < out->total) return ol_fail(CP_ERR_ARG, who, "state too small");
+    return 0;
+}
+
+extern "C" int cp_online_finetune_init(void* state, size_t state_bytes, int32_t dtype, const float* W, const float* b, const float* E,
+                                       const int32_t* slots, int64_t n_windows, int32_t n_classes, int32_t balanced, void* stream) {
+    const char* who = "cp_online_finetune_init";
+    OlfState k;
+    if (int e = olf_check_state(who, state, state_bytes, n_windows, n_classes, &k)) return e;
+    if (dtype != CP_F32 && dtype != CP_BF16) return ol_fail(CP_ERR_ARG, who, "dtype must be CP_F32 or CP_BF16");
+    if (!W || !b || !E || !slots) return ol_fail(CP_ERR_ARG, who, "W, b, E and slots are required");
+    if ((uintptr_t)W % 4 || (uintptr_t)b % 4 || (uintptr_t)E % 4 || (uintptr_t)slots % 4) return ol_fail(CP_ERR_ARG, who, "misaligned input");
+    if (balanced != 0 && balanced != 1) return ol_fail(CP_ERR_ARG, who, "balanced must be 0 or 1");
+    unsigned char* s = (unsigned char*)state;
+    OlfInitArgs a{};
+    a.head = (OlfHead*)(s + k.head); a.W = W; a.b = b; a.E = E; a.slots_in = slots;
+    a.theta = (float*)(s + k.theta); a.theta0 = (float*)(s + k.theta0); a.m = (float*)(s + k.m); a.v = (float*)(s + k.v);
+    a.wT = s + k.wT; a.slots = (int32_t*)(s + k.slots); a.grad = (double*)(s + k.grad);
+    a.n = (int)n_windows; a.K = n_classes; a.balanced = balanced;
+    return ol_dispatch(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((olf_init_kernel<T>), dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
+        CKL("olf_init_kernel");
+        return 0;
+    });
+}
+
+extern "C" int cp_online_finetune_steps(const cp_online_config* cfg, void* state, size_t state_bytes, const void* u, int64_t n_windows,
+                                        int32_t n_classes, int32_t n_steps, double lr, double lr_rows, double scale, double anchor,
+                                        int32_t flags, double* loss_out, void* stream) {
+    const char* who = "cp_online_finetune_steps";
+    if (!cfg) return ol_fail(CP_ERR_ARG, who, "config is required");
+    if (cfg->dtype != CP_F32 && cfg->dtype != CP_BF16) return ol_fail(CP_ERR_ARG, who, "dtype must be CP_F32 or CP_BF16 (no 8-bit path)");
+    OlfState k;
+    if (int e = olf_check_state(who, state, state_bytes, n_windows, n_classes, &k)) return e;
+    if (n_steps < 0) return ol_fail(CP_ERR_ARG, who, "negative n_steps");
+    if (!std::isfinite(lr) || !std::isfinite(lr_rows) || lr < 0.0 || lr_rows < 0.0) return ol_fail(CP_ERR_ARG, who, "lr and lr_rows must be finite and >= 0");
+    if (!std::isfinite(scale) || !std::isfinite((double)(float)scale)) return ol_fail(CP_ERR_ARG, who, "scale must be finite");
+    if (!std::isfinite(anchor) || anchor < 0.0) return ol_fail(CP_ERR_ARG, who, "anchor must be finite and >= 0");
+    if (flags & ~(OLF_TRAIN_PROJ | OLF_TRAIN_ROWS)) return ol_fail(CP_ERR_ARG, who, "unknown flags");
+    if (!u) return ol_fail(CP_ERR_ARG, who, "u is required");
+    if ((uintptr_t)u % 16) return ol_fail(CP_ERR_ARG, who, "u not 16-byte aligned");
+    if (n_steps == 0) return 0;
+    if (!loss_out) return ol_fail(CP_ERR_ARG, who, "loss_out is required");
+    if ((uintptr_t)loss_out % 8) return ol_fail(CP_ERR_ARG, who, "misaligned loss_out");
+    unsigned char* s = (unsigned char*)state;
+    const int chunks = (int)((n_windows + OLF_CHUNK - 1) / OLF_CHUNK);
+    OlfStepArgs sa{};
+    sa.proj.act = u; sa.proj.w = s + k.wT; sa.proj.bias = (const float*)(s + k.theta) + OLF_W; sa.proj.K = 512; sa.proj.F = CP_D_E;
+    sa.head = (OlfHead*)(s + k.head); sa.E = (const float*)(s + k.theta) + OLF_B; sa.slots = (const int32_t*)(s + k.slots);
+    sa.slabs = (float*)(s + k.slabs); sa.N = (int)n_windows; sa.K = n_classes; sa.scale = (float)scale;
+    OlfUpdateArgs ua{};
+    ua.head = sa.head; ua.theta = (float*)(s + k.theta); ua.m = (float*)(s + k.m); ua.v = (float*)(s + k.v);
+    ua.theta0 = (const float*)(s + k.theta0); ua.wT = s + k.wT; ua.grad = (double*)(s + k.grad); ua.slabs = sa.slabs;
+    ua.chunks = chunks; ua.K = n_classes; ua.flags = flags; ua.lr = lr; ua.lr_rows = lr_rows; ua.anchor = anchor;
+    return ol_dispatch(cfg->dtype, [&](auto t) {
+        using T = decltype(t);
+        for (int i = 0; i < n_steps; ++i) {
+            hipLaunchKernelGGL((olf_step_kernel<T>), dim3(chunks), dim3(OL_THREADS), 0, (hipStream_t)stream, sa);
+            CKL("olf_step_kernel");
+            ua.loss = loss_out + i;
+            hipLaunchKernelGGL((olf_update_kernel<T>), dim3(OLF_P / OLF_UPDATE_THREADS + 1), dim3(OLF_UPDATE_THREADS), 0,
+                               (hipStream_t)stream, ua);
+            CKL("olf_update_kernel");
+        }
+        return 0;
+    });
+}
+
+extern "C" int cp_online_finetune_read(void* state, size_t state_bytes, int64_t n_windows, int32_t n_classes, float* W, float* b, float* E,
+                                       double* grad_out, void* stream) {
+    const char* who = "cp_online_finetune_read";
+    OlfState k;
+    if (int e = olf_check_state(who, state, state_bytes, n_windows, n_classes, &k)) return e;
+    if (!W || !b || !E) return ol_fail(CP_ERR_ARG, who, "W, b and E are required");
+    if ((uintptr_t)W % 4 || (uintptr_t)b % 4 || (uintptr_t)E % 4 || (uintptr_t)grad_out % 8) return ol_fail(CP_ERR_ARG, who, "misaligned output");
+    const unsigned char* s = (const unsigned char*)state;
+    const float* theta = (const float*)(s + k.theta);
+    hipStream_t st = (hipStream_t)stream;
+    CK(hipMemcpyAsync(W, theta, (size_t)OLF_W * 4, hipMemcpyDeviceToDevice, st));
+    CK(hipMemcpyAsync(b, theta + OLF_W, (size_t)CP_D_E * 4, hipMemcpyDeviceToDevice, st));
+    CK(hipMemcpyAsync(E, theta + OLF_B, (size_t)n_classes * CP_D_E * 4, hipMemcpyDeviceToDevice, st));
+    if (grad_out) CK(hipMemcpyAsync(grad_out, s + k.grad, (size_t)(OLF_B + n_classes * CP_D_E) * 8, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+// the tail's projection of a workspace whose view is w: written from f32 (set) or read back widened
+static int olf_projection(const char* who, const cp_online_config* cfg, void* ws, const OlWS& w, bool set, float* W, float* b, void* stream) {
+    if (!W || !b) return ol_fail(CP_ERR_ARG, who, "W and b are required");
+    if ((uintptr_t)W % 4 || (uintptr_t)b % 4) return ol_fail(CP_ERR_ARG, who, "misaligned W or b");
+    unsigned char* base = (unsigned char*)ws;
+    return ol_dispatch(cfg->dtype, [&](auto t) {
+        using T = decltype(t);
+        if (set) hipLaunchKernelGGL((olf_set_projection_kernel<T>), dim3(OLF_W / 256), dim3(256), 0, (hipStream_t)stream, (const float*)W,
+                                    (const float*)b, (T*)(base + w.pw), (float*)(base + w.pb));
+        else hipLaunchKernelGGL((olf_get_projection_kernel<T>), dim3(OLF_W / 256), dim3(256), 0, (hipStream_t)stream,
+                                (const T*)(base + w.pw), (const float*)(base + w.pb), W, b);
+        CKL(set ? "olf_set_projection_kernel" : "olf_get_projection_kernel");
+        return 0;
+    });
+}
+
+extern "C" int cp_online_set_projection(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* W, const float* b, void* stream) {
+    const char* who = "cp_online_set_projection";
+    OlWS w;
+    if (int e = olf_check_single(who, cfg, ws, ws_bytes, false, &w)) return e;
+    return olf_projection(who, cfg, ws, w, true, (float*)W, (float*)b, stream);
+}
+
+extern "C" int cp_online_adapt_set_projection(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* W, const float* b,
+                                              void* stream) {
+    const char* who = "cp_online_adapt_set_projection";
+    OlWS w;
+    if (int e = olf_check_single(who, cfg, ws, ws_bytes, true, &w)) return e;
+    return olf_projection(who, cfg, ws, w, true, (float*)W, (float*)b, stream);
+}
+
+extern "C" int cp_online_projection(const cp_online_config* cfg, void* ws, size_t ws_bytes, float* W, float* b, void* stream) {
+    const char* who = "cp_online_projection";
+    OlWS w;
+    if (int e = olf_check_single(who, cfg, ws, ws_bytes, false, &w)) return e;
+    return olf_projection(who, cfg, ws, w, false, W, b, stream);
+}
+
+extern "C" int cp_online_adapt_projection(const cp_online_config* cfg, void* ws, size_t ws_bytes, float* W, float* b, void* stream) {
+    const char* who = "cp_online_adapt_projection";
+    OlWS w;
+    if (int e = olf_check_single(who, cfg, ws, ws_bytes, true, &w)) return e;
+    return olf_projection(who, cfg, ws, w, false, W, b, stream);
+}
+
+extern "C" int cp_online_multi_projection(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                          float* W, float* b, void* stream) {
+    const char* who = "cp_online_multi_projection";
+    OlWS w;
+    if (int e = olf_check_multi(who, cfg, n_streams, max_rows, ws, ws_bytes, false, &w)) return e;
+    return olf_projection(who, cfg, ws, w, false, W, b, stream);
+}
+
+extern "C" int cp_online_multi_adapt_projection(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
+                                                size_t ws_bytes, float* W, float* b, void* stream) {
+    const char* who = "cp_online_multi_adapt_projection";
+    OlWS w;
+    if (int e = olf_check_multi(who, cfg, n_streams, max_rows, ws, ws_bytes, true, &w)) return e;
+    return olf_projection(who, cfg, ws, w, false, W, b, stream);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -42,6 +42,11 @@ map: it scores many candidates (`rotations`, `leave_one_out`) over a cued record
 (cp_online_*map_sweep, csrc/online_maps.cuh) exactly as fresh mapped decoders would decode it, and `pick_channel_map` takes
 the best.
 
+`finetune` is the gradient step of the personalisation chain (calibrate -> enroll -> fine-tune -> sweep the gate): the
+projection and the class rows behind the shared encoder are trained on the device with the model's own loss on the user's cued
+recording (cp_online_finetune_*, csrc/online_finetune.cuh; `finetune.finetune_reference` is the definition), and
+`projection` / `set_projection` / `reset_projection` store, restore and drop the user's head.
+
 The number of windows a push emits follows from sample counts alone (`windows_emitted`), so a push never waits for the device:
 its outputs are device tensors on torch's current stream.
 """
@@ -404,6 +409,72 @@ class _EnrollMixin(_OnStream):
         self._enroll_rec[key] = rec
         return out
 
+    # ------------------------------------------------------------------ head fine-tuning (cp_online_finetune_*)
+    _shared_projection = False                                 # the multi-stream decoders: one projection for all streams
+
+    def _finetune(self, key, raw, labels, steps, lr, lr_rows, scale, anchor, balanced, train_projection, train_rows, min_windows,
+                  return_loss):
+        """`finetune` of the online decoders; a decoder supplies _enroll_view, _tail_inputs_call, _projection_read and
+        _finetune_install.  Every refusal comes before the first device call."""
+        if train_projection and self._shared_projection:
+            raise ValueError("train_projection=True: the projection is shared by all streams of a multi-stream decoder, so a "
+                             "stream cannot train it; pass train_projection=False to train the stream's class rows")
+        ids, table, calibrated = self._enroll_view(key)
+        if ids is None:
+            raise _lib.CpNativeError("finetune() needs a class table: set_classes() first (its rows are where training starts)")
+        if not calibrated:
+            raise _lib.CpNativeError("an AdaBN model has no BatchNorm statistics: calibrate() first, then finetune()")
+        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or int(steps) < 0:
+            raise ValueError("steps must be an integer >= 0")
+        lr_rows = lr if lr_rows is None else lr_rows
+        for name, x in (("lr", lr), ("lr_rows", lr_rows), ("anchor", anchor)):
+            if not (np.isfinite(float(x)) and float(x) >= 0.0):
+                raise ValueError(f"{name} must be finite and >= 0")
+        if not np.isfinite(float(scale)):
+            raise ValueError("scale must be finite")
+        if int(min_windows) < 1:
+            raise ValueError("min_windows must be at least 1")
+        _check_raw(raw)
+        wl = window_labels(_sample_labels(labels, raw.shape[0]), self.phase)
+        keep = np.nonzero(wl >= 0)[0]
+        if keep.size == 0:
+            raise ValueError("the recording has no labelled window: a window needs 11 samples in a row of one non-negative label")
+        new = np.setdiff1d(np.unique(wl[keep]), ids)
+        if new.size:
+            raise ValueError(f"labels hold class ids the decoder does not have: {new.tolist()} (enroll(add=True) adds a class)")
+        slots = np.searchsorted(ids, wl[keep])
+        counts = np.bincount(slots, minlength=ids.size)
+        short = [int(i) for i, c in zip(ids, counts) if 0 < c < int(min_windows)]
+        if short:
+            raise ValueError(f"classes {short} have fewer than min_windows={int(min_windows)} windows")
+        out = {int(i): int(c) for i, c in zip(ids, counts)}
+        flags = (_lib.CP_ONLINE_FINETUNE_PROJECTION if train_projection else 0) | (_lib.CP_ONLINE_FINETUNE_ROWS if train_rows else 0)
+        if int(steps) == 0 or flags == 0:                      # nothing to train: the decoder stays as it is, bit for bit
+            return (out, torch.zeros(0, dtype=torch.float64, device=self.device)) if return_loss else out
+        # ---- everything is checked: from here on work is enqueued
+        lib, n, k = self.lib, int(keep.size), int(ids.size)
+        w = recording_windows(raw, self.mean_std, self._b, self._a, self.phase, channel_map=self._map_of(key))
+        w = w[torch.as_tensor(keep, device=self.device)].contiguous()
+        u = torch.empty(n, 512, dtype=torch.float32 if self.dtype == "f32" else torch.bfloat16, device=self.device)
+        scratch = torch.empty(lib.cp_online_enroll_scratch_bytes(n, self._cfg.dtype), dtype=torch.uint8, device=self.device)
+        self._tail_inputs_call(key, w.data_ptr(), n, u.data_ptr(), scratch.data_ptr(), scratch.numel())
+        W, b = self._projection_read(key)
+        E = table.to(torch.float32).contiguous()
+        slots_dev = torch.as_tensor(slots.astype(np.int32), device=self.device)
+        state = torch.empty(lib.cp_online_finetune_state_bytes(n, k), dtype=torch.uint8, device=self.device)
+        loss = torch.empty(int(steps), dtype=torch.float64, device=self.device)
+        _lib.check(lib.cp_online_finetune_init(state.data_ptr(), state.numel(), self._cfg.dtype, W.data_ptr(), b.data_ptr(), E.data_ptr(),
+                                               slots_dev.data_ptr(), n, k, int(bool(balanced)), self._stream()),
+                   "cp_online_finetune_init")
+        _lib.check(lib.cp_online_finetune_steps(C.byref(self._cfg), state.data_ptr(), state.numel(), u.data_ptr(), n, k, int(steps),
+                                                float(lr), float(lr_rows), float(scale), float(anchor), flags, loss.data_ptr(),
+                                                self._stream()), "cp_online_finetune_steps")
+        W2, b2, E2 = torch.empty_like(W), torch.empty_like(b), torch.empty_like(E)
+        _lib.check(lib.cp_online_finetune_read(state.data_ptr(), state.numel(), n, k, W2.data_ptr(), b2.data_ptr(), E2.data_ptr(), None,
+                                               self._stream()), "cp_online_finetune_read")
+        self._finetune_install(key, W2 if train_projection else None, b2, E2 if train_rows else None, ids)
+        return (out, loss) if return_loss else out
+
 
 class OnlineDecoder(_EnrollMixin):
     """Streaming decoder over a trained model (eval mode, stock BatchNorm with running statistics).
@@ -454,6 +525,7 @@ class OnlineDecoder(_EnrollMixin):
         self._enroll_rec = {}
         self._map = None                                   # electrode map: (src, fill) numpy, and its device copy
         self._map_dev = None
+        self._user_projection = None                       # a user's (W, b) f32 on the device: set_projection / finetune
         self.refresh()
         if classes is not None:
             self.set_classes(classes)
@@ -467,7 +539,8 @@ class OnlineDecoder(_EnrollMixin):
         """Fold the model's current weights and running statistics into the decoder (after an optimiser step or a
         load_state_dict; until then the decoder keeps the copy of the last fold).  A class table that comes from the model
         (one-hot ids, glove rows) is derived again too, which empties the vote ring.  The adaptive form re-reads weights, gamma
-        and beta and keeps its BatchNorm statistics."""
+        and beta and keeps its BatchNorm statistics.  A user's projection (`set_projection`, `finetune`) is kept: it is
+        installed again over the model's."""
         e = self.engine
         if self.adapt is None:
             _lib.check(self.lib.cp_online_prepare(C.byref(self._cfg), C.byref(e._p), C.byref(e._bn), C.c_float(1e-5), *self._ws(),
@@ -477,6 +550,8 @@ class OnlineDecoder(_EnrollMixin):
             _lib.check(self.lib.cp_online_adapt_prepare(C.byref(self._cfg), C.byref(e._p), bn, C.c_float(1e-5), C.c_double(self.adapt),
                                                         *self._ws(), self._stream()), "cp_online_adapt_prepare")
         self._prepared = True
+        if self._user_projection is not None:              # the user's head survives, as an enrolled table does
+            self._install_projection()
         if self.class_ids is not None and self._source[2] is None:
             classes, glove, _, ids = self._source
             self.set_classes(classes, glove=glove, ids=ids)
@@ -618,6 +693,82 @@ class OnlineDecoder(_EnrollMixin):
 
     def _enroll_install(self, key, table, ids):
         self.set_classes(table=table, ids=ids)
+
+    # ------------------------------------------------------------------ head fine-tuning
+    def finetune(self, raw: torch.Tensor, labels, *, steps: int = 100, lr: float = 1e-3, lr_rows: Optional[float] = None,
+                 scale: float = 1.0, anchor: float = 0.0, balanced: bool = True, train_projection: bool = True,
+                 train_rows: bool = True, min_windows: int = 25, return_loss: bool = False):
+        """The user's own head by gradient: the projection (16 x 512 + 16) and the class rows (K x 16) are trained with the
+        loss the model was trained with on the labelled windows of a cued recording; the shared encoder is not touched.
+        raw (n, 12) f32 on the GPU and labels (n,) as `enroll` takes them (a stream of its own, read through the electrode
+        map); a label that is not in `class_ids` is a ValueError, as is a class with 1..min_windows-1 windows (a class
+        without windows keeps its row's direction but for what the others' gradients do to it).
+
+        The decoder's own encoder embeds the windows once (the adaptive form with its current statistics frozen:
+        `bn_statistics()` does not move), then `steps` Adam steps run on the device without a host synchronisation
+        (include/cpnative.h, "head fine-tuning"; `finetune.finetune_reference` is the definition): rates lr (projection) and
+        lr_rows (rows; default lr); scale multiplies the cosines (1.0: the reference's loss); anchor pulls every trained
+        tensor back to where it started with anchor * (theta - theta_0); balanced weighs every class with windows alike,
+        else every window alike.  Training starts from `projection()` and the rows of `class_table()` and ends by installing
+        what it trained: `set_projection(W, b)` (train_projection) and `set_classes(table=E, ids=...)` (train_rows), so the
+        vote ring empties, `refresh()` keeps both, and `projection()` / `class_table()` return them for storage.  A tensor that
+        is not trained stays bit-identical; steps=0 changes nothing at all.
+
+        Returns {class id: labelled windows}; with return_loss=True also the loss of every step, (steps,) float64 on the GPU
+        (entry 0 is the cross-entropy of the logits a push returns for these windows).  A head belongs to the weights and
+        statistics it was trained with: fine-tune after `calibrate()`, and again after a `refresh()` that changed the model."""
+        return self._finetune(None, raw, labels, steps, lr, lr_rows, scale, anchor, balanced, bool(train_projection), bool(train_rows),
+                              min_windows, return_loss)
+
+    def _entry(self, name: str):
+        """the C entry cp_online_<name> of this decoder's form"""
+        full = ("cp_online_" if self.adapt is None else "cp_online_adapt_") + name
+        return getattr(self.lib, full), full
+
+    def _tail_inputs_call(self, key, *args):
+        fn, name = self._entry("tail_inputs")
+        _lib.check(fn(C.byref(self._cfg), *self._ws(), *args, self._stream()), name)
+
+    def _projection_read(self, key):
+        W = torch.empty(CP_D_E, 512, dtype=torch.float32, device=self.device)
+        b = torch.empty(CP_D_E, dtype=torch.float32, device=self.device)
+        fn, name = self._entry("projection")
+        _lib.check(fn(C.byref(self._cfg), *self._ws(), W.data_ptr(), b.data_ptr(), self._stream()), name)
+        return W, b
+
+    def _finetune_install(self, key, W, b, E, ids):
+        if W is not None:
+            self.set_projection(W, b)
+        if E is not None:
+            self.set_classes(table=E, ids=ids)
+
+    def projection(self):
+        """(W (16, 512) f32, b (16,) f32) on the GPU: the projection the tail multiplies by, widened from the compute dtype,
+        and its bias -- the model's (BatchNorm 9 folded in; the adaptive form: a zero bias) or the user's.  As
+        `set_projection(W, b)` takes them: a projection stored and put back decodes bit for bit as this one does."""
+        return self._projection_read(None)
+
+    def set_projection(self, W, b):
+        """Install a user's projection: W (16, 512) and b (16,) f32 (rounded to the compute dtype once, here).  `refresh()`
+        keeps it -- it belongs to the user, not to the model -- until `reset_projection()`.  Stream state, vote ring and
+        classes stay."""
+        W = torch.as_tensor(W, dtype=torch.float32).to(self.device).contiguous()
+        b = torch.as_tensor(b, dtype=torch.float32).to(self.device).contiguous()
+        if tuple(W.shape) != (CP_D_E, 512) or tuple(b.shape) != (CP_D_E,):
+            raise ValueError(f"W must be ({CP_D_E}, 512) and b ({CP_D_E},)")
+        self._user_projection = (W.clone(), b.clone())
+        self._install_projection()
+
+    def _install_projection(self):
+        W, b = self._user_projection
+        fn, name = self._entry("set_projection")
+        _lib.check(fn(C.byref(self._cfg), *self._ws(), W.data_ptr(), b.data_ptr(), self._stream()), name)
+
+    def reset_projection(self):
+        """Drop the user's projection: the model's is folded in again (a `refresh()` without it), and the decoder's outputs
+        are the model's bit for bit."""
+        self._user_projection = None
+        self.refresh()
 
     # ------------------------------------------------------------------ adaptive form
     def _need_adapt(self, what: str):
@@ -830,6 +981,31 @@ class _MultiStreamBase(_EnrollMixin):
     def _enroll_install(self, s, table, ids):
         self.set_classes(s, table=table, ids=ids)
 
+    _shared_projection = True
+
+    def finetune(self, stream: int, raw: torch.Tensor, labels, *, steps: int = 100, lr: float = 1e-3, lr_rows: Optional[float] = None,
+                 scale: float = 1.0, anchor: float = 0.0, balanced: bool = True, train_projection: bool = False,
+                 train_rows: bool = True, min_windows: int = 25, return_loss: bool = False):
+        """`OnlineDecoder.finetune` for one stream's class rows: its class table becomes, bit for bit, the one its own
+        `OnlineDecoder.finetune(train_projection=False)` gets from the same call; no other stream's table, state or statistics
+        change.  The projection is shared by all streams, so train_projection=True is a ValueError."""
+        return self._finetune(self._index(stream), raw, labels, steps, lr, lr_rows, scale, anchor, balanced, bool(train_projection),
+                              bool(train_rows), min_windows, return_loss)
+
+    def _tail_inputs_call(self, s, *args):
+        _lib.check(self.lib.cp_online_multi_tail_inputs(*self._args(), *args, self._stream()), "cp_online_multi_tail_inputs")
+
+    def _projection_read(self, s):
+        W = torch.empty(CP_D_E, 512, dtype=torch.float32, device=self.device)
+        b = torch.empty(CP_D_E, dtype=torch.float32, device=self.device)
+        name = self._ENTRY + "_projection"
+        _lib.check(getattr(self.lib, name)(*self._args(), W.data_ptr(), b.data_ptr(), self._stream()), name)
+        return W, b
+
+    def _finetune_install(self, s, W, b, E, ids):
+        if E is not None:
+            self.set_classes(s, table=E, ids=ids)
+
     def reset(self, streams=None):
         """Start new streams: filter, RMS history, sample count and vote ring of the listed streams (default: all) to zero;
         their classes, the weights and the other streams stay."""
@@ -1017,6 +1193,10 @@ class AdaptiveMultiStreamDecoder(_MultiStreamBase):
 
     def _enroll_call(self, s, *args):
         _lib.check(self.lib.cp_online_multi_adapt_enroll(*self._args(), s, *args, self._stream()), "cp_online_multi_adapt_enroll")
+
+    def _tail_inputs_call(self, s, *args):
+        _lib.check(self.lib.cp_online_multi_adapt_tail_inputs(*self._args(), s, *args, self._stream()),
+                   "cp_online_multi_adapt_tail_inputs")
 
     # ------------------------------------------------------------------ API
     def refresh(self):

@@ -719,6 +719,82 @@ int cp_online_multi_adapt_enroll(const cp_online_config* cfg, int32_t n_streams,
 int cp_online_enroll_table(const double* acc, int32_t n_classes, const float* prior, double mix, int32_t min_windows, float* table,
                            void* stream);
 
+/* ---- head fine-tuning: a user's projection and class rows by gradient, behind the shared encoder ---------------------------
+ * Calibration moves statistics and enrolment replaces class rows; neither uses a gradient.  Fine-tuning trains what lies
+ * behind the encoder -- the projection W (16,512) with its bias b (16) and the class rows E (K,16), 8,208 + 16 K numbers -- with
+ * the loss the model was trained with, on the labelled windows of one user's cued recording (windows and labels as for
+ * enrolment above).  T is the decoder's compute dtype (f32 or bf16).
+ * Tail input.  u_i (512 values in T) is what the decoder's tail multiplies by the projection for labelled window i: the fc7
+ * activation (folded forms), or the BN9-normalised fc7 output with the stream's current statistics frozen (adaptive forms;
+ * fine-tuning never moves statistics).  The tail-input entries compute it once, through the chain of the enrol entries in
+ * chunks of <= 256 windows with the last layer's output kept: out (n_windows,512) in T, 16-byte aligned.  A row's value does
+ * not depend on the chunk or call it falls in.
+ * Forward.  z_i = W_T u_i + b with W_T the f32 master W rounded to T, multiplied and summed as the tail of a push does;
+ * z^_i = z_i / sqrtf(sum z^2) in f32, so training sees the embedding a push will produce bit for bit; E^_c = E_c / |E_c| in
+ * f32 as cp_online_set_classes normalises; l_ic = scale (z^_i . E^_c) for c < K <= 64, the dot product summed as a push sums it.
+ * Loss.  L = sum_i w_i (-log softmax_c(l_i)[y_i]) with y_i the slot of window i.  balanced: w_i = 1 / (C n_{y_i}) with C the
+ * number of slots that have windows and n_c the windows of slot c; otherwise w_i = 1 / N; w_i is held in f32.  A window whose
+ * slot lies outside 0..K-1 has w_i = 0.  scale = 1 is the reference's loss (raw cosines, code/models.py:129).
+ * Gradients.  g_ic = w_i scale (p_ic - [c = y_i]);  dz^_i = sum_c g_ic E^_c;  dz_i = (dz^_i - z^_i (z^_i . dz^_i)) / |z_i|;
+ * dW = sum_i dz_i u_i^T;  db = sum_i dz_i;  dE^_c = sum_i g_ic z^_i;  dE_c = (dE^_c - E^_c (E^_c . dE^_c)) / |E_c|.  dz stays
+ * f32 in the dW product (it is not rounded to T) and u enters as stored.  With anchor = lambda >= 0 every tensor theta gets
+ * + lambda (theta - theta_0), theta_0 its value at cp_online_finetune_init.  The loss reported is L, without the anchor's
+ * lambda / 2 |theta - theta_0|^2.
+ * Update.  Adam as torch.optim.Adam states it (beta 0.9 / 0.999, eps 1e-8, bias-corrected, no weight decay, amsgrad off) on
+ * the f32 masters W, b, E with f32 moments, evaluated in float64 per element and rounded once each; rates lr (W, b) and
+ * lr_rows (E).  A tensor whose flag is not set is not touched, bit for bit.
+ * Order.  Rows are cut into chunks of CP_ONLINE_FINETUNE_CHUNK; chunk j's partial gradients (f32, rows in order) and its
+ * weighted loss (float64) are one slab; the update sums the slabs in chunk order in float64.  No floating-point atomics: the
+ * result of a step depends on the inputs and the chunk constant only, not on the grid, the device or how the steps were cut
+ * into calls.
+ * A step is two launches (olf_step_kernel, one workgroup per chunk; olf_update_kernel); n_steps steps are enqueued without a
+ * host synchronisation.  None of these entries allocates, synchronises or keeps state in the library; each validates on the
+ * host and returns CP_ERR_ARG (a short workspace or scratch: CP_ERR_WORKSPACE) before anything is enqueued.  The entries that
+ * read or write a workspace's weights take ws_bytes as exactly the form's own workspace size: the forms lay their weights out
+ * differently, so a folded entry on an adaptive workspace, or the reverse, is refused. */
+#define CP_ONLINE_FINETUNE_CHUNK 64         /* rows per slab */
+#define CP_ONLINE_FINETUNE_PROJECTION 1     /* flags of cp_online_finetune_steps: train W and b */
+#define CP_ONLINE_FINETUNE_ROWS 2           /* train E */
+/* windows (n_windows,12) f32 as a push makes them -> out (n_windows,512) in T.  scratch: cp_online_enroll_scratch_bytes.
+ * n_windows == 0 is a valid empty call. */
+int cp_online_tail_inputs(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* windows, int64_t n_windows, void* out,
+                          void* scratch, size_t scratch_bytes, void* stream);
+int cp_online_adapt_tail_inputs(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* windows, int64_t n_windows,
+                                void* out, void* scratch, size_t scratch_bytes, void* stream);
+int cp_online_multi_tail_inputs(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                const float* windows, int64_t n_windows, void* out, void* scratch, size_t scratch_bytes,
+                                void* stream);
+int cp_online_multi_adapt_tail_inputs(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                      int32_t index, const float* windows, int64_t n_windows, void* out, void* scratch,
+                                      size_t scratch_bytes, void* stream);
+/* bytes of the caller-owned state (256-byte aligned device memory) of a run over n_windows labelled windows */
+size_t cp_online_finetune_state_bytes(int64_t n_windows, int32_t n_classes);
+/* W (16,512), b (16), E (n_classes,16) f32 and slots (n_windows) int32 on the device -> masters, theta_0, zero moments, step 0,
+ * W_T in `dtype`, and the weights w_i.  One launch. */
+int cp_online_finetune_init(void* state, size_t state_bytes, int32_t dtype, const float* W, const float* b, const float* E,
+                            const int32_t* slots, int64_t n_windows, int32_t n_classes, int32_t balanced, void* stream);
+/* n_steps steps on u (n_windows,512) in T = cfg.dtype, the dtype of the init, 16-byte aligned; n_windows and n_classes as at
+ * the init.  loss_out (n_steps) float64 on the device: L of each step, before its update.  n_steps == 0 enqueues nothing. */
+int cp_online_finetune_steps(const cp_online_config* cfg, void* state, size_t state_bytes, const void* u, int64_t n_windows,
+                             int32_t n_classes, int32_t n_steps, double lr, double lr_rows, double scale, double anchor,
+                             int32_t flags, double* loss_out, void* stream);
+/* the masters: W (16,512), b (16), E (n_classes,16) f32; grad_out (NULL, or 8208 + 16 n_classes float64): the last step's
+ * reduced gradient dW, db, dE with the anchor term.  Device-to-device copies on `stream`. */
+int cp_online_finetune_read(void* state, size_t state_bytes, int64_t n_windows, int32_t n_classes, float* W, float* b, float* E,
+                            double* grad_out, void* stream);
+/* W (16,512), b (16) f32 on the device -> the tail's weights in T and its bias (one launch); and back, widened.  A workspace
+ * that never sees a set call is byte for byte what cp_online_*prepare left.  The multi-stream forms share one projection
+ * among their streams: it is read, not set. */
+int cp_online_set_projection(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* W, const float* b, void* stream);
+int cp_online_adapt_set_projection(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* W, const float* b,
+                                   void* stream);
+int cp_online_projection(const cp_online_config* cfg, void* ws, size_t ws_bytes, float* W, float* b, void* stream);
+int cp_online_adapt_projection(const cp_online_config* cfg, void* ws, size_t ws_bytes, float* W, float* b, void* stream);
+int cp_online_multi_projection(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes, float* W,
+                               float* b, void* stream);
+int cp_online_multi_adapt_projection(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                     float* W, float* b, void* stream);
+
 /* ---- grasp command gate: rejection, weighted vote and dwell behind the online decoders --------------------------------------
  * A decoder forces every window onto one of its K class rows.  The gate is a stage behind it that reads the logits a push emits
  * (cosines in [-1, 1]) and keeps one state machine per stream, so that the stream can answer "none of these", report how sure

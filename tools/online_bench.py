@@ -36,6 +36,10 @@ recording of 41 classes x 500 windows in f32 and bf16 against the way without it
 turn and pushed the recording in 256-window pushes, its pred and voted copied to the host and counted there (both must give
 the same counts); (b) a mapped against an unmapped push of 1 and 25 windows on OnlineDecoder and of 256 streams x 1 window
 on MultiStreamDecoder, alternating in the same run, with the run-to-run spread of the unmapped medians next to the difference.
+With --finetune head fine-tuning (OnlineDecoder.finetune, csrc/online_finetune.cuh) is measured: (a) at 41 classes x 500
+windows in f32 and bf16 the embedding pass, one step (median run of 100 steps), the bytes a step must move and the same step
+composed from torch ops on the same u; (c) on the synthetic people of --enroll the held-out accuracy of one-hot rows, enrolled
+rows and the fine-tuned head.
 Each push is timed from the host with a synchronisation behind it (the latency a control loop sees); kernels per push are
 counted with torch.profiler over a few pushes.  One JSON line per case, and a table with --out.
 
@@ -49,6 +53,7 @@ counted with torch.profiler over a few pushes.  One JSON line per case, and a ta
     python tools/online_bench.py --gate-sweep --iters 20 --out profiles/online_gate_sweep.txt
     python tools/online_bench.py --subset-sweep --iters 20 --out profiles/online_subset_sweep.txt
     python tools/online_bench.py --map-sweep --iters 5 --out profiles/online_map_sweep.txt
+    python tools/online_bench.py --finetune --iters 10 --out profiles/online_finetune.txt
 """
 import argparse
 import json
@@ -109,9 +114,13 @@ def main():
     ap.add_argument("--map-sweep", action="store_true", help="score_channel_maps against a reset / set_channel_map / push loop, and "
                     "a mapped against an unmapped push")
     ap.add_argument("--case-seconds", type=float, default=150.0, help="--gate-sweep: time limit of each timed case")
+    ap.add_argument("--finetune", action="store_true", help="head fine-tuning: embedding pass, step against torch ops, accuracy on a "
+                    "synthetic person")
     a = ap.parse_args()
     if a.enroll:
         return enroll_main(a)
+    if a.finetune:
+        return finetune_main(a)
     if a.gate_sweep:
         return gate_sweep_main(a)
     if a.subset_sweep:
@@ -327,6 +336,164 @@ def enroll_main(a):
                     "# against the offline windows on 60 s;  (c) accuracy on a held-out recording of a synthetic person the model was\n"
                     "# not trained on (class amplitude pattern x per-person channel gains; 400 training steps on nine other people),\n"
                     "# per window and voted over 25 windows\n")
+            for r in lines:
+                f.write(json.dumps(r) + "\n")
+
+
+def _torch_step(u, uf, st, slots, wi, scale, lr, lr_rows, t):
+    """one fine-tuning step composed from torch ops on the device, on the same u: the baseline of finetune_main.  st: masters
+    W, b, E and their moments (f32); the forward multiplies u by W rounded to u's dtype, dW takes dz in f32 and u widened."""
+    W, b, E = st["W"], st["b"], st["E"]
+    z = (u @ W.to(u.dtype).t()).float() + b
+    zl = z.norm(dim=1, keepdim=True)
+    zn = z / zl
+    el = E.norm(dim=1, keepdim=True)
+    en = E / el
+    l = scale * (zn @ en.t())
+    lse = torch.logsumexp(l, dim=1)
+    loss = (wi * (lse - l.gather(1, slots[:, None])[:, 0])).sum()
+    g = torch.softmax(l, dim=1)
+    g.scatter_add_(1, slots[:, None], torch.full_like(lse, -1.0)[:, None])
+    g *= (wi * scale)[:, None]
+    dzn = g @ en
+    dz = (dzn - zn * (zn * dzn).sum(1, keepdim=True)) / zl
+    den = g.t() @ zn
+    grads = dict(W=dz.t() @ uf, b=dz.sum(0), E=(den - en * (en * den).sum(1, keepdim=True)) / el)
+    bc1, bc2 = 1.0 - 0.9 ** t, 1.0 - 0.999 ** t
+    for k, rate in (("W", lr), ("b", lr), ("E", lr_rows)):
+        m, v = st["m" + k], st["v" + k]
+        m.mul_(0.9).add_(grads[k], alpha=0.1)
+        v.mul_(0.999).addcmul_(grads[k], grads[k], value=0.001)
+        st[k].addcdiv_(m, v.sqrt().div_(bc2 ** 0.5).add_(1e-8), value=-rate / bc1)
+    return loss
+
+
+def finetune_main(a):
+    """--finetune: (a) the embedding pass and the step of OnlineDecoder.finetune at 41 classes x 500 windows against the same
+    step composed from torch ops on the same u; (c) held-out accuracy of one-hot rows, enrolled rows and the fine-tuned head on
+    the synthetic people of --enroll."""
+    import ctypes as C
+    from contrastiveprosthetics_amd import _lib
+    from contrastiveprosthetics_amd.online import recording_windows, window_labels
+    torch.manual_seed(0)
+    rng = np.random.default_rng(0)
+    classes = list(range(41))
+    pattern = rng.uniform(0.4, 3.0, (41, 12))
+    people = np.exp(rng.normal(0.0, 0.35, (10, 12)))              # per-person channel gains; person 9 is never trained on
+    params = dict(d_e=16, lr_emg=1e-3, reg_emg=1e-5, dp_emg=0.0, lr_glove=1e-3, reg_glove=1e-6, dp_glove=0.0)
+    e = Engine(adabn=False, dtype="f32", device="cuda:0")
+    e.init_parameters(1)
+    raw0, _ = _cue_recording(rng, pattern, people[0], 30, classes)
+    ident = torch.stack([torch.zeros(12), torch.ones(12)]).cuda()
+    w0 = recording_windows(raw0, ident)
+    mean, std = w0.mean(0), w0.std(0)
+    lines = []
+
+    def out(r):
+        print(json.dumps(r), flush=True)
+        lines.append(r)
+
+    # (c) the people, the training and the two recordings of person 9 are those of --enroll, draw for draw
+    probe = OnlineDecoder(e, mean, std, classes=classes)
+    train = []
+    for p in range(9):
+        raw, lab = _cue_recording(rng, pattern, people[p], 40, classes)
+        w = recording_windows(raw, probe.mean_std, probe._b, probe._a, 0)
+        wl = window_labels(lab, 0)
+        train.append(torch.stack([w[torch.as_tensor(np.nonzero(wl == c)[0][:40]).cuda()] for c in classes]))
+    train = torch.stack(train)
+    labels = torch.arange(41).repeat(8).cuda()
+    for step in range(400):
+        pi = torch.randint(0, 9, (8,))
+        wi = torch.randint(0, 40, (8, 41))
+        x = torch.stack([train[pi[g], torch.arange(41), wi[g]] for g in range(8)]).reshape(-1, 12).contiguous()
+        z = e.encoder_forward(x, training=True)
+        e.head(z, labels, 1, want_grad=True)
+        e.encoder_backward(x)
+        e.adam_step(params)
+    torch.cuda.synchronize()
+    rawE, labE = _cue_recording(rng, pattern, people[9], 100, rng.permutation(41))
+    rawT, labT = _cue_recording(rng, pattern, people[9], 100, rng.permutation(41))
+    wlT = window_labels(labT, 0)
+    ok = wlT >= 0
+    tune = dict(steps=200, lr=1e-3, lr_rows=1e-2, scale=10.0)
+    for dtype in ("f32", "bf16"):
+        r = dict(part="c", dtype=dtype, windows=int(ok.sum()), **tune)
+        for name in ("onehot", "enrolled", "finetuned", "enrolled_finetuned"):
+            dec = OnlineDecoder(e, mean, std, classes=classes, dtype=dtype)
+            if name.startswith("enrolled"):
+                dec.enroll(rawE, labE)
+            if name.endswith("finetuned"):
+                dec.finetune(rawE, labE, **tune)
+            pred, voted = (t.cpu().numpy() for t in dec.push(rawT))
+            r["acc_" + name] = round(float((pred[ok] == wlT[ok]).mean()), 4)
+            r["acc_" + name + "_voted"] = round(float((voted[ok] == wlT[ok]).mean()), 4)
+        out(r)
+
+    # (a) 41 classes x 500 windows
+    raw, lab = _cue_recording(rng, pattern, people[9], 500, classes)
+    wl = window_labels(lab, 0)
+    keep = torch.as_tensor(np.nonzero(wl >= 0)[0]).cuda()
+    slots = torch.as_tensor(wl[wl >= 0].astype(np.int32)).cuda()
+    n, steps = int(keep.numel()), 100
+    st = torch.cuda.current_stream().cuda_stream
+    for dtype in ("f32", "bf16"):
+        dec = OnlineDecoder(e, mean, std, classes=classes, dtype=dtype)
+        lib = dec.lib
+        w = recording_windows(raw, dec.mean_std, dec._b, dec._a, 0)[keep].contiguous()
+        tdt = torch.float32 if dtype == "f32" else torch.bfloat16
+        u = torch.empty(n, 512, dtype=tdt, device="cuda")
+        scratch = torch.empty(lib.cp_online_enroll_scratch_bytes(n, dec._cfg.dtype), dtype=torch.uint8, device="cuda")
+        embed = lambda: dec._tail_inputs_call(None, w.data_ptr(), n, u.data_ptr(), scratch.data_ptr(), scratch.numel())
+        embed_ms = _wall(embed, a.iters)
+        W, b = dec.projection()
+        E = dec.class_table()[0]
+        state = torch.zeros(lib.cp_online_finetune_state_bytes(n, 41), dtype=torch.uint8, device="cuda")
+        loss = torch.empty(steps, dtype=torch.float64, device="cuda")
+
+        def init():
+            _lib.check(lib.cp_online_finetune_init(state.data_ptr(), state.numel(), dec._cfg.dtype, W.data_ptr(), b.data_ptr(), E.data_ptr(),
+                                                   slots.data_ptr(), n, 41, 1, st), "cp_online_finetune_init")
+
+        def run():
+            _lib.check(lib.cp_online_finetune_steps(C.byref(dec._cfg), state.data_ptr(), state.numel(), u.data_ptr(), n, 41, steps, 1e-3,
+                                                    1e-2, 10.0, 0.0, 3, loss.data_ptr(), st), "cp_online_finetune_steps")
+
+        init()
+        step_us = _wall(run, a.iters) * 1e3 / steps
+        init()
+        run()
+        torch.cuda.synchronize()
+        first, last = float(loss[0]), float(loss[-1])
+        counts = torch.bincount(slots.long(), minlength=41).float()
+        wi = (1.0 / (41 * counts))[slots.long()]
+        uf = u.float()
+        ts = {}
+
+        def torch_run():
+            ts.update(W=W.clone(), b=b.clone(), E=E.clone())
+            for k in ("W", "b", "E"):
+                ts["m" + k], ts["v" + k] = torch.zeros_like(ts[k]), torch.zeros_like(ts[k])
+            for t in range(1, steps + 1):
+                ts["loss"] = _torch_step(u, uf, ts, slots.long(), wi, 10.0, 1e-3, 1e-2, t)
+
+        torch_us = _wall(torch_run, max(2, a.iters // 2)) * 1e3 / steps
+        chunks = (n + _lib.CP_ONLINE_FINETUNE_CHUNK - 1) // _lib.CP_ONLINE_FINETUNE_CHUNK
+        slab_bytes = chunks * (8208 + 64 * 16 + 16) * 4
+        moved = n * 512 * u.element_size() + 2 * slab_bytes          # u read once, the slabs written and read
+        out(dict(part="a", dtype=dtype, windows=n, chunks=chunks, embed_ms=round(embed_ms, 3), step_us=round(step_us, 2),
+                 torch_step_us=round(torch_us, 2), ratio=round(torch_us / step_us, 2), bytes_per_step=moved,
+                 gb_per_s=round(moved / step_us / 1e3, 1), loss_first=round(first, 5), loss_last=round(last, 5),
+                 torch_loss_last=round(float(ts["loss"]), 5)))
+    if a.out:
+        dev = torch.cuda.get_device_name(0)
+        with open(a.out, "w") as f:
+            f.write(f"# tools/online_bench.py --finetune --iters {a.iters} on {dev}\n")
+            f.write("# wall time, host-synchronised, median.  (a) 41 classes x 500 windows: the embedding pass (cp_online_tail_inputs),\n"
+                    "# one step of cp_online_finetune_steps (median run of 100 steps / 100), the same step composed from torch ops on\n"
+                    "# the same u, and the bytes a step must move (u once, the slabs written and read);  (c) accuracy, per window and\n"
+                    "# voted over 25 windows, on a held-out recording of a synthetic person the model was not trained on (the\n"
+                    "# people, training and recordings of --enroll): one-hot rows, enrolled rows, the head fine-tuned from either\n")
             for r in lines:
                 f.write(json.dumps(r) + "\n")
 
