@@ -112,6 +112,17 @@ class cp_debug_fc_gemm_args(C.Structure):
                 ("stat_rows_out", C.POINTER(C.c_int32))]
 
 
+class cp_debug_conv_args(C.Structure):
+    """One launch sequence of the large-batch conv front end on caller buffers (include/cpnative.h): what cp_debug_conv takes."""
+    _fields_ = [("dtype", C.c_int32), ("kind", C.c_int32), ("n_windows", C.c_int64),
+                ("x", C.c_void_p), ("conv1_w", C.c_void_p), ("conv1_b", C.c_void_p), ("conv2_w", C.c_void_p), ("conv2_b", C.c_void_p),
+                ("stats1", C.c_void_p), ("gin", C.c_void_p), ("gin_exp", C.c_void_p), ("gcols", C.c_void_p), ("coef", C.c_void_p),
+                ("wc", C.c_void_p), ("out", C.c_void_p), ("partials", C.c_void_p), ("slabs", C.c_void_p), ("fold", C.c_void_p),
+                ("dw", C.c_void_p), ("db", C.c_void_p),
+                ("gcol_rows", C.c_int32), ("reserved0", C.c_int32),
+                ("rows_out", C.POINTER(C.c_int32)), ("gcol_rows_out", C.POINTER(C.c_int32))]
+
+
 CP_ONLINE_MAX_CLASSES, CP_ONLINE_MAX_VOTE, CP_ONLINE_MAX_WINDOWS, CP_ONLINE_STRIDE = 64, 256, 256, 20
 CP_ONLINE_MULTI_MAX_STREAMS, CP_ONLINE_MULTI_MAX_ROWS = 256, 65536
 CP_ONLINE_GATE_SCORES, CP_ONLINE_GATE_SWEEP_MAX_CONFIGS = 10, 65536
@@ -172,6 +183,7 @@ SYMBOLS = {
     "cp_debug_glove_head_grad": (C.c_int, [_P(cp_config), _fp, C.c_size_t, C.c_int64, _fp, _fp]),
     "cp_debug_gemm": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "cp_debug_fc_gemm": (C.c_int, [_P(cp_debug_fc_gemm_args), _fp]),
+    "cp_debug_conv": (C.c_int, [_P(cp_debug_conv_args), _fp]),
     "cp_online_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "cp_online_prepare": (C.c_int, [_P(cp_online_config), _P(cp_params), _P(cp_bn_buffers), C.c_float, _fp, C.c_size_t, _fp]),
     "cp_online_set_classes": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, _fp, C.c_int32, _fp]),

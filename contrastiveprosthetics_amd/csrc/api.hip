@@ -873,6 +873,101 @@ extern "C" int cp_debug_fc_gemm(const cp_debug_fc_gemm_args* args, void* stream)
     return debug_fc_gemm_t<float>(args, (hipStream_t)stream);
 }
 
+// One launch sequence of the large-batch conv front end on caller buffers, through the launch functions of the step
+// (csrc/encoder_api.cuh: their grid arithmetic, slab counts and pre-reduce rule), at any n_windows
+template <typename T>
+static int debug_conv_t(const cp_debug_conv_args* d, hipStream_t st) {
+    const ConvLaunch cl{st, d->n_windows, d->partials, d->slabs, d->fold, d->stats1};
+    cp_params p{}, g{};
+    p.conv1_w = const_cast<float*>(d->conv1_w); p.conv1_b = const_cast<float*>(d->conv1_b);
+    p.conv2_w = const_cast<float*>(d->conv2_w); p.conv2_b = const_cast<float*>(d->conv2_b);
+    T* wc_f = (T*)d->wc;
+    T* wc_d = wc_f + 64 * 192;
+    const bool g8 = d->gin_exp != nullptr;
+    ConvArgs ca{};
+    ca.x = d->x; ca.w1 = d->conv1_w; ca.b1 = d->conv1_b; ca.n_windows = d->n_windows;
+    int rows = 0, gcol_rows = 0;
+    if (d->kind != 0 && d->kind != 3) {
+        launch_prep_conv2<T>(d->conv2_w, wc_f, wc_d, st);
+        CKL("prep_conv2_kernel");
+    }
+    switch (d->kind) {
+    case 0:
+        if (int e = launch_conv1_stats<T>(cl, &p, d->x, nullptr, "conv1_stats_kernel", &rows)) return e;
+        break;
+    case 1:
+        ca.stats1 = d->stats1; ca.wc = wc_f; ca.bias2 = d->conv2_b; ca.out = d->out; ca.partials = d->partials;
+        if (int e = launch_conv2_fwd<T>(cl, ca, "conv2_strip_kernel<fwd>", &rows)) return e;
+        break;
+    case 2:
+        ca.wc = wc_d; ca.gin = d->gin; ca.out = d->out; ca.partials = d->partials;
+        if (int e = launch_conv2_dgrad<T>(cl, ca, &rows)) return e;
+        break;
+    case 3: {
+        // (as conv_backward_tail: the image holds the raw r1, stats1 is the finish kernel's)
+        const float* gcols = d->gcols;
+        gcol_rows = d->gcol_rows;
+        if (!gcols) {
+            if (int e = launch_conv2_gcols<T>(cl, (const T*)d->gin, &gcol_rows)) return e;
+            gcols = d->partials;
+        }
+        ca.gin = d->gin; ca.gin_exp = (const int*)d->gin_exp;
+        g.conv2_w = d->dw;
+        if (int e = conv2_wgrad<T>(cl, &p, &g, ca, false, g8, gcols, gcol_rows, nullptr, nullptr, &rows)) return e;
+        break;
+    }
+    default:
+        ca.wc = wc_d; ca.gin = d->gin; ca.gin_exp = (const int*)d->gin_exp; ca.coef = d->coef; ca.partials = d->partials;
+        if (int e = launch_conv2_dgrad_conv1<T>(cl, ca, false, g8, &rows)) return e;
+        g.conv1_w = d->dw; g.conv1_b = d->db;
+        if (int e = conv1_bwd_finalize(cl, rows, &g)) return e;
+        break;
+    }
+    if (d->rows_out) *d->rows_out = rows;
+    if (d->gcol_rows_out) *d->gcol_rows_out = gcol_rows;
+    return 0;
+}
+
+// everything a launcher would refuse, or a kernel would read or write out of bounds, before anything launches
+static int check_debug_conv(const cp_debug_conv_args* d) {
+    if (!d) return fail(CP_ERR_ARG, "cp_debug_conv args");
+    if (d->dtype != CP_F32 && d->dtype != CP_BF16) return fail(CP_ERR_ARG, "cp_debug_conv: dtype must be CP_F32 or CP_BF16");
+    if (d->kind < 0 || d->kind > 4) return fail(CP_ERR_ARG, "cp_debug_conv: kind must be 0..4");
+    if (d->n_windows <= 0) return fail(CP_ERR_ARG, "cp_debug_conv: n_windows must be positive");
+    const int k = d->kind;
+    if (!d->x || !d->conv1_w || !d->conv1_b) return fail(CP_ERR_ARG, "cp_debug_conv: x, conv1_w and conv1_b must not be NULL");
+    if (k != 0 && !d->conv2_w) return fail(CP_ERR_ARG, "cp_debug_conv: conv2_w must not be NULL");
+    if (k == 1 && !d->conv2_b) return fail(CP_ERR_ARG, "cp_debug_conv: the forward needs conv2_b");
+    if ((k == 1 || k == 3) && !d->stats1) return fail(CP_ERR_ARG, "cp_debug_conv: kinds 1 and 3 need stats1");
+    if (k >= 2 && !d->gin) return fail(CP_ERR_ARG, "cp_debug_conv: gin must not be NULL");
+    if (k == 4 && !d->coef) return fail(CP_ERR_ARG, "cp_debug_conv: kind 4 needs coef");
+    if (k != 0 && k != 3 && !d->wc) return fail(CP_ERR_ARG, "cp_debug_conv: wc must not be NULL");
+    if ((k == 1 || k == 2) && !d->out) return fail(CP_ERR_ARG, "cp_debug_conv: out must not be NULL");
+    if ((k != 3 || !d->gcols) && !d->partials) return fail(CP_ERR_ARG, "cp_debug_conv: partials must not be NULL");
+    if (k == 3 && !d->slabs) return fail(CP_ERR_ARG, "cp_debug_conv: kind 3 needs slabs");
+    if (k >= 3 && (!d->fold || !d->dw)) return fail(CP_ERR_ARG, "cp_debug_conv: kinds 3 and 4 need fold and dw");
+    if (k == 4 && !d->db) return fail(CP_ERR_ARG, "cp_debug_conv: kind 4 needs db");
+    if (k == 3 && d->gcols && d->gcol_rows <= 0) return fail(CP_ERR_ARG, "cp_debug_conv: gcol_rows must be positive with gcols");
+    if (d->gin_exp) {
+        if (k < 3 || d->dtype != CP_BF16) return fail(CP_ERR_ARG, "cp_debug_conv: an e5m2 gradient belongs to kinds 3 and 4 under CP_BF16");
+        if (k == 3 && !d->gcols) return fail(CP_ERR_ARG, "cp_debug_conv: an e5m2 gradient needs its column sums (gcols)");
+    }
+    // The conv kernels, colsum_kernel and reduce_rows_kernel index rows in 64 bits, so nothing here wraps at 2^32; the entry still
+    // stops where the step does (check_cfg): beyond that no caller of the step has ever run them
+    const uint64_t es = d->dtype == CP_F32 ? 4 : 2;
+    if ((uint64_t)d->n_windows * 768 * es >= 0xFFF00000ull) return fail(CP_ERR_ARG, "cp_debug_conv: n_windows * 768 * sizeof(T) must stay below 2^32 - 2^20");
+    if ((((uintptr_t)d->x | (uintptr_t)d->gin | (uintptr_t)d->gcols | (uintptr_t)d->wc | (uintptr_t)d->out | (uintptr_t)d->partials |
+          (uintptr_t)d->slabs | (uintptr_t)d->fold) & 15) != 0)
+        return fail(CP_ERR_ARG, "cp_debug_conv: x, gin, gcols, wc, out, partials, slabs and fold must be 16-byte aligned");
+    return 0;
+}
+
+extern "C" int cp_debug_conv(const cp_debug_conv_args* args, void* stream) {
+    if (int e = check_debug_conv(args)) return e;
+    if (args->dtype == CP_BF16) return debug_conv_t<bf16_t>(args, (hipStream_t)stream);
+    return debug_conv_t<float>(args, (hipStream_t)stream);
+}
+
 __global__ __launch_bounds__(256) void hog_kernel(long long ticks, float* sink) {
     __shared__ float pad[30 * 1024];                       // 120 KiB: no 64 KiB-stage GEMM block fits beside this one
     pad[threadIdx.x] = (float)threadIdx.x;

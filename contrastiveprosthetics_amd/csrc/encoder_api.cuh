@@ -279,6 +279,18 @@ static int sync_row(const cp_config* c, const float* pp, int nrows, int width, u
     return 0;
 }
 
+// what a launch of the conv front end reads of its call besides its ConvArgs.  The step fills it from its pass (Pass::conv()),
+// cp_debug_conv from caller buffers: both reach the conv kernels through the launch functions below, with their grid arithmetic
+struct ConvLaunch {
+    hipStream_t st;
+    int64_t N;                  // windows
+    float* partials;            // partial rows
+    float* slabs;               // conv2's weight-gradient slabs [S][64][192]; the REDUCE_SLICES folded ones go behind them
+    float* rows2;               // PreReduce's folded rows; conv2_wgrad_finish_kernel's rows [CONV2_FINISH_ROWS][2][64]
+    const float* stats1;        // BatchNorm1's table [4][64]
+    const float* pre(int& nrows, int W, int direct_rows) const { return PreReduce{partials, rows2, st}(nrows, W, direct_rows); }
+};
+
 // ---------------------------------------------------------------------------------------
 // one pass: what every function of the encoder's forward and backward pass reads of its call
 // ---------------------------------------------------------------------------------------
@@ -299,6 +311,7 @@ struct Pass {
     const float* shift(int l) const { return stats(l) + 3 * kLayerC[l]; }
     float* rows2() const { return (float*)(base + w.partials2); }
     const float* pre(int& nrows, int W, int direct_rows = FIN_DIRECT_ROWS) const { return PreReduce{partials, rows2(), st}(nrows, W, direct_rows); }
+    ConvLaunch conv() const { return ConvLaunch{st, N(), partials, slabs, rows2(), stats(0)}; }
 };
 
 // the dropout in front of `layer`'s consumer: threshold, key, 1 / (1 - p) and the graph-replay salt, for every argument struct that
@@ -365,15 +378,21 @@ static void launch_running_stats(const Pass& ctx, const FwdBN& f) {
     hipLaunchKernelGGL(bn_running_stats_kernel, dim3(CP_N_BN), dim3(512), 0, ctx.st, ra);
 }
 
+// conv2's weights in the compute dtype, in the forward's and the data gradient's layout (the caller checks the launch)
+template <typename T>
+static inline void launch_prep_conv2(const float* conv2_w, T* fwd, T* dgr, hipStream_t st) {
+    hipLaunchKernelGGL((prep_conv2_kernel<T>), dim3(48), dim3(256), 0, st, conv2_w, fwd, dgr);
+}
+
 // conv1, statistics only: r1 is never stored, its consumers recompute it from x (conv_kernels.cuh).  *rows = partial rows written;
 // acc (small-batch form): the fixed-point totals of BatchNorm1
 template <typename T>
-static int launch_conv1_stats(const Pass& ctx, const cp_params* p, const float* x, long long* acc, const char* what, int* rows) {
+static int launch_conv1_stats(const ConvLaunch& ctx, const cp_params* p, const float* x, long long* acc, const char* what, int* rows) {
     constexpr int RPP = 256 / (64 / DT<T>::EPC);                      // windows per block and pass
-    const int64_t need = (ctx.N() + RPP - 1) / RPP, passes = (need + 2047) / 2048;          // (caps 1024 / 512 measured: 23.6 / 23.8 us against 20.6)
+    const int64_t need = (ctx.N + RPP - 1) / RPP, passes = (need + 2047) / 2048;          // (caps 1024 / 512 measured: 23.6 / 23.8 us against 20.6)
     const int g = (int)((need + passes - 1) / passes);            // every block makes the same number of passes
     ProfScope ps(CP_K_CONV1_FWD, ctx.st);
-    hipLaunchKernelGGL((conv1_stats_kernel<T>), dim3(g), dim3(256), 0, ctx.st, x, p->conv1_w, p->conv1_b, ctx.partials, ctx.N() * 12, acc);
+    hipLaunchKernelGGL((conv1_stats_kernel<T>), dim3(g), dim3(256), 0, ctx.st, x, p->conv1_w, p->conv1_b, ctx.partials, ctx.N * 12, acc);
     CKL(what);
     *rows = g;
     return 0;
@@ -388,8 +407,8 @@ static ConvArgs conv2_fwd_args(const Pass& ctx, const cp_params* p, const float*
     return ca;
 }
 template <typename T>
-static int launch_conv2_fwd(const Pass& ctx, const ConvArgs& ca, const char* what, int* rows) {
-    const int g = conv_grid<T>(ctx.N());
+static int launch_conv2_fwd(const ConvLaunch& ctx, const ConvArgs& ca, const char* what, int* rows) {
+    const int g = conv_grid<T>(ctx.N);
     ProfScope ps(CP_K_CONV2_FWD, ctx.st);
     hipLaunchKernelGGL((conv2_strip_kernel<T, 0>), dim3(g), dim3(256), 0, ctx.st, ca);
     CKL(what);
@@ -409,7 +428,7 @@ static int encoder_forward_t(const cp_config* c, const cp_params* p, const cp_bn
     float* partials = ctx.partials;
     {
         ProfScope ps(CP_K_PREP, st);
-        hipLaunchKernelGGL((prep_conv2_kernel<T>), dim3(48), dim3(256), 0, st, p->conv2_w, (T*)(base + w.wc2_f), (T*)(base + w.wc2_d));
+        launch_prep_conv2<T>(p->conv2_w, (T*)(base + w.wc2_f), (T*)(base + w.wc2_d), st);
         CKL("prep_conv2_kernel");
         if (!batch_stats) {
             launch_running_stats(ctx, f);
@@ -438,7 +457,7 @@ static int encoder_forward_t(const cp_config* c, const cp_params* p, const cp_bn
     // conv1 (evaluation with running statistics needs nothing of it but its recomputation)
     if (batch_stats) {
         int g = 0;
-        if (int e = launch_conv1_stats<T>(ctx, p, x, nullptr, "conv1_stats_kernel", &g)) return e;
+        if (int e = launch_conv1_stats<T>(ctx.conv(), p, x, nullptr, "conv1_stats_kernel", &g)) return e;
         if (int e = bn_finalize(ctx, f, 0, g, (double)R12)) return e;
     }
     // conv2
@@ -446,7 +465,7 @@ static int encoder_forward_t(const cp_config* c, const cp_params* p, const cp_bn
         ConvArgs ca = conv2_fwd_args(ctx, p, x, batch_stats);
         ca.stats1 = ctx.stats(0); ca.out = ctx.act<T>(1);
         int g = 0;
-        if (int e = launch_conv2_fwd<T>(ctx, ca, "conv2_strip_kernel<fwd>", &g)) return e;
+        if (int e = launch_conv2_fwd<T>(ctx.conv(), ca, "conv2_strip_kernel<fwd>", &g)) return e;
         if (int e = bn_finalize(ctx, f, 1, g, (double)R12)) return e;
     }
     // fc1..fc7
@@ -533,7 +552,7 @@ static int encoder_forward_fp8(const cp_config* c, const cp_params* p, const cp_
     {
         ProfScope ps(CP_K_PREP, st);
         hipLaunchKernelGGL(fp8_update_scales_kernel, dim3(1), dim3(64), 0, st, fs, N);
-        hipLaunchKernelGGL((prep_conv2_kernel<T>), dim3(48), dim3(256), 0, st, p->conv2_w, (T*)(base + w.wc2_f), (T*)(base + w.wc2_d));
+        launch_prep_conv2<T>(p->conv2_w, (T*)(base + w.wc2_f), (T*)(base + w.wc2_d), st);
         if (!batch_stats) launch_running_stats(ctx, f);
         if (batch_stats && drop) {
             // the folds of the layers behind a dropout (fc5..fc7: their operand is the dropout OUTPUT, no BatchNorm affine to fold) need
@@ -549,7 +568,7 @@ static int encoder_forward_fp8(const cp_config* c, const cp_params* p, const cp_
     // conv1 (statistics only) and conv2 (output as e4m3)
     if (batch_stats) {
         int g = 0;
-        if (int e = launch_conv1_stats<T>(ctx, p, x, nullptr, "conv1_stats_kernel", &g)) return e;
+        if (int e = launch_conv1_stats<T>(ctx.conv(), p, x, nullptr, "conv1_stats_kernel", &g)) return e;
         if (int e = bn_finalize(ctx, f, 0, g, (double)R12)) return e;
     }
     {
@@ -557,7 +576,7 @@ static int encoder_forward_fp8(const cp_config* c, const cp_params* p, const cp_
         ca.stats1 = ctx.stats(0);
         ca.out8 = ctx.act8(1); ca.out_exp = &fs->e[F8_T_ACT + 1]; ca.out_amax = &fs->amax[F8_T_ACT + 1];
         int g = 0;
-        if (int e = launch_conv2_fwd<T>(ctx, ca, "conv2_strip_kernel<fwd, e4m3>", &g)) return e;
+        if (int e = launch_conv2_fwd<T>(ctx.conv(), ca, "conv2_strip_kernel<fwd, e4m3>", &g)) return e;
         if (int e = bn_finalize(ctx, f, 1, g, (double)R12)) return e;      // (its sums are of the bf16-rounded values in true units)
     }
     if (!batch_stats) {
@@ -673,11 +692,11 @@ static int encoder_forward_small_t(const cp_config* c, const cp_params* p, const
         return b;
     };
     int g = 0;
-    if (int e = launch_conv1_stats<T>(ctx, p, x, acc_of(0), "conv1 (small)", &g)) return e;
+    if (int e = launch_conv1_stats<T>(ctx.conv(), p, x, acc_of(0), "conv1 (small)", &g)) return e;
     {
         ConvArgs ca = conv2_fwd_args(ctx, p, x, true);
         ca.bn1 = bn_of(0); ca.acc_out = acc_of(1); ca.out = ctx.act<T>(1);
-        if (int e = launch_conv2_fwd<T>(ctx, ca, "conv2 (small)", &g)) return e;
+        if (int e = launch_conv2_fwd<T>(ctx.conv(), ca, "conv2 (small)", &g)) return e;
     }
     // fc1..fc7 and the projection: each launch turns its input's two fixed-point totals per column into scale / shift itself
     for (int i = 0; i < CP_N_FC; ++i) {
@@ -850,12 +869,12 @@ static inline void rotate_grads(B*& cur, B*& nxt, bool aux_on, int L, B* keep2, 
 // (rows2).  small: the small-batch kernel, which applies BatchNorm2 + ReLU backward while staging and leaves the bias-gradient rows in
 // gcols3 (the caller has filled those fields of ca); g8: `cur` holds e5m2 bytes.  gcols / gcol_rows: the column sums of the gradient
 template <typename T>
-static int conv2_wgrad(const Pass& ctx, const cp_params* p, cp_params* g, ConvArgs& ca, bool small, bool g8, const float* gcols, int gcol_rows,
-                       const float* gcols3, float* db2) {
+static int conv2_wgrad(const ConvLaunch& ctx, const cp_params* p, cp_params* g, ConvArgs& ca, bool small, bool g8, const float* gcols, int gcol_rows,
+                       const float* gcols3, float* db2, int* nslabs = nullptr) {
     const hipStream_t st = ctx.st;
     float* slabs = ctx.slabs;
     ProfScope ps(CP_K_CONV2_WGRAD, st);
-    const int64_t strips = (ctx.N() + CONV_WG_WPB - 1) / CONV_WG_WPB;
+    const int64_t strips = (ctx.N + CONV_WG_WPB - 1) / CONV_WG_WPB;
     const int64_t cap = (small || sizeof(T) == 2) ? 512 : 256;      // two blocks per CU (194 registers with the strip prefetch)
     const int S = (int)(strips < cap ? strips : cap);
     ca.partials = slabs;
@@ -879,17 +898,62 @@ static int conv2_wgrad(const Pass& ctx, const cp_params* p, cp_params* g, ConvAr
         ns = REDUCE_SLICES;
     }
     hipLaunchKernelGGL((conv2_wgrad_finish_kernel<T>), dim3(CONV2_FINISH_ROWS), dim3(256), 0, st, sl, ns, gcols, small ? S : gcol_rows, p->conv2_w,
-                       ctx.stats(0), g->conv2_w, ctx.rows2(), gcols3, db2);
+                       ctx.stats1, g->conv2_w, ctx.rows2, gcols3, db2);
     CKL(small ? "conv2_wgrad_finish_kernel<small>" : "conv2_wgrad_finish_kernel");
+    if (nslabs) *nslabs = S;
     return 0;
 }
 
 // conv1's gradients from the partial rows of conv2_dgrad_conv1_kernel
-static int conv1_bwd_finalize(const Pass& ctx, int rows, cp_params* g) {
+static int conv1_bwd_finalize(const ConvLaunch& ctx, int rows, cp_params* g) {
     ProfScope ps(CP_K_CONV1_BWD, ctx.st);
     const float* pp = ctx.pre(rows, 4 * 64, 2 * REDUCE_SLICES);
     hipLaunchKernelGGL(conv1_bwd_finalize_kernel, dim3(1), dim3(256), 0, ctx.st, pp, rows, g->conv1_w, g->conv1_b);
     CKL("conv1_bwd_finalize_kernel");
+    return 0;
+}
+
+// column sums of conv2's gradient per (position, channel), for a caller without fc1's bias-gradient rows: one pass over the tensor.
+// *rows = partial rows [768] written
+template <typename T>
+static int launch_conv2_gcols(const ConvLaunch& ctx, const T* cur, int* rows) {
+    constexpr int cpr = 768 / DT<T>::EPC, rpp = 256 / cpr;
+    int64_t gb = (ctx.N + rpp - 1) / rpp;
+    if (gb > 256) gb = 256;
+    ProfScope ps(CP_K_BN_BWD, ctx.st);
+    hipLaunchKernelGGL((colsum_kernel<T>), dim3((int)gb), dim3(256), (size_t)rpp * 768 * 4, ctx.st, cur, ctx.partials, ctx.N, 768, 768);
+    CKL("colsum_kernel(conv2 gradient)");
+    *rows = (int)gb;
+    return 0;
+}
+
+// conv2's data gradient on its own (the gradient tap's): ca.out = dL/d(BN1 output), *rows = partial rows [2][64] written
+template <typename T>
+static int launch_conv2_dgrad(const ConvLaunch& ctx, const ConvArgs& ca, int* rows) {
+    const int g = conv_grid<T>(ctx.N);
+    hipLaunchKernelGGL((conv2_strip_kernel<T, 1>), dim3(g), dim3(256), 0, ctx.st, ca);
+    CKL("conv2_strip_kernel<dgrad>");
+    *rows = g;
+    return 0;
+}
+
+// conv2's data gradient, BatchNorm1 + ReLU backward and conv1's gradients in one pass over the gradient: *rows = partial rows
+// [4][64] written.  small: BatchNorm1's backward finalised in the prologue; g8: ca.gin holds e5m2 bytes
+template <typename T>
+static int launch_conv2_dgrad_conv1(const ConvLaunch& ctx, const ConvArgs& ca, bool small, bool g8, int* rows) {
+    const int g = conv_grid<T>(ctx.N);
+    const hipStream_t st = ctx.st;
+    ProfScope ps(CP_K_CONV2_DGRAD, st);
+    if (small) {
+        hipLaunchKernelGGL((conv2_dgrad_conv1_kernel<T, false, true>), dim3(g), dim3(256), 0, st, ca);
+    } else if constexpr (sizeof(T) == 2) {
+        if (g8) hipLaunchKernelGGL((conv2_dgrad_conv1_kernel<T, true>), dim3(g), dim3(256), 0, st, ca);
+        else hipLaunchKernelGGL((conv2_dgrad_conv1_kernel<T>), dim3(g), dim3(256), 0, st, ca);
+    } else {
+        hipLaunchKernelGGL((conv2_dgrad_conv1_kernel<T>), dim3(g), dim3(256), 0, st, ca);
+    }
+    CKL(small ? "conv2_dgrad_conv1_kernel<small>" : "conv2_dgrad_conv1_kernel");
+    *rows = g;
     return 0;
 }
 
@@ -941,13 +1005,7 @@ static int conv_backward_tail(const cp_config* c, const cp_params* p, const floa
     // column sums of that gradient per (position, channel): `partials` still holds them as fc1's data-gradient launch wrote them
     // (gcol_rows rows of 768, its bias-gradient rows); a caller without such rows gets them from one pass over the tensor
     if (!small && gcol_rows <= 0) {
-        constexpr int cpr = 768 / D::EPC, rpp = 256 / cpr;
-        int64_t gb = (N + rpp - 1) / rpp;
-        if (gb > 256) gb = 256;
-        ProfScope ps(CP_K_BN_BWD, st);
-        hipLaunchKernelGGL((colsum_kernel<T>), dim3((int)gb), dim3(256), (size_t)rpp * 768 * 4, st, cur, partials, N, 768, 768);
-        CKL("colsum_kernel(conv2 gradient)");
-        gcol_rows = (int)gb;
+        if (int e = launch_conv2_gcols<T>(ctx.conv(), cur, &gcol_rows)) return e;
     }
     ConvArgs ca{};
     ca.x = x; ca.w1 = p->conv1_w; ca.b1 = p->conv1_b; ca.stats1 = nullptr; ca.gin = cur; ca.n_windows = N;
@@ -956,44 +1014,36 @@ static int conv_backward_tail(const cp_config* c, const cp_params* p, const floa
         float* gcols3 = (float*)(base + w.praw);
         ca.bn2_rows = partials; ca.bn2_nr = stat_rows; ca.r2 = ctx.act<T>(1); ca.stats2 = ctx.stats(1);
         ca.dgamma2 = g->bn_g[1]; ca.dbeta2 = g->bn_b[1]; ca.gcols3 = gcols3;
-        if (int e = conv2_wgrad<T>(ctx, p, g, ca, true, false, nullptr, 0, gcols3, g->conv2_b)) return e;
+        if (int e = conv2_wgrad<T>(ctx.conv(), p, g, ca, true, false, nullptr, 0, gcols3, g->conv2_b)) return e;
         if (int e = tap_gradient(c, 1, cur, N, 768, sizeof(T), st)) return e;
     } else {
         ca.gin_exp = g8 ? (const int*)&g8->e[F8_T_GRAD + 1] : nullptr;
-        if (int e = conv2_wgrad<T>(ctx, p, g, ca, false, g8 != nullptr, partials, gcol_rows, nullptr, nullptr)) return e;
+        if (int e = conv2_wgrad<T>(ctx.conv(), p, g, ca, false, g8 != nullptr, partials, gcol_rows, nullptr, nullptr)) return e;
         ProfScope ps(CP_K_BN_BWD, st);
         if (int e = bwd_finalize(ctx, g, ctx.rows2(), CONV2_FINISH_ROWS, (double)R12, 0, 64, 1, "bn_bwd_finalize_kernel(conv1)")) return e;
         ca.coef = ctx.coef;
     }
-    const int grid_d = conv_grid<T>(N);
+    int grid_d = 0;
     ca.wc = base + w.wc2_d;
     if (c->grad_tap) {
         // test aid: dL/d(BN1 output) is not a tensor of the step any more; the tap gets it from the stand-alone data-gradient kernel
         ca.out = nxt; ca.partials = partials;
         if (g8) ca.gin = (unsigned char*)c->grad_tap + (size_t)N * 768 * 2;          // (its bf16 expansion in tap slot 1)
-        hipLaunchKernelGGL((conv2_strip_kernel<T, 1>), dim3(grid_d), dim3(256), 0, st, ca);
+        if (int e = launch_conv2_dgrad<T>(ctx.conv(), ca, &grid_d)) return e;
         ca.gin = cur;
-        CKL("conv2_strip_kernel<dgrad> (gradient tap)");
         if (int e = tap_gradient(c, 0, nxt, N, 768, sizeof(T), st)) return e;         // dL/d(BN1 output), [w][c]
     }
     // ---- conv2's data gradient, BatchNorm1 + ReLU backward and conv1's gradients in one pass over cur ------------------
     {
-        ProfScope ps(CP_K_CONV2_DGRAD, st);
         ca.out = nullptr; ca.partials = partials;
         if (small) {
             // (BatchNorm1's backward is finalised in the kernel's prologue, from the finish launch's rows)
             ca.stats1 = ctx.stats(0); ca.rows1 = ctx.rows2(); ca.rows1_nr = CONV2_FINISH_ROWS;
             ca.dgamma1 = g->bn_g[0]; ca.dbeta1 = g->bn_b[0];
-            hipLaunchKernelGGL((conv2_dgrad_conv1_kernel<T, false, true>), dim3(grid_d), dim3(256), 0, st, ca);
-        } else if constexpr (sizeof(T) == 2) {
-            if (g8) hipLaunchKernelGGL((conv2_dgrad_conv1_kernel<T, true>), dim3(grid_d), dim3(256), 0, st, ca);
-            else hipLaunchKernelGGL((conv2_dgrad_conv1_kernel<T>), dim3(grid_d), dim3(256), 0, st, ca);
-        } else {
-            hipLaunchKernelGGL((conv2_dgrad_conv1_kernel<T>), dim3(grid_d), dim3(256), 0, st, ca);
         }
-        CKL(small ? "conv2_dgrad_conv1_kernel<small>" : "conv2_dgrad_conv1_kernel");
+        if (int e = launch_conv2_dgrad_conv1<T>(ctx.conv(), ca, small, g8 != nullptr, &grid_d)) return e;
     }
-    if (int e = conv1_bwd_finalize(ctx, grid_d, g)) return e;
+    if (int e = conv1_bwd_finalize(ctx.conv(), grid_d, g)) return e;
     if (aux) { if (int e = aux->join()) return e; }      // everything the second stream was given is part of this call
     return 0;
 }

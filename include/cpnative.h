@@ -502,6 +502,58 @@ typedef struct cp_debug_fc_gemm_args {
 } cp_debug_fc_gemm_args;
 int cp_debug_fc_gemm(const cp_debug_fc_gemm_args* args, void* stream);
 
+/* debug/test access (tests/test_gpu_conv_exact.py): every launch of the LARGE-batch conv front end on caller buffers, one step of
+ * the pass at a time, at any n_windows (also below the 2,625 windows from which the step dispatches these kernels).  The kernels are
+ * reached through the launch functions of the step (csrc/encoder_api.cuh): its grids, slab counts and pre-reduce rule.  T = float
+ * (CP_F32) or bf16 (CP_BF16); rows = n_windows * 12, position-major [window][position][channel].
+ *   kind 0   conv1_stats_kernel<T>: partials[g][2][64] = sum and sum of squares of r1 = round_T(relu(conv1(x))); *rows_out = g
+ *   kind 1   prep_conv2_kernel<T>, conv2_strip_kernel<T, 0>: out[rows][64] = round_T(relu(conv2(s r1 + t) + conv2_b)) with
+ *            s = stats1[2][.], t = stats1[3][.] (rows 0 and 1 of stats1 are not read); partials[grid][2][64] = sum and sum of
+ *            squares of out as stored; *rows_out = grid
+ *   kind 2   prep_conv2_kernel<T>, conv2_strip_kernel<T, 1>: out[rows][64] = round_T(conv2's data gradient of gin[rows][64]);
+ *            partials[grid][2][64] = sum of out and of out * r1; *rows_out = grid
+ *   kind 3   (colsum_kernel<T> -> partials[<= 256][768] when gcols is NULL,) conv2_wgrad_kernel<T> (gin_exp: <T, true>) -> slabs[S][64][192]
+ *            = the raw product gin^T r1 of the strips s, s + S, ..; reduce_rows_kernel when S > 64 -> 32 folded slabs BEHIND slab S - 1;
+ *            conv2_wgrad_finish_kernel<T> -> dw = dW2 (64,64,3,3), fold = rows2[64][2][64] (BatchNorm1's backward sums per output
+ *            channel).  stats1 rows 2 and 3 are read.  *rows_out = S, *gcol_rows_out = rows of column sums the finish kernel read
+ *   kind 4   prep_conv2_kernel<T>, conv2_dgrad_conv1_kernel<T> (gin_exp: <T, true>) -> partials[grid][4][64] (dW1 tap 0..2, db1) with
+ *            gy = r1 > 0 ? ca g_v1 + cb r1 + cz : 0, ca / cb / cz = coef[0..2][.]; reduce_rows_kernel when grid > 64 -> fold[32][4][64];
+ *            conv1_bwd_finalize_kernel -> dw = dW1 (64,1,3,3), db = db1[64].  *rows_out = grid
+ * wc: scratch of 2 * 64 * 192 T that prep_conv2_kernel fills (kinds 1, 2, 4).  gin_exp (device int32, kinds 3 and 4 under CP_BF16):
+ * gin holds e5m2 bytes, stored = value * 2^*gin_exp.  Every scratch region is the caller's, so guards behind the rows and slabs
+ * a launch reports can be inspected.  rows_out / gcol_rows_out: host, may be NULL.
+ * Checked before anything launches, CP_ERR_ARG: a NULL pointer the kind reads or writes, n_windows <= 0, an unknown dtype or kind,
+ * gin_exp outside kinds 3 / 4 or CP_BF16, or in kind 3 without gcols (the step refuses that too), gcols with gcol_rows <= 0,
+ * x / gin / gcols / wc / out / partials / slabs / fold not 16-byte aligned, n_windows * 768 * sizeof(T) >= 2^32 - 2^20 (the conv
+ * kernels index in 64 bits; the bound is the step's, beyond which nothing has run them). */
+typedef struct cp_debug_conv_args {
+    int32_t dtype;             /* CP_F32 | CP_BF16 */
+    int32_t kind;              /* 0..4 */
+    int64_t n_windows;
+    const float* x;            /* [n_windows][12] */
+    const float* conv1_w;      /* (64,1,3,3) */
+    const float* conv1_b;      /* [64] */
+    const float* conv2_w;      /* (64,64,3,3), kinds 1..4 */
+    const float* conv2_b;      /* [64], kind 1 */
+    const float* stats1;       /* [4][64], kinds 1 and 3 */
+    const void* gin;           /* [n_windows * 12][64] T or e5m2 bytes, kinds 2..4 */
+    const int32_t* gin_exp;    /* device, or NULL */
+    const float* gcols;        /* [gcol_rows][768] or NULL, kind 3 */
+    const float* coef;         /* [3][64], kind 4 */
+    void* wc;
+    void* out;
+    float* partials;
+    float* slabs;
+    float* fold;
+    float* dw;
+    float* db;
+    int32_t gcol_rows;
+    int32_t reserved0;
+    int32_t* rows_out;
+    int32_t* gcol_rows_out;
+} cp_debug_conv_args;
+int cp_debug_conv(const cp_debug_conv_args* args, void* stream);
+
 /* BN statistics of `layer` as computed by the last forward: out[4][C] = mean, invstd, scale, shift */
 int cp_debug_bn_stats(const cp_config* cfg, void* ws, size_t ws_bytes, int32_t layer, float* out,
                       void* stream);

@@ -251,6 +251,61 @@ def test_debug_fc_gemm_refuses_what_a_launcher_would_before_it_launches(lib):
         assert rc == 10001 and b"cp_debug_gemm args" in lib.cp_last_error(), (kw, rc, lib.cp_last_error())
 
 
+def test_debug_conv_refuses_what_a_launcher_would_before_it_launches(lib):
+    """cp_debug_conv checks its arguments on the host, before any launch: CP_ERR_ARG with a message that names the entry (every
+    pointer is a dummy address that is never dereferenced; each case differs from a valid call of its kind in the one field under
+    test.  That the valid calls are accepted is shown on the GPU: tests/test_gpu_conv_exact.py).  The ctypes struct follows the
+    header field by field."""
+    from contrastiveprosthetics_amd import _lib
+    hdr = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    body = hdr[hdr.index("typedef struct cp_debug_conv_args {"):hdr.index("} cp_debug_conv_args;")]
+    assert re.findall(r"\b(\w+)\s*;", body) == [f[0] for f in _lib.cp_debug_conv_args._fields_]
+    assert ctypes.sizeof(_lib.cp_debug_conv_args) == 8 + 8 + 17 * 8 + 2 * 4 + 2 * 8
+    ok = 0x100000
+    rows, grows = ctypes.c_int32(-7), ctypes.c_int32(-9)
+    pointers = ("x", "conv1_w", "conv1_b", "conv2_w", "conv2_b", "stats1", "gin", "coef", "wc", "out", "partials", "slabs", "fold", "dw", "db")
+
+    def call(**kw):
+        d = _lib.cp_debug_conv_args()
+        d.dtype, d.kind, d.n_windows = 1, 0, 1000
+        for name in pointers:
+            setattr(d, name, ok)
+        d.rows_out, d.gcol_rows_out = ctypes.pointer(rows), ctypes.pointer(grows)
+        for k, v in kw.items():
+            setattr(d, k, v)
+        rc = lib.cp_debug_conv(ctypes.byref(d), None)
+        return rc, lib.cp_last_error()
+
+    e5 = dict(gin_exp=ok, gcols=ok, gcol_rows=3)
+    cases = [("n_windows = 0", dict(n_windows=0)), ("n_windows < 0", dict(n_windows=-41)),
+             ("dtype 2", dict(dtype=2)), ("dtype -1", dict(dtype=-1)), ("kind 5", dict(kind=5)), ("kind -1", dict(kind=-1))]
+    # every pointer a kind reads or writes
+    needs = {0: ("x", "conv1_w", "conv1_b", "partials"),
+             1: ("x", "conv1_w", "conv1_b", "conv2_w", "conv2_b", "stats1", "wc", "out", "partials"),
+             2: ("x", "conv1_w", "conv1_b", "conv2_w", "gin", "wc", "out", "partials"),
+             3: ("x", "conv1_w", "conv1_b", "conv2_w", "stats1", "gin", "partials", "slabs", "fold", "dw"),
+             4: ("x", "conv1_w", "conv1_b", "conv2_w", "gin", "coef", "wc", "partials", "fold", "dw", "db")}
+    for kind, names in needs.items():
+        cases += [("kind %d without %s" % (kind, name), {"kind": kind, name: None}) for name in names]
+    cases += [("kind 3 with gcols: slabs", dict(kind=3, gcols=ok, gcol_rows=3, slabs=None)),
+              ("gcols without rows", dict(kind=3, gcols=ok, gcol_rows=0)), ("gcols with -1 rows", dict(kind=3, gcols=ok, gcol_rows=-1)),
+              ("e5m2 in f32, kind 3", dict(e5, kind=3, dtype=0)), ("e5m2 in f32, kind 4", dict(kind=4, gin_exp=ok, dtype=0)),
+              ("e5m2 without gcols", dict(kind=3, gin_exp=ok)),
+              ("e5m2 in kind 0", dict(kind=0, gin_exp=ok)), ("e5m2 in kind 1", dict(kind=1, gin_exp=ok)), ("e5m2 in kind 2", dict(kind=2, gin_exp=ok)),
+              ("2^32 bytes, bf16", dict(n_windows=2796203)), ("2^32 bytes, f32", dict(dtype=0, n_windows=1398102)),
+              ("x + 8", dict(x=ok + 8)), ("gin + 8", dict(kind=2, gin=ok + 8)), ("out + 4", dict(kind=1, out=ok + 4)),
+              ("wc + 2", dict(kind=4, wc=ok + 2)), ("gcols + 4", dict(kind=3, gcols=ok + 4, gcol_rows=3)),
+              ("partials + 4", dict(partials=ok + 4)), ("slabs + 8", dict(kind=3, slabs=ok + 8)), ("fold + 4", dict(kind=4, fold=ok + 4))]
+    for what, kw in cases:
+        rc, msg = call(**kw)
+        assert rc == 10001 and msg.startswith(b"cp_debug_conv"), (what, rc, msg)
+        assert rows.value == -7 and grows.value == -9, what
+    for what, says in (("kind 5", b"kind"), ("dtype 2", b"dtype"), ("e5m2 without gcols", b"gcols"), ("2^32 bytes, bf16", b"2^32"),
+                       ("x + 8", b"aligned"), ("n_windows = 0", b"n_windows")):
+        assert says in call(**dict(cases)[what])[1], what
+    assert lib.cp_debug_conv(None, None) == 10001
+
+
 def test_backward_refuses_a_short_gradient_tap_before_it_launches(lib):
     """cp_config.grad_tap: cp_encoder_backward checks the whole buffer once, before its first launch -- 9 slots of n_windows x 768
     elements on the large-batch paths (CP_FP8: bf16 elements), 11 on the small-batch path (slot 9: fc1's data gradient before conv2's
