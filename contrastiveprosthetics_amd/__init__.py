@@ -21,4 +21,7 @@ def __getattr__(name):
     if name == "finetune_reference":
         from .finetune import finetune_reference
         return finetune_reference
+    if name in ("realign_cues", "realign_reference", "activity_profile", "activity_reference", "cue_segments", "sample_labels"):
+        from . import realign
+        return getattr(realign, name)
     raise AttributeError(name)

@@ -88,6 +88,11 @@ class cp_online_drive_config(C.Structure):
                 ("bad_after", C.c_int32), ("good_after", C.c_int32)]
 
 
+class cp_online_realign_config(C.Structure):
+    _fields_ = [("max_lag", C.c_int32), ("max_lead", C.c_int32), ("min_len", C.c_int32), ("min_rest", C.c_int32),
+                ("context", C.c_int32), ("min_contrast", C.c_int32), ("guard", C.c_int32)]
+
+
 class cp_augment(C.Structure):
     """Settings of one cp_gather_groups_aug launch (include/cpnative.h)."""
     _fields_ = [("seed", C.c_uint32), ("salt", C.c_uint32), ("salt_state_lo", C.c_uint32), ("salt_state_hi", C.c_uint32),
@@ -130,6 +135,7 @@ CP_ONLINE_SUBSET_SCORES, CP_ONLINE_SUBSET_SWEEP_MAX_SUBSETS = 7, 1048576
 CP_ONLINE_DRIVE_ONE, CP_ONLINE_DRIVE_MAX_SMOOTH = 4096, 256
 CP_ONLINE_MAP_SCORES, CP_ONLINE_MAP_SWEEP_MAX_MAPS = 3, 65536
 CP_ONLINE_FINETUNE_CHUNK, CP_ONLINE_FINETUNE_PROJECTION, CP_ONLINE_FINETUNE_ROWS = 64, 1, 2
+CP_ONLINE_REALIGN_MAX_ACTIVITY, CP_ONLINE_REALIGN_MAX_REGION = 4095, 4096
 
 # what the four map sweep entries take behind their workspace: rms, n_windows, mean_std, map_src, map_fill, n_maps, n_classes,
 # expected_slot, chunk_rows, scratch, scratch_bytes, pred, voted, scores, class_hits, stream
@@ -279,6 +285,8 @@ SYMBOLS = {
     "cp_online_multi_map_sweep": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, C.c_int32] + _MAP_SWEEP_TAIL),
     "cp_online_multi_adapt_map_sweep": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, C.c_int32]
                                         + _MAP_SWEEP_TAIL),
+    "cp_online_realign_activity": (C.c_int, [_fp, C.c_int32, C.c_int64, _P(C.c_float), _P(C.c_float), _fp, _fp]),
+    "cp_online_realign": (C.c_int, [_fp, _fp, C.c_int64, _fp, C.c_int32, _P(cp_online_realign_config), _fp, _fp, _fp, _fp]),
 }
 
 KERNEL_KINDS = ["gather", "prep", "conv1_fwd", "bn_finalize", "conv2_fwd", "fold", "fc_fwd", "dropout", "proj_fwd",

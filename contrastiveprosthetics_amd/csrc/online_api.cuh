@@ -1,6 +1,6 @@
 // Host layer of the online decoders (include/cpnative.h, cp_online_*): workspace layout, argument checks, launch chains and
 // the extern "C" entries of the folded, adaptive, multi-stream and adaptive multi-stream decoders, class enrolment, head
-// fine-tuning, the command gate, the grasp drive, the gate sweep, the subset sweep and the electrode-map sweep.  Host code only; api.hip includes it behind its own helpers (fail, CK, CKL) and encoder_api.cuh's (align256, fcK),
+// fine-tuning, the command gate, the grasp drive, the gate sweep, the subset sweep, the electrode-map sweep and cue realignment.  Host code only; api.hip includes it behind its own helpers (fail, CK, CKL) and encoder_api.cuh's (align256, fcK),
 // so the library stays one translation unit.  The four decoders share one workspace description (OlWS, ol_carve), one
 // parameter check, one set of front-end arguments, one folded chain and one unfolded weight copy; what an entry adds is its
 // name in the refusals and the kernels it launches.
@@ -1726,4 +1726,70 @@ extern "C" int cp_online_multi_adapt_map_sweep(const cp_online_config* cfg, int3
                        pred, voted, scores, class_hits};
     return olmap_sweep(who, cfg, [&](OlWS* w) { return olam_check_stream(who, cfg, n_streams, max_rows, ws, ws_bytes, index, w); }, true,
                        ws, a, stream);
+}
+
+// ---------------------------------------------------------------------------------------
+// cue realignment (csrc/online_realign.cuh): a window's activity from the normalised windows, and per cued segment the onset and
+// offset of the movement as the activity shows them.  No workspace: everything is the caller's
+// ---------------------------------------------------------------------------------------
+static_assert(OR_MAXREGION == CP_ONLINE_REALIGN_MAX_REGION && OR_MAXACT == CP_ONLINE_REALIGN_MAX_ACTIVITY && OR_C == CP_EMG_DIM,
+              "realign limits");
+static_assert(sizeof(OrConfig) == sizeof(cp_online_realign_config), "realign config");
+
+extern "C" int cp_online_realign_activity(const float* windows, int32_t ldw, int64_t n_rows, const float* base, const float* gain,
+                                          int32_t* activity, void* stream) {
+    const char* who = "cp_online_realign_activity";
+    if (n_rows < 1 || n_rows > INT32_MAX) return ol_fail(CP_ERR_ARG, who, "n_rows outside 1..2^31-1");
+    if (ldw < CP_EMG_DIM) return ol_fail(CP_ERR_ARG, who, "ldw must be at least 12");
+    if (!windows || !base || !gain || !activity) return ol_fail(CP_ERR_ARG, who, "windows, base, gain and activity are required");
+    if ((uintptr_t)windows % 4 || (uintptr_t)base % 4 || (uintptr_t)gain % 4 || (uintptr_t)activity % 4)
+        return ol_fail(CP_ERR_ARG, who, "misaligned argument");
+    OrActivityArgs a{};
+    a.windows = windows; a.ldw = ldw; a.n_rows = n_rows; a.activity = activity;
+    for (int c = 0; c < OR_C; ++c) {
+        a.base[c] = base[c];
+        a.gain[c] = gain[c];
+    }
+    hipLaunchKernelGGL(or_activity_kernel, dim3((unsigned)((n_rows + OR_THREADS - 1) / OR_THREADS)), dim3(OR_THREADS), 0,
+                       (hipStream_t)stream, a);
+    CKL("or_activity_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_realign(const int32_t* activity, const int32_t* cue, int64_t n_rows, const int32_t* segments,
+                                 int32_t n_segments, const cp_online_realign_config* cfg, int32_t* out_expected,
+                                 int32_t* out_segments, int64_t* out_sums, void* stream) {
+    const char* who = "cp_online_realign";
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (n_rows < 1 || n_rows > INT32_MAX) return bad("n_rows outside 1..2^31-1");
+    if (n_segments < 1 || n_segments > 65536) return bad("n_segments outside 1..65536");
+    if (!cfg) return bad("config is required");
+    if (cfg->max_lag < 0 || cfg->max_lag > 1024) return bad("max_lag outside 0..1024");
+    if (cfg->max_lead < 0 || cfg->max_lead > 1024) return bad("max_lead outside 0..1024");
+    if (cfg->context < 0 || cfg->context > 2048) return bad("context outside 0..2048");
+    if (cfg->min_len < 1) return bad("min_len must be at least 1");
+    if (cfg->min_rest < 1) return bad("min_rest must be at least 1");
+    if (cfg->guard < 0 || (int64_t)cfg->min_len <= 2 * (int64_t)cfg->guard) 
+        return bad("guard must not be negative, and min_len must exceed 2 guard");
+    if (cfg->min_contrast < 0 || cfg->min_contrast > CP_ONLINE_REALIGN_MAX_ACTIVITY) return bad("min_contrast outside 0..4095");
+    if (!activity || !cue || !segments || !out_expected || !out_segments || !out_sums)
+        return bad("activity, cue, segments, out_expected, out_segments and out_sums are required");
+    if ((uintptr_t)activity % 4 || (uintptr_t)cue % 4 || (uintptr_t)segments % 4 || (uintptr_t)out_expected % 4 ||
+        (uintptr_t)out_segments % 4 || (uintptr_t)out_sums % 8)
+        return bad("misaligned argument");
+    OrArgs a{};
+    a.activity = activity; a.cue = cue; a.n_rows = (int)n_rows; a.segments = segments; a.n_segments = n_segments;
+    a.expected = out_expected; a.out_segments = out_segments; a.out_sums = (long long*)out_sums;
+    // a pair is at most the region long and a found one longer than 2 guard: beyond the region's limit the three mean the same
+    const int32_t cap = CP_ONLINE_REALIGN_MAX_REGION + 1;
+    a.c.max_lag = cfg->max_lag; a.c.max_lead = cfg->max_lead; a.c.context = cfg->context; a.c.min_contrast = cfg->min_contrast;
+    a.c.min_len = cfg->min_len < cap ? cfg->min_len : cap;
+    a.c.min_rest = cfg->min_rest < cap ? cfg->min_rest : cap;
+    a.c.guard = cfg->guard < cap ? cfg->guard : cap;
+    hipLaunchKernelGGL(or_default_kernel, dim3((unsigned)((n_rows + OR_THREADS - 1) / OR_THREADS)), dim3(OR_THREADS), 0,
+                       (hipStream_t)stream, cue, (long long)n_rows, out_expected);
+    CKL("or_default_kernel");
+    hipLaunchKernelGGL(or_segment_kernel, dim3(n_segments), dim3(OR_THREADS), 0, (hipStream_t)stream, a);
+    CKL("or_segment_kernel");
+    return 0;
 }

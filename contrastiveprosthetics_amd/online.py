@@ -47,6 +47,11 @@ projection and the class rows behind the shared encoder are trained on the devic
 recording (cp_online_finetune_*, csrc/online_finetune.cuh; `finetune.finetune_reference` is the definition), and
 `projection` / `set_projection` / `reset_projection` store, restore and drop the user's head.
 
+`realign.realign_cues` stands in front of that chain: a user's cue runs ahead of the movement, and it moves the labels of a
+cued recording onto the onset and offset the sEMG itself shows, on the device and without the model (cp_online_realign*,
+csrc/online_realign.cuh; `realign.realign_reference` is the definition, `realign.sample_labels` gives `enroll` and `finetune`
+their per-sample labels).
+
 The number of windows a push emits follows from sample counts alone (`windows_emitted`), so a push never waits for the device:
 its outputs are device tensors on torch's current stream.
 """
@@ -268,7 +273,8 @@ def window_labels(labels, phase: int = 0) -> np.ndarray:
     """The label of each window of a recording with one label per raw sample (a class id, or a negative value for "not
     labelled"; what Ninapro's `restimulus` is): window k covers the raw samples phase + 20 k .. phase + 20 k + 2 WINDOW_EDGE and
     takes their label if all 11 carry the same non-negative label, else -1.  (K,) int64 with K = windows_before(n, phase).
-    Host only (numpy)."""
+    Host only (numpy).  A user's own cue is not yet such a label -- the movement starts and ends behind it --
+    and `realign.realign_cues` moves it onto the movement first."""
     lab = np.asarray(labels)
     if lab.ndim != 1 or lab.dtype.kind not in "iu":
         raise ValueError("labels must be a 1-d integer array: one class id (or a negative value) per raw sample")

@@ -1122,6 +1122,52 @@ int cp_online_multi_adapt_map_sweep(const cp_online_config* cfg, int32_t n_strea
                                     const int32_t* expected_slot, int64_t chunk_rows, void* scratch, size_t scratch_bytes,
                                     int32_t* pred, int32_t* voted, int64_t* scores, int32_t* class_hits, void* stream);
 
+/* ---- cue realignment: the onset and offset of each cued movement, from the sEMG itself ---------------------------------------
+ * A person starts a cued movement after the cue and lets go late; the labels the model was trained on had been moved onto
+ * the activity seen in the sEMG.  These two entries do that for a user's own cued recording, in front of enrolment, without
+ * the model.  realign_reference of contrastiveprosthetics_amd/realign.py is the definition; the device equals it in every
+ * integer (csrc/online_realign.cuh).
+ * - cp_online_realign_activity: a[k] = sum over the 12 channels of q_d, v = (x_d - base_d) * gain_d in two f32 operations
+ *   without contraction, r = rint(v) (ties to even), q_d = 0 unless r > 0 (NaN: 0), 255 if r >= 255, else (int)r; 0..3060.
+ *   windows (n_rows, ldw) f32 and activity (n_rows) int32 on the device; base and gain are 12 floats each on the HOST (they
+ *   travel as kernel arguments).
+ * - cp_online_realign: segments (n_segments, 2) int32 rows [s, e) on the device; with M = n_rows, prev_e the e of the row
+ *   before (0 for the first) and next_s the s of the row behind (M for the last), a row that is not 0 <= s < e <= M with
+ *   prev_e <= s has status 4: out_segments gets s, e, -1, -1, -1, -1, 4, -1 and nothing else of it is read or written.
+ *   Otherwise r0 = max(s - context, prev_e, 0), r1 = min(e + max_lag, max(next_s, e), M) (in a table without bad rows that is
+ *   max(s - context, prev_e) and min(e + max_lag, next_s)), L = r1 - r0; L > CP_ONLINE_REALIGN_MAX_REGION: status 3.
+ *   With the activity clamped to 0..CP_ONLINE_REALIGN_MAX_ACTIVITY, T its sum over [r0, r1): the pairs (o, f) with
+ *   s <= o <= min(s + max_lag, e - min_len), max(o + min_len, e - max_lead) <= f <= r1, n_A = f - o, n_R = L - n_A >= min_rest;
+ *   S_A the sum over [o, f), S_R = T - S_A, p = S_A^2 n_R + S_R^2 n_A (< 2^61), q = n_A n_R (< 2^24).  A pair has the
+ *   contrast if S_A n_R - S_R n_A >= max(min_contrast q, 1).  The choice is the largest p / q among the pairs with the
+ *   contrast (status 0), else among all pairs (status 2), fractions compared as exact 128-bit cross products, equals to the
+ *   smaller o, then the smaller f; no pair at all: status 1.
+ * - out_expected (M) int32: cue[k] where cue[k] < 0, else -2 (IGNORE); then for a row with status 0 and c = cue[s], over
+ *   k in [s, r1): c if o + guard <= k < f - guard; else for k < e: -1 (REST) if k < o - guard or k >= f + guard, else -2;
+ *   else -2 if k < f + guard, else cue[k].  The ranges [s, r1) of the rows of a table without bad rows are disjoint.
+ * - out_segments (n_segments, 8) int32: s, e, r0, r1, onset, offset, status, cue[s] (onset, offset -1 unless status is 0 or
+ *   2); out_sums (n_segments, 2) int64: S_A, S_R of the reported pair, else 0.
+ * - Two launches (the default labels; one workgroup per segment), no atomics, no floating point, the same bytes on every run.
+ *   The host checks n_rows in 1..2^31-1, n_segments in 1..65536, ldw >= 12, the config (below), pointers and alignment (4
+ *   bytes, out_sums 8) and returns CP_ERR_ARG with a cp_last_error that names the entry before anything is enqueued.  Both
+ *   entries never allocate and never synchronise. */
+#define CP_ONLINE_REALIGN_MAX_ACTIVITY 4095
+#define CP_ONLINE_REALIGN_MAX_REGION 4096
+typedef struct cp_online_realign_config {
+    int32_t max_lag;         /* 0..1024: the onset lies at most this far behind the cue's start, the offset behind its end */
+    int32_t max_lead;        /* 0..1024: the offset lies at most this far in front of the cue's end */
+    int32_t min_len;         /* >= 1, > 2 guard: windows of a movement */
+    int32_t min_rest;        /* >= 1: windows of the region outside the movement */
+    int32_t context;         /* 0..2048: windows in front of the cue's start that belong to the region */
+    int32_t min_contrast;    /* 0..4095: active mean minus resting mean must reach this (and be positive) */
+    int32_t guard;           /* >= 0: windows on either side of onset and offset that are not scored */
+} cp_online_realign_config;
+int cp_online_realign_activity(const float* windows, int32_t ldw, int64_t n_rows, const float* base, const float* gain,
+                               int32_t* activity, void* stream);
+int cp_online_realign(const int32_t* activity, const int32_t* cue, int64_t n_rows, const int32_t* segments, int32_t n_segments,
+                      const cp_online_realign_config* cfg, int32_t* out_expected, int32_t* out_segments, int64_t* out_sums,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,7 @@ counted with torch.profiler over a few pushes.  One JSON line per case, and a ta
     python tools/online_bench.py --subset-sweep --iters 20 --out profiles/online_subset_sweep.txt
     python tools/online_bench.py --map-sweep --iters 5 --out profiles/online_map_sweep.txt
     python tools/online_bench.py --finetune --iters 10 --out profiles/online_finetune.txt
+    python tools/online_bench.py --realign --iters 20 --out profiles/online_realign.txt
 """
 import argparse
 import json
@@ -116,9 +117,13 @@ def main():
     ap.add_argument("--case-seconds", type=float, default=150.0, help="--gate-sweep: time limit of each timed case")
     ap.add_argument("--finetune", action="store_true", help="head fine-tuning: embedding pass, step against torch ops, accuracy on a "
                     "synthetic person")
+    ap.add_argument("--realign", action="store_true", help="cue realignment: realign_cues against the definition, and enroll + "
+                    "finetune on the raw cue, the realigned labels and the planted truth")
     a = ap.parse_args()
     if a.enroll:
         return enroll_main(a)
+    if a.realign:
+        return realign_main(a)
     if a.finetune:
         return finetune_main(a)
     if a.gate_sweep:
@@ -494,6 +499,138 @@ def finetune_main(a):
                     "# the same u, and the bytes a step must move (u once, the slabs written and read);  (c) accuracy, per window and\n"
                     "# voted over 25 windows, on a held-out recording of a synthetic person the model was not trained on (the\n"
                     "# people, training and recordings of --enroll): one-hot rows, enrolled rows, the head fine-tuned from either\n")
+            for r in lines:
+                f.write(json.dumps(r) + "\n")
+
+
+def _lagged_recording(rng, pattern, gain, cue_windows, rest_windows, order, rest_label, rest_level=0.25):
+    """A cued recording of one synthetic person who follows the cue late: per class a cue of `cue_windows` windows and then
+    `rest_windows` of rest; the class's amplitudes start a drawn 20..80 windows behind the cue's start and end a drawn -20..+60
+    windows behind its end, and everything else is noise at `rest_level` times the person's channel gains.  Returns raw (n, 12)
+    on the GPU, the cue and the planted truth as one label per sample (`rest_label` between movements), and the planted
+    (onset, offset) of every cue in windows."""
+    n = 20 * (rest_windows + len(order) * (cue_windows + rest_windows)) + 11
+    cue, truth = np.full(n, rest_label, dtype=np.int64), np.full(n, rest_label, dtype=np.int64)
+    amp = np.tile(rest_level * gain, (n, 1))
+    planted = []
+    for i, c in enumerate(order):
+        s = rest_windows + i * (cue_windows + rest_windows)
+        e = s + cue_windows
+        o, f = s + int(rng.integers(20, 81)), e + int(rng.integers(-20, 61))
+        cue[20 * s:20 * e] = c
+        truth[20 * o:20 * f] = c
+        amp[20 * o:20 * f] = pattern[c] * gain
+        planted.append((o, f))
+    raw = torch.from_numpy((rng.standard_normal((n, 12)) * amp * 2e-3).astype(np.float32)).cuda()
+    return raw, cue, truth, np.array(planted)
+
+
+def realign_main(a):
+    """--realign: (a) realign_cues on a cued recording of the synthetic person of --enroll who follows the cue late, against
+    the definition on the host; (b) how far the found onsets and offsets lie from the planted ones; (c) held-out accuracy of
+    enroll + finetune fed with the raw cue, the realigned labels and the planted truth."""
+    from contrastiveprosthetics_amd.online import expected_commands, recording_windows, window_labels
+    from contrastiveprosthetics_amd.realign import (activity_profile, activity_reference, cue_segments, realign_cues, realign_reference,
+                                                    sample_labels)
+    torch.manual_seed(0)
+    rng = np.random.default_rng(0)
+    classes, rest = list(range(41)), 41
+    pattern = rng.uniform(0.4, 3.0, (41, 12))
+    people = np.exp(rng.normal(0.0, 0.35, (10, 12)))              # per-person channel gains; person 9 is never trained on
+    params = dict(d_e=16, lr_emg=1e-3, reg_emg=1e-5, dp_emg=0.0, lr_glove=1e-3, reg_glove=1e-6, dp_glove=0.0)
+    e = Engine(adabn=False, dtype="f32", device="cuda:0")
+    e.init_parameters(1)
+    raw0, _ = _cue_recording(rng, pattern, people[0], 30, classes)
+    ident = torch.stack([torch.zeros(12), torch.ones(12)]).cuda()
+    w0 = recording_windows(raw0, ident)
+    mean, std = w0.mean(0), w0.std(0)
+    lines = []
+
+    def out(r):
+        print(json.dumps(r), flush=True)
+        lines.append(r)
+
+    # the model of --enroll: 400 steps on people 0..8, one window per class and group
+    probe = OnlineDecoder(e, mean, std, classes=classes)
+    train = []
+    for p in range(9):
+        raw, lab = _cue_recording(rng, pattern, people[p], 40, classes)
+        w = recording_windows(raw, probe.mean_std, probe._b, probe._a, 0)
+        wl = window_labels(lab, 0)
+        train.append(torch.stack([w[torch.as_tensor(np.nonzero(wl == c)[0][:40]).cuda()] for c in classes]))
+    train = torch.stack(train)
+    labels = torch.arange(41).repeat(8).cuda()
+    for step in range(400):
+        pi = torch.randint(0, 9, (8,))
+        wi = torch.randint(0, 40, (8, 41))
+        x = torch.stack([train[pi[g], torch.arange(41), wi[g]] for g in range(8)]).reshape(-1, 12).contiguous()
+        z = e.encoder_forward(x, training=True)
+        e.head(z, labels, 1, want_grad=True)
+        e.encoder_backward(x)
+        e.adam_step(params)
+    torch.cuda.synchronize()
+
+    # person 9 follows the cue late, in the recording to personalise on and in the held-out one
+    rawE, cueE, truthE, plantedE = _lagged_recording(rng, pattern, people[9], 200, 150, rng.permutation(41), rest)
+    rawT, cueT, truthT, plantedT = _lagged_recording(rng, pattern, people[9], 200, 150, rng.permutation(41), rest)
+    wE = recording_windows(rawE, probe.mean_std, probe._b, probe._a, 0)
+    cue = expected_commands(cueE, classes, 0, rest=rest)
+    prof = activity_profile(wE, cue)
+
+    # (a) time: the device call with its one copy of the results, against the definition on the same windows on the host
+    dev_ms = _wall(lambda: realign_cues(wE, cue, prof), a.iters)
+    host_w = wE.cpu().numpy()
+    segs = cue_segments(cue)
+    t_act = _wall(lambda: activity_reference(host_w, prof["base"], prof["gain"]), max(2, a.iters // 3), warmup=1)
+    act = activity_reference(host_w, prof["base"], prof["gain"])
+    defaults = dict(max_lag=100, max_lead=50, min_len=25, min_rest=10, context=100, min_contrast=0, guard=5)
+    t_ref = _wall(lambda: realign_reference(act, cue, segs, **defaults), max(2, a.iters // 3), warmup=1)
+    got = realign_cues(wE, cue, prof)
+    want = realign_reference(act, cue, segs, **defaults)
+    out(dict(part="a", windows=int(wE.shape[0]), segments=int(segs.shape[0]), realign_cues_ms=round(dev_ms, 3),
+             activity_reference_ms=round(t_act, 3), realign_reference_ms=round(t_ref, 3), ratio=round((t_act + t_ref) / dev_ms, 1),
+             equal=bool(np.array_equal(got["expected"], want[0]))))
+
+    # (b) the pairs found against the planted ones (rows in cue order, as the planted ones are)
+    seg = got["segments"]
+    d_on, d_off = np.abs(seg["onset"] - plantedE[:, 0]), np.abs(seg["offset"] - plantedE[:, 1])
+    truth_w = expected_commands(truthE, classes, 0, rest=rest)
+    scored = (got["expected"] != -2) & (truth_w != -2)
+    out(dict(part="b", status_0=int((seg["status"] == 0).sum()), onset_err_mean=round(float(d_on.mean()), 2), onset_err_max=int(d_on.max()),
+             offset_err_mean=round(float(d_off.mean()), 2), offset_err_max=int(d_off.max()),
+             cue_windows_wrong=round(float((cue != truth_w)[(cue != -2) & (truth_w != -2)].mean()), 4),
+             realigned_windows_wrong=round(float((got["expected"] != truth_w)[scored].mean()), 4)))
+
+    # (c) enroll + finetune on the three labellings, scored on the held-out recording's planted truth
+    n = int(rawE.shape[0])
+    feeds = dict(cue=np.where(cueE == rest, -1, cueE), realigned=sample_labels(got["expected"], n), truth=np.where(truthE == rest, -1, truthE))
+    wlT = window_labels(np.where(truthT == rest, -1, truthT), 0)
+    ok = wlT >= 0
+    tune = dict(steps=200, lr=1e-3, lr_rows=1e-2, scale=10.0)
+    for dtype in ("f32", "bf16"):
+        r = dict(part="c", dtype=dtype, windows=int(ok.sum()), **tune)
+        for name, lab in feeds.items():
+            dec = OnlineDecoder(e, mean, std, classes=classes, dtype=dtype)
+            counts = dec.enroll(rawE, lab)
+            dec.finetune(rawE, lab, **tune)
+            pred, voted = (t.cpu().numpy() for t in dec.push(rawT))
+            r["labelled_" + name] = int(sum(counts.values()))
+            r["acc_" + name] = round(float((pred[ok] == wlT[ok]).mean()), 4)
+            r["acc_" + name + "_voted"] = round(float((voted[ok] == wlT[ok]).mean()), 4)
+        out(r)
+    if a.out:
+        dev = torch.cuda.get_device_name(0)
+        with open(a.out, "w") as f:
+            f.write(f"# tools/online_bench.py --realign --iters {a.iters} on {dev}\n")
+            f.write("# A synthetic person (the people, patterns and training of --enroll; rest at a quarter of the channel gains) who\n"
+                    "# follows each cue of 200 windows late: the movement starts a drawn 20..80 windows behind the cue's start and ends a\n"
+                    "# drawn -20..+60 windows behind its end.  Noise with planted amplitude steps proves nothing about real subjects:\n"
+                    "# the numbers are recorded, not asserted.  (a) wall time, host-synchronised, median: realign_cues with a given\n"
+                    "# profile (two launches of cp_online_realign* and one copy) against activity_reference + realign_reference on the\n"
+                    "# host;  (b) the found onsets and offsets against the planted ones, in windows, and the share of scored windows\n"
+                    "# whose label differs from the planted truth, for the cue and for the realigned labels;  (c) accuracy on the\n"
+                    "# planted movements of a held-out recording of the same person, per window and voted over 25 windows, after\n"
+                    "# enroll + finetune fed with the raw cue, the realigned labels and the planted truth\n")
             for r in lines:
                 f.write(json.dumps(r) + "\n")
 
