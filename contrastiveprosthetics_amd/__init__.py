@@ -24,4 +24,8 @@ def __getattr__(name):
     if name in ("realign_cues", "realign_reference", "activity_profile", "activity_reference", "cue_segments", "sample_labels"):
         from . import realign
         return getattr(realign, name)
+    if name in ("PrototypeTracker", "track_reference", "sweep_tracker", "pick_tracker", "track_grid", "embed_recording",
+                "TRACK_SCORE_KEYS"):
+        from . import track
+        return getattr(track, name)
     raise AttributeError(name)

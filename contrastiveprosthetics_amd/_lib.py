@@ -93,6 +93,11 @@ class cp_online_realign_config(C.Structure):
                 ("context", C.c_int32), ("min_contrast", C.c_int32), ("guard", C.c_int32)]
 
 
+class cp_online_track_config(C.Structure):
+    _fields_ = [("vote", C.c_int32), ("agree", C.c_int32), ("rate", C.c_double), ("min_cosine", C.c_float),
+                ("min_margin", C.c_float), ("min_anchor_cosine", C.c_float), ("reserved0", C.c_int32)]
+
+
 class cp_augment(C.Structure):
     """Settings of one cp_gather_groups_aug launch (include/cpnative.h)."""
     _fields_ = [("seed", C.c_uint32), ("salt", C.c_uint32), ("salt_state_lo", C.c_uint32), ("salt_state_hi", C.c_uint32),
@@ -136,6 +141,8 @@ CP_ONLINE_DRIVE_ONE, CP_ONLINE_DRIVE_MAX_SMOOTH = 4096, 256
 CP_ONLINE_MAP_SCORES, CP_ONLINE_MAP_SWEEP_MAX_MAPS = 3, 65536
 CP_ONLINE_FINETUNE_CHUNK, CP_ONLINE_FINETUNE_PROJECTION, CP_ONLINE_FINETUNE_ROWS = 64, 1, 2
 CP_ONLINE_REALIGN_MAX_ACTIVITY, CP_ONLINE_REALIGN_MAX_REGION = 4095, 4096
+CP_ONLINE_TRACK_SCORES, CP_ONLINE_TRACK_SWEEP_MAX_CONFIGS = 8, 65536
+CP_ONLINE_TRACK_RESET_RING, CP_ONLINE_TRACK_RESET_ROWS = 0, 1
 
 # what the four map sweep entries take behind their workspace: rms, n_windows, mean_std, map_src, map_fill, n_maps, n_classes,
 # expected_slot, chunk_rows, scratch, scratch_bytes, pred, voted, scores, class_hits, stream
@@ -287,6 +294,22 @@ SYMBOLS = {
                                         + _MAP_SWEEP_TAIL),
     "cp_online_realign_activity": (C.c_int, [_fp, C.c_int32, C.c_int64, _P(C.c_float), _P(C.c_float), _fp, _fp]),
     "cp_online_realign": (C.c_int, [_fp, _fp, C.c_int64, _fp, C.c_int32, _P(cp_online_realign_config), _fp, _fp, _fp, _fp]),
+    "cp_online_push_embed": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
+                                       _fp]),
+    "cp_online_adapt_push_embed": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
+                                             _fp, _fp]),
+    "cp_online_multi_push_embed": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, _fp, _fp, C.c_int64,
+                                             C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "cp_online_multi_adapt_push_embed": (C.c_int, [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t, _fp, _fp, C.c_int64,
+                                                   C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "cp_online_track_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "cp_online_track_set_rows": (C.c_int, [_P(cp_online_track_config), C.c_int32, _fp, C.c_size_t, C.c_int32, _P(C.c_int32), _fp,
+                                           C.c_int32, _fp]),
+    "cp_online_track_reset": (C.c_int, [_P(cp_online_track_config), C.c_int32, _fp, C.c_size_t, C.c_int32, C.c_int32, _fp]),
+    "cp_online_track_push": (C.c_int, [_P(cp_online_track_config), C.c_int32, _fp, C.c_size_t, _fp, _fp, _fp, C.c_int32, _fp, _fp,
+                                       _fp, C.c_int32, _fp, _fp]),
+    "cp_online_track_rows": (C.c_int, [_P(cp_online_track_config), C.c_int32, _fp, C.c_size_t, C.c_int32, _fp, _fp, _fp, _fp]),
+    "cp_online_track_sweep": (C.c_int, [_fp, C.c_int64, C.c_int32, _fp, _fp, C.c_int64, _fp, C.c_int32, _fp, _fp, _fp, _fp, _fp]),
 }
 
 KERNEL_KINDS = ["gather", "prep", "conv1_fwd", "bn_finalize", "conv2_fwd", "fold", "fc_fwd", "dropout", "proj_fwd",

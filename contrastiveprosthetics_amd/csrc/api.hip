@@ -31,6 +31,7 @@
 #include "online_subsets.cuh"
 #include "online_maps.cuh"
 #include "online_realign.cuh"
+#include "online_track.cuh"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* what) {

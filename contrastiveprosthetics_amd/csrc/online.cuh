@@ -331,6 +331,7 @@ struct OlTailArgs {
     int32_t* pred;            // [M] class ids
     int32_t* voted;           // [M]
     float* logits;            // optional [M][K]
+    float* emb;               // optional [M][16]: z / |z| of every window
 };
 
 // LDS of the tail
@@ -345,11 +346,12 @@ struct OlTailLds {
 
 // One 16-row tile of the tail, rows m0..m0+15 of the M rows of proj.act: projection -> z, z / |z|, logits against the table,
 // argmax (first maximum).  Row j's slot (its index into the sorted table) goes to pidx[j], in LDS or in global memory, its
-// logits to logits[j * ldl ..] (columns 0..K-1) if logits is given.  wf: the projection's fragments (ol_load_weights).  Ends
-// behind a barrier.
+// logits to logits[j * ldl ..] (columns 0..K-1) if logits is given, its z / |z| to emb[j * 16 ..] if emb is given.  wf: the
+// projection's fragments (ol_load_weights).  Ends behind a barrier.
 template <typename T>
 __device__ __forceinline__ void ol_tail_tile(const OlLayerArgs& proj, const OlState* st, int K, int m0, int M, float* logits, int ldl,
-                                             int* pidx, OlTailLds<T>& S, const uint4 (&wf)[OL_MAXCH][OL_KC * (int)sizeof(T) / 64]) {
+                                             float* emb, int* pidx, OlTailLds<T>& S,
+                                             const uint4 (&wf)[OL_MAXCH][OL_KC * (int)sizeof(T) / 64]) {
 #pragma clang fp contract(off)
     OlTileLds<T>& L = S.L;
     auto& zn = S.zn;
@@ -366,6 +368,10 @@ __device__ __forceinline__ void ol_tail_tile(const OlLayerArgs& proj, const OlSt
         const float nrm = sqrtf(ss);
 #pragma unroll
         for (int d = 0; d < 16; ++d) zn[tid][d] = z[d] / nrm;
+        if (emb && m0 + tid < M) {
+#pragma unroll
+            for (int d = 0; d < 16; ++d) emb[(size_t)(m0 + tid) * 16 + d] = zn[tid][d];
+        }
     }
     __syncthreads();
     for (int e = tid; e < 16 * K; e += OL_THREADS) {
@@ -404,17 +410,17 @@ __device__ __forceinline__ int ol_vote_step(int* ring, int& head, int& len, int&
 
 // ol_tail_tile over the M (1..OL_MAXM) rows of proj.act, then one wave runs the vote ring over the push's windows in order:
 // mode of the last `vote` predictions, ties to the smallest class id (the table is sorted by id).
-// Row j's outputs go to pred[j], voted[j] and logits[j * ldl ..] (columns 0..K-1).
+// Row j's outputs go to pred[j], voted[j], logits[j * ldl ..] (columns 0..K-1) and emb[j * 16 ..] (logits, emb: optional).
 template <typename T>
 __device__ __forceinline__ void ol_tail_run(const OlLayerArgs& proj, OlState* st, int M, int vote, int32_t* pred, int32_t* voted,
-                                            float* logits, int ldl, OlTailLds<T>& S) {
+                                            float* logits, int ldl, float* emb, OlTailLds<T>& S) {
     auto& pidx = S.pidx;
     auto& ring = S.ring;
     const int K = st->K;
     const int tid = threadIdx.x;
     uint4 wf[OL_MAXCH][OL_KC * (int)sizeof(T) / 64];
     ol_load_weights<T>((const T*)proj.w, 512, 0, wf);
-    for (int m0 = 0; m0 < M; m0 += 16) ol_tail_tile<T>(proj, st, K, m0, M, logits, ldl, pidx, S, wf);
+    for (int m0 = 0; m0 < M; m0 += 16) ol_tail_tile<T>(proj, st, K, m0, M, logits, ldl, emb, pidx, S, wf);
     if (tid < 64) {
         const int lane = tid, V = vote;
         int head = st->vote_head, len = st->vote_len;
@@ -445,7 +451,7 @@ __global__ __launch_bounds__(OL_THREADS) void ol_tail_kernel(OlTailArgs t) {
     OlState* st = t.st;
     const int M = st->m_cur;
     if (M <= 0) return;
-    ol_tail_run<T>(t.proj, st, M, t.vote, t.pred, t.voted, t.logits, st->K, S);
+    ol_tail_run<T>(t.proj, st, M, t.vote, t.pred, t.voted, t.logits, st->K, t.emb, S);
 }
 
 // ---- cp_online_prepare: fold running-statistics BatchNorm into the layer behind it ------------------------------------

@@ -1,6 +1,7 @@
 // Host layer of the online decoders (include/cpnative.h, cp_online_*): workspace layout, argument checks, launch chains and
 // the extern "C" entries of the folded, adaptive, multi-stream and adaptive multi-stream decoders, class enrolment, head
-// fine-tuning, the command gate, the grasp drive, the gate sweep, the subset sweep, the electrode-map sweep and cue realignment.  Host code only; api.hip includes it behind its own helpers (fail, CK, CKL) and encoder_api.cuh's (align256, fcK),
+// fine-tuning, the command gate, the grasp drive, the gate sweep, the subset sweep, the electrode-map sweep, cue realignment and prototype
+// tracking.  Host code only; api.hip includes it behind its own helpers (fail, CK, CKL) and encoder_api.cuh's (align256, fcK),
 // so the library stays one translation unit.  The four decoders share one workspace description (OlWS, ol_carve), one
 // parameter check, one set of front-end arguments, one folded chain and one unfolded weight copy; what an entry adds is its
 // name in the refusals and the kernels it launches.
@@ -198,6 +199,7 @@ static OlFrontArgs ol_front_args(const cp_online_config* c) {
 struct OlMap {                           // an electrode map as the entries take it: one row per stream, or none (the identity)
     const int32_t* src;
     const float* fill;
+    float* emb;                          // rides along to the tail: where a push leaves z / |z| of its rows, (rows,16); NULL: nowhere
 };
 
 static int ol_launch_frontend(const cp_online_config* c, OlState* state, float* X, const float* raw, int64_t n, const float* mean_std,
@@ -256,11 +258,11 @@ static int ol_folded_chain(unsigned char* base, const OlWS& w, const OlState* st
 
 template <typename T>
 static int ol_launch_tail(T, const cp_online_config* c, unsigned char* base, const OlWS& w, int32_t* pred, int32_t* voted, float* logits,
-                          hipStream_t st) {
+                          float* emb, hipStream_t st) {
     OlTailArgs ta{};
     ta.st = (OlState*)(base + w.state);
     ta.proj = ol_layer_args(base, w, OL_PROJ, ta.st, base + w.H1, nullptr);
-    ta.vote = c->vote; ta.pred = pred; ta.voted = voted; ta.logits = logits;
+    ta.vote = c->vote; ta.pred = pred; ta.voted = voted; ta.logits = logits; ta.emb = emb;
     hipLaunchKernelGGL((ol_tail_kernel<T>), dim3(1), dim3(OL_THREADS), 0, st, ta);
     CKL("ol_tail_kernel");
     return 0;
@@ -268,11 +270,11 @@ static int ol_launch_tail(T, const cp_online_config* c, unsigned char* base, con
 
 template <typename T>
 static int olm_launch_tail(T, const cp_online_config* c, int n_streams, unsigned char* base, const OlWS& w, int32_t* pred, int32_t* voted,
-                           float* logits, hipStream_t st) {
+                           float* logits, float* emb, hipStream_t st) {
     OlmTailArgs ta{};
     ta.proj = ol_layer_args(base, w, OL_PROJ, nullptr, base + w.H1, nullptr);
     ta.states = (OlState*)(base + w.state); ta.meta = (const OlmMeta*)(base + w.meta);
-    ta.vote = c->vote; ta.pred = pred; ta.voted = voted; ta.logits = logits;
+    ta.vote = c->vote; ta.pred = pred; ta.voted = voted; ta.logits = logits; ta.emb = emb;
     hipLaunchKernelGGL((olm_tail_kernel<T>), dim3(n_streams), dim3(OL_THREADS), 0, st, ta);
     CKL("olm_tail_kernel");
     return 0;
@@ -348,7 +350,7 @@ static int online_push_t(T t, const cp_online_config* c, unsigned char* base, co
         return 0;
     };
     if (int e = ol_folded_chain(base, w, state, (const float*)(base + w.X), base + w.H0, base + w.H1, layer)) return e;
-    return ol_launch_tail(t, c, base, w, pred, voted, logits, st);
+    return ol_launch_tail(t, c, base, w, pred, voted, logits, map.emb, st);
 }
 
 // cp_online_push, cp_online_adapt_push and their mapped forms
@@ -364,6 +366,7 @@ static int ol_push(const char* who, bool adaptive, const cp_online_config* cfg, 
     if (int e = ol_check(cfg, ws, ws_bytes, adaptive, &w)) return e;
     if (int e = ol_check_push(who, cfg, n_samples, raw, mean_std, pred, voted)) return e;
     if (int e = ol_check_map(who, map.src, map.fill, 1)) return e;
+    if ((uintptr_t)map.emb % 4) return ol_fail(CP_ERR_ARG, who, "misaligned embeddings");
     if (n_samples == 0) return 0;
     return ol_dispatch(cfg->dtype, [&](auto t) {
         return adaptive ? online_adapt_push_t(t, cfg, (unsigned char*)ws, w, raw, n_samples, mean_std, pred, voted, logits, windows, map,
@@ -383,6 +386,14 @@ extern "C" int cp_online_push_mapped(const cp_online_config* cfg, void* ws, size
                                      int32_t* voted, float* logits, float* windows, void* stream) {
     return ol_push("cp_online_push_mapped", false, cfg, ws, ws_bytes, raw, n_samples, mean_std, pred, voted, logits, windows,
                    OlMap{map_src, map_fill}, stream);
+}
+
+// the mapped push that also leaves z / |z| of every window in embeddings (n_windows,16); map and embeddings may be NULL
+extern "C" int cp_online_push_embed(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* raw, int64_t n_samples,
+                                    const float* mean_std, const int32_t* map_src, const float* map_fill, int32_t* pred,
+                                    int32_t* voted, float* logits, float* windows, float* embeddings, void* stream) {
+    return ol_push("cp_online_push_embed", false, cfg, ws, ws_bytes, raw, n_samples, mean_std, pred, voted, logits, windows,
+                   OlMap{map_src, map_fill, embeddings}, stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -510,7 +521,7 @@ static int online_adapt_push_t(T t, const cp_online_config* c, unsigned char* ba
     if (int e = ola_chain(t, base, w, (const float*)(base + w.X), -1, c->max_windows, OLA_TRACK, base + w.C1, base + w.R2, base + w.H0,
                           base + w.H1, st))
         return e;
-    return ol_launch_tail(t, c, base, w, pred, voted, logits, st);
+    return ol_launch_tail(t, c, base, w, pred, voted, logits, map.emb, st);
 }
 
 extern "C" int cp_online_adapt_push(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* raw, int64_t n_samples,
@@ -523,6 +534,13 @@ extern "C" int cp_online_adapt_push_mapped(const cp_online_config* cfg, void* ws
                                            int32_t* voted, float* logits, float* windows, void* stream) {
     return ol_push("cp_online_adapt_push_mapped", true, cfg, ws, ws_bytes, raw, n_samples, mean_std, pred, voted, logits, windows,
                    OlMap{map_src, map_fill}, stream);
+}
+
+extern "C" int cp_online_adapt_push_embed(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* raw, int64_t n_samples,
+                                          const float* mean_std, const int32_t* map_src, const float* map_fill, int32_t* pred,
+                                          int32_t* voted, float* logits, float* windows, float* embeddings, void* stream) {
+    return ol_push("cp_online_adapt_push_embed", true, cfg, ws, ws_bytes, raw, n_samples, mean_std, pred, voted, logits, windows,
+                   OlMap{map_src, map_fill, embeddings}, stream);
 }
 
 // calibration scratch: the normalised activations of all windows (two buffers), one chunk of conv2 operand and output, and
@@ -687,7 +705,7 @@ static int online_multi_push_t(T t, const cp_online_config* c, int n_streams, un
     };
     if (rows > 0)
         if (int e = ol_folded_chain(base, w, nullptr, (const float*)(base + w.X), base + w.H0, base + w.H1, layer)) return e;
-    return olm_launch_tail(t, c, n_streams, base, w, pred, voted, logits, st);
+    return olm_launch_tail(t, c, n_streams, base, w, pred, voted, logits, map.emb, st);
 }
 
 // cp_online_multi_push, cp_online_multi_adapt_push and their mapped forms
@@ -703,6 +721,7 @@ static int olm_push(const char* who, bool adaptive, const cp_online_config* cfg,
     if (int e = olm_check(cfg, n_streams, max_rows, ws, ws_bytes, adaptive, &w)) return e;
     if (int e = olm_check_push(who, max_rows, raw, counts, total_samples, total_windows, mean_std, pred, voted)) return e;
     if (int e = ol_check_map(who, map.src, map.fill, n_streams)) return e;
+    if ((uintptr_t)map.emb % 4) return ol_fail(CP_ERR_ARG, who, "misaligned embeddings");
     if (total_samples == 0) return 0;
     return ol_dispatch(cfg->dtype, [&](auto t) {
         return adaptive ? online_multi_adapt_push_t(t, cfg, n_streams, (unsigned char*)ws, w, raw, counts, total_samples, total_windows,
@@ -725,6 +744,14 @@ extern "C" int cp_online_multi_push_mapped(const cp_online_config* cfg, int32_t 
                                            int32_t* voted, float* logits, float* windows, void* stream) {
     return olm_push("cp_online_multi_push_mapped", false, cfg, n_streams, max_rows, ws, ws_bytes, raw, counts, total_samples,
                     total_windows, mean_std, pred, voted, logits, windows, OlMap{map_src, map_fill}, stream);
+}
+
+extern "C" int cp_online_multi_push_embed(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                          const float* raw, const int32_t* counts, int64_t total_samples, int32_t total_windows,
+                                          const float* mean_std, const int32_t* map_src, const float* map_fill, int32_t* pred,
+                                          int32_t* voted, float* logits, float* windows, float* embeddings, void* stream) {
+    return olm_push("cp_online_multi_push_embed", false, cfg, n_streams, max_rows, ws, ws_bytes, raw, counts, total_samples,
+                    total_windows, mean_std, pred, voted, logits, windows, OlMap{map_src, map_fill, embeddings}, stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -834,7 +861,7 @@ static int online_multi_adapt_push_t(T t, const cp_online_config* c, int n_strea
             CKL("olam_fc_kernel");
         }
     }
-    return olm_launch_tail(t, c, n_streams, base, w, pred, voted, logits, st);
+    return olm_launch_tail(t, c, n_streams, base, w, pred, voted, logits, map.emb, st);
 }
 
 extern "C" int cp_online_multi_adapt_push(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
@@ -852,6 +879,15 @@ extern "C" int cp_online_multi_adapt_push_mapped(const cp_online_config* cfg, in
                                                  void* stream) {
     return olm_push("cp_online_multi_adapt_push_mapped", true, cfg, n_streams, max_rows, ws, ws_bytes, raw, counts, total_samples,
                     total_windows, mean_std, pred, voted, logits, windows, OlMap{map_src, map_fill}, stream);
+}
+
+extern "C" int cp_online_multi_adapt_push_embed(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
+                                                size_t ws_bytes, const float* raw, const int32_t* counts, int64_t total_samples,
+                                                int32_t total_windows, const float* mean_std, const int32_t* map_src,
+                                                const float* map_fill, int32_t* pred, int32_t* voted, float* logits, float* windows,
+                                                float* embeddings, void* stream) {
+    return olm_push("cp_online_multi_adapt_push_embed", true, cfg, n_streams, max_rows, ws, ws_bytes, raw, counts, total_samples,
+                    total_windows, mean_std, pred, voted, logits, windows, OlMap{map_src, map_fill, embeddings}, stream);
 }
 
 extern "C" int cp_online_multi_adapt_statistics(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
@@ -1791,5 +1827,146 @@ extern "C" int cp_online_realign(const int32_t* activity, const int32_t* cue, in
     CKL("or_default_kernel");
     hipLaunchKernelGGL(or_segment_kernel, dim3(n_segments), dim3(OR_THREADS), 0, (hipStream_t)stream, a);
     CKL("or_segment_kernel");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// prototype tracking (csrc/online_track.cuh): one OtState per stream in a workspace of its own, behind any decoder's embeddings
+// ---------------------------------------------------------------------------------------
+static_assert(OT_MAXK == CP_ONLINE_MAX_CLASSES && OT_MAXVOTE == CP_ONLINE_MAX_VOTE && OT_MAXM == CP_ONLINE_MAX_WINDOWS && OT_D == CP_D_E &&
+              OT_SCORES == CP_ONLINE_TRACK_SCORES, "tracker limits");
+static_assert(sizeof(OtConfig) == sizeof(cp_online_track_config) && offsetof(OtConfig, rate) == offsetof(cp_online_track_config, rate) &&
+              offsetof(OtConfig, min_anchor_cosine) == offsetof(cp_online_track_config, min_anchor_cosine),
+              "the sweep reads cp_online_track_config from the device as OtConfig");
+static_assert(sizeof(OtState) == 16 + 4 * (OT_MAXK + OT_MAXVOTE) + 16 * OT_MAXK + 8 * OT_MAXK * OT_D + 8 * OT_MAXK * OT_D &&
+              offsetof(OtState, anchor) == 2320 && sizeof(OtState) % 16 == 0, "OtState as PrototypeTracker.state reads it back");
+static_assert(offsetof(OlState, table) == 3576 && sizeof(OlState) == 7672,
+              "PrototypeTracker takes its anchor from the decoders' normalised class table, where their workspace keeps it");
+
+static OtConfig ot_config(const cp_online_track_config* c) {
+    OtConfig o{};
+    o.vote = c->vote; o.agree = c->agree; o.rate = c->rate;
+    o.min_cosine = c->min_cosine; o.min_margin = c->min_margin; o.min_anchor_cosine = c->min_anchor_cosine;
+    return o;
+}
+
+static int ot_check_config(const char* who, const cp_online_track_config* c) {
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (!c) return bad("config is required");
+    if (c->vote < 1 || c->vote > CP_ONLINE_MAX_VOTE) return bad("vote outside 1..256");
+    if (!(c->rate >= 0.0 && c->rate < 1.0)) return bad("rate must lie in [0, 1)");
+    if (c->agree != 0 && c->agree != 1) return bad("agree must be 0 or 1");
+    if (std::isnan(c->min_cosine) || std::isnan(c->min_margin) || std::isnan(c->min_anchor_cosine))
+        return bad("min_cosine, min_margin and min_anchor_cosine must not be NaN");
+    return 0;
+}
+
+static int ot_check(const char* who, const cp_online_track_config* c, int32_t n_streams, void* ws, size_t ws_bytes) {
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (!ws) return bad("config and workspace are required");
+    if (int e = ot_check_config(who, c)) return e;
+    if (n_streams < 1 || n_streams > CP_ONLINE_MULTI_MAX_STREAMS) return bad("n_streams outside 1..256");
+    if ((uintptr_t)ws % 256) return bad("workspace not 256-byte aligned");
+    if (ws_bytes < (size_t)n_streams * sizeof(OtState)) return bad("workspace too small");
+    return 0;
+}
+
+extern "C" size_t cp_online_track_workspace_bytes(int32_t n_streams) {
+    if (n_streams < 1) n_streams = 1;
+    return align256((size_t)n_streams * sizeof(OtState));
+}
+
+extern "C" int cp_online_track_set_rows(const cp_online_track_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index,
+                                        const int32_t* ids, const float* rows, int32_t n_classes, void* stream) {
+    const char* who = "cp_online_track_set_rows";
+    if (int e = ot_check(who, cfg, n_streams, ws, ws_bytes)) return e;
+    if (int e = ol_check_index(who, index, n_streams)) return e;
+    if (!ids || !rows || n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return ol_fail(CP_ERR_ARG, who, "1..64 classes, with ids and rows");
+    if ((uintptr_t)ids % 4 || (uintptr_t)rows % 4) return ol_fail(CP_ERR_ARG, who, "misaligned argument");
+    OtIds c{};
+    c.K = n_classes;
+    for (int k = 0; k < n_classes; ++k) {
+        if (ids[k] < 0 || ids[k] == INT32_MAX || (k > 0 && ids[k] <= ids[k - 1]))
+            return ol_fail(CP_ERR_ARG, who, "ids must be ascending, distinct and in 0..2^31-2");
+        c.ids[k] = ids[k];
+    }
+    hipLaunchKernelGGL(ot_set_rows_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (OtState*)ws + index, c, rows);
+    CKL("ot_set_rows_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_track_reset(const cp_online_track_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index,
+                                     int32_t what, void* stream) {
+    const char* who = "cp_online_track_reset";
+    if (int e = ot_check(who, cfg, n_streams, ws, ws_bytes)) return e;
+    if (index < -1 || index >= n_streams) return ol_fail(CP_ERR_ARG, who, "stream index outside -1..n_streams-1");
+    if (what != CP_ONLINE_TRACK_RESET_RING && what != CP_ONLINE_TRACK_RESET_ROWS)
+        return ol_fail(CP_ERR_ARG, who, "what must be CP_ONLINE_TRACK_RESET_RING or CP_ONLINE_TRACK_RESET_ROWS");
+    hipLaunchKernelGGL(ot_reset_kernel, dim3(index < 0 ? n_streams : 1), dim3(64), 0, (hipStream_t)stream, (OtState*)ws,
+                       index < 0 ? 0 : index, (int)what);
+    CKL("ot_reset_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_track_push(const cp_online_track_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes,
+                                    const float* embeddings, const int32_t* row0, const int32_t* m, int32_t total_rows, int32_t* pred,
+                                    int32_t* voted, float* logits, int32_t ldl, int32_t* updated, void* stream) {
+    const char* who = "cp_online_track_push";
+    if (int e = ot_check(who, cfg, n_streams, ws, ws_bytes)) return e;
+    if (total_rows < 0 || total_rows > CP_ONLINE_MULTI_MAX_ROWS) return ol_fail(CP_ERR_ARG, who, "total_rows outside 0..65536");
+    if (total_rows == 0) return 0;
+    if (!embeddings || !row0 || !m || !pred || !voted || !updated)
+        return ol_fail(CP_ERR_ARG, who, "embeddings, row0, m, pred, voted and updated are required");
+    if (logits && (ldl < 1 || ldl > CP_ONLINE_MULTI_MAX_ROWS)) return ol_fail(CP_ERR_ARG, who, "ldl must be at least 1");
+    if ((uintptr_t)embeddings % 16) return ol_fail(CP_ERR_ARG, who, "embeddings must be 16-byte aligned");
+    if ((uintptr_t)row0 % 4 || (uintptr_t)m % 4 || (uintptr_t)pred % 4 || (uintptr_t)voted % 4 || (uintptr_t)logits % 4 ||
+        (uintptr_t)updated % 4)
+        return ol_fail(CP_ERR_ARG, who, "misaligned argument");
+    OtPushArgs a{};
+    a.states = (OtState*)ws; a.emb = embeddings; a.row0 = row0; a.m = m; a.total_rows = total_rows; a.ldl = logits ? ldl : 0;
+    a.pred = pred; a.voted = voted; a.logits = logits; a.updated = updated; a.c = ot_config(cfg);
+    hipLaunchKernelGGL(ot_push_kernel, dim3(n_streams), dim3(64), 0, (hipStream_t)stream, a);
+    CKL("ot_push_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_track_rows(const cp_online_track_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index,
+                                    float* rows_out, int64_t* n_updates_out, int64_t* n_refused_out, void* stream) {
+    const char* who = "cp_online_track_rows";
+    if (int e = ot_check(who, cfg, n_streams, ws, ws_bytes)) return e;
+    if (int e = ol_check_index(who, index, n_streams)) return e;
+    if ((uintptr_t)rows_out % 4 || (uintptr_t)n_updates_out % 8 || (uintptr_t)n_refused_out % 8)
+        return ol_fail(CP_ERR_ARG, who, "misaligned argument");
+    const OtState* st = (const OtState*)ws + index;
+    hipStream_t s = (hipStream_t)stream;
+    if (rows_out) CK(hipMemcpyAsync(rows_out, st->row, sizeof st->row, hipMemcpyDeviceToDevice, s));
+    if (n_updates_out) CK(hipMemcpyAsync(n_updates_out, st->n_updates, sizeof st->n_updates, hipMemcpyDeviceToDevice, s));
+    if (n_refused_out) CK(hipMemcpyAsync(n_refused_out, st->n_refused, sizeof st->n_refused, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+// tracker sweep: n_configs settings over one recording's embeddings, one wave each, from a fresh tracker (ot_sweep_kernel)
+extern "C" int cp_online_track_sweep(const float* embeddings, int64_t n_rows, int32_t n_classes, const float* rows,
+                                     const int32_t* expected_slot, int64_t tail_from, const cp_online_track_config* configs,
+                                     int32_t n_configs, int64_t* scores, int32_t* pred, int32_t* voted, int32_t* updated, void* stream) {
+    const char* who = "cp_online_track_sweep";
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return bad("n_classes outside 1..64");
+    if (n_configs < 1 || n_configs > CP_ONLINE_TRACK_SWEEP_MAX_CONFIGS) return bad("n_configs outside 1..65536");
+    if (n_rows < 1 || n_rows > INT32_MAX) return bad("n_rows outside 1..2^31-1");
+    if (tail_from < 0) return bad("tail_from must not be negative");
+    if (!embeddings || !rows || !expected_slot || !configs || !scores)
+        return bad("embeddings, rows, expected_slot, configs and scores are required");
+    if ((uintptr_t)embeddings % 16) return bad("embeddings must be 16-byte aligned");
+    if ((uintptr_t)rows % 4 || (uintptr_t)expected_slot % 4 || (uintptr_t)configs % 8 || (uintptr_t)scores % 8 || (uintptr_t)pred % 4 ||
+        (uintptr_t)voted % 4 || (uintptr_t)updated % 4)
+        return bad("misaligned argument");
+    OtSweepArgs a{};
+    a.emb = embeddings; a.expected = expected_slot; a.configs = (const OtConfig*)configs; a.rows = rows; a.n_rows = n_rows;
+    a.tail_from = tail_from; a.n_configs = n_configs; a.K = n_classes; a.scores = (long long*)scores; a.pred = pred; a.voted = voted;
+    a.updated = updated;
+    hipLaunchKernelGGL(ot_sweep_kernel, dim3((n_configs + OT_SWEEP_WAVES - 1) / OT_SWEEP_WAVES), dim3(64 * OT_SWEEP_WAVES), 0,
+                       (hipStream_t)stream, a);
+    CKL("ot_sweep_kernel");
     return 0;
 }

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(OL_THREADS) void olmap_tail_kernel(OlMapTailArgs a)
     const int K = a.st->K;
     uint4 wf[OL_MAXCH][OL_KC * (int)sizeof(T) / 64];
     ol_load_weights<T>((const T*)a.proj.w, 512, 0, wf);
-    for (int m0 = m_begin; m0 < m_end; m0 += 16) ol_tail_tile<T>(a.proj, a.st, K, m0, a.rows, nullptr, 0, a.slot, S, wf);
+    for (int m0 = m_begin; m0 < m_end; m0 += 16) ol_tail_tile<T>(a.proj, a.st, K, m0, a.rows, nullptr, 0, nullptr, a.slot, S, wf);
 }
 
 struct OlMapVoteArgs {

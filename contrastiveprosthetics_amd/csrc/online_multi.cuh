@@ -94,6 +94,7 @@ struct OlmTailArgs {
     int32_t* pred;                       // [R] packed rows
     int32_t* voted;                      // [R]
     float* logits;                       // optional [R][OL_MAXK], columns >= K_s not written
+    float* emb;                          // optional [R][16]: z / |z| of every packed row
 };
 
 template <typename T>
@@ -107,7 +108,8 @@ __global__ __launch_bounds__(OL_THREADS) void olm_tail_kernel(OlmTailArgs t) {
     OlLayerArgs proj = t.proj;
     proj.act = (const T*)t.proj.act + (size_t)mt.row0 * 512;
     ol_tail_run<T>(proj, st, mt.m, t.vote, t.pred + mt.row0, t.voted + mt.row0,
-                   t.logits ? t.logits + (size_t)mt.row0 * OL_MAXK : nullptr, OL_MAXK, S);
+                   t.logits ? t.logits + (size_t)mt.row0 * OL_MAXK : nullptr, OL_MAXK,
+                   t.emb ? t.emb + (size_t)mt.row0 * 16 : nullptr, S);
 }
 
 // cp_online_multi_reset: the stream part of streams first .. first + gridDim.x - 1 to zero (as cp_online_reset's memset)

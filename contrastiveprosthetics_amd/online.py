@@ -52,6 +52,10 @@ cued recording onto the onset and offset the sEMG itself shows, on the device an
 csrc/online_realign.cuh; `realign.realign_reference` is the definition, `realign.sample_labels` gives `enroll` and `finetune`
 their per-sample labels).
 
+`push(..., return_embeddings=True)` also gives out z / |z| of every window (cp_online_*_push_embed), which is what
+`track.PrototypeTracker` reads: class rows that follow the user's drifting embeddings between enrolments, on the device behind
+any of the four decoders (cp_online_track_*, csrc/online_track.cuh; `track.track_reference` is the definition).
+
 The number of windows a push emits follows from sample counts alone (`windows_emitted`), so a push never waits for the device:
 its outputs are device tensors on torch's current stream.
 """
@@ -607,10 +611,11 @@ class OnlineDecoder(_EnrollMixin):
     def _map_of(self, key):
         return self._map
 
-    def push(self, raw: torch.Tensor, return_logits: bool = False, return_windows: bool = False):
-        """raw (n, 12) f32 on the GPU: the next n samples of the stream.  Returns (pred, voted[, logits][, windows]) for the
-        M = windows_emitted(n_seen, n, phase) windows the chunk completes: pred, voted (M,) int32 class ids, logits (M, K) f32,
-        windows (M, 12) f32 (the normalised windows, a test aid)."""
+    def push(self, raw: torch.Tensor, return_logits: bool = False, return_windows: bool = False, return_embeddings: bool = False):
+        """raw (n, 12) f32 on the GPU: the next n samples of the stream.  Returns (pred, voted[, logits][, windows][, embeddings])
+        for the M = windows_emitted(n_seen, n, phase) windows the chunk completes: pred, voted (M,) int32 class ids, logits
+        (M, K) f32, windows (M, 12) f32 (the normalised windows, a test aid), embeddings (M, 16) f32 (z / |z| of every window:
+        what the tail multiplies with the class rows, and what a `track.PrototypeTracker` reads)."""
         if self.class_ids is None:
             raise _lib.CpNativeError("set_classes() first")
         if not self.calibrated:
@@ -630,17 +635,22 @@ class OnlineDecoder(_EnrollMixin):
             pred, voted = pv[0, :M], pv[1, :M]
             logits = torch.empty(M, K, dtype=torch.float32, device=self.device) if return_logits else None
             wins = torch.empty(M, EMG_DIM, dtype=torch.float32, device=self.device) if return_windows else None
+            emb = torch.empty(M, CP_D_E, dtype=torch.float32, device=self.device) if return_embeddings else None
             name = "cp_online_push" if self.adapt is None else "cp_online_adapt_push"
             cmap = () if self._map_dev is None else (self._map_dev[0].data_ptr(), self._map_dev[1].data_ptr())
-            fn = getattr(self.lib, name + "_mapped" if cmap else name)
+            if return_embeddings:                              # the mapped entry with one more destination; no map: NULL, NULL
+                fn, cmap, tail = getattr(self.lib, name + "_embed"), cmap or (None, None), (emb.data_ptr(),)
+            else:
+                fn, tail = getattr(self.lib, name + "_mapped" if cmap else name), ()
             _lib.check(fn(C.byref(self._cfg), *self._ws(), piece.data_ptr(), n, self.mean_std.data_ptr(), *cmap,
                           pv[0].data_ptr(), pv[1].data_ptr(), logits.data_ptr() if logits is not None else None,
-                          wins.data_ptr() if wins is not None else None, self._stream()), name)
+                          wins.data_ptr() if wins is not None else None, *tail, self._stream()), name)
             self.n_seen += n
-            outs.append((pred, voted, logits, wins))
+            outs.append((pred, voted, logits, wins, emb))
         if not outs:
             outs.append((torch.empty(0, dtype=torch.int32, device=self.device),) * 2
-                        + (torch.empty(0, K, device=self.device), torch.empty(0, EMG_DIM, device=self.device)))
+                        + (torch.empty(0, K, device=self.device), torch.empty(0, EMG_DIM, device=self.device),
+                           torch.empty(0, CP_D_E, device=self.device)))
 
         def cat(i):
             parts = [o[i] for o in outs]
@@ -651,6 +661,8 @@ class OnlineDecoder(_EnrollMixin):
             res.append(cat(2))
         if return_windows:
             res.append(cat(3))
+        if return_embeddings:
+            res.append(cat(4))
         return tuple(res)
 
     # ------------------------------------------------------------------ class enrolment
@@ -1024,10 +1036,11 @@ class _MultiStreamBase(_EnrollMixin):
             _lib.check(self.lib.cp_online_multi_reset(*self._args(), s, self._stream()), "cp_online_multi_reset")
             self._seen[s] = 0
 
-    def push(self, chunks, return_logits: bool = False, return_windows: bool = False):
+    def push(self, chunks, return_logits: bool = False, return_windows: bool = False, return_embeddings: bool = False):
         """chunks: n_streams entries, each None or an (n_s, 12) float32 GPU tensor, the next samples of stream s.  Returns one
-        tuple per stream, (pred, voted[, logits][, windows]) for its windows_emitted(n_seen[s], n_s, phase) windows: views into
-        the packed outputs (pred, voted int32 class ids, logits (M_s, K_s) f32, windows (M_s, 12) f32)."""
+        tuple per stream, (pred, voted[, logits][, windows][, embeddings]) for its windows_emitted(n_seen[s], n_s, phase)
+        windows: views into the packed outputs (pred, voted int32 class ids, logits (M_s, K_s) f32, windows (M_s, 12) f32,
+        embeddings (M_s, 16) f32, z / |z| of every window)."""
         if isinstance(chunks, torch.Tensor) or len(chunks) != self.n_streams:
             raise ValueError(f"chunks must be a sequence of {self.n_streams} entries (None or (n, 12) tensors)")
         counts, parts = [], []
@@ -1045,9 +1058,10 @@ class _MultiStreamBase(_EnrollMixin):
             raw = parts[0].contiguous()
         else:
             raw = torch.cat(parts)
-        return self._push(raw, np.asarray(counts, dtype=np.int64), return_logits, return_windows)
+        return self._push(raw, np.asarray(counts, dtype=np.int64), return_logits, return_windows, return_embeddings)
 
-    def push_packed(self, raw: torch.Tensor, counts, return_logits: bool = False, return_windows: bool = False):
+    def push_packed(self, raw: torch.Tensor, counts, return_logits: bool = False, return_windows: bool = False,
+                    return_embeddings: bool = False):
         """As push, for samples already packed in stream order: raw (sum(counts), 12) float32 on the GPU, counts[s] >= 0 the
         samples of stream s."""
         _check_raw(raw)
@@ -1058,7 +1072,7 @@ class _MultiStreamBase(_EnrollMixin):
             raise ValueError("counts must be >= 0")
         if int(cnt.sum()) != raw.shape[0]:
             raise ValueError(f"counts sum to {int(cnt.sum())} samples, raw holds {raw.shape[0]}")
-        return self._push(raw.contiguous(), cnt, return_logits, return_windows)
+        return self._push(raw.contiguous(), cnt, return_logits, return_windows, return_embeddings)
 
     def _check_push(self, counts: np.ndarray):
         """refusals of a subclass, before anything is enqueued"""
@@ -1074,7 +1088,7 @@ class _MultiStreamBase(_EnrollMixin):
         self._counts_cache = (key, dev)
         return dev
 
-    def _push(self, raw: torch.Tensor, counts: np.ndarray, return_logits: bool, return_windows: bool):
+    def _push(self, raw: torch.Tensor, counts: np.ndarray, return_logits: bool, return_windows: bool, return_embeddings: bool = False):
         if ((counts > 0) & ~self._has_table).any():
             s = int(np.nonzero((counts > 0) & ~self._has_table)[0][0])
             raise _lib.CpNativeError(f"stream {s} has samples but no class table: set_classes({s}, ...) first")
@@ -1099,13 +1113,18 @@ class _MultiStreamBase(_EnrollMixin):
             pv = torch.empty(2, max(R, 1), dtype=torch.int32, device=self.device)     # (an empty tensor's pointer is NULL)
             logits = torch.empty(R, MAX_CLASSES, dtype=torch.float32, device=self.device) if return_logits else None
             wins = torch.empty(R, EMG_DIM, dtype=torch.float32, device=self.device) if return_windows else None
+            emb = torch.empty(R, CP_D_E, dtype=torch.float32, device=self.device) if return_embeddings else None
             if piece.shape[0]:
                 cmap = (self._map_src.data_ptr(), self._map_fill.data_ptr()) if any(m is not None for m in self._maps) else ()
-                _lib.check(getattr(self.lib, self._ENTRY + ("_push_mapped" if cmap else "_push"))(
+                if return_embeddings:                          # the mapped entry with one more destination; no map: NULL, NULL
+                    name, cmap, tail = "_push_embed", cmap or (None, None), (emb.data_ptr(),)
+                else:
+                    name, tail = "_push_mapped" if cmap else "_push", ()
+                _lib.check(getattr(self.lib, self._ENTRY + name)(
                     *self._args(), piece.data_ptr(), self._counts_on_device(take).data_ptr(), int(piece.shape[0]), R,
                     self.mean_std.data_ptr(), *cmap, pv[0].data_ptr(), pv[1].data_ptr(),
                     logits.data_ptr() if logits is not None else None, wins.data_ptr() if wins is not None else None,
-                    self._stream()), self._ENTRY + "_push")
+                    *tail, self._stream()), self._ENTRY + "_push")
             self._seen += take
             ml = m.tolist()
             cols = [pv[0, :R].split(ml), pv[1, :R].split(ml)]
@@ -1113,6 +1132,8 @@ class _MultiStreamBase(_EnrollMixin):
                 cols.append([x[:, :k] for x, k in zip(logits.split(ml), self._k)])
             if return_windows:
                 cols.append(wins.split(ml))
+            if return_embeddings:
+                cols.append(emb.split(ml))
             outs.append(list(zip(*cols)))
         if len(outs) == 1:
             return outs[0]

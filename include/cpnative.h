@@ -1168,6 +1168,107 @@ int cp_online_realign(const int32_t* activity, const int32_t* cue, int64_t n_row
                       const cp_online_realign_config* cfg, int32_t* out_expected, int32_t* out_segments, int64_t* out_sums,
                       void* stream);
 
+/* ---- embeddings out of a push ------------------------------------------------------------------------------------------------
+ * The tail of every decoder computes e = z / |z|, sixteen floats per window, and gives out only its cosines against the class
+ * rows.  These four entries are the mapped pushes (map_src, map_fill NULL: no map) with one more destination: embeddings
+ * (rows,16) f32 on the device, NULL for none, rows in the order and packing of pred.  Row j is the e the tail multiplied
+ * with the class rows, so logits[j][k] = sum_d e[j][d] * row[k][d] as sequential f32 multiply-adds from 0 reproduces the
+ * logits bit for bit.  Everything else a push returns, launches and keeps is unchanged; the eight entries without
+ * `embeddings` are these with NULL. */
+int cp_online_push_embed(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* raw, int64_t n_samples,
+                         const float* mean_std, const int32_t* map_src, const float* map_fill, int32_t* pred, int32_t* voted,
+                         float* logits, float* windows, float* embeddings, void* stream);
+int cp_online_adapt_push_embed(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* raw, int64_t n_samples,
+                               const float* mean_std, const int32_t* map_src, const float* map_fill, int32_t* pred,
+                               int32_t* voted, float* logits, float* windows, float* embeddings, void* stream);
+int cp_online_multi_push_embed(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                               const float* raw, const int32_t* counts, int64_t total_samples, int32_t total_windows,
+                               const float* mean_std, const int32_t* map_src, const float* map_fill, int32_t* pred,
+                               int32_t* voted, float* logits, float* windows, float* embeddings, void* stream);
+int cp_online_multi_adapt_push_embed(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                     const float* raw, const int32_t* counts, int64_t total_samples, int32_t total_windows,
+                                     const float* mean_std, const int32_t* map_src, const float* map_fill, int32_t* pred,
+                                     int32_t* voted, float* logits, float* windows, float* embeddings, void* stream);
+
+/* ---- prototype tracking: class rows that follow the user between enrolments -------------------------------------------------
+ * A stage behind a decoder, as the gate is, with a workspace of its own (cp_online_track_workspace_bytes; a zeroed one is a
+ * valid start: no classes).  One launch per push for up to 256 streams, one wave per stream, lane k = class slot k.
+ * track_reference of contrastiveprosthetics_amd/track.py is the definition; the device equals it in every integer and bit
+ * (csrc/online_track.cuh).
+ * - Per stream: K, ids[K] ascending; anchor[K][16] f32, the enrolled unit rows as cp_online_track_set_rows took them, bit for
+ *   bit; row[K][16] f32, the current rows, which start as the anchor; acc[K][16] f64, the tracked direction, which starts as
+ *   (double)anchor; n_updates[K], n_refused[K] int64; the decoders' vote ring of cfg.vote slots.
+ * - Per window j with embedding e, in window order, every f32 and f64 operation on its own (no contraction):
+ *   logits: l[k] = sum_d e[d] * row[k][d], d ascending, from 0.f, multiply then add: the tail's operations.
+ *   row: k1 = 0, then every k in ascending order with l[k] > l[k1] becomes k1 (the tail's first maximum; a NaN is never
+ *   greater, and nothing is greater than a NaN in slot 0).  c1 = l[k1], c2 = the maximum over k != k1 (-1.0f for K = 1),
+ *   margin = c1 - c2.
+ *   outputs: pred[j] = ids[k1]; voted[j] from the ring as the decoders compute it (k1 enters, the oldest entry leaves once
+ *   cfg.vote are in, the slot with the most entries, the smallest among equals); logits[j][0..K-1] if logits is given.
+ *   eligible: rate > 0, every logit finite, c1 >= min_cosine, margin >= min_margin, and with agree k1 == this window's voted slot.
+ *   update (eligible windows only), f64: a'[d] = (1 - rate) * acc[k1][d] + rate * (double)e[d]; n2 = sum_d a'[d]^2, d
+ *   ascending; cand[d] = (float)(a'[d] / sqrt(n2)); f32: ca = sum_d cand[d] * anchor[k1][d], d ascending.  If n2 is finite and
+ *   > 0 and ca >= min_anchor_cosine: acc[k1] = a', row[k1] = cand, n_updates[k1] += 1, updated[j] = ids[k1].  Otherwise
+ *   n_refused[k1] += 1 and nothing else changes.  updated[j] = -1 for a refused window and for one that was not eligible.
+ *   The new row is first used by window j + 1.
+ * - What follows: a stream's outputs depend neither on the cut into pushes nor on the streams that share a launch; with
+ *   rate = 0 pred, voted and logits are the decoder's own, bit for bit; with min_anchor_cosine above every cosine no row moves.
+ * - cp_online_track_set_rows: ids (n_classes) int32 on the HOST, ascending, distinct, in 0..2^31-2; rows (n_classes,16) f32
+ *   on the device, taken as they are (unit rows: the decoder's normalised table).  Installs the anchor and resets the stream's
+ *   rows, accumulators, counters and ring.
+ * - cp_online_track_reset: index -1 for all streams; what = CP_ONLINE_TRACK_RESET_RING empties the ring,
+ *   CP_ONLINE_TRACK_RESET_ROWS also puts rows and accumulators back to the anchor and the counters to 0.
+ * - cp_online_track_push: embeddings (total_rows,16) f32, 16-byte aligned, what a *_push_embed entry wrote; row0, m
+ *   (n_streams) int32 on the device: stream s owns rows row0[s] .. row0[s] + m[s] - 1, m[s] in 0..256.  pred, voted, updated
+ *   (total_rows) int32; logits (total_rows, ldl) f32 or NULL.  A stream without classes, with m[s] = 0 or with rows outside
+ *   0..total_rows (or K > ldl with logits) is left untouched.
+ * - cp_online_track_rows: the current rows (64,16) f32 and the counters (64) int64 each of one stream, device to device;
+ *   any of the three may be NULL.  Slots >= K hold 0.
+ * - The host checks the config (vote in 1..256, rate in [0,1), agree 0 or 1, no NaN), n_streams in 1..256, the workspace
+ *   (256-byte aligned, large enough), indices, counts, pointers and alignment and returns CP_ERR_ARG with a cp_last_error
+ *   that names the entry before anything is enqueued.  The entries never allocate and never synchronise. */
+#define CP_ONLINE_TRACK_RESET_RING 0
+#define CP_ONLINE_TRACK_RESET_ROWS 1
+typedef struct cp_online_track_config {
+    int32_t vote;                /* 1..256: length of the vote ring */
+    int32_t agree;               /* 1: only a window whose slot is also the voted slot may update */
+    double rate;                 /* beta in [0, 1): the share of a window in the tracked direction; 0: nothing ever moves */
+    float min_cosine;            /* the top cosine an updating window must reach */
+    float min_margin;            /* and its lead over the runner-up */
+    float min_anchor_cosine;     /* a row never falls below this cosine to its enrolled row */
+    int32_t reserved0;
+} cp_online_track_config;
+size_t cp_online_track_workspace_bytes(int32_t n_streams);
+int cp_online_track_set_rows(const cp_online_track_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index,
+                             const int32_t* ids, const float* rows, int32_t n_classes, void* stream);
+int cp_online_track_reset(const cp_online_track_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index,
+                          int32_t what, void* stream);
+int cp_online_track_push(const cp_online_track_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, const float* embeddings,
+                         const int32_t* row0, const int32_t* m, int32_t total_rows, int32_t* pred, int32_t* voted, float* logits,
+                         int32_t ldl, int32_t* updated, void* stream);
+int cp_online_track_rows(const cp_online_track_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index,
+                         float* rows_out, int64_t* n_updates_out, int64_t* n_refused_out, void* stream);
+
+/* ---- tracker sweep: many tracker settings over one recording's embeddings, scored on the device ------------------------------
+ * One wave per setting, each from a fresh tracker on rows (n_classes,16) (anchor = rows, empty ring), through the device
+ * function cp_online_track_push walks: setting g's pred, voted and updated sequences are the ones a fresh stream of the
+ * stage returns for the same embeddings, as class SLOTS (updated: slot or -1); (n_configs, n_rows) int32 each, optional.
+ * - expected_slot (n_rows) int32: the cue's slot, -1 for rest, anything else negative: the row is not scored.  tail_from: the
+ *   cue rows are counted from 0 in window order, and those with count >= tail_from are "the last quarter" (the caller sets
+ *   tail_from = n_cue - n_cue / 4).
+ * - scores (n_configs, CP_ONLINE_TRACK_SCORES) int64, over the scored rows: cue rows; cue rows with pred == cue; with voted
+ *   == cue; rows that updated; rows that were refused; rows that updated a slot other than the cue's (any update under
+ *   rest); pred hits in the last quarter; voted hits in the last quarter.
+ * - configs (n_configs) cp_online_track_config on the device, 8-byte aligned; a setting the stage would refuse (vote, rate)
+ *   scores -1 in every counter and its sequences are not written.
+ * - The host checks n_classes in 1..64, n_configs in 1..CP_ONLINE_TRACK_SWEEP_MAX_CONFIGS, n_rows in 1..2^31-1, pointers and
+ *   alignment (embeddings 16 bytes) and returns CP_ERR_ARG before anything is enqueued. */
+#define CP_ONLINE_TRACK_SCORES 8
+#define CP_ONLINE_TRACK_SWEEP_MAX_CONFIGS 65536
+int cp_online_track_sweep(const float* embeddings, int64_t n_rows, int32_t n_classes, const float* rows, const int32_t* expected_slot,
+                          int64_t tail_from, const cp_online_track_config* configs, int32_t n_configs, int64_t* scores,
+                          int32_t* pred, int32_t* voted, int32_t* updated, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

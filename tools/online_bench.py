@@ -40,6 +40,11 @@ With --finetune head fine-tuning (OnlineDecoder.finetune, csrc/online_finetune.c
 windows in f32 and bf16 the embedding pass, one step (median run of 100 steps), the bytes a step must move and the same step
 composed from torch ops on the same u; (c) on the synthetic people of --enroll the held-out accuracy of one-hot rows, enrolled
 rows and the fine-tuned head.
+With --track the prototype tracker (track.PrototypeTracker.push, csrc/online_track.cuh) is timed against the plain decoder.push
+in the same run: 1 and 25 windows on OnlineDecoder and 256 streams x 1 window on MultiStreamDecoder, a push that only gives out
+its embeddings, and the stage's launch alone (PrototypeTracker.apply on the embeddings of one push).  With --track-sweep the
+tracker sweep (track.sweep_tracker, ot_sweep_kernel) is timed on the synthetic drifting stream of 41 classes at 2,400 and 24,000
+rows for 64, 1,024 and 16,384 settings, next to the numpy definition for one setting.  Both together write one file.
 Each push is timed from the host with a synchronisation behind it (the latency a control loop sees); kernels per push are
 counted with torch.profiler over a few pushes.  One JSON line per case, and a table with --out.
 
@@ -55,6 +60,7 @@ counted with torch.profiler over a few pushes.  One JSON line per case, and a ta
     python tools/online_bench.py --map-sweep --iters 5 --out profiles/online_map_sweep.txt
     python tools/online_bench.py --finetune --iters 10 --out profiles/online_finetune.txt
     python tools/online_bench.py --realign --iters 20 --out profiles/online_realign.txt
+    python tools/online_bench.py --track --track-sweep --iters 100 --out profiles/online_track.txt
 """
 import argparse
 import json
@@ -119,7 +125,11 @@ def main():
                     "synthetic person")
     ap.add_argument("--realign", action="store_true", help="cue realignment: realign_cues against the definition, and enroll + "
                     "finetune on the raw cue, the realigned labels and the planted truth")
+    ap.add_argument("--track", action="store_true", help="the prototype tracker against the plain push, and its launch alone")
+    ap.add_argument("--track-sweep", action="store_true", help="sweep_tracker over a synthetic drifting stream, next to the definition")
     a = ap.parse_args()
+    if a.track or a.track_sweep:
+        return track_main(a)
     if a.enroll:
         return enroll_main(a)
     if a.realign:
@@ -844,6 +854,115 @@ class _Ids:
 
     def push(self, *a, **k):
         raise RuntimeError("apply() does not push the decoder")
+
+
+def track_main(a):
+    """--track: tracked against plain pushes, interleaved case by case in one run (rate 0.05 and every bound open, so that
+    every window runs the float64 update); --track-sweep: one sweep_tracker call per case (scores on the host)."""
+    from contrastiveprosthetics_amd import track as T
+    rows, sweeps = [], []
+    if a.track:
+        torch.manual_seed(0)
+        e = Engine(adabn=False, dtype="f32", device="cuda:0")
+        e.init_parameters(1)
+        stream = (torch.randn(200000, 12) * 2e-3).cuda()
+        mean, std = torch.full((12,), 0.4).cuda(), torch.full((12,), 0.1).cuda()
+        classes = list(range(41))
+        settings = dict(rate=0.05, min_cosine=-2.0, min_margin=0.0, min_anchor_cosine=-2.0, agree=False)
+        for dtype in ("f32", "bf16"):
+            for S, n in ((1, 20), (1, 500), (256, 20)):
+                m = n // 20
+                if S == 1:
+                    plain, tracked = (OnlineDecoder(e, mean, std, classes=classes, dtype=dtype) for _ in range(2))
+                else:
+                    plain, tracked = (MultiStreamDecoder(e, mean, std, S, dtype=dtype, max_rows=S * m) for _ in range(2))
+                    for s in range(S):
+                        plain.set_classes(s, classes=classes)
+                        tracked.set_classes(s, classes=classes)
+                tracker = T.PrototypeTracker(tracked, **settings)
+                pos = [0]
+                span = stream.shape[0] - S * n
+
+                def chunk():
+                    base = pos[0] % span
+                    pos[0] += S * n
+                    return stream[base:base + S * n]
+
+                if S == 1:
+                    fns = (("plain", lambda: plain.push(chunk())), ("embeddings", lambda: plain.push(chunk(), return_embeddings=True)),
+                           ("tracked", lambda: tracker.push(chunk())))
+                else:
+                    fns = (("plain", lambda: plain.push_packed(chunk(), [n] * S)),
+                           ("embeddings", lambda: plain.push_packed(chunk(), [n] * S, return_embeddings=True)),
+                           ("tracked", lambda: tracker.push_packed(chunk(), [n] * S)))
+                res = {}
+                for name, fn in fns:
+                    med, p90 = time_pushes(fn, a.iters, a.warmup)
+                    res[name] = med
+                    rows.append(dict(kind=name, dtype=dtype, streams=S, windows=m, median_us=round(med, 1), p90_us=round(p90, 1),
+                                     kernels_per_push=count_kernels(fn, pushes=3)))
+                emb = [r[-1] for r in plain.push_packed(chunk(), [n] * S, return_embeddings=True)] if S > 1 \
+                    else plain.push(chunk(), return_embeddings=True)[-1]
+                alone = T.PrototypeTracker(plain, **settings)
+                med, p90 = time_pushes(lambda: alone.apply(emb), a.iters, a.warmup)
+                rows.append(dict(kind="stage alone", dtype=dtype, streams=S, windows=m, median_us=round(med, 1), p90_us=round(p90, 1),
+                                 kernels_per_push=count_kernels(lambda: alone.apply(emb), pushes=3)))
+                for r in rows[-4:]:
+                    r["tracked_minus_plain_us"] = round(res["tracked"] - res["plain"], 1)
+                    print(json.dumps(r), flush=True)
+                del plain, tracked, tracker, alone
+                torch.cuda.empty_cache()
+    if a.track_sweep:
+        base = dict(min_cosine=0.3, min_margin=0.02, min_anchor_cosine=0.5)
+        grids = {64: dict(rate=[0.0, 0.01, 0.02, 0.05], agree=[True, False], vote=[10, 25], min_anchor_cosine=[0.5, 0.7, 0.8, 0.9])}
+        grids[1024] = dict(grids[64], min_cosine=[0.2, 0.3, 0.4, 0.5], min_margin=[0.0, 0.02, 0.05, 0.1])
+        grids[16384] = dict(grids[1024], rate=[i / 256 for i in range(64)])
+        for m in (2400, 24000):
+            emb, exp, anchor = T.drifting_stream(m, 41, seed=3, noise=0.4, degrees=40.0, segment=50)
+            ids = np.arange(41)
+            dev = torch.from_numpy(emb).cuda()
+            t0 = time.perf_counter()
+            ref = T.track_reference(emb, anchor, ids, expected=exp, **dict(base, rate=0.05, agree=True, vote=25))["scores"]
+            ref_ms = (time.perf_counter() - t0) * 1e3
+            for G, lists in grids.items():
+                configs = [dict(base, **c) for c in T.track_grid(**lists)]
+                assert len(configs) == G
+                sc = T.sweep_tracker(dev, exp, ids, anchor, configs)
+                ts = []
+                for _ in range(min(a.iters, 10)):
+                    t0 = time.perf_counter()
+                    T.sweep_tracker(dev, exp, ids, anchor, configs)          # (returns host arrays: it has synchronised)
+                    ts.append(time.perf_counter() - t0)
+                g = T.pick_tracker(sc)
+                frozen = int(np.max(sc["voted_hit_tail"][[i for i, c in enumerate(configs) if c["rate"] == 0.0]]))
+                r = dict(rows=m, configs=G, sweep_ms=round(float(np.median(ts)) * 1e3, 3), reference_one_setting_ms=round(ref_ms, 1),
+                         picked=configs[g] if g is not None else None, picked_voted_hit_tail=int(sc["voted_hit_tail"][g]) if g is not None else -1,
+                         frozen_voted_hit_tail=frozen, tail_rows=int(sc["n_cue"][0]) // 4,
+                         reference_voted_hit_tail=ref["voted_hit_tail"])
+                print(json.dumps(r), flush=True)
+                sweeps.append(r)
+    if a.out:
+        dev = torch.cuda.get_device_name(0)
+        with open(a.out, "w") as f:
+            f.write(f"# tools/online_bench.py{' --track' if a.track else ''}{' --track-sweep' if a.track_sweep else ''} --iters {a.iters} "
+                    f"--warmup {a.warmup} on {dev}\n")
+            if rows:
+                f.write("# plain = decoder.push, embeddings = decoder.push(return_embeddings=True), tracked = PrototypeTracker.push on a\n"
+                        "# decoder of its own, stage alone = PrototypeTracker.apply on the embeddings of one push; per-push wall time,\n"
+                        "# host-synchronised (median, p90), kernels per push (torch.profiler: library kernels plus torch's own), delta =\n"
+                        "# tracked - plain median\n")
+                f.write(f"{'kind':<12} {'dtype':<5} {'streams':>7} {'windows':>7} {'median_us':>10} {'p90_us':>9} {'kernels':>8} {'delta_us':>9}\n")
+                for r in rows:
+                    f.write(f"{r['kind']:<12} {r['dtype']:<5} {r['streams']:>7} {r['windows']:>7} {r['median_us']:>10.1f} {r['p90_us']:>9.1f} "
+                            f"{r['kernels_per_push']:>8.1f} {r['tracked_minus_plain_us']:>9.1f}\n")
+            if sweeps:
+                f.write("# sweep = one sweep_tracker call over the synthetic drifting stream of 41 classes (scores on the host), wall time,\n"
+                        "# median; reference = track_reference (numpy) for ONE setting; hits in the last quarter of the cue rows: the\n"
+                        "# picked setting's and the best frozen (rate 0) setting's\n")
+                f.write(f"{'rows':>6} {'configs':>7} {'sweep_ms':>9} {'reference_ms':>13} {'tail_rows':>9} {'picked_hits':>11} {'frozen_hits':>11}  picked\n")
+                for r in sweeps:
+                    f.write(f"{r['rows']:>6} {r['configs']:>7} {r['sweep_ms']:>9.3f} {r['reference_one_setting_ms']:>13.1f} {r['tail_rows']:>9} "
+                            f"{r['picked_voted_hit_tail']:>11} {r['frozen_voted_hit_tail']:>11}  {json.dumps(r['picked'])}\n")
 
 
 def _cued_logits(m, k, seed=0):
