@@ -28,4 +28,8 @@ def __getattr__(name):
                 "TRACK_SCORE_KEYS"):
         from . import track
         return getattr(track, name)
+    if name in ("score_enrolment", "score_plans", "holdout_logits", "holdout_reference", "holdout_logits_reference", "repetitions",
+                "learning_curve", "plan_grid", "assign_folds", "HOLDOUT_SCORE_KEYS"):       # (holdout.leave_one_out: by module)
+        from . import holdout
+        return getattr(holdout, name)
     raise AttributeError(name)

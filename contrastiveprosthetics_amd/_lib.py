@@ -98,6 +98,11 @@ class cp_online_track_config(C.Structure):
                 ("min_margin", C.c_float), ("min_anchor_cosine", C.c_float), ("reserved0", C.c_int32)]
 
 
+class cp_online_holdout_plan(C.Structure):
+    _fields_ = [("train", C.c_uint32), ("eval", C.c_uint32), ("sums_index", C.c_int32), ("min_windows", C.c_int32),
+                ("mix", C.c_double)]
+
+
 class cp_augment(C.Structure):
     """Settings of one cp_gather_groups_aug launch (include/cpnative.h)."""
     _fields_ = [("seed", C.c_uint32), ("salt", C.c_uint32), ("salt_state_lo", C.c_uint32), ("salt_state_hi", C.c_uint32),
@@ -143,6 +148,7 @@ CP_ONLINE_FINETUNE_CHUNK, CP_ONLINE_FINETUNE_PROJECTION, CP_ONLINE_FINETUNE_ROWS
 CP_ONLINE_REALIGN_MAX_ACTIVITY, CP_ONLINE_REALIGN_MAX_REGION = 4095, 4096
 CP_ONLINE_TRACK_SCORES, CP_ONLINE_TRACK_SWEEP_MAX_CONFIGS = 8, 65536
 CP_ONLINE_TRACK_RESET_RING, CP_ONLINE_TRACK_RESET_ROWS = 0, 1
+CP_ONLINE_HOLDOUT_SCORES, CP_ONLINE_HOLDOUT_MAX_PLANS, CP_ONLINE_HOLDOUT_MAX_REPS = 9, 4096, 32
 
 # what the four map sweep entries take behind their workspace: rms, n_windows, mean_std, map_src, map_fill, n_maps, n_classes,
 # expected_slot, chunk_rows, scratch, scratch_bytes, pred, voted, scores, class_hits, stream
@@ -310,6 +316,11 @@ SYMBOLS = {
                                        _fp, C.c_int32, _fp, _fp]),
     "cp_online_track_rows": (C.c_int, [_P(cp_online_track_config), C.c_int32, _fp, C.c_size_t, C.c_int32, _fp, _fp, _fp, _fp]),
     "cp_online_track_sweep": (C.c_int, [_fp, C.c_int64, C.c_int32, _fp, _fp, C.c_int64, _fp, C.c_int32, _fp, _fp, _fp, _fp, _fp]),
+    "cp_online_holdout_sums": (C.c_int, [_fp, C.c_int64, C.c_int32, _fp, _fp, _fp, C.c_int32, _fp, _fp]),
+    "cp_online_holdout_tables": (C.c_int, [_fp, C.c_int32, C.c_int32, _fp, _fp, C.c_int32, _fp, _fp, _fp]),
+    "cp_online_holdout_score": (C.c_int, [_fp, C.c_int64, C.c_int32, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp,
+                                          _fp]),
+    "cp_online_holdout_logits": (C.c_int, [_fp, C.c_int64, C.c_int32, _fp, C.c_int32, _fp, _fp, C.c_int32, _fp]),
 }
 
 KERNEL_KINDS = ["gather", "prep", "conv1_fwd", "bn_finalize", "conv2_fwd", "fold", "fc_fwd", "dropout", "proj_fwd",

@@ -1,7 +1,7 @@
 // Host layer of the online decoders (include/cpnative.h, cp_online_*): workspace layout, argument checks, launch chains and
 // the extern "C" entries of the folded, adaptive, multi-stream and adaptive multi-stream decoders, class enrolment, head
-// fine-tuning, the command gate, the grasp drive, the gate sweep, the subset sweep, the electrode-map sweep, cue realignment and prototype
-// tracking.  Host code only; api.hip includes it behind its own helpers (fail, CK, CKL) and encoder_api.cuh's (align256, fcK),
+// fine-tuning, the command gate, the grasp drive, the gate sweep, the subset sweep, the electrode-map sweep, cue realignment, prototype
+// tracking and held-out enrolment scoring.  Host code only; api.hip includes it behind its own helpers (fail, CK, CKL) and encoder_api.cuh's (align256, fcK),
 // so the library stays one translation unit.  The four decoders share one workspace description (OlWS, ol_carve), one
 // parameter check, one set of front-end arguments, one folded chain and one unfolded weight copy; what an entry adds is its
 // name in the refusals and the kernels it launches.
@@ -1968,5 +1968,97 @@ extern "C" int cp_online_track_sweep(const float* embeddings, int64_t n_rows, in
     hipLaunchKernelGGL(ot_sweep_kernel, dim3((n_configs + OT_SWEEP_WAVES - 1) / OT_SWEEP_WAVES), dim3(64 * OT_SWEEP_WAVES), 0,
                        (hipStream_t)stream, a);
     CKL("ot_sweep_kernel");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// held-out enrolment scoring (csrc/online_holdout.cuh): sums per training mask, rows per plan, one wave per plan over the
+// evaluated windows, and the held-out logits.  Plans and masks live on the device and are checked by the kernels.
+// ---------------------------------------------------------------------------------------
+static_assert(OH_SCORES == CP_ONLINE_HOLDOUT_SCORES && OH_MAX_PLANS == CP_ONLINE_HOLDOUT_MAX_PLANS &&
+              OH_MAX_REPS == CP_ONLINE_HOLDOUT_MAX_REPS && OH_MAXK == CP_ONLINE_MAX_CLASSES && OH_D == CP_D_E, "hold-out constants");
+static_assert(sizeof(OhPlan) == sizeof(cp_online_holdout_plan) && sizeof(OhPlan) == 24 &&
+              offsetof(OhPlan, sums_index) == offsetof(cp_online_holdout_plan, sums_index) &&
+              offsetof(OhPlan, mix) == offsetof(cp_online_holdout_plan, mix), "the kernels read cp_online_holdout_plan as OhPlan");
+static_assert(sizeof(OlState) == 7672 && sizeof(OlmMeta) == 16 && sizeof(OlaHead) == 16 && OLAM_STATS * 8 == 9 * 2 * 512 * 8,
+              "holdout.score_enrolment keeps a copy of what ol_carve lays in front of the weights and puts it back");
+
+// what the four entries share: the recording's size and class count
+static int oh_check_shape(const char* who, int64_t n_rows, int32_t n_classes) {
+    if (n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return ol_fail(CP_ERR_ARG, who, "n_classes outside 1..64");
+    if (n_rows < 1 || n_rows > INT32_MAX) return ol_fail(CP_ERR_ARG, who, "n_rows outside 1..2^31-1");
+    return 0;
+}
+
+extern "C" int cp_online_holdout_sums(const float* embeddings, int64_t n_rows, int32_t n_classes, const int32_t* slot,
+                                      const int32_t* rep, const uint32_t* train_masks, int32_t n_masks, double* sums, void* stream) {
+    const char* who = "cp_online_holdout_sums";
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (int e = oh_check_shape(who, n_rows, n_classes)) return e;
+    if (n_masks < 1 || n_masks > CP_ONLINE_HOLDOUT_MAX_PLANS) return bad("n_masks outside 1..4096");
+    if (!embeddings || !slot || !rep || !train_masks || !sums) return bad("embeddings, slot, rep, train_masks and sums are required");
+    if ((uintptr_t)embeddings % 16) return bad("embeddings must be 16-byte aligned");
+    if ((uintptr_t)slot % 4 || (uintptr_t)rep % 4 || (uintptr_t)train_masks % 4 || (uintptr_t)sums % 8) return bad("misaligned argument");
+    hipLaunchKernelGGL(oh_sums_kernel, dim3((n_masks + OH_SUM_MASKS - 1) / OH_SUM_MASKS, OH_MAXK), dim3(64), 0, (hipStream_t)stream,
+                       embeddings, (long long)n_rows, (int)n_classes, slot, rep, train_masks, (int)n_masks, sums);
+    CKL("oh_sums_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_holdout_tables(const double* sums, int32_t n_masks, int32_t n_classes, const float* prior,
+                                        const cp_online_holdout_plan* plans, int32_t n_plans, float* rows, float* unit, void* stream) {
+    const char* who = "cp_online_holdout_tables";
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return bad("n_classes outside 1..64");
+    if (n_masks < 1 || n_masks > CP_ONLINE_HOLDOUT_MAX_PLANS) return bad("n_masks outside 1..4096");
+    if (n_plans < 1 || n_plans > CP_ONLINE_HOLDOUT_MAX_PLANS) return bad("n_plans outside 1..4096");
+    if (!sums || !prior || !plans || !rows || !unit) return bad("sums, prior, plans, rows and unit are required");
+    if ((uintptr_t)sums % 8 || (uintptr_t)plans % 8 || (uintptr_t)prior % 4 || (uintptr_t)rows % 4 || (uintptr_t)unit % 16)
+        return bad("misaligned argument (unit: 16 bytes)");
+    hipLaunchKernelGGL(oh_tables_kernel, dim3(n_plans), dim3(64), 0, (hipStream_t)stream, sums, (int)n_masks, (int)n_classes, prior,
+                       (const OhPlan*)plans, rows, unit);
+    CKL("oh_tables_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_holdout_score(const float* embeddings, int64_t n_rows, int32_t n_classes, const int32_t* slot,
+                                       const int32_t* rep, const float* unit, const cp_online_holdout_plan* plans, int32_t n_plans,
+                                       int32_t vote, int64_t* scores, int32_t* confusion, int32_t* voted_confusion, int32_t* pred,
+                                       int32_t* voted, void* stream) {
+    const char* who = "cp_online_holdout_score";
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (int e = oh_check_shape(who, n_rows, n_classes)) return e;
+    if (n_plans < 1 || n_plans > CP_ONLINE_HOLDOUT_MAX_PLANS) return bad("n_plans outside 1..4096");
+    if (vote < 1 || vote > CP_ONLINE_MAX_VOTE) return bad("vote outside 1..256");
+    if (!embeddings || !slot || !rep || !unit || !plans || !scores) return bad("embeddings, slot, rep, unit, plans and scores are required");
+    if ((uintptr_t)embeddings % 16 || (uintptr_t)unit % 16) return bad("embeddings and unit must be 16-byte aligned");
+    if ((uintptr_t)slot % 4 || (uintptr_t)rep % 4 || (uintptr_t)plans % 8 || (uintptr_t)scores % 8 || (uintptr_t)confusion % 4 ||
+        (uintptr_t)voted_confusion % 4 || (uintptr_t)pred % 4 || (uintptr_t)voted % 4)
+        return bad("misaligned argument");
+    OhScoreArgs a{};
+    a.emb = embeddings; a.slot = slot; a.rep = rep; a.unit = unit; a.plans = (const OhPlan*)plans; a.n_rows = n_rows;
+    a.n_plans = n_plans; a.K = n_classes; a.vote = vote; a.scores = (long long*)scores; a.confusion = confusion;
+    a.voted_confusion = voted_confusion; a.pred = pred; a.voted = voted;
+    if (confusion || voted_confusion) {
+        hipLaunchKernelGGL(oh_score_kernel<true>, dim3(n_plans), dim3(64), 0, (hipStream_t)stream, a);
+    } else {
+        hipLaunchKernelGGL(oh_score_kernel<false>, dim3(n_plans), dim3(64), 0, (hipStream_t)stream, a);
+    }
+    CKL("oh_score_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_holdout_logits(const float* embeddings, int64_t n_rows, int32_t n_classes, const float* unit, int32_t n_plans,
+                                        const int32_t* assign, float* logits, int32_t ldl, void* stream) {
+    const char* who = "cp_online_holdout_logits";
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (int e = oh_check_shape(who, n_rows, n_classes)) return e;
+    if (n_plans < 1 || n_plans > CP_ONLINE_HOLDOUT_MAX_PLANS) return bad("n_plans outside 1..4096");
+    if (ldl < n_classes) return bad("ldl must be at least n_classes");
+    if (!embeddings || !unit || !assign || !logits) return bad("embeddings, unit, assign and logits are required");
+    if ((uintptr_t)embeddings % 4 || (uintptr_t)unit % 4 || (uintptr_t)assign % 4 || (uintptr_t)logits % 4) return bad("misaligned argument");
+    hipLaunchKernelGGL(oh_logits_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, embeddings,
+                       (long long)n_rows, (int)n_classes, unit, (int)n_plans, assign, logits, (int)ldl);
+    CKL("oh_logits_kernel");
     return 0;
 }

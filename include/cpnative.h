@@ -1269,6 +1269,65 @@ int cp_online_track_sweep(const float* embeddings, int64_t n_rows, int32_t n_cla
                           int64_t tail_from, const cp_online_track_config* configs, int32_t n_configs, int64_t* scores,
                           int32_t* pred, int32_t* voted, int32_t* updated, void* stream);
 
+/* ---- held-out enrolment scoring: leave-a-repetition-out over one recording's embeddings ---------------------------------------
+ * A plan trains class rows on the windows of some repetitions and scores them on the windows of others, as enrolment with
+ * masked labels, a fresh decoder and a push would, from the embeddings alone (csrc/online_holdout.cuh).  holdout_reference of
+ * contrastiveprosthetics_amd/holdout.py is the definition; the device equals it in every integer and bit.  Every f32 and f64
+ * operation is rounded on its own (no contraction).
+ * - The recording: embeddings (n_rows,16) f32; slot (n_rows) int32, the cue's class slot, -1 for rest, anything else (also a
+ *   slot >= n_classes): the window trains nothing and is not scored; rep (n_rows) int32, the window's repetition in 0..31,
+ *   anything else: the window neither trains nor is evaluated.
+ * - cp_online_holdout_sums: sums (n_masks,64,17) f64, the accumulator layout of cp_online_enroll.  sums[u][c][d] starts at 0
+ *   and takes one add of (double)embeddings[i][d] per window i in ascending i with slot[i] == c and bit rep[i] of
+ *   train_masks[u] set; sums[u][c][16] is the count of those windows.  Slots >= n_classes hold 0.  train_masks (n_masks)
+ *   uint32 on the device.
+ * - cp_online_holdout_tables: for plan t with S = sums[plans[t].sums_index], slot c: len = (double)sqrtf(sum_d prior[c][d]^2)
+ *   in f32, d ascending; sn = sqrt(sum_d S[c][d]^2) in f64; enrolled iff S[c][16] >= min_windows and sn > 0;
+ *   rows[t][c][d] = (float)((1 - mix) * (double)prior[c][d] + mix * (len * (S[c][d] / sn))), or prior[c][d] itself if not
+ *   enrolled: the row cp_online_enroll_table writes.  unit[t][c][d] = rows[t][c][d] / sqrtf(sum_d rows[t][c][d]^2), f32, d
+ *   ascending: the row cp_online_set_classes keeps.  rows, unit (n_plans,n_classes,16) f32; prior (n_classes,16) f32.
+ * - cp_online_holdout_score: one wave per plan over the windows with bit rep[i] of plans[t].eval set, in ascending i:
+ *   l[k] = sum_d embeddings[i][d] * unit[t][k][d] in f32, d ascending, from 0.f (the tail's operations); the prediction is
+ *   none (-1) if any of the n_classes logits is not finite, else the first maximum under `>` (the lowest slot on ties); the
+ *   decoders' vote ring of `vote` slots runs from empty over the plan's evaluated windows, a "none" takes a place and does not
+ *   vote; the voted slot is the one with the most entries, the smallest among equals, none if no slot has an entry.
+ *   scores (n_plans, CP_ONLINE_HOLDOUT_SCORES) int64: evaluated windows with a cue slot (n_cue); of those, windows whose
+ *   prediction is the cue (pred_hit); whose vote is the cue (voted_hit); evaluated rest windows (n_rest); training windows,
+ *   those with a cue slot and bit rep[i] of plans[t].train set (n_train); slots with at least min_windows of them
+ *   (n_enrolled); the slot with the smallest voted recall among slots with cue windows, fractions compared by
+ *   cross-multiplication in 64 bits, the smallest slot among equals (worst_class, -1 if none), its hits and its count.
+ *   confusion, voted_confusion (n_plans,64,64) int32, optional: cell [cue slot][predicted / voted slot] over the cue windows,
+ *   "none" not counted.  pred, voted (n_plans,n_rows) int32, optional: slot, -1 none, -3 for a window the plan does not
+ *   evaluate.
+ * - cp_online_holdout_logits: logits[i][k] = the l[k] above of window i against unit[assign[i]], k < n_classes; NaN where
+ *   assign[i] is outside 0..n_plans-1.  assign (n_rows) int32; logits (n_rows, ldl) f32.
+ * - plans (n_plans) cp_online_holdout_plan on the device, 8-byte aligned, checked by the kernels: a plan with mix outside
+ *   [0, 1] or NaN, min_windows < 1 or sums_index outside 0..n_masks-1 (cp_online_holdout_score, which is not told n_masks:
+ *   0..CP_ONLINE_HOLDOUT_MAX_PLANS-1) scores -1 in every counter, and nothing else of it is written.
+ * - The host checks n_classes in 1..64, n_rows in 1..2^31-1, n_masks and n_plans in 1..CP_ONLINE_HOLDOUT_MAX_PLANS, vote in
+ *   1..256, ldl >= n_classes, pointers and alignment (embeddings and unit 16 bytes where a wave reads whole rows) and returns
+ *   CP_ERR_ARG with a cp_last_error that names the entry before anything is enqueued.  The entries never allocate and never
+ *   synchronise. */
+#define CP_ONLINE_HOLDOUT_SCORES 9
+#define CP_ONLINE_HOLDOUT_MAX_PLANS 4096
+#define CP_ONLINE_HOLDOUT_MAX_REPS 32
+typedef struct cp_online_holdout_plan {
+    uint32_t train;              /* bit r: the windows of repetition r train the rows */
+    uint32_t eval;               /* bit r: the windows of repetition r are scored */
+    int32_t sums_index;          /* which of the n_masks sums holds this plan's training mask */
+    int32_t min_windows;         /* a class with fewer training windows keeps its prior row; at least 1 */
+    double mix;                  /* in [0, 1]: the share of the prototype in the row */
+} cp_online_holdout_plan;
+int cp_online_holdout_sums(const float* embeddings, int64_t n_rows, int32_t n_classes, const int32_t* slot, const int32_t* rep,
+                           const uint32_t* train_masks, int32_t n_masks, double* sums, void* stream);
+int cp_online_holdout_tables(const double* sums, int32_t n_masks, int32_t n_classes, const float* prior,
+                             const cp_online_holdout_plan* plans, int32_t n_plans, float* rows, float* unit, void* stream);
+int cp_online_holdout_score(const float* embeddings, int64_t n_rows, int32_t n_classes, const int32_t* slot, const int32_t* rep,
+                            const float* unit, const cp_online_holdout_plan* plans, int32_t n_plans, int32_t vote, int64_t* scores,
+                            int32_t* confusion, int32_t* voted_confusion, int32_t* pred, int32_t* voted, void* stream);
+int cp_online_holdout_logits(const float* embeddings, int64_t n_rows, int32_t n_classes, const float* unit, int32_t n_plans,
+                             const int32_t* assign, float* logits, int32_t ldl, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

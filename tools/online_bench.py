@@ -45,6 +45,10 @@ in the same run: 1 and 25 windows on OnlineDecoder and 256 streams x 1 window on
 its embeddings, and the stage's launch alone (PrototypeTracker.apply on the embeddings of one push).  With --track-sweep the
 tracker sweep (track.sweep_tracker, ot_sweep_kernel) is timed on the synthetic drifting stream of 41 classes at 2,400 and 24,000
 rows for 64, 1,024 and 16,384 settings, next to the numpy definition for one setting.  Both together write one file.
+With --holdout held-out enrolment scoring (holdout.score_plans, csrc/online_holdout.cuh) is timed on a synthetic person of 41
+classes x 6 repetitions (about 14,500 windows): the embedding pass, the 30 learning-curve plans and a 4,096-plan grid, the numpy
+definition for the 30 plans, the host loop it replaces (masked enroll + set_classes + push per leave-one-out fold) and
+score_enrolment as a whole; the loop's hits per fold are written next to the sweep's.
 Each push is timed from the host with a synchronisation behind it (the latency a control loop sees); kernels per push are
 counted with torch.profiler over a few pushes.  One JSON line per case, and a table with --out.
 
@@ -61,6 +65,7 @@ counted with torch.profiler over a few pushes.  One JSON line per case, and a ta
     python tools/online_bench.py --finetune --iters 10 --out profiles/online_finetune.txt
     python tools/online_bench.py --realign --iters 20 --out profiles/online_realign.txt
     python tools/online_bench.py --track --track-sweep --iters 100 --out profiles/online_track.txt
+    python tools/online_bench.py --holdout --iters 10 --out profiles/online_holdout.txt
 """
 import argparse
 import json
@@ -127,7 +132,11 @@ def main():
                     "finetune on the raw cue, the realigned labels and the planted truth")
     ap.add_argument("--track", action="store_true", help="the prototype tracker against the plain push, and its launch alone")
     ap.add_argument("--track-sweep", action="store_true", help="sweep_tracker over a synthetic drifting stream, next to the definition")
+    ap.add_argument("--holdout", action="store_true", help="held-out enrolment scoring: score_plans against the definition and against "
+                    "a masked enroll + set_classes + push loop per fold")
     a = ap.parse_args()
+    if a.holdout:
+        return holdout_main(a)
     if a.track or a.track_sweep:
         return track_main(a)
     if a.enroll:
@@ -963,6 +972,98 @@ def track_main(a):
                 for r in sweeps:
                     f.write(f"{r['rows']:>6} {r['configs']:>7} {r['sweep_ms']:>9.3f} {r['reference_one_setting_ms']:>13.1f} {r['tail_rows']:>9} "
                             f"{r['picked_voted_hit_tail']:>11} {r['frozen_voted_hit_tail']:>11}  {json.dumps(r['picked'])}\n")
+
+
+def holdout_main(a):
+    """--holdout: a synthetic person of 41 classes x 6 repetitions (a cue of 45 windows, 14 windows of rest behind it, about
+    14,500 windows) through an untrained model's folded decoder.  Timed: the embedding pass; score_plans over the 30
+    learning-curve plans and over a grid of 4,096 plans (32 plans x 16 mixes x 8 min_windows); holdout_reference for the 30
+    plans; the host loop this replaces for the 6 leave-one-out plans (masked enroll, which installs the rows, reset, push, hits
+    counted on the host); score_enrolment as a whole.  The loop's hits are compared with the sweep's."""
+    from contrastiveprosthetics_amd import holdout as H
+    from contrastiveprosthetics_amd.online import expected_commands
+    from contrastiveprosthetics_amd.track import embed_recording
+    torch.manual_seed(0)
+    rng = np.random.default_rng(0)
+    e = Engine(adabn=False, dtype="f32", device="cuda:0")
+    e.init_parameters(1)
+    mean, std = torch.full((12,), 0.4).cuda(), torch.full((12,), 0.1).cuda()
+    K, REPS, REST_LABEL = 41, 6, 41
+    ids = np.arange(K)
+    pattern = 0.3 + 1.7 * rng.random((K, 12))
+    raws, labs, sreps = [], [], []
+    for r in range(REPS):
+        for c in rng.permutation(K):
+            raws += [rng.standard_normal((900, 12)) * pattern[c] * (1.0 + 0.1 * rng.standard_normal(12)), rng.standard_normal((280, 12)) * 0.2]
+            labs += [np.full(900, c), np.full(280, REST_LABEL)]
+            sreps += [np.full(900, r), np.full(280, -1)]
+    raw = torch.from_numpy((np.concatenate(raws) * 2e-3).astype(np.float32)).cuda()
+    lab, srep = np.concatenate(labs).astype(np.int64), np.concatenate(sreps)
+    dec = OnlineDecoder(e, mean, std, classes=list(range(K)), dtype="f32")
+    exp = expected_commands(lab, ids, rest=REST_LABEL)
+    rep, n_rep = H.repetitions(exp)
+    assert n_rep == REPS
+    prior = dec.class_table()[0]
+    iters = min(a.iters, 10)
+    embed_ms = _wall(lambda: embed_recording(dec, raw), iters)
+    emb = embed_recording(dec, raw)
+    curve = H.learning_curve(REPS)
+    loo = H.leave_one_out(REPS)
+    both = [dict(train=2 ** REPS - 1, eval=2 ** REPS - 1, mix=1.0, min_windows=25), dict(train=0, eval=2 ** REPS - 1, mix=1.0, min_windows=25)]
+    grid = H.plan_grid(curve + both, mix=[i / 15 for i in range(16)], min_windows=[1, 5, 10, 25, 50, 100, 150, 200])
+    assert len(grid) == 4096
+    got = H.score_plans(emb, exp, ids, rep, prior, curve, vote=dec.vote)
+    t0 = time.perf_counter()
+    ref = H.holdout_reference(emb, exp, ids, rep, prior, curve, vote=dec.vote)
+    ref_ms = (time.perf_counter() - t0) * 1e3
+    equal = all(np.array_equal(got[k], ref[k]) for k in H.HOLDOUT_SCORE_KEYS) and \
+        got["rows"].cpu().numpy().tobytes() == ref["rows"].tobytes()
+    curve_ms = _wall(lambda: H.score_plans(emb, exp, ids, rep, prior, curve, vote=dec.vote), iters)       # (host arrays: it has synchronised)
+    grid_ms = _wall(lambda: H.score_plans(emb, exp, ids, rep, prior, grid, vote=dec.vote), iters)
+    whole_ms = _wall(lambda: H.score_enrolment(dec, raw, exp, plan="learning_curve"), iters)
+    table0 = dec.class_table()
+    cue = torch.from_numpy(exp).cuda()
+
+    def host_loop():
+        hits = []
+        for h in range(REPS):
+            dec.set_classes(table=table0[0], ids=table0[1])
+            dec.enroll(raw, np.where((lab == REST_LABEL) | (srep == h), -1, lab), mix=1.0, min_windows=25)
+            dec.reset()
+            pred = dec.push(raw)[0]
+            held = torch.from_numpy((rep == h) & (exp >= 0)).cuda()
+            hits.append(int(((pred == cue) & held).sum()))
+        return hits
+
+    loop_hits = host_loop()
+    loop_ms = _wall(host_loop, min(iters, 3), warmup=1)
+    dec.set_classes(table=table0[0], ids=table0[1])
+    dec.reset()
+    sweep = H.score_plans(emb, exp, ids, rep, prior, loo, vote=dec.vote)
+    r = dict(windows=int(emb.shape[0]), classes=K, repetitions=REPS, embed_ms=round(embed_ms, 3), curve_plans=len(curve),
+             curve_ms=round(curve_ms, 3), grid_plans=len(grid), grid_ms=round(grid_ms, 3), reference_curve_ms=round(ref_ms, 1),
+             device_equals_reference=bool(equal), score_enrolment_ms=round(whole_ms, 3), host_loop_folds=REPS, host_loop_ms=round(loop_ms, 3),
+             host_loop_hits=loop_hits, sweep_pred_hits=[int(x) for x in sweep["pred_hit"]],
+             curve={n: list(v) for n, v in H.score_enrolment(dec, raw, exp, plan="learning_curve")["curve"].items()})
+    print(json.dumps(r), flush=True)
+    if a.out:
+        dev = torch.cuda.get_device_name(0)
+        with open(a.out, "w") as f:
+            f.write(f"# tools/online_bench.py --holdout --iters {a.iters} on {dev}\n")
+            f.write("# A synthetic person (41 classes x 6 repetitions, cue 45 windows, rest 14; an untrained model's folded f32 decoder),\n"
+                    "# nothing about real subjects.  Wall time, host-synchronised, median.  embed = track.embed_recording; curve, grid = one\n"
+                    "# score_plans call (three launches, scores on the host); reference = holdout_reference (numpy) for the curve's plans;\n"
+                    "# host loop = per leave-one-out fold: set_classes, masked enroll, reset, push, hits counted; score_enrolment = embed +\n"
+                    "# curve + held-out logits.  The last lines: per fold the loop's and the sweep's raw hits on the held-out repetition, and\n"
+                    "# the curve, training repetitions -> (voted hits, cue windows) summed over the held-out repetitions.\n")
+            f.write(f"windows {r['windows']}  classes {K}  repetitions {REPS}\n")
+            f.write(f"{'what':<34} {'plans':>6} {'ms':>12}\n")
+            for what, plans, ms in (("embed", "", r["embed_ms"]), ("score_plans: learning curve", len(curve), r["curve_ms"]),
+                                    ("score_plans: grid", len(grid), r["grid_ms"]), ("holdout_reference: learning curve", len(curve), r["reference_curve_ms"]),
+                                    ("host loop: leave-one-out", REPS, r["host_loop_ms"]), ("score_enrolment: learning curve", len(curve), r["score_enrolment_ms"])):
+                f.write(f"{what:<34} {plans:>6} {ms:>12.3f}\n")
+            f.write(f"device equals reference: {r['device_equals_reference']}\n")
+            f.write(f"host loop hits  {r['host_loop_hits']}\nsweep pred_hit  {r['sweep_pred_hits']}\ncurve  {json.dumps(r['curve'])}\n")
 
 
 def _cued_logits(m, k, seed=0):
