@@ -138,6 +138,16 @@ class cp_debug_conv_args(C.Structure):
                 ("rows_out", C.POINTER(C.c_int32)), ("gcol_rows_out", C.POINTER(C.c_int32))]
 
 
+class cp_debug_proj_args(C.Structure):
+    """One launch sequence of the large-batch 512 -> 16 projection on caller buffers (include/cpnative.h): what cp_debug_proj takes."""
+    _fields_ = [("dtype", C.c_int32), ("kind", C.c_int32), ("M", C.c_int64),
+                ("Wp", C.c_void_p), ("act", C.c_void_p), ("r_exp", C.c_void_p), ("dz", C.c_void_p), ("scale", C.c_void_p),
+                ("shift", C.c_void_p), ("coef", C.c_void_p), ("w32", C.c_void_p), ("blast", C.c_void_p), ("out", C.c_void_p),
+                ("slabs", C.c_void_p), ("partials", C.c_void_p), ("praw", C.c_void_p), ("dzsum", C.c_void_p),
+                ("dp_thresh", C.c_uint32), ("dp_key", C.c_uint32), ("dp_inv_keep", C.c_float), ("reserved0", C.c_int32),
+                ("rows_out", C.POINTER(C.c_int32))]
+
+
 CP_ONLINE_MAX_CLASSES, CP_ONLINE_MAX_VOTE, CP_ONLINE_MAX_WINDOWS, CP_ONLINE_STRIDE = 64, 256, 256, 20
 CP_ONLINE_MULTI_MAX_STREAMS, CP_ONLINE_MULTI_MAX_ROWS = 256, 65536
 CP_ONLINE_GATE_SCORES, CP_ONLINE_GATE_SWEEP_MAX_CONFIGS = 10, 65536
@@ -203,6 +213,7 @@ SYMBOLS = {
     "cp_debug_gemm": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "cp_debug_fc_gemm": (C.c_int, [_P(cp_debug_fc_gemm_args), _fp]),
     "cp_debug_conv": (C.c_int, [_P(cp_debug_conv_args), _fp]),
+    "cp_debug_proj": (C.c_int, [_P(cp_debug_proj_args), _fp]),
     "cp_online_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "cp_online_prepare": (C.c_int, [_P(cp_online_config), _P(cp_params), _P(cp_bn_buffers), C.c_float, _fp, C.c_size_t, _fp]),
     "cp_online_set_classes": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, _fp, C.c_int32, _fp]),

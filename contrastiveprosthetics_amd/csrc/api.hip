@@ -971,6 +971,104 @@ extern "C" int cp_debug_conv(const cp_debug_conv_args* args, void* stream) {
     return debug_conv_t<float>(args, (hipStream_t)stream);
 }
 
+// One launch sequence of the 512 -> 16 projection on caller buffers, through the launch functions of the step
+// (csrc/encoder_api.cuh, gemm_ws.cuh: their row splits, grids and partial-row counts), at any row count
+template <typename T>
+static int debug_proj_t(const cp_debug_proj_args* d, hipStream_t st) {
+    const ProjLaunch pl{st, d->M, d->partials};
+    const T* dz = (const T*)d->dz;
+    const int* r_exp = (const int*)d->r_exp;
+    ProjDrop dp{};
+    dp.dp_thresh = d->dp_thresh; dp.dp_key = d->dp_key; dp.dp_inv_keep = d->dp_inv_keep;
+    const bool drop = dp.dp_thresh != 0;
+    int rows = 0;
+    switch (d->kind) {
+    case 0:
+        if (drop && !r_exp) {
+            // (encoder_forward_t: the copy is one job of the batched launch at the start of the pass)
+            FoldBatch fb{};
+            fb.job[0] = FoldJob{d->Wp, nullptr, d->w32, d->blast, CP_D_E, 512, 32};
+            hipLaunchKernelGGL((fold_copy_batch_kernel<T>), dim3(32, 1), dim3(256), 0, st, fb);
+            CKL("fold_copy_batch_kernel(last)");
+        } else {
+            launch_proj_fold<T>(d->Wp, drop ? (const float*)nullptr : d->scale, drop ? (const float*)nullptr : d->shift, d->w32, d->blast, st);
+            CKL("fold_linear_kernel(last)");
+        }
+        if (int e = launch_proj_fwd<T>(pl, d->act, r_exp, d->w32, d->blast, d->scale, d->shift, dp, (float*)d->out)) return e;
+        break;
+    case 1:
+        if (int e = proj_dz_sums<T>(pl, dz, d->dzsum)) return e;
+        if (int e = launch_proj_wgrad_tn<T>(pl, st, dz, d->act, r_exp, d->slabs, nullptr, nullptr, dp, d->scale, d->shift, d->dzsum, (float*)d->out,
+                                            d->praw, &rows)) return e;
+        if (int e = proj_sums_from_wgrad(pl, d->Wp, d->praw, d->dzsum)) return e;
+        break;
+    case 2:
+        if (int e = launch_proj_wgrad_tn<T>(pl, st, dz, d->act, nullptr, d->slabs, d->scale, d->shift, dp, nullptr, nullptr, nullptr, (float*)d->out,
+                                            nullptr, &rows)) return e;
+        break;
+    default:
+        if constexpr (sizeof(T) == 2) {
+            if (d->kind == 3) {
+                if (int e = launch_proj_wgrad_onepass(pl, dz, d->act, r_exp, d->slabs, dp, d->scale, d->shift, d->Wp, (float*)d->out, &rows)) return e;
+            } else {
+                launch_proj_transpose<T>(d->Wp, d->w32, st);
+                CKL("transpose_w_kernel(last)");
+                GemmNTArgs a{};
+                a.A = dz; a.lda = 64; a.M = d->M; a.K = 64;
+                a.W = d->w32; a.F = 512;
+                a.C = d->out; a.ldc = 512; a.R = d->act; a.ldr = 512; a.partials = d->partials;
+                a.dp_thresh = dp.dp_thresh; a.dp_key = dp.dp_key; a.dp_inv_keep = dp.dp_inv_keep;
+                a.coef = d->coef; a.coef_mod = 512;
+                CK(launch_proj_dgrad(a, st, &rows));
+            }
+        }
+        break;
+    }
+    if (d->rows_out) *d->rows_out = rows;
+    return 0;
+}
+
+// everything a launcher would refuse, or a kernel would read or write out of bounds, before anything launches
+static int check_debug_proj(const cp_debug_proj_args* d) {
+    if (!d) return fail(CP_ERR_ARG, "cp_debug_proj args");
+    if (d->dtype != CP_F32 && d->dtype != CP_BF16) return fail(CP_ERR_ARG, "cp_debug_proj: dtype must be CP_F32 or CP_BF16");
+    if (d->kind < 0 || d->kind > 4) return fail(CP_ERR_ARG, "cp_debug_proj: kind must be 0..4");
+    if (d->M <= 0) return fail(CP_ERR_ARG, "cp_debug_proj: M must be positive");
+    const int k = d->kind;
+    const bool b16 = d->dtype == CP_BF16;
+    if (k >= 3 && !b16) return fail(CP_ERR_ARG, "cp_debug_proj: kinds 3 and 4 belong to CP_BF16");
+    if (d->r_exp && (!b16 || k == 2 || k == 4)) return fail(CP_ERR_ARG, "cp_debug_proj: an e4m3 activation (r_exp) belongs to kinds 0, 1 and 3 under CP_BF16");
+    if (!d->Wp || !d->act || !d->out) return fail(CP_ERR_ARG, "cp_debug_proj: Wp, act and out must not be NULL");
+    if (k != 0 && !d->dz) return fail(CP_ERR_ARG, "cp_debug_proj: dz must not be NULL");
+    if (k != 4 && (!d->scale || !d->shift)) return fail(CP_ERR_ARG, "cp_debug_proj: kinds 0..3 need scale and shift");
+    if (k == 4 && !d->coef) return fail(CP_ERR_ARG, "cp_debug_proj: kind 4 needs coef");
+    if ((k == 0 || k == 4) && !d->w32) return fail(CP_ERR_ARG, "cp_debug_proj: kinds 0 and 4 need w32");
+    if (k == 0 && !d->blast) return fail(CP_ERR_ARG, "cp_debug_proj: the forward needs blast");
+    if (k >= 1 && k <= 3 && !d->slabs) return fail(CP_ERR_ARG, "cp_debug_proj: kinds 1..3 need slabs");
+    if ((k == 1 || k >= 3) && !d->partials) return fail(CP_ERR_ARG, "cp_debug_proj: kinds 1, 3 and 4 need partials");
+    if (k == 1 && (!d->praw || !d->dzsum)) return fail(CP_ERR_ARG, "cp_debug_proj: kind 1 needs praw and dzsum");
+    const bool drop = d->dp_thresh != 0;
+    if (k == 1 && (drop || d->dp_key != 0 || d->dp_inv_keep != 0.f)) return fail(CP_ERR_ARG, "cp_debug_proj: kind 1 takes no dropout");
+    if (k >= 2 && !drop) return fail(CP_ERR_ARG, "cp_debug_proj: kinds 2..4 run behind a dropout (dp_thresh != 0)");
+    if (!drop && (d->dp_key != 0 || d->dp_inv_keep != 0.f)) return fail(CP_ERR_ARG, "cp_debug_proj: dp_key and dp_inv_keep without dp_thresh");
+    if (drop && (d->dp_thresh > 65535u || !(d->dp_inv_keep > 0.f))) return fail(CP_ERR_ARG, "cp_debug_proj: dp_thresh in 1..65535, dp_inv_keep > 0");
+    // 32-bit byte offsets of the buffer loads and stores and the dropout hash's 32-bit element index (check_cfg)
+    const uint64_t es = b16 ? 2 : 4;
+    // (by division: no M wraps the product)
+    if ((uint64_t)d->M >= (0xFFF00000ull + 512 * es - 1) / (512 * es)) return fail(CP_ERR_ARG, "cp_debug_proj: M * 512 * sizeof(T) must stay below 2^32 - 2^20");
+    if ((((uintptr_t)d->Wp | (uintptr_t)d->act | (uintptr_t)d->dz | (uintptr_t)d->w32 | (uintptr_t)d->out | (uintptr_t)d->slabs |
+          (uintptr_t)d->partials | (uintptr_t)d->praw | (uintptr_t)d->scale | (uintptr_t)d->shift | (uintptr_t)d->coef | (uintptr_t)d->blast |
+          (uintptr_t)d->dzsum) & 15) != 0)
+        return fail(CP_ERR_ARG, "cp_debug_proj: Wp, act, dz, w32, out, slabs, partials, praw, scale, shift, coef, blast and dzsum must be 16-byte aligned");
+    return 0;
+}
+
+extern "C" int cp_debug_proj(const cp_debug_proj_args* args, void* stream) {
+    if (int e = check_debug_proj(args)) return e;
+    if (args->dtype == CP_BF16) return debug_proj_t<bf16_t>(args, (hipStream_t)stream);
+    return debug_proj_t<float>(args, (hipStream_t)stream);
+}
+
 __global__ __launch_bounds__(256) void hog_kernel(long long ticks, float* sink) {
     __shared__ float pad[30 * 1024];                       // 120 KiB: no 64 KiB-stage GEMM block fits beside this one
     pad[threadIdx.x] = (float)threadIdx.x;

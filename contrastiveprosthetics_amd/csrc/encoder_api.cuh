@@ -166,6 +166,18 @@ static Aux make_aux(const cp_config* c, hipStream_t st, bool eligible) {
     return a;
 }
 
+// the projection's weights as its launches read them, from the reference layout Wp (16, 512) f32 (the caller checks the launch):
+// wlast[32][512] T = Wp diag s (s NULL: the plain copy) with rows 16..31 zero and blast[16] = Wp t, for the forward launch;
+// wlast_t[512][64] T = Wp^T with columns 16..63 zero, for the data gradient
+template <typename T>
+static inline void launch_proj_fold(const float* Wp, const float* s, const float* t, void* wlast, float* blast, hipStream_t st) {
+    hipLaunchKernelGGL((fold_linear_kernel<T>), dim3(32), dim3(256), 0, st, Wp, (const float*)nullptr, s, t, (T*)wlast, blast, CP_D_E, 512, 0);
+}
+template <typename T>
+static inline void launch_proj_transpose(const float* Wp, void* wlast_t, hipStream_t st) {
+    hipLaunchKernelGGL((transpose_w_kernel<T>), dim3(64), dim3(256), 0, st, Wp, (T*)wlast_t, CP_D_E, 512, 64, 0);
+}
+
 // the transposed weights the data-gradient launches read: fc1..fc7 and the projection (bf16 / f32), their e4m3 form + the projection's
 // (CP_FP8).  Made once per step: at the start of the backward pass, or -- second stream -- beside the forward pass.
 template <typename T>
@@ -185,7 +197,7 @@ static int launch_weight_transposes_fp8(const cp_params* p, unsigned char* base,
     for (int i = 0; i < CP_N_FC; ++i)
         tb.job[i] = Transpose8Job{p->fc_w[i], base + w.wfc8t[i], base + w.wsc8t[i], fcK(i), i == 0 ? 1 : 0, F8_T_GRAD + (i + 2)};
     hipLaunchKernelGGL(transpose_w8_batch_kernel, dim3(12, CP_N_FC, 4), dim3(256), 0, st, tb, fs);
-    hipLaunchKernelGGL((transpose_w_kernel<bf16_t>), dim3(64), dim3(256), 0, st, p->last_w, (bf16_t*)(base + w.wlast_t), CP_D_E, 512, 64, 0);
+    launch_proj_transpose<bf16_t>(p->last_w, base + w.wlast_t, st);
     CKL("transpose kernels (fp8)");
     return 0;
 }
@@ -291,6 +303,21 @@ struct ConvLaunch {
     const float* pre(int& nrows, int W, int direct_rows) const { return PreReduce{partials, rows2, st}(nrows, W, direct_rows); }
 };
 
+// what a launch sequence of the 512 -> 16 projection reads of its call.  The step fills it from its pass (Pass::proj()), cp_debug_proj
+// from caller buffers: both reach the projection's kernels through the launch functions below (launch_proj_fwd, proj_dz_sums,
+// launch_proj_wgrad_tn, launch_proj_wgrad_onepass, proj_sums_from_wgrad; launch_proj_dgrad in gemm_ws.cuh), with their splits and grids
+struct ProjLaunch {
+    hipStream_t st;
+    int64_t N;                  // rows
+    float* partials;            // partial rows
+};
+// the dropout in front of the projection as set_dropout fills it; dp_thresh == 0: none
+struct ProjDrop {
+    uint32_t dp_thresh, dp_key;
+    float dp_inv_keep;
+    const uint32_t* dp_salt;
+};
+
 // ---------------------------------------------------------------------------------------
 // one pass: what every function of the encoder's forward and backward pass reads of its call
 // ---------------------------------------------------------------------------------------
@@ -312,17 +339,14 @@ struct Pass {
     float* rows2() const { return (float*)(base + w.partials2); }
     const float* pre(int& nrows, int W, int direct_rows = FIN_DIRECT_ROWS) const { return PreReduce{partials, rows2(), st}(nrows, W, direct_rows); }
     ConvLaunch conv() const { return ConvLaunch{st, N(), partials, slabs, rows2(), stats(0)}; }
+    ProjLaunch proj() const { return ProjLaunch{st, N(), partials}; }
 };
 
 // the dropout in front of `layer`'s consumer: threshold, key, 1 / (1 - p) and the graph-replay salt, for every argument struct that
-// carries them (GemmNTArgs, GemmTNArgs, Proj8Args, SmFwdArgs, SmBwdArgs)
+// carries them (GemmNTArgs, ProjDrop, Proj8Args, SmFwdArgs, SmBwdArgs)
 template <typename Args>
 static inline void set_dropout(Args& a, const Pass& ctx, int layer) {
     a.dp_thresh = dp_thresh(ctx.cfg->dp_emg); a.dp_key = dp_key(ctx.cfg, layer); a.dp_inv_keep = dp_inv_keep(ctx.cfg->dp_emg); a.dp_salt = dp_salt(ctx.cfg);
-}
-// (ProjWgradArgs has no 1 / (1 - p): proj_wgrad_finish_kernel applies it to the finished product)
-static inline void set_dropout(ProjWgradArgs& a, const Pass& ctx, int layer) {
-    a.dp_thresh = dp_thresh(ctx.cfg->dp_emg); a.dp_key = dp_key(ctx.cfg, layer); a.dp_salt = dp_salt(ctx.cfg);
 }
 
 // the dtype ladder of the entry points: f(TypeTag<float>) for CP_F32, f(TypeTag<bf16_t>) for 16-bit storage (CP_BF16, and what CP_FP8
@@ -413,6 +437,34 @@ static int launch_conv2_fwd(const ConvLaunch& ctx, const ConvArgs& ca, const cha
     hipLaunchKernelGGL((conv2_strip_kernel<T, 0>), dim3(g), dim3(256), 0, ctx.st, ca);
     CKL(what);
     *rows = g;
+    return 0;
+}
+
+// the projection's forward launch, 512 -> 16 on weights padded to 32 rows: z[N][16] f32 = A wlast^T + blast.  With a dropout
+// (dp.dp_thresh != 0) the operand is dropout(scale A + shift), formed from the saved activation while staging; a_exp (bf16 kernels
+// only): A holds e4m3 bytes with the scale 2^*a_exp
+template <typename T>
+static int launch_proj_fwd(const ProjLaunch& ctx, const void* A, const int* a_exp, const void* wlast, const float* blast,
+                           const float* scale, const float* shift, const ProjDrop& dp, float* z) {
+    GemmNTArgs a{};
+    a.A = A; a.lda = 512; a.M = ctx.N; a.K = 512;
+    a.W = wlast; a.F = 32;
+    a.C = z; a.ldc = CP_D_E; a.f_valid = CP_D_E; a.bias = blast;
+    a.a_exp = a_exp;
+    const bool drop = dp.dp_thresh != 0;
+    if (drop) {
+        a.a_scale = scale; a.a_shift = shift;
+        a.dp_thresh = dp.dp_thresh; a.dp_key = dp.dp_key; a.dp_inv_keep = dp.dp_inv_keep; a.dp_salt = dp.dp_salt;
+    }
+    if constexpr (sizeof(T) == 2) {
+        if (a_exp) {
+            if (drop) CK((launch_gemm_nt<T, 128, 32, ALOAD_BNDROP_F8, EPI_PLAIN_F32>(a, ctx.st)));
+            else CK((launch_gemm_nt<T, 128, 32, ALOAD_F8, EPI_PLAIN_F32>(a, ctx.st)));
+            return 0;
+        }
+    }
+    if (drop) CK((launch_gemm_nt<T, 128, 32, ALOAD_BNDROP, EPI_PLAIN_F32>(a, ctx.st)));
+    else CK((launch_gemm_nt<T, 128, 32, ALOAD_PLAIN, EPI_PLAIN_F32>(a, ctx.st)));
     return 0;
 }
 
@@ -511,24 +563,13 @@ static int encoder_forward_t(const cp_config* c, const cp_params* p, const cp_bn
         // the pass that materialised it moved 344 MB.  (That pass, as fc4..fc6 keep it, was removed here; see git history.)
         if (!drop && batch_stats) {        // (with dropout: copied by fold_copy_batch_kernel at the start of the pass; running statistics: folded up front)
             ProfScope ps(CP_K_FOLD, st);
-            hipLaunchKernelGGL((fold_linear_kernel<T>), dim3(32), dim3(256), 0, st, p->last_w, (const float*)nullptr, ctx.scale(Lp), ctx.shift(Lp),
-                               (T*)(base + w.wlast), (float*)(base + w.blast), CP_D_E, 512, 0);
+            launch_proj_fold<T>(p->last_w, ctx.scale(Lp), ctx.shift(Lp), base + w.wlast, (float*)(base + w.blast), st);
             CKL("fold_linear_kernel(last)");
         }
-        GemmNTArgs a{};
-        a.A = ctx.act<T>(Lp); a.lda = 512; a.M = N; a.K = 512;
-        a.W = base + w.wlast; a.F = 32;
-        a.C = z; a.ldc = CP_D_E; a.f_valid = CP_D_E; a.bias = (float*)(base + w.blast);
-        {
-            ProfScope ps(CP_K_PROJ_FWD, st);
-            if (drop) {
-                a.a_scale = ctx.scale(Lp); a.a_shift = ctx.shift(Lp);
-                set_dropout(a, ctx, Lp);
-                CK((launch_gemm_nt<T, 128, 32, ALOAD_BNDROP, EPI_PLAIN_F32>(a, st)));
-            } else {
-                CK((launch_gemm_nt<T, 128, 32, ALOAD_PLAIN, EPI_PLAIN_F32>(a, st)));
-            }
-        }
+        ProjDrop dp{};
+        if (drop) set_dropout(dp, ctx, Lp);
+        ProfScope ps(CP_K_PROJ_FWD, st);
+        if (int e = launch_proj_fwd<T>(ctx.proj(), ctx.act<T>(Lp), nullptr, base + w.wlast, (float*)(base + w.blast), ctx.scale(Lp), ctx.shift(Lp), dp, z)) return e;
     }
     return 0;
 }
@@ -629,23 +670,14 @@ static int encoder_forward_fp8(const cp_config* c, const cp_params* p, const cp_
         const int Lp = 8;
         {
             ProfScope ps(CP_K_FOLD, st);
-            hipLaunchKernelGGL((fold_linear_kernel<T>), dim3(32), dim3(256), 0, st, p->last_w, (const float*)nullptr, drop ? (const float*)nullptr : ctx.scale(Lp),
-                               drop ? (const float*)nullptr : ctx.shift(Lp), (T*)(base + w.wlast), (float*)(base + w.blast), CP_D_E, 512, 0);
+            launch_proj_fold<T>(p->last_w, drop ? (const float*)nullptr : ctx.scale(Lp), drop ? (const float*)nullptr : ctx.shift(Lp), base + w.wlast,
+                                (float*)(base + w.blast), st);
             CKL("fold_linear_kernel(last)");
         }
-        GemmNTArgs a{};
-        a.A = ctx.act8(Lp); a.lda = 512; a.M = N; a.K = 512;
-        a.W = base + w.wlast; a.F = 32;
-        a.C = z; a.ldc = CP_D_E; a.f_valid = CP_D_E; a.bias = (float*)(base + w.blast);
-        a.a_exp = &fs->e[F8_T_ACT + Lp];
+        ProjDrop dp{};
+        if (drop) set_dropout(dp, ctx, Lp);
         ProfScope ps(CP_K_PROJ_FWD, st);
-        if (drop) {
-            a.a_scale = ctx.scale(Lp); a.a_shift = ctx.shift(Lp);
-            set_dropout(a, ctx, Lp);
-            CK((launch_gemm_nt<T, 128, 32, ALOAD_BNDROP_F8, EPI_PLAIN_F32>(a, st)));
-        } else {
-            CK((launch_gemm_nt<T, 128, 32, ALOAD_F8, EPI_PLAIN_F32>(a, st)));
-        }
+        if (int e = launch_proj_fwd<T>(ctx.proj(), ctx.act8(Lp), &fs->e[F8_T_ACT + Lp], base + w.wlast, (float*)(base + w.blast), ctx.scale(Lp), ctx.shift(Lp), dp, z)) return e;
     }
     return 0;
 }
@@ -817,17 +849,74 @@ static int bias_grad_from_rows(const Pass& ctx, int rows, int C, float* db, cons
 // projection without a dropout in front: the column sums of dz, and from them and the RAW weight-gradient product (praw) the
 // BatchNorm-backward sums of fc7's BatchNorm in one partial row -- no N-sized read
 template <typename T>
-static int proj_dz_sums(const Pass& ctx, const T* dz, float* dzsum) {
+static int proj_dz_sums(const ProjLaunch& ctx, const T* dz, float* dzsum) {
     using D = DT<T>;
-    const int gb = grid_rows(ctx.N(), 256 / (CP_D_E / D::EPC), 64);
-    hipLaunchKernelGGL((colsum_kernel<T>), dim3(gb), dim3(256), 256 * D::EPC * 4, ctx.st, dz, ctx.partials, ctx.N(), 64, CP_D_E);
+    const int gb = grid_rows(ctx.N, 256 / (CP_D_E / D::EPC), 64);
+    hipLaunchKernelGGL((colsum_kernel<T>), dim3(gb), dim3(256), 256 * D::EPC * 4, ctx.st, dz, ctx.partials, ctx.N, 64, CP_D_E);
     hipLaunchKernelGGL(colsum_finalize_kernel, dim3(FIN_GRID(CP_D_E)), dim3(FIN_THREADS), 0, ctx.st, ctx.partials, gb, CP_D_E, dzsum);  // 16 columns: tiny
     CKL("colsum(dz)");
     return 0;
 }
-static int proj_sums_from_wgrad(const Pass& ctx, const cp_params* p, const float* praw, const float* dzsum) {
-    hipLaunchKernelGGL(bn_bwd_sums_from_wgrad_kernel, dim3(512 / 64, 1), dim3(256), 0, ctx.st, praw, p->last_w, dzsum, ctx.partials, CP_D_E, 512, 0);
+static int proj_sums_from_wgrad(const ProjLaunch& ctx, const float* Wp, const float* praw, const float* dzsum) {
+    hipLaunchKernelGGL(bn_bwd_sums_from_wgrad_kernel, dim3(512 / 64, 1), dim3(256), 0, ctx.st, praw, Wp, dzsum, ctx.partials, CP_D_E, 512, 0);
     CKL("bn_bwd_sums_from_wgrad_kernel(last)");
+    return 0;
+}
+
+// the projection's weight gradient as two launches on stream sw: gemm_tn_kernel<T, 64, 128, .> over kProjSplits row splits ->
+// slabs[S][64][512], reduce_slabs_kernel -> dW (16, 512) = s P + t dzsum (s NULL: the plain product) and the raw product praw (or
+// NULL).  Y is the saved activation [N][512] (y_exp, bf16 kernels only: as e4m3 bytes); behind a dropout (dp.dp_thresh != 0) the
+// operand is dropout(y_scale Y + y_shift), formed while staging.  *splits = S
+template <typename T>
+static int launch_proj_wgrad_tn(const ProjLaunch& ctx, hipStream_t sw, const T* dz, const void* Y, const int* y_exp, float* slabs,
+                                const float* y_scale, const float* y_shift, const ProjDrop& dp, const float* s, const float* t,
+                                const float* dzsum, float* dW, float* praw, int* splits) {
+    GemmTNArgs ta{};
+    ta.X = dz; ta.ldx = 64; ta.Y = Y; ta.ldy = 512; ta.slabs = slabs; ta.M = ctx.N; ta.P = 64; ta.Q = 512;
+    ta.y_exp = y_exp;
+    int S;
+    split_rows(ctx.N, kProjSplits, &S, &ta.rows_per_split);
+    if (dp.dp_thresh != 0) {
+        // u8 = dropout(BN(fc7)) was never written (encoder_forward_t): formed from the saved activation while staging
+        ta.y_scale = y_scale; ta.y_shift = y_shift;
+        ta.dp_thresh = dp.dp_thresh; ta.dp_key = dp.dp_key; ta.dp_inv_keep = dp.dp_inv_keep; ta.dp_salt = dp.dp_salt;
+        CK((launch_gemm_tn<T, 64, 128, YLOAD_BNDROP>(ta, S, sw)));
+    } else if (y_exp) {
+        if constexpr (sizeof(T) == 2) CK((launch_gemm_tn<T, 64, 128, YLOAD_F8>(ta, S, sw)));
+        else return fail(CP_ERR_ARG, "an e4m3 operand feeds the bf16 kernels");
+    } else {
+        CK((launch_gemm_tn<T, 64, 128, YLOAD_PLAIN>(ta, S, sw)));
+    }
+    hipLaunchKernelGGL(reduce_slabs_kernel<float>, dim3(32), dim3(256), 0, sw, ta.slabs, S, 64, 512, CP_D_E, s, t, dzsum, dW, 0, praw,
+                       (const int*)nullptr, (const int*)nullptr);
+    CKL("reduce_slabs(last)");
+    *splits = S;
+    return 0;
+}
+
+// the projection's weight gradient behind fc7's dropout in one pass over the saved activation R (gemm_tn.cuh): proj_wgrad_sums_kernel
+// (r_exp: <true>, R as e4m3 bytes) -> slabs[S][32][512], proj_wgrad_finish_kernel -> dW (16, 512) and PROJ_FINISH_ROWS partial rows
+// [2][512] of fc7's BatchNorm-backward sums in ctx.partials.  *splits = S
+static int launch_proj_wgrad_onepass(const ProjLaunch& ctx, const bf16_t* dz, const void* R, const int* r_exp, float* slabs,
+                                     const ProjDrop& dp, const float* scale, const float* shift, const float* Wp, float* dW, int* splits) {
+    ProjWgradArgs pa{};
+    pa.dz = dz; pa.R = R; pa.slabs = slabs; pa.M = ctx.N;
+    int S;
+    split_rows(ctx.N, kProjSplits, &S, &pa.rows_per_split);
+    pa.splits = S;
+    // (ProjWgradArgs has no 1 / (1 - p): proj_wgrad_finish_kernel applies it to the finished product)
+    pa.dp_thresh = dp.dp_thresh; pa.dp_key = dp.dp_key; pa.dp_salt = dp.dp_salt;
+    if (r_exp) {
+        hipLaunchKernelGGL(proj_wgrad_sums_kernel<true>, dim3(PROJ_WGRAD_GRID(S)), dim3(256), 0, ctx.st, pa);
+        CKL("proj_wgrad_sums_kernel<e4m3>");
+    } else {
+        hipLaunchKernelGGL(proj_wgrad_sums_kernel<false>, dim3(PROJ_WGRAD_GRID(S)), dim3(256), 0, ctx.st, pa);
+        CKL("proj_wgrad_sums_kernel");
+    }
+    hipLaunchKernelGGL(proj_wgrad_finish_kernel, dim3(32, PROJ_FINISH_ROWS), dim3(256), 0, ctx.st, slabs, S, scale, shift, Wp, dp.dp_inv_keep, r_exp,
+                       dW, ctx.partials);
+    CKL("proj_wgrad_finish_kernel");
+    *splits = S;
     return 0;
 }
 
@@ -1156,46 +1245,30 @@ static int encoder_backward_t(const cp_config* c, const cp_params* p, const floa
     // ---- projection ------------------------------------------------------------------
     {
         ProfScope ps(CP_K_PROJ_BWD, st);
+        const ProjLaunch pl = ctx.proj();
         const float *s = nullptr, *t = nullptr;
         float* dzsum = (float*)(base + w.dzsum);
         if (!drop) {
             s = ctx.scale(8); t = ctx.shift(8);
-            if (int e = proj_dz_sums<T>(ctx, dz, dzsum)) return e;
+            if (int e = proj_dz_sums<T>(pl, dz, dzsum)) return e;
         }
-        GemmTNArgs ta{};
+        ProjDrop dp{};
+        if (drop) set_dropout(dp, ctx, 8);
         const hipStream_t sw = aux.s();                 // (with dropout nothing waits for this weight gradient: second stream)
-        ta.X = dz; ta.ldx = 64; ta.Y = ctx.act<T>(8); ta.ldy = 512; ta.slabs = aux.on ? (float*)(base + w.slabs_b) : slabs; ta.M = N; ta.P = 64; ta.Q = 512;
         int S;
-        split_rows(N, kProjSplits, &S, &ta.rows_per_split);
         const bool proj_alg = fuse_ok && drop && sizeof(T) == 2;
         if (proj_alg) {
             // behind fc7's dropout, 16-bit storage (round 4): the weight gradient's launch reads r8 ONCE and leaves both dW and fc7's
             // BatchNorm-backward sums (gemm_tn.cuh, proj_wgrad_sums_kernel); on the critical path -- the data gradient below needs the sums
             if constexpr (sizeof(T) == 2) {
-                ProjWgradArgs pa{};
-                pa.dz = (const bf16_t*)dz; pa.R = ctx.act<T>(8); pa.slabs = slabs; pa.M = N; pa.rows_per_split = ta.rows_per_split; pa.splits = S;
-                set_dropout(pa, ctx, 8);
-                hipLaunchKernelGGL(proj_wgrad_sums_kernel<false>, dim3(PROJ_WGRAD_GRID(S)), dim3(256), 0, st, pa);
-                CKL("proj_wgrad_sums_kernel");
-                hipLaunchKernelGGL(proj_wgrad_finish_kernel, dim3(32, PROJ_FINISH_ROWS), dim3(256), 0, st, slabs, S, ctx.scale(8), ctx.shift(8), p->last_w,
-                                   dp_inv_keep(c->dp_emg), (const int*)nullptr, g->last_w, partials);
-                CKL("proj_wgrad_finish_kernel");
+                if (int e = launch_proj_wgrad_onepass(pl, (const bf16_t*)dz, ctx.act<T>(8), nullptr, slabs, dp, ctx.scale(8), ctx.shift(8), p->last_w, g->last_w, &S)) return e;
             }
-        } else if (drop) {
-            // u8 = dropout(BN(fc7)) was never written (encoder_forward_t): formed from the saved activation while staging
-            ta.y_scale = ctx.scale(8); ta.y_shift = ctx.shift(8);
-            set_dropout(ta, ctx, 8);
-            CK((launch_gemm_tn<T, 64, 128, YLOAD_BNDROP>(ta, S, sw)));
         } else {
-            CK((launch_gemm_tn<T, 64, 128, YLOAD_PLAIN>(ta, S, sw)));
-        }
-        if (!proj_alg) {
-            hipLaunchKernelGGL(reduce_slabs_kernel<float>, dim3(32), dim3(256), 0, sw, ta.slabs, S, 64, 512, CP_D_E, s, t, dzsum, g->last_w, 0,
-                               drop ? (float*)nullptr : praw);
-            CKL("reduce_slabs(last)");
+            if (int e = launch_proj_wgrad_tn<T>(pl, sw, dz, ctx.act<T>(8), nullptr, aux.on ? (float*)(base + w.slabs_b) : slabs, ctx.scale(8), ctx.shift(8), dp,
+                                                s, t, dzsum, g->last_w, drop ? (float*)nullptr : praw, &S)) return e;
         }
         if (!drop) {
-            if (int e = proj_sums_from_wgrad(ctx, p, praw, dzsum)) return e;
+            if (int e = proj_sums_from_wgrad(pl, p->last_w, praw, dzsum)) return e;
             stat_rows = 1;
         }
         GemmNTArgs a{};
@@ -1374,33 +1447,21 @@ static int encoder_backward_fp8(const cp_config* c, const cp_params* p, const fl
     // ---- projection ------------------------------------------------------------------
     {
         ProfScope ps(CP_K_PROJ_BWD, st);
+        const ProjLaunch pl = ctx.proj();
         float* dzsum = (float*)(base + w.dzsum);
         if (!drop) {
-            if (int e = proj_dz_sums<T>(ctx, dz, dzsum)) return e;
+            if (int e = proj_dz_sums<T>(pl, dz, dzsum)) return e;
         }
         int S;
-        int64_t rows_per_split;
-        split_rows(N, kProjSplits, &S, &rows_per_split);
         if (drop) {
             // (encoder_backward_t: one pass over r8 for the weight gradient AND fc7's BatchNorm-backward sums, on the critical path)
-            ProjWgradArgs pa{};
-            pa.dz = (const bf16_t*)dz; pa.R = ctx.act8(8); pa.slabs = slabs; pa.M = N; pa.rows_per_split = rows_per_split; pa.splits = S;
-            set_dropout(pa, ctx, 8);
-            hipLaunchKernelGGL(proj_wgrad_sums_kernel<true>, dim3(PROJ_WGRAD_GRID(S)), dim3(256), 0, st, pa);
-            CKL("proj_wgrad_sums_kernel<e4m3>");
-            hipLaunchKernelGGL(proj_wgrad_finish_kernel, dim3(32, PROJ_FINISH_ROWS), dim3(256), 0, st, slabs, S, ctx.scale(8), ctx.shift(8), p->last_w,
-                               dp_inv_keep(c->dp_emg), (const int*)&fs->e[F8_T_ACT + 8], g->last_w, partials);
-            CKL("proj_wgrad_finish_kernel");
+            ProjDrop dp{};
+            set_dropout(dp, ctx, 8);
+            if (int e = launch_proj_wgrad_onepass(pl, (const bf16_t*)dz, ctx.act8(8), (const int*)&fs->e[F8_T_ACT + 8], slabs, dp, ctx.scale(8), ctx.shift(8),
+                                                  p->last_w, g->last_w, &S)) return e;
         } else {
-            GemmTNArgs ta{};
-            const hipStream_t sw = aux.s();
-            ta.X = dz; ta.ldx = 64; ta.Y = ctx.act8(8); ta.ldy = 512; ta.slabs = aux.on ? (float*)(base + w.slabs_b) : slabs; ta.M = N; ta.P = 64; ta.Q = 512;
-            ta.y_exp = &fs->e[F8_T_ACT + 8];
-            ta.rows_per_split = rows_per_split;
-            CK((launch_gemm_tn<T, 64, 128, YLOAD_F8>(ta, S, sw)));
-            hipLaunchKernelGGL(reduce_slabs_kernel<float>, dim3(32), dim3(256), 0, sw, ta.slabs, S, 64, 512, CP_D_E, ctx.scale(8), ctx.shift(8), dzsum, g->last_w, 0,
-                               praw, (const int*)nullptr, (const int*)nullptr);
-            CKL("reduce_slabs(last)");
+            if (int e = launch_proj_wgrad_tn<T>(pl, aux.s(), dz, ctx.act8(8), &fs->e[F8_T_ACT + 8], aux.on ? (float*)(base + w.slabs_b) : slabs, nullptr, nullptr,
+                                                ProjDrop{}, ctx.scale(8), ctx.shift(8), dzsum, g->last_w, praw, &S)) return e;
         }
         Proj8Args a{};
         a.A = dz; a.lda = 64; a.W = (const bf16_t*)(base + w.wlast_t); a.K = 64; a.R = ctx.act8(8); a.C = cur;
@@ -1410,7 +1471,7 @@ static int encoder_backward_fp8(const cp_config* c, const cp_params* p, const fl
             set_dropout(a, ctx, 8);
             if (int e = bwd_finalize(ctx, g, partials, PROJ_FINISH_ROWS, (double)N, 8, 512, 1, "bn_bwd_finalize_kernel(fc7, projection)")) return e;
         } else {
-            if (int e = proj_sums_from_wgrad(ctx, p, praw, dzsum)) return e;
+            if (int e = proj_sums_from_wgrad(pl, p->last_w, praw, dzsum)) return e;
             if (int e = bwd_finalize(ctx, g, partials, 1, (double)N, 8, 512, 1, "bn_bwd_finalize_kernel(fc7, fused)")) return e;
         }
         a.coef = coef;

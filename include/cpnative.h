@@ -554,6 +554,70 @@ typedef struct cp_debug_conv_args {
 } cp_debug_conv_args;
 int cp_debug_conv(const cp_debug_conv_args* args, void* stream);
 
+/* debug/test access (tests/test_gpu_proj_exact.py): every launch sequence of the 512 -> 16 projection of the LARGE-batch step on
+ * caller buffers, one at a time, at any row count M (no 41-window groups; also below the size from which the step dispatches these
+ * kernels).  The kernels are reached through the launch functions of the step (csrc/encoder_api.cuh: launch_proj_fwd, proj_dz_sums,
+ * launch_proj_wgrad_tn, launch_proj_wgrad_onepass, proj_sums_from_wgrad; csrc/gemm_ws.cuh: launch_proj_dgrad): its row splits,
+ * grids and partial-row counts.  T = float (CP_F32) or bf16 (CP_BF16).  Wp (16, 512) f32 is the weight in the reference layout;
+ * the entry runs the step's preparation kernels on it into caller scratch, so the zero padding they write is part of what runs.
+ * act[M][512] is the saved post-ReLU activation r, dz[M][64] T the head's gradient (columns 16..63 zero), s = scale[512],
+ * t = shift[512].  keep(m, f): the 16-bit draw of the dropout hash of (dp_key, m, 512, f) is >= dp_thresh.
+ *   kind 0   forward, out = z[M][16] f32.  dp_thresh == 0: fold_linear_kernel<T> -> w32 = wlast[32][512] = round_T(Wp diag s), rows
+ *            16..31 zero, blast[16] = Wp t; gemm_nt_kernel<T,128,32,ALOAD_PLAIN,EPI_PLAIN_F32> -> z = r wlast^T + blast.
+ *            dp_thresh != 0: the plain copy (fold_copy_batch_kernel<T>, one job; with r_exp fold_linear_kernel<T> without s / t, as
+ *            the CP_FP8 step) -> wlast = round_T(Wp), blast = 0; ALOAD_BNDROP -> z = round_T(keep (s r + t) dp_inv_keep) wlast^T.
+ *            r_exp: ALOAD_F8 / ALOAD_BNDROP_F8
+ *   kind 1   weight gradient, no dropout.  colsum_kernel<T>, colsum_finalize_kernel -> dzsum[16]; gemm_tn_kernel<T,64,128,YLOAD_PLAIN>
+ *            (r_exp: YLOAD_F8) -> slabs[S][64][512]; reduce_slabs_kernel -> out = dW (16, 512) = s P + t dzsum with P = dz^T r
+ *            -> praw[16][512]; bn_bwd_sums_from_wgrad_kernel -> partials[2][512] = sum_j Wp[j][.] dzsum[j], sum_j Wp[j][.] P[j][.]
+ *            (the column sums of dz first pass through partials[<= 64][16]).  *rows_out = S
+ *   kind 2   weight gradient behind a dropout, two products (CP_F32, or CP_BF16 under CP_OPT_UNFUSED_BN_BWD).
+ *            gemm_tn_kernel<T,64,128,YLOAD_BNDROP> -> slabs[S][64][512]; reduce_slabs_kernel -> out = dW = dz^T u with
+ *            u = round_T(keep (s r + t) dp_inv_keep).  *rows_out = S
+ *   kind 3   the same gradient in one pass (CP_BF16).  proj_wgrad_sums_kernel<false> (r_exp: <true>) -> slabs[S][32][512], rows 0..15
+ *            A = dz^T (keep r), rows 16..31 B = dz^T keep; proj_wgrad_finish_kernel -> out = dW = (s A 2^-r_exp + t B) dp_inv_keep
+ *            and partials[4][2][512]: row y holds sum_j bf16(Wp[j][.]) B[j][.] and sum_j bf16(Wp[j][.]) A[j][.] (times dp_inv_keep,
+ *            A in true units) over j = 4y..4y+3.  *rows_out = S
+ *   kind 4   data gradient behind a dropout (CP_BF16).  transpose_w_kernel<bf16> -> w32 = wlast_t[512][64] = bf16(Wp)^T, columns 16..63
+ *            zero; proj_dgrad_kernel -> out = C[M][512] bf16 = r > 0 ? ca g + cb r + cz : 0 with g = bf16(keep (dz wlast_t^T) dp_inv_keep),
+ *            ca / cb / cz = coef[0..2][.]; partials[rows][512] = column sums of C as stored, one row per worker; *rows_out = rows as
+ *            launch_proj_dgrad reports them
+ * S = the splits of split_rows(M, 128 splits, 32-row steps).  w32: scratch of 32 * 512 T (kind 0) or 512 * 64 T (kind 4).  r_exp
+ * (device int32, kinds 0, 1 and 3 under CP_BF16): act holds e4m3 bytes, stored = value * 2^*r_exp.  Every scratch and output region
+ * is the caller's, so guards behind them can be inspected.  rows_out: host, may be NULL.
+ * proj_dgrad8_kernel (csrc/fp8.cuh), the CP_FP8 step's data gradient, needs the 8-bit state block and is NOT reachable from here.
+ * Checked before anything launches, CP_ERR_ARG: a NULL pointer the kind reads or writes (Wp, act; dz for kinds 1..4; scale and
+ * shift for kinds 0..3; coef for kind 4; w32 for kinds 0 and 4; blast for kind 0; out; slabs for kinds 1..3; partials for kinds 1, 3
+ * and 4; praw and dzsum for kind 1), M <= 0, an unknown dtype or kind, kinds 3 and 4 or r_exp outside CP_BF16, r_exp in kinds 2 and
+ * 4, dropout (dp_thresh, dp_key or dp_inv_keep non-zero) in kind 1, dp_key or dp_inv_keep non-zero with dp_thresh == 0 in kind 0,
+ * no dropout (dp_thresh == 0) in kinds 2..4, dp_thresh > 65535, dp_inv_keep <= 0 with dropout, Wp / act / dz / w32 / out / slabs / partials / praw / scale / shift / coef / blast / dzsum not
+ * 16-byte aligned, M * 512 * sizeof(T) >= 2^32 - 2^20 (the step's bound: 32-bit byte offsets and the hash's 32-bit element index). */
+typedef struct cp_debug_proj_args {
+    int32_t dtype;             /* CP_F32 | CP_BF16 */
+    int32_t kind;              /* 0..4 */
+    int64_t M;
+    const float* Wp;           /* (16, 512) */
+    const void* act;           /* [M][512] T or e4m3 bytes */
+    const int32_t* r_exp;      /* device, or NULL */
+    const void* dz;            /* [M][64] T, kinds 1..4 */
+    const float* scale;        /* [512], kinds 0..3 */
+    const float* shift;        /* [512], kinds 0..3 */
+    const float* coef;         /* [3][512], kind 4 */
+    void* w32;
+    float* blast;              /* [32], kind 0 */
+    void* out;
+    float* slabs;
+    float* partials;
+    float* praw;               /* [16][512], kind 1 */
+    float* dzsum;              /* [16], kind 1 */
+    uint32_t dp_thresh;        /* 0: no dropout */
+    uint32_t dp_key;
+    float dp_inv_keep;
+    int32_t reserved0;
+    int32_t* rows_out;
+} cp_debug_proj_args;
+int cp_debug_proj(const cp_debug_proj_args* args, void* stream);
+
 /* BN statistics of `layer` as computed by the last forward: out[4][C] = mean, invstd, scale, shift */
 int cp_debug_bn_stats(const cp_config* cfg, void* ws, size_t ws_bytes, int32_t layer, float* out,
                       void* stream);

@@ -306,6 +306,75 @@ def test_debug_conv_refuses_what_a_launcher_would_before_it_launches(lib):
     assert lib.cp_debug_conv(None, None) == 10001
 
 
+def test_debug_proj_refuses_what_a_launcher_would_before_it_launches(lib):
+    """cp_debug_proj checks its arguments on the host, before any launch: CP_ERR_ARG with a message that names the entry (every
+    pointer is a dummy address that is never dereferenced; each case differs from a valid call of its kind in the one field under
+    test -- kinds 2..4 carry a dropout, kind 1 none.  That the valid calls are accepted is shown on the GPU:
+    tests/test_gpu_proj_exact.py).  The ctypes struct follows the header field by field."""
+    from contrastiveprosthetics_amd import _lib
+    hdr = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    body = hdr[hdr.index("typedef struct cp_debug_proj_args {"):hdr.index("} cp_debug_proj_args;")]
+    assert re.findall(r"\b(\w+)\s*;", body) == [f[0] for f in _lib.cp_debug_proj_args._fields_]
+    assert ctypes.sizeof(_lib.cp_debug_proj_args) == 8 + 8 + 14 * 8 + 4 * 4 + 8
+    ok = 0x100000
+    rows = ctypes.c_int32(-7)
+    pointers = ("Wp", "act", "dz", "scale", "shift", "coef", "w32", "blast", "out", "slabs", "partials", "praw", "dzsum")
+    drop = dict(dp_thresh=32768, dp_key=7, dp_inv_keep=2.0)
+
+    def call(**kw):
+        d = _lib.cp_debug_proj_args()
+        d.dtype, d.kind, d.M = 1, kw.get("kind", 0), 1000
+        for name in pointers:
+            setattr(d, name, ok)
+        d.rows_out = ctypes.pointer(rows)
+        if d.kind >= 2:
+            d.dp_thresh, d.dp_key, d.dp_inv_keep = 32768, 7, 2.0
+        for k, v in kw.items():
+            setattr(d, k, v)
+        rc = lib.cp_debug_proj(ctypes.byref(d), None)
+        return rc, lib.cp_last_error()
+
+    cases = [("M = 0", dict(M=0)), ("M < 0", dict(M=-41)), ("dtype 2", dict(dtype=2)), ("dtype -1", dict(dtype=-1)),
+             ("kind 5", dict(kind=5)), ("kind -1", dict(kind=-1))]
+    # every pointer a kind reads or writes
+    needs = {0: ("Wp", "act", "scale", "shift", "w32", "blast", "out"),
+             1: ("Wp", "act", "dz", "scale", "shift", "out", "slabs", "partials", "praw", "dzsum"),
+             2: ("Wp", "act", "dz", "scale", "shift", "out", "slabs"),
+             3: ("Wp", "act", "dz", "scale", "shift", "out", "slabs", "partials"),
+             4: ("Wp", "act", "dz", "coef", "w32", "out", "partials")}
+    for kind, names in needs.items():
+        cases += [("kind %d without %s" % (kind, name), {"kind": kind, name: None}) for name in names]
+    cases += [("kind 0 with dropout, without scale", dict(drop, scale=None)),
+              ("kind 3 in f32", dict(kind=3, dtype=0)), ("kind 4 in f32", dict(kind=4, dtype=0)),
+              ("e4m3 in f32, kind 0", dict(kind=0, dtype=0, r_exp=ok)), ("e4m3 in f32, kind 1", dict(kind=1, dtype=0, r_exp=ok)),
+              ("e4m3 in kind 2", dict(kind=2, r_exp=ok)), ("e4m3 in kind 4", dict(kind=4, r_exp=ok)),
+              ("dropout in kind 1", dict(drop, kind=1)), ("a key in kind 1", dict(kind=1, dp_key=7)),
+              ("1 / (1 - p) in kind 1", dict(kind=1, dp_inv_keep=2.0)), ("a key without a threshold, kind 0", dict(dp_key=7)),
+              ("1 / (1 - p) without a threshold, kind 0", dict(dp_inv_keep=2.0)),
+              ("kind 2 without dropout", dict(kind=2, dp_thresh=0)), ("kind 3 without dropout", dict(kind=3, dp_thresh=0)),
+              ("kind 4 without dropout", dict(kind=4, dp_thresh=0)),
+              ("dp_thresh 65536, kind 0", dict(drop, dp_thresh=65536)), ("dp_inv_keep 0, kind 0", dict(drop, dp_inv_keep=0.0)),
+              ("dp_inv_keep < 0, kind 0", dict(drop, dp_inv_keep=-2.0)),
+              ("2^32 bytes, bf16", dict(M=4193280)), ("2^32 bytes, f32", dict(dtype=0, M=2096640)),
+              ("2^32 bytes, kind 4", dict(kind=4, M=4193280)), ("M = 2^54: the byte count wraps to 0", dict(M=1 << 54)),
+              ("M = 2^63 - 1", dict(M=(1 << 63) - 1))]
+    for kind in range(2, 5):
+        cases += [("dp_thresh 65536, kind %d" % kind, dict(kind=kind, dp_thresh=65536)),
+                  ("dp_inv_keep 0, kind %d" % kind, dict(kind=kind, dp_inv_keep=0.0))]
+    cases += [("%s + %d" % (name, off), {"kind": kind, name: ok + off})
+              for name, kind, off in (("Wp", 0, 4), ("act", 0, 8), ("dz", 1, 8), ("scale", 0, 4), ("shift", 2, 8), ("coef", 4, 4), ("w32", 4, 2),
+                                      ("blast", 0, 4), ("out", 0, 8), ("slabs", 3, 4), ("partials", 4, 8), ("praw", 1, 4), ("dzsum", 1, 4))]
+    for what, kw in cases:
+        rc, msg = call(**kw)
+        assert rc == 10001 and msg.startswith(b"cp_debug_proj"), (what, rc, msg)
+        assert rows.value == -7, what
+    for what, says in (("kind 5", b"kind"), ("dtype 2", b"dtype"), ("e4m3 in kind 2", b"r_exp"), ("2^32 bytes, bf16", b"2^32"),
+                       ("Wp + 4", b"aligned"), ("M = 0", b"M must"), ("dropout in kind 1", b"no dropout"),
+                       ("kind 3 without dropout", b"behind a dropout"), ("kind 4 in f32", b"CP_BF16"), ("dp_thresh 65536, kind 3", b"dp_thresh")):
+        assert says in call(**dict(cases)[what])[1], what
+    assert lib.cp_debug_proj(None, None) == 10001
+
+
 def test_backward_refuses_a_short_gradient_tap_before_it_launches(lib):
     """cp_config.grad_tap: cp_encoder_backward checks the whole buffer once, before its first launch -- 9 slots of n_windows x 768
     elements on the large-batch paths (CP_FP8: bf16 elements), 11 on the small-batch path (slot 9: fc1's data gradient before conv2's

@@ -9,6 +9,8 @@ Which launch reaches which kernel (csrc/encoder_api.cuh launch_fc_gemm; bf16):
     data gradient, R and coef (BN mode)      gemm_wsd16<0>                       gemm_nt256p<EPI_DGRAD_BN, dyn>
     data gradient, R, no coef (ST mode)      gemm_wsd16<1>                       gemm_nt256p<EPI_DGRAD_ST, dyn>   (with and without dropout)
     weight gradient                          gemm_tn256                          gemm_tn256
+    K = 64 (the projection's data gradient): every launch above with R runs the persistent kernel under BOTH schedules, on one K
+    block -- <EPI_DGRAD_BN | EPI_DGRAD_ST, static> where K = 512 reaches gemm_wsd16
 
 Why zero: the operands are ternary (-1 / 1 with probability 1/16 each, else 0), the bias, the saved activation and the BatchNorm
 coefficients small integers or halves.  Every product is then -1, 0 or 1, every float32 accumulator an integer far below 2^24
@@ -32,6 +34,7 @@ seven XCDs without an item), 255 / 256 / 257 (the tile boundary), 2,049 (nine sa
 (177 sample tiles, 69 items on XCD 0's 32 blocks: a third tile, the s_item slots wrap; three rounds of the static assignment);
 and, for the kernels only the static schedule reaches, a multiple of the kernel's row tile times its workers plus one tile, one
 row more and one row less (WS16_RT = WSN_RT = 48, WSD16_RT = 32; the weight gradient: the rounding of its rows per split).
+K = 64, F = 512 (the 64 columns of dz against the projection's transposed weight; all 64 columns live here): the same M table.
 
 Each case prints the largest |value| and the largest column sum of |values| in steps it saw (pytest -s): the margin to 2^24."""
 import ctypes
@@ -224,7 +227,7 @@ def test_forward_is_exact(K, F, M):
 
 
 # ---- data gradient without a saved activation -------------------------------------------------------------------------------------
-@pytest.mark.parametrize("K,F,M", [(512, 512, m) for m in TABLE_512] + [(512, 768, m) for m in TABLE_768])
+@pytest.mark.parametrize("K,F,M", [(512, 512, m) for m in TABLE_512] + [(512, 768, m) for m in TABLE_768] + [(64, 512, m) for m in TABLE_512])
 def test_plain_data_gradient_is_exact(K, F, M):
     o = _operands(K, F)
     tag = "dgrad K=%d F=%d M=%d" % (K, F, M)
@@ -251,18 +254,26 @@ def _bn_reference(tag, K, F, mod, M):
     return o, coef, ref
 
 
-@pytest.mark.parametrize("K,F,mod,M", [(512, 512, 512, m) for m in TABLE_512 + WSD512_M] + [(512, 768, 64, m) for m in TABLE_768 + WSD768_M])
+def _static_rows(K, F, M):
+    """partial rows of a data gradient with R under the static schedule: gemm_wsd16 (K = 512) writes one per worker that drew a 32-row
+    tile, the persistent kernel (any other K) one per slot of a round of 256-row sample tiles: 32 / (F / 256) x 8 either way"""
+    workers = (32 // (F // 256)) * 8
+    return min(_tiles(M, 32 if K == 512 else 256), workers)
+
+
+@pytest.mark.parametrize("K,F,mod,M", [(512, 512, 512, m) for m in TABLE_512 + WSD512_M] + [(512, 768, 64, m) for m in TABLE_768 + WSD768_M] +
+                         [(64, 512, 512, m) for m in TABLE_512])
 def test_bn_mode_data_gradient_is_exact(K, F, mod, M):
-    """F = 768 with coef_mod = 64: fc1's gradient into the conv layout, where feature f takes channel f % 64's coefficients"""
+    """F = 768 with coef_mod = 64: fc1's gradient into the conv layout, where feature f takes channel f % 64's coefficients.
+    K = 64 with coef_mod = 512: the projection's data gradient without a dropout in front of it"""
     tag = "dgrad+BN K=%d F=%d coef_mod=%d M=%d" % (K, F, mod, M)
     o, coef, ref = _bn_reference(tag, K, F, mod, M)
-    workers = (32 // (F // 256)) * 8
     for schedule, name in SCHEDULES:
         C, P = _c_buffer(M, F), _p_buffer()
         n = _launch(1, schedule, M, K, F, o["A"], o["W"], C, R=o["R"], partials=P, coef=coef, coef_mod=mod)
         torch.cuda.synchronize()
         _check_c(tag + " " + name, C, M, ref)
-        _check_partials(tag + " " + name, P, n, _tiles(M) if schedule else min(_tiles(M, 32), workers), [ref], schedule == DYNAMIC)
+        _check_partials(tag + " " + name, P, n, _tiles(M) if schedule else _static_rows(K, F, M), [ref], schedule == DYNAMIC)
     _report(tag)
 
 
@@ -280,7 +291,18 @@ def _hash_keep(M, F):
 @pytest.mark.parametrize("dropout", [False, True], ids=["nodrop", "drop"])
 @pytest.mark.parametrize("M", TABLE_512 + WSD512_M)
 def test_st_mode_data_gradient_is_exact(M, dropout):
-    K = F = 512
+    _st_mode_case(512, M, dropout)
+
+
+@pytest.mark.parametrize("dropout", [False, True], ids=["nodrop", "drop"])
+@pytest.mark.parametrize("M", TABLE_512)
+def test_st_mode_data_gradient_of_the_projection_is_exact(M, dropout):
+    """K = 64: the projection's data gradient on the unfused route, with and without the dropout behind fc7"""
+    _st_mode_case(64, M, dropout)
+
+
+def _st_mode_case(K, M, dropout):
+    F = 512
     o = _operands(K, F)
     tag = "dgrad+ST K=%d F=%d M=%d %s" % (K, F, M, "p=0.5" if dropout else "no dropout")
     acc = o["A"][:M].double() @ o["W"].double().T
@@ -304,7 +326,7 @@ def test_st_mode_data_gradient_is_exact(M, dropout):
             share = float(((c != 0) & live).sum()) / count
             assert abs(share - 0.5) <= 6 * (0.25 / count) ** 0.5, (tag, name, share, count)
         _check_c(tag + " " + name, C, M, ref)                                              # ... and the mask is the hash's
-        _check_partials(tag + " " + name, P, n, _tiles(M) if schedule else min(_tiles(M, 32), 128), [ref, ref * r], schedule == DYNAMIC)
+        _check_partials(tag + " " + name, P, n, _tiles(M) if schedule else _static_rows(K, F, M), [ref, ref * r], schedule == DYNAMIC)
     live = acc != 0
     assert torch.equal((got[STATIC] == 0) & live, (got[DYNAMIC] == 0) & live), (tag, "the schedules drop different elements")
     _report(tag)
