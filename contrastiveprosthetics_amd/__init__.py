@@ -32,4 +32,8 @@ def __getattr__(name):
                 "learning_curve", "plan_grid", "assign_folds", "HOLDOUT_SCORE_KEYS"):       # (holdout.leave_one_out: by module)
         from . import holdout
         return getattr(holdout, name)
+    if name in ("fit_prototypes", "fit_reference", "Prototypes", "PostureRows", "group_reference", "posture_recording",
+                "prototype_table"):                            # (prototypes.class_of_row, row_id: by module)
+        from . import prototypes
+        return getattr(prototypes, name)
     raise AttributeError(name)

@@ -159,6 +159,7 @@ CP_ONLINE_REALIGN_MAX_ACTIVITY, CP_ONLINE_REALIGN_MAX_REGION = 4095, 4096
 CP_ONLINE_TRACK_SCORES, CP_ONLINE_TRACK_SWEEP_MAX_CONFIGS = 8, 65536
 CP_ONLINE_TRACK_RESET_RING, CP_ONLINE_TRACK_RESET_ROWS = 0, 1
 CP_ONLINE_HOLDOUT_SCORES, CP_ONLINE_HOLDOUT_MAX_PLANS, CP_ONLINE_HOLDOUT_MAX_REPS = 9, 4096, 32
+CP_ONLINE_PROTO_MAX_ROWS, CP_ONLINE_PROTO_MAX_ITERS = 4, 64
 
 # what the four map sweep entries take behind their workspace: rms, n_windows, mean_std, map_src, map_fill, n_maps, n_classes,
 # expected_slot, chunk_rows, scratch, scratch_bytes, pred, voted, scores, class_hits, stream
@@ -332,6 +333,14 @@ SYMBOLS = {
     "cp_online_holdout_score": (C.c_int, [_fp, C.c_int64, C.c_int32, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp,
                                           _fp]),
     "cp_online_holdout_logits": (C.c_int, [_fp, C.c_int64, C.c_int32, _fp, C.c_int32, _fp, _fp, C.c_int32, _fp]),
+    "cp_online_proto_fit": (C.c_int, [_fp, C.c_int64, C.c_int32, _fp, _fp, _P(C.c_int32), C.c_int32, C.c_int32, _fp, _fp, _fp, _fp,
+                                      _fp, _fp]),
+    "cp_online_group_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "cp_online_group_set_groups": (C.c_int, [C.c_int32, C.c_int32, _fp, C.c_size_t, C.c_int32, _P(C.c_int32), _P(C.c_int32),
+                                             C.c_int32, _fp]),
+    "cp_online_group_reset": (C.c_int, [C.c_int32, C.c_int32, _fp, C.c_size_t, C.c_int32, _fp]),
+    "cp_online_group_push": (C.c_int, [C.c_int32, C.c_int32, _fp, C.c_size_t, _fp, C.c_int32, _fp, _fp, C.c_int32, _fp, _fp, _fp,
+                                       _fp, C.c_int32, _fp]),
 }
 
 KERNEL_KINDS = ["gather", "prep", "conv1_fwd", "bn_finalize", "conv2_fwd", "fold", "fc_fwd", "dropout", "proj_fwd",

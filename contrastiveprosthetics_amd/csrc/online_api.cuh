@@ -2062,3 +2062,118 @@ extern "C" int cp_online_holdout_logits(const float* embeddings, int64_t n_rows,
     CKL("oh_logits_kernel");
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------
+// posture prototypes (csrc/online_prototypes.cuh): the fit of up to four rows per class in one launch, and the group stage
+// behind any decoder's logits, one OpgState per stream in a workspace of its own
+// ---------------------------------------------------------------------------------------
+static_assert(OP_MAXR == CP_ONLINE_PROTO_MAX_ROWS && OP_MAX_ITERS == CP_ONLINE_PROTO_MAX_ITERS && OP_MAXK == CP_ONLINE_MAX_CLASSES &&
+              OP_D == CP_D_E && OPG_MAXM == CP_ONLINE_MAX_WINDOWS && OP_MAXR * OP_D == 64, "posture prototype constants");
+static_assert(sizeof(OpgState) == 4 * (4 + 3 * OP_MAXK + OL_MAXVOTE), "OpgState is 452 words");
+
+extern "C" int cp_online_proto_fit(const float* embeddings, int64_t n_rows, int32_t n_classes, const int32_t* slot, const uint8_t* use,
+                                   const int32_t* rows_per_class, int32_t iters, int32_t min_windows, float* rows, int64_t* counts,
+                                   uint8_t* valid, int64_t* moved, int32_t* assign, void* stream) {
+    const char* who = "cp_online_proto_fit";
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (int e = oh_check_shape(who, n_rows, n_classes)) return e;
+    if (iters < 0 || iters > CP_ONLINE_PROTO_MAX_ITERS) return bad("iters outside 0..64");
+    if (min_windows < 1) return bad("min_windows must be at least 1");
+    if (!embeddings || !slot || !rows_per_class || !rows || !counts || !valid || !assign || (iters > 0 && !moved))
+        return bad("embeddings, slot, rows_per_class, rows, counts, valid, assign (and moved, with iters > 0) are required");
+    if ((uintptr_t)embeddings % 16) return bad("embeddings must be 16-byte aligned");
+    if ((uintptr_t)slot % 4 || (uintptr_t)rows_per_class % 4 || (uintptr_t)rows % 4 || (uintptr_t)counts % 8 || (uintptr_t)moved % 8 ||
+        (uintptr_t)assign % 4)
+        return bad("misaligned argument");
+    OpFitArgs a{};
+    int total = 0;
+    for (int c = 0; c < n_classes; ++c) {
+        if (rows_per_class[c] < 1 || rows_per_class[c] > CP_ONLINE_PROTO_MAX_ROWS) return bad("rows_per_class outside 1..4");
+        a.rows_per_class[c] = (unsigned char)rows_per_class[c];
+        total += rows_per_class[c];
+    }
+    if (total > CP_ONLINE_MAX_CLASSES) return bad("rows_per_class sums to more than 64 rows");
+    a.emb = embeddings; a.slot = slot; a.use = use; a.n_rows = n_rows; a.K = n_classes; a.iters = iters; a.min_windows = min_windows;
+    a.rows = rows; a.counts = (long long*)counts; a.valid = valid; a.moved = (long long*)moved; a.assign = assign;
+    hipLaunchKernelGGL(op_fit_kernel, dim3(n_classes + 1), dim3(64), 0, (hipStream_t)stream, a);
+    CKL("op_fit_kernel");
+    return 0;
+}
+
+static int opg_check(const char* who, int32_t vote, int32_t n_streams, void* ws, size_t ws_bytes) {
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (!ws) return bad("workspace is required");
+    if (n_streams < 1 || n_streams > CP_ONLINE_MULTI_MAX_STREAMS) return bad("n_streams outside 1..256");
+    if (vote < 1 || vote > CP_ONLINE_MAX_VOTE) return bad("vote outside 1..256");
+    if ((uintptr_t)ws % 256) return bad("workspace not 256-byte aligned");
+    if (ws_bytes < (size_t)n_streams * sizeof(OpgState)) return bad("workspace too small");
+    return 0;
+}
+
+extern "C" size_t cp_online_group_workspace_bytes(int32_t n_streams) {
+    if (n_streams < 1) n_streams = 1;
+    return align256((size_t)n_streams * sizeof(OpgState));
+}
+
+extern "C" int cp_online_group_set_groups(int32_t vote, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index,
+                                          const int32_t* row_ids, const int32_t* class_of_row, int32_t n_rows, void* stream) {
+    const char* who = "cp_online_group_set_groups";
+    if (int e = opg_check(who, vote, n_streams, ws, ws_bytes)) return e;
+    if (int e = ol_check_index(who, index, n_streams)) return e;
+    if (!row_ids || !class_of_row || n_rows < 1 || n_rows > CP_ONLINE_MAX_CLASSES)
+        return ol_fail(CP_ERR_ARG, who, "1..64 rows, with row_ids and class_of_row");
+    OpgGroups g{};
+    g.R = n_rows;
+    for (int r = 0; r < n_rows; ++r) {
+        if (row_ids[r] < 0 || row_ids[r] == INT32_MAX || (r > 0 && row_ids[r] <= row_ids[r - 1]))
+            return ol_fail(CP_ERR_ARG, who, "row_ids must be ascending, distinct and in 0..2^31-2");
+        if (class_of_row[r] < 0 || class_of_row[r] == INT32_MAX) return ol_fail(CP_ERR_ARG, who, "class ids must lie in 0..2^31-2");
+        g.row_ids[r] = row_ids[r];
+        int at = 0;                                            // group ids stay ascending: insert a new class id in its place
+        while (at < g.G && g.group_ids[at] < class_of_row[r]) ++at;
+        if (at == g.G || g.group_ids[at] != class_of_row[r]) {
+            for (int i = g.G; i > at; --i) g.group_ids[i] = g.group_ids[i - 1];
+            g.group_ids[at] = class_of_row[r];
+            ++g.G;
+        }
+    }
+    for (int r = 0; r < n_rows; ++r) {
+        int at = 0;
+        while (g.group_ids[at] != class_of_row[r]) ++at;
+        g.group_of[r] = at;
+    }
+    hipLaunchKernelGGL(opg_set_groups_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (OpgState*)ws + index, g);
+    CKL("opg_set_groups_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_group_reset(int32_t vote, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index, void* stream) {
+    const char* who = "cp_online_group_reset";
+    if (int e = opg_check(who, vote, n_streams, ws, ws_bytes)) return e;
+    if (index < -1 || index >= n_streams) return ol_fail(CP_ERR_ARG, who, "stream index outside -1..n_streams-1");
+    hipLaunchKernelGGL(opg_reset_kernel, dim3(index < 0 ? n_streams : 1), dim3(64), 0, (hipStream_t)stream, (OpgState*)ws,
+                       index < 0 ? 0 : index);
+    CKL("opg_reset_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_group_push(int32_t vote, int32_t n_streams, void* ws, size_t ws_bytes, const float* logits, int32_t ldl,
+                                    const int32_t* row0, const int32_t* m, int32_t total_rows, int32_t* pred, int32_t* voted,
+                                    int32_t* row, float* class_logits, int32_t ldc, void* stream) {
+    const char* who = "cp_online_group_push";
+    if (int e = opg_check(who, vote, n_streams, ws, ws_bytes)) return e;
+    if (total_rows < 0 || total_rows > CP_ONLINE_MULTI_MAX_ROWS) return ol_fail(CP_ERR_ARG, who, "total_rows outside 0..65536");
+    if (total_rows == 0) return 0;
+    if (ldl < 1) return ol_fail(CP_ERR_ARG, who, "ldl must be at least 1");
+    if (class_logits && ldc < 1) return ol_fail(CP_ERR_ARG, who, "ldc must be at least 1");
+    if (!logits || !row0 || !m || !pred || !voted || !row) return ol_fail(CP_ERR_ARG, who, "logits, row0, m, pred, voted and row are required");
+    if ((uintptr_t)logits % 4 || (uintptr_t)row0 % 4 || (uintptr_t)m % 4 || (uintptr_t)pred % 4 || (uintptr_t)voted % 4 ||
+        (uintptr_t)row % 4 || (uintptr_t)class_logits % 4)
+        return ol_fail(CP_ERR_ARG, who, "misaligned argument");
+    OpgPushArgs a{};
+    a.states = (OpgState*)ws; a.logits = logits; a.row0 = row0; a.m = m; a.ldl = ldl; a.total_rows = total_rows; a.vote = vote;
+    a.ldc = class_logits ? ldc : 0; a.pred = pred; a.voted = voted; a.row = row; a.class_logits = class_logits;
+    hipLaunchKernelGGL(opg_push_kernel, dim3(n_streams), dim3(64), 0, (hipStream_t)stream, a);
+    CKL("opg_push_kernel");
+    return 0;
+}

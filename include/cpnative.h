@@ -1392,6 +1392,66 @@ int cp_online_holdout_score(const float* embeddings, int64_t n_rows, int32_t n_c
 int cp_online_holdout_logits(const float* embeddings, int64_t n_rows, int32_t n_classes, const float* unit, int32_t n_plans,
                              const int32_t* assign, float* logits, int32_t ldl, void* stream);
 
+/* ---- posture prototypes: several class rows per grasp, and the stage that answers with the grasp ---------------------------------
+ * A grasp made with the arm down, reaching forward or overhead lands in different places of the 16-d space.  The fit finds up to
+ * CP_ONLINE_PROTO_MAX_ROWS rows per class from one cued recording's embeddings; the group stage sits behind a decoder that holds
+ * such a table, as the gate does, and turns its row logits into class logits, a class prediction and a class vote
+ * (csrc/online_prototypes.cuh).  fit_reference and group_reference of contrastiveprosthetics_amd/prototypes.py are the
+ * definitions; the device equals them in every integer and bit.  Every f32 and f64 operation is rounded on its own (no
+ * contraction); every dot product is sum_d a[d] * b[d] in f32, d ascending, from 0.f.
+ *
+ * cp_online_proto_fit, one launch (one wave per class; the classes do not meet):
+ * - embeddings (n_rows,16) f32, 16-byte aligned; slot (n_rows) int32 on the device, the cue's class slot, anything outside
+ *   0..n_classes-1: the window belongs to no class; use (n_rows) uint8 on the device, optional: 0 keeps a window from training;
+ *   rows_per_class (n_classes) int32 in HOST memory, each 1..CP_ONLINE_PROTO_MAX_ROWS, their sum <= 64; iters in
+ *   0..CP_ONLINE_PROTO_MAX_ITERS; min_windows >= 1.
+ * - The windows of slot c are those with slot[i] == c, use[i] != 0 and all 16 components finite, in ascending i.
+ * - centre 0 = (float)(S[d] / |S|), S the float64 sum of the windows in window order, |S| = sqrt(sum_d S[d]^2) in f64, d
+ *   ascending: the row cp_online_enroll_table writes for a zero prior at mix = 1.  A slot with fewer than min_windows windows or
+ *   |S| = 0 is not fitted: its rows, counts, valid and moved are 0 and assign is -1 for its windows.
+ * - centre t = 1..R_c-1 (farthest-first): near(i) starts at -inf and takes every dot product with centres 0..t-1 that is > it;
+ *   the window with the smallest near (-0 equals +0), the earliest among equals, is copied bit for bit.
+ * - `iters` Lloyd rounds: a window goes to the centre with the largest dot product, the first maximum under `>` from centre 0;
+ *   per centre the float64 sum in window order and the count; a centre with count > 0 and |S| > 0 becomes (float)(S / |S|),
+ *   otherwise it stays.  moved[c][t] counts the windows whose centre differs from the round before (round 0: every window).
+ *   A round that moves nothing leaves a fixed point; the device skips the rounds behind it, which would repeat it.
+ * - A final assignment against the final centres gives counts[c][q] and assign[i], the row index within the class; assign is -1
+ *   for a window that did not train (no class, use = 0, a non-finite component, a slot that is not fitted).
+ *   valid[c][q] = the slot is fitted, q < R_c and counts[c][q] >= min_windows.
+ * - rows (n_classes,4,16) f32, counts (n_classes,4) int64, valid (n_classes,4) uint8, moved (n_classes,iters) int64 (may be NULL
+ *   with iters = 0), assign (n_rows) int32: every element is written.
+ *
+ * The group stage.  A stage behind a decoder with a workspace of its own (cp_online_group_workspace_bytes; a zeroed one is a
+ * valid start: no stream has groups).  `vote` is the ring length, the decoder's.
+ * - cp_online_group_set_groups: row_ids (n_rows) int32 ascending, the ids of the decoder's table rows, and class_of_row
+ *   (n_rows) int32, the class id of each, both in HOST memory; the groups are the distinct class ids in ascending order.  The
+ *   ring empties.
+ * - cp_online_group_reset: index -1 for all streams; the ring empties, the groups stay.
+ * - cp_online_group_push, the argument shape of cp_online_gate_push: logits (total_rows, ldl) f32, the decoder's row logits;
+ *   stream s owns rows row0[s] .. row0[s] + m[s] - 1 (device int32, m <= 256).  Per window, in window order: the class logit of
+ *   group g is the first maximum under `>` of its rows' logits in row order (the f32 maximum), a quiet NaN if one of them is a
+ *   NaN; a window with a logit among its n_rows that is not finite predicts nothing (pred = row = -1; its class logits are
+ *   written by the rule above, +-inf included); otherwise pred is the group with the largest class logit, the smallest group
+ *   among equals (-0 equals +0), and row the id of that group's first maximum.  pred enters the decoders' vote ring, a "none"
+ *   takes a place and does not vote; voted is the group with the most entries, the smallest among equals, -1 if none has one.
+ *   pred, voted (class ids), row (row id) (total_rows) int32; class_logits (total_rows, ldc) f32, optional, columns
+ *   0..n_groups-1.  A stream with m = 0, without groups, with more rows than ldl or more groups than ldc is left untouched.
+ *   With one row per class pred, voted and class_logits are the decoder's own bit for bit (finite logits).
+ * - The host checks before anything is enqueued and returns CP_ERR_ARG with a cp_last_error that names the entry.  The entries
+ *   never allocate and never synchronise. */
+#define CP_ONLINE_PROTO_MAX_ROWS 4
+#define CP_ONLINE_PROTO_MAX_ITERS 64
+int cp_online_proto_fit(const float* embeddings, int64_t n_rows, int32_t n_classes, const int32_t* slot, const uint8_t* use,
+                        const int32_t* rows_per_class, int32_t iters, int32_t min_windows, float* rows, int64_t* counts,
+                        uint8_t* valid, int64_t* moved, int32_t* assign, void* stream);
+size_t cp_online_group_workspace_bytes(int32_t n_streams);
+int cp_online_group_set_groups(int32_t vote, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index, const int32_t* row_ids,
+                               const int32_t* class_of_row, int32_t n_rows, void* stream);
+int cp_online_group_reset(int32_t vote, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index, void* stream);
+int cp_online_group_push(int32_t vote, int32_t n_streams, void* ws, size_t ws_bytes, const float* logits, int32_t ldl,
+                         const int32_t* row0, const int32_t* m, int32_t total_rows, int32_t* pred, int32_t* voted, int32_t* row,
+                         float* class_logits, int32_t ldc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,10 @@ With --holdout held-out enrolment scoring (holdout.score_plans, csrc/online_hold
 classes x 6 repetitions (about 14,500 windows): the embedding pass, the 30 learning-curve plans and a 4,096-plan grid, the numpy
 definition for the 30 plans, the host loop it replaces (masked enroll + set_classes + push per leave-one-out fold) and
 score_enrolment as a whole; the loop's hits per fold are written next to the sweep's.
+With --prototypes posture prototypes (prototypes.fit_prototypes and PostureRows, csrc/online_prototypes.cuh) are timed: the fit
+of the synthetic posture person of 41 classes (about 14,500 windows, 10 Lloyd rounds) with two rows per class for the first 23
+classes and with four rows for the first 7 (the sum stays at 64 rows or below), next to fit_reference on the host, and the
+per-push latency and kernels of OnlineDecoder.push with logits against PostureRows.push behind it at 1 and 25 windows.
 Each push is timed from the host with a synchronisation behind it (the latency a control loop sees); kernels per push are
 counted with torch.profiler over a few pushes.  One JSON line per case, and a table with --out.
 
@@ -66,6 +70,7 @@ counted with torch.profiler over a few pushes.  One JSON line per case, and a ta
     python tools/online_bench.py --realign --iters 20 --out profiles/online_realign.txt
     python tools/online_bench.py --track --track-sweep --iters 100 --out profiles/online_track.txt
     python tools/online_bench.py --holdout --iters 10 --out profiles/online_holdout.txt
+    python tools/online_bench.py --prototypes --iters 200 --out profiles/online_prototypes.txt
 """
 import argparse
 import json
@@ -134,7 +139,11 @@ def main():
     ap.add_argument("--track-sweep", action="store_true", help="sweep_tracker over a synthetic drifting stream, next to the definition")
     ap.add_argument("--holdout", action="store_true", help="held-out enrolment scoring: score_plans against the definition and against "
                     "a masked enroll + set_classes + push loop per fold")
+    ap.add_argument("--prototypes", action="store_true", help="posture prototypes: fit_prototypes against the definition, and the "
+                    "push with and without PostureRows behind it")
     a = ap.parse_args()
+    if a.prototypes:
+        return prototypes_main(a)
     if a.holdout:
         return holdout_main(a)
     if a.track or a.track_sweep:
@@ -1064,6 +1073,75 @@ def holdout_main(a):
                 f.write(f"{what:<34} {plans:>6} {ms:>12.3f}\n")
             f.write(f"device equals reference: {r['device_equals_reference']}\n")
             f.write(f"host loop hits  {r['host_loop_hits']}\nsweep pred_hit  {r['sweep_pred_hits']}\ncurve  {json.dumps(r['curve'])}\n")
+
+
+def prototypes_main(a):
+    """--prototypes: the fit at the workload's shape (the synthetic posture person of 41 classes, about 14,500 windows, three
+    arm positions, 10 Lloyd rounds) for two and for four rows per class, cut so that the table stays at 64 rows, against
+    fit_reference on the host; and a decoder's push with logits against PostureRows.push behind the same decoder, 1 and 25
+    windows per push, with the kernels per push of each."""
+    from contrastiveprosthetics_amd import prototypes as P
+    torch.manual_seed(0)
+    k, m = 41, 14_514
+    emb, exp, _ = P.posture_recording(m, k, 3, seed=0, segment=45, rest=14)
+    ids = np.arange(k)
+    emb_d = torch.from_numpy(emb).cuda()
+    rows = []
+    for name, rpc in (("R=2 (23 classes), 1 (18)", [2] * 23 + [1] * 18), ("R=4 (7 classes), 1 (34)", [4] * 7 + [1] * 34)):
+        fit = lambda: P.fit_prototypes(emb_d, exp, ids, rpc, iters=10, min_windows=25)
+        got = fit()
+        t0 = time.perf_counter()
+        ref = P.fit_reference(emb, exp, ids, rpc, iters=10, min_windows=25)
+        ref_ms = (time.perf_counter() - t0) * 1e3
+        same = bool(np.array_equal(got.rows.cpu().numpy().view(np.int32), ref["rows"].view(np.int32))
+                    and np.array_equal(got.counts, ref["counts"]) and np.array_equal(got.moved, ref["moved"])
+                    and np.array_equal(got.assign.cpu().numpy(), ref["assign"]))
+        med, p90 = time_pushes(fit, max(a.iters // 10, 5), 2)
+        r = dict(kind="fit", case=name, windows=m, classes=k, table_rows=int(got.valid.sum()), rounds_that_moved=int((ref["moved"] > 0).sum(axis=1).max()),
+                 fit_prototypes_ms=round(med / 1e3, 3), p90_ms=round(p90 / 1e3, 3), fit_reference_ms=round(ref_ms, 1), equal=same)
+        print(json.dumps(r), flush=True)
+        rows.append(r)
+    e = Engine(adabn=False, dtype="f32", device="cuda:0")
+    e.init_parameters(1)
+    stream = (torch.randn(200000, 12) * 2e-3).cuda()
+    mean, std = torch.full((12,), 0.4).cuda(), torch.full((12,), 0.1).cuda()
+    table, rid = got.table()
+    for n in (20, 500):
+        plain = OnlineDecoder(e, mean, std, dtype="f32")
+        plain.set_classes(table=torch.from_numpy(table), ids=rid)
+        staged = OnlineDecoder(e, mean, std, dtype="f32")
+        stage = got.install(staged)
+        pos = [0]
+
+        def chunk():
+            s = pos[0] % (stream.shape[0] - n)
+            pos[0] += n
+            return stream[s:s + n]
+
+        for name, fn in (("decoder.push", lambda: plain.push(chunk(), return_logits=True)),
+                         ("PostureRows.push", lambda: stage.push(chunk(), return_logits=True))):
+            med, p90 = time_pushes(fn, a.iters, a.warmup)
+            r = dict(kind="push", case=name, samples=n, windows=n // 20, table_rows=int(rid.shape[0]), median_us=round(med, 1),
+                     p90_us=round(p90, 1), kernels_per_push=count_kernels(fn))
+            print(json.dumps(r), flush=True)
+            rows.append(r)
+    if a.out:
+        dev = torch.cuda.get_device_name(0)
+        with open(a.out, "w") as f:
+            f.write(f"# tools/online_bench.py --prototypes --iters {a.iters} --warmup {a.warmup} on {dev}\n")
+            f.write("# the fit: one cp_online_proto_fit launch and the copy of counts / valid / moved, host-synchronised (median, p90),\n"
+                    "# next to fit_reference (numpy) on the same recording; `equal`: rows, counts, moved and assign agree in every bit\n")
+            f.write(f"{'fit':<28} {'windows':>8} {'classes':>8} {'rows':>5} {'rounds':>7} {'device_ms':>10} {'p90_ms':>8} {'reference_ms':>13} {'equal':>6}\n")
+            for r in rows:
+                if r["kind"] == "fit":
+                    f.write(f"{r['case']:<28} {r['windows']:>8} {r['classes']:>8} {r['table_rows']:>5} {r['rounds_that_moved']:>7} "
+                            f"{r['fit_prototypes_ms']:>10.3f} {r['p90_ms']:>8.3f} {r['fit_reference_ms']:>13.1f} {str(r['equal']):>6}\n")
+            f.write("# per-push wall time with logits, host-synchronised (median, p90), and kernels per push (torch.profiler)\n")
+            f.write(f"{'push':<18} {'samples':>7} {'windows':>7} {'rows':>5} {'median_us':>10} {'p90_us':>9} {'kernels':>8}\n")
+            for r in rows:
+                if r["kind"] == "push":
+                    f.write(f"{r['case']:<18} {r['samples']:>7} {r['windows']:>7} {r['table_rows']:>5} {r['median_us']:>10.1f} "
+                            f"{r['p90_us']:>9.1f} {r['kernels_per_push']:>8.1f}\n")
 
 
 def _cued_logits(m, k, seed=0):
