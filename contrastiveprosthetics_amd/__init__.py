@@ -36,4 +36,8 @@ def __getattr__(name):
                 "prototype_table"):                            # (prototypes.class_of_row, row_id: by module)
         from . import prototypes
         return getattr(prototypes, name)
+    if name in ("fit_metric", "Metric", "MetricRows", "pick_shrink", "metric_enrolment", "metric_recording", "apply_reference",
+                "stage_reference"):                            # (metric.fit_reference: by module)
+        from . import metric
+        return getattr(metric, name)
     raise AttributeError(name)

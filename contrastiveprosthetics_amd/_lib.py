@@ -160,6 +160,8 @@ CP_ONLINE_TRACK_SCORES, CP_ONLINE_TRACK_SWEEP_MAX_CONFIGS = 8, 65536
 CP_ONLINE_TRACK_RESET_RING, CP_ONLINE_TRACK_RESET_ROWS = 0, 1
 CP_ONLINE_HOLDOUT_SCORES, CP_ONLINE_HOLDOUT_MAX_PLANS, CP_ONLINE_HOLDOUT_MAX_REPS = 9, 4096, 32
 CP_ONLINE_PROTO_MAX_ROWS, CP_ONLINE_PROTO_MAX_ITERS = 4, 64
+CP_ONLINE_METRIC_MOMENTS, CP_ONLINE_METRIC_MAX_SHRINKS = 152, 64
+CP_ONLINE_METRIC_RESET_RING, CP_ONLINE_METRIC_RESET_ALL = 0, 1
 
 # what the four map sweep entries take behind their workspace: rms, n_windows, mean_std, map_src, map_fill, n_maps, n_classes,
 # expected_slot, chunk_rows, scratch, scratch_bytes, pred, voted, scores, class_hits, stream
@@ -341,6 +343,14 @@ SYMBOLS = {
     "cp_online_group_reset": (C.c_int, [C.c_int32, C.c_int32, _fp, C.c_size_t, C.c_int32, _fp]),
     "cp_online_group_push": (C.c_int, [C.c_int32, C.c_int32, _fp, C.c_size_t, _fp, C.c_int32, _fp, _fp, C.c_int32, _fp, _fp, _fp,
                                        _fp, C.c_int32, _fp]),
+    "cp_online_metric_moments": (C.c_int, [_fp, C.c_int64, C.c_int32, _fp, _fp, _fp, _fp, _fp]),
+    "cp_online_metric_factor": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, _P(C.c_double), C.c_int32, _fp, _fp, _fp]),
+    "cp_online_metric_apply": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp]),
+    "cp_online_metric_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "cp_online_metric_set": (C.c_int, [C.c_int32, C.c_int32, _fp, C.c_size_t, C.c_int32, _fp, _fp, _P(C.c_int32), C.c_int32, _fp]),
+    "cp_online_metric_reset": (C.c_int, [C.c_int32, C.c_int32, _fp, C.c_size_t, C.c_int32, C.c_int32, _fp]),
+    "cp_online_metric_push": (C.c_int, [C.c_int32, C.c_int32, _fp, C.c_size_t, _fp, _fp, _fp, C.c_int32, _fp, _fp, _fp, C.c_int32,
+                                        _fp]),
 }
 
 KERNEL_KINDS = ["gather", "prep", "conv1_fwd", "bn_finalize", "conv2_fwd", "fold", "fc_fwd", "dropout", "proj_fwd",

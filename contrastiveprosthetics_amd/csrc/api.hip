@@ -34,6 +34,7 @@
 #include "online_track.cuh"
 #include "online_holdout.cuh"
 #include "online_prototypes.cuh"
+#include "online_metric.cuh"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* what) {

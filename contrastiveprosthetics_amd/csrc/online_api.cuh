@@ -1,7 +1,7 @@
 // Host layer of the online decoders (include/cpnative.h, cp_online_*): workspace layout, argument checks, launch chains and
 // the extern "C" entries of the folded, adaptive, multi-stream and adaptive multi-stream decoders, class enrolment, head
 // fine-tuning, the command gate, the grasp drive, the gate sweep, the subset sweep, the electrode-map sweep, cue realignment, prototype
-// tracking and held-out enrolment scoring.  Host code only; api.hip includes it behind its own helpers (fail, CK, CKL) and encoder_api.cuh's (align256, fcK),
+// tracking, held-out enrolment scoring, posture prototypes and the user metric.  Host code only; api.hip includes it behind its own helpers (fail, CK, CKL) and encoder_api.cuh's (align256, fcK),
 // so the library stays one translation unit.  The four decoders share one workspace description (OlWS, ol_carve), one
 // parameter check, one set of front-end arguments, one folded chain and one unfolded weight copy; what an entry adds is its
 // name in the refusals and the kernels it launches.
@@ -2175,5 +2175,132 @@ extern "C" int cp_online_group_push(int32_t vote, int32_t n_streams, void* ws, s
     a.ldc = class_logits ? ldc : 0; a.pred = pred; a.voted = voted; a.row = row; a.class_logits = class_logits;
     hipLaunchKernelGGL(opg_push_kernel, dim3(n_streams), dim3(64), 0, (hipStream_t)stream, a);
     CKL("opg_push_kernel");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// user metric (csrc/online_metric.cuh): the moments of a cued recording, the shrunk and factored within-class scatter, the
+// transform of a recording, and the stage behind any decoder's embeddings, one OmState per stream in a workspace of its own
+// ---------------------------------------------------------------------------------------
+static_assert(OM_MAXK == CP_ONLINE_MAX_CLASSES && OM_D == CP_D_E && OM_MAXM == CP_ONLINE_MAX_WINDOWS && OM_MOMENTS == CP_ONLINE_METRIC_MOMENTS &&
+              OM_MAX_SHRINKS == CP_ONLINE_METRIC_MAX_SHRINKS && OM_APPLY_THREADS == OM_D * OM_D, "user metric constants");
+static_assert(sizeof(OmState) == 4 * (4 + OM_MAXK + OL_MAXVOTE + OM_D * OM_D + OM_MAXK * OM_D) && offsetof(OmState, A) == 4 * (4 + OM_MAXK + OL_MAXVOTE) &&
+              sizeof(OmState) % 16 == 0 && offsetof(OmState, row) % 16 == 0, "OmState as MetricRows.state reads it back");
+
+extern "C" int cp_online_metric_moments(const float* embeddings, int64_t n_rows, int32_t n_classes, const int32_t* slot, const uint8_t* use,
+                                        double* moments, int64_t* counts, void* stream) {
+    const char* who = "cp_online_metric_moments";
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (int e = oh_check_shape(who, n_rows, n_classes)) return e;
+    if (!embeddings || !slot || !moments || !counts) return bad("embeddings, slot, moments and counts are required");
+    if ((uintptr_t)embeddings % 16) return bad("embeddings must be 16-byte aligned");
+    if ((uintptr_t)slot % 4 || (uintptr_t)moments % 8 || (uintptr_t)counts % 8) return bad("misaligned argument");
+    hipLaunchKernelGGL(om_moments_kernel, dim3(n_classes), dim3(64), 0, (hipStream_t)stream, embeddings, (long long)n_rows, slot, use,
+                       moments, (long long*)counts);
+    CKL("om_moments_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_metric_factor(const double* moments, const int64_t* counts, int32_t n_classes, int32_t min_windows,
+                                       const double* shrinks, int32_t n_shrinks, float* A, uint8_t* valid, void* stream) {
+    const char* who = "cp_online_metric_factor";
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return bad("n_classes outside 1..64");
+    if (min_windows < 1) return bad("min_windows must be at least 1");
+    if (n_shrinks < 1 || n_shrinks > CP_ONLINE_METRIC_MAX_SHRINKS) return bad("n_shrinks outside 1..64");
+    if (!moments || !counts || !shrinks || !A || !valid) return bad("moments, counts, shrinks, A and valid are required");
+    if ((uintptr_t)moments % 8 || (uintptr_t)counts % 8 || (uintptr_t)shrinks % 8 || (uintptr_t)A % 4) return bad("misaligned argument");
+    OmFactorArgs a{};
+    for (int t = 0; t < n_shrinks; ++t) {
+        if (!(shrinks[t] >= 0.0 && shrinks[t] <= 1.0)) return bad("every shrink value must lie in [0, 1]");
+        a.shrinks[t] = shrinks[t];
+    }
+    a.moments = moments; a.counts = (const long long*)counts; a.K = n_classes; a.min_windows = min_windows; a.n_shrinks = n_shrinks;
+    a.A = A; a.valid = valid;
+    hipLaunchKernelGGL(om_factor_kernel, dim3(n_shrinks), dim3(64), 0, (hipStream_t)stream, a);
+    CKL("om_factor_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_metric_apply(const float* embeddings, int64_t n_rows, const float* A, float* out, void* stream) {
+    const char* who = "cp_online_metric_apply";
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (n_rows < 1 || n_rows > INT32_MAX) return bad("n_rows outside 1..2^31-1");
+    if (!embeddings || !A || !out) return bad("embeddings, A and out are required");
+    if ((uintptr_t)embeddings % 16 || (uintptr_t)out % 16) return bad("embeddings and out must be 16-byte aligned");
+    if ((uintptr_t)A % 4) return bad("misaligned argument");
+    hipLaunchKernelGGL(om_apply_kernel, dim3((unsigned)((n_rows + OM_APPLY_THREADS - 1) / OM_APPLY_THREADS)), dim3(OM_APPLY_THREADS), 0,
+                       (hipStream_t)stream, embeddings, (long long)n_rows, A, out);
+    CKL("om_apply_kernel");
+    return 0;
+}
+
+extern "C" size_t cp_online_metric_workspace_bytes(int32_t n_streams) {
+    if (n_streams < 1) n_streams = 1;
+    return align256((size_t)n_streams * sizeof(OmState));
+}
+
+static int om_check(const char* who, int32_t vote, int32_t n_streams, void* ws, size_t ws_bytes) {
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (!ws) return bad("workspace is required");
+    if (n_streams < 1 || n_streams > CP_ONLINE_MULTI_MAX_STREAMS) return bad("n_streams outside 1..256");
+    if (vote < 1 || vote > CP_ONLINE_MAX_VOTE) return bad("vote outside 1..256");
+    if ((uintptr_t)ws % 256) return bad("workspace not 256-byte aligned");
+    if (ws_bytes != cp_online_metric_workspace_bytes(n_streams)) return bad("ws_bytes is not cp_online_metric_workspace_bytes(n_streams)");
+    return 0;
+}
+
+extern "C" int cp_online_metric_set(int32_t vote, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index, const float* A,
+                                    const float* rows, const int32_t* ids, int32_t n_classes, void* stream) {
+    const char* who = "cp_online_metric_set";
+    if (int e = om_check(who, vote, n_streams, ws, ws_bytes)) return e;
+    if (int e = ol_check_index(who, index, n_streams)) return e;
+    if (!A && !rows) return ol_fail(CP_ERR_ARG, who, "A or rows is required");
+    if ((uintptr_t)A % 4 || (uintptr_t)rows % 4 || (uintptr_t)ids % 4) return ol_fail(CP_ERR_ARG, who, "misaligned argument");
+    OmIds c{};
+    if (rows) {
+        if (!ids || n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return ol_fail(CP_ERR_ARG, who, "rows come with 1..64 classes and their ids");
+        c.K = n_classes;
+        for (int k = 0; k < n_classes; ++k) {
+            if (ids[k] < 0 || ids[k] == INT32_MAX || (k > 0 && ids[k] <= ids[k - 1]))
+                return ol_fail(CP_ERR_ARG, who, "ids must be ascending, distinct and in 0..2^31-2");
+            c.ids[k] = ids[k];
+        }
+    }
+    hipLaunchKernelGGL(om_set_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (OmState*)ws + index, A, rows, c);
+    CKL("om_set_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_metric_reset(int32_t vote, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index, int32_t what,
+                                      void* stream) {
+    const char* who = "cp_online_metric_reset";
+    if (int e = om_check(who, vote, n_streams, ws, ws_bytes)) return e;
+    if (index < -1 || index >= n_streams) return ol_fail(CP_ERR_ARG, who, "stream index outside -1..n_streams-1");
+    if (what != CP_ONLINE_METRIC_RESET_RING && what != CP_ONLINE_METRIC_RESET_ALL)
+        return ol_fail(CP_ERR_ARG, who, "what must be CP_ONLINE_METRIC_RESET_RING or CP_ONLINE_METRIC_RESET_ALL");
+    hipLaunchKernelGGL(om_reset_kernel, dim3(index < 0 ? n_streams : 1), dim3(64), 0, (hipStream_t)stream, (OmState*)ws,
+                       index < 0 ? 0 : index, (int)what);
+    CKL("om_reset_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_metric_push(int32_t vote, int32_t n_streams, void* ws, size_t ws_bytes, const float* embeddings,
+                                     const int32_t* row0, const int32_t* m, int32_t total_rows, int32_t* pred, int32_t* voted,
+                                     float* logits, int32_t ldl, void* stream) {
+    const char* who = "cp_online_metric_push";
+    if (int e = om_check(who, vote, n_streams, ws, ws_bytes)) return e;
+    if (total_rows < 0 || total_rows > CP_ONLINE_MULTI_MAX_ROWS) return ol_fail(CP_ERR_ARG, who, "total_rows outside 0..65536");
+    if (total_rows == 0) return 0;
+    if (!embeddings || !row0 || !m || !pred || !voted) return ol_fail(CP_ERR_ARG, who, "embeddings, row0, m, pred and voted are required");
+    if (logits && (ldl < 1 || ldl > CP_ONLINE_MULTI_MAX_ROWS)) return ol_fail(CP_ERR_ARG, who, "ldl must be at least 1");
+    if ((uintptr_t)embeddings % 16) return ol_fail(CP_ERR_ARG, who, "embeddings must be 16-byte aligned");
+    if ((uintptr_t)row0 % 4 || (uintptr_t)m % 4 || (uintptr_t)pred % 4 || (uintptr_t)voted % 4 || (uintptr_t)logits % 4)
+        return ol_fail(CP_ERR_ARG, who, "misaligned argument");
+    OmPushArgs a{};
+    a.states = (OmState*)ws; a.emb = embeddings; a.row0 = row0; a.m = m; a.total_rows = total_rows; a.ldl = logits ? ldl : 0;
+    a.vote = vote; a.pred = pred; a.voted = voted; a.logits = logits;
+    hipLaunchKernelGGL(om_push_kernel, dim3(n_streams), dim3(64), 0, (hipStream_t)stream, a);
+    CKL("om_push_kernel");
     return 0;
 }

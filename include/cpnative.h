@@ -1452,6 +1452,72 @@ int cp_online_group_push(int32_t vote, int32_t n_streams, void* ws, size_t ws_by
                          const int32_t* row0, const int32_t* m, int32_t total_rows, int32_t* pred, int32_t* voted, int32_t* row,
                          float* class_logits, int32_t ldc, void* stream);
 
+/* ---- user metric: within-class whitening of the embedding, and the stage that decodes in the whitened space ----------------------
+ * Every stage above compares a window with a class row by a plain cosine, which weighs all sixteen directions alike.  The pooled
+ * within-class scatter of one cued recording, shrunk towards the identity and factored, gives a lower-triangular 16 x 16 matrix A
+ * per user; a window e becomes A e / |A e| and is compared with class rows fitted in that space (csrc/online_metric.cuh).
+ * fit_reference, apply_reference and stage_reference of contrastiveprosthetics_amd/metric.py are the definitions; the device
+ * equals them in every integer and bit (the payload of a NaN is not compared).  Every f32 and f64 operation is rounded on its own
+ * (no fused multiply-add).
+ *
+ * cp_online_metric_moments, one launch (one wave per class):
+ * - embeddings (n_rows, 16) f32, 16-byte aligned; slot (n_rows) int32, the class slot of each window, anything outside
+ *   0..n_classes-1: the window belongs to no class; use (n_rows) uint8, optional: 0: the window does not train.  A class's
+ *   windows are those with its slot, use set and 16 finite components, in window order.
+ * - counts (n_classes) int64: the windows of each class.  moments (n_classes, CP_ONLINE_METRIC_MOMENTS) f64: S[d], d = 0..15, the
+ *   sum of (double)e[d], then P[i][j] for i <= j in i-major order (136 entries), the sum of (double)e[i] * (double)e[j]; every
+ *   accumulator starts from 0 and takes one add per window in window order (the product of two f32 values is exact in f64).
+ *
+ * cp_online_metric_factor, one launch (one wave per shrink value):
+ * - shrinks (n_shrinks <= CP_ONLINE_METRIC_MAX_SHRINKS) f64 in host memory, each within [0, 1], checked before the launch.
+ * - A class is fitted when counts[c] >= min_windows; C the fitted classes, N their windows.  N - C < 1: no metric.  Else for
+ *   i <= j, over the fitted classes in slot order: t = S_c[i] * S_c[j]; t = t / (double)n_c; Sw[i][j] += P_c[i][j] - t; then
+ *   Sw[i][j] /= (double)(N - C).  tr = the diagonal summed in order, s = tr / 16; no metric unless s is finite and > 0.
+ * - Per shrink value l: B[i][j] = (1 - l) * (Sw[i][j] / s) + (i == j ? l : 0.0).  Cholesky B = L L^T in f64, row by row:
+ *   r = B[i][j]; r = r - L[i][k] * L[j][k] for k = 0..j-1; a pivot (i == j) that is not > 0 or not finite: no metric for this
+ *   l; L[i][i] = sqrt(r), L[i][j] = r / L[j][j].  The inverse, column j by column j: Ai[j][j] = 1.0 / L[j][j]; for i > j: r = 0.0;
+ *   r = r - L[i][k] * Ai[k][j] for k = j..i-1; Ai[i][j] = r / L[i][i].  A = (float)Ai, lower triangular, the rest +0; an entry
+ *   that is not finite in f32: no metric for this l.  l = 1 gives the identity in every bit.
+ * - A (n_shrinks, 16, 16) f32 and valid (n_shrinks) uint8; where there is no metric valid = 0 and A is the identity, so every
+ *   element is written.
+ *
+ * cp_online_metric_apply, row-parallel over n_rows windows with one A (16, 16) f32 (only its lower triangle is read):
+ * - y[i] = the f32 sum over j = 0..i, in that order, from 0, of A[i][j] * e[j]; ss = the f32 sum over i of y[i] * y[i];
+ *   out[i] = y[i] / sqrtf(ss).  A window with a component that is not finite, or with y = 0, gives a row that is not finite.
+ *
+ * The stage.  A stage behind a decoder with a workspace of its own (cp_online_metric_workspace_bytes; a zeroed one is a valid
+ * start: no metric, no rows, empty ring), which reads the embeddings of a push (cp_online_*_push_embed).  The entries take ws_bytes
+ * as exactly cp_online_metric_workspace_bytes(n_streams).
+ * - cp_online_metric_set: A (16, 16) f32 on the device, or NULL: the stream's metric stays; rows (n_classes, 16) f32 on the
+ *   device with ids (n_classes) int32 ascending in host memory, or NULL: the stream's rows stay.  The rows are normalised as
+ *   cp_online_set_classes normalises a table.  The ring empties.
+ * - cp_online_metric_reset: index -1 for all streams; CP_ONLINE_METRIC_RESET_RING empties the ring, CP_ONLINE_METRIC_RESET_ALL
+ *   also removes the metric and the rows.
+ * - cp_online_metric_push, the argument shape of cp_online_track_push: per window, in window order, e' as cp_online_metric_apply
+ *   forms it; logit of slot k = the f32 sum over d = 0..15 of e'[d] * row[k][d]; if a logit of the K slots is not finite the
+ *   window predicts nothing (-1), else the first maximum under `>` (-0 equals +0); pred enters the decoders' vote ring, where a
+ *   "none" takes a place and does not vote; voted is the slot with the most entries, the smallest among equals, -1 if none has
+ *   one.  pred, voted (total_rows) int32 class ids; logits (total_rows, ldl) f32, optional, columns 0..K-1.  A stream with
+ *   m = 0, without a metric, without rows, with more rows than ldl, or whose row0 / m leave total_rows is left untouched.
+ * - The host checks before anything is enqueued and returns CP_ERR_ARG with a cp_last_error that names the entry.  The entries
+ *   never allocate and never synchronise. */
+#define CP_ONLINE_METRIC_MOMENTS 152
+#define CP_ONLINE_METRIC_MAX_SHRINKS 64
+#define CP_ONLINE_METRIC_RESET_RING 0
+#define CP_ONLINE_METRIC_RESET_ALL 1
+int cp_online_metric_moments(const float* embeddings, int64_t n_rows, int32_t n_classes, const int32_t* slot, const uint8_t* use,
+                             double* moments, int64_t* counts, void* stream);
+int cp_online_metric_factor(const double* moments, const int64_t* counts, int32_t n_classes, int32_t min_windows,
+                            const double* shrinks, int32_t n_shrinks, float* A, uint8_t* valid, void* stream);
+int cp_online_metric_apply(const float* embeddings, int64_t n_rows, const float* A, float* out, void* stream);
+size_t cp_online_metric_workspace_bytes(int32_t n_streams);
+int cp_online_metric_set(int32_t vote, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index, const float* A,
+                         const float* rows, const int32_t* ids, int32_t n_classes, void* stream);
+int cp_online_metric_reset(int32_t vote, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index, int32_t what, void* stream);
+int cp_online_metric_push(int32_t vote, int32_t n_streams, void* ws, size_t ws_bytes, const float* embeddings, const int32_t* row0,
+                          const int32_t* m, int32_t total_rows, int32_t* pred, int32_t* voted, float* logits, int32_t ldl,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,10 @@ With --prototypes posture prototypes (prototypes.fit_prototypes and PostureRows,
 of the synthetic posture person of 41 classes (about 14,500 windows, 10 Lloyd rounds) with two rows per class for the first 23
 classes and with four rows for the first 7 (the sum stays at 64 rows or below), next to fit_reference on the host, and the
 per-push latency and kernels of OnlineDecoder.push with logits against PostureRows.push behind it at 1 and 25 windows.
+With --metric the user metric (metric.fit_metric, Metric.apply, pick_shrink and MetricRows, csrc/online_metric.cuh) is timed on
+the synthetic person of 41 classes (about 14,500 windows, 6 repetitions): the fit for 5 shrink values next to fit_reference on
+the host, the transform of the recording, pick_shrink over the 6 folds, and the per-push latency and kernels of
+OnlineDecoder.push with logits against MetricRows.push behind it at 1 and 25 windows.
 Each push is timed from the host with a synchronisation behind it (the latency a control loop sees); kernels per push are
 counted with torch.profiler over a few pushes.  One JSON line per case, and a table with --out.
 
@@ -71,6 +75,7 @@ counted with torch.profiler over a few pushes.  One JSON line per case, and a ta
     python tools/online_bench.py --track --track-sweep --iters 100 --out profiles/online_track.txt
     python tools/online_bench.py --holdout --iters 10 --out profiles/online_holdout.txt
     python tools/online_bench.py --prototypes --iters 200 --out profiles/online_prototypes.txt
+    python tools/online_bench.py --metric --iters 200 --out profiles/online_metric.txt
 """
 import argparse
 import json
@@ -141,7 +146,11 @@ def main():
                     "a masked enroll + set_classes + push loop per fold")
     ap.add_argument("--prototypes", action="store_true", help="posture prototypes: fit_prototypes against the definition, and the "
                     "push with and without PostureRows behind it")
+    ap.add_argument("--metric", action="store_true", help="the user metric: fit_metric against the definition, apply, pick_shrink, and "
+                    "the push with and without MetricRows behind it")
     a = ap.parse_args()
+    if a.metric:
+        return metric_main(a)
     if a.prototypes:
         return prototypes_main(a)
     if a.holdout:
@@ -1136,6 +1145,93 @@ def prototypes_main(a):
                 if r["kind"] == "fit":
                     f.write(f"{r['case']:<28} {r['windows']:>8} {r['classes']:>8} {r['table_rows']:>5} {r['rounds_that_moved']:>7} "
                             f"{r['fit_prototypes_ms']:>10.3f} {r['p90_ms']:>8.3f} {r['fit_reference_ms']:>13.1f} {str(r['equal']):>6}\n")
+            f.write("# per-push wall time with logits, host-synchronised (median, p90), and kernels per push (torch.profiler)\n")
+            f.write(f"{'push':<18} {'samples':>7} {'windows':>7} {'rows':>5} {'median_us':>10} {'p90_us':>9} {'kernels':>8}\n")
+            for r in rows:
+                if r["kind"] == "push":
+                    f.write(f"{r['case']:<18} {r['samples']:>7} {r['windows']:>7} {r['table_rows']:>5} {r['median_us']:>10.1f} "
+                            f"{r['p90_us']:>9.1f} {r['kernels_per_push']:>8.1f}\n")
+
+
+def metric_main(a):
+    """--metric: the fit at the workload's shape (the synthetic person of 41 classes, about 14,500 windows in 6 repetitions, 5
+    shrink values) against fit_reference on the host, the transform of the recording, pick_shrink over the 6 folds, and a
+    decoder's push with logits against MetricRows.push behind the same decoder, 1 and 25 windows per push, with the kernels per
+    push of each.  The decoder holds the 52-row table of --prototypes, so that its push is the one profiles/online_prototypes.txt
+    timed."""
+    from contrastiveprosthetics_amd import metric as M
+    from contrastiveprosthetics_amd import prototypes as P
+    torch.manual_seed(0)
+    k, m = 41, 14_514
+    emb, exp = M.metric_recording(m, k, seed=0, segment=45, rest=14)
+    ids = np.arange(k)
+    emb_d = torch.from_numpy(emb).cuda()
+    rows = []
+    fit = lambda: M.fit_metric(emb_d, exp, ids, M.SHRINKS, min_windows=25)
+    got = fit()
+    t0 = time.perf_counter()
+    ref = M.fit_reference(emb, exp, ids, M.SHRINKS, min_windows=25)
+    ref_ms = (time.perf_counter() - t0) * 1e3
+    same = bool(np.array_equal(got.A.cpu().numpy().view(np.int32), ref["A"].view(np.int32)) and np.array_equal(got.counts, ref["counts"])
+                and np.array_equal(got.valid, ref["valid"]) and np.array_equal(got.moments.cpu().numpy().view(np.int64), ref["moments"].view(np.int64)))
+    med, p90 = time_pushes(fit, max(a.iters // 10, 5), 2)
+    rows.append(dict(kind="host", case="fit_metric (5 shrink values)", windows=m, classes=k, device_ms=round(med / 1e3, 3), p90_ms=round(p90 / 1e3, 3),
+                     reference_ms=round(ref_ms, 1), equal=same))
+    t0 = time.perf_counter()
+    ref2 = M.apply_reference(emb, ref["A"][2])
+    ref_ms = (time.perf_counter() - t0) * 1e3
+    e2 = got.apply(emb_d, 2).cpu().numpy()
+    med, p90 = time_pushes(lambda: got.apply(emb_d, 2), max(a.iters // 10, 5), 2)
+    rows.append(dict(kind="host", case="Metric.apply", windows=m, classes=k, device_ms=round(med / 1e3, 3), p90_ms=round(p90 / 1e3, 3),
+                     reference_ms=round(ref_ms, 1), equal=bool(np.array_equal(e2.view(np.int32), ref2.view(np.int32)))))
+    pick = M.pick_shrink(emb_d, exp, ids, M.SHRINKS, min_windows=25)
+    med, p90 = time_pushes(lambda: M.pick_shrink(emb_d, exp, ids, M.SHRINKS, min_windows=25), 3, 1)
+    rows.append(dict(kind="host", case=f"pick_shrink ({pick['n_rep']} folds x 5)", windows=m, classes=k, device_ms=round(med / 1e3, 3),
+                     p90_ms=round(p90 / 1e3, 3), reference_ms=None, equal=None, voted_hit=pick["voted_hit"].tolist(), n_cue=int(pick["n_cue"][0]),
+                     baseline=list(pick["baseline"]), shrink=pick["shrink"]))
+    for r in rows:
+        print(json.dumps(r), flush=True)
+    e = Engine(adabn=False, dtype="f32", device="cuda:0")
+    e.init_parameters(1)
+    stream = (torch.randn(200000, 12) * 2e-3).cuda()
+    mean, std = torch.full((12,), 0.4).cuda(), torch.full((12,), 0.1).cuda()
+    pemb, pexp, _ = P.posture_recording(m, k, 3, seed=0, segment=45, rest=14)
+    table, rid = P.fit_prototypes(torch.from_numpy(pemb).cuda(), pexp, ids, [4] * 7 + [1] * 34, iters=10, min_windows=25).table()
+    class_rows, valid = got.rows(emb_d, exp, 2)
+    assert valid.all()
+    for n in (20, 500):
+        plain = OnlineDecoder(e, mean, std, dtype="f32")
+        plain.set_classes(table=torch.from_numpy(table), ids=rid)
+        staged = OnlineDecoder(e, mean, std, dtype="f32")
+        staged.set_classes(table=torch.from_numpy(table), ids=rid)
+        stage = got.install(staged, class_rows, t=2)
+        pos = [0]
+
+        def chunk():
+            s = pos[0] % (stream.shape[0] - n)
+            pos[0] += n
+            return stream[s:s + n]
+
+        for name, fn in (("decoder.push", lambda: plain.push(chunk(), return_logits=True)),
+                         ("MetricRows.push", lambda: stage.push(chunk(), return_logits=True))):
+            med, p90 = time_pushes(fn, a.iters, a.warmup)
+            r = dict(kind="push", case=name, samples=n, windows=n // 20, table_rows=int(rid.shape[0]), median_us=round(med, 1),
+                     p90_us=round(p90, 1), kernels_per_push=count_kernels(fn))
+            print(json.dumps(r), flush=True)
+            rows.append(r)
+    if a.out:
+        dev = torch.cuda.get_device_name(0)
+        with open(a.out, "w") as f:
+            f.write(f"# tools/online_bench.py --metric --iters {a.iters} --warmup {a.warmup} on {dev}\n")
+            f.write("# wall time, host-synchronised (median, p90), next to the numpy definition on the same recording; `equal`: every bit agrees\n")
+            f.write(f"{'call':<32} {'windows':>8} {'classes':>8} {'device_ms':>10} {'p90_ms':>8} {'reference_ms':>13} {'equal':>6}\n")
+            for r in rows:
+                if r["kind"] == "host":
+                    ref_s = "-" if r["reference_ms"] is None else f"{r['reference_ms']:.1f}"
+                    f.write(f"{r['case']:<32} {r['windows']:>8} {r['classes']:>8} {r['device_ms']:>10.3f} {r['p90_ms']:>8.3f} {ref_s:>13} "
+                            f"{'-' if r['equal'] is None else str(r['equal']):>6}\n")
+            f.write(f"# pick_shrink on the synthetic person: voted hits per shrink value {list(M.SHRINKS)} = {pick['voted_hit'].tolist()} of "
+                    f"{int(pick['n_cue'][0])} held-out cue windows, plain cosine {pick['baseline'][0]}, picked {pick['shrink']}\n")
             f.write("# per-push wall time with logits, host-synchronised (median, p90), and kernels per push (torch.profiler)\n")
             f.write(f"{'push':<18} {'samples':>7} {'windows':>7} {'rows':>5} {'median_us':>10} {'p90_us':>9} {'kernels':>8}\n")
             for r in rows:
