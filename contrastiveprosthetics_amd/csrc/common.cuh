@@ -263,4 +263,60 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     return v;
 }
 
+// ---- BatchNorm-backward coefficients in a consumer's prologue --------------------------------------------------------------
+// A persistent consumer of bn_bwd_finalize_kernel's `coef` (kernels_misc.cuh) can form the coefficients of its channels itself when the
+// partial rows are few: every block repeats the fold, the finalize launch disappears.  The numbers keep their bits, so the fold walks as
+// that kernel does with up to BNP_MAX_ROWS rows: row r sits alone on row lane r (a lane adds its row's nfold positions in order, in
+// fp64, from zero); the four lanes 4q..4q+3 of a wave are summed as (s0 + s1) + (s2 + s3) (fin_block_sum's two shuffles); the 16
+// waves in order (bnp_total).  A missing row is a zero, as it is on a lane without rows.
+#define BNP_MAX_ROWS 64
+template <int NFOLD>
+struct BnpQuad { float v1[4][NFOLD], v2[4][NFOLD]; };         // the rows of lanes 4q..4q+3: (sum g, sum g r) of one channel
+template <int NFOLD>
+__device__ __forceinline__ void bnp_load(BnpQuad<NFOLD>& u, const float* __restrict__ rows, int nr, int C, int c, int q) {
+    const int W = C * NFOLD;
+#pragma unroll
+    for (int gi = 0; gi < 4; ++gi) {
+        const int r = 4 * q + gi;
+        const bool ok = r < nr;
+        const float* p = rows + (int64_t)(ok ? r : 0) * 2 * W + c;          // clamped: the loads are unconditional
+#pragma unroll
+        for (int f = 0; f < NFOLD; ++f) {
+            const float a = p[f * C], b = p[W + f * C];
+            u.v1[gi][f] = ok ? a : 0.f;
+            u.v2[gi][f] = ok ? b : 0.f;
+        }
+    }
+}
+template <int NFOLD>
+__device__ __forceinline__ void bnp_quad_sum(const BnpQuad<NFOLD>& u, double& w1, double& w2) {
+    double s1[4], s2[4];
+#pragma unroll
+    for (int gi = 0; gi < 4; ++gi) {
+        s1[gi] = s2[gi] = 0;
+#pragma unroll
+        for (int f = 0; f < NFOLD; ++f) { s1[gi] += (double)u.v1[gi][f]; s2[gi] += (double)u.v2[gi][f]; }
+    }
+    w1 = (s1[0] + s1[1]) + (s1[2] + s1[3]);
+    w2 = (s2[0] + s2[1]) + (s2[2] + s2[3]);
+}
+// the quads' sums in wave order (nq = quads that hold rows; the others add zeros, which changes nothing)
+__device__ __forceinline__ double bnp_total(const double* w, int nq, int stride) {
+    double t = 0;
+    for (int q = 0; q < nq; ++q) t += w[q * stride];
+    return t;
+}
+// bn_bwd_finalize_kernel's expressions for one channel (local == nullptr)
+__device__ __forceinline__ void bnp_coef(double s1, double s2, const float* __restrict__ stats, int C, int c, double count, float& ca, float& cb,
+                                         float& cz, float& dgamma, float& dbeta) {
+    const double mean = stats[c], invstd = stats[C + c], sc = stats[2 * C + c];
+    const double dot = (s2 - mean * s1) * invstd;          // sum g * x_hat
+    const double c1 = s1 / count, c2 = dot / count;
+    ca = (float)sc;
+    cb = (float)(-sc * invstd * c2);
+    cz = (float)(-sc * (c1 - mean * invstd * c2));
+    dgamma = (float)dot;
+    dbeta = (float)s1;
+}
+
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

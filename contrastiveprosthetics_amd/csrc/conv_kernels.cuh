@@ -49,6 +49,8 @@ struct ConvArgs {
     float* dbeta2;
     float* gcols3;          // [grid][3][64]: column sums of the transformed gradient over all positions / position 0 / position 11
     //   conv2_dgrad_conv1_kernel<T, false, true>: BatchNorm1's backward coefficients from conv2_wgrad_finish_kernel's rows (stats1 = its table)
+    //   conv2_dgrad_conv1_kernel<T, false, false> (large batches) with rows1 != nullptr: the same in bn_bwd_finalize_kernel's own order of
+    //   additions (rows1_nr <= BNP_MAX_ROWS), instead of a ready `coef`
     const float* rows1;     // [rows1_nr][2][64]
     int rows1_nr;
     float* dgamma1;
@@ -713,6 +715,32 @@ __global__ __launch_bounds__(256, 2) void conv2_dgrad_conv1_kernel(ConvArgs a) {
                          a.dgamma1, a.dbeta1);
         ca = ca_s[ch1]; cb = cb_s[ch1]; cz = cz_s[ch1];
         __syncthreads();                               // (the reduction scratch is the image region; the weights come after it)
+    } else if (a.rows1 != nullptr) {
+        // large batches: the same, with bn_bwd_finalize_kernel's own walk (common.cuh, bnp_*), so that the coefficients and dgamma / dbeta keep
+        // the bits of that launch.  Up to BNP_MAX_ROWS rows = 16 quads: thread = (channel, quads part, part + 4, ..)
+        __shared__ float cf_s[3][64];
+        static_assert(IMG_BYTES >= 2 * 16 * 64 * 8, "the quads' sums use the image region");
+        double* quad_s = (double*)smem;                // [2][16][64]
+        const int c = tid & 63, part = tid >> 6;
+        BnpQuad<1> bq[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) bnp_load(bq[i], a.rows1, a.rows1_nr, 64, c, part + 4 * i);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            double w1, w2;
+            bnp_quad_sum(bq[i], w1, w2);
+            quad_s[(part + 4 * i) * 64 + c] = w1;
+            quad_s[(16 + part + 4 * i) * 64 + c] = w2;
+        }
+        __syncthreads();
+        if (tid < 64) {
+            float dg, db;
+            bnp_coef(bnp_total(quad_s + c, 16, 64), bnp_total(quad_s + 16 * 64 + c, 16, 64), a.stats1, 64, c, (double)a.n_windows * 12, cf_s[0][c], cf_s[1][c],
+                     cf_s[2][c], dg, db);
+            if (blockIdx.x == 0) { a.dgamma1[c] = dg; a.dbeta1[c] = db; }
+        }
+        __syncthreads();
+        ca = cf_s[0][ch1]; cb = cf_s[1][ch1]; cz = cf_s[2][ch1];          // (the image region was last read before that barrier)
     } else {
         ca = a.coef[ch1]; cb = a.coef[64 + ch1]; cz = a.coef[128 + ch1];
     }

@@ -240,6 +240,7 @@ static inline hipError_t launch_fc_gemm(const GemmNTArgs& a, hipStream_t st, int
         if (EPI == EPI_FWD && a.K == WSK_K && a.lda == WSK_K && a.F == 512 && a.relu && ws_ok) return launch_gemm_ws16n(a, st, stat_rows);
         if (EPI == EPI_FWD || (a.R == nullptr && a.dp_thresh == 0)) return launch_gemm_nt256p<EPI>(a, st, stat_rows, dyn);
         if (EPI == EPI_DGRAD && a.R != nullptr && a.K == WS_K && a.lda == WS_K && ws_ok) return launch_gemm_wsd_bn(a, st, stat_rows);
+        if (a.bn_rows) return hipErrorInvalidValue;          // (only that kernel forms its coefficients itself)
         // the persistent kernel's R epilogues (dynamic schedule, or K != 512): BN + ReLU backward of the layer below (coef), or
         // dropout + BN-backward sums
         if constexpr (EPI == EPI_DGRAD)
@@ -838,6 +839,18 @@ static int bwd_finalize(const Pass& ctx, cp_params* g, const float* pp, int nr, 
     return 0;
 }
 
+// BatchNorm backward, step 1 without a launch: a persistent consumer (gemm_wsd16_kernel<0>, proj_dgrad_kernel, conv2_dgrad_conv1_kernel) folds
+// the `nr` partial rows in its prologue, every block for its own channels, with bn_bwd_finalize_kernel's order of additions and
+// expressions (common.cuh, bnp_*).  Not under synchronised BatchNorm (a row crosses the ranks between the two launches), not with
+// more rows than the kernel's prologue walks, not under CP_OPT_FINALIZE_LAUNCHES.  The rows must not lie in the buffer the consumer
+// writes its own partial rows to (a block that starts late reads them while an early one finishes): the producers write to ctx.rows2().
+static inline bool bwd_in_prologue(const Pass& ctx, int nr, int max_rows) {
+    return !opt(ctx.cfg, CP_OPT_FINALIZE_LAUNCHES) && !ctx.cfg->stats_allreduce && nr <= max_rows;
+}
+static inline void set_bn_prologue(GemmNTArgs& a, const Pass& ctx, cp_params* g, const float* rows, int nr, double count, int l) {
+    a.bn_rows = rows; a.bn_nr = nr; a.bn_stats = ctx.stats(l); a.bn_count = count; a.bn_dgamma = g->bn_g[l]; a.bn_dbeta = g->bn_b[l];
+}
+
 // a bias gradient = the column sums of `rows` partial rows of C floats (ctx.partials)
 static int bias_grad_from_rows(const Pass& ctx, int rows, int C, float* db, const char* what) {
     const float* pp = ctx.pre(rows, C);
@@ -1108,9 +1121,16 @@ static int conv_backward_tail(const cp_config* c, const cp_params* p, const floa
     } else {
         ca.gin_exp = g8 ? (const int*)&g8->e[F8_T_GRAD + 1] : nullptr;
         if (int e = conv2_wgrad<T>(ctx.conv(), p, g, ca, false, g8 != nullptr, partials, gcol_rows, nullptr, nullptr)) return e;
-        ProfScope ps(CP_K_BN_BWD, st);
-        if (int e = bwd_finalize(ctx, g, ctx.rows2(), CONV2_FINISH_ROWS, (double)R12, 0, 64, 1, "bn_bwd_finalize_kernel(conv1)")) return e;
-        ca.coef = ctx.coef;
+        ProfScope ps(CP_K_BN_BWD, st);          // (the profiler keeps its record of this step of the plan; with the prologue it brackets no launch)
+        if (!g8 && bwd_in_prologue(ctx, CONV2_FINISH_ROWS, BNP_MAX_ROWS)) {
+            // BatchNorm1's backward is finalised in conv2_dgrad_conv1_kernel's prologue, from the finish launch's rows and with the finalize
+            // launch's bits (the 8-bit step keeps the launch)
+            ca.stats1 = ctx.stats(0); ca.rows1 = ctx.rows2(); ca.rows1_nr = CONV2_FINISH_ROWS;
+            ca.dgamma1 = g->bn_g[0]; ca.dbeta1 = g->bn_b[0];
+        } else {
+            if (int e = bwd_finalize(ctx, g, ctx.rows2(), CONV2_FINISH_ROWS, (double)R12, 0, 64, 1, "bn_bwd_finalize_kernel(conv1)")) return e;
+            ca.coef = ctx.coef;
+        }
     }
     int grid_d = 0;
     ca.wc = base + w.wc2_d;
@@ -1257,11 +1277,15 @@ static int encoder_backward_t(const cp_config* c, const cp_params* p, const floa
         const hipStream_t sw = aux.s();                 // (with dropout nothing waits for this weight gradient: second stream)
         int S;
         const bool proj_alg = fuse_ok && drop && sizeof(T) == 2;
+        // (proj_dgrad_kernel finalises fc7's BatchNorm backward in its prologue: the finish launch's rows then go to rows2, bwd_in_prologue)
+        const bool proj_pro = proj_alg && bwd_in_prologue(ctx, PROJ_FINISH_ROWS, 16);
         if (proj_alg) {
             // behind fc7's dropout, 16-bit storage (round 4): the weight gradient's launch reads r8 ONCE and leaves both dW and fc7's
             // BatchNorm-backward sums (gemm_tn.cuh, proj_wgrad_sums_kernel); on the critical path -- the data gradient below needs the sums
             if constexpr (sizeof(T) == 2) {
-                if (int e = launch_proj_wgrad_onepass(pl, (const bf16_t*)dz, ctx.act<T>(8), nullptr, slabs, dp, ctx.scale(8), ctx.shift(8), p->last_w, g->last_w, &S)) return e;
+                ProjLaunch pw = pl;
+                if (proj_pro) pw.partials = ctx.rows2();
+                if (int e = launch_proj_wgrad_onepass(pw, (const bf16_t*)dz, ctx.act<T>(8), nullptr, slabs, dp, ctx.scale(8), ctx.shift(8), p->last_w, g->last_w, &S)) return e;
             }
         } else {
             if (int e = launch_proj_wgrad_tn<T>(pl, sw, dz, ctx.act<T>(8), nullptr, aux.on ? (float*)(base + w.slabs_b) : slabs, ctx.scale(8), ctx.shift(8), dp,
@@ -1289,7 +1313,8 @@ static int encoder_backward_t(const cp_config* c, const cp_params* p, const floa
             // behind fc7's dropout: the rank-16 product is formed with fc7's BN + ReLU backward applied (gemm_ws.cuh, proj_dgrad_kernel)
             // instead of being written out for a separate bn_relu_bwd pass; the BatchNorm-backward sums it needs came with the weight
             // gradient above (round 3's first pass of the same product was removed; see git history)
-            if (int e = bwd_finalize(ctx, g, partials, PROJ_FINISH_ROWS, (double)N, 8, 512, 1, "bn_bwd_finalize_kernel(fc7, projection)")) return e;
+            if (proj_pro) set_bn_prologue(a, ctx, g, ctx.rows2(), PROJ_FINISH_ROWS, (double)N, 8);
+            else if (int e = bwd_finalize(ctx, g, partials, PROJ_FINISH_ROWS, (double)N, 8, 512, 1, "bn_bwd_finalize_kernel(fc7, projection)")) return e;
             a.coef = coef; a.coef_mod = 512;
             CK(launch_proj_dgrad(a, st, &drows));
             if (int e = bias_grad_from_rows(ctx, drows, 512, g->fc_b[6], "colsum_finalize_kernel(fc7, projection)")) return e;
@@ -1325,6 +1350,9 @@ static int encoder_backward_t(const cp_config* c, const cp_params* p, const floa
         const T* Y = in_drop ? (const T*)(base + w.u[Lp - 5]) : ctx.act<T>(Lp);
         const float* s = in_drop ? nullptr : ctx.scale(Lp);
         const float* t = in_drop ? nullptr : ctx.shift(Lp);
+        // the fused data gradient below runs gemm_wsd16_kernel<0> (launch_fc_gemm: 16 bits, static schedule), which finalises layer Lp's
+        // BatchNorm backward in its prologue: the sums' rows then go to rows2 (bwd_in_prologue)
+        const bool dgrad_pro = fuse_ok && !in_drop && !dyn_tiles(c) && bwd_in_prologue(ctx, kSumSlices, 16);
         int S;
         WgradPlace pl;           // (paired launches: 16-bit storage only, and not under CP_OPT_UNPAIRED_WGRAD)
         if (int e = place_wgrad(ctx, aux, in_drop, i, sizeof(T) == 2 && !opt(c, CP_OPT_UNPAIRED_WGRAD), &pl)) return e;
@@ -1349,21 +1377,31 @@ static int encoder_backward_t(const cp_config* c, const cp_params* p, const floa
         }
         if (!pl.defer) {
             ProfScope ps(CP_K_REDUCE_SLABS, pl.sw);
-            if (pending) {
-                // the deferred layer (always behind a dropout: no BN fold to undo, no raw product wanted)
-                hipLaunchKernelGGL(reduce_slabs_kernel<float>, dim3(512), dim3(256), 0, pl.sw, pl.slabs + (size_t)32 * 512 * 512, S, 512, 512, 512,
-                                   (const float*)nullptr, (const float*)nullptr, g->fc_b[pend.i], g->fc_w[pend.i], 0, (float*)nullptr);
-                CKL("reduce_slabs(fc, deferred)");
+            if (pending && !opt(c, CP_OPT_FINALIZE_LAUNCHES)) {
+                // the deferred layer (always behind a dropout: no BN fold to undo, no raw product wanted) and this one in one launch
+                ReduceSlabsPair rp{};
+                rp.job[0] = ReduceSlabsJob{pl.slabs + (size_t)32 * 512 * 512, nullptr, nullptr, g->fc_b[pend.i], g->fc_w[pend.i], nullptr, S, 512, 512, 512, 0};
+                rp.job[1] = ReduceSlabsJob{pl.slabs, s, t, g->fc_b[i], g->fc_w[i], in_drop ? (float*)nullptr : praw, S, 512, K, 512, i == 0 ? 1 : 0};
+                hipLaunchKernelGGL(reduce_slabs_pair_kernel, dim3(512, 2), dim3(256), 0, pl.sw, rp);
+                CKL("reduce_slabs_pair(fc)");
                 pending = false;
+            } else {
+                if (pending) {
+                    // the deferred layer (always behind a dropout: no BN fold to undo, no raw product wanted)
+                    hipLaunchKernelGGL(reduce_slabs_kernel<float>, dim3(512), dim3(256), 0, pl.sw, pl.slabs + (size_t)32 * 512 * 512, S, 512, 512, 512,
+                                       (const float*)nullptr, (const float*)nullptr, g->fc_b[pend.i], g->fc_w[pend.i], 0, (float*)nullptr);
+                    CKL("reduce_slabs(fc, deferred)");
+                    pending = false;
+                }
+                hipLaunchKernelGGL(reduce_slabs_kernel<float>, dim3(512), dim3(256), 0, pl.sw, pl.slabs, S, 512, K, 512, s, t, g->fc_b[i], g->fc_w[i],
+                                   i == 0 ? 1 : 0, in_drop ? (float*)nullptr : praw);
+                CKL("reduce_slabs(fc)");
             }
-            hipLaunchKernelGGL(reduce_slabs_kernel<float>, dim3(512), dim3(256), 0, pl.sw, pl.slabs, S, 512, K, 512, s, t, g->fc_b[i], g->fc_w[i],
-                               i == 0 ? 1 : 0, in_drop ? (float*)nullptr : praw);
-            CKL("reduce_slabs(fc)");
             if (!in_drop) {
                 // no dropout between this layer and the previous BN: its backward sums follow from P = g_y^T r
                 // (just reduced), W and db -- the data-gradient launch below then reads no saved activation
                 hipLaunchKernelGGL(bn_bwd_sums_from_wgrad_kernel, dim3(K / 64, kSumSlices), dim3(256), 0, st, praw, p->fc_w[i],
-                                   g->fc_b[i], partials, 512, K, i == 0 ? 1 : 0);
+                                   g->fc_b[i], dgrad_pro ? ctx.rows2() : partials, 512, K, i == 0 ? 1 : 0);
                 CKL("bn_bwd_sums_from_wgrad_kernel");
             }
         }
@@ -1379,10 +1417,12 @@ static int encoder_backward_t(const cp_config* c, const cp_params* p, const floa
             // now and let this launch's epilogue apply BN backward + the ReLU mask to its own output tile
             const int Cp = kLayerC[Lp], nfold = K / Cp;                   // fc below: 512 x 1; conv2 below: 64 x 12
             {
+                // (the profiler keeps its record of this step of the plan; with the prologue it brackets no launch)
                 ProfScope ps(CP_K_BN_BWD, st);
                 int nr = stat_rows;
                 const float* pp = ctx.pre(nr, 2 * K);
-                if (int e = bwd_finalize(ctx, g, pp, nr, (double)N * nfold, Lp, Cp, nfold, "bn_bwd_finalize_kernel(fused)")) return e;
+                if (dgrad_pro) set_bn_prologue(a, ctx, g, ctx.rows2(), nr, (double)N * nfold, Lp);
+                else if (int e = bwd_finalize(ctx, g, pp, nr, (double)N * nfold, Lp, Cp, nfold, "bn_bwd_finalize_kernel(fused)")) return e;
             }
             a.R = ctx.act<T>(Lp); a.coef = coef; a.coef_mod = Cp;
             int drows = 0;

@@ -44,6 +44,16 @@ struct GemmNTArgs {
     const uint32_t* dp_salt;   // optional device word XOR-ed into dp_key (graph replay: the per-step part of the key)
     float dp_inv_keep;
     int* sched;          // persistent kernel: its stream's tile counters (per XCD, and blocks finished; 32 ints apart); set by the launcher
+    // gemm_wsd16_kernel<0> and proj_dgrad_kernel only; bn_rows == nullptr (every other caller): `coef` is ready.  Else the coefficients are
+    // formed in the kernel's prologue (common.cuh, bnp_*) from bn_nr <= 16 partial rows [2][F] of (sum g, sum g r) and the layer's
+    // statistics table bn_stats [4][coef_mod], as bn_bwd_finalize_kernel forms them; the blocks of the first row worker store
+    // bn_dgamma / bn_dbeta [coef_mod].  `coef` is not read.
+    const float* bn_rows;
+    const float* bn_stats;
+    float* bn_dgamma;
+    float* bn_dbeta;
+    double bn_count;
+    int bn_nr;
 };
 
 template <typename T, int BM, int BN, int ALOAD, int EPI>

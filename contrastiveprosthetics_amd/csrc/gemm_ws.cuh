@@ -501,7 +501,9 @@ __global__ __launch_bounds__(256, 1) void gemm_wsd16_kernel(GemmNTArgs a) {
     constexpr int RT = WSD16_RT, TILE_BYTES = RT * WS_K * 2, R_BYTES = RT * 128;          // R: per wave and buffer, rows of 64 features
     constexpr int K = WS_K, KB = K / 32, RPW = RT / 4, ST = RT / 16;
     constexpr int R_OFF = 2 * TILE_BYTES, COEF_OFF = R_OFF + 4 * 2 * R_BYTES;
-    __shared__ __attribute__((aligned(16))) unsigned char smem[COEF_OFF];
+    // MODE 0, coefficients formed here (GemmNTArgs::bn_rows): their table [3][256] and the quads' sums [2][4][64] of the 64-channel form
+    constexpr int BNP_BYTES = STATS ? 0 : 3 * 256 * 4 + 2 * 4 * 64 * 8;
+    __shared__ __attribute__((aligned(16))) unsigned char smem[COEF_OFF + BNP_BYTES];
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -519,20 +521,73 @@ __global__ __launch_bounds__(256, 1) void gemm_wsd16_kernel(GemmNTArgs a) {
     // MODE 0: the three BatchNorm-backward coefficients of this lane's 16 features stay in registers (48 of them; read from an LDS
     // table per epilogue slot they were 6 of its 8 ds_read_b128)
     float4 cfa[STATS ? 1 : 4], cfb[STATS ? 1 : 4], cfz[STATS ? 1 : 4];
+    // ... or are formed below from the partial rows (GemmNTArgs::bn_rows)
+    const bool bnp = !STATS && a.bn_rows != nullptr, bnp_wide = a.coef_mod == a.F;
     if constexpr (!STATS) {
+        if (!bnp) {
 #pragma unroll
-        for (int ft = 0; ft < 4; ++ft) {
-            float v[3][4];
+            for (int ft = 0; ft < 4; ++ft) {
+                float v[3][4];
 #pragma unroll
-            for (int c = 0; c < 3; ++c)
+                for (int c = 0; c < 3; ++c)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[c][e] = a.coef[c * a.coef_mod + (f0 + ft * 16 + 4 * (lane >> 4) + e) % a.coef_mod];
-            cfa[ft] = make_float4(v[0][0], v[0][1], v[0][2], v[0][3]);
-            cfb[ft] = make_float4(v[1][0], v[1][1], v[1][2], v[1][3]);
-            cfz[ft] = make_float4(v[2][0], v[2][1], v[2][2], v[2][3]);
+                    for (int e = 0; e < 4; ++e) v[c][e] = a.coef[c * a.coef_mod + (f0 + ft * 16 + 4 * (lane >> 4) + e) % a.coef_mod];
+                cfa[ft] = make_float4(v[0][0], v[0][1], v[0][2], v[0][3]);
+                cfb[ft] = make_float4(v[1][0], v[1][1], v[1][2], v[1][3]);
+                cfz[ft] = make_float4(v[2][0], v[2][1], v[2][2], v[2][3]);
+            }
         }
     }
 
+    if constexpr (!STATS) {
+        if (bnp) {
+            // bn_bwd_finalize_kernel's sums and expressions (common.cuh, bnp_*) for this block's channels -> LDS table.  coef_mod == F: thread =
+            // one of the block's 256 channels, all four quads of rows; coef_mod == 64 (F = 768, the conv stack seen through fc1: 12
+            // positions per channel): thread = (channel, quad).  All of it BEFORE the weights are requested: between the weight loads
+            // and their wait hipcc must find nothing to schedule (with this fold there it moved a requested fragment out of its
+            // accumulator registers before the data had landed).
+            float* coef_s = (float*)(smem + COEF_OFF);                      // [3][256]
+            double* quad_s = (double*)(smem + COEF_OFF + 3 * 256 * 4);      // [2][4][64]
+            const bool writer = xcd == 0 && wkr == 0;                       // (these blocks have a tile whenever M > 0)
+            if (bnp_wide) {
+                const int c = fb * 256 + tid;
+                double w1[4], w2[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    BnpQuad<1> bq;
+                    bnp_load(bq, a.bn_rows, a.bn_nr, a.F, c, q);
+                    bnp_quad_sum(bq, w1[q], w2[q]);
+                }
+                float ca, cb, cz, dg, db;
+                bnp_coef(bnp_total(w1, 4, 1), bnp_total(w2, 4, 1), a.bn_stats, a.F, c, a.bn_count, ca, cb, cz, dg, db);
+                coef_s[tid] = ca; coef_s[256 + tid] = cb; coef_s[512 + tid] = cz;
+                if (writer) { a.bn_dgamma[c] = dg; a.bn_dbeta[c] = db; }
+            } else {
+                const int c = tid & 63, q = tid >> 6;
+                BnpQuad<12> bq;
+                bnp_load(bq, a.bn_rows, a.bn_nr, 64, c, q);
+                double w1, w2;
+                bnp_quad_sum(bq, w1, w2);
+                quad_s[q * 64 + c] = w1;
+                quad_s[(4 + q) * 64 + c] = w2;
+                __syncthreads();
+                if (tid < 64) {
+                    float ca, cb, cz, dg, db;
+                    bnp_coef(bnp_total(quad_s + c, 4, 64), bnp_total(quad_s + 4 * 64 + c, 4, 64), a.bn_stats, 64, c, a.bn_count, ca, cb, cz, dg, db);
+                    coef_s[c] = ca; coef_s[256 + c] = cb; coef_s[512 + c] = cz;
+                    if (writer && fb == 0) { a.bn_dgamma[c] = dg; a.bn_dbeta[c] = db; }
+                }
+            }
+            __syncthreads();
+            const int fl = (bnp_wide ? wave * 64 : 0) + 4 * q4;
+#pragma unroll
+            for (int ft = 0; ft < 4; ++ft) {
+                cfa[ft] = *(const float4*)(coef_s + fl + ft * 16);
+                cfb[ft] = *(const float4*)(coef_s + 256 + fl + ft * 16);
+                cfz[ft] = *(const float4*)(coef_s + 512 + fl + ft * 16);
+            }
+        }
+    }
     s16x8 wreg[4][KB];
     {
         const bf16_t* Wg = (const bf16_t*)a.W + (int64_t)(f0 + s16) * K + 8 * q4;
@@ -742,9 +797,24 @@ __global__ __launch_bounds__(256, 2) void proj_dgrad_kernel(GemmNTArgs a) {
     const int first = wkr * 8 + xcd, stride = nwk * 8;
     const int ntile = (wkr < nwk && first < tiles) ? (int)((tiles - first + stride - 1) / stride) : 0;
     if (ntile == 0) return;
-    for (int q = tid; q < 3 * 256; q += 256) {
-        const int c = q >> 8, f = fb * 256 + (q & 255);
-        coef_s[q] = a.coef[c * a.coef_mod + f % a.coef_mod];
+    if (a.bn_rows != nullptr) {
+        // the coefficients formed here (GemmNTArgs::bn_rows; common.cuh, bnp_*; coef_mod == F): thread = one of the block's 256 channels
+        BnpQuad<1> bq[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) bnp_load(bq[q], a.bn_rows, a.bn_nr, a.F, fb * 256 + tid, q);
+        double w1[4], w2[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) bnp_quad_sum(bq[q], w1[q], w2[q]);
+        const int c = fb * 256 + tid;
+        float ca, cb, cz, dg, db;
+        bnp_coef(bnp_total(w1, 4, 1), bnp_total(w2, 4, 1), a.bn_stats, a.F, c, a.bn_count, ca, cb, cz, dg, db);
+        coef_s[tid] = ca; coef_s[256 + tid] = cb; coef_s[512 + tid] = cz;
+        if (xcd == 0 && wkr == 0) { a.bn_dgamma[c] = dg; a.bn_dbeta[c] = db; }          // (these blocks have a tile whenever M > 0)
+    } else {
+        for (int q = tid; q < 3 * 256; q += 256) {
+            const int c = q >> 8, f = fb * 256 + (q & 255);
+            coef_s[q] = a.coef[c * a.coef_mod + f % a.coef_mod];
+        }
     }
     __syncthreads();
     const int f0 = fb * 256 + wave * 64, fl0 = wave * 64;
@@ -868,6 +938,7 @@ __global__ __launch_bounds__(256, 2) void proj_dgrad_kernel(GemmNTArgs a) {
 // grid: 4 workgroups per CU (32 KiB of LDS and ~100 registers each); *stat_rows = partial rows written
 static inline hipError_t launch_proj_dgrad(const GemmNTArgs& a, hipStream_t st, int* stat_rows) {
     if ((a.F & 255) || a.K < 16 || (a.K & 3) || !a.R || !a.coef) return hipErrorInvalidValue;
+    if (a.bn_rows && (a.coef_mod != a.F || a.bn_nr < 1 || a.bn_nr > 16 || !a.bn_stats || !a.bn_dgamma || !a.bn_dbeta)) return hipErrorInvalidValue;
 // workgroups of the projection's data-gradient launches (this one and fp8.cuh's): two per CU.  1024 / 768 / 512 / 384 / 256 on one box:
 // 84-89 / 82-84 / 76-81 / 95 / 98 us (16-bit), 62-63 / 57 / 54-57 / 70 / 68 (8-bit)
 #define PROJ_DGRAD_BLOCKS 512
@@ -880,6 +951,10 @@ static inline hipError_t launch_proj_dgrad(const GemmNTArgs& a, hipStream_t st, 
 
 static inline hipError_t launch_gemm_wsd_bn(const GemmNTArgs& a, hipStream_t st, int* stat_rows) {
     if (a.K != WS_K || (a.F & 255) || a.F > 768 || a.lda != WS_K || !a.R) return hipErrorInvalidValue;
+    // coefficients formed in the prologue: one channel per feature, or the 64 channels x 12 positions of fc1's output
+    if (a.bn_rows && (!a.coef || !(a.coef_mod == a.F || (a.coef_mod == 64 && a.F == 768)) || a.bn_nr < 1 || a.bn_nr > 16 || !a.bn_stats ||
+                      !a.bn_dgamma || !a.bn_dbeta))
+        return hipErrorInvalidValue;
     const int nfb = a.F >> 8, nwk = 32 / nfb;
     const int64_t tiles = (a.M + WSD16_RT - 1) / WSD16_RT;
     const int64_t workers = (int64_t)nwk * 8;

@@ -660,11 +660,11 @@ __global__ void conv1_bwd_finalize_kernel(const float* __restrict__ partials, in
 //   mode 3 (transposed): grad[q*p_valid + p] = P   (slab rows are the operand that was padded)
 //   rows p >= p_valid are dropped (projection padded 16 -> 64)
 // ------------------------------------------------------------------------------------
-template <typename ST = float>         // ST: element type of the slabs (bf16_t: the 8-bit path's gemm_tn8_kernel)
-__global__ void reduce_slabs_kernel(const float* __restrict__ slabs_, int S, int P, int Q, int p_valid,
-                                    const float* __restrict__ s, const float* __restrict__ t,
-                                    const float* __restrict__ dbsum, float* __restrict__ grad, int mode,
-                                    float* __restrict__ raw, const int* __restrict__ exp_x = nullptr, const int* __restrict__ exp_y = nullptr) {
+template <typename ST>
+__device__ __forceinline__ void reduce_slabs_body(const float* __restrict__ slabs_, int S, int P, int Q, int p_valid,
+                                                  const float* __restrict__ s, const float* __restrict__ t,
+                                                  const float* __restrict__ dbsum, float* __restrict__ grad, int mode,
+                                                  float* __restrict__ raw, const int* __restrict__ exp_x, const int* __restrict__ exp_y) {
     // exp_x / exp_y (CP_FP8): scale exponents of the two 8-bit operands of the product; the slabs hold it in stored units
     const float unscale = exp_x != nullptr ? f8_exp2i(-*exp_x - *exp_y) : 1.f;
     // FOUR consecutive columns per thread and load (round 4, third part: one column per thread was 64 four-byte loads per output and
@@ -717,6 +717,21 @@ __global__ void reduce_slabs_kernel(const float* __restrict__ slabs_, int S, int
             grad[dst] = acc;
         }
     }
+}
+template <typename ST = float>         // ST: element type of the slabs (bf16_t: the 8-bit path's gemm_tn8_kernel)
+__global__ void reduce_slabs_kernel(const float* __restrict__ slabs_, int S, int P, int Q, int p_valid,
+                                    const float* __restrict__ s, const float* __restrict__ t,
+                                    const float* __restrict__ dbsum, float* __restrict__ grad, int mode,
+                                    float* __restrict__ raw, const int* __restrict__ exp_x = nullptr, const int* __restrict__ exp_y = nullptr) {
+    reduce_slabs_body<ST>(slabs_, S, P, Q, p_valid, s, t, dbsum, grad, mode, raw, exp_x, exp_y);
+}
+// the two folds behind a paired weight-gradient launch (gemm_tn256_kernel with X2 / Y2) in ONE launch: blockIdx.y = job, each job on the
+// blocks and with the per-block work of its own reduce_slabs_kernel<float> launch
+struct ReduceSlabsJob { const float* slabs; const float* s; const float* t; const float* dbsum; float* grad; float* raw; int S, P, Q, p_valid, mode; };
+struct ReduceSlabsPair { ReduceSlabsJob job[2]; };
+__global__ void reduce_slabs_pair_kernel(ReduceSlabsPair rp) {
+    const ReduceSlabsJob& j = rp.job[blockIdx.y];
+    reduce_slabs_body<float>(j.slabs, j.S, j.P, j.Q, j.p_valid, j.s, j.t, j.dbsum, j.grad, j.mode, j.raw, nullptr, nullptr);
 }
 
 // ------------------------------------------------------------------------------------
