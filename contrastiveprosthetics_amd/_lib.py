@@ -149,6 +149,19 @@ class cp_debug_proj_args(C.Structure):
                 ("rows_out", C.POINTER(C.c_int32))]
 
 
+class cp_debug_fp8_args(C.Structure):
+    """One launch sequence of the 8-bit fc path on caller buffers and a caller scale table (include/cpnative.h): what cp_debug_fp8 takes."""
+    _fields_ = [("kind", C.c_int32), ("mode", C.c_int32), ("M", C.c_int64), ("K", C.c_int32), ("F", C.c_int32),
+                ("coef_mod", C.c_int32), ("t_in", C.c_int32), ("t_r", C.c_int32), ("t_out", C.c_int32), ("t_in2", C.c_int32),
+                ("t_r2", C.c_int32),
+                ("state", C.c_void_p), ("A", C.c_void_p), ("W", C.c_void_p), ("wsc", C.c_void_p), ("bias", C.c_void_p),
+                ("R", C.c_void_p), ("coef", C.c_void_p), ("bn_stats", C.c_void_p), ("scale", C.c_void_p), ("shift", C.c_void_p),
+                ("C", C.c_void_p), ("partials", C.c_void_p), ("A2", C.c_void_p), ("R2", C.c_void_p), ("partials2", C.c_void_p),
+                ("C2", C.c_void_p),
+                ("dp_thresh", C.c_uint32), ("dp_key", C.c_uint32), ("dp_inv_keep", C.c_float), ("reserved0", C.c_int32),
+                ("rows_out", C.POINTER(C.c_int32))]
+
+
 CP_ONLINE_MAX_CLASSES, CP_ONLINE_MAX_VOTE, CP_ONLINE_MAX_WINDOWS, CP_ONLINE_STRIDE = 64, 256, 256, 20
 CP_ONLINE_MULTI_MAX_STREAMS, CP_ONLINE_MULTI_MAX_ROWS = 256, 65536
 CP_ONLINE_GATE_SCORES, CP_ONLINE_GATE_SWEEP_MAX_CONFIGS = 10, 65536
@@ -218,6 +231,7 @@ SYMBOLS = {
     "cp_debug_fc_gemm": (C.c_int, [_P(cp_debug_fc_gemm_args), _fp]),
     "cp_debug_conv": (C.c_int, [_P(cp_debug_conv_args), _fp]),
     "cp_debug_proj": (C.c_int, [_P(cp_debug_proj_args), _fp]),
+    "cp_debug_fp8": (C.c_int, [_P(cp_debug_fp8_args), _fp]),
     "cp_online_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "cp_online_prepare": (C.c_int, [_P(cp_online_config), _P(cp_params), _P(cp_bn_buffers), C.c_float, _fp, C.c_size_t, _fp]),
     "cp_online_set_classes": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, _fp, C.c_int32, _fp]),

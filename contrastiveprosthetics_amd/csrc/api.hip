@@ -1071,6 +1071,141 @@ extern "C" int cp_debug_proj(const cp_debug_proj_args* args, void* stream) {
     return debug_proj_t<float>(args, (hipStream_t)stream);
 }
 
+// One launch sequence of the 8-bit fc path on caller buffers and a caller scale table, through the launch functions of the step
+// (csrc/fp8.cuh, csrc/encoder_api.cuh: their grids, row splits and partial-row counts), at any row count
+static int debug_fp8(const cp_debug_fp8_args* d, hipStream_t st) {
+    Fp8State* fs = (Fp8State*)d->state;
+    const int64_t M = d->M;
+    int rows = 0;
+    switch (d->kind) {
+    case 0: {
+        Ws8Args a{};
+        a.A = (const uint8_t*)d->A; a.W = (const uint8_t*)d->W; a.wsc = (const uint8_t*)d->wsc; a.bias = d->bias; a.C = (uint8_t*)d->C;
+        a.partials = d->partials; a.amax = &fs->amax[d->t_out]; a.M = M; a.F = d->F;
+        if (d->K == 512) CK(launch_gemm_ws8<512>(a, st, &rows));
+        else CK(launch_gemm_ws8<768>(a, st, &rows));
+        if (!d->partials) rows = 0;
+        break;
+    }
+    case 1:
+    case 2: {
+        Wsd8Args a{};
+        a.A = (const uint8_t*)d->A; a.W = (const uint8_t*)d->W; a.wsc = (const uint8_t*)d->wsc; a.R = (const uint8_t*)d->R; a.C = d->C;
+        a.partials = d->partials; a.st = fs; a.t_r = d->t_r; a.t_out = d->t_out; a.M = M; a.F = d->F;
+        if (d->kind == 1) {
+            a.coef = d->coef; a.coef_mod = d->coef_mod;
+            CK((launch_gemm_wsd8<0>(a, st, &rows)));
+        } else {
+            a.bn_stats = d->bn_stats; a.dp_inv_keep = d->dp_inv_keep;
+            CK((launch_gemm_wsd8<1>(a, st, &rows)));
+        }
+        break;
+    }
+    case 3: {
+        const bool paired = d->mode == 1;
+        GemmTN8Args ta{};
+        ta.X = (const uint8_t*)d->A; ta.ldx = 512; ta.Y = (const uint8_t*)d->R; ta.ldy = d->F; ta.slabs = d->partials; ta.M = M; ta.P = 512; ta.Q = d->F;
+        split_rows_tn8(M, paired, d->F, &rows, &ta.rows_per_split);
+        if (paired) { ta.X2 = (const uint8_t*)d->A2; ta.Y2 = (const uint8_t*)d->R2; ta.slabs2 = d->partials2; }
+        ta.splits = rows;
+        CK(launch_gemm_tn8(ta, st));
+        if (paired) launch_reduce_slabs8(d->partials2, rows, 512, nullptr, nullptr, nullptr, d->C2, 0, nullptr, (const int*)&fs->e[d->t_in2], (const int*)&fs->e[d->t_r2], st);
+        launch_reduce_slabs8(d->partials, rows, d->F, nullptr, nullptr, nullptr, (float*)d->C, 0, nullptr, (const int*)&fs->e[d->t_in], (const int*)&fs->e[d->t_r], st);
+        CKL("reduce_slabs_kernel<bf16>");
+        break;
+    }
+    case 4:
+        launch_bn_dropout_apply8((const uint8_t*)d->A, d->bn_stats, (uint8_t*)d->C, M, d->dp_thresh, d->dp_key, d->dp_inv_keep, nullptr, fs, d->t_in, d->t_out, st);
+        CKL("bn_dropout_apply8_kernel");
+        break;
+    case 5:
+        rows = launch_bn_relu_bwd8((uint8_t*)d->C, (const uint8_t*)d->R, d->coef, d->partials, M, fs, d->t_in, d->t_r, d->t_out, st);
+        CKL("bn_relu_bwd8_kernel");
+        break;
+    case 6: {
+        Proj8Args a{};
+        a.A = (const bf16_t*)d->A; a.lda = 64; a.W = (const bf16_t*)d->W; a.K = 64; a.R = (const uint8_t*)d->R; a.C = (uint8_t*)d->C;
+        a.partials = d->partials; a.coef = d->coef; a.st = fs; a.t_r = d->t_r; a.t_out = d->t_out; a.M = M;
+        a.dp_thresh = d->dp_thresh; a.dp_key = d->dp_key; a.dp_inv_keep = d->dp_inv_keep;
+        CK(launch_proj_dgrad8(a, st, &rows));
+        break;
+    }
+    case 7:
+        if (d->mode < 2) {
+            launch_fold_linear8((const float*)d->A, d->bias, d->scale, d->shift, (uint8_t*)d->C, (uint8_t*)d->wsc, d->partials, d->K, d->mode, fs,
+                                d->t_in, d->t_out, st);
+            CKL("fold_linear8_kernel");
+        } else {
+            Transpose8Batch tb{};
+            tb.job[0] = Transpose8Job{(const float*)d->A, (uint8_t*)d->C, (uint8_t*)d->wsc, d->K, d->mode == 3 ? 1 : 0, d->t_in};
+            launch_transpose_w8_batch(tb, 1, fs, st);
+            CKL("transpose_w8_batch_kernel");
+        }
+        break;
+    default:
+        hipLaunchKernelGGL(fp8_update_scales_kernel, dim3(1), dim3(64), 0, st, fs, M);
+        CKL("fp8_update_scales_kernel");
+        break;
+    }
+    if (d->rows_out) *d->rows_out = rows;
+    return 0;
+}
+
+// everything a launcher would refuse, or a kernel would read or write out of bounds, before anything launches
+static int check_debug_fp8(const cp_debug_fp8_args* d) {
+    if (!d) return fail(CP_ERR_ARG, "cp_debug_fp8 args");
+    if (d->kind < 0 || d->kind > 8) return fail(CP_ERR_ARG, "cp_debug_fp8: kind must be 0..8");
+    const int k = d->kind;
+    if (!d->state) return fail(CP_ERR_ARG, "cp_debug_fp8: state must not be NULL");
+    if (d->M <= 0) return fail(CP_ERR_ARG, "cp_debug_fp8: M must be positive");
+    if ((k == 3 && d->mode != 0 && d->mode != 1) || (k == 7 && (d->mode < 0 || d->mode > 3)) || (k != 3 && k != 7 && d->mode != 0))
+        return fail(CP_ERR_ARG, "cp_debug_fp8: mode must be 0 | 1 in kind 3, 0..3 in kind 7, else 0");
+    const bool paired = k == 3 && d->mode == 1;
+    if (k != 8) {
+        if ((k != 5 && !d->A) || !d->C) return fail(CP_ERR_ARG, "cp_debug_fp8: A and C must not be NULL");
+        if (k != 0 && k != 4 && !(k == 7 && d->mode >= 2) && !d->partials) return fail(CP_ERR_ARG, "cp_debug_fp8: partials must not be NULL");
+        if ((k <= 2 || k == 6) && !d->W) return fail(CP_ERR_ARG, "cp_debug_fp8: W must not be NULL");
+        if ((k <= 2 || k == 7) && !d->wsc) return fail(CP_ERR_ARG, "cp_debug_fp8: wsc must not be NULL");
+        if (k == 0 && !d->bias) return fail(CP_ERR_ARG, "cp_debug_fp8: the forward needs a bias");
+        if ((k == 1 || k == 2 || k == 3 || k == 5 || k == 6) && !d->R) return fail(CP_ERR_ARG, "cp_debug_fp8: R must not be NULL");
+        if ((k == 1 || k == 5 || k == 6) && !d->coef) return fail(CP_ERR_ARG, "cp_debug_fp8: kinds 1, 5 and 6 need coef");
+        if ((k == 2 || k == 4) && !d->bn_stats) return fail(CP_ERR_ARG, "cp_debug_fp8: kinds 2 and 4 need bn_stats");
+        if (paired && (!d->A2 || !d->R2 || !d->partials2 || !d->C2)) return fail(CP_ERR_ARG, "cp_debug_fp8: a paired launch needs A2, R2, partials2 and C2");
+        if (k == 7 && d->mode < 2 && !d->scale != !d->shift) return fail(CP_ERR_ARG, "cp_debug_fp8: scale and shift come together");
+    }
+    // shapes the launch functions refuse or the kernels are not written for
+    if (k == 0 && ((d->K != 512 && d->K != 768) || d->F != 512)) return fail(CP_ERR_ARG, "cp_debug_fp8: kind 0 takes K = 512 | 768 and F = 512");
+    if ((k == 1 || k == 3) && d->F != 512 && d->F != 768) return fail(CP_ERR_ARG, "cp_debug_fp8: kinds 1 and 3 take F = 512 | 768");
+    if ((k == 2 || (k >= 4 && k <= 6) || paired) && d->F != 512) return fail(CP_ERR_ARG, "cp_debug_fp8: kinds 2, 4, 5, 6 and a paired launch take F = 512");
+    if (k == 7 && d->K != 512 && d->K != 768) return fail(CP_ERR_ARG, "cp_debug_fp8: kind 7 takes K = 512 | 768");
+    if (k == 1 && d->coef_mod <= 0) return fail(CP_ERR_ARG, "cp_debug_fp8: coef_mod must be positive");
+    // scale-table ids
+    auto id_ok = [](int t) { return t >= 0 && t < F8_NT; };
+    if ((k == 3 || k == 4 || k == 5 || k == 7) && !id_ok(d->t_in)) return fail(CP_ERR_ARG, "cp_debug_fp8: t_in outside 0..63");
+    if (((k >= 1 && k <= 3) || k == 5 || k == 6) && !id_ok(d->t_r)) return fail(CP_ERR_ARG, "cp_debug_fp8: t_r outside 0..63");
+    if ((k <= 2 || (k >= 4 && k <= 6)) && !id_ok(d->t_out)) return fail(CP_ERR_ARG, "cp_debug_fp8: t_out outside 0..63");
+    if (k == 7 && d->mode < 2 && !(id_ok(d->t_out) || d->t_out == -1)) return fail(CP_ERR_ARG, "cp_debug_fp8: t_out outside -1..63");
+    if (paired && (!id_ok(d->t_in2) || !id_ok(d->t_r2))) return fail(CP_ERR_ARG, "cp_debug_fp8: t_in2 and t_r2 outside 0..63");
+    // dropout
+    if (d->dp_thresh > 65535u) return fail(CP_ERR_ARG, "cp_debug_fp8: dp_thresh must not exceed 65535");
+    if ((k == 2 || k == 4 || (k == 6 && d->dp_thresh != 0)) && !(d->dp_inv_keep > 0.f)) return fail(CP_ERR_ARG, "cp_debug_fp8: dp_inv_keep must be positive");
+    // 32-bit byte offsets of the buffer loads and stores, the "no such tile" offset 0xFFF00000 and the hash's 32-bit element index
+    if (k <= 6) {
+        const int kk = k == 0 ? d->K : 512, wide = kk > d->F ? kk : d->F;
+        if ((uint64_t)d->M >= (0xFFF00000ull + wide - 1) / wide) return fail(CP_ERR_ARG, "cp_debug_fp8: M * max(K, F) must stay below 2^32 - 2^20");
+    }
+    if ((((uintptr_t)d->state | (uintptr_t)d->A | (uintptr_t)d->W | (uintptr_t)d->wsc | (uintptr_t)d->bias | (uintptr_t)d->R | (uintptr_t)d->coef |
+          (uintptr_t)d->bn_stats | (uintptr_t)d->scale | (uintptr_t)d->shift | (uintptr_t)d->C | (uintptr_t)d->partials | (uintptr_t)d->A2 |
+          (uintptr_t)d->R2 | (uintptr_t)d->partials2 | (uintptr_t)d->C2) & 15) != 0)
+        return fail(CP_ERR_ARG, "cp_debug_fp8: state, A, W, wsc, bias, R, coef, bn_stats, scale, shift, C, partials, A2, R2, partials2 and C2 must be 16-byte aligned");
+    return 0;
+}
+
+extern "C" int cp_debug_fp8(const cp_debug_fp8_args* args, void* stream) {
+    if (int e = check_debug_fp8(args)) return e;
+    return debug_fp8(args, (hipStream_t)stream);
+}
+
 __global__ __launch_bounds__(256) void hog_kernel(long long ticks, float* sink) {
     __shared__ float pad[30 * 1024];                       // 120 KiB: no 64 KiB-stage GEMM block fits beside this one
     pad[threadIdx.x] = (float)threadIdx.x;

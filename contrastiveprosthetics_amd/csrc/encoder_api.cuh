@@ -190,13 +190,22 @@ static int launch_weight_transposes(const cp_params* p, unsigned char* base, con
     CKL("transpose_w_batch_kernel");
     return 0;
 }
+// the 8-bit weight preparation launches (cp_debug_fp8 runs the same two on one layer): one block per output row of a fold; 12 column
+// blocks of 64 (K <= 768) x jobs x 4 row quarters of a transpose
+static inline void launch_fold_linear8(const float* W, const float* b, const float* s, const float* t, uint8_t* out_w, uint8_t* out_sc, float* out_b,
+                                       int K, int mode, const Fp8State* fs, int t_in, int t_out, hipStream_t st) {
+    hipLaunchKernelGGL(fold_linear8_kernel, dim3(512), dim3(256), 0, st, W, b, s, t, out_w, out_sc, out_b, K, mode, fs, t_in, t_out);
+}
+static inline void launch_transpose_w8_batch(const Transpose8Batch& tb, int jobs, const Fp8State* fs, hipStream_t st) {
+    hipLaunchKernelGGL(transpose_w8_batch_kernel, dim3(12, jobs, 4), dim3(256), 0, st, tb, fs);
+}
 static int launch_weight_transposes_fp8(const cp_params* p, unsigned char* base, const WS& w, hipStream_t st) {
     ProfScope ps(CP_K_PREP, st);
     const Fp8State* fs = (const Fp8State*)(base + w.f8state);
     Transpose8Batch tb{};
     for (int i = 0; i < CP_N_FC; ++i)
         tb.job[i] = Transpose8Job{p->fc_w[i], base + w.wfc8t[i], base + w.wsc8t[i], fcK(i), i == 0 ? 1 : 0, F8_T_GRAD + (i + 2)};
-    hipLaunchKernelGGL(transpose_w8_batch_kernel, dim3(12, CP_N_FC, 4), dim3(256), 0, st, tb, fs);
+    launch_transpose_w8_batch(tb, CP_N_FC, fs, st);
     launch_proj_transpose<bf16_t>(p->last_w, base + w.wlast_t, st);
     CKL("transpose kernels (fp8)");
     return 0;
@@ -218,6 +227,20 @@ static int launch_weight_transposes_fp8(const cp_params* p, unsigned char* base,
 static inline int grid_rows(int64_t rows, int rows_per_block, int cap) {
     int64_t g = (rows + rows_per_block - 1) / rows_per_block;
     return (int)(g > cap ? cap : (g < 1 ? 1 : g));
+}
+
+// The 8-bit streaming passes around a dropout as the step launches them (cp_debug_fp8 runs the same functions on caller buffers):
+// 512 features, 8 rows per block.  launch_bn_relu_bwd8 returns the number of partial rows (= its grid).
+static inline void launch_bn_dropout_apply8(const uint8_t* r, const float* stats, uint8_t* u, int64_t N, uint32_t thresh, uint32_t key, float inv_keep,
+                                            const uint32_t* salt, Fp8State* fs, int t_in, int t_out, hipStream_t st) {
+    hipLaunchKernelGGL(bn_dropout_apply8_kernel, dim3(grid_rows(N, 256 / (512 / 16), CAP_BDA8)), dim3(256), 0, st, r, stats, u, N, 512,
+                       thresh, key, inv_keep, salt, fs, t_in, t_out);
+}
+static inline int launch_bn_relu_bwd8(uint8_t* g, const uint8_t* r, const float* coef, float* partials, int64_t N, Fp8State* fs, int t_in, int t_r,
+                                      int t_out, hipStream_t st) {
+    const int gb = grid_rows(N, 256 / (512 / 16), CAP_BRB8);
+    hipLaunchKernelGGL(bn_relu_bwd8_kernel, dim3(gb), dim3(256), 8 * 512 * 4, st, g, r, coef, partials, N, 512, fs, t_in, t_r, t_out);
+    return gb;
 }
 
 // fc-layer NT GEMM dispatch: bf16 runs the 256x256 LDS-DMA kernel (one 8-wave block per CU), f32
@@ -643,15 +666,15 @@ static int encoder_forward_fp8(const cp_config* c, const cp_params* p, const cp_
             uint8_t* u = base + w.u8[Lp - 5];
             t_in = F8_T_U + (Lp - 5);
             ProfScope ps(CP_K_DROPOUT, st);
-            hipLaunchKernelGGL(bn_dropout_apply8_kernel, dim3(grid_rows(N, 256 / (512 / 16), CAP_BDA8)), dim3(256), 0, st, A, ctx.stats(Lp), u, N, 512,
-                               dp_thresh(c->dp_emg), dp_key(c, Lp), dp_inv_keep(c->dp_emg), dp_salt(c), fs, F8_T_ACT + Lp, t_in);
+            launch_bn_dropout_apply8(A, ctx.stats(Lp), u, N, dp_thresh(c->dp_emg), dp_key(c, Lp), dp_inv_keep(c->dp_emg), dp_salt(c), fs, F8_T_ACT + Lp,
+                                     t_in, st);
             CKL("bn_dropout_apply8_kernel");
             A = u;
         }
         if (batch_stats && !in_drop) {     // (running statistics: all seven folds were made in one launch before the loop; behind a dropout: in the prep launch)
             ProfScope ps(CP_K_FOLD, st);
-            hipLaunchKernelGGL(fold_linear8_kernel, dim3(512), dim3(256), 0, st, p->fc_w[i], p->fc_b[i], ctx.scale(Lp), ctx.shift(Lp), base + w.wfc8[i],
-                               base + w.wsc8[i], (float*)(base + w.bfc[i]), K, i == 0 ? 1 : 0, fs, t_in, F8_T_ACT + L);
+            launch_fold_linear8(p->fc_w[i], p->fc_b[i], ctx.scale(Lp), ctx.shift(Lp), base + w.wfc8[i], base + w.wsc8[i], (float*)(base + w.bfc[i]), K,
+                                i == 0 ? 1 : 0, fs, t_in, F8_T_ACT + L, st);
             CKL("fold_linear8_kernel");
         }
         Ws8Args a{};
@@ -820,6 +843,16 @@ static inline void split_rows(int64_t M, int target_splits, int* splits, int64_t
     if (floor_rows && rps < round) rps = round;
     *rows_per_split = rps;
     *splits = (int)((M + rps - 1) / rps);
+}
+// the row split of an 8-bit weight-gradient launch (gemm_tn8_kernel: 64-row stages, rows past the end zero-filled): 64 splits for a
+// 512 x 512 layer, 40 for fc1's 512 x 768, 32 per problem of a paired launch
+static inline void split_rows_tn8(int64_t M, bool paired, int Q, int* splits, int64_t* rows_per_split) {
+    split_rows(M, paired ? 32 : (Q == 512 ? 64 : 40), splits, rows_per_split, 64, false);
+}
+// the fold of its bf16 slabs: the two tensors' scale exponents (device words of the scale table) are divided out
+static inline void launch_reduce_slabs8(const float* slabs, int S, int Q, const float* s, const float* t, const float* dbsum, float* grad, int mode,
+                                        float* raw, const int* exp_x, const int* exp_y, hipStream_t st) {
+    hipLaunchKernelGGL(reduce_slabs_kernel<bf16_t>, dim3(512), dim3(256), 0, st, slabs, S, 512, Q, 512, s, t, dbsum, grad, mode, raw, exp_x, exp_y);
 }
 
 // BatchNorm backward, step 1 for layer l (C channels, each seen nfold times in the partial rows): sums -> coefficients of
@@ -1531,9 +1564,7 @@ static int encoder_backward_fp8(const cp_config* c, const cp_params* p, const fl
             int nr = stat_rows;
             const float* pp = ctx.pre(nr, 2 * 512);
             if (int e = bwd_finalize(ctx, g, pp, nr, (double)N, L, 512, 1, "bn_bwd_finalize_kernel")) return e;
-            const int gb = grid_rows(N, 256 / (512 / 16), CAP_BRB8);
-            hipLaunchKernelGGL(bn_relu_bwd8_kernel, dim3(gb), dim3(256), 8 * 512 * 4, st, cur, ctx.act8(L), coef, partials, N, 512, fs,
-                               F8_T_GB + L, F8_T_ACT + L, F8_T_GRAD + L);
+            const int gb = launch_bn_relu_bwd8(cur, ctx.act8(L), coef, partials, N, fs, F8_T_GB + L, F8_T_ACT + L, F8_T_GRAD + L, st);
             if (int e = bias_grad_from_rows(ctx, gb, 512, g->fc_b[i], "bn_relu_bwd8_kernel")) return e;
         }
         if (int e = tap8(L, cur, F8_T_GRAD + L)) return e;
@@ -1553,7 +1584,7 @@ static int encoder_backward_fp8(const cp_config* c, const cp_params* p, const fl
             ta.X = cur; ta.ldx = 512; ta.Y = Y; ta.ldy = K; ta.slabs = pl.slabs; ta.M = N; ta.P = 512; ta.Q = K;
             // (32 splits for the single-layer launches too -- half the slab bytes, half the blocks -- measured: weight gradients 5 x 67 -> 82 us,
             //  slab reductions 9 x 11.0 -> 9.1: 70 us lost for 17 gained)
-            split_rows(N, pending ? 32 : (K == 512 ? 64 : 40), &S, &ta.rows_per_split, 64, false);
+            split_rows_tn8(N, pending, K, &S, &ta.rows_per_split);
             if (pending) { ta.X2 = pend.X; ta.Y2 = pend.Y; ta.slabs2 = pl.slabs + (size_t)32 * 512 * 512; }
             ta.splits = S;
             ProfScope ps(CP_K_FC_WGRAD, pl.sw);
@@ -1562,14 +1593,13 @@ static int encoder_backward_fp8(const cp_config* c, const cp_params* p, const fl
         if (!pl.defer) {
             ProfScope ps(CP_K_REDUCE_SLABS, pl.sw);
             if (pending) {
-                hipLaunchKernelGGL(reduce_slabs_kernel<bf16_t>, dim3(512), dim3(256), 0, pl.sw, pl.slabs + (size_t)32 * 512 * 512, S, 512, 512, 512,
-                                   (const float*)nullptr, (const float*)nullptr, g->fc_b[pend.i], g->fc_w[pend.i], 0, (float*)nullptr,
-                                   (const int*)&fs->e[pend.tx], (const int*)&fs->e[pend.ty]);
+                launch_reduce_slabs8(pl.slabs + (size_t)32 * 512 * 512, S, 512, nullptr, nullptr, g->fc_b[pend.i], g->fc_w[pend.i], 0, nullptr,
+                                     (const int*)&fs->e[pend.tx], (const int*)&fs->e[pend.ty], pl.sw);
                 CKL("reduce_slabs(fc, deferred)");
                 pending = false;
             }
-            hipLaunchKernelGGL(reduce_slabs_kernel<bf16_t>, dim3(512), dim3(256), 0, pl.sw, pl.slabs, S, 512, K, 512, s, t, g->fc_b[i], g->fc_w[i],
-                               i == 0 ? 1 : 0, in_drop ? (float*)nullptr : praw, (const int*)&fs->e[tx], (const int*)&fs->e[ty]);
+            launch_reduce_slabs8(pl.slabs, S, K, s, t, g->fc_b[i], g->fc_w[i], i == 0 ? 1 : 0, in_drop ? (float*)nullptr : praw,
+                                 (const int*)&fs->e[tx], (const int*)&fs->e[ty], pl.sw);
             CKL("reduce_slabs(fc)");
             if (!in_drop) {
                 hipLaunchKernelGGL(bn_bwd_sums_from_wgrad_kernel, dim3(K / 64, kSumSlices), dim3(256), 0, st, praw, p->fc_w[i], g->fc_b[i],

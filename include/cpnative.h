@@ -586,7 +586,7 @@ int cp_debug_conv(const cp_debug_conv_args* args, void* stream);
  * S = the splits of split_rows(M, 128 splits, 32-row steps).  w32: scratch of 32 * 512 T (kind 0) or 512 * 64 T (kind 4).  r_exp
  * (device int32, kinds 0, 1 and 3 under CP_BF16): act holds e4m3 bytes, stored = value * 2^*r_exp.  Every scratch and output region
  * is the caller's, so guards behind them can be inspected.  rows_out: host, may be NULL.
- * proj_dgrad8_kernel (csrc/fp8.cuh), the CP_FP8 step's data gradient, needs the 8-bit state block and is NOT reachable from here.
+ * proj_dgrad8_kernel (csrc/fp8.cuh), the CP_FP8 step's data gradient, needs the 8-bit state block: cp_debug_fp8, kind 6.
  * Checked before anything launches, CP_ERR_ARG: a NULL pointer the kind reads or writes (Wp, act; dz for kinds 1..4; scale and
  * shift for kinds 0..3; coef for kind 4; w32 for kinds 0 and 4; blast for kind 0; out; slabs for kinds 1..3; partials for kinds 1, 3
  * and 4; praw and dzsum for kind 1), M <= 0, an unknown dtype or kind, kinds 3 and 4 or r_exp outside CP_BF16, r_exp in kinds 2 and
@@ -618,6 +618,75 @@ typedef struct cp_debug_proj_args {
     int32_t* rows_out;
 } cp_debug_proj_args;
 int cp_debug_proj(const cp_debug_proj_args* args, void* stream);
+
+/* debug/test access (tests/test_gpu_fp8_exact.py): every launch of the 8-bit fc path (CP_FP8, csrc/fp8.cuh) on caller buffers, one
+ * launch sequence at a time, at any row count M >= 1.  The kernels are reached through the launch functions and the grid and split
+ * expressions of the step (csrc/fp8.cuh: launch_gemm_ws8, launch_gemm_wsd8, launch_gemm_tn8, launch_proj_dgrad8; csrc/encoder_api.cuh:
+ * launch_bn_dropout_apply8, launch_bn_relu_bwd8, split_rows_tn8, launch_reduce_slabs8).  state is the caller's scale table: 1,024
+ * device bytes laid out as Fp8State (int32 e[64], uint32 amax[64], uint32 init, padding): stored = value * 2^e[t], amax[t] the float
+ * bits of the largest stored-unit magnitude before clamping.  A launch reads e[] of the ids it is given and raises amax[t_out].
+ *   kind 0   launch_gemm_ws8<K> (K = 512 | 768, F = 512): C[M][F] e4m3 = clamp(relu(A[M][K] W[F][K]^T 2^(wsc[f] - 127) + bias[f]), 448);
+ *            partials[rows][2][F] = column sums of the clamped values and of their squares, one row per worker (partials NULL: the
+ *            evaluation form, no sums); amax[t_out] = the largest accumulator
+ *   kind 1   launch_gemm_wsd8<0> (F = 512 | 768): C[M][F] e5m2 = R > 0 ? ca' acc + cb' R + cz' : 0 with acc = A[M][512] (e5m2) W[F][512]^T
+ *            2^(wsc[f] - 127), ca' = ca 2^eo, cb' = cb 2^(eo - er), cz' = cz 2^eo, ca / cb / cz[f] = coef[{0,1,2} * coef_mod + f % coef_mod],
+ *            eo = e[t_out], er = e[t_r], R[M][F] e4m3; partials[rows][F] = column sums of C as stored, in true units
+ *   kind 2   launch_gemm_wsd8<1> (F = 512): C = R != 0 ? acc dp_inv_keep 2^eo : 0 (R = a dropout output u); partials[rows][2][F] =
+ *            sum g (true units) and sum g r derived from sum g u through bn_stats[4][F] (mean, invstd, scale, shift)
+ *   kind 3   launch_gemm_tn8, reduce_slabs_kernel<bf16>: slabs[S][512][F] bf16 = the products A[m][512]^T (e5m2) R[m][F] (e4m3) of the
+ *            rows of split s, C = dW[512][F] f32 = their sum times 2^-(e[t_in] + e[t_r]).  A2 / R2 / partials2 / C2 / t_in2 / t_r2: a
+ *            second problem in the same launch (F = 512, 32 splits each; its slabs lie in partials2).  partials = the slabs
+ *   kind 4   launch_bn_dropout_apply8: C[M][512] e4m3 = keep ? (s A 2^-e[t_in] + t) dp_inv_keep 2^e[t_out] : 0 with s / t = bn_stats[2 / 3][.]
+ *   kind 5   launch_bn_relu_bwd8, in place: C[M][512] e5m2 (t_in) -> R > 0 ? ca' g + cb' R + cz' : 0 (t_out), ca' = ca 2^(eo - e[t_in]);
+ *            partials[rows][512] = column sums as stored, true units, one row per block
+ *   kind 6   launch_proj_dgrad8: C[M][512] e5m2 = R > 0 ? ca' g + cb' R + cz' : 0, g = keep (A[M][64] bf16 W[512][64]^T bf16) dp_inv_keep
+ *            (dp_thresh == 0: no mask); partials[rows][512]
+ *   kind 7   weight preparation of one layer from A = W[512][K] f32 (mode 0 | 1: fold_linear8_kernel, mode 1 = fc1's order k' = w*64 + c,
+ *            scale / shift NULL or the previous BatchNorm's affine; C = weight bytes [512][K], wsc[512], partials = bias[512] in output
+ *            units, t_out < 0: f32 output;  mode 2 | 3: transpose_w8_batch_kernel with one job, mode 3 = fc1's order; C = [K][512], wsc[K],
+ *            t_in = the gradient's id)
+ *   kind 8   fp8_update_scales_kernel on state with n_windows = M
+ * keep(m, f): the 16-bit draw of the dropout hash of (dp_key, m, 512, f) is >= dp_thresh.  *rows_out (host, may be NULL): partial rows
+ * written (kinds 0..2, 5, 6), splits (kind 3), else 0.
+ * Checked before anything launches, CP_ERR_ARG: a NULL pointer the kind reads or writes, M <= 0, a shape the launch functions refuse
+ * (kind 0: K 512 | 768 and F 512; kinds 1, 3: F 512 | 768; kinds 2, 4..6: F 512; kind 3 paired: F 512; kind 7: K 512 | 768), an
+ * unknown kind or mode, a pointer not 16-byte aligned, an id outside 0..63 (kind 7: t_out may be -1), coef_mod <= 0 in kind 1,
+ * dp_thresh > 65535, dp_inv_keep <= 0 where it is read, M max(K, F) >= 2^32 - 2^20. */
+typedef struct cp_debug_fp8_args {
+    int32_t kind;              /* 0..8 */
+    int32_t mode;              /* kind 3: 1 = paired; kind 7: 0..3 */
+    int64_t M;
+    int32_t K;
+    int32_t F;
+    int32_t coef_mod;
+    int32_t t_in;
+    int32_t t_r;
+    int32_t t_out;
+    int32_t t_in2;
+    int32_t t_r2;
+    void* state;               /* 1,024 bytes, Fp8State */
+    const void* A;
+    const void* W;
+    const void* wsc;
+    const float* bias;
+    const void* R;
+    const float* coef;
+    const float* bn_stats;
+    const float* scale;        /* kind 7 */
+    const float* shift;
+    void* C;
+    float* partials;
+    const void* A2;            /* kind 3, paired */
+    const void* R2;
+    float* partials2;
+    float* C2;
+    uint32_t dp_thresh;        /* 0: no dropout */
+    uint32_t dp_key;
+    float dp_inv_keep;
+    int32_t reserved0;
+    int32_t* rows_out;
+} cp_debug_fp8_args;
+int cp_debug_fp8(const cp_debug_fp8_args* args, void* stream);
 
 /* BN statistics of `layer` as computed by the last forward: out[4][C] = mean, invstd, scale, shift */
 int cp_debug_bn_stats(const cp_config* cfg, void* ws, size_t ws_bytes, int32_t layer, float* out,

@@ -375,6 +375,84 @@ def test_debug_proj_refuses_what_a_launcher_would_before_it_launches(lib):
     assert lib.cp_debug_proj(None, None) == 10001
 
 
+def test_debug_fp8_refuses_what_a_launcher_would_before_it_launches(lib):
+    """cp_debug_fp8 checks its arguments on the host, before any launch: CP_ERR_ARG with a message that names the entry (every
+    pointer is a dummy address that is never dereferenced; each case differs from a valid call of its kind in the one field under
+    test.  That the valid calls are accepted is shown on the GPU: tests/test_gpu_fp8_exact.py).  The ctypes struct follows the header
+    field by field."""
+    from contrastiveprosthetics_amd import _lib
+    hdr = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    body = hdr[hdr.index("typedef struct cp_debug_fp8_args {"):hdr.index("} cp_debug_fp8_args;")]
+    assert re.findall(r"\b(\w+)\s*;", body) == [f[0] for f in _lib.cp_debug_fp8_args._fields_]
+    assert ctypes.sizeof(_lib.cp_debug_fp8_args) == 2 * 4 + 8 + 8 * 4 + 16 * 8 + 4 * 4 + 8
+    ok = 0x100000
+    rows = ctypes.c_int32(-7)
+    pointers = ("state", "A", "W", "wsc", "bias", "R", "coef", "bn_stats", "scale", "shift", "C", "partials", "A2", "R2", "partials2", "C2")
+
+    def call(**kw):
+        d = _lib.cp_debug_fp8_args()
+        d.kind, d.M, d.K, d.F, d.coef_mod = kw.get("kind", 0), 1000, 512, 512, 512
+        d.t_in, d.t_r, d.t_out, d.t_in2, d.t_r2 = 1, 2, 3, 4, 5
+        for name in pointers:
+            setattr(d, name, ok)
+        d.rows_out = ctypes.pointer(rows)
+        d.dp_thresh, d.dp_key, d.dp_inv_keep = 32768, 7, 2.0
+        for k, v in kw.items():
+            setattr(d, k, v)
+        rc = lib.cp_debug_fp8(ctypes.byref(d), None)
+        return rc, lib.cp_last_error()
+
+    cases = [("kind 9", dict(kind=9)), ("kind -1", dict(kind=-1)), ("mode 1 in kind 0", dict(mode=1)), ("mode 2 in kind 3", dict(kind=3, mode=2)),
+             ("mode 4 in kind 7", dict(kind=7, mode=4)), ("mode -1 in kind 7", dict(kind=7, mode=-1))]
+    for kind in range(9):
+        cases += [("kind %d, M = 0" % kind, dict(kind=kind, M=0)), ("kind %d, M < 0" % kind, dict(kind=kind, M=-41)),
+                  ("kind %d without state" % kind, dict(kind=kind, state=None)), ("kind %d, state + 4" % kind, dict(kind=kind, state=ok + 4)),
+                  ("kind %d, dp_thresh 65536" % kind, dict(kind=kind, dp_thresh=65536))]
+    # every pointer a kind reads or writes (kind 0 without partials is the evaluation form; kind 7's bias, scale and shift are optional)
+    needs = {0: ("A", "W", "wsc", "bias", "C"), 1: ("A", "W", "wsc", "R", "coef", "C", "partials"),
+             2: ("A", "W", "wsc", "R", "bn_stats", "C", "partials"), 3: ("A", "R", "C", "partials"), 4: ("A", "bn_stats", "C"),
+             5: ("R", "coef", "C", "partials"), 6: ("A", "W", "R", "coef", "C", "partials"), 7: ("A", "wsc", "C", "partials")}
+    for kind, names in needs.items():
+        cases += [("kind %d without %s" % (kind, name), {"kind": kind, name: None}) for name in names]
+        cases += [("kind %d, %s + 8" % (kind, name), {"kind": kind, name: ok + 8}) for name in names]
+    cases += [("paired without %s" % name, {"kind": 3, "mode": 1, name: None}) for name in ("A2", "R2", "partials2", "C2")]
+    cases += [("kind 7, scale without shift", dict(kind=7, shift=None)), ("kind 7, shift without scale", dict(kind=7, mode=1, scale=None))]
+    # shapes
+    cases += [("kind 0, K = 256", dict(K=256)), ("kind 0, K = 1024", dict(K=1024)), ("kind 0, F = 768", dict(F=768)), ("kind 0, F = 256", dict(F=256)),
+              ("kind 1, F = 1024", dict(kind=1, F=1024)), ("kind 1, F = 256", dict(kind=1, F=256)), ("kind 1, F = 0", dict(kind=1, F=0)),
+              ("kind 1, coef_mod 0", dict(kind=1, coef_mod=0)), ("kind 1, coef_mod < 0", dict(kind=1, coef_mod=-64)),
+              ("kind 3, F = 640", dict(kind=3, F=640)), ("paired, F = 768", dict(kind=3, mode=1, F=768)),
+              ("kind 7, K = 640", dict(kind=7, K=640)), ("kind 7 transposed, K = 0", dict(kind=7, mode=2, K=0))]
+    cases += [("kind %d, F = 768" % kind, dict(kind=kind, F=768)) for kind in (2, 4, 5, 6)]
+    # ids
+    reads = {0: ("t_out",), 1: ("t_r", "t_out"), 2: ("t_r", "t_out"), 3: ("t_in", "t_r"), 4: ("t_in", "t_out"), 5: ("t_in", "t_r", "t_out"),
+             6: ("t_r", "t_out"), 7: ("t_in", "t_out")}
+    for kind, names in reads.items():
+        cases += [("kind %d, %s = 64" % (kind, name), {"kind": kind, name: 64}) for name in names]
+        cases += [("kind %d, %s = -1" % (kind, name), {"kind": kind, name: -1}) for name in names if (kind, name) != (7, "t_out")]
+    cases += [("kind 7, t_out = -2", dict(kind=7, t_out=-2)), ("kind 7 transposed, t_in = 64", dict(kind=7, mode=2, t_in=64)),
+              ("paired, t_in2 = 64", dict(kind=3, mode=1, t_in2=64)), ("paired, t_r2 = -1", dict(kind=3, mode=1, t_r2=-1))]
+    # dropout
+    cases += [("kind %d, dp_inv_keep 0" % kind, dict(kind=kind, dp_inv_keep=0.0)) for kind in (2, 4, 6)]
+    cases += [("kind 4, dp_inv_keep < 0", dict(kind=4, dp_inv_keep=-2.0))]
+    # 32-bit offsets: 0xFFF00000 / 512 = 8386560, / 768 = 5591040
+    cases += [("kind %d, 2^32 bytes" % kind, dict(kind=kind, M=8386560)) for kind in range(7)]
+    cases += [("kind 0, K = 768, 2^32 bytes", dict(K=768, M=5591040)), ("kind 1, F = 768, 2^32 bytes", dict(kind=1, F=768, M=5591040)),
+              ("M = 2^54: the byte count wraps to 0", dict(M=1 << 54)), ("M = 2^63 - 1", dict(kind=2, M=(1 << 63) - 1))]
+    for what, kw in cases:
+        rc, msg = call(**kw)
+        assert rc == 10001 and msg.startswith(b"cp_debug_fp8"), (what, rc, msg)
+        assert rows.value == -7, what
+    for what, says in (("kind 9", b"kind"), ("mode 1 in kind 0", b"mode"), ("kind 3, M = 0", b"M must"), ("kind 5 without state", b"state"),
+                       ("kind 1 without coef", b"coef"), ("kind 2 without bn_stats", b"bn_stats"), ("paired without R2", b"R2"),
+                       ("kind 0, K = 256", b"K = 512 | 768"), ("kind 4, F = 768", b"F = 512"), ("kind 1, coef_mod 0", b"coef_mod"),
+                       ("kind 5, t_in = 64", b"t_in"), ("kind 6, t_r = -1", b"t_r"), ("kind 0, t_out = 64", b"t_out"), ("paired, t_in2 = 64", b"t_in2"),
+                       ("kind 4, dp_thresh 65536", b"dp_thresh"), ("kind 2, dp_inv_keep 0", b"dp_inv_keep"), ("kind 6, 2^32 bytes", b"2^32"),
+                       ("kind 3, R + 8", b"aligned"), ("kind 7, scale without shift", b"scale and shift")):
+        assert says in call(**dict(cases)[what])[1], (what, call(**dict(cases)[what])[1])
+    assert lib.cp_debug_fp8(None, None) == 10001
+
+
 def test_backward_refuses_a_short_gradient_tap_before_it_launches(lib):
     """cp_config.grad_tap: cp_encoder_backward checks the whole buffer once, before its first launch -- 9 slots of n_windows x 768
     elements on the large-batch paths (CP_FP8: bf16 elements), 11 on the small-batch path (slot 9: fc1's data gradient before conv2's
