@@ -40,4 +40,7 @@ def __getattr__(name):
                 "stage_reference"):                            # (metric.fit_reference: by module)
         from . import metric
         return getattr(metric, name)
+    if name in ("SequenceGate", "SequenceReference", "potts", "transitions_from_cues", "sweep_sequence", "sequence_grid"):
+        from . import sequence
+        return getattr(sequence, name)
     raise AttributeError(name)

@@ -84,6 +84,10 @@ class cp_online_gate_config(C.Structure):
                 ("weight", C.c_int32), ("min_margin", C.c_float)]
 
 
+class cp_online_seq_config(C.Structure):
+    _fields_ = [("model", C.c_int32), ("lag", C.c_int32)]
+
+
 class cp_online_drive_config(C.Structure):
     _fields_ = [("smooth", C.c_int32), ("on_level", C.c_int32), ("off_level", C.c_int32), ("rise", C.c_int32), ("fall", C.c_int32),
                 ("bad_after", C.c_int32), ("good_after", C.c_int32)]
@@ -165,6 +169,7 @@ class cp_debug_fp8_args(C.Structure):
 CP_ONLINE_MAX_CLASSES, CP_ONLINE_MAX_VOTE, CP_ONLINE_MAX_WINDOWS, CP_ONLINE_STRIDE = 64, 256, 256, 20
 CP_ONLINE_MULTI_MAX_STREAMS, CP_ONLINE_MULTI_MAX_ROWS = 256, 65536
 CP_ONLINE_GATE_SCORES, CP_ONLINE_GATE_SWEEP_MAX_CONFIGS = 10, 65536
+CP_ONLINE_SEQ_RING, CP_ONLINE_SEQ_MAX_COST, CP_ONLINE_SEQ_FLOOR, CP_ONLINE_SEQ_SWEEP_MAX_CONFIGS = 64, 1 << 28, -(1 << 29), 65536
 CP_ONLINE_SUBSET_SCORES, CP_ONLINE_SUBSET_SWEEP_MAX_SUBSETS = 7, 1048576
 CP_ONLINE_DRIVE_ONE, CP_ONLINE_DRIVE_MAX_SMOOTH = 4096, 256
 CP_ONLINE_MAP_SCORES, CP_ONLINE_MAP_SWEEP_MAX_MAPS = 3, 65536
@@ -309,6 +314,14 @@ SYMBOLS = {
     "cp_online_gate_sweep_scratch_bytes": (C.c_size_t, [C.c_int64]),
     "cp_online_gate_sweep": (C.c_int, [_fp, C.c_int32, C.c_int64, C.c_int32, _fp, _fp, _fp, C.c_int32, _fp, C.c_size_t, _fp, _fp,
                                        _fp]),
+    "cp_online_seq_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "cp_online_seq_set_model": (C.c_int, [C.c_int32, _fp, C.c_size_t, C.c_int32, _P(C.c_int32), _P(C.c_float), C.c_int32, _fp,
+                                          C.c_int32, _fp]),
+    "cp_online_seq_reset": (C.c_int, [C.c_int32, _fp, C.c_size_t, C.c_int32, _fp]),
+    "cp_online_seq_push": (C.c_int, [C.c_int32, _fp, C.c_size_t, _fp, C.c_int32, _fp, _fp, C.c_int32, _fp, _fp, _fp, _fp]),
+    "cp_online_seq_sweep_scratch_bytes": (C.c_size_t, [C.c_int64]),
+    "cp_online_seq_sweep": (C.c_int, [_fp, C.c_int32, C.c_int64, C.c_int32, _fp, _fp, C.c_int32, _fp, _fp, C.c_int32, _fp, C.c_size_t,
+                                      _fp, _fp, _fp]),
     "cp_online_subset_sweep_scratch_bytes": (C.c_size_t, [C.c_int64]),
     "cp_online_subset_sweep": (C.c_int, [_fp, C.c_int32, C.c_int64, C.c_int32, _fp, _fp, C.c_int32, C.c_int32, _fp, C.c_size_t, _fp,
                                          _fp, _fp]),

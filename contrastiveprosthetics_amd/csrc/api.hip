@@ -27,6 +27,7 @@
 #include "online_enroll.cuh"
 #include "online_finetune.cuh"
 #include "online_gate.cuh"
+#include "online_sequence.cuh"
 #include "online_drive.cuh"
 #include "online_subsets.cuh"
 #include "online_maps.cuh"

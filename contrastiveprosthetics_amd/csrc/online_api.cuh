@@ -1,6 +1,6 @@
 // Host layer of the online decoders (include/cpnative.h, cp_online_*): workspace layout, argument checks, launch chains and
 // the extern "C" entries of the folded, adaptive, multi-stream and adaptive multi-stream decoders, class enrolment, head
-// fine-tuning, the command gate, the grasp drive, the gate sweep, the subset sweep, the electrode-map sweep, cue realignment, prototype
+// fine-tuning, the command gate, the sequence decoder and its sweep, the grasp drive, the gate sweep, the subset sweep, the electrode-map sweep, cue realignment, prototype
 // tracking, held-out enrolment scoring, posture prototypes and the user metric.  Host code only; api.hip includes it behind its own helpers (fail, CK, CKL) and encoder_api.cuh's (align256, fcK),
 // so the library stays one translation unit.  The four decoders share one workspace description (OlWS, ol_carve), one
 // parameter check, one set of front-end arguments, one folded chain and one unfolded weight copy; what an entry adds is its
@@ -1439,6 +1439,116 @@ extern "C" int cp_online_gate_sweep(const float* logits, int32_t ldl, int64_t n_
     hipLaunchKernelGGL(og_sweep_kernel, dim3((n_configs + OG_SWEEP_WAVES - 1) / OG_SWEEP_WAVES), dim3(64 * OG_SWEEP_WAVES), 0,
                        (hipStream_t)stream, a);
     CKL("og_sweep_kernel");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// grasp sequence decoder (csrc/online_sequence.cuh): one SqState per stream in a workspace of its own, behind any decoder's logits
+// ---------------------------------------------------------------------------------------
+static_assert(SQ_MAXK == CP_ONLINE_MAX_CLASSES && SQ_MAXM == CP_ONLINE_MAX_WINDOWS && SQ_RING == CP_ONLINE_SEQ_RING, "sequence limits");
+static_assert(SQ_COST_MAX == CP_ONLINE_SEQ_MAX_COST && SQ_FLOOR == CP_ONLINE_SEQ_FLOOR, "sequence constants");
+static_assert(sizeof(SqState) == 4 * (8 + 4 * SQ_MAXK + SQ_MAXK * SQ_MAXK + SQ_MAXK) + SQ_RING * SQ_BP_STRIDE,
+              "SqState is 4424 words and 4352 ring bytes (SequenceGate.state reads it back)");
+static_assert(sizeof(SqSweepConfig) == sizeof(cp_online_seq_config), "the sweep reads cp_online_seq_config from the device as SqSweepConfig");
+
+static int sq_check(const char* who, int32_t n_streams, void* ws, size_t ws_bytes) {
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (!ws) return bad("workspace is required");
+    if (n_streams < 1 || n_streams > CP_ONLINE_MULTI_MAX_STREAMS) return bad("n_streams outside 1..256");
+    if ((uintptr_t)ws % 256) return bad("workspace not 256-byte aligned");
+    if (ws_bytes < (size_t)n_streams * sizeof(SqState)) return bad("workspace too small");
+    return 0;
+}
+
+extern "C" size_t cp_online_seq_workspace_bytes(int32_t n_streams) {
+    if (n_streams < 1) n_streams = 1;
+    return align256((size_t)n_streams * sizeof(SqState));
+}
+
+extern "C" int cp_online_seq_set_model(int32_t n_streams, void* ws, size_t ws_bytes, int32_t index, const int32_t* ids,
+                                       const float* min_cosine, int32_t n_classes, const int32_t* cost, int32_t lag, void* stream) {
+    if (int e = sq_check("cp_online_seq_set_model", n_streams, ws, ws_bytes)) return e;
+    if (int e = ol_check_index("cp_online_seq_set_model", index, n_streams)) return e;
+    if (!ids || !min_cosine || n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES)
+        return fail(CP_ERR_ARG, "cp_online_seq_set_model: 1..64 classes, with ids and min_cosine");
+    if (!cost || (uintptr_t)cost % 4) return fail(CP_ERR_ARG, "cp_online_seq_set_model: cost is required, 4-byte aligned");
+    if (lag < 0 || lag >= CP_ONLINE_SEQ_RING) return fail(CP_ERR_ARG, "cp_online_seq_set_model: lag outside 0..63");
+    SqModelArgs c{};
+    c.K = n_classes;
+    c.lag = lag;
+    for (int k = 0; k < n_classes; ++k) {
+        if (ids[k] < 0 || ids[k] == INT32_MAX || (k > 0 && ids[k] <= ids[k - 1]))
+            return fail(CP_ERR_ARG, "cp_online_seq_set_model: ids must be ascending, distinct and in 0..2^31-2");
+        if (std::isnan(min_cosine[k])) return fail(CP_ERR_ARG, "cp_online_seq_set_model: min_cosine must not be NaN");
+        c.ids[k] = ids[k];
+        c.thr[k] = (int)std::nearbyint(std::fmin(std::fmax(min_cosine[k], -2.0f), 2.0f) * SQ_SCALE);     // q(): half-even, exact product
+    }
+    hipLaunchKernelGGL(seq_set_model_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (SqState*)ws + index, c, cost);
+    CKL("seq_set_model_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_seq_reset(int32_t n_streams, void* ws, size_t ws_bytes, int32_t index, void* stream) {
+    if (int e = sq_check("cp_online_seq_reset", n_streams, ws, ws_bytes)) return e;
+    if (index < -1 || index >= n_streams) return fail(CP_ERR_ARG, "cp_online_seq_reset: stream index outside -1..n_streams-1");
+    hipLaunchKernelGGL(seq_reset_kernel, dim3(index < 0 ? n_streams : 1), dim3(64), 0, (hipStream_t)stream, (SqState*)ws,
+                       index < 0 ? 0 : index);
+    CKL("seq_reset_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_seq_push(int32_t n_streams, void* ws, size_t ws_bytes, const float* logits, int32_t ldl, const int32_t* row0,
+                                  const int32_t* m, int32_t total_rows, int32_t* command, int32_t* now, int32_t* lead, void* stream) {
+    if (int e = sq_check("cp_online_seq_push", n_streams, ws, ws_bytes)) return e;
+    if (total_rows < 0 || total_rows > CP_ONLINE_MULTI_MAX_ROWS) return fail(CP_ERR_ARG, "cp_online_seq_push: total_rows outside 0..65536");
+    if (total_rows == 0) return 0;
+    if (ldl < 1) return fail(CP_ERR_ARG, "cp_online_seq_push: ldl must be at least 1");
+    if (!logits || !row0 || !m || !command) return fail(CP_ERR_ARG, "cp_online_seq_push: logits, row0, m and command are required");
+    if ((uintptr_t)logits % 4 || (uintptr_t)row0 % 4 || (uintptr_t)m % 4 || (uintptr_t)command % 4 || (uintptr_t)now % 4 ||
+        (uintptr_t)lead % 4)
+        return fail(CP_ERR_ARG, "cp_online_seq_push: misaligned argument");
+    SqPushArgs a{};
+    a.states = (SqState*)ws; a.logits = logits; a.row0 = row0; a.m = m; a.ldl = ldl; a.total_rows = total_rows;
+    a.command = command; a.now = now; a.lead = lead;
+    hipLaunchKernelGGL(seq_push_kernel, dim3(n_streams), dim3(64), 0, (hipStream_t)stream, a);
+    CKL("seq_push_kernel");
+    return 0;
+}
+
+// sequence sweep: n_configs (model, lag, thresholds) over one recording, one wave each, scored on the device
+extern "C" size_t cp_online_seq_sweep_scratch_bytes(int64_t n_rows) {
+    if (n_rows < 1) n_rows = 1;
+    return align256((size_t)n_rows * SQ_MAXK * sizeof(int32_t));
+}
+
+extern "C" int cp_online_seq_sweep(const float* logits, int32_t ldl, int64_t n_rows, int32_t n_classes, const int32_t* expected_slot,
+                                   const int32_t* costs, int32_t n_models, const cp_online_seq_config* configs, const float* min_cosine,
+                                   int32_t n_configs, void* scratch, size_t scratch_bytes, int64_t* scores, int32_t* commands,
+                                   void* stream) {
+    if (n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return fail(CP_ERR_ARG, "cp_online_seq_sweep: n_classes outside 1..64");
+    if (ldl < n_classes) return fail(CP_ERR_ARG, "cp_online_seq_sweep: ldl must be at least n_classes");
+    if (n_configs < 1 || n_configs > CP_ONLINE_SEQ_SWEEP_MAX_CONFIGS)
+        return fail(CP_ERR_ARG, "cp_online_seq_sweep: n_configs outside 1..65536");
+    if (n_models < 1 || n_models > CP_ONLINE_SEQ_SWEEP_MAX_CONFIGS)
+        return fail(CP_ERR_ARG, "cp_online_seq_sweep: n_models outside 1..65536");
+    if (n_rows < 1 || n_rows > INT32_MAX) return fail(CP_ERR_ARG, "cp_online_seq_sweep: n_rows outside 1..2^31-1");
+    if (!logits || !expected_slot || !costs || !configs || !min_cosine || !scratch || !scores)
+        return fail(CP_ERR_ARG, "cp_online_seq_sweep: logits, expected_slot, costs, configs, min_cosine, scratch and scores are required");
+    if ((uintptr_t)logits % 4 || (uintptr_t)expected_slot % 4 || (uintptr_t)costs % 4 || (uintptr_t)configs % 4 ||
+        (uintptr_t)min_cosine % 4 || (uintptr_t)scratch % 4 || (uintptr_t)scores % 8 || (uintptr_t)commands % 4)
+        return fail(CP_ERR_ARG, "cp_online_seq_sweep: misaligned argument");
+    if (scratch_bytes < (size_t)n_rows * SQ_MAXK * sizeof(int32_t)) return fail(CP_ERR_ARG, "cp_online_seq_sweep: scratch too small");
+    const int rows_per_block = 4 * SQ_ROWS_PER_WAVE;
+    hipLaunchKernelGGL(seq_rows_kernel, dim3((unsigned)((n_rows + rows_per_block - 1) / rows_per_block)), dim3(256), 0, (hipStream_t)stream,
+                       logits, (int)ldl, (long long)n_rows, (int)n_classes, (int32_t*)scratch);
+    CKL("seq_rows_kernel");
+    SqSweepArgs a{};
+    a.q = (const int32_t*)scratch; a.expected = expected_slot; a.costs = costs; a.configs = (const SqSweepConfig*)configs;
+    a.min_cosine = min_cosine; a.n_rows = n_rows; a.n_models = n_models; a.n_configs = n_configs; a.K = n_classes;
+    a.scores = (long long*)scores; a.commands = commands;
+    hipLaunchKernelGGL(seq_sweep_kernel, dim3((n_configs + SQ_SWEEP_WAVES - 1) / SQ_SWEEP_WAVES), dim3(64 * SQ_SWEEP_WAVES), 0,
+                       (hipStream_t)stream, a);
+    CKL("seq_sweep_kernel");
     return 0;
 }
 

@@ -1126,6 +1126,81 @@ int cp_online_gate_sweep(const float* logits, int32_t ldl, int64_t n_rows, int32
                          int32_t* commands,                     /* optional (n_configs, n_rows): slot or -1 */
                          void* stream);
 
+/* ---- grasp sequence decoder: fixed-lag Viterbi behind the logits ------------------------------------------------------------
+ * The gate counts hard votes; this stage sums evidence.  Behind any decoder's logits it keeps, per stream, the score of the best
+ * path into each of K <= 64 class states (slots 0..K-1) and one "none" state (slot K, reported as -1), with a transition cost
+ * between states, and it may decide a few windows late.  One launch per push for any n_streams <= 256 (seq_push_kernel: one wave
+ * per stream, lane j = class slot j); the decoders' kernels and outputs do not change.  All values are int32 in units of 2^-20.
+ * q(x) = (int32) rint(fminf(fmaxf(x, -2), 2) * 2^20), round-half-even, the product exact: the gate's margin quantisation.
+ *   model      ids[K] ascending; thr[k] = q(min_cosine[k]) (min_cosine not NaN); a cost matrix C[i][j], (K+1) x (K+1), entry i -> j
+ *              the price of being in j one window after i, clamped into 0..CP_ONLINE_SEQ_MAX_COST (2^28: as good as forbidden)
+ *              where it is installed; lag L in 0..63.
+ *   state      score[K+1], all 0 at the start; a ring of the last CP_ONLINE_SEQ_RING back-pointer rows (bytes); n, the windows
+ *              seen since the last reset (it saturates at 2^30).  A zeroed workspace is a valid start (no classes).
+ * Per window, in window order:
+ *   emission   a row with a non-finite logit among its K: e[.] = 0 (no evidence).  Otherwise e[k] = q(l[k]) - thr[k]; e[K] = 0.
+ *   step       best[j] = max_i (score[i] - C[i][j]); bp[j] = the smallest i that attains it (class slots before none);
+ *              new[j] = best[j] + e[j].
+ *   renormalise  every entry minus max_j new[j], then every entry below CP_ONLINE_SEQ_FLOOR (-2^29) raised to it: scores lie in
+ *              [-2^29, 0], and the step's smallest intermediate is -2^29 - 2^28 - 2^22.
+ *   now        the first maximum of score (class slots before none); lead = score[now] - the largest score among the other
+ *              states (K + 1 >= 2: there is one).
+ *   command    none while n <= L.  Otherwise start at now and follow L back-pointer rows, the newest first: the state of the
+ *              best path L windows ago.  L = 0: command = now.
+ *   outputs    command and now (class id, or -1 for none), lead.
+ * So a stream's outputs and workspace depend neither on how its rows are cut into calls nor on the streams that share a launch;
+ * with C = 0, min_cosine = -2 and L = 0, now is the first maximum of q(l[k]); with C = 0 and any L, command[t] = now[t-L]; and
+ * the path read from the back-pointers is a maximum-score path.  SequenceReference of contrastiveprosthetics_amd/sequence.py
+ * restates this in numpy.
+ * The entries keep no state in the library and validate on the host: a bad argument -- a short workspace included -- returns
+ * CP_ERR_ARG with a cp_last_error that names the entry, before anything is enqueued. */
+#define CP_ONLINE_SEQ_RING 64                 /* back-pointer rows kept: lag <= 63 */
+#define CP_ONLINE_SEQ_MAX_COST 268435456      /* 2^28 */
+#define CP_ONLINE_SEQ_FLOOR (-536870912)      /* -2^29 */
+#define CP_ONLINE_SEQ_SWEEP_MAX_CONFIGS 65536
+/* bytes of the stage's workspace (256-byte aligned) for n_streams streams; zero it before the first call */
+size_t cp_online_seq_workspace_bytes(int32_t n_streams);
+/* ids (n_classes) int32 ascending, distinct, >= 0 and min_cosine (n_classes) f32 on the HOST (they travel as kernel arguments);
+ * cost (n_classes + 1, n_classes + 1) int32 on the DEVICE, row and column n_classes the none state.  Installs them with `lag`
+ * for stream `index` and restarts that stream (scores 0, empty ring, n = 0). */
+int cp_online_seq_set_model(int32_t n_streams, void* ws, size_t ws_bytes, int32_t index, const int32_t* ids, const float* min_cosine,
+                            int32_t n_classes, const int32_t* cost, int32_t lag, void* stream);
+/* restarts stream `index` (every stream for index -1); the model stays */
+int cp_online_seq_reset(int32_t n_streams, void* ws, size_t ws_bytes, int32_t index, void* stream);
+/* logits, ldl, row0, m and total_rows as cp_online_gate_push takes them, with the same limits.  command (total_rows) int32 and
+ * now, lead (total_rows) int32, which may be NULL, receive the rows' outputs.  A stream with m[s] = 0, without a model, with more
+ * classes than ldl, or whose rows do not lie inside 0..total_rows-1 is left untouched (its outputs are not written).  Nothing is
+ * enqueued for total_rows = 0. */
+int cp_online_seq_push(int32_t n_streams, void* ws, size_t ws_bytes, const float* logits, int32_t ldl, const int32_t* row0,
+                       const int32_t* m, int32_t total_rows, int32_t* command, int32_t* now, int32_t* lead, void* stream);
+/* The sweep: n_configs runs of the stage over one cued recording in one pair of launches (seq_rows_kernel: q(l) of every row and
+ * its finite flag, once per row; seq_sweep_kernel: one wave per config, from the zero state), scored as cp_online_gate_sweep
+ * scores them: expected_slot, the ten counters, their order and `commands` (slots, -1: none) are those of that entry.
+ * - Config g runs model configs[g].model of `costs` (n_models, K+1, K+1) with lag configs[g].lag and the thresholds
+ *   min_cosine[g]; its command sequence is the one cp_online_seq_push produces for the same rows, in any cut into calls.
+ * - A config's results do not depend on the other configs in the call.
+ * - The host checks n_classes in 1..64 and <= ldl, n_configs and n_models in 1..65536, n_rows in 1..2^31-1, the size of scratch
+ *   and the pointers (commands may be NULL) before anything is enqueued.  The values inside `configs`, `costs` and `min_cosine`
+ *   lie on the device: costs are clamped into 0..2^28 as they are read, thresholds must not be NaN (the caller checks), and a
+ *   config with lag outside 0..63 or model outside 0..n_models-1 gets all scores -1 and its row of `commands` is not written;
+ *   the kernel never indexes with such a value. */
+typedef struct cp_online_seq_config {
+    int32_t model;           /* 0..n_models-1 */
+    int32_t lag;             /* 0..63 */
+} cp_online_seq_config;
+/* bytes of the sweep's scratch (256-byte aligned): 256 per row */
+size_t cp_online_seq_sweep_scratch_bytes(int64_t n_rows);
+int cp_online_seq_sweep(const float* logits, int32_t ldl, int64_t n_rows, int32_t n_classes,
+                        const int32_t* expected_slot,           /* (n_rows) device: slot 0..K-1, -1 rest, -2 ignore */
+                        const int32_t* costs,                   /* (n_models, K+1, K+1) device */
+                        int32_t n_models,
+                        const cp_online_seq_config* configs,    /* (n_configs) device */
+                        const float* min_cosine,                /* (n_configs, 64) device */
+                        int32_t n_configs, void* scratch, size_t scratch_bytes,
+                        int64_t* scores,                        /* (n_configs, CP_ONLINE_GATE_SCORES) device */
+                        int32_t* commands,                      /* optional (n_configs, n_rows): slot or -1 */
+                        void* stream);
+
 /* ---- grasp-set search: many class subsets of one cued recording, scored on the device --------------------------------------
  * Which grasps to keep is a search over subsets of the K class slots, and a subset's score is an independent exact integer
  * walk over the same logits.  The sweep runs n_subsets of them in one pair of launches (os_rows_kernel: a row's slots in

@@ -27,6 +27,11 @@ With --subset-sweep the grasp-set search's sweep (sweep_subsets, csrc/online_sub
 41 classes, 6,000 and 20,500 windows, G = 64, 1,024, 10,660 (all triples) and 112,750 (all pairs, triples and quadruples)
 subsets at vote 25; for G = 64 the same scores are also computed the way without it (per subset a row and column select plus
 a one-config sweep_gate), must be equal, and the ratio of the two times is stated.
+With --sequence the sequence decoder (SequenceGate.push, csrc/online_sequence.cuh) at lag 0 and lag 63 is timed next to the
+ungated and the CommandGate push of the same run: 1 and 25 windows on OnlineDecoder, 256 streams x 1 window, f32 and bf16.
+With --sequence-sweep sweep_sequence runs 4,096 configs over 14,514 windows at lag 0 and at lag 63 next to the numpy definition
+for 16 of them (scaled up; their scores must be equal), and the best config of sweep_gate and of sweep_sequence under pick_gate's
+default limits are set side by side on one synthetic recording of 41 classes.
 With --drive the grasp drive (GraspDrive.push, csrc/online_drive.cuh) is timed behind gate-wrapped decoders next to the gate
 itself in the same run: ungated, gated and driven pushes of 1 and 25 windows on OnlineDecoder and of 256 streams x 1 window on
 MultiStreamDecoder, plus the drive's launch alone (GraspDrive.apply on the windows and commands of one push).  A driven push
@@ -68,6 +73,7 @@ counted with torch.profiler over a few pushes.  One JSON line per case, and a ta
     python tools/online_bench.py --gate --iters 200 --out profiles/online_gate_latency.txt
     python tools/online_bench.py --drive --iters 200 --out profiles/online_drive_latency.txt
     python tools/online_bench.py --gate-sweep --iters 20 --out profiles/online_gate_sweep.txt
+    python tools/online_bench.py --sequence --sequence-sweep --iters 200 --out profiles/online_sequence.txt
     python tools/online_bench.py --subset-sweep --iters 20 --out profiles/online_subset_sweep.txt
     python tools/online_bench.py --map-sweep --iters 5 --out profiles/online_map_sweep.txt
     python tools/online_bench.py --finetune --iters 10 --out profiles/online_finetune.txt
@@ -132,6 +138,9 @@ def main():
     ap.add_argument("--gate", action="store_true", help="the command gate against the ungated push with logits")
     ap.add_argument("--drive", action="store_true", help="the grasp drive behind gate-wrapped decoders, next to the gate's own cost")
     ap.add_argument("--gate-sweep", action="store_true", help="sweep_gate against G CommandGate.apply calls in turn")
+    ap.add_argument("--sequence", action="store_true", help="the sequence decoder's push next to the ungated and the gated push")
+    ap.add_argument("--sequence-sweep", action="store_true", help="sweep_sequence against the numpy definition, and its best config "
+                    "next to sweep_gate's on one recording")
     ap.add_argument("--subset-sweep", action="store_true", help="sweep_subsets, and for 64 subsets a select + sweep_gate per subset")
     ap.add_argument("--map-sweep", action="store_true", help="score_channel_maps against a reset / set_channel_map / push loop, and "
                     "a mapped against an unmapped push")
@@ -178,6 +187,8 @@ def main():
     table = (e.values.views["glove_net.easy.0.weight"].t() + e.values.views["glove_net.easy.0.bias"]).contiguous()
     tn = table / table.norm(dim=-1, keepdim=True)
     rows = []
+    if a.sequence or a.sequence_sweep:
+        return sequence_main(a, e, stream, mean, std, classes)
     if a.gate:
         return gate_main(a, e, stream, mean, std, classes)
     if a.drive:
@@ -1632,6 +1643,161 @@ def streams_adapt_main(a, e, stream, mean, std, classes):
             f.write("# cp_online_multi_adapt_calibrate of one stream (of 64) on 6,000 windows, host-synchronised, median of 20\n")
             for r in cal:
                 f.write(f"{r['kind']:<13} {r['dtype']:<5} {r['windows']:>7} {r['median_ms']:>8.2f} ms\n")
+
+
+def _cued_recording_41(m=600, K=41, seed=0):
+    """a synthetic person's cued logits on the host: rest stretches, then cue segments of 30..80 windows in which the cued class
+    is raised by a margin that ramps up over the first 12 windows, over noise as wide as the raise -> ids, logits (m, K), expected"""
+    from contrastiveprosthetics_amd.online import IGNORE, REST
+    rng = np.random.default_rng(1000 * K + seed)
+    ids = np.sort(rng.choice(200, K, replace=False)).astype(np.int64)
+    lg = rng.uniform(-0.25, 0.35, (m, K))
+    exp = np.full(m, IGNORE, dtype=np.int64)
+    j = int(rng.integers(3, 10))
+    exp[:j] = REST
+    while j < m:
+        c, n = int(rng.integers(K)), int(rng.integers(30, 81))
+        t = np.arange(min(n, m - j))
+        lg[j:j + n, c] += 0.45 * np.minimum(1.0, (t + 1) / 12.0)
+        exp[j:j + n] = ids[c]
+        j += n + 2
+        r = int(rng.integers(0, 40))
+        exp[j:j + r] = REST
+        j += r + (2 if r else 0)
+    return ids, lg.astype(np.float32), exp
+
+
+def sequence_main(a, e, stream, mean, std, classes):
+    """--sequence: ungated, gated and sequence-decoded pushes (lag 0 and lag 63), interleaved case by case in one run, each on a
+    decoder of its own.  --sequence-sweep: sweep_sequence next to the numpy definition, and the comparison with the gate."""
+    from contrastiveprosthetics_amd.online import SCORE_KEYS, gate_grid, pick_gate, score_commands, sweep_gate
+    from contrastiveprosthetics_amd.sequence import SequenceGate, SequenceReference, _matrix_for, sequence_grid, sweep_sequence
+    rows, sweeps, versus = [], [], []
+    settings = dict(min_cosine=0.2, min_margin=0.02, min_votes=3, dwell=5, release=10, weight="margin")
+    seq = dict(transitions=dict(switch=0.5, engage=0.5, release=0.5), min_cosine=0.2)
+    for dtype in ("f32", "bf16") if a.sequence else ():
+        for S, n in ((1, 20), (1, 500), (256, 20)):
+            m = n // 20
+
+            def decoder():
+                if S == 1:
+                    return OnlineDecoder(e, mean, std, classes=classes, dtype=dtype)
+                d = MultiStreamDecoder(e, mean, std, S, dtype=dtype, max_rows=S * m)
+                for s in range(S):
+                    d.set_classes(s, classes=classes)
+                return d
+
+            plain, gate = decoder(), CommandGate(decoder(), **settings)
+            seq0, seq63 = SequenceGate(decoder(), lag=0, **seq), SequenceGate(decoder(), lag=63, **seq)
+            pos = [0]
+            span = stream.shape[0] - S * n
+
+            def chunk():
+                base = pos[0] % span
+                pos[0] += S * n
+                return stream[base:base + S * n]
+
+            if S == 1:
+                fns = (("ungated", lambda: plain.push(chunk(), return_logits=True)), ("gated", lambda: gate.push(chunk())),
+                       ("sequence lag 0", lambda: seq0.push(chunk())), ("sequence lag 63", lambda: seq63.push(chunk())))
+            else:
+                fns = (("ungated", lambda: plain.push_packed(chunk(), [n] * S, return_logits=True)),
+                       ("gated", lambda: gate.push_packed(chunk(), [n] * S)),
+                       ("sequence lag 0", lambda: seq0.push_packed(chunk(), [n] * S)),
+                       ("sequence lag 63", lambda: seq63.push_packed(chunk(), [n] * S)))
+            res = {}
+            for name, fn in fns:
+                med, p90 = time_pushes(fn, a.iters, a.warmup)
+                res[name] = med
+                rows.append(dict(kind=name, dtype=dtype, streams=S, windows=m, median_us=round(med, 1), p90_us=round(p90, 1),
+                                 kernels_per_push=count_kernels(fn, pushes=3)))
+            gate_adds = res["gated"] - res["ungated"]
+            for r in rows[-4:]:
+                r["adds_us"] = round(res[r["kind"]] - res["ungated"], 1)
+                r["of_gate"] = round((res[r["kind"]] - res["ungated"]) / gate_adds, 2) if gate_adds > 0 else float("nan")
+                r["lag63_per_window_us"] = round((res["sequence lag 63"] - res["sequence lag 0"]) / m, 2)
+                print(json.dumps(r), flush=True)
+            del plain, gate, seq0, seq63
+            torch.cuda.empty_cache()
+    if a.sequence_sweep:
+        from contrastiveprosthetics_amd.sequence import potts
+        K, M, G = 8, 14514, 4096
+        ids = list(range(K))
+        logits, exp = _cued_logits(M, K)
+        mats = [potts(K, sw, en, rl, tr) for sw in (0.25, 0.5) for en in (0.25, 0.5) for rl in (0.25, 0.5) for tr in (False, True)]
+        for lag in (0, 63):
+            configs = sequence_grid(transitions=mats, min_cosine=[0.1 + 0.4 * i / 255 for i in range(256)], lag=[lag])
+            assert len(configs) == G
+            scores = sweep_sequence(logits, exp, ids, configs)
+            ts, t_case = [], time.perf_counter()
+            while len(ts) < min(a.iters, 10) and (not ts or time.perf_counter() - t_case < a.case_seconds):
+                t0 = time.perf_counter()
+                sweep_sequence(logits, exp, ids, configs)      # (returns host arrays: it has synchronised)
+                ts.append(time.perf_counter() - t0)
+            host, t0 = logits.cpu().numpy(), time.perf_counter()
+            some = list(range(0, G, G // 16))
+            for g in some:
+                c = configs[g]
+                cmd = SequenceReference(ids, c["min_cosine"], _matrix_for(c["transitions"], np.arange(K)), lag).run_rows(host)[0]
+                want = score_commands(cmd, exp)
+                if any(int(scores[k][g]) != want[k] for k in SCORE_KEYS):
+                    raise SystemExit(f"config {g} at lag {lag}: the sweep's scores are not the definition's")
+            ref_ms = (time.perf_counter() - t0) * 1e3 * G / len(some)
+            r = dict(windows=M, configs=G, models=len(mats), lag=lag, sweep_ms=round(float(np.median(ts)) * 1e3, 3), reps=len(ts),
+                     definition_ms_scaled_from_16=round(ref_ms, 0), ratio=round(ref_ms / (float(np.median(ts)) * 1e3), 0))
+            print(json.dumps(r), flush=True)
+            sweeps.append(r)
+        # the best gate next to the best sequence decoder on one recording of 41 classes, 600 windows
+        cid, lg, exp41 = _cued_recording_41()
+        dev = torch.from_numpy(lg).cuda()
+        gates = gate_grid(min_cosine=[0.2, 0.3, 0.4, 0.5], dwell=[1, 2, 3, 5], release=[1, 2, 5, 10], weight=["count", "margin"],
+                          min_votes=[1, 2], vote=[1, 3, 5, 10, 25])
+        seqs = sequence_grid(transitions=[dict(switch=sw, engage=en, release=rl, through_rest=tr) for sw in (0.125, 0.25, 0.5, 1.0)
+                                          for en in (0.125, 0.25, 0.5, 1.0) for rl in (0.125, 0.25, 0.5, 1.0) for tr in (False, True)],
+                             min_cosine=[0.2, 0.3, 0.4, 0.5], lag=[0, 2, 5, 10])
+        for name, grid, table in (("sweep_gate", gates, sweep_gate(dev, exp41, cid, gates)),
+                                  ("sweep_sequence", seqs, sweep_sequence(dev, exp41, cid, seqs))):
+            g = pick_gate(table)
+            r = dict(sweep=name, configs=len(grid), picked=g)
+            if g is not None:
+                r.update({k: int(table[k][g]) for k in ("n_cue", "n_rest", "hit", "wrong", "false_active", "switches", "reached")})
+                r["mean_latency_windows"] = round(int(table["latency_sum"][g]) / max(int(table["reached"][g]), 1), 2)
+                r["config"] = {k: v for k, v in grid[g].items()}
+            print(json.dumps(r, default=str), flush=True)
+            versus.append(r)
+    if a.out:
+        dev_name = torch.cuda.get_device_name(0)
+        with open(a.out, "w") as f:
+            f.write(f"# tools/online_bench.py{' --sequence' if a.sequence else ''}{' --sequence-sweep' if a.sequence_sweep else ''} "
+                    f"--iters {a.iters} --warmup {a.warmup} on {dev_name}\n")
+            if rows:
+                f.write("# ungated = decoder.push(return_logits=True), gated = CommandGate.push, sequence = SequenceGate.push (potts 0.5, min_cosine\n"
+                        "# 0.2), each on a decoder of its own; per-push wall time, host-synchronised (median, p90), kernels per push\n"
+                        "# (torch.profiler); adds = median - ungated median of the same run, of_gate = adds / the gate's adds,\n"
+                        "# lag63/window = (sequence lag 63 - sequence lag 0) / windows of one stream's push\n")
+                f.write(f"{'kind':<16} {'dtype':<5} {'streams':>7} {'windows':>7} {'median_us':>10} {'p90_us':>9} {'kernels':>8} {'adds_us':>8} "
+                        f"{'of_gate':>8} {'lag63/window':>13}\n")
+                for r in rows:
+                    f.write(f"{r['kind']:<16} {r['dtype']:<5} {r['streams']:>7} {r['windows']:>7} {r['median_us']:>10.1f} {r['p90_us']:>9.1f} "
+                            f"{r['kernels_per_push']:>8.1f} {r['adds_us']:>8.1f} {r['of_gate']:>8.2f} {r['lag63_per_window_us']:>13.2f}\n")
+            if sweeps:
+                f.write("# sweep_sequence: synthetic cued logits, 8 classes, 16 cost matrices x 256 thresholds at one lag; wall time of one call\n"
+                        "# (scores on the host), median over reps; definition = SequenceReference + score_commands on the host for 16 of the\n"
+                        "# configs, scaled to all of them; the 16 score rows equal the sweep's\n")
+                f.write(f"{'windows':>7} {'configs':>7} {'lag':>4} {'sweep_ms':>9} {'reps':>5} {'definition_ms':>14} {'ratio':>8}\n")
+                for r in sweeps:
+                    f.write(f"{r['windows']:>7} {r['configs']:>7} {r['lag']:>4} {r['sweep_ms']:>9.3f} {r['reps']:>5} "
+                            f"{r['definition_ms_scaled_from_16']:>14.0f} {r['ratio']:>8.0f}\n")
+            if versus:
+                f.write("# one synthetic recording, 41 classes, 600 windows: the config pick_gate takes (default limits) from each sweep\n")
+                f.write(f"{'sweep':<15} {'configs':>7} {'hit':>5} {'n_cue':>6} {'wrong':>6} {'false_active':>13} {'n_rest':>7} {'switches':>9} "
+                        f"{'mean_latency':>13}  config\n")
+                for r in versus:
+                    if r["picked"] is None:
+                        f.write(f"{r['sweep']:<15} {r['configs']:>7}  no config within the limits\n")
+                    else:
+                        f.write(f"{r['sweep']:<15} {r['configs']:>7} {r['hit']:>5} {r['n_cue']:>6} {r['wrong']:>6} {r['false_active']:>13} "
+                                f"{r['n_rest']:>7} {r['switches']:>9} {r['mean_latency_windows']:>13.2f}  {r['config']}\n")
 
 
 if __name__ == "__main__":
