@@ -166,6 +166,22 @@ class cp_debug_fp8_args(C.Structure):
                 ("rows_out", C.POINTER(C.c_int32))]
 
 
+class cp_debug_bn_args(C.Structure):
+    """One f32 / bf16 BatchNorm or weight-preparation launch sequence on caller buffers (include/cpnative.h): what cp_debug_bn takes."""
+    _fields_ = [("dtype", C.c_int32), ("kind", C.c_int32), ("mode", C.c_int32), ("C", C.c_int32), ("nfold", C.c_int32),
+                ("K", C.c_int32), ("update_running", C.c_int32), ("reserved0", C.c_int32),
+                ("M", C.c_int64), ("count", C.c_double), ("momentum", C.c_float), ("eps", C.c_float),
+                ("dp_thresh", C.c_uint32), ("dp_key", C.c_uint32), ("dp_inv_keep", C.c_float), ("reserved1", C.c_int32),
+                ("rows", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("running_mean", C.c_void_p),
+                ("running_var", C.c_void_p), ("unscale_exp", C.c_void_p), ("scratch", C.c_void_p), ("stats", C.c_void_p),
+                ("local", C.c_void_p), ("coef", C.c_void_p), ("dgamma", C.c_void_p), ("dbeta", C.c_void_p),
+                ("r", C.c_void_p), ("g", C.c_void_p), ("partials", C.c_void_p), ("db", C.c_void_p),
+                ("params", C.c_void_p), ("bn", C.c_void_p),
+                ("W", C.c_void_p), ("b", C.c_void_p), ("s", C.c_void_p), ("t", C.c_void_p),
+                ("stats9", C.c_void_p * 9), ("wimg", C.c_void_p * 8), ("bimg", C.c_void_p * 8),
+                ("rows_out", C.POINTER(C.c_int32))]
+
+
 CP_ONLINE_MAX_CLASSES, CP_ONLINE_MAX_VOTE, CP_ONLINE_MAX_WINDOWS, CP_ONLINE_STRIDE = 64, 256, 256, 20
 CP_ONLINE_MULTI_MAX_STREAMS, CP_ONLINE_MULTI_MAX_ROWS = 256, 65536
 CP_ONLINE_GATE_SCORES, CP_ONLINE_GATE_SWEEP_MAX_CONFIGS = 10, 65536
@@ -237,6 +253,7 @@ SYMBOLS = {
     "cp_debug_conv": (C.c_int, [_P(cp_debug_conv_args), _fp]),
     "cp_debug_proj": (C.c_int, [_P(cp_debug_proj_args), _fp]),
     "cp_debug_fp8": (C.c_int, [_P(cp_debug_fp8_args), _fp]),
+    "cp_debug_bn": (C.c_int, [_P(cp_debug_bn_args), _fp]),
     "cp_online_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "cp_online_prepare": (C.c_int, [_P(cp_online_config), _P(cp_params), _P(cp_bn_buffers), C.c_float, _fp, C.c_size_t, _fp]),
     "cp_online_set_classes": (C.c_int, [_P(cp_online_config), _fp, C.c_size_t, _fp, _fp, C.c_int32, _fp]),

@@ -1207,6 +1207,137 @@ extern "C" int cp_debug_fp8(const cp_debug_fp8_args* args, void* stream) {
     return debug_fp8(args, (hipStream_t)stream);
 }
 
+// One f32 / bf16 BatchNorm or weight-preparation launch sequence of the large-batch step on caller buffers, through the launch
+// functions of the step (csrc/encoder_api.cuh: their grids, caps, job tables and the pre-reduce rule), at any row count
+template <typename T>
+static int debug_bn_t(const cp_debug_bn_args* d, hipStream_t st) {
+    const PreReduce pre{d->kind == 4 ? d->partials : d->rows, d->scratch, st};
+    PrepImages im{};
+    for (int i = 0; i < CP_N_FC; ++i) { im.wfc[i] = d->wimg[i]; im.bfc[i] = d->bimg[i]; im.wfc_t[i] = d->wimg[i]; }
+    im.wlast = d->wimg[CP_N_FC]; im.blast = d->bimg[CP_N_FC]; im.wlast_t = d->wimg[CP_N_FC];
+    int rows = 0;
+    switch (d->kind) {
+    case 0: {
+        int nrows = (int)d->M;
+        const float* pp = pre(nrows, 2 * d->C);
+        launch_bn_finalize(pp, nrows, d->count, d->gamma, d->beta, d->running_mean, d->running_var, d->update_running ? 1 : 0, d->momentum, d->eps,
+                           d->stats, d->C, (const int*)d->unscale_exp, st);
+        CKL("bn_finalize_kernel");
+        break;
+    }
+    case 1: {
+        StatsTables tb{};
+        for (int l = 0; l < CP_N_BN; ++l) tb.t[l] = d->stats9[l];
+        launch_running_stats(d->params, d->bn, tb, d->eps, st);
+        CKL("bn_running_stats_kernel");
+        launch_eval_folds<T>(d->params, tb, im, st);
+        CKL("fold_linear_batch_kernel");
+        break;
+    }
+    case 2: {
+        int nr = (int)d->M;
+        const float* pp = pre(nr, 2 * d->C * d->nfold);
+        launch_bn_bwd_finalize(pp, nr, d->count, d->stats, d->coef, d->dgamma, d->dbeta, d->C, d->nfold, d->local, st);
+        CKL("bn_bwd_finalize_kernel");
+        break;
+    }
+    case 3:
+        launch_bn_dropout_apply<T>((const T*)d->r, d->stats, (T*)d->g, d->M, d->dp_thresh, d->dp_key, d->dp_inv_keep, nullptr, st);
+        CKL("bn_dropout_apply_kernel");
+        break;
+    case 4:
+        rows = launch_bn_relu_bwd<T>((T*)d->g, (const T*)d->r, d->coef, d->partials, d->M, d->C, d->C == 512 ? CAP_BRB16 : 2048, st);
+        launch_bias_grad_from_rows(pre, rows, d->C, d->db);
+        CKL("bn_relu_bwd_kernel");
+        break;
+    default:
+        if (d->mode <= 1) {
+            launch_fold_linear<T>(d->W, d->b, d->s, d->t, d->wimg[0], d->bimg[0], d->K, d->mode, st);
+            CKL("fold_linear_kernel");
+        } else if (d->mode == 2) {
+            launch_fold_copies<T>(d->params, im, st);
+            CKL("fold_copy_batch_kernel");
+        } else {
+            if (int e = launch_weight_transposes<T>(d->params, im, st)) return e;
+        }
+        break;
+    }
+    if (d->rows_out) *d->rows_out = rows;
+    return 0;
+}
+
+// everything a launch function would be handed blindly, or a kernel would read or write out of bounds, before anything launches
+static int check_debug_bn(const cp_debug_bn_args* d) {
+    if (!d) return fail(CP_ERR_ARG, "cp_debug_bn args");
+    if (d->dtype != CP_F32 && d->dtype != CP_BF16) return fail(CP_ERR_ARG, "cp_debug_bn: dtype must be CP_F32 or CP_BF16");
+    if (d->kind < 0 || d->kind > 5) return fail(CP_ERR_ARG, "cp_debug_bn: kind must be 0..5");
+    const int k = d->kind;
+    if (d->mode < 0 || d->mode > (k == 5 ? 3 : 0)) return fail(CP_ERR_ARG, "cp_debug_bn: mode must be 0..3 in kind 5, else 0");
+    const bool rowed = k == 0 || k == 2 || k == 3 || k == 4;
+    if (rowed && d->M <= 0) return fail(CP_ERR_ARG, "cp_debug_bn: M must be positive");
+    if ((k == 0 || k == 2 || k == 4) && d->C != 64 && d->C != 512) return fail(CP_ERR_ARG, "cp_debug_bn: C must be 64 or 512");
+    if (k == 2 && !(d->nfold == 1 || (d->nfold == 12 && d->C == 64))) return fail(CP_ERR_ARG, "cp_debug_bn: (C, nfold) must be (512, 1), (64, 1) or (64, 12)");
+    if (k == 5 && d->mode <= 1 && !(d->K == 768 || (d->K == 512 && d->mode == 0))) return fail(CP_ERR_ARG, "cp_debug_bn: K must be 512 or 768 in mode 0, 768 in mode 1");
+    if ((k == 0 || k == 2) && !(d->count >= 1.0)) return fail(CP_ERR_ARG, "cp_debug_bn: count must be at least 1");
+    if ((k == 0 || k == 2) && d->M >= (1ll << 31)) return fail(CP_ERR_ARG, "cp_debug_bn: M must stay below 2^31 partial rows");
+    uintptr_t al = 0;          // every pointer the kind hands on, for the alignment check
+    auto need = [&](const void* p) { al |= (uintptr_t)p; return p != nullptr; };
+    auto opt_ = [&](const void* p) { al |= (uintptr_t)p; };
+    if (k == 0) {
+        if (!need(d->rows) || !need(d->gamma) || !need(d->beta) || !need(d->scratch) || !need(d->stats))
+            return fail(CP_ERR_ARG, "cp_debug_bn: kind 0 needs rows, gamma, beta, scratch and stats");
+        if (!d->running_mean != !d->running_var) return fail(CP_ERR_ARG, "cp_debug_bn: running_mean and running_var come together");
+        if (d->update_running && !d->running_mean) return fail(CP_ERR_ARG, "cp_debug_bn: update_running without running buffers");
+        opt_(d->running_mean); opt_(d->running_var);
+        if ((uintptr_t)d->unscale_exp & 3) return fail(CP_ERR_ARG, "cp_debug_bn: unscale_exp must be 4-byte aligned");
+    }
+    if (k == 1 || (k == 5 && d->mode >= 2)) {
+        const cp_params* p = d->params;
+        if (!p) return fail(CP_ERR_ARG, "cp_debug_bn: params must not be NULL");
+        const int first = (k == 5 && d->mode == 2) ? 4 : 0;
+        for (int i = first; i < CP_N_FC; ++i)
+            if (!need(p->fc_w[i]) || !need(d->wimg[i]) || (!(k == 5 && d->mode == 3) && (!need(p->fc_b[i]) || !need(d->bimg[i]))))
+                return fail(CP_ERR_ARG, "cp_debug_bn: params->fc_w, params->fc_b, wimg and bimg of every layer the launch prepares must not be NULL");
+        if (!need(p->last_w) || !need(d->wimg[CP_N_FC]) || (!(k == 5 && d->mode == 3) && !need(d->bimg[CP_N_FC])))
+            return fail(CP_ERR_ARG, "cp_debug_bn: params->last_w, wimg[7] and bimg[7] must not be NULL");
+    }
+    if (k == 1) {
+        if (!d->bn) return fail(CP_ERR_ARG, "cp_debug_bn: bn must not be NULL");
+        for (int l = 0; l < CP_N_BN; ++l)
+            if (!need(d->params->bn_g[l]) || !need(d->params->bn_b[l]) || !need(d->bn->running_mean[l]) || !need(d->bn->running_var[l]) || !need(d->stats9[l]))
+                return fail(CP_ERR_ARG, "cp_debug_bn: kind 1 needs nine bn_g, bn_b, running_mean, running_var and stats9 tables");
+    }
+    if (k == 2) {
+        if (!need(d->rows) || !need(d->scratch) || !need(d->stats) || !need(d->coef) || !need(d->dgamma) || !need(d->dbeta))
+            return fail(CP_ERR_ARG, "cp_debug_bn: kind 2 needs rows, scratch, stats, coef, dgamma and dbeta");
+        opt_(d->local);
+    }
+    if (k == 3) {
+        if (!need(d->r) || !need(d->stats) || !need(d->g)) return fail(CP_ERR_ARG, "cp_debug_bn: kind 3 needs r, stats and g");
+        if (d->dp_thresh > 65535u || !(d->dp_inv_keep > 0.f)) return fail(CP_ERR_ARG, "cp_debug_bn: dp_thresh must not exceed 65535, dp_inv_keep must be positive");
+    }
+    if (k == 4 && (!need(d->r) || !need(d->g) || !need(d->coef) || !need(d->partials) || !need(d->scratch) || !need(d->db)))
+        return fail(CP_ERR_ARG, "cp_debug_bn: kind 4 needs r, g, coef, partials, scratch and db");
+    if (k == 5 && d->mode <= 1) {
+        if (!need(d->W) || !need(d->b) || !need(d->wimg[0]) || !need(d->bimg[0])) return fail(CP_ERR_ARG, "cp_debug_bn: modes 0 and 1 need W, b, wimg[0] and bimg[0]");
+        if (!d->s != !d->t) return fail(CP_ERR_ARG, "cp_debug_bn: s and t come together");
+        opt_(d->s); opt_(d->t);
+    }
+    if (k == 3 || k == 4) {
+        // 32-bit byte offsets of the buffer loads and stores and the dropout hash's 32-bit element index (check_cfg); by division: no M wraps
+        const uint64_t rowb = (uint64_t)(k == 3 ? 512 : d->C) * (d->dtype == CP_BF16 ? 2 : 4);
+        if ((uint64_t)d->M >= (0xFFF00000ull + rowb - 1) / rowb) return fail(CP_ERR_ARG, "cp_debug_bn: M * C * sizeof(T) must stay below 2^32 - 2^20");
+    }
+    if ((al & 15) != 0) return fail(CP_ERR_ARG, "cp_debug_bn: every buffer must be 16-byte aligned");
+    return 0;
+}
+
+extern "C" int cp_debug_bn(const cp_debug_bn_args* args, void* stream) {
+    if (int e = check_debug_bn(args)) return e;
+    if (args->dtype == CP_BF16) return debug_bn_t<bf16_t>(args, (hipStream_t)stream);
+    return debug_bn_t<float>(args, (hipStream_t)stream);
+}
+
 __global__ __launch_bounds__(256) void hog_kernel(long long ticks, float* sink) {
     __shared__ float pad[30 * 1024];                       // 120 KiB: no 64 KiB-stage GEMM block fits beside this one
     pad[threadIdx.x] = (float)threadIdx.x;

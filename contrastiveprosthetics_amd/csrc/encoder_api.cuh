@@ -180,15 +180,33 @@ static inline void launch_proj_transpose(const float* Wp, void* wlast_t, hipStre
 
 // the transposed weights the data-gradient launches read: fc1..fc7 and the projection (bf16 / f32), their e4m3 form + the projection's
 // (CP_FP8).  Made once per step: at the start of the backward pass, or -- second stream -- beside the forward pass.
+// where the weight preparation launches put what they make: the images in the compute dtype and the f32 biases of fc1..fc7 and the
+// projection, and the transposed images.  The step fills it from its workspace (prep_images), cp_debug_bn from caller buffers: both
+// reach the batched kernels through the launch functions that take it (launch_weight_transposes here; launch_eval_folds,
+// launch_fold_copies below), with their job tables and grids
+struct PrepImages {
+    void* wfc[CP_N_FC]; float* bfc[CP_N_FC]; void* wlast; float* blast;
+    void* wfc_t[CP_N_FC]; void* wlast_t;
+};
+static inline PrepImages prep_images(unsigned char* base, const WS& w) {
+    PrepImages im{};
+    for (int i = 0; i < CP_N_FC; ++i) { im.wfc[i] = base + w.wfc[i]; im.bfc[i] = (float*)(base + w.bfc[i]); im.wfc_t[i] = base + w.wfc_t[i]; }
+    im.wlast = base + w.wlast; im.blast = (float*)(base + w.blast); im.wlast_t = base + w.wlast_t;
+    return im;
+}
 template <typename T>
-static int launch_weight_transposes(const cp_params* p, unsigned char* base, const WS& w, hipStream_t st) {
-    ProfScope ps(CP_K_PREP, st);
+static int launch_weight_transposes(const cp_params* p, const PrepImages& im, hipStream_t st) {
     TransposeBatch tb{};
-    for (int i = 0; i < CP_N_FC; ++i) tb.job[i] = TransposeJob{p->fc_w[i], base + w.wfc_t[i], 512, fcK(i), 512, i == 0 ? 1 : 0};
-    tb.job[CP_N_FC] = TransposeJob{p->last_w, base + w.wlast_t, CP_D_E, 512, 64, 0};
+    for (int i = 0; i < CP_N_FC; ++i) tb.job[i] = TransposeJob{p->fc_w[i], im.wfc_t[i], 512, fcK(i), 512, i == 0 ? 1 : 0};
+    tb.job[CP_N_FC] = TransposeJob{p->last_w, im.wlast_t, CP_D_E, 512, 64, 0};
     hipLaunchKernelGGL((transpose_w_batch_kernel<T>), dim3(128, CP_N_FC + 1), dim3(256), 0, st, tb);
     CKL("transpose_w_batch_kernel");
     return 0;
+}
+template <typename T>
+static int launch_weight_transposes(const cp_params* p, unsigned char* base, const WS& w, hipStream_t st) {
+    ProfScope ps(CP_K_PREP, st);
+    return launch_weight_transposes<T>(p, prep_images(base, w), st);
 }
 // the 8-bit weight preparation launches (cp_debug_fp8 runs the same two on one layer): one block per output row of a fold; 12 column
 // blocks of 64 (K <= 768) x jobs x 4 row quarters of a transpose
@@ -297,6 +315,44 @@ struct PreReduce {
     }
 };
 
+// The f32 / bf16 BatchNorm launches between the GEMMs as the step makes them (cp_debug_bn runs the same functions on caller buffers;
+// the caller checks the launch).  launch_bn_relu_bwd returns the number of partial rows (= its grid); `cap`: CAP_BRB16 at C = 512,
+// 2,048 at C = 64 (conv2's BatchNorm, rows = windows * 12).
+static inline void launch_bn_finalize(const float* pp, int nrows, double count, const float* gamma, const float* beta, float* running_mean,
+                                      float* running_var, int update_running, float momentum, float eps, float* stats, int C, const int* unscale,
+                                      hipStream_t st) {
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3(FIN_GRID(C)), dim3(FIN_THREADS), 0, st, pp, nrows, count, gamma, beta, running_mean, running_var,
+                       update_running, 0, momentum, eps, stats, C, unscale);
+}
+static inline void launch_bn_bwd_finalize(const float* pp, int nr, double count, const float* stats, float* coef, float* dgamma, float* dbeta, int C,
+                                          int nfold, const float* local, hipStream_t st) {
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(FIN_GRID(C)), dim3(FIN_THREADS), 0, st, pp, nr, count, stats, coef, dgamma, dbeta, C, nfold, local);
+}
+template <typename T>
+static inline void launch_bn_dropout_apply(const T* r, const float* stats, T* u, int64_t N, uint32_t thresh, uint32_t key, float inv_keep,
+                                           const uint32_t* salt, hipStream_t st) {
+    hipLaunchKernelGGL((bn_dropout_apply_kernel<T>), dim3(grid_rows(N, 256 / (512 / DT<T>::EPC), CAP_BDA16)), dim3(256), 0, st, r, stats, u, N, 512,
+                       thresh, key, inv_keep, salt);
+}
+template <typename T>
+static inline int launch_bn_relu_bwd(T* g, const T* r, const float* coef, float* partials, int64_t rows, int C, int cap, hipStream_t st) {
+    using D = DT<T>;
+    const int gb = grid_rows(rows, 256 / (C / D::EPC), cap);
+    hipLaunchKernelGGL((bn_relu_bwd_kernel<T>), dim3(gb), dim3(256), 256 * D::EPC * 4, st, g, r, coef, partials, rows, C);
+    return gb;
+}
+// a bias gradient = the column sums of `rows` partial rows of C floats
+static inline void launch_bias_grad_from_rows(const PreReduce& pre, int rows, int C, float* db) {
+    const float* pp = pre(rows, C);
+    hipLaunchKernelGGL(colsum_finalize_kernel, dim3(FIN_GRID(C)), dim3(FIN_THREADS), 0, pre.st, pp, rows, C, db);
+}
+// one layer's BatchNorm fold during training: W (512, K) f32 -> out_w[512][K] T = W diag s in the layer's operand order, out_b = b + W t
+template <typename T>
+static inline void launch_fold_linear(const float* W, const float* b, const float* s, const float* t, void* out_w, float* out_b, int K, int mode,
+                                      hipStream_t st) {
+    hipLaunchKernelGGL((fold_linear_kernel<T>), dim3(512), dim3(256), 0, st, W, b, s, t, (T*)out_w, out_b, 512, K, mode);
+}
+
 // Synchronised BatchNorm: fold `nrows` partial rows of `width` floats into ONE row (this rank's sums, kept in ws.sync_loc),
 // copy it, and have the caller's hook sum the copy over the ranks in place (ws.sync_glob).  Returns the global row;
 // *local = this rank's row.  Stream-ordered: the hook enqueues its collective behind `st` and makes `st` wait for it.
@@ -342,6 +398,9 @@ struct ProjDrop {
     const uint32_t* dp_salt;
 };
 
+// where the nine statistics tables [4][C] lie: the step's workspace (Pass::stats_tables()), or cp_debug_bn's caller buffers
+struct StatsTables { float* t[CP_N_BN]; };
+
 // ---------------------------------------------------------------------------------------
 // one pass: what every function of the encoder's forward and backward pass reads of its call
 // ---------------------------------------------------------------------------------------
@@ -361,7 +420,9 @@ struct Pass {
     const float* scale(int l) const { return stats(l) + 2 * kLayerC[l]; }
     const float* shift(int l) const { return stats(l) + 3 * kLayerC[l]; }
     float* rows2() const { return (float*)(base + w.partials2); }
-    const float* pre(int& nrows, int W, int direct_rows = FIN_DIRECT_ROWS) const { return PreReduce{partials, rows2(), st}(nrows, W, direct_rows); }
+    PreReduce prered() const { return PreReduce{partials, rows2(), st}; }
+    const float* pre(int& nrows, int W, int direct_rows = FIN_DIRECT_ROWS) const { return prered()(nrows, W, direct_rows); }
+    StatsTables stats_tables() const { StatsTables s{}; for (int l = 0; l < CP_N_BN; ++l) s.t[l] = stats(l); return s; }
     ConvLaunch conv() const { return ConvLaunch{st, N(), partials, slabs, rows2(), stats(0)}; }
     ProjLaunch proj() const { return ProjLaunch{st, N(), partials}; }
 };
@@ -409,21 +470,45 @@ static int bn_finalize(const Pass& ctx, const FwdBN& f, int l, int nrows, double
         count *= c->stats_world;
         unscale = nullptr;
     }
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(FIN_GRID(C)), dim3(FIN_THREADS), 0, ctx.st, pp, nrows, count, f.p->bn_g[l], f.p->bn_b[l],
-                       f.mean(l), f.var(l), f.upd, 0, c->bn_momentum, c->bn_eps, ctx.stats(l), C, unscale);
+    launch_bn_finalize(pp, nrows, count, f.p->bn_g[l], f.p->bn_b[l], f.mean(l), f.var(l), f.upd, c->bn_momentum, c->bn_eps, ctx.stats(l), C, unscale, ctx.st);
     CKL("bn_finalize_kernel");
     return 0;
 }
 
 // evaluation with the running statistics: one launch writes all nine statistics tables (the caller checks the launch)
-static void launch_running_stats(const Pass& ctx, const FwdBN& f) {
+static void launch_running_stats(const cp_params* p, const cp_bn_buffers* bn, const StatsTables& stats, float eps, hipStream_t st) {
     BnRunningAll ra{};
     for (int l = 0; l < CP_N_BN; ++l) {
-        ra.gamma[l] = f.p->bn_g[l]; ra.beta[l] = f.p->bn_b[l]; ra.mean[l] = f.bn->running_mean[l]; ra.var[l] = f.bn->running_var[l];
-        ra.stats[l] = ctx.stats(l); ra.C[l] = kLayerC[l];
+        ra.gamma[l] = p->bn_g[l]; ra.beta[l] = p->bn_b[l]; ra.mean[l] = bn->running_mean[l]; ra.var[l] = bn->running_var[l];
+        ra.stats[l] = stats.t[l]; ra.C[l] = kLayerC[l];
     }
-    ra.eps = ctx.cfg->bn_eps;
-    hipLaunchKernelGGL(bn_running_stats_kernel, dim3(CP_N_BN), dim3(512), 0, ctx.st, ra);
+    ra.eps = eps;
+    hipLaunchKernelGGL(bn_running_stats_kernel, dim3(CP_N_BN), dim3(512), 0, st, ra);
+}
+static void launch_running_stats(const Pass& ctx, const FwdBN& f) {
+    launch_running_stats(f.p, f.bn, ctx.stats_tables(), ctx.cfg->bn_eps, ctx.st);
+}
+// ... so every BatchNorm fold of an evaluation pass (fc1..fc7 and the projection) can be made up front, in one launch instead of eight
+// between the GEMMs (the caller checks the launch)
+template <typename T>
+static void launch_eval_folds(const cp_params* p, const StatsTables& stats, const PrepImages& im, hipStream_t st) {
+    FoldBnBatch fb{};
+    for (int i = 0; i < CP_N_FC; ++i) {
+        const int Lp = 1 + i;
+        fb.job[i] = FoldBnJob{p->fc_w[i], p->fc_b[i], stats.t[Lp] + 2 * kLayerC[Lp], stats.t[Lp] + 3 * kLayerC[Lp], im.wfc[i], im.bfc[i], 512, fcK(i),
+                              i == 0 ? 1 : 0, 512};
+    }
+    fb.job[CP_N_FC] = FoldBnJob{p->last_w, nullptr, stats.t[8] + 2 * kLayerC[8], stats.t[8] + 3 * kLayerC[8], im.wlast, im.blast, CP_D_E, 512, 0, 32};
+    hipLaunchKernelGGL((fold_linear_batch_kernel<T>), dim3(512, CP_N_FC + 1), dim3(256), 0, st, fb);
+}
+// the weights of the layers behind a dropout (fc5..fc7, projection) carry no BatchNorm fold: plain copies, all in one launch (the
+// caller checks the launch)
+template <typename T>
+static void launch_fold_copies(const cp_params* p, const PrepImages& im, hipStream_t st) {
+    FoldBatch fb{};
+    for (int q = 0; q < 3; ++q) fb.job[q] = FoldJob{p->fc_w[4 + q], p->fc_b[4 + q], im.wfc[4 + q], im.bfc[4 + q], 512, 512, 512};
+    fb.job[3] = FoldJob{p->last_w, nullptr, im.wlast, im.blast, CP_D_E, 512, 32};
+    hipLaunchKernelGGL((fold_copy_batch_kernel<T>), dim3(512, 4), dim3(256), 0, st, fb);
 }
 
 // conv2's weights in the compute dtype, in the forward's and the data gradient's layout (the caller checks the launch)
@@ -509,24 +594,11 @@ static int encoder_forward_t(const cp_config* c, const cp_params* p, const cp_bn
         if (!batch_stats) {
             launch_running_stats(ctx, f);
             CKL("bn_running_stats_kernel");
-            // ... so every BatchNorm fold of the pass (fc1..fc7 and the projection) can be made now, in one launch instead of eight between the GEMMs
-            FoldBnBatch fb{};
-            for (int i = 0; i < CP_N_FC; ++i) {
-                const int Lp = 1 + i;
-                fb.job[i] = FoldBnJob{p->fc_w[i], p->fc_b[i], ctx.scale(Lp), ctx.shift(Lp), base + w.wfc[i],
-                                      (float*)(base + w.bfc[i]), 512, fcK(i), i == 0 ? 1 : 0, 512};
-            }
-            fb.job[CP_N_FC] = FoldBnJob{p->last_w, nullptr, ctx.scale(8), ctx.shift(8), base + w.wlast, (float*)(base + w.blast), CP_D_E, 512, 0, 32};
-            hipLaunchKernelGGL((fold_linear_batch_kernel<T>), dim3(512, CP_N_FC + 1), dim3(256), 0, st, fb);
+            launch_eval_folds<T>(p, ctx.stats_tables(), prep_images(base, w), st);
             CKL("fold_linear_batch_kernel");
         }
         if (drop) {
-            // the weights of the layers behind a dropout (fc5..fc7, projection) carry no BatchNorm fold: plain copies, all in one launch
-            FoldBatch fb{};
-            for (int q = 0; q < 3; ++q)
-                fb.job[q] = FoldJob{p->fc_w[4 + q], p->fc_b[4 + q], base + w.wfc[4 + q], (float*)(base + w.bfc[4 + q]), 512, 512, 512};
-            fb.job[3] = FoldJob{p->last_w, nullptr, base + w.wlast, (float*)(base + w.blast), CP_D_E, 512, 32};
-            hipLaunchKernelGGL((fold_copy_batch_kernel<T>), dim3(512, 4), dim3(256), 0, st, fb);
+            launch_fold_copies<T>(p, prep_images(base, w), st);
             CKL("fold_copy_batch_kernel");
         }
     }
@@ -552,15 +624,13 @@ static int encoder_forward_t(const cp_config* c, const cp_params* p, const cp_bn
         if (in_drop) {
             T* u = (T*)(base + w.u[Lp - 5]);
             ProfScope ps(CP_K_DROPOUT, st);
-            hipLaunchKernelGGL((bn_dropout_apply_kernel<T>), dim3(grid_rows(N, 256 / (512 / D::EPC), CAP_BDA16)), dim3(256), 0, st,
-                               ctx.act<T>(Lp), ctx.stats(Lp), u, N, 512, dp_thresh(c->dp_emg), dp_key(c, Lp), dp_inv_keep(c->dp_emg), dp_salt(c));
+            launch_bn_dropout_apply<T>(ctx.act<T>(Lp), ctx.stats(Lp), u, N, dp_thresh(c->dp_emg), dp_key(c, Lp), dp_inv_keep(c->dp_emg), dp_salt(c), st);
             CKL("bn_dropout_apply_kernel");
             A = u;
         }
         if (!in_drop && batch_stats) {          // (the layers behind a dropout were copied by fold_copy_batch_kernel above; running statistics: folded up front)
             ProfScope ps(CP_K_FOLD, st);
-            hipLaunchKernelGGL((fold_linear_kernel<T>), dim3(512), dim3(256), 0, st, p->fc_w[i], p->fc_b[i], ctx.scale(Lp), ctx.shift(Lp),
-                               (T*)(base + w.wfc[i]), (float*)(base + w.bfc[i]), 512, K, i == 0 ? 1 : 0);
+            launch_fold_linear<T>(p->fc_w[i], p->fc_b[i], ctx.scale(Lp), ctx.shift(Lp), base + w.wfc[i], (float*)(base + w.bfc[i]), K, i == 0 ? 1 : 0, st);
             CKL("fold_linear_kernel");
         }
         GemmNTArgs a{};
@@ -866,8 +936,7 @@ static int bwd_finalize(const Pass& ctx, cp_params* g, const float* pp, int nr, 
         nr = 1;
         count *= c->stats_world;
     }
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(FIN_GRID(C)), dim3(FIN_THREADS), 0, ctx.st, pp, nr, count, ctx.stats(l), ctx.coef, g->bn_g[l],
-                       g->bn_b[l], C, nfold, local);
+    launch_bn_bwd_finalize(pp, nr, count, ctx.stats(l), ctx.coef, g->bn_g[l], g->bn_b[l], C, nfold, local, ctx.st);
     CKL(what);
     return 0;
 }
@@ -886,8 +955,7 @@ static inline void set_bn_prologue(GemmNTArgs& a, const Pass& ctx, cp_params* g,
 
 // a bias gradient = the column sums of `rows` partial rows of C floats (ctx.partials)
 static int bias_grad_from_rows(const Pass& ctx, int rows, int C, float* db, const char* what) {
-    const float* pp = ctx.pre(rows, C);
-    hipLaunchKernelGGL(colsum_finalize_kernel, dim3(FIN_GRID(C)), dim3(FIN_THREADS), 0, ctx.st, pp, rows, C, db);
+    launch_bias_grad_from_rows(ctx.prered(), rows, C, db);
     CKL(what);
     return 0;
 }
@@ -1121,8 +1189,7 @@ static int conv_backward_tail(const cp_config* c, const cp_params* p, const floa
         int nr = stat_rows;          // 1: fc1's input (conv2's BN) never has dropout
         const float* pp = ctx.pre(nr, 2 * 768);
         if (int e = bwd_finalize(ctx, g, pp, nr, (double)R12, 1, 64, 12, "bn_bwd_finalize_kernel(conv2)")) return e;
-        const int gb = grid_rows(R12, 256 / (64 / D::EPC), 2048);
-        hipLaunchKernelGGL((bn_relu_bwd_kernel<T>), dim3(gb), dim3(256), 256 * D::EPC * 4, st, cur, ctx.act<T>(1), ctx.coef, partials, R12, 64);
+        const int gb = launch_bn_relu_bwd<T>(cur, ctx.act<T>(1), ctx.coef, partials, R12, 64, 2048, st);
         if (int e = bias_grad_from_rows(ctx, gb, 64, g->conv2_b, "bn_relu_bwd_kernel(conv2)")) return e;
         gcol_rows = 0;
     }
@@ -1372,8 +1439,7 @@ static int encoder_backward_t(const cp_config* c, const cp_params* p, const floa
             int nr = stat_rows;
             const float* pp = ctx.pre(nr, 2 * 512);
             if (int e = bwd_finalize(ctx, g, pp, nr, (double)N, L, 512, 1, "bn_bwd_finalize_kernel")) return e;
-            const int gb = grid_rows(N, 256 / (512 / D::EPC), CAP_BRB16);
-            hipLaunchKernelGGL((bn_relu_bwd_kernel<T>), dim3(gb), dim3(256), 256 * D::EPC * 4, st, cur, ctx.act<T>(L), coef, partials, N, 512);
+            const int gb = launch_bn_relu_bwd<T>(cur, ctx.act<T>(L), coef, partials, N, 512, CAP_BRB16, st);
             // (the bias gradient is consumed within this pass -- reduce_slabs' BatchNorm un-fold and
             //  bn_bwd_sums_from_wgrad_kernel read it -- so these small launches cannot be batched at the end of the loop)
             if (int e = bias_grad_from_rows(ctx, gb, 512, g->fc_b[i], "bn_relu_bwd_kernel")) return e;

@@ -688,6 +688,87 @@ typedef struct cp_debug_fp8_args {
 } cp_debug_fp8_args;
 int cp_debug_fp8(const cp_debug_fp8_args* args, void* stream);
 
+/* debug/test access (tests/test_gpu_bn_exact.py): the f32 / bf16 BatchNorm and weight-preparation launches that sit between the GEMMs
+ * of the large-batch step (csrc/kernels_misc.cuh) on caller buffers, one launch sequence at a time, at any row count >= 1.  The kernels
+ * are reached through the launch functions of the step (csrc/encoder_api.cuh: PreReduce, launch_bn_finalize, launch_running_stats,
+ * launch_eval_folds, launch_bn_bwd_finalize, launch_bn_dropout_apply, launch_bn_relu_bwd, launch_bias_grad_from_rows,
+ * launch_fold_linear, launch_fold_copies, launch_weight_transposes): its grids, caps, job tables and pre-reduce rule.  T = float
+ * (CP_F32) or bf16 (CP_BF16) where the kernel is templated (kinds 1, 3, 4, 5; kinds 0 and 2 are f32 throughout and ignore dtype
+ * beyond its check).  M is the number of partial rows in kinds 0 and 2, the number of activation rows in kinds 3 and 4.
+ *   kind 0   statistics.  rows = partials[M][2][C] (sum, sum of squares), C = 64 | 512.  PreReduce (reduce_rows_kernel into
+ *            scratch[32][2C] when M > 2,048) then bn_finalize_kernel -> stats[4][C] = mean, invstd, scale = gamma invstd, shift =
+ *            beta - mean scale, from mean = s1 / count, var = max(s2 / count - mean^2, 0), invstd = 1 / sqrt(var + eps); update_running
+ *            != 0: running_mean / running_var (both non-NULL then) <- (1 - momentum) old + momentum (mean | var count / (count - 1)).
+ *            unscale_exp (device int32 or NULL): s1 is scaled by 2^-e and s2 by 2^-2e first.
+ *   kind 1   evaluation prologue.  launch_running_stats on the nine tables params->bn_g / bn_b, bn->running_mean / running_var
+ *            (C = 64, 64, 512 x 7) -> stats9[l][4][C]; then the eight-job fold_linear_batch_kernel<T> as the evaluation forward fills
+ *            it: fc1 (params->fc_w[0], K = 768, mode 1: stored k' = w*64 + c of k = c*12 + w) .. fc7 folded with the affine of the
+ *            BatchNorm below each -> wimg[i][512][K] T = W diag s, bimg[i][512] = b + W t; the projection params->last_w (16, 512),
+ *            no bias -> wimg[7][32][512] T (rows 16..31 zero), bimg[7][16] = W t
+ *   kind 2   backward coefficients.  rows = partials[M][2][C nfold] (sum g, sum g r; feature f*C + c belongs to channel c), (C, nfold) =
+ *            (512, 1) | (64, 1) | (64, 12).  PreReduce (into scratch[32][2 C nfold] when M > 2,048) then bn_bwd_finalize_kernel with
+ *            stats[4][C] -> coef[3][C], dgamma[C], dbeta[C].  local (or NULL): one row [2][C nfold]; dgamma / dbeta then come from it
+ *   kind 3   bn_dropout_apply_kernel<T> on the step's grid: g = u[M][512] T = keep ? (s r + t) dp_inv_keep : 0 with r[M][512] T,
+ *            s / t = stats[2 | 3][.], keep(m, f): the 16-bit draw of the dropout hash of (dp_key, m, 512, f) is >= dp_thresh
+ *   kind 4   bn_relu_bwd_kernel<T> in place, then launch_bias_grad_from_rows.  C = 512 (cap CAP_BRB16) | 64 (cap 2,048):
+ *            g[M][C] T <- r > 0 ? ca g + cb r + cz : 0 with ca / cb / cz = coef[0..2][.]; partials[gb][C] = per-block column sums
+ *            of g as stored; db[C] = their sum; *rows_out = gb
+ *   kind 5   weight preparation during training.  mode 0 | 1: launch_fold_linear<T> in that mode on W (512, K) f32, K = 512 | 768
+ *            (mode 1: K = 768), b[512], s / t (both or neither; NULL: the plain copy) -> wimg[0][512][K] T, bimg[0][512].  mode 2: the
+ *            four-job fold_copy_batch_kernel<T> as the dropout forward fills it -> wimg[4..6], bimg[4..6] (fc5..fc7), wimg[7][32][512],
+ *            bimg[7][16] = 0 (projection).  mode 3: the eight-job transpose_w_batch_kernel<T> as the backward fills it ->
+ *            wimg[i][K][512] T = W^T (fc1 in the order k' = w*64 + c), wimg[7][512][64] T = last_w^T, columns 16..63 zero
+ * Every scratch and output region is the caller's, so guards behind them can be inspected.  rows_out: host, may be NULL.
+ * Checked before anything launches, CP_ERR_ARG: a NULL pointer the kind reads or writes (params' and bn's members included), M <= 0
+ * (kinds 0, 2, 3, 4), count < 1 (kinds 0, 2), an unknown dtype, kind, mode or shape (C, nfold, K), s without t, update_running without
+ * running buffers, a pointer not 16-byte aligned, dp_thresh > 65535 or dp_inv_keep <= 0 in kind 3,
+ * M * C * sizeof(T) >= 2^32 - 2^20 in kinds 3 and 4 (the step's bound), M >= 2^31 in kinds 0 and 2 (partial rows are counted in 32 bits). */
+typedef struct cp_debug_bn_args {
+    int32_t dtype;             /* CP_F32 | CP_BF16 */
+    int32_t kind;              /* 0..5 */
+    int32_t mode;              /* kind 5: 0..3, else 0 */
+    int32_t C;                 /* kinds 0, 2, 4: 64 | 512 */
+    int32_t nfold;             /* kind 2: 1 | 12 */
+    int32_t K;                 /* kind 5, modes 0 and 1: 512 | 768 */
+    int32_t update_running;    /* kind 0 */
+    int32_t reserved0;
+    int64_t M;
+    double count;              /* kinds 0, 2 */
+    float momentum;            /* kind 0 */
+    float eps;                 /* kinds 0, 1 */
+    uint32_t dp_thresh;        /* kind 3 */
+    uint32_t dp_key;
+    float dp_inv_keep;
+    int32_t reserved1;
+    const float* rows;         /* kinds 0, 2: the partial rows */
+    const float* gamma;        /* [C], kind 0 */
+    const float* beta;
+    float* running_mean;       /* [C] or NULL, kind 0 */
+    float* running_var;
+    const int32_t* unscale_exp; /* device, or NULL, kind 0 */
+    float* scratch;            /* kinds 0, 2, 4: the pre-reduce's 32 rows */
+    float* stats;              /* [4][C]: out in kind 0, in in kinds 2 and 3 */
+    const float* local;        /* [2][C nfold] or NULL, kind 2 */
+    float* coef;               /* [3][C]: out in kind 2, in in kind 4 */
+    float* dgamma;             /* [C], kind 2 */
+    float* dbeta;
+    const void* r;             /* [M][C] T, kinds 3, 4 */
+    void* g;                   /* [M][C] T: u in kind 3, the gradient in kind 4 */
+    float* partials;           /* [gb][C], kind 4 */
+    float* db;                 /* [C], kind 4 */
+    const cp_params* params;   /* kinds 1, 5 (modes 2, 3): device pointers in a host struct */
+    const cp_bn_buffers* bn;   /* kind 1 */
+    const float* W;            /* kind 5, modes 0 and 1 */
+    const float* b;
+    const float* s;            /* or NULL */
+    const float* t;
+    float* stats9[CP_N_BN];    /* kind 1 */
+    void* wimg[CP_N_FC + 1];   /* kinds 1, 5 */
+    float* bimg[CP_N_FC + 1];
+    int32_t* rows_out;
+} cp_debug_bn_args;
+int cp_debug_bn(const cp_debug_bn_args* args, void* stream);
+
 /* BN statistics of `layer` as computed by the last forward: out[4][C] = mean, invstd, scale, shift */
 int cp_debug_bn_stats(const cp_config* cfg, void* ws, size_t ws_bytes, int32_t layer, float* out,
                       void* stream);

@@ -375,6 +375,106 @@ def test_debug_proj_refuses_what_a_launcher_would_before_it_launches(lib):
     assert lib.cp_debug_proj(None, None) == 10001
 
 
+def test_debug_bn_refuses_what_a_launcher_would_before_it_launches(lib):
+    """cp_debug_bn checks its arguments on the host, before any launch: CP_ERR_ARG with a message that names the entry (every device
+    pointer is a dummy address that is never dereferenced; params and bn are real host structs of such addresses; each case differs
+    from a valid call of its kind in the one field under test.  That the valid calls are accepted is shown on the GPU:
+    tests/test_gpu_bn_exact.py).  The ctypes struct follows the header field by field."""
+    from contrastiveprosthetics_amd import _lib
+    hdr = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    body = hdr[hdr.index("typedef struct cp_debug_bn_args {"):hdr.index("} cp_debug_bn_args;")]
+    assert re.findall(r"\b(\w+)(?:\[[^\]]*\])?\s*;", body) == [f[0] for f in _lib.cp_debug_bn_args._fields_]
+    assert ctypes.sizeof(_lib.cp_debug_bn_args) == 8 * 4 + 8 + 8 + 6 * 4 + 22 * 8 + (9 + 8 + 8) * 8 + 8
+    ok = 0x100000
+    rows = ctypes.c_int32(-7)
+    pointers = ("rows", "gamma", "beta", "running_mean", "running_var", "scratch", "stats", "coef", "dgamma", "dbeta", "r", "g",
+                "partials", "db", "W", "b", "s", "t")
+
+    def call(**kw):
+        kw = dict(kw)
+        d = _lib.cp_debug_bn_args()
+        d.dtype, d.kind, d.M, d.C, d.nfold, d.K, d.count = 1, kw.get("kind", 0), 1000, 512, 1, 512, 4096.0
+        d.momentum, d.eps, d.update_running = 0.5, 1e-5, 1
+        d.dp_thresh, d.dp_key, d.dp_inv_keep = 32768, 7, 2.0
+        p, bn = _lib.cp_params(), _lib.cp_bn_buffers()
+        for i in range(7):
+            p.fc_w[i], p.fc_b[i] = ok, ok
+        for l in range(9):
+            p.bn_g[l], p.bn_b[l], bn.running_mean[l], bn.running_var[l], d.stats9[l] = ok, ok, ok, ok, ok
+        p.last_w = ok
+        for i in range(8):
+            d.wimg[i], d.bimg[i] = ok, ok
+        d.params, d.bn = ctypes.addressof(p), ctypes.addressof(bn)
+        for name in pointers:
+            setattr(d, name, ok)
+        d.rows_out = ctypes.pointer(rows)
+        for path in kw.pop("clear", ()):                 # a member of params, bn or an array: ("fc_w", 3) | ("stats9", 2) | ("last_w",)
+            tgt = p if hasattr(p, path[0]) else (bn if hasattr(bn, path[0]) else d)
+            if len(path) == 2:
+                getattr(tgt, path[0])[path[1]] = kw.get("to", None)
+            else:
+                setattr(tgt, path[0], kw.get("to", None))
+        kw.pop("to", None)
+        for k, v in kw.items():
+            setattr(d, k, v)
+        rc = lib.cp_debug_bn(ctypes.byref(d), None)
+        return rc, lib.cp_last_error()
+
+    cases = [("dtype 2", dict(dtype=2)), ("dtype -1", dict(dtype=-1)), ("kind 6", dict(kind=6)), ("kind -1", dict(kind=-1)),
+             ("mode 1 outside kind 5", dict(kind=0, mode=1)), ("mode 4", dict(kind=5, mode=4)), ("mode -1", dict(kind=5, mode=-1))]
+    for kind in (0, 2, 3, 4):
+        cases += [("M = 0, kind %d" % kind, dict(kind=kind, M=0)), ("M < 0, kind %d" % kind, dict(kind=kind, M=-41))]
+    for kind in (0, 2, 4):
+        cases += [("C = 128, kind %d" % kind, dict(kind=kind, C=128)), ("C = 0, kind %d" % kind, dict(kind=kind, C=0))]
+    cases += [("nfold 12 at C = 512", dict(kind=2, nfold=12)), ("nfold 2", dict(kind=2, C=64, nfold=2)), ("nfold 0", dict(kind=2, nfold=0)),
+              ("K = 640", dict(kind=5, K=640)), ("K = 512 in mode 1", dict(kind=5, mode=1, K=512)),
+              ("count 0", dict(count=0.0)), ("count nan, kind 2", dict(kind=2, count=float("nan"))),
+              ("2^31 partial rows", dict(M=1 << 31)), ("2^31 partial rows, kind 2", dict(kind=2, M=1 << 31)),
+              ("update_running without buffers", dict(running_mean=None, running_var=None)),
+              ("running_mean alone", dict(running_var=None, update_running=0)), ("unscale_exp + 2", dict(unscale_exp=ok + 2)),
+              ("s without t", dict(kind=5, t=None)), ("t without s", dict(kind=5, mode=1, K=768, s=None)),
+              ("params NULL, kind 1", dict(kind=1, params=None)), ("bn NULL", dict(kind=1, bn=None)),
+              ("params NULL, mode 2", dict(kind=5, mode=2, params=None)), ("params NULL, mode 3", dict(kind=5, mode=3, params=None)),
+              ("dp_thresh 65536", dict(kind=3, dp_thresh=65536)), ("dp_inv_keep 0", dict(kind=3, dp_inv_keep=0.0)),
+              ("dp_inv_keep < 0", dict(kind=3, dp_inv_keep=-2.0)),
+              ("2^32 bytes, bf16, kind 3", dict(kind=3, M=4193280)), ("2^32 bytes, f32, kind 3", dict(kind=3, dtype=0, M=2096640)),
+              ("2^32 bytes, bf16, kind 4", dict(kind=4, M=4193280)), ("2^32 bytes, f32, C = 64", dict(kind=4, dtype=0, C=64, M=16773120)),
+              ("M = 2^54: the byte count wraps to 0", dict(kind=4, M=1 << 54)), ("M = 2^63 - 1", dict(kind=3, M=(1 << 63) - 1))]
+    # every pointer a kind reads or writes
+    needs = {0: ("rows", "gamma", "beta", "scratch", "stats"), 2: ("rows", "scratch", "stats", "coef", "dgamma", "dbeta"),
+             3: ("r", "stats", "g"), 4: ("r", "g", "coef", "partials", "scratch", "db")}
+    for kind, names in needs.items():
+        cases += [("kind %d without %s" % (kind, name), {"kind": kind, name: None}) for name in names]
+    cases += [("mode %d without %s" % (mode, name), {"kind": 5, "mode": mode, "K": 768, name: None}) for mode in (0, 1) for name in ("W", "b")]
+    cases += [("mode 0 without its image", dict(kind=5, clear=[("wimg", 0)])), ("mode 1 without its bias", dict(kind=5, mode=1, K=768, clear=[("bimg", 0)]))]
+    for member in ("fc_w", "fc_b", "wimg", "bimg"):
+        cases += [("kind 1 without %s[%d]" % (member, i), dict(kind=1, clear=[(member, i)])) for i in (0, 6)]
+        cases += [("mode 2 without %s[%d]" % (member, i), dict(kind=5, mode=2, clear=[(member, i)])) for i in (4, 6)]
+    for member in ("fc_w", "wimg"):
+        cases += [("mode 3 without %s[%d]" % (member, i), dict(kind=5, mode=3, clear=[(member, i)])) for i in (0, 6)]
+    for kind, mode in ((1, 0), (5, 2), (5, 3)):
+        cases += [("kind %d mode %d without last_w" % (kind, mode), dict(kind=kind, mode=mode, clear=[("last_w",)])),
+                  ("kind %d mode %d without wimg[7]" % (kind, mode), dict(kind=kind, mode=mode, clear=[("wimg", 7)]))]
+    cases += [("kind 1 without bimg[7]", dict(kind=1, clear=[("bimg", 7)])), ("mode 2 without bimg[7]", dict(kind=5, mode=2, clear=[("bimg", 7)]))]
+    for member in ("bn_g", "bn_b", "running_mean", "running_var", "stats9"):
+        cases += [("kind 1 without %s[%d]" % (member, l), dict(kind=1, clear=[(member, l)])) for l in (0, 8)]
+    cases += [("%s + %d, kind %d" % (name, off, kind), {"kind": kind, name: ok + off})
+              for name, kind, off in (("rows", 0, 4), ("gamma", 0, 4), ("beta", 0, 8), ("running_mean", 0, 4), ("running_var", 0, 8), ("scratch", 2, 4),
+                                      ("stats", 3, 8), ("local", 2, 4), ("coef", 4, 4), ("dgamma", 2, 4), ("dbeta", 2, 8), ("r", 3, 2), ("g", 4, 8),
+                                      ("partials", 4, 4), ("db", 4, 4), ("W", 5, 4), ("b", 5, 8), ("s", 5, 4), ("t", 5, 4))]
+    cases += [("fc_w[2] + 4, kind 1", dict(kind=1, clear=[("fc_w", 2)], to=ok + 4)), ("wimg[7] + 2, mode 3", dict(kind=5, mode=3, clear=[("wimg", 7)], to=ok + 2)),
+              ("stats9[8] + 8", dict(kind=1, clear=[("stats9", 8)], to=ok + 8)), ("running_var[1] + 4", dict(kind=1, clear=[("running_var", 1)], to=ok + 4))]
+    for what, kw in cases:
+        rc, msg = call(**kw)
+        assert rc == 10001 and msg.startswith(b"cp_debug_bn"), (what, rc, msg)
+        assert rows.value == -7, what
+    for what, says in (("kind 6", b"kind"), ("dtype 2", b"dtype"), ("mode 4", b"mode"), ("C = 128, kind 4", b"C must"), ("nfold 2", b"nfold"),
+                       ("K = 640", b"K must"), ("2^32 bytes, bf16, kind 3", b"2^32"), ("rows + 4, kind 0", b"aligned"), ("M = 0, kind 3", b"M must"),
+                       ("dp_thresh 65536", b"dp_thresh"), ("s without t", b"together"), ("count 0", b"count"), ("bn NULL", b"bn must")):
+        assert says in call(**dict(cases)[what])[1], what
+    assert lib.cp_debug_bn(None, None) == 10001
+
+
 def test_debug_fp8_refuses_what_a_launcher_would_before_it_launches(lib):
     """cp_debug_fp8 checks its arguments on the host, before any launch: CP_ERR_ARG with a message that names the entry (every
     pointer is a dummy address that is never dereferenced; each case differs from a valid call of its kind in the one field under
