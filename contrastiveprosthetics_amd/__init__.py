@@ -40,6 +40,9 @@ def __getattr__(name):
                 "stage_reference"):                            # (metric.fit_reference: by module)
         from . import metric
         return getattr(metric, name)
+    if name in ("fit_projection", "Readout", "pick_ridge", "readout_recording"):   # (readout.fit_reference, apply_reference: by module)
+        from . import readout
+        return getattr(readout, name)
     if name in ("SequenceGate", "SequenceReference", "potts", "transitions_from_cues", "sweep_sequence", "sequence_grid"):
         from . import sequence
         return getattr(sequence, name)

@@ -197,6 +197,7 @@ CP_ONLINE_HOLDOUT_SCORES, CP_ONLINE_HOLDOUT_MAX_PLANS, CP_ONLINE_HOLDOUT_MAX_REP
 CP_ONLINE_PROTO_MAX_ROWS, CP_ONLINE_PROTO_MAX_ITERS = 4, 64
 CP_ONLINE_METRIC_MOMENTS, CP_ONLINE_METRIC_MAX_SHRINKS = 152, 64
 CP_ONLINE_METRIC_RESET_RING, CP_ONLINE_METRIC_RESET_ALL = 0, 1
+CP_ONLINE_READOUT_MAX_GROUPS, CP_ONLINE_READOUT_MAX_PLANS, CP_ONLINE_READOUT_STAGE, CP_ONLINE_READOUT_X = 16, 256, 16, 513
 
 # what the four map sweep entries take behind their workspace: rms, n_windows, mean_std, map_src, map_fill, n_maps, n_classes,
 # expected_slot, chunk_rows, scratch, scratch_bytes, pred, voted, scores, class_hits, stream
@@ -396,6 +397,12 @@ SYMBOLS = {
     "cp_online_metric_reset": (C.c_int, [C.c_int32, C.c_int32, _fp, C.c_size_t, C.c_int32, C.c_int32, _fp]),
     "cp_online_metric_push": (C.c_int, [C.c_int32, C.c_int32, _fp, C.c_size_t, _fp, _fp, _fp, C.c_int32, _fp, _fp, _fp, C.c_int32,
                                         _fp]),
+    "cp_online_readout_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "cp_online_readout_moments": (C.c_int, [_fp, C.c_int32, C.c_int64, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, _fp, _fp, _fp, C.c_size_t,
+                                            _fp]),
+    "cp_online_readout_solve": (C.c_int, [_fp, _fp, C.c_int32, _P(C.c_uint32), _P(C.c_double), C.c_int32, _fp, _fp, _fp, _fp, C.c_size_t,
+                                          _fp]),
+    "cp_online_readout_apply": (C.c_int, [_fp, C.c_int32, C.c_int64, _fp, _fp, C.c_int32, _fp, _fp, C.c_size_t, _fp]),
 }
 
 KERNEL_KINDS = ["gather", "prep", "conv1_fwd", "bn_finalize", "conv2_fwd", "fold", "fc_fwd", "dropout", "proj_fwd",

@@ -36,6 +36,7 @@
 #include "online_holdout.cuh"
 #include "online_prototypes.cuh"
 #include "online_metric.cuh"
+#include "online_readout.cuh"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* what) {

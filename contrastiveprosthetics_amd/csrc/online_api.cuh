@@ -1,7 +1,7 @@
 // Host layer of the online decoders (include/cpnative.h, cp_online_*): workspace layout, argument checks, launch chains and
 // the extern "C" entries of the folded, adaptive, multi-stream and adaptive multi-stream decoders, class enrolment, head
 // fine-tuning, the command gate, the sequence decoder and its sweep, the grasp drive, the gate sweep, the subset sweep, the electrode-map sweep, cue realignment, prototype
-// tracking, held-out enrolment scoring, posture prototypes and the user metric.  Host code only; api.hip includes it behind its own helpers (fail, CK, CKL) and encoder_api.cuh's (align256, fcK),
+// tracking, held-out enrolment scoring, posture prototypes, the user metric and the closed-form head fit.  Host code only; api.hip includes it behind its own helpers (fail, CK, CKL) and encoder_api.cuh's (align256, fcK),
 // so the library stays one translation unit.  The four decoders share one workspace description (OlWS, ol_carve), one
 // parameter check, one set of front-end arguments, one folded chain and one unfolded weight copy; what an entry adds is its
 // name in the refusals and the kernels it launches.
@@ -2413,4 +2413,115 @@ extern "C" int cp_online_metric_push(int32_t vote, int32_t n_streams, void* ws, 
     hipLaunchKernelGGL(om_push_kernel, dim3(n_streams), dim3(64), 0, (hipStream_t)stream, a);
     CKL("om_push_kernel");
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// closed-form head fit (csrc/online_readout.cuh): the weighted moments of a recording's tail inputs per group, the ridge
+// normal equations of many plans solved by Cholesky, and the fitted projections applied as the push's tail applies its own
+// ---------------------------------------------------------------------------------------
+static_assert(OLR_MAXK == CP_ONLINE_MAX_CLASSES && OLR_MAX_GROUPS == CP_ONLINE_READOUT_MAX_GROUPS && OLR_MAX_PLANS == CP_ONLINE_READOUT_MAX_PLANS &&
+              OLR_STAGE == CP_ONLINE_READOUT_STAGE && OLR_X == CP_ONLINE_READOUT_X, "readout constants");
+static_assert(sizeof(OlrSolveArgs) <= 4096, "olr_solve_kernel takes its plans as kernel arguments");
+
+// One scratch serves the three entries in turn: the index lists and their lengths (moments), a matrix per plan
+// (solve), the fitted projections in the compute dtype, sized for f32 (apply).
+static size_t olr_moments_bytes(int64_t n_rows, int32_t n_groups) {
+    return align256((size_t)n_groups * (size_t)n_rows * 4) + align256((size_t)OLR_MAX_GROUPS * 4);
+}
+static size_t olr_solve_bytes(int32_t n_plans) { return align256((size_t)n_plans * OLR_PLAN_DOUBLES * 8); }
+static size_t olr_apply_bytes(int32_t n_plans) { return align256((size_t)n_plans * OLF_W * 4); }
+
+extern "C" size_t cp_online_readout_scratch_bytes(int64_t n_rows, int32_t n_groups, int32_t n_plans) {
+    if (n_rows < 1) n_rows = 1;
+    if (n_groups < 1) n_groups = 1;
+    if (n_plans < 1) n_plans = 1;
+    size_t n = olr_moments_bytes(n_rows, n_groups);
+    if (olr_solve_bytes(n_plans) > n) n = olr_solve_bytes(n_plans);
+    if (olr_apply_bytes(n_plans) > n) n = olr_apply_bytes(n_plans);
+    return n;
+}
+
+extern "C" int cp_online_readout_moments(const void* u, int32_t dtype, int64_t n_rows, const int32_t* slot, const int32_t* group,
+                                         const double* weight, const float* targets, int32_t n_classes, int32_t n_groups, double* G,
+                                         double* C, void* scratch, size_t scratch_bytes, void* stream) {
+    const char* who = "cp_online_readout_moments";
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (dtype != CP_F32 && dtype != CP_BF16) return bad("dtype must be CP_F32 or CP_BF16");
+    if (n_rows < 0 || n_rows > (int64_t)1 << 24) return bad("n_rows outside 0..2**24");
+    if (n_classes < 1 || n_classes > CP_ONLINE_MAX_CLASSES) return bad("n_classes outside 1..64");
+    if (n_groups < 1 || n_groups > CP_ONLINE_READOUT_MAX_GROUPS) return bad("n_groups outside 1..16");
+    if (!targets || !G || !C || !scratch) return bad("targets, G, C and scratch are required");
+    if (n_rows > 0 && (!u || !slot || !group || !weight)) return bad("u, slot, group and weight are required");
+    if ((uintptr_t)u % 16 || (uintptr_t)slot % 4 || (uintptr_t)group % 4 || (uintptr_t)weight % 8 || (uintptr_t)targets % 4 ||
+        (uintptr_t)G % 8 || (uintptr_t)C % 8 || (uintptr_t)scratch % 256)
+        return bad("misaligned argument");
+    if (scratch_bytes < olr_moments_bytes(n_rows < 1 ? 1 : n_rows, n_groups)) return ol_fail(CP_ERR_WORKSPACE, who, "scratch too small");
+    int32_t* idx = (int32_t*)scratch;
+    int32_t* count = (int32_t*)((unsigned char*)scratch + align256((size_t)n_groups * (size_t)(n_rows < 1 ? 1 : n_rows) * 4));
+    hipLaunchKernelGGL(olr_index_kernel, dim3(n_groups), dim3(64), 0, (hipStream_t)stream, slot, group, (int)n_rows, (int)n_classes, idx, count);
+    CKL("olr_index_kernel");
+    return ol_dispatch(dtype, [&](auto t) {
+        using T = decltype(t);
+        OlrMomentsArgs<T> a{};
+        a.u = (const T*)u; a.slot = slot; a.weight = weight; a.targets = targets; a.idx = idx; a.count = count; a.G = G; a.C = C;
+        a.n_rows = (int)n_rows; a.K = n_classes;
+        hipLaunchKernelGGL((olr_moments_kernel<T>), dim3(OLR_TILES, n_groups), dim3(OLR_MOM_THREADS), 0, (hipStream_t)stream, a);
+        CKL("olr_moments_kernel");
+        return 0;
+    });
+}
+
+extern "C" int cp_online_readout_solve(const double* G, const double* C, int32_t n_groups, const uint32_t* masks, const double* ridges,
+                                       int32_t n_plans, float* W, float* b, int32_t* status, void* scratch, size_t scratch_bytes,
+                                       void* stream) {
+    const char* who = "cp_online_readout_solve";
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (n_groups < 1 || n_groups > CP_ONLINE_READOUT_MAX_GROUPS) return bad("n_groups outside 1..16");
+    if (n_plans < 0 || n_plans > CP_ONLINE_READOUT_MAX_PLANS) return bad("n_plans outside 0..256");
+    if (n_plans == 0) return 0;
+    if (!G || !C || !masks || !ridges || !W || !b || !status || !scratch) return bad("G, C, masks, ridges, W, b, status and scratch are required");
+    if ((uintptr_t)G % 8 || (uintptr_t)C % 8 || (uintptr_t)W % 4 || (uintptr_t)b % 4 || (uintptr_t)status % 4 || (uintptr_t)scratch % 256)
+        return bad("misaligned argument");
+    OlrSolveArgs a{};
+    for (int t = 0; t < n_plans; ++t) {
+        if (masks[t] >> n_groups) return bad("a plan's mask names a group at or above n_groups");
+        if (!(ridges[t] >= 0.0) || !std::isfinite(ridges[t])) return bad("every ridge must be finite and >= 0");
+        a.mask[t] = (unsigned short)masks[t];
+        a.ridge[t] = ridges[t];
+    }
+    if (scratch_bytes < olr_solve_bytes(n_plans)) return ol_fail(CP_ERR_WORKSPACE, who, "scratch too small");
+    a.G = G; a.C = C; a.scratch = (double*)scratch; a.W = W; a.b = b; a.status = status; a.n_groups = n_groups;
+    static bool attr_set = false;
+    if (!attr_set) {      // > 64 KiB of dynamic LDS needs the opt-in once per process
+        CK(hipFuncSetAttribute((const void*)olr_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, OLR_SOLVE_LDS));
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(olr_solve_kernel, dim3(n_plans), dim3(OLR_SOLVE_THREADS), OLR_SOLVE_LDS, (hipStream_t)stream, a);
+    CKL("olr_solve_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_readout_apply(const void* u, int32_t dtype, int64_t n_rows, const float* W, const float* b, int32_t n_plans,
+                                       float* out, void* scratch, size_t scratch_bytes, void* stream) {
+    const char* who = "cp_online_readout_apply";
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (dtype != CP_F32 && dtype != CP_BF16) return bad("dtype must be CP_F32 or CP_BF16");
+    if (n_rows < 0 || n_rows > (int64_t)1 << 24) return bad("n_rows outside 0..2**24");
+    if (n_plans < 0 || n_plans > CP_ONLINE_READOUT_MAX_PLANS) return bad("n_plans outside 0..256");
+    if (n_rows == 0 || n_plans == 0) return 0;
+    if (!u || !W || !b || !out || !scratch) return bad("u, W, b, out and scratch are required");
+    if ((uintptr_t)u % 16 || (uintptr_t)W % 4 || (uintptr_t)b % 4 || (uintptr_t)out % 4 || (uintptr_t)scratch % 256) return bad("misaligned argument");
+    if (scratch_bytes < olr_apply_bytes(n_plans)) return ol_fail(CP_ERR_WORKSPACE, who, "scratch too small");
+    OlrApplyArgs a{};
+    a.u = u; a.wT = scratch; a.b = b; a.out = out; a.n_rows = (int)n_rows;
+    const long long n = (long long)n_plans * OLF_W;
+    return ol_dispatch(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((olr_round_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, W, (T*)scratch, n);
+        CKL("olr_round_kernel");
+        hipLaunchKernelGGL((olr_apply_kernel<T>), dim3((unsigned)((n_rows + OLR_APPLY_ROWS - 1) / OLR_APPLY_ROWS), n_plans), dim3(OL_THREADS), 0,
+                           (hipStream_t)stream, a);
+        CKL("olr_apply_kernel");
+        return 0;
+    });
 }

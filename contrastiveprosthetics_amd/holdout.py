@@ -38,7 +38,8 @@ evaluate.
 A plan with mix outside [0, 1] or not finite, min_windows < 1 or a mask with bits at or above 32 is refused: it scores -1 in
 every counter, its rows stay 0, its confusions 0 and its sequences NOT_EVALUATED.
 
-What was not built: held-out fine-tuning (loop `finetune` with masked labels), held-out AdaBN calibration, and anything about
+What was not built: held-out fine-tuning (loop `finetune` with masked labels; the closed-form `readout.pick_ridge` scores a
+projection on held-out repetitions), held-out AdaBN calibration, and anything about
 real subjects; the person of tools/online_bench.py --holdout is synthetic.
 """
 from __future__ import annotations

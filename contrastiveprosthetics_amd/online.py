@@ -422,6 +422,35 @@ class _EnrollMixin(_OnStream):
     # ------------------------------------------------------------------ head fine-tuning (cp_online_finetune_*)
     _shared_projection = False                                 # the multi-stream decoders: one projection for all streams
 
+    @staticmethod
+    def _labelled_slots(wl: np.ndarray, ids: np.ndarray, min_windows):
+        """what `finetune` and `readout.fit_projection` ask of a recording's window labels wl (M,), negative: not labelled ->
+        (keep: the labelled windows, slots: their index into ids, counts (K,)); a label outside ids or a class with
+        1..min_windows-1 windows is a ValueError"""
+        keep = np.nonzero(wl >= 0)[0]
+        if keep.size == 0:
+            raise ValueError("the recording has no labelled window: a window needs 11 samples in a row of one non-negative label")
+        new = np.setdiff1d(np.unique(wl[keep]), ids)
+        if new.size:
+            raise ValueError(f"labels hold class ids the decoder does not have: {new.tolist()} (enroll(add=True) adds a class)")
+        slots = np.searchsorted(ids, wl[keep])
+        counts = np.bincount(slots, minlength=ids.size)
+        short = [int(i) for i, c in zip(ids, counts) if 0 < c < int(min_windows)]
+        if short:
+            raise ValueError(f"classes {short} have fewer than min_windows={int(min_windows)} windows")
+        return keep, slots, counts
+
+    def _recording_tail_inputs(self, key, raw, keep: np.ndarray) -> torch.Tensor:
+        """u (len(keep), 512) in the compute dtype: the tail inputs of the windows `keep` of the recording raw, a stream of its
+        own read through the electrode map, embedded by the decoder's own encoder (cp_online_*tail_inputs)"""
+        n = int(keep.size)
+        w = recording_windows(raw, self.mean_std, self._b, self._a, self.phase, channel_map=self._map_of(key))
+        w = w[torch.as_tensor(keep, device=self.device)].contiguous()
+        u = torch.empty(n, 512, dtype=torch.float32 if self.dtype == "f32" else torch.bfloat16, device=self.device)
+        scratch = torch.empty(self.lib.cp_online_enroll_scratch_bytes(n, self._cfg.dtype), dtype=torch.uint8, device=self.device)
+        self._tail_inputs_call(key, w.data_ptr(), n, u.data_ptr(), scratch.data_ptr(), scratch.numel())
+        return u
+
     def _finetune(self, key, raw, labels, steps, lr, lr_rows, scale, anchor, balanced, train_projection, train_rows, min_windows,
                   return_loss):
         """`finetune` of the online decoders; a decoder supplies _enroll_view, _tail_inputs_call, _projection_read and
@@ -445,29 +474,14 @@ class _EnrollMixin(_OnStream):
         if int(min_windows) < 1:
             raise ValueError("min_windows must be at least 1")
         _check_raw(raw)
-        wl = window_labels(_sample_labels(labels, raw.shape[0]), self.phase)
-        keep = np.nonzero(wl >= 0)[0]
-        if keep.size == 0:
-            raise ValueError("the recording has no labelled window: a window needs 11 samples in a row of one non-negative label")
-        new = np.setdiff1d(np.unique(wl[keep]), ids)
-        if new.size:
-            raise ValueError(f"labels hold class ids the decoder does not have: {new.tolist()} (enroll(add=True) adds a class)")
-        slots = np.searchsorted(ids, wl[keep])
-        counts = np.bincount(slots, minlength=ids.size)
-        short = [int(i) for i, c in zip(ids, counts) if 0 < c < int(min_windows)]
-        if short:
-            raise ValueError(f"classes {short} have fewer than min_windows={int(min_windows)} windows")
+        keep, slots, counts = _EnrollMixin._labelled_slots(window_labels(_sample_labels(labels, raw.shape[0]), self.phase), ids, min_windows)
         out = {int(i): int(c) for i, c in zip(ids, counts)}
         flags = (_lib.CP_ONLINE_FINETUNE_PROJECTION if train_projection else 0) | (_lib.CP_ONLINE_FINETUNE_ROWS if train_rows else 0)
         if int(steps) == 0 or flags == 0:                      # nothing to train: the decoder stays as it is, bit for bit
             return (out, torch.zeros(0, dtype=torch.float64, device=self.device)) if return_loss else out
         # ---- everything is checked: from here on work is enqueued
         lib, n, k = self.lib, int(keep.size), int(ids.size)
-        w = recording_windows(raw, self.mean_std, self._b, self._a, self.phase, channel_map=self._map_of(key))
-        w = w[torch.as_tensor(keep, device=self.device)].contiguous()
-        u = torch.empty(n, 512, dtype=torch.float32 if self.dtype == "f32" else torch.bfloat16, device=self.device)
-        scratch = torch.empty(lib.cp_online_enroll_scratch_bytes(n, self._cfg.dtype), dtype=torch.uint8, device=self.device)
-        self._tail_inputs_call(key, w.data_ptr(), n, u.data_ptr(), scratch.data_ptr(), scratch.numel())
+        u = self._recording_tail_inputs(key, raw, keep)
         W, b = self._projection_read(key)
         E = table.to(torch.float32).contiguous()
         slots_dev = torch.as_tensor(slots.astype(np.int32), device=self.device)

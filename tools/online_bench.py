@@ -62,6 +62,10 @@ With --metric the user metric (metric.fit_metric, Metric.apply, pick_shrink and 
 the synthetic person of 41 classes (about 14,500 windows, 6 repetitions): the fit for 5 shrink values next to fit_reference on
 the host, the transform of the recording, pick_shrink over the 6 folds, and the per-push latency and kernels of
 OnlineDecoder.push with logits against MetricRows.push behind it at 1 and 25 windows.
+With --readout the closed-form head fit (readout.moments, solve, apply and pick_ridge_inputs, csrc/online_readout.cuh) is timed
+on the synthetic person of 41 classes (14,514 windows of 512 tail inputs, 6 repetitions): the moments of the 6 repetitions, the
+solve for 1, 8 and 48 plans, the apply of 24 projections and the ridge pick over 6 folds x 4 ridges, next to numpy's
+X.T @ diag(w) @ X and numpy.linalg.solve on the host.
 Each push is timed from the host with a synchronisation behind it (the latency a control loop sees); kernels per push are
 counted with torch.profiler over a few pushes.  One JSON line per case, and a table with --out.
 
@@ -82,6 +86,7 @@ counted with torch.profiler over a few pushes.  One JSON line per case, and a ta
     python tools/online_bench.py --holdout --iters 10 --out profiles/online_holdout.txt
     python tools/online_bench.py --prototypes --iters 200 --out profiles/online_prototypes.txt
     python tools/online_bench.py --metric --iters 200 --out profiles/online_metric.txt
+    python tools/online_bench.py --readout --iters 200 --out profiles/online_readout.txt
 """
 import argparse
 import json
@@ -157,7 +162,11 @@ def main():
                     "push with and without PostureRows behind it")
     ap.add_argument("--metric", action="store_true", help="the user metric: fit_metric against the definition, apply, pick_shrink, and "
                     "the push with and without MetricRows behind it")
+    ap.add_argument("--readout", action="store_true", help="the closed-form head fit: moments, solve for 1 / 8 / 48 plans and pick_ridge "
+                    "over 6 folds, next to numpy's X.T @ X and numpy.linalg.solve")
     a = ap.parse_args()
+    if a.readout:
+        return readout_main(a)
     if a.metric:
         return metric_main(a)
     if a.prototypes:
@@ -1249,6 +1258,70 @@ def metric_main(a):
                 if r["kind"] == "push":
                     f.write(f"{r['case']:<18} {r['samples']:>7} {r['windows']:>7} {r['table_rows']:>5} {r['median_us']:>10.1f} "
                             f"{r['p90_us']:>9.1f} {r['kernels_per_push']:>8.1f}\n")
+
+
+def readout_main(a):
+    """--readout: the closed-form head fit at the workload's shape (the synthetic person of readout.readout_recording: 41 classes,
+    6 repetitions of 59 windows, 14,514 windows of 512 tail inputs): the moments of the 6 repetitions, the solve for 1, 8 and 48
+    plans, the apply of 24 projections, and pick_ridge over the 6 folds and 4 ridges behind the encoder, next to what numpy takes
+    for X.T @ diag(w) @ X and numpy.linalg.solve of one plan (BLAS and LAPACK: not the definition's order, a yardstick only)."""
+    from contrastiveprosthetics_amd import readout as R
+    torch.manual_seed(0)
+    k, reps, seg = 41, 6, 59
+    p = R.readout_recording(k, reps, seg, seed=0)
+    u, slots, rep = p["u"], p["slots"], p["rep"]
+    m = int(u.shape[0])
+    u_d = torch.from_numpy(u).cuda()
+    emb0 = R.apply(u_d, p["W0"][None], p["b0"][None])[0].contiguous()
+    table = R.enrolled_rows_reference(emb0.cpu().numpy(), slots, k, np.ones(m, dtype=bool))
+    targets = R.unit_targets(table)
+    w = R.window_weights(slots, k, True, rep)
+    iters = max(a.iters // 20, 3)
+    rows = []
+
+    def row(case, fn, n_iter, reference_ms=None, **more):
+        fn()
+        med, p90 = time_pushes(fn, n_iter, 1)
+        r = dict(case=case, windows=m, device_ms=round(med / 1e3, 3), p90_ms=round(p90 / 1e3, 3), reference_ms=reference_ms, **more)
+        print(json.dumps(r), flush=True)
+        rows.append(r)
+
+    t0 = time.perf_counter()
+    xm = np.concatenate([u.astype(np.float64), np.ones((m, 1))], axis=1)
+    a_np = xm.T @ (w[:, None] * xm)
+    b_np = xm.T @ (w[:, None] * targets.astype(np.float64)[slots])
+    gram_ms = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    x_np = np.linalg.solve(a_np + 0.1 * np.diag(np.r_[np.ones(512), 0.0]), b_np)
+    solve_ms = (time.perf_counter() - t0) * 1e3
+    row(f"moments ({reps} groups)", lambda: R.moments(u_d, slots, w, targets, rep, reps), iters, round(gram_ms, 1))
+    G, Cm = R.moments(u_d, slots, w, targets, rep, reps)
+    full = (1 << reps) - 1
+    for n_plans in (1, 8, 48):
+        plans = [(full & ~(1 << (t % reps)) if n_plans > 1 else full, 0.1 * 2.0 ** (t // reps)) for t in range(n_plans)]
+        row(f"solve ({n_plans} plans)", lambda: R.solve(G, Cm, plans), iters, round(solve_ms * n_plans, 1))
+    W, b, status = R.solve(G, Cm, [(full, 0.1)])
+    dev = float(np.abs(W[0].cpu().numpy().T.astype(np.float64) - x_np[:512]).max() / np.abs(x_np[:512]).max())
+    plans = [(full & ~(1 << h), lam) for h in range(reps) for lam in R.RIDGES]
+    W24, b24, _ = R.solve(G, Cm, plans)
+    row("apply (24 projections)", lambda: R.apply(u_d, W24, b24), iters)
+    pick = R.pick_ridge_inputs(u_d, emb0, slots, np.arange(k), table, R.RIDGES)
+    row(f"pick_ridge ({pick['n_rep']} folds x {len(R.RIDGES)} ridges)", lambda: R.pick_ridge_inputs(u_d, emb0, slots, np.arange(k), table, R.RIDGES), 3,
+        raw_hit=pick["raw_hit"].tolist(), voted_hit=pick["voted_hit"].tolist(), n_cue=int(pick["n_cue"][0]), baseline=pick["baseline"], ridge=pick["ridge"])
+    if a.out:
+        name = torch.cuda.get_device_name(0)
+        with open(a.out, "w") as f:
+            f.write(f"# tools/online_bench.py --readout --iters {a.iters} on {name}\n")
+            f.write(f"# the synthetic person of readout.readout_recording({k}, {reps}, {seg}): {m} windows x 512 tail inputs, f32\n")
+            f.write("# wall time, host-synchronised (median, p90); reference_ms: numpy on the host for the same shape, X.T @ diag(w) @ X\n")
+            f.write("# (BLAS) beside the moments and numpy.linalg.solve (LAPACK) per plan beside the solve: not the definition's order\n")
+            f.write(f"{'call':<34} {'windows':>8} {'device_ms':>10} {'p90_ms':>9} {'reference_ms':>13}\n")
+            for r in rows:
+                ref_s = "-" if r["reference_ms"] is None else f"{r['reference_ms']:.1f}"
+                f.write(f"{r['case']:<34} {r['windows']:>8} {r['device_ms']:>10.3f} {r['p90_ms']:>9.3f} {ref_s:>13}\n")
+            f.write(f"# W of the plan (all repetitions, ridge 0.1) against numpy.linalg.solve: largest deviation {dev:.2e} of the largest entry\n")
+            f.write(f"# pick_ridge: held-out raw hits per ridge {list(R.RIDGES)} = {pick['raw_hit'].tolist()}, voted {pick['voted_hit'].tolist()} of "
+                    f"{int(pick['n_cue'][0])} cue windows; the unfitted projection with enrolled rows {pick['baseline']}; picked {pick['ridge']}\n")
 
 
 def _cued_logits(m, k, seed=0):
