@@ -202,6 +202,11 @@ CP_ONLINE_READOUT_MAX_GROUPS, CP_ONLINE_READOUT_MAX_PLANS, CP_ONLINE_READOUT_STA
 # what the four map sweep entries take behind their workspace: rms, n_windows, mean_std, map_src, map_fill, n_maps, n_classes,
 # expected_slot, chunk_rows, scratch, scratch_bytes, pred, voted, scores, class_hits, stream
 _MAP_SWEEP_TAIL = [_fp, C.c_int64, _fp, _fp, _fp, C.c_int32, C.c_int32, _fp, C.c_int64, _fp, C.c_size_t, _fp, _fp, _fp, _fp, _fp]
+# the *_proj entries (per-stream projections): cfg, n_streams, max_rows, ws, ws_bytes; then index, bank, bank_bytes (enrolment and
+# map sweep) or, for the pushes, the arguments of cp_online_multi_push_embed with bank, bank_bytes in front of the stream
+_MULTI_HEAD = [_P(cp_online_config), C.c_int32, C.c_int32, _fp, C.c_size_t]
+_STREAM_BANK = [C.c_int32, _fp, C.c_size_t]
+_PUSH_PROJ_TAIL = [_fp, _fp, C.c_int64, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp]
 
 SYMBOLS = {
     "cp_version": (C.c_int, []),
@@ -403,6 +408,17 @@ SYMBOLS = {
     "cp_online_readout_solve": (C.c_int, [_fp, _fp, C.c_int32, _P(C.c_uint32), _P(C.c_double), C.c_int32, _fp, _fp, _fp, _fp, C.c_size_t,
                                           _fp]),
     "cp_online_readout_apply": (C.c_int, [_fp, C.c_int32, C.c_int64, _fp, _fp, C.c_int32, _fp, _fp, C.c_size_t, _fp]),
+    "cp_online_projections_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "cp_online_projections_set": (C.c_int, [C.c_int32, _fp, C.c_size_t, C.c_int32, C.c_int32, _fp, _fp, _fp]),
+    "cp_online_projections_get": (C.c_int, [C.c_int32, _fp, C.c_size_t, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp]),
+    "cp_online_projections_clear": (C.c_int, [C.c_int32, _fp, C.c_size_t, C.c_int32, C.c_int32, _fp]),
+    "cp_online_multi_push_proj": (C.c_int, _MULTI_HEAD + _PUSH_PROJ_TAIL),
+    "cp_online_multi_adapt_push_proj": (C.c_int, _MULTI_HEAD + _PUSH_PROJ_TAIL),
+    "cp_online_multi_enroll_proj": (C.c_int, _MULTI_HEAD + _STREAM_BANK + [_fp, C.c_int64, _fp, C.c_int32, _fp, _fp, C.c_size_t, _fp]),
+    "cp_online_multi_adapt_enroll_proj": (C.c_int, _MULTI_HEAD + _STREAM_BANK + [_fp, C.c_int64, _fp, C.c_int32, _fp, _fp, C.c_size_t,
+                                                                                _fp]),
+    "cp_online_multi_map_sweep_proj": (C.c_int, _MULTI_HEAD + _STREAM_BANK + _MAP_SWEEP_TAIL),
+    "cp_online_multi_adapt_map_sweep_proj": (C.c_int, _MULTI_HEAD + _STREAM_BANK + _MAP_SWEEP_TAIL),
 }
 
 KERNEL_KINDS = ["gather", "prep", "conv1_fwd", "bn_finalize", "conv2_fwd", "fold", "fc_fwd", "dropout", "proj_fwd",

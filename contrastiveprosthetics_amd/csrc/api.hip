@@ -37,6 +37,7 @@
 #include "online_prototypes.cuh"
 #include "online_metric.cuh"
 #include "online_readout.cuh"
+#include "online_projections.cuh"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* what) {

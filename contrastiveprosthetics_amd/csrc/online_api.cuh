@@ -1,7 +1,7 @@
 // Host layer of the online decoders (include/cpnative.h, cp_online_*): workspace layout, argument checks, launch chains and
 // the extern "C" entries of the folded, adaptive, multi-stream and adaptive multi-stream decoders, class enrolment, head
 // fine-tuning, the command gate, the sequence decoder and its sweep, the grasp drive, the gate sweep, the subset sweep, the electrode-map sweep, cue realignment, prototype
-// tracking, held-out enrolment scoring, posture prototypes, the user metric and the closed-form head fit.  Host code only; api.hip includes it behind its own helpers (fail, CK, CKL) and encoder_api.cuh's (align256, fcK),
+// tracking, held-out enrolment scoring, posture prototypes, the user metric, the closed-form head fit and the per-stream projections of the multi-stream forms.  Host code only; api.hip includes it behind its own helpers (fail, CK, CKL) and encoder_api.cuh's (align256, fcK),
 // so the library stays one translation unit.  The four decoders share one workspace description (OlWS, ol_carve), one
 // parameter check, one set of front-end arguments, one folded chain and one unfolded weight copy; what an entry adds is its
 // name in the refusals and the kernels it launches.
@@ -200,6 +200,7 @@ struct OlMap {                           // an electrode map as the entries take
     const int32_t* src;
     const float* fill;
     float* emb;                          // rides along to the tail: where a push leaves z / |z| of its rows, (rows,16); NULL: nowhere
+    const void* bank;                    // rides along to the multi-stream tail: the streams' own projections (olp_check_bank); NULL: none
 };
 
 static int ol_launch_frontend(const cp_online_config* c, OlState* state, float* X, const float* raw, int64_t n, const float* mean_std,
@@ -268,13 +269,26 @@ static int ol_launch_tail(T, const cp_online_config* c, unsigned char* base, con
     return 0;
 }
 
+// slot 0 of a projection bank (csrc/online_projections.cuh) in compute type T
 template <typename T>
-static int olm_launch_tail(T, const cp_online_config* c, int n_streams, unsigned char* base, const OlWS& w, int32_t* pred, int32_t* voted,
-                           float* logits, float* emb, hipStream_t st) {
+static OlpSlot olp_slot0(T, const void* bank) {
+    const unsigned char* b = (const unsigned char*)bank;
+    return OlpSlot{b, (const float*)(b + (size_t)OLF_W * sizeof(T)), (const unsigned*)(b + (size_t)OLF_W * sizeof(T) + CP_D_E * 4)};
+}
+
+// bank: NULL, or the streams' own projections: workgroup s then takes slot s where it is set
+template <typename T>
+static int olm_launch_tail(T t, const cp_online_config* c, int n_streams, unsigned char* base, const OlWS& w, int32_t* pred, int32_t* voted,
+                           float* logits, float* emb, const void* bank, hipStream_t st) {
     OlmTailArgs ta{};
     ta.proj = ol_layer_args(base, w, OL_PROJ, nullptr, base + w.H1, nullptr);
     ta.states = (OlState*)(base + w.state); ta.meta = (const OlmMeta*)(base + w.meta);
     ta.vote = c->vote; ta.pred = pred; ta.voted = voted; ta.logits = logits; ta.emb = emb;
+    if (bank) {
+        hipLaunchKernelGGL((olp_tail_kernel<T>), dim3(n_streams), dim3(OL_THREADS), 0, st, ta, olp_slot0(t, bank));
+        CKL("olp_tail_kernel");
+        return 0;
+    }
     hipLaunchKernelGGL((olm_tail_kernel<T>), dim3(n_streams), dim3(OL_THREADS), 0, st, ta);
     CKL("olm_tail_kernel");
     return 0;
@@ -705,7 +719,7 @@ static int online_multi_push_t(T t, const cp_online_config* c, int n_streams, un
     };
     if (rows > 0)
         if (int e = ol_folded_chain(base, w, nullptr, (const float*)(base + w.X), base + w.H0, base + w.H1, layer)) return e;
-    return olm_launch_tail(t, c, n_streams, base, w, pred, voted, logits, map.emb, st);
+    return olm_launch_tail(t, c, n_streams, base, w, pred, voted, logits, map.emb, map.bank, st);
 }
 
 // cp_online_multi_push, cp_online_multi_adapt_push and their mapped forms
@@ -861,7 +875,7 @@ static int online_multi_adapt_push_t(T t, const cp_online_config* c, int n_strea
             CKL("olam_fc_kernel");
         }
     }
-    return olm_launch_tail(t, c, n_streams, base, w, pred, voted, logits, map.emb, st);
+    return olm_launch_tail(t, c, n_streams, base, w, pred, voted, logits, map.emb, map.bank, st);
 }
 
 extern "C" int cp_online_multi_adapt_push(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
@@ -979,25 +993,30 @@ static int ole_encode_chunk(T t, bool adaptive, unsigned char* base, const OlWS&
 // The caller's windows through the encoder chunk by chunk, each chunk's z / |z| added to acc
 template <typename T>
 static int online_enroll_t(T t, bool adaptive, unsigned char* base, const OlWS& w, const float* x, int64_t N, const int32_t* slots,
-                           int n_classes, double* acc, unsigned char* sc, const OleScratch& k, hipStream_t st) {
+                           int n_classes, double* acc, unsigned char* sc, const OleScratch& k, const OlpSlot* own, hipStream_t st) {
     for (int64_t r0 = 0; r0 < N; r0 += OL_MAXM) {
         const int m = (int)(N - r0 < OL_MAXM ? N - r0 : OL_MAXM);
         if (int e = ole_encode_chunk(t, adaptive, base, w, x + r0 * OL_C, m, sc, k, sc + k.H1, st)) return e;
         OleAccArgs a{};
         a.proj = ol_layer_args(base, w, OL_PROJ, nullptr, sc + k.H1, nullptr);
         a.slots = slots + r0; a.acc = acc; a.M = m; a.n_classes = n_classes;
+        if (own) {                                        // the stream's own projection where its slot is set
+            hipLaunchKernelGGL((olp_accumulate_kernel<T>), dim3(1), dim3(OL_THREADS), 0, st, a, *own);
+            CKL("olp_accumulate_kernel");
+            continue;
+        }
         hipLaunchKernelGGL((ole_accumulate_kernel<T>), dim3(1), dim3(OL_THREADS), 0, st, a);
         CKL("ole_accumulate_kernel");
     }
     return 0;
 }
 
-// the four accumulate entries: check_ws(&w) checks the entry's workspace arguments and gives the view of the stream to enrol
-// with.  n_windows == 0 is a valid empty call
+// the accumulate entries: check_ws(&w) checks the entry's workspace arguments and gives the view of the stream to enrol
+// with.  n_windows == 0 is a valid empty call.  own_slot (the *_proj entries): NULL, or the slot of the stream in its bank
 template <typename CheckWs>
 static int ole_enroll(const char* who, const cp_online_config* cfg, CheckWs check_ws, bool adaptive, void* ws, const float* windows,
                       int64_t n_windows, const int32_t* slots, int32_t n_classes, double* acc, void* scratch, size_t scratch_bytes,
-                      void* stream) {
+                      void* stream, const void* own_slot = nullptr) {
     OlWS w;
     if (int e = check_ws(&w)) return e;
     if (n_windows < 0 || n_windows > (int64_t)1 << 24) return ol_fail(CP_ERR_ARG, who, "n_windows outside 0..2**24");
@@ -1010,8 +1029,9 @@ static int ole_enroll(const char* who, const cp_online_config* cfg, CheckWs chec
     const OleScratch k = ole_carve(n_windows, cfg->dtype);
     if (scratch_bytes < k.total) return ol_fail(CP_ERR_WORKSPACE, who, "scratch too small");
     return ol_dispatch(cfg->dtype, [&](auto t) {
+        const OlpSlot own = own_slot ? olp_slot0(t, own_slot) : OlpSlot{};
         return online_enroll_t(t, adaptive, (unsigned char*)ws, w, windows, n_windows, slots, n_classes, acc, (unsigned char*)scratch, k,
-                               (hipStream_t)stream);
+                               own_slot ? &own : nullptr, (hipStream_t)stream);
     });
 }
 
@@ -1746,6 +1766,7 @@ struct OlMapSweep {                      // what the four sweep entries share
     int32_t *pred, *voted;               // (n_maps, M)
     int64_t* scores;
     int32_t* class_hits;
+    const void* own_slot;                // (the *_proj entries) NULL, or the slot of the stream in its projection bank
 };
 
 template <typename T>
@@ -1790,6 +1811,11 @@ static int online_map_sweep_t(T t, bool adaptive, const cp_online_config* c, uns
         ta.st = state; ta.slot = a.pred + r0; ta.rows = rows;
         int blocks;
         olm_row_blocks(rows, 1, &blocks, &ta.tiles_per_block);
+        if (a.own_slot) {
+            hipLaunchKernelGGL((olp_map_tail_kernel<T>), dim3(blocks), dim3(OL_THREADS), 0, st, ta, olp_slot0(t, a.own_slot));
+            CKL("olp_map_tail_kernel");
+            continue;
+        }
         hipLaunchKernelGGL((olmap_tail_kernel<T>), dim3(blocks), dim3(OL_THREADS), 0, st, ta);
         CKL("olmap_tail_kernel");
     }
@@ -2524,4 +2550,184 @@ extern "C" int cp_online_readout_apply(const void* u, int32_t dtype, int64_t n_r
         CKL("olr_apply_kernel");
         return 0;
     });
+}
+
+// ---------------------------------------------------------------------------------------
+// per-stream projections of the multi-stream decoders (csrc/online_projections.cuh): a bank of one slot per stream in a buffer
+// of the caller's, next to the workspace; the *_proj entries are the push, enrolment and map-sweep entries of the two
+// multi-stream forms with that bank.  bank == NULL: the entry they are named after, launch for launch
+// ---------------------------------------------------------------------------------------
+static size_t olp_bank_bytes(int32_t n_streams, int32_t dtype) {
+    return (size_t)n_streams * (dtype == CP_BF16 ? olp_slot_bytes<bf16_t>() : olp_slot_bytes<float>());
+}
+
+extern "C" size_t cp_online_projections_bytes(int32_t n_streams, int32_t dtype) {
+    if (n_streams < 1) n_streams = 1;
+    return olp_bank_bytes(n_streams, dtype);
+}
+
+// a bank an entry was given (bank != NULL) for n_streams streams in dtype
+static int olp_check_bank(const char* who, int32_t dtype, const void* bank, size_t bank_bytes, int32_t n_streams) {
+    if (dtype != CP_F32 && dtype != CP_BF16) return ol_fail(CP_ERR_ARG, who, "dtype must be CP_F32 or CP_BF16 (no 8-bit path)");
+    if (n_streams < 1 || n_streams > CP_ONLINE_MULTI_MAX_STREAMS) return ol_fail(CP_ERR_ARG, who, "n_streams outside 1..256");
+    if ((uintptr_t)bank % 256) return ol_fail(CP_ERR_ARG, who, "bank not 256-byte aligned");
+    if (bank_bytes < olp_bank_bytes(n_streams, dtype)) return ol_fail(CP_ERR_WORKSPACE, who, "bank too small");
+    return 0;
+}
+
+// the entries that work on the bank alone; out: slot `index` (index -1, clear only: slot 0)
+static int olp_check_slot(const char* who, int32_t dtype, void* bank, size_t bank_bytes, int32_t n_streams, int32_t index, bool all_ok,
+                          unsigned char** out) {
+    if (!bank) return ol_fail(CP_ERR_ARG, who, "bank is required");
+    if (int e = olp_check_bank(who, dtype, bank, bank_bytes, n_streams)) return e;
+    if (all_ok ? (index < -1 || index >= n_streams) : (index < 0 || index >= n_streams))
+        return ol_fail(CP_ERR_ARG, who, all_ok ? "stream index outside -1..n_streams-1" : "stream index outside 0..n_streams-1");
+    *out = (unsigned char*)bank + (size_t)(index < 0 ? 0 : index) * olp_bank_bytes(1, dtype);
+    return 0;
+}
+
+extern "C" int cp_online_projections_set(int32_t dtype, void* bank, size_t bank_bytes, int32_t n_streams, int32_t index, const float* W,
+                                         const float* b, void* stream) {
+    const char* who = "cp_online_projections_set";
+    unsigned char* slot;
+    if (int e = olp_check_slot(who, dtype, bank, bank_bytes, n_streams, index, false, &slot)) return e;
+    if (!W || !b) return ol_fail(CP_ERR_ARG, who, "W and b are required");
+    if ((uintptr_t)W % 4 || (uintptr_t)b % 4) return ol_fail(CP_ERR_ARG, who, "misaligned W or b");
+    return ol_dispatch(dtype, [&](auto t) {
+        using T = decltype(t);
+        const OlpSlot sl = olp_slot0(t, slot);
+        hipLaunchKernelGGL((olp_set_kernel<T>), dim3(OLF_W / 256), dim3(256), 0, (hipStream_t)stream, W, b, (T*)sl.w, (float*)sl.bias,
+                           (unsigned*)sl.set);
+        CKL("olp_set_kernel");
+        return 0;
+    });
+}
+
+extern "C" int cp_online_projections_get(int32_t dtype, const void* bank, size_t bank_bytes, int32_t n_streams, int32_t index, float* W,
+                                         float* b, int32_t* is_set, void* stream) {
+    const char* who = "cp_online_projections_get";
+    unsigned char* slot;
+    if (int e = olp_check_slot(who, dtype, (void*)bank, bank_bytes, n_streams, index, false, &slot)) return e;
+    if (!W || !b) return ol_fail(CP_ERR_ARG, who, "W and b are required");
+    if ((uintptr_t)W % 4 || (uintptr_t)b % 4 || (uintptr_t)is_set % 4) return ol_fail(CP_ERR_ARG, who, "misaligned W, b or is_set");
+    return ol_dispatch(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((olp_get_kernel<T>), dim3(OLF_W / 256), dim3(256), 0, (hipStream_t)stream, olp_slot0(t, slot), W, b, is_set);
+        CKL("olp_get_kernel");
+        return 0;
+    });
+}
+
+extern "C" int cp_online_projections_clear(int32_t dtype, void* bank, size_t bank_bytes, int32_t n_streams, int32_t index, void* stream) {
+    const char* who = "cp_online_projections_clear";
+    unsigned char* slot;
+    if (int e = olp_check_slot(who, dtype, bank, bank_bytes, n_streams, index, true, &slot)) return e;
+    return ol_dispatch(dtype, [&](auto t) {
+        hipLaunchKernelGGL(olp_clear_kernel, dim3(index < 0 ? n_streams : 1), dim3(64), 0, (hipStream_t)stream,
+                           (unsigned char*)olp_slot0(t, slot).set, olp_bank_bytes(1, dtype));
+        CKL("olp_clear_kernel");
+        return 0;
+    });
+}
+
+// the two pushes: cp_online_multi*_push_embed and a bank
+static int olp_push(const char* who, bool adaptive, const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
+                    size_t ws_bytes, const float* raw, const int32_t* counts, int64_t total_samples, int32_t total_windows,
+                    const float* mean_std, const OlMap& map, int32_t* pred, int32_t* voted, float* logits, float* windows,
+                    size_t bank_bytes, void* stream) {
+    if (map.bank) {
+        OlWS w;                                               // (the configuration first: the bank is sized by its dtype)
+        if (int e = olm_check(cfg, n_streams, max_rows, ws, ws_bytes, adaptive, &w)) return e;
+        if (int e = olp_check_bank(who, cfg->dtype, map.bank, bank_bytes, n_streams)) return e;
+    }
+    return olm_push(who, adaptive, cfg, n_streams, max_rows, ws, ws_bytes, raw, counts, total_samples, total_windows, mean_std, pred, voted,
+                    logits, windows, map, stream);
+}
+
+extern "C" int cp_online_multi_push_proj(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                         const float* raw, const int32_t* counts, int64_t total_samples, int32_t total_windows,
+                                         const float* mean_std, const int32_t* map_src, const float* map_fill, int32_t* pred,
+                                         int32_t* voted, float* logits, float* windows, float* embeddings, const void* bank,
+                                         size_t bank_bytes, void* stream) {
+    return olp_push("cp_online_multi_push_proj", false, cfg, n_streams, max_rows, ws, ws_bytes, raw, counts, total_samples, total_windows,
+                    mean_std, OlMap{map_src, map_fill, embeddings, bank}, pred, voted, logits, windows, bank_bytes, stream);
+}
+
+extern "C" int cp_online_multi_adapt_push_proj(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
+                                               size_t ws_bytes, const float* raw, const int32_t* counts, int64_t total_samples,
+                                               int32_t total_windows, const float* mean_std, const int32_t* map_src,
+                                               const float* map_fill, int32_t* pred, int32_t* voted, float* logits, float* windows,
+                                               float* embeddings, const void* bank, size_t bank_bytes, void* stream) {
+    return olp_push("cp_online_multi_adapt_push_proj", true, cfg, n_streams, max_rows, ws, ws_bytes, raw, counts, total_samples,
+                    total_windows, mean_std, OlMap{map_src, map_fill, embeddings, bank}, pred, voted, logits, windows, bank_bytes, stream);
+}
+
+// what the enrolment and sweep entries with a bank check of their workspace: the form's view of stream `index` (the folded form:
+// its class table; the weights are shared) and, with a bank, the stream's slot
+static int olp_check_stream(const char* who, bool adaptive, const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
+                            size_t ws_bytes, int32_t index, const void* bank, size_t bank_bytes, OlWS* w, const void** own_slot) {
+    if (int e = olm_check(cfg, n_streams, max_rows, ws, ws_bytes, adaptive, w)) return e;
+    if (int e = ol_check_index(who, index, n_streams)) return e;
+    if (bank)
+        if (int e = olp_check_bank(who, cfg->dtype, bank, bank_bytes, n_streams)) return e;
+    if (adaptive) *w = ol_stream(*w, index);
+    else w->state += (size_t)index * sizeof(OlState);
+    *own_slot = bank ? (const unsigned char*)bank + (size_t)index * olp_bank_bytes(1, cfg->dtype) : nullptr;
+    return 0;
+}
+
+static int olp_enroll(const char* who, bool adaptive, const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
+                      size_t ws_bytes, int32_t index, const void* bank, size_t bank_bytes, const float* windows, int64_t n_windows,
+                      const int32_t* slots, int32_t n_classes, double* acc, void* scratch, size_t scratch_bytes, void* stream) {
+    OlWS view;
+    const void* own = nullptr;
+    if (int e = olp_check_stream(who, adaptive, cfg, n_streams, max_rows, ws, ws_bytes, index, bank, bank_bytes, &view, &own)) return e;
+    return ole_enroll(who, cfg, [&](OlWS* w) { *w = view; return 0; }, adaptive, ws, windows, n_windows, slots, n_classes, acc, scratch,
+                      scratch_bytes, stream, own);
+}
+
+extern "C" int cp_online_multi_enroll_proj(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                           int32_t index, const void* bank, size_t bank_bytes, const float* windows, int64_t n_windows,
+                                           const int32_t* slots, int32_t n_classes, double* acc, void* scratch, size_t scratch_bytes,
+                                           void* stream) {
+    return olp_enroll("cp_online_multi_enroll_proj", false, cfg, n_streams, max_rows, ws, ws_bytes, index, bank, bank_bytes, windows,
+                      n_windows, slots, n_classes, acc, scratch, scratch_bytes, stream);
+}
+
+extern "C" int cp_online_multi_adapt_enroll_proj(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
+                                                 size_t ws_bytes, int32_t index, const void* bank, size_t bank_bytes, const float* windows,
+                                                 int64_t n_windows, const int32_t* slots, int32_t n_classes, double* acc, void* scratch,
+                                                 size_t scratch_bytes, void* stream) {
+    return olp_enroll("cp_online_multi_adapt_enroll_proj", true, cfg, n_streams, max_rows, ws, ws_bytes, index, bank, bank_bytes, windows,
+                      n_windows, slots, n_classes, acc, scratch, scratch_bytes, stream);
+}
+
+static int olp_map_sweep(const char* who, bool adaptive, const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
+                         size_t ws_bytes, int32_t index, const void* bank, size_t bank_bytes, OlMapSweep a, void* stream) {
+    OlWS view;
+    if (int e = olp_check_stream(who, adaptive, cfg, n_streams, max_rows, ws, ws_bytes, index, bank, bank_bytes, &view, &a.own_slot)) return e;
+    return olmap_sweep(who, cfg, [&](OlWS* w) { *w = view; return 0; }, adaptive, ws, a, stream);
+}
+
+extern "C" int cp_online_multi_map_sweep_proj(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                              int32_t index, const void* bank, size_t bank_bytes, const float* rms, int64_t n_windows,
+                                              const float* mean_std, const int32_t* map_src, const float* map_fill, int32_t n_maps,
+                                              int32_t n_classes, const int32_t* expected_slot, int64_t chunk_rows, void* scratch,
+                                              size_t scratch_bytes, int32_t* pred, int32_t* voted, int64_t* scores, int32_t* class_hits,
+                                              void* stream) {
+    const OlMapSweep a{rms, n_windows, mean_std, map_src, map_fill, n_maps, n_classes, expected_slot, chunk_rows, scratch, scratch_bytes,
+                       pred, voted, scores, class_hits, nullptr};
+    return olp_map_sweep("cp_online_multi_map_sweep_proj", false, cfg, n_streams, max_rows, ws, ws_bytes, index, bank, bank_bytes, a, stream);
+}
+
+extern "C" int cp_online_multi_adapt_map_sweep_proj(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws,
+                                                    size_t ws_bytes, int32_t index, const void* bank, size_t bank_bytes, const float* rms,
+                                                    int64_t n_windows, const float* mean_std, const int32_t* map_src,
+                                                    const float* map_fill, int32_t n_maps, int32_t n_classes,
+                                                    const int32_t* expected_slot, int64_t chunk_rows, void* scratch, size_t scratch_bytes,
+                                                    int32_t* pred, int32_t* voted, int64_t* scores, int32_t* class_hits, void* stream) {
+    const OlMapSweep a{rms, n_windows, mean_std, map_src, map_fill, n_maps, n_classes, expected_slot, chunk_rows, scratch, scratch_bytes,
+                       pred, voted, scores, class_hits, nullptr};
+    return olp_map_sweep("cp_online_multi_adapt_map_sweep_proj", true, cfg, n_streams, max_rows, ws, ws_bytes, index, bank, bank_bytes, a,
+                         stream);
 }

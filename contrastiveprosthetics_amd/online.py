@@ -45,7 +45,12 @@ the best.
 `finetune` is the gradient step of the personalisation chain (calibrate -> enroll -> fine-tune -> sweep the gate): the
 projection and the class rows behind the shared encoder are trained on the device with the model's own loss on the user's cued
 recording (cp_online_finetune_*, csrc/online_finetune.cuh; `finetune.finetune_reference` is the definition), and
-`projection` / `set_projection` / `reset_projection` store, restore and drop the user's head.
+`projection` / `set_projection` / `reset_projection` store, restore and drop the user's head.  The multi-stream decoders share
+one projection among their streams unless they are built with `stream_projections=True`: then each stream has a slot of its
+own in a projection bank next to the workspace (cp_online_projections_*, the *_proj entries, csrc/online_projections.cuh),
+`set_projection(stream, W, b)`, `finetune(stream, ..., train_projection=True)` and `Readout.install(decoder, stream=)` fill
+it, and push, `enroll` and `score_channel_maps` of that stream decode with it, bit for bit as the stream's own
+`OnlineDecoder` with the same projection set; the launches per push do not change.
 
 `realign.realign_cues` stands in front of that chain: a user's cue runs ahead of the movement, and it moves the labels of a
 cued recording onto the onset and offset the sEMG itself shows, on the device and without the model (cp_online_realign*,
@@ -195,6 +200,16 @@ def _map_windows(w: torch.Tensor, m) -> torch.Tensor:
     if masked.size:
         w[:, torch.as_tensor(masked, device=w.device)] = torch.as_tensor(m[1][masked], device=w.device)
     return w
+
+
+def _check_projection(W, b):
+    """(W (16, 512), b (16,)) as f32 tensors where they are; a wrong shape or a value that is not finite is a ValueError"""
+    W, b = torch.as_tensor(W, dtype=torch.float32), torch.as_tensor(b, dtype=torch.float32)
+    if tuple(W.shape) != (CP_D_E, 512) or tuple(b.shape) != (CP_D_E,):
+        raise ValueError(f"W must be ({CP_D_E}, 512) and b ({CP_D_E},)")
+    if not (bool(torch.isfinite(W).all()) and bool(torch.isfinite(b).all())):
+        raise ValueError("W and b must be finite")
+    return W, b
 
 
 class _OnStream:
@@ -888,7 +903,8 @@ class _MultiStreamBase(_EnrollMixin):
     _WHO = "MultiStreamDecoder"
     _ENTRY = "cp_online_multi"
 
-    def _setup(self, e: Engine, mean, std, n_streams, vote, dtype, phase, max_windows_per_push, max_rows, b, a):
+    def _setup(self, e: Engine, mean, std, n_streams, vote, dtype, phase, max_windows_per_push, max_rows, b, a,
+               stream_projections: bool = False):
         dtype = _check_settings(e, dtype, vote, phase, max_windows_per_push, self._WHO)
         if not 1 <= int(n_streams) <= MAX_STREAMS:
             raise ValueError(f"n_streams must lie in 1..{MAX_STREAMS}")
@@ -922,10 +938,24 @@ class _MultiStreamBase(_EnrollMixin):
         self._maps = [None] * self.n_streams               # electrode maps: (src, fill) numpy per stream, None: the identity
         self._map_src = torch.arange(EMG_DIM, dtype=torch.int32, device=self.device).repeat(self.n_streams, 1).contiguous()
         self._map_fill = torch.zeros(self.n_streams, EMG_DIM, dtype=torch.float32, device=self.device)
+        self.stream_projections = bool(stream_projections)
+        self._bank = None                                  # the streams' own projections (cp_online_projections_*): zeros, none set
+        if self.stream_projections:
+            self._shared_projection = False                # (this decoder's: the class attribute stays)
+            self._bank = torch.zeros(self.lib.cp_online_projections_bytes(self.n_streams, self._cfg.dtype), dtype=torch.uint8,
+                                     device=self.device)
+            self._own_projection = np.zeros(self.n_streams, dtype=bool)
 
     # ------------------------------------------------------------------ helpers
     def _args(self):
         return (C.byref(self._cfg), self.n_streams, self.max_rows, self.ws.data_ptr(), self.ws.numel())
+
+    def _bank_args(self):
+        return (self._bank.data_ptr(), self._bank.numel())
+
+    def _slot_args(self, s: int):
+        """what the cp_online_projections_* entries take in front: dtype, bank, bank_bytes, n_streams, index"""
+        return (self._cfg.dtype, *self._bank_args(), self.n_streams, s)
 
     def _index(self, stream) -> int:
         if isinstance(stream, bool) or not isinstance(stream, (int, np.integer)) or not 0 <= int(stream) < self.n_streams:
@@ -1008,6 +1038,13 @@ class _MultiStreamBase(_EnrollMixin):
         return self.class_ids[s].numpy().astype(np.int64), self._tables[s][0], self._enroll_calibrated(s)
 
     def _enroll_call(self, s, *args):
+        if self._bank is not None:                             # with the projection stream s decodes with
+            name = self._ENTRY + "_enroll_proj"
+            _lib.check(getattr(self.lib, name)(*self._args(), s, *self._bank_args(), *args, self._stream()), name)
+            return
+        self._enroll_call_shared(s, *args)
+
+    def _enroll_call_shared(self, s, *args):
         _lib.check(self.lib.cp_online_multi_enroll(*self._args(), *args, self._stream()), "cp_online_multi_enroll")
 
     def _enroll_install(self, s, table, ids):
@@ -1020,7 +1057,10 @@ class _MultiStreamBase(_EnrollMixin):
                  train_rows: bool = True, min_windows: int = 25, return_loss: bool = False):
         """`OnlineDecoder.finetune` for one stream's class rows: its class table becomes, bit for bit, the one its own
         `OnlineDecoder.finetune(train_projection=False)` gets from the same call; no other stream's table, state or statistics
-        change.  The projection is shared by all streams, so train_projection=True is a ValueError."""
+        change.  Without `stream_projections=True` the projection is shared by all streams, so train_projection=True is a
+        ValueError.  With it the stream's own head is trained as `OnlineDecoder.finetune` trains one: from `projection(stream)`
+        and the stream's rows, into the stream's slot (`set_projection(stream, W, b)`) and its class table, bit for bit what
+        the stream's own `OnlineDecoder` gets; nothing of any other stream changes."""
         return self._finetune(self._index(stream), raw, labels, steps, lr, lr_rows, scale, anchor, balanced, bool(train_projection),
                               bool(train_rows), min_windows, return_loss)
 
@@ -1030,13 +1070,60 @@ class _MultiStreamBase(_EnrollMixin):
     def _projection_read(self, s):
         W = torch.empty(CP_D_E, 512, dtype=torch.float32, device=self.device)
         b = torch.empty(CP_D_E, dtype=torch.float32, device=self.device)
+        if self._bank is not None and self._own_projection[s]:
+            _lib.check(self.lib.cp_online_projections_get(*self._slot_args(s), W.data_ptr(), b.data_ptr(), None, self._stream()),
+                       "cp_online_projections_get")
+            return W, b
         name = self._ENTRY + "_projection"
         _lib.check(getattr(self.lib, name)(*self._args(), W.data_ptr(), b.data_ptr(), self._stream()), name)
         return W, b
 
     def _finetune_install(self, s, W, b, E, ids):
+        if W is not None:                                      # (train_projection: only with stream_projections=True)
+            self.set_projection(s, W, b)
         if E is not None:
             self.set_classes(s, table=E, ids=ids)
+
+    # ------------------------------------------------------------------ per-stream projections (stream_projections=True)
+    def _need_bank(self, what: str):
+        if self._bank is None:
+            raise _lib.CpNativeError(f"{what}: the streams of this decoder share one projection; build it with "
+                                     "stream_projections=True to give each stream a slot of its own")
+
+    def set_projection(self, stream: int, W, b):
+        """Install a user's projection for one stream, as `OnlineDecoder.set_projection`: W (16, 512) and b (16,) finite f32
+        (rounded to the compute dtype once, here).  It lives in the stream's slot of the decoder's projection bank, outside
+        the workspace: `refresh()` keeps it, `reset_projection(stream)` drops it, and from the next push on the stream's
+        outputs equal bit for bit those of its own `OnlineDecoder` with the same projection set.  The stream's state, vote ring
+        and classes, and everything of the other streams, stay.  Needs `stream_projections=True`."""
+        self._need_bank("set_projection")
+        s = self._index(stream)
+        W, b = _check_projection(W, b)
+        W, b = W.to(self.device).contiguous(), b.to(self.device).contiguous()
+        _lib.check(self.lib.cp_online_projections_set(*self._slot_args(s), W.data_ptr(), b.data_ptr(), self._stream()),
+                   "cp_online_projections_set")
+        self._own_projection[s] = True
+
+    def projection(self, stream: int):
+        """(W (16, 512) f32, b (16,) f32) on the GPU: the projection the tail multiplies stream `stream`'s rows by -- its own
+        if one is set, else the one all streams share --, widened from the compute dtype, as `OnlineDecoder.projection`."""
+        return self._projection_read(self._index(stream))
+
+    def has_projection(self, stream: int) -> bool:
+        """whether the stream decodes with a projection of its own (always False without `stream_projections=True`)"""
+        s = self._index(stream)
+        return bool(self._bank is not None and self._own_projection[s])
+
+    def reset_projection(self, stream=None):
+        """Drop the own projection of one stream, or of all (stream=None): from the next push on they decode with the shared
+        projection again, bit for bit as streams that never had one.  Needs `stream_projections=True`."""
+        self._need_bank("reset_projection")
+        s = -1 if stream is None else self._index(stream)
+        _lib.check(self.lib.cp_online_projections_clear(*self._slot_args(s), self._stream()), "cp_online_projections_clear")
+        if s < 0:
+            self._own_projection[:] = False
+        else:
+            self._own_projection[s] = False
 
     def reset(self, streams=None):
         """Start new streams: filter, RMS history, sample count and vote ring of the listed streams (default: all) to zero;
@@ -1130,7 +1217,10 @@ class _MultiStreamBase(_EnrollMixin):
             emb = torch.empty(R, CP_D_E, dtype=torch.float32, device=self.device) if return_embeddings else None
             if piece.shape[0]:
                 cmap = (self._map_src.data_ptr(), self._map_fill.data_ptr()) if any(m is not None for m in self._maps) else ()
-                if return_embeddings:                          # the mapped entry with one more destination; no map: NULL, NULL
+                if self._bank is not None:                     # the embed entry with the bank; no map, no embeddings: NULL
+                    name, cmap = "_push_proj", cmap or (None, None)
+                    tail = (emb.data_ptr() if emb is not None else None, *self._bank_args())
+                elif return_embeddings:                        # the mapped entry with one more destination; no map: NULL, NULL
                     name, cmap, tail = "_push_embed", cmap or (None, None), (emb.data_ptr(),)
                 else:
                     name, tail = "_push_mapped" if cmap else "_push", ()
@@ -1161,11 +1251,18 @@ class MultiStreamDecoder(_MultiStreamBase):
     those of an `OnlineDecoder` with the same settings and class table fed the same chunks of that stream alone.
 
     max_windows_per_push bounds the windows of one stream per launch chain, max_rows (default min(n_streams *
-    max_windows_per_push, 4096)) the windows of all streams; larger pushes are split on the host.  Stock BatchNorm only: the
+    max_windows_per_push, 4096)) the windows of all streams; larger pushes are split on the host.  stream_projections=True
+    gives every stream a slot for a projection of its own (`set_projection(stream, W, b)`, `projection`, `has_projection`,
+    `reset_projection`; `finetune(stream, ..., train_projection=True)` and `Readout.install(decoder, stream=)` fill it): a
+    stream with one decodes, enrols and sweeps maps bit for bit as its own `OnlineDecoder` with `set_projection(W, b)`, a
+    stream without one as before, still in ten launches per push; the stages behind the decoder (`CommandGate`,
+    `SequenceGate`, `GraspDrive`, `PostureRows`, `MetricRows`, `PrototypeTracker`, `embed_recording`,
+    `holdout.score_enrolment`, `pick_ridge(..., stream=)`) read what a push emits and need nothing.  Stock BatchNorm only: the
     adaptive form (adapt=) and AdaBN models are refused, as is fp8 (`AdaptiveMultiStreamDecoder` is the adaptive form)."""
 
     def __init__(self, model_or_engine, mean, std, n_streams: int, vote: int = VOTE, dtype: Optional[str] = None, phase: int = 0,
-                 max_windows_per_push: int = 256, max_rows: Optional[int] = None, b=None, a=None, adapt: Optional[float] = None):
+                 max_windows_per_push: int = 256, max_rows: Optional[int] = None, b=None, a=None, adapt: Optional[float] = None,
+                 stream_projections: bool = False):
         e = _engine_of(model_or_engine, "MultiStreamDecoder")
         if adapt is not None:
             raise _lib.CpNativeError("MultiStreamDecoder has no adaptive form (adapt=): decode adapting streams with "
@@ -1173,7 +1270,7 @@ class MultiStreamDecoder(_MultiStreamBase):
         if e.adabn:
             raise _lib.CpNativeError("MultiStreamDecoder needs stock BatchNorm with running statistics: an AdaBN model normalises "
                                      "with the statistics of its batch (AdaptiveMultiStreamDecoder calibrates them)")
-        self._setup(e, mean, std, n_streams, vote, dtype, phase, max_windows_per_push, max_rows, b, a)
+        self._setup(e, mean, std, n_streams, vote, dtype, phase, max_windows_per_push, max_rows, b, a, stream_projections)
         self.refresh()
 
     def refresh(self):
@@ -1193,7 +1290,8 @@ class AdaptiveMultiStreamDecoder(_MultiStreamBase):
     `MultiStreamDecoder` keeps, float64 statistics of the 9 BatchNorms and its own alpha in [0, 1) (a float for all streams,
     or one per stream; 0 freezes).  A push is one chain of twelve launches for all streams, and every stream's pred, voted,
     logits, windows and `bn_statistics` equal bit for bit those of an `OnlineDecoder(adapt=alpha_s)` with the same settings,
-    class table and calibration fed the same chunks of that stream alone.
+    class table and calibration fed the same chunks of that stream alone.  stream_projections=True as on `MultiStreamDecoder`:
+    a slot per stream for a projection of its own, the twelve launches unchanged.
 
     Stock models start every stream at the running statistics; under an AdaBN model every stream starts uncalibrated and
     takes samples only after `calibrate(stream, raw)`.  fp8, and glove class rows under an AdaBN model, are refused."""
@@ -1201,7 +1299,8 @@ class AdaptiveMultiStreamDecoder(_MultiStreamBase):
     _ENTRY = "cp_online_multi_adapt"
 
     def __init__(self, model_or_engine, mean, std, n_streams: int, alpha, vote: int = VOTE, dtype: Optional[str] = None,
-                 phase: int = 0, max_windows_per_push: int = 256, max_rows: Optional[int] = None, b=None, a=None):
+                 phase: int = 0, max_windows_per_push: int = 256, max_rows: Optional[int] = None, b=None, a=None,
+                 stream_projections: bool = False):
         e = _engine_of(model_or_engine, "AdaptiveMultiStreamDecoder")
         if not 1 <= int(n_streams) <= MAX_STREAMS:
             raise ValueError(f"n_streams must lie in 1..{MAX_STREAMS}")
@@ -1211,7 +1310,7 @@ class AdaptiveMultiStreamDecoder(_MultiStreamBase):
             raise ValueError(f"alpha: one value, or one per stream ({int(n_streams)})")
         for x in alphas:
             self._check_alpha(x)
-        self._setup(e, mean, std, n_streams, vote, dtype, phase, max_windows_per_push, max_rows, b, a)
+        self._setup(e, mean, std, n_streams, vote, dtype, phase, max_windows_per_push, max_rows, b, a, stream_projections)
         self.alpha = alphas
         self.calibrated = np.full(self.n_streams, not e.adabn)     # the running statistics are a calibration
         self._prepared = False
@@ -1232,7 +1331,7 @@ class AdaptiveMultiStreamDecoder(_MultiStreamBase):
     def _enroll_calibrated(self, s: int) -> bool:
         return bool(self.calibrated[s])
 
-    def _enroll_call(self, s, *args):
+    def _enroll_call_shared(self, s, *args):
         _lib.check(self.lib.cp_online_multi_adapt_enroll(*self._args(), s, *args, self._stream()), "cp_online_multi_adapt_enroll")
 
     def _tail_inputs_call(self, s, *args):
@@ -2478,8 +2577,11 @@ def _sweep_target(decoder, stream):
         s = decoder._index(stream)
         if not decoder._has_table[s]:
             raise _lib.CpNativeError(f"stream {s} has no class table: set_classes({s}, ...) first")
-        return (decoder._ENTRY + "_map_sweep", (*decoder._args(), s), decoder.class_ids[s].numpy().astype(np.int64),
-                decoder._ENTRY.endswith("adapt"), decoder._enroll_calibrated(s))
+        name, lead = decoder._ENTRY + "_map_sweep", (*decoder._args(), s)
+        if decoder._bank is not None:                          # the tail with the projection stream s decodes with
+            name, lead = name + "_proj", (*lead, *decoder._bank_args())
+        return (name, lead, decoder.class_ids[s].numpy().astype(np.int64), decoder._ENTRY.endswith("adapt"),
+                decoder._enroll_calibrated(s))
     if isinstance(decoder, OnlineDecoder):
         if stream is not None:
             raise ValueError("stream= goes with a multi-stream decoder")

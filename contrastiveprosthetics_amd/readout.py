@@ -459,15 +459,25 @@ class Readout:
                              f"definite (pivot {int(self.status[int(index)]) - 1}); raise the ridge")
         return int(index)
 
-    def install(self, decoder, index: int = 0):
+    def install(self, decoder, index: int = 0, stream: Optional[int] = None):
         """`decoder.set_projection(W[index], b[index])` on an `OnlineDecoder` (folded or adaptive): `refresh()` keeps it,
-        `reset_projection()` drops it.  The multi-stream decoders share one projection among their streams and are refused.
+        `reset_projection()` drops it.  On a multi-stream decoder built with `stream_projections=True`, `stream=` names the
+        stream whose slot takes it (`decoder.set_projection(stream, W[index], b[index])`); without that option the streams
+        share one projection and the decoder is refused, as is one with the option but no stream=.
         A plan whose status is not 0 is a ValueError.  Enrol again afterwards (`enroll_reset()`, `enroll`): class rows belong
         to the space they were made in, and the fitted space only approximates the rows it was regressed onto -- at a large
         ridge it shrinks towards the bias and the old rows fit it badly."""
-        if isinstance(getattr(decoder, "class_ids", None), (list, tuple)) or not hasattr(decoder, "set_projection"):
+        multi = isinstance(getattr(decoder, "class_ids", None), (list, tuple))
+        if multi and stream is not None and getattr(decoder, "stream_projections", False):
+            s = decoder._index(stream)
+            i = self._index(index)
+            decoder.set_projection(s, self.W[i], self.b[i])
+            return
+        if multi or not hasattr(decoder, "set_projection"):
             raise _lib.CpNativeError("the streams of a multi-stream decoder share one projection: a user's projection cannot be "
                                      "installed for one of them (fit on a stream, install on that user's OnlineDecoder)")
+        if stream is not None:
+            raise ValueError("stream= goes with a multi-stream decoder")
         i = self._index(index)
         decoder.set_projection(self.W[i], self.b[i])
 

@@ -1051,7 +1051,7 @@ int cp_online_finetune_read(void* state, size_t state_bytes, int64_t n_windows, 
                             double* grad_out, void* stream);
 /* W (16,512), b (16) f32 on the device -> the tail's weights in T and its bias (one launch); and back, widened.  A workspace
  * that never sees a set call is byte for byte what cp_online_*prepare left.  The multi-stream forms share one projection
- * among their streams: it is read, not set. */
+ * among their streams: it is read, not set (a stream's own goes into a projection bank: "per-stream projections" below). */
 int cp_online_set_projection(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* W, const float* b, void* stream);
 int cp_online_adapt_set_projection(const cp_online_config* cfg, void* ws, size_t ws_bytes, const float* W, const float* b,
                                    void* stream);
@@ -1790,6 +1790,69 @@ int cp_online_readout_solve(const double* G, const double* C, int32_t n_groups, 
                             int32_t n_plans, float* W, float* b, int32_t* status, void* scratch, size_t scratch_bytes, void* stream);
 int cp_online_readout_apply(const void* u, int32_t dtype, int64_t n_rows, const float* W, const float* b, int32_t n_plans, float* out,
                             void* scratch, size_t scratch_bytes, void* stream);
+
+/* ---- per-stream projections: each stream of the multi-stream decoders with a projection of its own ---------------------------
+ * The workspace of the multi-stream forms holds one projection for all streams (cp_online_multi*_projection reads it).  A
+ * projection bank gives every stream a slot for a user's own (head fine-tuning, closed-form head fit): a device buffer of the
+ * caller's, 256-byte aligned, separate from the workspace (whose size and layout do not change), of
+ *   cp_online_projections_bytes(n_streams, dtype) = n_streams * (16 * 512 * sizeof(T) + 256) bytes, T = float or bf16.
+ * Slot s starts s * (16 * 512 * sizeof(T) + 256) bytes in: W (16,512) in T, rounded exactly as cp_online_*set_projection rounds
+ * it; the 16 f32 biases; one "set" word.  A zeroed bank holds no projection (zero it once after allocating).  A stream whose
+ * slot is not set decodes with the workspace's projection, and the choice is made on the device: cp_online_multi*_prepare
+ * (a refresh) needs no bank call, a user's projection survives it, and an unset stream's outputs are in every bit those of the
+ * entries without a bank.  A set stream's outputs are in every bit those of a single-stream decoder of the same form with the
+ * same W, b installed (cp_online_*set_projection).
+ *
+ * - set: W (16,512), b (16) f32 on the device into slot `index` (one launch); get: the slot widened into W, b, and is_set (NULL,
+ *   or one int32 on the device: 1 if the slot is set, else 0; an unset slot's W and b are whatever the bank holds); clear: the
+ *   set word of slot `index`, or of every slot (index == -1), to zero (one launch).
+ * - cp_online_multi_push_proj / cp_online_multi_adapt_push_proj: cp_online_multi_push_embed / cp_online_multi_adapt_push_embed
+ *   with `bank`, `bank_bytes` (the bank of the same n_streams and cfg.dtype); workgroup s of the tail launch takes slot s.  The
+ *   launches per push do not change.  bank == NULL is the _push_embed entry, launch for launch.
+ * - cp_online_multi_enroll_proj / cp_online_multi_adapt_enroll_proj: cp_online_multi_enroll / cp_online_multi_adapt_enroll for
+ *   stream `index` with its slot: the accumulated directions are those of the projection the stream decodes with.
+ * - cp_online_multi_map_sweep_proj / cp_online_multi_adapt_map_sweep_proj: cp_online_multi_map_sweep /
+ *   cp_online_multi_adapt_map_sweep (the push's own tail) for stream `index` with its slot.
+ *   In both pairs bank == NULL is the entry they are named after.  cp_online_*tail_inputs are upstream of the projection and
+ *   take no bank.
+ *
+ * The host checks before anything is enqueued: CP_ERR_ARG (a NULL bank where one is required, a misaligned one, dtype, n_streams
+ * outside 1..256, a stream index outside 0..n_streams-1) or CP_ERR_WORKSPACE (bank_bytes too small), with a cp_last_error that
+ * names the entry.  The entries never allocate, never synchronise and keep no state. */
+size_t cp_online_projections_bytes(int32_t n_streams, int32_t dtype);
+int cp_online_projections_set(int32_t dtype, void* bank, size_t bank_bytes, int32_t n_streams, int32_t index, const float* W,
+                              const float* b, void* stream);
+int cp_online_projections_get(int32_t dtype, const void* bank, size_t bank_bytes, int32_t n_streams, int32_t index, float* W, float* b,
+                              int32_t* is_set, void* stream);
+int cp_online_projections_clear(int32_t dtype, void* bank, size_t bank_bytes, int32_t n_streams, int32_t index, void* stream);
+int cp_online_multi_push_proj(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                              const float* raw, const int32_t* counts, int64_t total_samples, int32_t total_windows,
+                              const float* mean_std, const int32_t* map_src, const float* map_fill, int32_t* pred, int32_t* voted,
+                              float* logits, float* windows, float* embeddings, const void* bank, size_t bank_bytes, void* stream);
+int cp_online_multi_adapt_push_proj(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                    const float* raw, const int32_t* counts, int64_t total_samples, int32_t total_windows,
+                                    const float* mean_std, const int32_t* map_src, const float* map_fill, int32_t* pred,
+                                    int32_t* voted, float* logits, float* windows, float* embeddings, const void* bank,
+                                    size_t bank_bytes, void* stream);
+int cp_online_multi_enroll_proj(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                int32_t index, const void* bank, size_t bank_bytes, const float* windows, int64_t n_windows,
+                                const int32_t* slots, int32_t n_classes, double* acc, void* scratch, size_t scratch_bytes, void* stream);
+int cp_online_multi_adapt_enroll_proj(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                      int32_t index, const void* bank, size_t bank_bytes, const float* windows, int64_t n_windows,
+                                      const int32_t* slots, int32_t n_classes, double* acc, void* scratch, size_t scratch_bytes,
+                                      void* stream);
+int cp_online_multi_map_sweep_proj(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                   int32_t index, const void* bank, size_t bank_bytes, const float* rms, int64_t n_windows,
+                                   const float* mean_std, const int32_t* map_src, const float* map_fill, int32_t n_maps,
+                                   int32_t n_classes, const int32_t* expected_slot, int64_t chunk_rows, void* scratch,
+                                   size_t scratch_bytes, int32_t* pred, int32_t* voted, int64_t* scores, int32_t* class_hits,
+                                   void* stream);
+int cp_online_multi_adapt_map_sweep_proj(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, void* ws, size_t ws_bytes,
+                                         int32_t index, const void* bank, size_t bank_bytes, const float* rms, int64_t n_windows,
+                                         const float* mean_std, const int32_t* map_src, const float* map_fill, int32_t n_maps,
+                                         int32_t n_classes, const int32_t* expected_slot, int64_t chunk_rows, void* scratch,
+                                         size_t scratch_bytes, int32_t* pred, int32_t* voted, int64_t* scores, int32_t* class_hits,
+                                         void* stream);
 
 #ifdef __cplusplus
 }

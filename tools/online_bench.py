@@ -66,6 +66,10 @@ With --readout the closed-form head fit (readout.moments, solve, apply and pick_
 on the synthetic person of 41 classes (14,514 windows of 512 tail inputs, 6 repetitions): the moments of the 6 repetitions, the
 solve for 1, 8 and 48 plans, the apply of 24 projections and the ridge pick over 6 folds x 4 ridges, next to numpy's
 X.T @ diag(w) @ X and numpy.linalg.solve on the host.
+With --stream-projections the pushes of MultiStreamDecoder and AdaptiveMultiStreamDecoder built with stream_projections=True
+(csrc/online_projections.cuh) are timed with no slot set and with every slot set, next to the same decoder built without the
+option, alternating in the same run: 1, 16 and 256 streams of 1 and 25 windows each in f32 and bf16, with the run-to-run spread
+of the option-off medians and the kernels per push of all three.
 Each push is timed from the host with a synchronisation behind it (the latency a control loop sees); kernels per push are
 counted with torch.profiler over a few pushes.  One JSON line per case, and a table with --out.
 
@@ -87,6 +91,7 @@ counted with torch.profiler over a few pushes.  One JSON line per case, and a ta
     python tools/online_bench.py --prototypes --iters 200 --out profiles/online_prototypes.txt
     python tools/online_bench.py --metric --iters 200 --out profiles/online_metric.txt
     python tools/online_bench.py --readout --iters 200 --out profiles/online_readout.txt
+    python tools/online_bench.py --stream-projections --iters 50 --out profiles/online_stream_projections.txt
 """
 import argparse
 import json
@@ -164,6 +169,8 @@ def main():
                     "the push with and without MetricRows behind it")
     ap.add_argument("--readout", action="store_true", help="the closed-form head fit: moments, solve for 1 / 8 / 48 plans and pick_ridge "
                     "over 6 folds, next to numpy's X.T @ X and numpy.linalg.solve")
+    ap.add_argument("--stream-projections", action="store_true", help="the multi-stream pushes with stream_projections=True, no slot "
+                    "set and every slot set, next to the same decoder built without the option")
     a = ap.parse_args()
     if a.readout:
         return readout_main(a)
@@ -198,6 +205,8 @@ def main():
     rows = []
     if a.sequence or a.sequence_sweep:
         return sequence_main(a, e, stream, mean, std, classes)
+    if a.stream_projections:
+        return stream_projections_main(a, e, stream, mean, std, classes)
     if a.gate:
         return gate_main(a, e, stream, mean, std, classes)
     if a.drive:
@@ -1626,6 +1635,70 @@ def streams_main(a, e, stream, mean, std, classes):
             for r in rows:
                 f.write(f"{r['kind']:<11} {r['dtype']:<5} {r['streams']:>7} {r['samples']:>7} {r['windows']:>7} {r['median_us']:>10.1f} "
                         f"{r['p90_us']:>9.1f} {r['kernels_per_push']:>8.1f} {r['speedup']:>8.2f}\n")
+
+
+def stream_projections_main(a, e, stream, mean, std, classes):
+    """--stream-projections: a push of the two multi-stream decoders built without the option (`off`), with it and no slot set
+    (`unset`) and with it and every slot set (`set`), for S = 1, 16, 256 streams at 1 and 25 windows per stream: 5 alternating
+    rounds of host-synchronised medians per case, and the kernels per push of each."""
+    rows = []
+    g = torch.Generator().manual_seed(0)
+    for adaptive in (False, True):
+        for dtype in ("f32", "bf16"):
+            for S in (1, 16, 256):
+                for n in (20, 500):
+                    m = n // 20
+
+                    def build(on):
+                        kw = dict(dtype=dtype, max_rows=S * m, stream_projections=on)
+                        d = AdaptiveMultiStreamDecoder(e, mean, std, S, 0.01, **kw) if adaptive else MultiStreamDecoder(e, mean, std, S, **kw)
+                        for s in range(S):
+                            d.set_classes(s, classes=classes)
+                        return d
+
+                    decs = {"off": build(False), "unset": build(True), "set": build(True)}
+                    W, b = decs["set"].projection(0)
+                    for s in range(S):                               # every stream its own 16 x 512 + 16 numbers
+                        decs["set"].set_projection(s, W + 0.01 * torch.randn(W.shape, generator=g).cuda(),
+                                                   b + 0.01 * torch.randn(b.shape, generator=g).cuda())
+                    pos = {k: 0 for k in decs}
+                    span = stream.shape[0] - S * n
+
+                    def push(k):
+                        base = pos[k] % span
+                        pos[k] += S * n
+                        return decs[k].push_packed(stream[base:base + S * n], [n] * S)
+
+                    meds = {k: [] for k in decs}
+                    for _ in range(5):                               # alternate, so that a drift of the machine hits all three
+                        for k in decs:
+                            meds[k].append(time_pushes(lambda: push(k), a.iters, a.warmup)[0])
+                    med = {k: float(np.median(v)) for k, v in meds.items()}
+                    r = dict(form="adaptive" if adaptive else "folded", dtype=dtype, streams=S, windows=m,
+                             off_us=round(med["off"], 1), unset_us=round(med["unset"], 1), set_us=round(med["set"], 1),
+                             off_spread_us=round(float(max(meds["off"]) - min(meds["off"])), 1),
+                             unset_minus_off_us=round(med["unset"] - med["off"], 1), set_minus_off_us=round(med["set"] - med["off"], 1),
+                             kernels={k: count_kernels(lambda: push(k), pushes=2) for k in decs})
+                    print(json.dumps(r), flush=True)
+                    rows.append(r)
+                    del decs
+                    torch.cuda.empty_cache()
+    if a.out:
+        dev = torch.cuda.get_device_name(0)
+        with open(a.out, "w") as f:
+            f.write(f"# tools/online_bench.py --stream-projections --iters {a.iters} --warmup {a.warmup} on {dev}\n")
+            f.write("# one push_packed of S streams x `windows` windows each on MultiStreamDecoder (folded) and\n"
+                    "# AdaptiveMultiStreamDecoder (adaptive): off = built without stream_projections, unset = built with it and no slot\n"
+                    "# set, set = every stream with a projection of its own.  5 alternating rounds of host-synchronised medians, the\n"
+                    "# median of the 5; off_spread = max - min of the 5 medians of `off`; kernels per push (torch.profiler: library\n"
+                    "# kernels plus torch's own, e.g. the copy of the counts) as off / unset / set\n")
+            f.write(f"{'form':<9} {'dtype':<5} {'streams':>7} {'windows':>7} {'off_us':>9} {'unset_us':>9} {'set_us':>9} {'off_spread':>11} "
+                    f"{'unset-off':>10} {'set-off':>9} {'kernels':>17}\n")
+            for r in rows:
+                k = r["kernels"]
+                f.write(f"{r['form']:<9} {r['dtype']:<5} {r['streams']:>7} {r['windows']:>7} {r['off_us']:>9.1f} {r['unset_us']:>9.1f} "
+                        f"{r['set_us']:>9.1f} {r['off_spread_us']:>11.1f} {r['unset_minus_off_us']:>10.1f} {r['set_minus_off_us']:>9.1f} "
+                        f"{k['off']:>5.1f}/{k['unset']:>5.1f}/{k['set']:>5.1f}\n")
 
 
 def streams_adapt_main(a, e, stream, mean, std, classes):
