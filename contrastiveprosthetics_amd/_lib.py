@@ -93,6 +93,10 @@ class cp_online_drive_config(C.Structure):
                 ("bad_after", C.c_int32), ("good_after", C.c_int32)]
 
 
+class cp_online_kin_config(C.Structure):
+    _fields_ = [("smooth", C.c_int32), ("rate", C.c_int32)]
+
+
 class cp_online_realign_config(C.Structure):
     _fields_ = [("max_lag", C.c_int32), ("max_lead", C.c_int32), ("min_len", C.c_int32), ("min_rest", C.c_int32),
                 ("context", C.c_int32), ("min_contrast", C.c_int32), ("guard", C.c_int32)]
@@ -198,6 +202,7 @@ CP_ONLINE_PROTO_MAX_ROWS, CP_ONLINE_PROTO_MAX_ITERS = 4, 64
 CP_ONLINE_METRIC_MOMENTS, CP_ONLINE_METRIC_MAX_SHRINKS = 152, 64
 CP_ONLINE_METRIC_RESET_RING, CP_ONLINE_METRIC_RESET_ALL = 0, 1
 CP_ONLINE_READOUT_MAX_GROUPS, CP_ONLINE_READOUT_MAX_PLANS, CP_ONLINE_READOUT_STAGE, CP_ONLINE_READOUT_X = 16, 256, 16, 513
+CP_ONLINE_KIN_MAX_JOINTS, CP_ONLINE_KIN_MAX_SMOOTH, CP_ONLINE_KIN_ONE, CP_ONLINE_KIN_SUMS = 32, 64, 4096, 7
 
 # what the four map sweep entries take behind their workspace: rms, n_windows, mean_std, map_src, map_fill, n_maps, n_classes,
 # expected_slot, chunk_rows, scratch, scratch_bytes, pred, voted, scores, class_hits, stream
@@ -419,6 +424,17 @@ SYMBOLS = {
                                                                                 _fp]),
     "cp_online_multi_map_sweep_proj": (C.c_int, _MULTI_HEAD + _STREAM_BANK + _MAP_SWEEP_TAIL),
     "cp_online_multi_adapt_map_sweep_proj": (C.c_int, _MULTI_HEAD + _STREAM_BANK + _MAP_SWEEP_TAIL),
+    "cp_online_tail_offset": (C.c_size_t, [_P(cp_online_config), C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "cp_online_kin_moments": (C.c_int, [_fp, C.c_int32, C.c_int64, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp,
+                                        C.c_size_t, _fp]),
+    "cp_online_kin_apply": (C.c_int, [_fp, C.c_int32, C.c_int64, _fp, _fp, C.c_int32, C.c_int32, _fp, _fp]),
+    "cp_online_kin_score": (C.c_int, [_fp, _fp, C.c_int32, _fp, _P(C.c_uint32), C.c_int32, C.c_int64, C.c_int32, _fp, _fp]),
+    "cp_online_kin_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "cp_online_kin_set_model": (C.c_int, [_P(cp_online_kin_config), C.c_int32, _fp, C.c_size_t, C.c_int32, _fp, _fp, C.c_int32,
+                                          _P(C.c_float), _P(C.c_float), _P(C.c_int32), _fp]),
+    "cp_online_kin_reset": (C.c_int, [_P(cp_online_kin_config), C.c_int32, _fp, C.c_size_t, C.c_int32, _fp]),
+    "cp_online_kin_push": (C.c_int, [_P(cp_online_kin_config), C.c_int32, _fp, C.c_size_t, _fp, C.c_int32, C.c_int32, _fp, _fp, _fp,
+                                     C.c_int32, _fp, _fp, _fp, _fp]),
 }
 
 KERNEL_KINDS = ["gather", "prep", "conv1_fwd", "bn_finalize", "conv2_fwd", "fold", "fc_fwd", "dropout", "proj_fwd",

@@ -38,6 +38,7 @@
 #include "online_metric.cuh"
 #include "online_readout.cuh"
 #include "online_projections.cuh"
+#include "online_kinematics.cuh"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* what) {

@@ -2731,3 +2731,191 @@ extern "C" int cp_online_multi_adapt_map_sweep_proj(const cp_online_config* cfg,
     return olp_map_sweep("cp_online_multi_adapt_map_sweep_proj", true, cfg, n_streams, max_rows, ws, ws_bytes, index, bank, bank_bytes, a,
                          stream);
 }
+
+// ---------------------------------------------------------------------------------------
+// joint-angle decoding (csrc/online_kinematics.cuh): where a push leaves its tail inputs, the moments of a recording's tail
+// inputs against the glove sample of every window, the fitted readouts applied and scored on held-out windows, and one OknState
+// per stream in a workspace of its own behind any decoder's push
+// ---------------------------------------------------------------------------------------
+static_assert(OKN_MAXD == CP_ONLINE_KIN_MAX_JOINTS && OKN_MAXSMOOTH == CP_ONLINE_KIN_MAX_SMOOTH && OKN_ONE == CP_ONLINE_KIN_ONE &&
+              OKN_SUMS == CP_ONLINE_KIN_SUMS && OKN_MAXM == CP_ONLINE_MAX_WINDOWS, "kinematics limits");
+static_assert(sizeof(OknState) == 4 * (8 + 6 * OKN_MAXD + OKN_MAXSMOOTH * OKN_MAXD + OKN_MAXD * OKN_F) && sizeof(OknState) % 16 == 0 &&
+              offsetof(OknState, W) % 16 == 0 && offsetof(OknState, ring) % 16 == 0,
+              "OknState is 18632 words (JointAngles.state reads it back)");
+static_assert(sizeof(OknScoreArgs) <= 4096 && sizeof(OknModelArgs) <= 4096, "kinematics kernel arguments");
+
+extern "C" size_t cp_online_tail_offset(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, int32_t adaptive, int32_t multi) {
+    const char* who = "cp_online_tail_offset";
+    auto bad = [&](const char* what) { ol_fail(CP_ERR_ARG, who, what); return (size_t)0; };
+    if (!cfg) return bad("config is required");
+    if (cfg->dtype != CP_F32 && cfg->dtype != CP_BF16) return bad("dtype must be CP_F32 or CP_BF16 (no 8-bit path)");
+    if (cfg->max_windows < 1 || cfg->max_windows > CP_ONLINE_MAX_WINDOWS) return bad("max_windows outside 1..256");
+    if (multi) {
+        if (n_streams < 1 || n_streams > CP_ONLINE_MULTI_MAX_STREAMS) return bad("n_streams outside 1..256");
+        if (max_rows < 1 || max_rows > CP_ONLINE_MULTI_MAX_ROWS) return bad("max_rows outside 1..65536");
+        return ol_carve(max_rows, cfg->dtype, n_streams, adaptive != 0, true).H1;
+    }
+    if (n_streams != 1) return bad("a single-stream form has one stream");
+    return ol_carve(cfg->max_windows, cfg->dtype, 1, adaptive != 0, false).H1;
+}
+
+extern "C" int cp_online_kin_moments(const void* u, int32_t dtype, int64_t n_rows, const int32_t* group, const double* weight,
+                                     const float* y, int32_t ldy, int32_t n_joints, int32_t n_groups, double* G, double* C,
+                                     void* scratch, size_t scratch_bytes, void* stream) {
+    const char* who = "cp_online_kin_moments";
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (dtype != CP_F32 && dtype != CP_BF16) return bad("dtype must be CP_F32 or CP_BF16");
+    if (n_rows < 0 || n_rows > (int64_t)1 << 24) return bad("n_rows outside 0..2**24");
+    if (n_joints < 1 || n_joints > CP_ONLINE_KIN_MAX_JOINTS) return bad("n_joints outside 1..32");
+    if (n_groups < 1 || n_groups > CP_ONLINE_READOUT_MAX_GROUPS) return bad("n_groups outside 1..16");
+    if (ldy < n_joints) return bad("ldy must be at least n_joints");
+    if (!G || !C || !scratch) return bad("G, C and scratch are required");
+    if (n_rows > 0 && (!u || !group || !weight || !y)) return bad("u, group, weight and y are required");
+    if ((uintptr_t)u % 16 || (uintptr_t)group % 4 || (uintptr_t)weight % 8 || (uintptr_t)y % 4 || (uintptr_t)G % 8 || (uintptr_t)C % 8 ||
+        (uintptr_t)scratch % 256)
+        return bad("misaligned argument");
+    if (scratch_bytes < olr_moments_bytes(n_rows < 1 ? 1 : n_rows, n_groups)) return ol_fail(CP_ERR_WORKSPACE, who, "scratch too small");
+    int32_t* idx = (int32_t*)scratch;
+    int32_t* count = (int32_t*)((unsigned char*)scratch + align256((size_t)n_groups * (size_t)(n_rows < 1 ? 1 : n_rows) * 4));
+    hipLaunchKernelGGL(okn_index_kernel, dim3(n_groups), dim3(64), 0, (hipStream_t)stream, group, (int)n_rows, idx, count);
+    CKL("okn_index_kernel");
+    return ol_dispatch(dtype, [&](auto t) {
+        using T = decltype(t);
+        OknMomentsArgs<T> a{};
+        a.u = (const T*)u; a.weight = weight; a.y = y; a.idx = idx; a.count = count; a.G = G; a.C = C;
+        a.n_rows = (int)n_rows; a.ldy = ldy; a.D = n_joints; a.n_groups = n_groups;
+        hipLaunchKernelGGL((okn_moments_kernel<T>), dim3(OLR_TILES, n_groups), dim3(OLR_MOM_THREADS), 0, (hipStream_t)stream, a);
+        CKL("okn_moments_kernel");
+        return 0;
+    });
+}
+
+extern "C" int cp_online_kin_apply(const void* u, int32_t dtype, int64_t n_rows, const float* W, const float* b, int32_t n_plans,
+                                   int32_t n_joints, float* out, void* stream) {
+    const char* who = "cp_online_kin_apply";
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (dtype != CP_F32 && dtype != CP_BF16) return bad("dtype must be CP_F32 or CP_BF16");
+    if (n_rows < 0 || n_rows > (int64_t)1 << 24) return bad("n_rows outside 0..2**24");
+    if (n_plans < 0 || n_plans > CP_ONLINE_READOUT_MAX_PLANS) return bad("n_plans outside 0..256");
+    if (n_joints < 1 || n_joints > CP_ONLINE_KIN_MAX_JOINTS) return bad("n_joints outside 1..32");
+    if (n_rows == 0 || n_plans == 0) return 0;
+    if (!u || !W || !b || !out) return bad("u, W, b and out are required");
+    if ((uintptr_t)u % 16 || (uintptr_t)W % 16 || (uintptr_t)b % 4 || (uintptr_t)out % 4) return bad("misaligned argument");
+    OknApplyArgs a{};
+    a.u = u; a.W = W; a.b = b; a.out = out; a.n_rows = (int)n_rows; a.D = n_joints;
+    return ol_dispatch(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((okn_apply_kernel<T>), dim3((unsigned)((n_rows + OKN_BATCH - 1) / OKN_BATCH), n_plans), dim3(OKN_THREADS),
+                           OKN_APPLY_LDS, (hipStream_t)stream, a);
+        CKL("okn_apply_kernel");
+        return 0;
+    });
+}
+
+extern "C" int cp_online_kin_score(const float* pred, const float* y, int32_t ldy, const int32_t* group, const uint32_t* test_masks,
+                                   int32_t n_plans, int64_t n_rows, int32_t n_joints, double* sums, void* stream) {
+    const char* who = "cp_online_kin_score";
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (n_rows < 0 || n_rows > (int64_t)1 << 24) return bad("n_rows outside 0..2**24");
+    if (n_plans < 0 || n_plans > CP_ONLINE_READOUT_MAX_PLANS) return bad("n_plans outside 0..256");
+    if (n_joints < 1 || n_joints > CP_ONLINE_KIN_MAX_JOINTS) return bad("n_joints outside 1..32");
+    if (ldy < n_joints) return bad("ldy must be at least n_joints");
+    if (n_plans == 0) return 0;
+    if (!test_masks || !sums) return bad("test_masks and sums are required");
+    if (n_rows > 0 && (!pred || !y || !group)) return bad("pred, y and group are required");
+    if ((uintptr_t)pred % 4 || (uintptr_t)y % 4 || (uintptr_t)group % 4 || (uintptr_t)sums % 8) return bad("misaligned argument");
+    OknScoreArgs a{};
+    for (int t = 0; t < n_plans; ++t) {
+        if (test_masks[t] >> CP_ONLINE_READOUT_MAX_GROUPS) return bad("a plan's test mask names a group at or above 16");
+        a.mask[t] = (unsigned short)test_masks[t];
+    }
+    a.pred = pred; a.y = y; a.group = group; a.sums = sums; a.n_rows = (int)n_rows; a.ldy = ldy; a.D = n_joints;
+    hipLaunchKernelGGL(okn_score_kernel, dim3(n_plans), dim3(64), 0, (hipStream_t)stream, a);
+    CKL("okn_score_kernel");
+    return 0;
+}
+
+static int okn_check(const char* who, const cp_online_kin_config* c, int32_t n_streams, void* ws, size_t ws_bytes) {
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (!c || !ws) return bad("config and workspace are required");
+    if (n_streams < 1 || n_streams > CP_ONLINE_MULTI_MAX_STREAMS) return bad("n_streams outside 1..256");
+    if (c->smooth < 1 || c->smooth > CP_ONLINE_KIN_MAX_SMOOTH) return bad("smooth outside 1..64");
+    if (c->rate < 1 || c->rate > CP_ONLINE_KIN_ONE) return bad("rate outside 1..4096");
+    if ((uintptr_t)ws % 256) return bad("workspace not 256-byte aligned");
+    if (ws_bytes < (size_t)n_streams * sizeof(OknState)) return ol_fail(CP_ERR_WORKSPACE, who, "workspace too small");
+    return 0;
+}
+
+extern "C" size_t cp_online_kin_workspace_bytes(int32_t n_streams) {
+    if (n_streams < 1) n_streams = 1;
+    return align256((size_t)n_streams * sizeof(OknState));
+}
+
+extern "C" int cp_online_kin_set_model(const cp_online_kin_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index,
+                                       const float* W, const float* b, int32_t n_joints, const float* lo, const float* span,
+                                       const int32_t* rest, void* stream) {
+    const char* who = "cp_online_kin_set_model";
+    if (int e = okn_check(who, cfg, n_streams, ws, ws_bytes)) return e;
+    if (int e = ol_check_index(who, index, n_streams)) return e;
+    if (n_joints < 1 || n_joints > CP_ONLINE_KIN_MAX_JOINTS) return ol_fail(CP_ERR_ARG, who, "n_joints outside 1..32");
+    if (!W || !b || !lo || !span || !rest) return ol_fail(CP_ERR_ARG, who, "W, b, lo, span and rest are required");
+    if ((uintptr_t)W % 16 || (uintptr_t)b % 4) return ol_fail(CP_ERR_ARG, who, "misaligned W or b");
+    OknModelArgs p{};
+    p.D = n_joints;
+    for (int d = 0; d < n_joints; ++d) {
+        if (!std::isfinite(lo[d])) return ol_fail(CP_ERR_ARG, who, "lo must be finite");
+        if (!(span[d] > 0.f) || !std::isfinite(span[d])) return ol_fail(CP_ERR_ARG, who, "span must be finite and > 0");
+        if (rest[d] < 0 || rest[d] > CP_ONLINE_KIN_ONE) return ol_fail(CP_ERR_ARG, who, "rest outside 0..4096");
+        p.lo[d] = lo[d];
+        p.span[d] = span[d];
+        p.rest[d] = rest[d];
+    }
+    hipLaunchKernelGGL(okn_set_model_kernel, dim3(1), dim3(OKN_THREADS), 0, (hipStream_t)stream, (OknState*)ws + index, W, b, p);
+    CKL("okn_set_model_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_kin_reset(const cp_online_kin_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index,
+                                   void* stream) {
+    const char* who = "cp_online_kin_reset";
+    if (int e = okn_check(who, cfg, n_streams, ws, ws_bytes)) return e;
+    if (index < -1 || index >= n_streams) return ol_fail(CP_ERR_ARG, who, "stream index outside -1..n_streams-1");
+    hipLaunchKernelGGL(okn_reset_kernel, dim3(index < 0 ? n_streams : 1), dim3(OKN_THREADS), 0, (hipStream_t)stream, (OknState*)ws,
+                       index < 0 ? 0 : index);
+    CKL("okn_reset_kernel");
+    return 0;
+}
+
+// more than 64 KB of dynamic LDS needs the opt-in once per process and kernel
+template <typename T>
+static int okn_push_launch(int32_t n_streams, const OknPushArgs& a, void* stream) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        CK(hipFuncSetAttribute((const void*)okn_push_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, OKN_PUSH_LDS));
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((okn_push_kernel<T>), dim3(n_streams), dim3(OKN_THREADS), OKN_PUSH_LDS, (hipStream_t)stream, a);
+    CKL("okn_push_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_kin_push(const cp_online_kin_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, const void* tail,
+                                  int32_t dtype, int32_t ldt, const int32_t* cls, const int32_t* row0, const int32_t* m,
+                                  int32_t total_rows, float* raw, int32_t* pose, float* angle, void* stream) {
+    const char* who = "cp_online_kin_push";
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (int e = okn_check(who, cfg, n_streams, ws, ws_bytes)) return e;
+    if (dtype != CP_F32 && dtype != CP_BF16) return bad("dtype must be CP_F32 or CP_BF16");
+    if (total_rows < 0 || total_rows > CP_ONLINE_MULTI_MAX_ROWS) return bad("total_rows outside 0..65536");
+    if (total_rows == 0) return 0;
+    if (ldt < OKN_F) return bad("ldt must be at least 512");
+    if (!tail || !row0 || !m || !raw || !pose || !angle) return bad("tail, row0, m, raw, pose and angle are required");
+    const size_t es = dtype == CP_BF16 ? 2 : 4;
+    if ((uintptr_t)tail % 16 || ((size_t)ldt * es) % 16 || (uintptr_t)cls % 4 || (uintptr_t)row0 % 4 || (uintptr_t)m % 4 ||
+        (uintptr_t)raw % 4 || (uintptr_t)pose % 4 || (uintptr_t)angle % 4)
+        return bad("misaligned argument");
+    OknPushArgs a{};
+    a.states = (OknState*)ws; a.tail = tail; a.cls = cls; a.row0 = row0; a.m = m; a.ldt = ldt; a.total_rows = total_rows;
+    a.smooth = cfg->smooth; a.rate = cfg->rate; a.raw = raw; a.pose = pose; a.angle = angle;
+    return ol_dispatch(dtype, [&](auto t) { return okn_push_launch<decltype(t)>(n_streams, a, stream); });
+}

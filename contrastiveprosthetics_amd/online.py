@@ -212,6 +212,15 @@ def _check_projection(W, b):
     return W, b
 
 
+def _tail_view(dec, n_streams: int, max_rows: int, rows: int, adaptive: bool, multi: bool) -> torch.Tensor:
+    """the block of a decoder's workspace that holds the tail inputs of its last push, as a (rows, 512) view"""
+    off = dec.lib.cp_online_tail_offset(C.byref(dec._cfg), n_streams, max_rows, int(adaptive), int(multi))
+    if off == 0:
+        raise _lib.CpNativeError("cp_online_tail_offset failed: " + dec.lib.cp_last_error().decode("utf-8", "replace"))
+    dt = torch.float32 if dec.dtype == "f32" else torch.bfloat16
+    return dec.ws[off:off + rows * 512 * (4 if dec.dtype == "f32" else 2)].view(dt).view(rows, 512)
+
+
 class _OnStream:
     """a decoder or gate on `self.device`: its C entries run on torch's current stream there"""
 
@@ -572,6 +581,13 @@ class OnlineDecoder(_EnrollMixin):
     # ------------------------------------------------------------------ helpers
     def _ws(self):
         return self.ws.data_ptr(), self.ws.numel()
+
+    def tail_view(self) -> torch.Tensor:
+        """(max_windows_per_push, 512) in the compute dtype: the tail inputs (fc7's output) the last push left in the
+        workspace, as a view of the workspace tensor (cp_online_tail_offset; no copy, no launch).  Row r belongs to window r
+        of the last chain of launches (a push of more than max_windows_per_push windows runs several) and stays valid until
+        the next call that runs the encoder on this workspace."""
+        return _tail_view(self, 1, 0, self.max_windows, self.adapt is not None, False)
 
     # ------------------------------------------------------------------ API
     def refresh(self):
@@ -949,6 +965,12 @@ class _MultiStreamBase(_EnrollMixin):
     # ------------------------------------------------------------------ helpers
     def _args(self):
         return (C.byref(self._cfg), self.n_streams, self.max_rows, self.ws.data_ptr(), self.ws.numel())
+
+    def tail_view(self) -> torch.Tensor:
+        """(max_rows, 512) in the compute dtype: the tail inputs (fc7's output) the last push left in the workspace, as a view
+        of the workspace tensor (cp_online_tail_offset; no copy, no launch).  Row r belongs to packed row r (stream, window)
+        of the last chain of launches and stays valid until the next call that runs the encoder on this workspace."""
+        return _tail_view(self, self.n_streams, self.max_rows, self.max_rows, self._ENTRY.endswith("adapt"), True)
 
     def _bank_args(self):
         return (self._bank.data_ptr(), self._bank.numel())

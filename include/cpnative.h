@@ -1854,6 +1854,74 @@ int cp_online_multi_adapt_map_sweep_proj(const cp_online_config* cfg, int32_t n_
                                          size_t scratch_bytes, int32_t* pred, int32_t* voted, int64_t* scores, int32_t* class_hits,
                                          void* stream);
 
+/* ---- joint-angle decoding: a ridge pose readout behind the decoders -----------------------------------------------------------
+ * Everything above emits a class, or one level beside a class.  This stage emits a pose: per 10 ms window and stream the angle of
+ * up to CP_ONLINE_KIN_MAX_JOINTS joints, regressed linearly from the tail inputs (fc7's output, 512 values per window) onto the
+ * glove samples recorded alongside the sEMG, then bounded, smoothed and rate-limited by an integer state machine.  The numpy
+ * definitions are in contrastiveprosthetics_amd/kinematics.py (window_targets, moments_reference, fit_reference, pose_reference,
+ * JointReference, score_reference); every entry equals them in every bit.  Nothing a push launches or emits changes.
+ *
+ * cp_online_tail_offset (host only): the byte offset, inside the workspace of the form (adaptive, multi) with this config,
+ *   n_streams and max_rows (the single-stream forms: n_streams 1, max_rows ignored, cfg->max_windows rows), of the block that
+ *   holds the tail inputs of the last push: row r is (512) values in the compute dtype with leading dimension 512 and belongs
+ *   to row r of that push's logits (packed (stream, window) in the multi forms).  It stays valid until the next call that runs
+ *   the encoder on that workspace.  0 with cp_last_error set for a bad config.
+ *
+ * cp_online_kin_moments (two launches: the index lists, then a grid of (tiles, groups)): cp_online_readout_moments with the
+ *   window's own target row y[i] (n_joints of ldy f32 values) in place of a class row.  u (n_rows, 512) in dtype, 16-byte
+ *   aligned; group (n_rows) int32, outside 0..n_groups-1: not used; weight (n_rows) f64.  G (n_groups, 513, 513) f64 and C
+ *   (2, n_groups, 513, 16) f64: column block k holds joints 16 k .. 16 k + 15 (joints from n_joints on: zero), so C + k *
+ *   n_groups * 513 * 16 goes to cp_online_readout_solve as it is.  scratch: cp_online_readout_scratch_bytes(n_rows, n_groups, 1).
+ *
+ * cp_online_kin_apply (one launch, grid (row chunks, plans)): out[t][i][d] = W[t][d] . u[i] + b[t][d] in the pose matvec's order:
+ *   u widened to f32; partial sum l of 64 takes the products W[d][l + 64 j] * u[l + 64 j], j = 0..7 ascending, from +0.0f, each
+ *   product rounded, then added and rounded; p[l] = p[l] + p[l + s] for l < s, s = 32, 16, 8, 4, 2, 1; then p[0] + b[d].
+ *   W (n_plans, n_joints, 512) 16-byte aligned and b (n_plans, n_joints) f32 on the device; out (n_plans, n_rows, n_joints) f32.
+ *
+ * cp_online_kin_score (one launch, one wave per plan): per plan t and joint d, over the rows whose group is in test_masks[t]
+ *   (host memory, uint32 bit masks of groups 0..15), in row order, in f64 with every operation rounded on its own:
+ *   sums[t][d] = n, sum y, sum y^2, sum p, sum p^2, sum y p, sum (p - y)^2 with p = pred[t][i][d], y = y[i][d] widened.
+ *
+ * The stage (cp_online_kin_workspace_bytes, _set_model, _reset, _push): one state machine per stream in a workspace of its own,
+ *   256-byte aligned; zeroed it is a valid start (no model, empty rings, pose 0).  A stream's model is W (n_joints, 512) and b
+ *   (n_joints) f32 ON THE DEVICE (16- and 4-byte aligned; one copy launch installs them) and lo, span (finite, span > 0) and rest
+ *   (0..4096) per joint from the host.  Installing a model restarts the stream; reset (index, or -1 for every stream) empties the
+ *   rings and zeroes the pose, the models stay.
+ *   cp_online_kin_push (one launch, one workgroup per stream): stream s takes rows row0[s] .. row0[s] + m[s] - 1 of tail
+ *   (total_rows, ldt) in dtype (ldt >= 512, rows 16-byte aligned) and of cls (total_rows) int32 (class ids, < 0: none; cls may
+ *   be NULL).  Per row, in row order, per joint d, levels being integers out of CP_ONLINE_KIN_ONE and every f32 operation single:
+ *     a = the pose matvec; t = (a - lo) / span; q = (int) rintf(fminf(fmaxf(t, 0), 1) * 4096), a NaN t or a class < 0: q = rest;
+ *     q enters the joint's ring of cfg->smooth entries, s = floor(ring sum / entries); out moves towards s by at most cfg->rate.
+ *   raw (a), pose (out) and angle (lo + ((float) out / 4096.f) * span) are (total_rows, CP_ONLINE_KIN_MAX_JOINTS) f32, int32, f32;
+ *   columns from the stream's n_joints on are zero.  A stream with m[s] == 0, without a model, with m[s] above
+ *   CP_ONLINE_MAX_WINDOWS or with rows outside 0..total_rows-1 is left untouched.  row0, m: (n_streams) int32 on the device.
+ *
+ * The host checks before anything is enqueued: CP_ERR_ARG or CP_ERR_WORKSPACE with a cp_last_error that names the entry.  The
+ * entries never allocate, never synchronise and keep no state outside the stage's workspace. */
+#define CP_ONLINE_KIN_MAX_JOINTS 32
+#define CP_ONLINE_KIN_MAX_SMOOTH 64
+#define CP_ONLINE_KIN_ONE 4096
+#define CP_ONLINE_KIN_SUMS 7
+typedef struct cp_online_kin_config {
+    int32_t smooth;                       /* ring length, 1..CP_ONLINE_KIN_MAX_SMOOTH */
+    int32_t rate;                         /* largest change of a joint's level per window, 1..CP_ONLINE_KIN_ONE */
+} cp_online_kin_config;
+size_t cp_online_tail_offset(const cp_online_config* cfg, int32_t n_streams, int32_t max_rows, int32_t adaptive, int32_t multi);
+int cp_online_kin_moments(const void* u, int32_t dtype, int64_t n_rows, const int32_t* group, const double* weight, const float* y,
+                          int32_t ldy, int32_t n_joints, int32_t n_groups, double* G, double* C, void* scratch, size_t scratch_bytes,
+                          void* stream);
+int cp_online_kin_apply(const void* u, int32_t dtype, int64_t n_rows, const float* W, const float* b, int32_t n_plans,
+                        int32_t n_joints, float* out, void* stream);
+int cp_online_kin_score(const float* pred, const float* y, int32_t ldy, const int32_t* group, const uint32_t* test_masks,
+                        int32_t n_plans, int64_t n_rows, int32_t n_joints, double* sums, void* stream);
+size_t cp_online_kin_workspace_bytes(int32_t n_streams);
+int cp_online_kin_set_model(const cp_online_kin_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index, const float* W,
+                            const float* b, int32_t n_joints, const float* lo, const float* span, const int32_t* rest, void* stream);
+int cp_online_kin_reset(const cp_online_kin_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index, void* stream);
+int cp_online_kin_push(const cp_online_kin_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, const void* tail, int32_t dtype,
+                       int32_t ldt, const int32_t* cls, const int32_t* row0, const int32_t* m, int32_t total_rows, float* raw,
+                       int32_t* pose, float* angle, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -92,6 +92,7 @@ counted with torch.profiler over a few pushes.  One JSON line per case, and a ta
     python tools/online_bench.py --metric --iters 200 --out profiles/online_metric.txt
     python tools/online_bench.py --readout --iters 200 --out profiles/online_readout.txt
     python tools/online_bench.py --stream-projections --iters 50 --out profiles/online_stream_projections.txt
+    python tools/online_bench.py --kinematics --iters 100 --out profiles/online_kinematics.txt
 """
 import argparse
 import json
@@ -171,6 +172,8 @@ def main():
                     "over 6 folds, next to numpy's X.T @ X and numpy.linalg.solve")
     ap.add_argument("--stream-projections", action="store_true", help="the multi-stream pushes with stream_projections=True, no slot "
                     "set and every slot set, next to the same decoder built without the option")
+    ap.add_argument("--kinematics", action="store_true", help="joint-angle decoding: the push with and without JointAngles behind it at "
+                    "1, 16 and 256 streams, and moments, solve, apply and score of a 14,514-window recording x 20 joints")
     a = ap.parse_args()
     if a.readout:
         return readout_main(a)
@@ -211,6 +214,8 @@ def main():
         return gate_main(a, e, stream, mean, std, classes)
     if a.drive:
         return drive_main(a, e, stream, mean, std, classes)
+    if a.kinematics:
+        return kinematics_main(a, e, stream, mean, std, classes)
     if a.adapt and a.streams:
         return streams_adapt_main(a, e, stream, mean, std, classes)
     if a.adapt:
@@ -899,6 +904,120 @@ def drive_main(a, e, stream, mean, std, classes):
             for r in rows:
                 f.write(f"{r['kind']:<11} {r['dtype']:<5} {r['streams']:>7} {r['windows']:>7} {r['median_us']:>10.1f} {r['p90_us']:>9.1f} "
                         f"{r['kernels_per_push']:>8.1f} {r['gate_adds_us']:>10.1f} {r['drive_adds_us']:>10.1f}\n")
+
+
+def kinematics_main(a, e, stream, mean, std, classes):
+    """--kinematics.  Part 1: a push of 1 and of 25 windows per stream with and without a `JointAngles` stage (20 joints, smooth
+    5) behind it, at 1, 16 and 256 streams, f32 and bf16, each on a decoder of its own in this one process: host-synchronised
+    medians and kernels per push.  The bare push is timed twice, before and after the posed one; the difference of the two
+    medians is the run-to-run spread the stage's cost is read against.  Part 2: moments, solve, apply and score on the synthetic
+    person of kinematics.kinematics_recording(41, 6, 59): 14,514 windows x 512 tail inputs x 20 joints, 6 repetitions, beside
+    the numpy definitions (the moments' definition on the first 1,024 windows only: it walks a 513 x 513 matrix per window)."""
+    from contrastiveprosthetics_amd import kinematics as K
+    rng = np.random.default_rng(0)
+    D = 20
+    W = (0.05 * rng.standard_normal((D, 512))).astype(np.float32)
+    b = rng.standard_normal(D).astype(np.float32)
+    lo, span, rest = np.full(D, -2.0, np.float32), np.full(D, 4.0, np.float32), np.full(D, 2048, np.int32)
+    rows = []
+    for dtype in ("f32", "bf16"):
+        for S in (1, 16, 256):
+            for n in (20, 500):
+                m = n // 20
+
+                def decoder():
+                    if S == 1:
+                        return OnlineDecoder(e, mean, std, classes=classes, dtype=dtype)
+                    d = MultiStreamDecoder(e, mean, std, S, dtype=dtype, max_rows=S * m)
+                    for s in range(S):
+                        d.set_classes(s, classes=classes)
+                    return d
+
+                plain, under = decoder(), decoder()
+                stage = K.JointAngles(under, smooth=5, rate=400)
+                for s in range(S):
+                    stage.set_model(*((s,) if S > 1 else ()), W, b, lo, span, rest)
+                pos = [0]
+                span_s = stream.shape[0] - S * n
+
+                def chunk():
+                    base = pos[0] % span_s
+                    pos[0] += S * n
+                    return stream[base:base + S * n]
+
+                if S == 1:
+                    bare, posed = (lambda: plain.push(chunk())), (lambda: stage.push(chunk()))
+                else:
+                    bare, posed = (lambda: plain.push_packed(chunk(), [n] * S)), (lambda: stage.push_packed(chunk(), [n] * S))
+                b1, _ = time_pushes(bare, a.iters, a.warmup)
+                pm, pp90 = time_pushes(posed, a.iters, a.warmup)
+                b2, bp90 = time_pushes(bare, a.iters, a.warmup)
+                kb, kp = count_kernels(bare, pushes=3), count_kernels(posed, pushes=3)
+                if kp != kb + 1:
+                    raise SystemExit(f"a posed push launches {kp} kernels, a bare one {kb}: not one more")
+                bm = 0.5 * (b1 + b2)
+                r = dict(dtype=dtype, streams=S, windows=m, bare_us=round(bm, 1), posed_us=round(pm, 1), posed_p90_us=round(pp90, 1),
+                         stage_adds_us=round(pm - bm, 1), bare_spread_us=round(abs(b1 - b2), 1), kernels_bare=kb, kernels_posed=kp)
+                print(json.dumps(r), flush=True)
+                rows.append(r)
+                del plain, under, stage
+                torch.cuda.empty_cache()
+    # ---- part 2: the fit on a whole recording
+    k, reps, seg = 41, 6, 59
+    p = K.kinematics_recording(k, reps, seg, joints=D, seed=0)
+    u, y, rep = p["u"], p["y"], p["rep"]
+    m = int(u.shape[0])
+    u_d = torch.from_numpy(u).cuda()
+    iters = max(a.iters // 20, 3)
+    fits = []
+
+    def row(case, fn, n_iter, definition, note=""):
+        fn()
+        med, p90 = time_pushes(fn, n_iter, 1)
+        t0 = time.perf_counter()
+        definition()
+        r = dict(case=case, windows=m, device_ms=round(med / 1e3, 3), p90_ms=round(p90 / 1e3, 3),
+                 definition_ms=round((time.perf_counter() - t0) * 1e3, 1), note=note)
+        print(json.dumps(r), flush=True)
+        fits.append(r)
+
+    full = (1 << reps) - 1
+    plans = [(full & ~(1 << h), lam) for h in range(reps) for lam in (1e-2, 1.0)]
+    tests = [1 << h for h in range(reps) for _ in range(2)]
+    row(f"moments ({reps} groups)", lambda: K.moments(u_d, y, None, rep, reps), iters,
+        lambda: K.moments_reference(u[:1024], y[:1024], None, rep[:1024], reps), "definition: the first 1,024 windows")
+    G, Cm = K.moments(u_d, y, None, rep, reps)
+    Gh, Ch = G.cpu().numpy(), np.concatenate(list(Cm.cpu().numpy()), axis=2)[:, :, :D]
+    row("solve (1 plan, 2 blocks)", lambda: K.solve(G, Cm, [(full, 0.1)], D), iters, lambda: K.solve_reference(Gh, Ch, [(full, 0.1)]))
+    row(f"solve ({len(plans)} plans, 2 blocks)", lambda: K.solve(G, Cm, plans, D), iters, lambda: K.solve_reference(Gh, Ch, plans[:1]),
+        "definition: one plan")
+    Wp, bp, _ = K.solve(G, Cm, plans, D)
+    Wh, bh = Wp.cpu().numpy(), bp.cpu().numpy()
+    row(f"apply ({len(plans)} plans)", lambda: K.apply(u_d, Wp, bp), iters, lambda: K.pose_reference(u, Wh[0], bh[0]), "definition: one plan")
+    pred = K.apply(u_d, Wp, bp)
+    ph = pred[:1].cpu().numpy()
+    row(f"score ({len(plans)} plans)", lambda: K.score(pred, y, rep, tests), iters, lambda: K.score_reference(ph, y, rep, tests[:1]),
+        "definition: one plan")
+    pick = K.pick_pose_inputs(u_d, p["glove"], (rep, reps), (1e-2, 1.0), (0, 2))
+    if a.out:
+        name = torch.cuda.get_device_name(0)
+        with open(a.out, "w") as f:
+            f.write(f"# tools/online_bench.py --kinematics --iters {a.iters} --warmup {a.warmup} on {name}\n")
+            f.write("# bare = decoder.push / push_packed, posed = JointAngles.push on a decoder of its own (20 joints, smooth 5); per-push wall\n"
+                    "# time, host-synchronised medians; bare is timed before and after posed: bare_us is the mean of the two medians,\n"
+                    "# spread their difference; stage_adds = posed - bare; kernels per push (torch.profiler)\n")
+            f.write(f"{'dtype':<5} {'streams':>7} {'windows':>7} {'bare_us':>9} {'posed_us':>9} {'p90_us':>9} {'stage_adds':>10} {'spread':>8} "
+                    f"{'kernels':>9}\n")
+            for r in rows:
+                f.write(f"{r['dtype']:<5} {r['streams']:>7} {r['windows']:>7} {r['bare_us']:>9.1f} {r['posed_us']:>9.1f} {r['posed_p90_us']:>9.1f} "
+                        f"{r['stage_adds_us']:>10.1f} {r['bare_spread_us']:>8.1f} {r['kernels_bare']:>4.0f}+{r['kernels_posed'] - r['kernels_bare']:.0f}\n")
+            f.write(f"# the synthetic person of kinematics.kinematics_recording({k}, {reps}, {seg}): {m} windows x 512 tail inputs x {D} joints, f32\n")
+            f.write("# wall time, host-synchronised (median, p90); definition_ms: the numpy definition on the host, once\n")
+            f.write(f"{'call':<28} {'windows':>8} {'device_ms':>10} {'p90_ms':>9} {'definition_ms':>14}  note\n")
+            for r in fits:
+                f.write(f"{r['case']:<28} {r['windows']:>8} {r['device_ms']:>10.3f} {r['p90_ms']:>9.3f} {r['definition_ms']:>14.1f}  {r['note']}\n")
+            f.write(f"# pick_pose on the synthetic person (tail inputs lead the angles by 2 windows): mean held-out RMSE per (lag, ridge) "
+                    f"{np.round(pick['rmse_mean'], 3).tolist()} degrees, picked lag {pick['lag']} ridge {pick['ridge']}\n")
 
 
 class _Ids:
