@@ -97,6 +97,14 @@ class cp_online_kin_config(C.Structure):
     _fields_ = [("smooth", C.c_int32), ("rate", C.c_int32)]
 
 
+class cp_online_kf_plan(C.Structure):
+    _fields_ = [("groups", C.c_uint32), ("iters", C.c_int32), ("lam", C.c_double), ("rho", C.c_double), ("kappa", C.c_double)]
+
+
+class cp_online_kf_config(C.Structure):
+    _fields_ = [("rate", C.c_int32), ("reserved0", C.c_int32)]
+
+
 class cp_online_realign_config(C.Structure):
     _fields_ = [("max_lag", C.c_int32), ("max_lead", C.c_int32), ("min_len", C.c_int32), ("min_rest", C.c_int32),
                 ("context", C.c_int32), ("min_contrast", C.c_int32), ("guard", C.c_int32)]
@@ -203,6 +211,7 @@ CP_ONLINE_METRIC_MOMENTS, CP_ONLINE_METRIC_MAX_SHRINKS = 152, 64
 CP_ONLINE_METRIC_RESET_RING, CP_ONLINE_METRIC_RESET_ALL = 0, 1
 CP_ONLINE_READOUT_MAX_GROUPS, CP_ONLINE_READOUT_MAX_PLANS, CP_ONLINE_READOUT_STAGE, CP_ONLINE_READOUT_X = 16, 256, 16, 513
 CP_ONLINE_KIN_MAX_JOINTS, CP_ONLINE_KIN_MAX_SMOOTH, CP_ONLINE_KIN_ONE, CP_ONLINE_KIN_SUMS = 32, 64, 4096, 7
+CP_ONLINE_KF_MAX_ITERS, CP_ONLINE_KF_PLANS_PER_LAUNCH, CP_ONLINE_KF_SUMS = 1024, 128, 8
 
 # what the four map sweep entries take behind their workspace: rms, n_windows, mean_std, map_src, map_fill, n_maps, n_classes,
 # expected_slot, chunk_rows, scratch, scratch_bytes, pred, voted, scores, class_hits, stream
@@ -435,6 +444,18 @@ SYMBOLS = {
     "cp_online_kin_reset": (C.c_int, [_P(cp_online_kin_config), C.c_int32, _fp, C.c_size_t, C.c_int32, _fp]),
     "cp_online_kin_push": (C.c_int, [_P(cp_online_kin_config), C.c_int32, _fp, C.c_size_t, _fp, C.c_int32, C.c_int32, _fp, _fp, _fp,
                                      C.c_int32, _fp, _fp, _fp, _fp]),
+    "cp_online_kf_moments": (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int32, C.c_int32, _P(C.c_float), _fp, _fp, _fp, _fp, _fp, _fp]),
+    "cp_online_kf_design_bytes": (C.c_size_t, [C.c_int32]),
+    "cp_online_kf_design": (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, _P(cp_online_kf_plan), C.c_int32, _fp, _fp, _fp,
+                                      _fp, _fp, C.c_size_t, _fp]),
+    "cp_online_kf_sweep": (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int32, _P(C.c_uint32), C.c_int32, _fp, _fp, _P(C.c_float), _fp, _fp,
+                                     _fp]),
+    "cp_online_kf_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "cp_online_kf_set_model": (C.c_int, [_P(cp_online_kf_config), C.c_int32, _fp, C.c_size_t, C.c_int32, _fp, _fp, C.c_int32,
+                                         _P(C.c_float), _P(C.c_float), _P(C.c_int32), _fp, _fp, _fp]),
+    "cp_online_kf_reset": (C.c_int, [_P(cp_online_kf_config), C.c_int32, _fp, C.c_size_t, C.c_int32, _fp]),
+    "cp_online_kf_push": (C.c_int, [_P(cp_online_kf_config), C.c_int32, _fp, C.c_size_t, _fp, C.c_int32, C.c_int32, _fp, _fp, _fp,
+                                    C.c_int32, _fp, _fp, _fp, _fp, _fp]),
 }
 
 KERNEL_KINDS = ["gather", "prep", "conv1_fwd", "bn_finalize", "conv2_fwd", "fold", "fc_fwd", "dropout", "proj_fwd",

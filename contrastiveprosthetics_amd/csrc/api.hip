@@ -39,6 +39,7 @@
 #include "online_readout.cuh"
 #include "online_projections.cuh"
 #include "online_kinematics.cuh"
+#include "online_kalman.cuh"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* what) {

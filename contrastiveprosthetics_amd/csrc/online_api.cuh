@@ -2919,3 +2919,204 @@ extern "C" int cp_online_kin_push(const cp_online_kin_config* cfg, int32_t n_str
     a.smooth = cfg->smooth; a.rate = cfg->rate; a.raw = raw; a.pose = pose; a.angle = angle;
     return ol_dispatch(dtype, [&](auto t) { return okn_push_launch<decltype(t)>(n_streams, a, stream); });
 }
+
+// ---------------------------------------------------------------------------------------
+// pose filter (csrc/online_kalman.cuh): the trajectory and error moments of a cued recording, the steady-state gain of every
+// plan, the held-out sweep, and one OkfState per stream in a workspace of its own behind any decoder's push
+// ---------------------------------------------------------------------------------------
+static_assert(OKF_MAX_ITERS == CP_ONLINE_KF_MAX_ITERS && OKF_SUMS == CP_ONLINE_KF_SUMS && OKF_MAXD == CP_ONLINE_KIN_MAX_JOINTS,
+              "pose filter limits");
+static_assert(sizeof(OkfState) == 4 * (8 + OKF_MAXS + 6 * OKF_MAXD + OKF_MAXS * OKF_MAXS + OKF_MAXS * OKF_MAXD + OKF_MAXD * OKN_F) &&
+              sizeof(OkfState) % 16 == 0 && offsetof(OkfState, M) % 16 == 0 && offsetof(OkfState, W) % 16 == 0 &&
+              offsetof(OkfState, K) == offsetof(OkfState, M) + sizeof(float) * OKF_MAXS * OKF_MAXS,
+              "OkfState is 22792 words (PoseFilter.state reads it back)");
+static_assert(sizeof(OkfDesignArgs) <= 4096 && sizeof(OkfSweepArgs) <= 4096 && sizeof(OkfMomentsArgs) <= 4096 && sizeof(OkfModelArgs) <= 4096,
+              "pose filter kernel arguments");
+
+static int okf_check_centre(const char* who, const float* centre, int32_t n_joints, float* out) {
+    if (!centre) return ol_fail(CP_ERR_ARG, who, "centre is required");
+    for (int d = 0; d < n_joints; ++d) {
+        if (!std::isfinite(centre[d])) return ol_fail(CP_ERR_ARG, who, "centre must be finite");
+        out[d] = centre[d];
+    }
+    return 0;
+}
+
+extern "C" int cp_online_kf_moments(const float* a, const float* y, const int32_t* group, int64_t n_rows, int32_t n_joints,
+                                    int32_t n_groups, const float* centre, double* G, double* C, double* S, double* E, int32_t* count,
+                                    void* stream) {
+    const char* who = "cp_online_kf_moments";
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (n_rows < 0 || n_rows > (int64_t)1 << 24) return bad("n_rows outside 0..2**24");
+    if (n_joints < 1 || n_joints > CP_ONLINE_KIN_MAX_JOINTS) return bad("n_joints outside 1..32");
+    if (n_groups < 1 || n_groups > CP_ONLINE_READOUT_MAX_GROUPS) return bad("n_groups outside 1..16");
+    if (!G || !C || !S || !E || !count) return bad("G, C, S, E and count are required");
+    if (n_rows > 0 && (!a || !y || !group)) return bad("a, y and group are required");
+    if ((uintptr_t)a % 4 || (uintptr_t)y % 4 || (uintptr_t)group % 4 || (uintptr_t)G % 8 || (uintptr_t)C % 8 || (uintptr_t)S % 8 ||
+        (uintptr_t)E % 8 || (uintptr_t)count % 4)
+        return bad("misaligned argument");
+    OkfMomentsArgs k{};
+    if (int e = okf_check_centre(who, centre, n_joints, k.c)) return e;
+    k.a = a; k.y = y; k.group = group; k.G = G; k.C = C; k.S = S; k.E = E; k.count = count; k.n_rows = (int)n_rows; k.D = n_joints;
+    hipLaunchKernelGGL(okf_moments_kernel, dim3(n_groups), dim3(OKF_THREADS), 0, (hipStream_t)stream, k);
+    CKL("okf_moments_kernel");
+    return 0;
+}
+
+extern "C" size_t cp_online_kf_design_bytes(int32_t n_plans) {
+    if (n_plans < 1) n_plans = 1;
+    if (n_plans > OKF_PLANS_PER_LAUNCH) n_plans = OKF_PLANS_PER_LAUNCH;
+    return align256((size_t)n_plans * OKF_PLAN_DOUBLES * sizeof(double));
+}
+
+extern "C" int cp_online_kf_design(const double* G, const double* C, const double* S, const double* E, const int32_t* count,
+                                   int32_t n_joints, int32_t n_groups, const cp_online_kf_plan* plans, int32_t n_plans, float* M,
+                                   float* K, double* delta, int32_t* status, void* scratch, size_t scratch_bytes, void* stream) {
+    const char* who = "cp_online_kf_design";
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (n_joints < 1 || n_joints > CP_ONLINE_KIN_MAX_JOINTS) return bad("n_joints outside 1..32");
+    if (n_groups < 1 || n_groups > CP_ONLINE_READOUT_MAX_GROUPS) return bad("n_groups outside 1..16");
+    if (n_plans < 0 || n_plans > CP_ONLINE_READOUT_MAX_PLANS) return bad("n_plans outside 0..256");
+    if (n_plans == 0) return 0;
+    if (!G || !C || !S || !E || !count || !plans || !M || !K || !delta || !status || !scratch)
+        return bad("G, C, S, E, count, plans, M, K, delta, status and scratch are required");
+    if ((uintptr_t)G % 8 || (uintptr_t)C % 8 || (uintptr_t)S % 8 || (uintptr_t)E % 8 || (uintptr_t)count % 4 || (uintptr_t)M % 4 ||
+        (uintptr_t)K % 4 || (uintptr_t)delta % 8 || (uintptr_t)status % 4 || (uintptr_t)scratch % 256)
+        return bad("misaligned argument");
+    for (int t = 0; t < n_plans; ++t) {
+        const cp_online_kf_plan& p = plans[t];
+        if (p.groups >> n_groups) return bad("a plan's mask names a group at or above n_groups");
+        if (p.iters < 1 || p.iters > CP_ONLINE_KF_MAX_ITERS) return bad("a plan's iters outside 1..1024");
+        if (!(p.lam >= 0.0) || !std::isfinite(p.lam)) return bad("a plan's lam must be finite and >= 0");
+        if (!(p.rho > 0.0) || !std::isfinite(p.rho)) return bad("a plan's rho must be finite and > 0");
+        if (!(p.kappa > 0.0) || !std::isfinite(p.kappa)) return bad("a plan's kappa must be finite and > 0");
+    }
+    if (scratch_bytes < cp_online_kf_design_bytes(n_plans)) return ol_fail(CP_ERR_WORKSPACE, who, "scratch too small");
+    static bool attr_set = false;
+    if (!attr_set) {                                           // more than 64 KB of dynamic LDS needs the opt-in once per process
+        CK(hipFuncSetAttribute((const void*)okf_design_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, OKF_DESIGN_LDS));
+        attr_set = true;
+    }
+    const int n2 = 2 * n_joints;
+    for (int t0 = 0; t0 < n_plans; t0 += OKF_PLANS_PER_LAUNCH) {
+        const int np = n_plans - t0 < OKF_PLANS_PER_LAUNCH ? n_plans - t0 : OKF_PLANS_PER_LAUNCH;
+        OkfDesignArgs k{};
+        k.G = G; k.C = C; k.S = S; k.E = E; k.count = count; k.scratch = (double*)scratch; k.D = n_joints; k.n_groups = n_groups;
+        k.M = M + (size_t)t0 * n2 * n2; k.K = K + (size_t)t0 * n2 * n_joints; k.delta = delta + t0; k.status = status + t0;
+        for (int t = 0; t < np; ++t) {
+            const cp_online_kf_plan& p = plans[t0 + t];
+            k.mask[t] = (unsigned short)p.groups; k.iters[t] = (unsigned short)p.iters; k.lam[t] = p.lam; k.rho[t] = p.rho; k.kappa[t] = p.kappa;
+        }
+        hipLaunchKernelGGL(okf_design_kernel, dim3(np), dim3(OKF_THREADS), (size_t)okf_design_doubles(n_joints) * 8, (hipStream_t)stream, k);
+        CKL("okf_design_kernel");
+    }
+    return 0;
+}
+
+extern "C" int cp_online_kf_sweep(const float* a, const float* y, const int32_t* group, int64_t n_rows, int32_t n_joints,
+                                  const uint32_t* test_masks, int32_t n_plans, const float* M, const float* K, const float* centre,
+                                  double* sums, float* filtered, void* stream) {
+    const char* who = "cp_online_kf_sweep";
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (n_rows < 0 || n_rows > (int64_t)1 << 24) return bad("n_rows outside 0..2**24");
+    if (n_joints < 1 || n_joints > CP_ONLINE_KIN_MAX_JOINTS) return bad("n_joints outside 1..32");
+    if (n_plans < 0 || n_plans > CP_ONLINE_READOUT_MAX_PLANS) return bad("n_plans outside 0..256");
+    if (n_plans == 0) return 0;
+    if (!test_masks || !M || !K || !sums) return bad("test_masks, M, K and sums are required");
+    if (n_rows > 0 && (!a || !y || !group)) return bad("a, y and group are required");
+    if ((uintptr_t)a % 4 || (uintptr_t)y % 4 || (uintptr_t)group % 4 || (uintptr_t)M % 4 || (uintptr_t)K % 4 || (uintptr_t)sums % 8 ||
+        (uintptr_t)filtered % 4)
+        return bad("misaligned argument");
+    OkfSweepArgs k{};
+    if (int e = okf_check_centre(who, centre, n_joints, k.c)) return e;
+    for (int t = 0; t < n_plans; ++t) {
+        if (test_masks[t] >> CP_ONLINE_READOUT_MAX_GROUPS) return bad("a plan's test mask names a group at or above 16");
+        k.mask[t] = (unsigned short)test_masks[t];
+    }
+    k.a = a; k.y = y; k.group = group; k.M = M; k.K = K; k.sums = sums; k.filtered = filtered; k.n_rows = (int)n_rows; k.D = n_joints;
+    hipLaunchKernelGGL(okf_sweep_kernel, dim3(n_plans), dim3(64), 0, (hipStream_t)stream, k);
+    CKL("okf_sweep_kernel");
+    return 0;
+}
+
+static int okf_check(const char* who, const cp_online_kf_config* c, int32_t n_streams, void* ws, size_t ws_bytes) {
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (!c || !ws) return bad("config and workspace are required");
+    if (n_streams < 1 || n_streams > CP_ONLINE_MULTI_MAX_STREAMS) return bad("n_streams outside 1..256");
+    if (c->rate < 1 || c->rate > CP_ONLINE_KIN_ONE) return bad("rate outside 1..4096");
+    if ((uintptr_t)ws % 256) return bad("workspace not 256-byte aligned");
+    if (ws_bytes < (size_t)n_streams * sizeof(OkfState)) return ol_fail(CP_ERR_WORKSPACE, who, "workspace too small");
+    return 0;
+}
+
+extern "C" size_t cp_online_kf_workspace_bytes(int32_t n_streams) {
+    if (n_streams < 1) n_streams = 1;
+    return align256((size_t)n_streams * sizeof(OkfState));
+}
+
+extern "C" int cp_online_kf_set_model(const cp_online_kf_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index,
+                                      const float* W, const float* b, int32_t n_joints, const float* lo, const float* span,
+                                      const int32_t* rest, const float* M, const float* K, void* stream) {
+    const char* who = "cp_online_kf_set_model";
+    if (int e = okf_check(who, cfg, n_streams, ws, ws_bytes)) return e;
+    if (int e = ol_check_index(who, index, n_streams)) return e;
+    if (n_joints < 1 || n_joints > CP_ONLINE_KIN_MAX_JOINTS) return ol_fail(CP_ERR_ARG, who, "n_joints outside 1..32");
+    if (!W || !b || !lo || !span || !rest || !M || !K) return ol_fail(CP_ERR_ARG, who, "W, b, lo, span, rest, M and K are required");
+    if ((uintptr_t)W % 16 || (uintptr_t)b % 4 || (uintptr_t)M % 4 || (uintptr_t)K % 4) return ol_fail(CP_ERR_ARG, who, "misaligned W, b, M or K");
+    OkfModelArgs p{};
+    p.D = n_joints;
+    for (int d = 0; d < n_joints; ++d) {
+        if (!std::isfinite(lo[d])) return ol_fail(CP_ERR_ARG, who, "lo must be finite");
+        if (!(span[d] > 0.f) || !std::isfinite(span[d])) return ol_fail(CP_ERR_ARG, who, "span must be finite and > 0");
+        if (rest[d] < 0 || rest[d] > CP_ONLINE_KIN_ONE) return ol_fail(CP_ERR_ARG, who, "rest outside 0..4096");
+        p.lo[d] = lo[d];
+        p.span[d] = span[d];
+        p.rest[d] = rest[d];
+    }
+    hipLaunchKernelGGL(okf_set_model_kernel, dim3(1), dim3(OKF_THREADS), 0, (hipStream_t)stream, (OkfState*)ws + index, W, b, M, K, p);
+    CKL("okf_set_model_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_kf_reset(const cp_online_kf_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index, void* stream) {
+    const char* who = "cp_online_kf_reset";
+    if (int e = okf_check(who, cfg, n_streams, ws, ws_bytes)) return e;
+    if (index < -1 || index >= n_streams) return ol_fail(CP_ERR_ARG, who, "stream index outside -1..n_streams-1");
+    hipLaunchKernelGGL(okf_reset_kernel, dim3(index < 0 ? n_streams : 1), dim3(OKF_THREADS), 0, (hipStream_t)stream, (OkfState*)ws,
+                       index < 0 ? 0 : index);
+    CKL("okf_reset_kernel");
+    return 0;
+}
+
+template <typename T>
+static int okf_push_launch(int32_t n_streams, const OkfPushArgs& a, void* stream) {
+    static bool attr_set = false;
+    if (!attr_set) {                                           // more than 64 KB of dynamic LDS needs the opt-in once per process and kernel
+        CK(hipFuncSetAttribute((const void*)okf_push_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, OKF_PUSH_LDS));
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((okf_push_kernel<T>), dim3(n_streams), dim3(OKF_THREADS), OKF_PUSH_LDS, (hipStream_t)stream, a);
+    CKL("okf_push_kernel");
+    return 0;
+}
+
+extern "C" int cp_online_kf_push(const cp_online_kf_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, const void* tail,
+                                 int32_t dtype, int32_t ldt, const int32_t* cls, const int32_t* row0, const int32_t* m,
+                                 int32_t total_rows, float* raw, float* filtered, int32_t* pose, float* angle, void* stream) {
+    const char* who = "cp_online_kf_push";
+    auto bad = [&](const char* what) { return ol_fail(CP_ERR_ARG, who, what); };
+    if (int e = okf_check(who, cfg, n_streams, ws, ws_bytes)) return e;
+    if (dtype != CP_F32 && dtype != CP_BF16) return bad("dtype must be CP_F32 or CP_BF16");
+    if (total_rows < 0 || total_rows > CP_ONLINE_MULTI_MAX_ROWS) return bad("total_rows outside 0..65536");
+    if (total_rows == 0) return 0;
+    if (ldt < OKN_F) return bad("ldt must be at least 512");
+    if (!tail || !row0 || !m || !raw || !filtered || !pose || !angle) return bad("tail, row0, m, raw, filtered, pose and angle are required");
+    const size_t es = dtype == CP_BF16 ? 2 : 4;
+    if ((uintptr_t)tail % 16 || ((size_t)ldt * es) % 16 || (uintptr_t)cls % 4 || (uintptr_t)row0 % 4 || (uintptr_t)m % 4 ||
+        (uintptr_t)raw % 4 || (uintptr_t)filtered % 4 || (uintptr_t)pose % 4 || (uintptr_t)angle % 4)
+        return bad("misaligned argument");
+    OkfPushArgs a{};
+    a.states = (OkfState*)ws; a.tail = tail; a.cls = cls; a.row0 = row0; a.m = m; a.ldt = ldt; a.total_rows = total_rows;
+    a.rate = cfg->rate; a.raw = raw; a.filtered = filtered; a.pose = pose; a.angle = angle;
+    return ol_dispatch(dtype, [&](auto t) { return okf_push_launch<decltype(t)>(n_streams, a, stream); });
+}

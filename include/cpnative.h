@@ -1922,6 +1922,73 @@ int cp_online_kin_push(const cp_online_kin_config* cfg, int32_t n_streams, void*
                        int32_t ldt, const int32_t* cls, const int32_t* row0, const int32_t* m, int32_t total_rows, float* raw,
                        int32_t* pose, float* angle, void* stream);
 
+/* ---- pose filter: a steady-state Kalman stage behind the joint readout --------------------------------------------------------
+ * The joint readout above is filtered joint by joint with a ring mean.  This stage carries a model instead: the state is
+ * x = [theta (D), omega (D)] around the resting pose c[d] = lo[d] + ((float) rest[d] / 4096.f) * span[d]; how the joints move
+ * together between windows (A, W) is fitted to the glove, how wrong the readout is (Q) to its held-out error, and the Riccati
+ * recursion is iterated to a fixed gain K, so that a window costs x' = M x + K o with M = (I - K H) A, H = [I 0], o = a - c.  The
+ * numpy definitions are in contrastiveprosthetics_amd/kalman.py (moments_reference, design_reference, FilterReference,
+ * sweep_reference), which also state the order of every reduction; every entry equals them in every bit, float64 words
+ * included.  Nothing a push launches or emits changes.
+ *
+ * cp_online_kf_moments (one launch, one workgroup per group): a (the readout's prediction) and y (the target) are (n_rows,
+ *   n_joints) f32, group (n_rows) int32 (outside 0..n_groups-1: not used), centre (n_joints) f32 in host memory.  theta_k =
+ *   y_k - c, omega_k = theta_k - theta_{k-1}, s_k = [theta_k, omega_k], e_k = a_k - y_k (f32 subtractions).  Index k counts for
+ *   group r when windows k-1, k and k+1 all have group r.  Per group, over its counted k in order, in f64 (an exact product and
+ *   one rounded add per term): count, G = sum s_k s_k^T, C = sum s_{k+1} s_k^T, S = sum s_{k+1} s_{k+1}^T (each (n_groups, 2D, 2D))
+ *   and E = sum e_{k+1} e_{k+1}^T (n_groups, D, D).
+ *
+ * cp_online_kf_design (one launch per CP_ONLINE_KF_PLANS_PER_LAUNCH plans, one workgroup per plan): per plan (host memory) the
+ *   group sums over plan.groups in ascending order divided by n; A from (G + lambda I) A^T = C^T by Cholesky with lambda = lam *
+ *   tr(G) / (2D); W = rho * (sym(S - A C^T - C A^T + A G A^T) + 1e-6 * tr(S) / (2D) * I); Q = kappa * (E + 1e-6 * tr(E) / D * I);
+ *   P = W, then plan.iters times P- = A P A^T + W, K = P- H^T (H P- H^T + Q)^-1 by Cholesky, P = (I - K H) P- (I - K H)^T + K Q K^T.
+ *   M (n_plans, 2D, 2D) and K (n_plans, 2D, D) f32, delta (n_plans) f64 = max|P_T - P_{T-1}| / max|P_T|, status (n_plans) int32:
+ *   0, 1 (fewer than 2D + 1 samples), 2 (G + lambda I is not positive definite) or 3 (an innovation matrix is not); with a status
+ *   M and K are zero and delta is +inf.  scratch: cp_online_kf_design_bytes(n_plans), 256-byte aligned.
+ *
+ * cp_online_kf_sweep (one launch, one wave per plan): the filter step over the rows whose group is in test_masks[t] (host
+ *   memory), in row order, restarted wherever the row before has another group; sums[t][d] = the seven of cp_online_kin_score on
+ *   the filtered pose against y (rows whose filtered pose is NaN skipped) and sum (filtered_k - filtered_{k-1})^2 inside runs.
+ *   filtered (n_plans, n_rows, n_joints) f32 or NULL: the filtered pose, NaN on the rows outside the plan's mask.
+ *
+ * The stage (cp_online_kf_workspace_bytes, _set_model, _reset, _push): as the joint-angle stage, with M (2D, 2D) and K (2D, D)
+ *   f32 ON THE DEVICE beside W and b.  Per row: a = the pose matvec (raw, the joint-angle stage's bits); o = a - c; before the
+ *   first row whose o is all finite filtered is NaN and that row sets x = [o, 0]; later a row with a non-finite o leaves x as it
+ *   is, else x'[i] = sum_j M[i][j] x[j] + sum_j K[i][j] o[j], one accumulator, j ascending from +0.0f, each product rounded, then
+ *   added; filtered = x[d] + c[d]; t, q, the rate limit and angle follow the joint-angle stage with smooth = 1.  raw, filtered,
+ *   pose, angle are (total_rows, CP_ONLINE_KIN_MAX_JOINTS).  Streams are left untouched as cp_online_kin_push leaves them. */
+#define CP_ONLINE_KF_MAX_ITERS 1024
+#define CP_ONLINE_KF_PLANS_PER_LAUNCH 128
+#define CP_ONLINE_KF_SUMS 8
+typedef struct cp_online_kf_plan {
+    uint32_t groups;                      /* bit mask of the groups the plan is fitted on */
+    int32_t iters;                        /* Riccati iterations, 1..CP_ONLINE_KF_MAX_ITERS */
+    double lam;                           /* relative ridge of the trajectory fit, >= 0 */
+    double rho;                           /* scale of the process noise, > 0 */
+    double kappa;                         /* scale of the measurement noise, > 0 */
+} cp_online_kf_plan;
+typedef struct cp_online_kf_config {
+    int32_t rate;                         /* largest change of a joint's level per window, 1..CP_ONLINE_KIN_ONE */
+    int32_t reserved0;
+} cp_online_kf_config;
+int cp_online_kf_moments(const float* a, const float* y, const int32_t* group, int64_t n_rows, int32_t n_joints, int32_t n_groups,
+                         const float* centre, double* G, double* C, double* S, double* E, int32_t* count, void* stream);
+size_t cp_online_kf_design_bytes(int32_t n_plans);
+int cp_online_kf_design(const double* G, const double* C, const double* S, const double* E, const int32_t* count, int32_t n_joints,
+                        int32_t n_groups, const cp_online_kf_plan* plans, int32_t n_plans, float* M, float* K, double* delta,
+                        int32_t* status, void* scratch, size_t scratch_bytes, void* stream);
+int cp_online_kf_sweep(const float* a, const float* y, const int32_t* group, int64_t n_rows, int32_t n_joints,
+                       const uint32_t* test_masks, int32_t n_plans, const float* M, const float* K, const float* centre, double* sums,
+                       float* filtered, void* stream);
+size_t cp_online_kf_workspace_bytes(int32_t n_streams);
+int cp_online_kf_set_model(const cp_online_kf_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index, const float* W,
+                           const float* b, int32_t n_joints, const float* lo, const float* span, const int32_t* rest, const float* M,
+                           const float* K, void* stream);
+int cp_online_kf_reset(const cp_online_kf_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, int32_t index, void* stream);
+int cp_online_kf_push(const cp_online_kf_config* cfg, int32_t n_streams, void* ws, size_t ws_bytes, const void* tail, int32_t dtype,
+                      int32_t ldt, const int32_t* cls, const int32_t* row0, const int32_t* m, int32_t total_rows, float* raw,
+                      float* filtered, int32_t* pose, float* angle, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

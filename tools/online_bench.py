@@ -93,6 +93,7 @@ counted with torch.profiler over a few pushes.  One JSON line per case, and a ta
     python tools/online_bench.py --readout --iters 200 --out profiles/online_readout.txt
     python tools/online_bench.py --stream-projections --iters 50 --out profiles/online_stream_projections.txt
     python tools/online_bench.py --kinematics --iters 100 --out profiles/online_kinematics.txt
+    python tools/online_bench.py --kalman --iters 100 --out profiles/online_kalman.txt
 """
 import argparse
 import json
@@ -174,6 +175,8 @@ def main():
                     "set and every slot set, next to the same decoder built without the option")
     ap.add_argument("--kinematics", action="store_true", help="joint-angle decoding: the push with and without JointAngles behind it at "
                     "1, 16 and 256 streams, and moments, solve, apply and score of a 14,514-window recording x 20 joints")
+    ap.add_argument("--kalman", action="store_true", help="the pose filter: the push bare, with JointAngles and with PoseFilter behind it "
+                    "at 1, 16 and 256 streams, and cross-fit, moments, design, sweep and pick_filter of a 14,514-window recording x 20 joints")
     a = ap.parse_args()
     if a.readout:
         return readout_main(a)
@@ -214,6 +217,8 @@ def main():
         return gate_main(a, e, stream, mean, std, classes)
     if a.drive:
         return drive_main(a, e, stream, mean, std, classes)
+    if a.kalman:
+        return kalman_main(a, e, stream, mean, std, classes)
     if a.kinematics:
         return kinematics_main(a, e, stream, mean, std, classes)
     if a.adapt and a.streams:
@@ -1018,6 +1023,138 @@ def kinematics_main(a, e, stream, mean, std, classes):
                 f.write(f"{r['case']:<28} {r['windows']:>8} {r['device_ms']:>10.3f} {r['p90_ms']:>9.3f} {r['definition_ms']:>14.1f}  {r['note']}\n")
             f.write(f"# pick_pose on the synthetic person (tail inputs lead the angles by 2 windows): mean held-out RMSE per (lag, ridge) "
                     f"{np.round(pick['rmse_mean'], 3).tolist()} degrees, picked lag {pick['lag']} ridge {pick['ridge']}\n")
+
+
+def kalman_main(a, e, stream, mean, std, classes):
+    """--kalman.  Part 1: a push of 1 and of 25 windows per stream bare, with a `JointAngles` stage (smooth 5) and with a
+    `PoseFilter` stage behind it (20 joints), at 1, 16 and 256 streams, f32 and bf16, each on a decoder of its own in this one
+    process: host-synchronised medians and kernels per push.  The bare push is timed twice, before and after the staged ones; the
+    difference of the two medians is the run-to-run spread the stages' cost is read against.  Part 2: the cross-fit, moments,
+    design and sweep on the synthetic person of kinematics.kinematics_recording(41, 6, 59): 14,514 windows x 20 joints, 6
+    repetitions, beside the numpy definitions, and `pick_filter`'s table at lag 0 and 2."""
+    from contrastiveprosthetics_amd import kalman as KF
+    from contrastiveprosthetics_amd import kinematics as K
+    rng = np.random.default_rng(0)
+    D = 20
+    W = (0.05 * rng.standard_normal((D, 512))).astype(np.float32)
+    b = rng.standard_normal(D).astype(np.float32)
+    lo, span, rest = np.full(D, -2.0, np.float32), np.full(D, 4.0, np.float32), np.full(D, 2048, np.int32)
+    walk = np.cumsum(rng.standard_normal((400, D)), axis=0).astype(np.float32) * 0.1
+    noisy = (walk + 0.3 * rng.standard_normal((400, D))).astype(np.float32)
+    des = KF.design_reference(KF.moments_reference(noisy, walk, None, 1, KF.centre(lo, span, rest)), [(1, 1e-3, 1.0, 1.0, 64)])
+    if des["status"][0] != 0:
+        raise SystemExit("the bench's filter has no solution")
+    Mf, Kf = des["M"][0], des["K"][0]
+    rows = []
+    for dtype in ("f32", "bf16"):
+        for S in (1, 16, 256):
+            for n in (20, 500):
+                m = n // 20
+
+                def decoder():
+                    if S == 1:
+                        return OnlineDecoder(e, mean, std, classes=classes, dtype=dtype)
+                    d = MultiStreamDecoder(e, mean, std, S, dtype=dtype, max_rows=S * m)
+                    for s in range(S):
+                        d.set_classes(s, classes=classes)
+                    return d
+
+                plain, under_j, under_f = decoder(), decoder(), decoder()
+                joint, filt = K.JointAngles(under_j, smooth=5, rate=400), KF.PoseFilter(under_f, rate=400)
+                for s in range(S):
+                    joint.set_model(*((s,) if S > 1 else ()), W, b, lo, span, rest)
+                    filt.set_model(*((s,) if S > 1 else ()), W, b, lo, span, rest, Mf, Kf)
+                pos = [0]
+                span_s = stream.shape[0] - S * n
+
+                def chunk():
+                    base = pos[0] % span_s
+                    pos[0] += S * n
+                    return stream[base:base + S * n]
+
+                if S == 1:
+                    bare, posed, filtered = (lambda: plain.push(chunk())), (lambda: joint.push(chunk())), (lambda: filt.push(chunk()))
+                else:
+                    bare, posed, filtered = ((lambda: plain.push_packed(chunk(), [n] * S)), (lambda: joint.push_packed(chunk(), [n] * S)),
+                                             (lambda: filt.push_packed(chunk(), [n] * S)))
+                b1, _ = time_pushes(bare, a.iters, a.warmup)
+                jm, _ = time_pushes(posed, a.iters, a.warmup)
+                fm, fp90 = time_pushes(filtered, a.iters, a.warmup)
+                b2, _ = time_pushes(bare, a.iters, a.warmup)
+                kb, kj, kf = count_kernels(bare, pushes=3), count_kernels(posed, pushes=3), count_kernels(filtered, pushes=3)
+                if kf != kb + 1 or kj != kb + 1:
+                    raise SystemExit(f"a filtered push launches {kf} kernels, a posed one {kj}, a bare one {kb}: not one more")
+                bm = 0.5 * (b1 + b2)
+                r = dict(dtype=dtype, streams=S, windows=m, bare_us=round(bm, 1), joint_us=round(jm, 1), filtered_us=round(fm, 1),
+                         filtered_p90_us=round(fp90, 1), joint_adds_us=round(jm - bm, 1), filter_adds_us=round(fm - bm, 1),
+                         bare_spread_us=round(abs(b1 - b2), 1), kernels_bare=kb, kernels_filtered=kf)
+                print(json.dumps(r), flush=True)
+                rows.append(r)
+                del plain, under_j, under_f, joint, filt
+                torch.cuda.empty_cache()
+    # ---- part 2: the fit on a whole recording
+    k, reps, seg = 41, 6, 59
+    p = K.kinematics_recording(k, reps, seg, joints=D, seed=0)
+    iters = max(a.iters // 20, 3)
+    fits, picks = [], []
+
+    def row(case, fn, n_iter, definition, m, note=""):
+        fn()
+        med, p90 = time_pushes(fn, n_iter, 1)
+        t0 = time.perf_counter()
+        definition()
+        r = dict(case=case, windows=m, device_ms=round(med / 1e3, 3), p90_ms=round(p90 / 1e3, 3),
+                 definition_ms=round((time.perf_counter() - t0) * 1e3, 1), note=note)
+        print(json.dumps(r), flush=True)
+        fits.append(r)
+
+    for lag in (0, 2):
+        y = K.window_targets(p["glove"], 0, lag)
+        m = int(y.shape[0])
+        rep = (p["rep"][:m], reps)
+        u_d = torch.from_numpy(p["u"][:m]).cuda()
+        a_d = KF.crossfit_inputs(u_d, y, rep, 0.01)
+        lo_p, span_p, rest_p = K.limits(y, p["cls"][:m], 0)
+        fit = K.PoseFit(torch.zeros(1, D, 512), torch.zeros(1, D), [0], [(tuple(range(reps)), 0.01)], {}, lo_p, span_p, rest_p, lag)
+        c = KF.centre(lo_p, span_p, rest_p)
+        if lag == 0:
+            a_h = a_d.cpu().numpy()
+            rows_g, plans, tests = KF._pick_grid(KF.KAPPAS, (1.0,), 1e-3, 128, reps)
+            row("crossfit (6 folds)", lambda: KF.crossfit_inputs(u_d, y, rep, 0.01), iters, lambda: None, m, "no definition timed")
+            row(f"moments ({reps} groups)", lambda: KF.moments(a_d, y, rep[0], reps, c), iters,
+                lambda: KF.moments_reference(a_h, y, rep[0], reps, c), m)
+            mom = KF.moments(a_d, y, rep[0], reps, c)
+            mom_h = {key: v.cpu().numpy() for key, v in mom.items()}
+            row("design (1 plan, T = 128)", lambda: KF.design(mom, plans[:1]), iters, lambda: KF.design_reference(mom_h, plans[:1]), m)
+            row(f"design ({len(plans)} plans, T = 128)", lambda: KF.design(mom, plans), iters, lambda: KF.design_reference(mom_h, plans), m)
+            des = KF.design(mom, plans)
+            Mh, Kh = des["M"].cpu().numpy(), des["K"].cpu().numpy()
+            row(f"sweep ({len(plans)} plans)", lambda: KF.sweep(a_d, y, rep[0], tests, des["M"], des["K"], c), iters,
+                lambda: KF.sweep_reference(a_h, y, rep[0], tests[:1], Mh[:1], Kh[:1], c), m, "definition: one plan")
+        pick = KF.pick_filter(a_d, y, rep, fit)
+        picks.append((lag, pick))
+        print(json.dumps(dict(lag=lag, table=np.round(pick["table"], 4).tolist(), pick=pick["pick"], delta=float(pick["delta"].max()))), flush=True)
+    if a.out:
+        name = torch.cuda.get_device_name(0)
+        with open(a.out, "w") as f:
+            f.write(f"# tools/online_bench.py --kalman --iters {a.iters} --warmup {a.warmup} on {name}\n")
+            f.write("# bare = decoder.push / push_packed, joint = JointAngles.push (smooth 5), filtered = PoseFilter.push, each on a decoder of\n"
+                    "# its own (20 joints); per-push wall time, host-synchronised medians; bare is timed before and after the staged pushes:\n"
+                    "# bare_us is the mean of the two medians, spread their difference; adds = staged - bare; kernels per push (torch.profiler)\n")
+            f.write(f"{'dtype':<5} {'streams':>7} {'windows':>7} {'bare_us':>9} {'joint_us':>9} {'filtered_us':>11} {'p90_us':>9} {'joint_adds':>10} "
+                    f"{'filter_adds':>11} {'spread':>8} {'kernels':>9}\n")
+            for r in rows:
+                f.write(f"{r['dtype']:<5} {r['streams']:>7} {r['windows']:>7} {r['bare_us']:>9.1f} {r['joint_us']:>9.1f} {r['filtered_us']:>11.1f} "
+                        f"{r['filtered_p90_us']:>9.1f} {r['joint_adds_us']:>10.1f} {r['filter_adds_us']:>11.1f} {r['bare_spread_us']:>8.1f} "
+                        f"{r['kernels_bare']:>4.0f}+{r['kernels_filtered'] - r['kernels_bare']:.0f}\n")
+            f.write(f"# the synthetic person of kinematics.kinematics_recording({k}, {reps}, {seg}): 14,514 windows x {D} joints, f32\n")
+            f.write("# wall time, host-synchronised (median, p90); definition_ms: the numpy definition on the host, once\n")
+            f.write(f"{'call':<28} {'windows':>8} {'device_ms':>10} {'p90_ms':>9} {'definition_ms':>14}  note\n")
+            for r in fits:
+                f.write(f"{r['case']:<28} {r['windows']:>8} {r['device_ms']:>10.3f} {r['p90_ms']:>9.3f} {r['definition_ms']:>14.1f}  {r['note']}\n")
+            for lag, pick in picks:
+                f.write(f"# pick_filter at lag {lag} (ridge 0.01, T = 128): rows (rho, kappa, mean held-out RMSE in degrees, jitter) "
+                        f"{np.round(pick['table'], 4).tolist()}, picked row {pick['pick']}, largest delta {float(pick['delta'].max()):.2e}\n")
 
 
 class _Ids:
