@@ -251,6 +251,10 @@ SYMBOLS = {
     "cp_glove_forward": (C.c_int, [_P(cp_config), _P(cp_glove_params), _fp, C.c_int64, _fp, C.c_size_t, _fp, _fp]),
     "cp_head_glove": (C.c_int, [_P(cp_config), _fp, _fp, _fp, C.c_int64, C.c_int32, C.c_int32, _fp, C.c_size_t, _fp,
                                 C.c_size_t, _fp, _fp, _fp, _fp]),
+    "cp_head_temp": (C.c_int, [_P(cp_config), _P(cp_params), _fp, _fp, C.c_int64, C.c_int32, C.c_int32, _fp, C.c_size_t,
+                               _fp, _fp, _fp, _P(cp_params), _fp, _fp, _fp]),
+    "cp_head_glove_temp": (C.c_int, [_P(cp_config), _fp, _fp, _fp, C.c_int64, C.c_int32, C.c_int32, _fp, C.c_size_t, _fp,
+                                     C.c_size_t, _fp, _fp, _fp, _fp, _fp, _fp]),
     "cp_glove_backward": (C.c_int, [_P(cp_config), _P(cp_glove_params), C.c_int64, _fp, C.c_size_t, _P(cp_glove_params), _fp]),
     "cp_optimizer_scratch_floats": (C.c_size_t, [_P(C.c_int64), C.c_int32]),
     "cp_l2_norms": (C.c_int, [_fp, _P(C.c_int64), _P(C.c_int64), _P(C.c_int32), _P(C.c_int32), C.c_int32,

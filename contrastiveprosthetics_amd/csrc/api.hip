@@ -260,7 +260,8 @@ extern "C" int cp_global_negatives(const cp_params* p, const float* z_all, int64
 
 static int head_impl(const cp_config* cfg, const cp_params* p, const float* z, const int64_t* labels, int64_t n_groups,
                      int32_t V, int32_t want_grad, void* ws, size_t ws_bytes, float* loss_correct, int32_t* pred,
-                     float* logits, cp_params* grads, const float* gneg, void* stream);
+                     float* logits, cp_params* grads, const float* gneg, void* stream, bool temp = false,
+                     const float* logit_scale = nullptr, float* d_logit_scale = nullptr);
 
 extern "C" int cp_head(const cp_config* cfg, const cp_params* p, const float* z, const int64_t* labels, int64_t n_groups,
                        int32_t V, int32_t want_grad, void* ws, size_t ws_bytes, float* loss_correct, int32_t* pred,
@@ -275,9 +276,20 @@ extern "C" int cp_head_gneg(const cp_config* cfg, const cp_params* p, const floa
     return head_impl(cfg, p, z, labels, n_groups, V, want_grad, ws, ws_bytes, loss_correct, pred, logits, grads, gh, stream);
 }
 
+// the temperature twin (include/cpnative.h): logits = exp(clamp(*logit_scale)) * cosines; the reference's per-group loss only
+extern "C" int cp_head_temp(const cp_config* cfg, const cp_params* p, const float* z, const int64_t* labels, int64_t n_groups,
+                            int32_t V, int32_t want_grad, void* ws, size_t ws_bytes, float* loss_correct, int32_t* pred,
+                            float* logits, cp_params* grads, const float* logit_scale, float* d_logit_scale, void* stream) {
+    if (!logit_scale) return fail(CP_ERR_ARG, "cp_head_temp: logit_scale (a device float) is NULL");
+    if (want_grad && !d_logit_scale) return fail(CP_ERR_ARG, "cp_head_temp: gradients need d_logit_scale");
+    return head_impl(cfg, p, z, labels, n_groups, V, want_grad, ws, ws_bytes, loss_correct, pred, logits, grads, nullptr, stream, true,
+                     logit_scale, d_logit_scale);
+}
+
 static int head_impl(const cp_config* cfg, const cp_params* p, const float* z, const int64_t* labels, int64_t n_groups,
                      int32_t V, int32_t want_grad, void* ws, size_t ws_bytes, float* loss_correct, int32_t* pred,
-                     float* logits, cp_params* grads, const float* gneg, void* stream) {
+                     float* logits, cp_params* grads, const float* gneg, void* stream, bool temp, const float* logit_scale,
+                     float* d_logit_scale) {
     WS w;
     if (int e = check_cfg(cfg, ws, ws_bytes, &w)) return e;
     // (n_groups % V: group g reads the z rows of batch entry g / V, V to a position -- a remainder would reach past n_windows)
@@ -296,10 +308,15 @@ static int head_impl(const cp_config* cfg, const cp_params* p, const float* z, c
     a.G = n_groups; a.V = V; a.want_grad = want_grad; a.dz_ld = 64; a.dz = base + w.dz;
     a.logits = logits; a.pred = pred; a.partials = (float*)(base + w.head_part);
     a.gneg = gneg;
+    a.logit_scale = logit_scale;
     const int blocks = grid_rows(n_groups, HEAD_WAVES * (n_groups >= 2048 ? 2 : 1), kHeadBlocksMax);   // (>= 2048 groups: two per wave, half the prologues)
     // CP_FP8 (BASELINE config 4): the logits on the block-scaled 8-bit MFMA; "fp8_head_f32" keeps the f32 products (tests)
     const bool f8l = cfg->dtype == CP_FP8 && !opt(cfg, CP_OPT_FP8_HEAD_F32);
-    if (cfg->dtype != CP_F32) {
+    if (temp) {
+        if (cfg->dtype == CP_F32) hipLaunchKernelGGL((head_kernel<float, false, false, false, true>), dim3(blocks), dim3(256), 0, st, a);
+        else if (f8l) hipLaunchKernelGGL((head_kernel<bf16_t, false, false, true, true>), dim3(blocks), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((head_kernel<bf16_t, false, false, false, true>), dim3(blocks), dim3(256), 0, st, a);
+    } else if (cfg->dtype != CP_F32) {
         if (f8l) {
             if (gneg) hipLaunchKernelGGL((head_kernel<bf16_t, false, true, true>), dim3(blocks), dim3(256), 0, st, a);
             else hipLaunchKernelGGL((head_kernel<bf16_t, false, false, true>), dim3(blocks), dim3(256), 0, st, a);
@@ -316,7 +333,8 @@ static int head_impl(const cp_config* cfg, const cp_params* p, const float* z, c
     const PreReduce pre{a.partials, (float*)(base + w.partials2), st};
     const float* pp = pre(nr, HEAD_PART, 2 * REDUCE_SLICES);
     hipLaunchKernelGGL(head_finalize_kernel, dim3(1), dim3(256), 0, st, pp, nr, n_groups, p->easy_w, p->easy_b,
-                       want_grad, loss_correct, want_grad ? grads->easy_w : nullptr, want_grad ? grads->easy_b : nullptr);
+                       want_grad, loss_correct, want_grad ? grads->easy_w : nullptr, want_grad ? grads->easy_b : nullptr,
+                       logit_scale, (temp && want_grad) ? d_logit_scale : nullptr);
     CKL("head_finalize_kernel");
     return 0;
 }
@@ -558,9 +576,32 @@ extern "C" int cp_glove_forward(const cp_config* cfg, const cp_glove_params* gp,
     return glove_forward_t<float>(cfg, gp, glove, rows, (unsigned char*)gws, w, zg, (hipStream_t)stream);
 }
 
+static int head_glove_impl(const cp_config* cfg, const float* z, const float* zg, const int64_t* labels, int64_t n_groups,
+                           int32_t V, int32_t want_grad, void* ws, size_t ws_bytes, void* gws, size_t gws_bytes,
+                           float* loss_correct, int32_t* pred, float* logits, void* stream, bool temp, const float* logit_scale,
+                           float* d_logit_scale);
+
 extern "C" int cp_head_glove(const cp_config* cfg, const float* z, const float* zg, const int64_t* labels, int64_t n_groups,
                              int32_t V, int32_t want_grad, void* ws, size_t ws_bytes, void* gws, size_t gws_bytes,
                              float* loss_correct, int32_t* pred, float* logits, void* stream) {
+    return head_glove_impl(cfg, z, zg, labels, n_groups, V, want_grad, ws, ws_bytes, gws, gws_bytes, loss_correct, pred, logits, stream,
+                           false, nullptr, nullptr);
+}
+
+extern "C" int cp_head_glove_temp(const cp_config* cfg, const float* z, const float* zg, const int64_t* labels, int64_t n_groups,
+                                  int32_t V, int32_t want_grad, void* ws, size_t ws_bytes, void* gws, size_t gws_bytes,
+                                  float* loss_correct, int32_t* pred, float* logits, const float* logit_scale, float* d_logit_scale,
+                                  void* stream) {
+    if (!logit_scale) return fail(CP_ERR_ARG, "cp_head_glove_temp: logit_scale (a device float) is NULL");
+    if (want_grad && !d_logit_scale) return fail(CP_ERR_ARG, "cp_head_glove_temp: gradients need d_logit_scale");
+    return head_glove_impl(cfg, z, zg, labels, n_groups, V, want_grad, ws, ws_bytes, gws, gws_bytes, loss_correct, pred, logits, stream,
+                           true, logit_scale, d_logit_scale);
+}
+
+static int head_glove_impl(const cp_config* cfg, const float* z, const float* zg, const int64_t* labels, int64_t n_groups,
+                           int32_t V, int32_t want_grad, void* ws, size_t ws_bytes, void* gws, size_t gws_bytes,
+                           float* loss_correct, int32_t* pred, float* logits, void* stream, bool temp, const float* logit_scale,
+                           float* d_logit_scale) {
     WS w;
     if (int e = check_cfg(cfg, ws, ws_bytes, &w)) return e;
     if (!z || !zg || !labels || !loss_correct || !pred || V <= 0 || n_groups * CP_TASKS != cfg->n_windows || n_groups % V != 0)
@@ -580,8 +621,13 @@ extern "C" int cp_head_glove(const cp_config* cfg, const float* z, const float* 
     a.z = z; a.labels = labels; a.zg = zg; a.dzg = gbase + gw.dzg; a.dzg_ld = 64;
     a.G = n_groups; a.V = V; a.want_grad = want_grad; a.dz_ld = 64; a.dz = base + w.dz;
     a.logits = logits; a.pred = pred; a.partials = (float*)(base + w.head_part);
+    a.logit_scale = logit_scale;
     const int blocks = grid_rows(n_groups, HEAD_WAVES * (n_groups >= 2048 ? 2 : 1), kHeadBlocksMax);   // (>= 2048 groups: two per wave, half the prologues)
-    if (cfg->dtype != CP_F32)
+    if (temp && cfg->dtype != CP_F32)
+        hipLaunchKernelGGL((head_kernel<bf16_t, true, false, false, true>), dim3(blocks), dim3(256), 0, st, a);
+    else if (temp)
+        hipLaunchKernelGGL((head_kernel<float, true, false, false, true>), dim3(blocks), dim3(256), 0, st, a);
+    else if (cfg->dtype != CP_F32)
         hipLaunchKernelGGL((head_kernel<bf16_t, true>), dim3(blocks), dim3(256), 0, st, a);
     else
         hipLaunchKernelGGL((head_kernel<float, true>), dim3(blocks), dim3(256), 0, st, a);
@@ -590,7 +636,7 @@ extern "C" int cp_head_glove(const cp_config* cfg, const float* z, const float* 
     const PreReduce pre{a.partials, (float*)(base + w.partials2), st};
     const float* pp = pre(nr, HEAD_PART, 2 * REDUCE_SLICES);
     hipLaunchKernelGGL(head_finalize_kernel, dim3(1), dim3(256), 0, st, pp, nr, n_groups, (const float*)nullptr, (const float*)nullptr,
-                       0, loss_correct, (float*)nullptr, (float*)nullptr);
+                       0, loss_correct, (float*)nullptr, (float*)nullptr, logit_scale, (temp && want_grad) ? d_logit_scale : nullptr);
     CKL("head_finalize_kernel");
     return 0;
 }

@@ -34,9 +34,16 @@ struct HeadArgs {
     // global negatives (SURVEY 8e extension, one-hot class table only): gneg = [2][41] device floats {G, H} from
     // gneg_* below, or nullptr = the reference's per-group column softmax
     const float* gneg;
+    // TEMP = true (learnable temperature): one DEVICE float s = logit_scale, read once per kernel, so that a replayed graph
+    // sees the value the optimiser left; logits = tau * cosines, tau = exp(clamp(s, -ln 100, ln 100)); nullptr otherwise
+    const float* logit_scale;
 };
 #define GNEG_PART 64         // stride of the {G, H} table of the global-negatives extension
 #define HEAD_PART 704        // 2 + 41*16 = 658 used, padded to a multiple of 64 for reduce_rows_kernel
+#define HEAD_PART_DS 658     // TEMP: the block's sum of dl * logit (d loss / d logit_scale); reduce_rows_kernel folds all 704 columns
+// logit_scale is clamped to [-ln 100, ln 100] (as CLIP does).  float(ln 100) = 4.60517025 lies ABOVE ln 100 = 4.605170186: the bound
+// is the largest float inside the interval, so that "inside" means the same here and in a float64 reference
+#define HEAD_SCALE_MAX 4.605169773f
 
 // ---- the kernel ------------------------------------------------------------------------------------------------------
 // One wavefront per group, the 41x41 tile on the matrix cores (v_mfma_f32_16x16x4_f32, full fp32): lane l = (c = l & 15, q = l >> 4).
@@ -74,8 +81,17 @@ __device__ __forceinline__ float head_log2(float x) { return __builtin_amdgcn_lo
 // v_mfma_scale_f32_16x16x128_f8f6f4 per 16x16 tile on e4m3 copies of z_hat and E_hat (the 16 dims in the first 16 of the 128 k slots
 // of lane group 0, scale 2^0) instead of four f32 MFMAs; loss, predictions and dl are those of the quantised logits, the two gradient
 // products keep the f32 operands (straight-through).  e4m3 resolves [0.5, 1) in steps of 1/16: a logit moves by ~0.025 rms.
+//
+// TEMP (learnable temperature, off in the seven instantiations of the reference's loss, whose source path is untouched):
+//   logits = tau * z_hat . E_hat: tau * log2 e takes HEAD_LOG2E's place where z_hat enters the MFMAs (F8L: where the MX MFMA's result
+//   is scaled); loss, predictions and dl are today's functions of those logits; dz_hat = dl (tau E_hat) and dE_hat = dl^T (tau z_hat):
+//   the factor rides on the B operands of the two gradient products, where no fma can absorb it (a multiply of the product itself
+//   was contracted into the normalisation's fma and changed bits at tau = 1); z_hat_i . dz_hat_i is still sum_j dl l.
+//   d loss / d logit_scale = sum over groups, rows and columns of dl * logit: the per-lane pieces of dotz (F8L: its own sum of dl
+//   times the quantised, scaled logit) are carried across the wave's groups, summed per wave and per block in a fixed order and
+//   left in column HEAD_PART_DS of the block's partial row; head_finalize_kernel adds the rows.
 typedef __attribute__((ext_vector_type(8))) int head_i32x8;
-template <typename T, bool GLOVE = false, bool GNEG = false, bool F8L = false>
+template <typename T, bool GLOVE = false, bool GNEG = false, bool F8L = false, bool TEMP = false>
 __global__ __launch_bounds__(256, 2) void head_kernel(HeadArgs a) {
     using D = DT<T>;
     __shared__ float Eh[HEAD_T][HEAD_D];                               // normalised class table (one-hot path)
@@ -88,6 +104,8 @@ __global__ __launch_bounds__(256, 2) void head_kernel(HeadArgs a) {
     __shared__ int Cls[HEAD_WAVES][48];                                // class of position j in this group
     __shared__ float dE[HEAD_WAVES][HEAD_T][HEAD_D];                   // per-wave accumulator of d/dE_hat (by class): a fixed summation order
     __shared__ float wl[HEAD_WAVES], wc[HEAD_WAVES];
+    __shared__ float wds[TEMP ? HEAD_WAVES : 1];                       // TEMP: per-wave sum of dl * logit
+    static_assert(!(TEMP && GNEG), "the global-negatives table would need the temperature as well");
     __shared__ int Tg[48];                                             // CE target column of row i = labels[i]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, q = lane >> 4;
@@ -135,6 +153,11 @@ __global__ __launch_bounds__(256, 2) void head_kernel(HeadArgs a) {
     const bool lane_ok2 = 32 + c < HEAD_T;                             // lane-side index of the third tile is a real row / column
     const float cscale = 1.0f / (2.0f * (float)a.G * (float)HEAD_T);
     float loss_acc = 0.f, corr_acc = 0.f;                              // (loss in log2 units)
+    float tau = 1.f, tl2e = HEAD_LOG2E, ds_acc = 0.f;                  // TEMP: tau, tau * log2 e, this lane's sum of dl * l2
+    if constexpr (TEMP) {
+        tau = expf(fminf(fmaxf(*a.logit_scale, -HEAD_SCALE_MAX), HEAD_SCALE_MAX));
+        tl2e = tau * HEAD_LOG2E;
+    }
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
     for (int64_t g = (int64_t)blockIdx.x * HEAD_WAVES + wave; g < a.G; g += (int64_t)gridDim.x * HEAD_WAVES) {
@@ -160,7 +183,9 @@ __global__ __launch_bounds__(256, 2) void head_kernel(HeadArgs a) {
                 if (q == 0) En[wave][i] = ie;
             }
             e4 *= keep;
-            zA[t] = F8L ? z4 : z4 * HEAD_LOG2E; eA[t] = e4;
+            if constexpr (TEMP) zA[t] = F8L ? z4 : z4 * tl2e;
+            else zA[t] = F8L ? z4 : z4 * HEAD_LOG2E;
+            eA[t] = e4;
             *(f32x4*)&Zs[wave][i][4 * q] = z4;
             *(f32x4*)&Es[wave][i][4 * q] = e4;
             if (q == 0) { Nz[wave][i] = iz; Cls[wave][i] = cls; }
@@ -188,6 +213,11 @@ __global__ __launch_bounds__(256, 2) void head_kernel(HeadArgs a) {
             for (int ti = 0; ti < 3; ++ti)
 #pragma unroll
                 for (int tj = 0; tj < 3; ++tj) {
+                    if constexpr (TEMP) {
+                        L[ti][tj] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(zq[ti], eq[tj], zero4, 0, 0, 0, 127, 0, 127) * tl2e;
+                        Lt[tj][ti] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(eq[tj], zq[ti], zero4, 0, 0, 0, 127, 0, 127) * tl2e;
+                        continue;
+                    }
                     L[ti][tj] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(zq[ti], eq[tj], zero4, 0, 0, 0, 127, 0, 127) * HEAD_LOG2E;
                     Lt[tj][ti] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(eq[tj], zq[ti], zero4, 0, 0, 0, 127, 0, 127) * HEAD_LOG2E;
                 }
@@ -312,7 +342,8 @@ __global__ __launch_bounds__(256, 2) void head_kernel(HeadArgs a) {
                 const int i = 16 * ti + 4 * q + r;                     // row i on (q, r), column j = 16tj + c
                 const bool iok = ti < 2 || 4 * q + r < HEAD_T - 32;
                 const float rl = Rl[wave][i];
-                const float zB = Zs[wave][i][c];
+                float zB = Zs[wave][i][c];
+                if constexpr (TEMP) zB *= tau;                         // (the factor tau of dE_hat, on its way into the MFMA)
 #pragma unroll
                 for (int tj = 0; tj < 3; ++tj) {
                     const float s = L[ti][tj][r];
@@ -324,6 +355,8 @@ __global__ __launch_bounds__(256, 2) void head_kernel(HeadArgs a) {
                     dl *= cscale;
                     if (iok) Ts[wave][iok ? i : 0][16 * tj + c] = dl;
                     if constexpr (GLOVE) dote[tj] = fmaf(dl, s, dote[tj]);
+                    // (a padded row's dl is exactly 0 and a padded column's logit is exactly 0: no mask)
+                    if constexpr (TEMP && F8L) ds_acc = fmaf(dl, s, ds_acc);
                     dEp[tj] = head_mfma(dl, zB, dEp[tj]);              // A[m = c][k = q] = dl[i][16tj + c],  B[k = q][n = c] = z_hat[i][c]
                 }
             }
@@ -339,7 +372,8 @@ __global__ __launch_bounds__(256, 2) void head_kernel(HeadArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const bool jok = tj < 2 || 4 * q + r < HEAD_T - 32;
-                const float eB = Es[wave][16 * tj + 4 * q + r][c];
+                float eB = Es[wave][16 * tj + 4 * q + r][c];
+                if constexpr (TEMP) eB *= tau;                         // (the factor tau of dz_hat)
 #pragma unroll
                 for (int ti = 0; ti < 3; ++ti) {
                     const float dl = (tj == 2 && !jok) ? 0.f : dlt[ti][r];      // (columns 41..47 of the tile hold the padded columns' dl)
@@ -348,6 +382,8 @@ __global__ __launch_bounds__(256, 2) void head_kernel(HeadArgs a) {
                 }
             }
         }
+        // (rows 41..47 of the third tile read another row's dl: masked)
+        if constexpr (TEMP && !F8L) ds_acc += dotz[0] + dotz[1] + (lane_ok2 ? dotz[2] : 0.f);
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
             if constexpr (F8L) {
@@ -399,11 +435,16 @@ __global__ __launch_bounds__(256, 2) void head_kernel(HeadArgs a) {
     loss_acc = wave_sum(loss_acc) * HEAD_LN2;
     corr_acc = wave_sum(corr_acc);
     if (lane == 0) { wl[wave] = loss_acc; wc[wave] = corr_acc; }
+    if constexpr (TEMP) {
+        ds_acc = wave_sum(ds_acc) * HEAD_LN2;
+        if (lane == 0) wds[wave] = ds_acc;
+    }
     __syncthreads();
     float* part = a.partials + (int64_t)blockIdx.x * HEAD_PART;
     if (tid == 0) {
         part[0] = wl[0] + wl[1] + wl[2] + wl[3];
         part[1] = wc[0] + wc[1] + wc[2] + wc[3];
+        if constexpr (TEMP) part[HEAD_PART_DS] = wds[0] + wds[1] + wds[2] + wds[3];     // (0 without gradients)
     }
     for (int i = tid; i < HEAD_T * HEAD_D; i += 256) {
         const float* p = &dE[0][0][0];
@@ -412,10 +453,14 @@ __global__ __launch_bounds__(256, 2) void head_kernel(HeadArgs a) {
 }
 
 // one block: loss, correct count, class-table gradient (through E/|E| and E = W[:,c] + b)
+// d_logit_scale (TEMP launches with gradients, else nullptr) = the sum of column HEAD_PART_DS over the rows, in float64 in row order;
+// 0 where logit_scale lies outside [-ln 100, ln 100] (the clamp's gradient)
 __global__ __launch_bounds__(256) void head_finalize_kernel(const float* __restrict__ partials, int nblocks, int64_t G,
                                                             const float* __restrict__ easy_w, const float* __restrict__ easy_b,
                                                             int want_grad, float* __restrict__ out /* loss, correct */,
-                                                            float* __restrict__ d_easy_w, float* __restrict__ d_easy_b) {
+                                                            float* __restrict__ d_easy_w, float* __restrict__ d_easy_b,
+                                                            const float* __restrict__ logit_scale = nullptr,
+                                                            float* __restrict__ d_logit_scale = nullptr) {
     __shared__ double dEh[HEAD_T][HEAD_D];
     __shared__ float dEc[HEAD_T][HEAD_D];
     const int tid = threadIdx.x;
@@ -438,6 +483,11 @@ __global__ __launch_bounds__(256) void head_finalize_kernel(const float* __restr
         const int k = tid - 254;
         const double s = colsum(k);
         out[k] = k == 0 ? (float)(s / (2.0 * (double)G * HEAD_T)) : (float)s;
+    }
+    if (d_logit_scale != nullptr && tid == 253) {
+        const double s = colsum(HEAD_PART_DS);
+        const float ls = *logit_scale;
+        *d_logit_scale = (ls >= -HEAD_SCALE_MAX && ls <= HEAD_SCALE_MAX) ? (float)s : 0.f;
     }
     if (!want_grad) return;
     for (int i = tid; i < HEAD_T * HEAD_D; i += 256) (&dEh[0][0])[i] = colsum(2 + i);

@@ -37,10 +37,20 @@ def glove_bn_base(adabn: bool) -> str:
     return "glove_net.linear.2" + (".bn" if adabn else "")
 
 
-def param_specs(adabn: bool, d_e: int = CP_D_E, class_encoder: str = "onehot") -> "OrderedDict[str, Tuple[int, ...]]":
+LOGIT_SCALE_KEY = "logit_scale"
+# the parameter is clamped to [-ln 100, ln 100] after every step (as CLIP does): the bound as the kernel holds it, the largest
+# float32 inside the interval (float32(ln 100) itself lies above ln 100)
+_S32 = np.float32(np.log(100.0))
+LOGIT_SCALE_MAX = float(_S32 if float(_S32) <= np.log(100.0) else np.nextafter(_S32, np.float32(0.0)))
+
+
+def param_specs(adabn: bool, d_e: int = CP_D_E, class_encoder: str = "onehot",
+                logit_scale: bool = False) -> "OrderedDict[str, Tuple[int, ...]]":
     """Trainable tensors in reference state_dict order, without logit_scale.
     class_encoder="glove" adds the layers GLOVENet keeps as comments (code/models.py:386-391), where
-    nn.Module.state_dict() would list them: glove_net.linear.* before glove_net.easy.*."""
+    nn.Module.state_dict() would list them: glove_net.linear.* before glove_net.easy.*.
+    logit_scale=True (a LEARNT temperature): one trailing entry "logit_scale" of shape () -- trailing, so that every other
+    offset is what it is without it."""
     bn = bn_bases(adabn)
     s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
     s["emg_net.conv_emg.0.weight"] = (64, 1, 3, 3)
@@ -66,11 +76,16 @@ def param_specs(adabn: bool, d_e: int = CP_D_E, class_encoder: str = "onehot") -
     s["glove_net.easy.0.weight"] = (d_e, CP_TASKS)
     s["glove_net.easy.0.bias"] = (d_e,)
     s["glove_net.last.0.weight"] = (d_e, 256)
+    if logit_scale:
+        s[LOGIT_SCALE_KEY] = ()
     return s
 
 
 def l2_member(name: str) -> bool:
-    """code/models.py:344-349, 467-472: name (inside its sub-net) has neither 'bn' nor 'bias'."""
+    """code/models.py:344-349, 467-472: name (inside its sub-net) has neither 'bn' nor 'bias'.
+    The temperature belongs to neither sub-net's regulariser."""
+    if name == LOGIT_SCALE_KEY:
+        return False
     local = name.split(".", 1)[1]
     return ("bn" not in local) and ("bias" not in local)
 
@@ -186,9 +201,18 @@ def confusion(y_pred: torch.Tensor, labels: torch.Tensor, counts: torch.Tensor =
 
 class Engine:
     def __init__(self, adabn: bool = True, dtype: str = "bf16", dp_emg: float = 0.0, device="cuda",
-                 d_e: int = CP_D_E, seed: int = 0, class_encoder: str = "onehot"):
+                 d_e: int = CP_D_E, seed: int = 0, class_encoder: str = "onehot", temperature: Optional[float] = None,
+                 learn_temperature: bool = True):
+        """temperature=tau0 (None: the reference's loss on raw cosines, the entries and bits of an engine without the argument):
+        logits = tau * cosines, tau = exp(clamp(logit_scale, -ln 100, ln 100)), logit_scale initialised to ln tau0
+        (cp_head_temp / cp_head_glove_temp).  learn_temperature: logit_scale is the trailing entry of the parameter table,
+        in the class encoder's Adam group (lr_glove) and outside the L2 term; False keeps it a constant outside the table."""
         if class_encoder not in ("onehot", "glove"):
             raise ValueError("class_encoder must be 'onehot' or 'glove'")
+        if temperature is not None and not float(temperature) > 0.0:
+            raise ValueError("temperature must be positive")
+        self.temperature0 = None if temperature is None else float(temperature)
+        self.learn_temperature = temperature is not None and bool(learn_temperature)
         self.class_encoder = class_encoder
         if d_e != CP_D_E:
             raise ValueError(f"the HIP head kernel is built for d_e={CP_D_E} (code/train.py:183), got {d_e}")
@@ -203,9 +227,18 @@ class Engine:
         self.dp_emg = float(dp_emg)
         self.seed = int(seed)
         self.step_count = 0              # forward passes in train mode (dropout stream)
-        self.specs = param_specs(self.adabn, d_e, class_encoder)
+        self.specs = param_specs(self.adabn, d_e, class_encoder, logit_scale=self.learn_temperature)
         self.values = FlatStore(self.specs, self.device)
         self.grads = FlatStore(self.specs, self.device)
+        # the temperature's device scalar and the slot of its gradient: the table's trailing entry, or (fixed) tensors of their own
+        self.logit_scale = self.d_logit_scale = None
+        if self.learn_temperature:
+            self.logit_scale, self.d_logit_scale = self.values.views[LOGIT_SCALE_KEY], self.grads.views[LOGIT_SCALE_KEY]
+        elif self.temperature0 is not None:
+            self.logit_scale = torch.zeros((), dtype=torch.float32, device=self.device)
+            self.d_logit_scale = torch.zeros((), dtype=torch.float32, device=self.device)
+        if self.logit_scale is not None:
+            self.logit_scale.fill_(float(np.log(self.temperature0)))
         self.exp_avg = torch.zeros_like(self.values.flat)
         self.exp_avg_sq = torch.zeros_like(self.values.flat)
         self.adam_steps = 0
@@ -263,7 +296,7 @@ class Engine:
         self._tab_n = len(names)
         self._tab_off = (C.c_int64 * self._tab_n)(*[self.values.offsets[k][0] for k in names])
         self._tab_numel = (C.c_int64 * self._tab_n)(*[self.values.offsets[k][1] for k in names])
-        self._tab_group = (C.c_int32 * self._tab_n)(*[1 if k.startswith("glove_net.") else 0 for k in names])
+        self._tab_group = (C.c_int32 * self._tab_n)(*[1 if k.startswith("glove_net.") or k == LOGIT_SCALE_KEY else 0 for k in names])
         self._tab_l2 = (C.c_int32 * self._tab_n)(*[1 if l2_member(k) else 0 for k in names])
         nscratch = self.lib.cp_optimizer_scratch_floats(self._tab_numel, self._tab_n)
         self._opt_scratch = torch.zeros(nscratch, device=self.device)
@@ -395,7 +428,10 @@ class Engine:
     def head(self, z: torch.Tensor, labels: torch.Tensor, V: int, want_grad: bool, want_logits: bool = False,
              gneg: Optional[torch.Tensor] = None):
         """gneg: the {G, H} table of global_negatives() -> the column direction of the loss ranges over the global batch
-        (cp_head_gneg); None = the reference's per-group loss (cp_head)."""
+        (cp_head_gneg); None = the reference's per-group loss (cp_head; with a temperature cp_head_temp, which also leaves
+        d loss / d logit_scale in self.d_logit_scale when want_grad)."""
+        if gneg is not None and self.logit_scale is not None:
+            raise NotImplementedError("global negatives with a temperature: the {G, H} table would need tau as well")
         n = z.shape[0]
         G = n // CP_TASKS
         assert labels.dtype == torch.int64 and labels.numel() * V == n
@@ -405,7 +441,13 @@ class Engine:
         pred = torch.empty(G, CP_TASKS, dtype=torch.int32, device=self.device)
         logits = torch.empty(G, CP_TASKS, CP_TASKS, dtype=torch.float32, device=self.device) if want_logits else None
         ws, nb = self._ws_args(cfg)
-        if gneg is None:
+        if self.logit_scale is not None:
+            _lib.check(self.lib.cp_head_temp(C.byref(cfg), C.byref(self._p), z.data_ptr(), labels.data_ptr(), G, V,
+                                             1 if want_grad else 0, ws, nb, out.data_ptr(), pred.data_ptr(),
+                                             logits.data_ptr() if want_logits else None, C.byref(self._g),
+                                             self.logit_scale.data_ptr(), self.d_logit_scale.data_ptr(), self._stream()),
+                       "cp_head_temp")
+        elif gneg is None:
             _lib.check(self.lib.cp_head(C.byref(cfg), C.byref(self._p), z.data_ptr(), labels.data_ptr(), G, V,
                                         1 if want_grad else 0, ws, nb, out.data_ptr(), pred.data_ptr(),
                                         logits.data_ptr() if want_logits else None, C.byref(self._g), self._stream()),
@@ -419,12 +461,14 @@ class Engine:
         return out, pred, logits
 
     def global_negatives(self, z_all: torch.Tensor, labels: torch.Tensor, all_reduce=None) -> torch.Tensor:
-        """The (2,64) table {G, H} that head(..., gneg=) takes.
+        """The (2,64) table {G, H} that head(..., gneg=) takes (not with a temperature: the table would need tau).
         all_reduce=None (cp_global_negatives): z_all (n_all,16) f32 = the z rows of the GLOBAL batch (dist.all_gather_rows of every
         rank's encoder output; one rank: its own z).
         all_reduce=fn (cp_global_negatives_g / _h): z_all = THIS rank's rows only; fn(t) sums a 64-float device tensor over the ranks
         in place on the current stream (torch.distributed.all_reduce).  The class table is replicated, so G and H are sums of
         per-rank terms: two 256-byte collectives instead of the all-gather of z, same table."""
+        if self.logit_scale is not None:
+            raise NotImplementedError("global negatives with a temperature: the {G, H} table would need tau as well")
         assert z_all.dtype == torch.float32 and z_all.is_contiguous() and z_all.shape[1] == CP_D_E
         n_all = z_all.shape[0]
         need = self.lib.cp_global_negatives_scratch_floats(n_all)
@@ -511,6 +555,12 @@ class Engine:
         logits = torch.empty(G, CP_TASKS, CP_TASKS, dtype=torch.float32, device=self.device) if want_logits else None
         ws, nb = self._ws_args(cfg)
         gws, gnb = self._gws_args(zg.shape[0])
+        if self.logit_scale is not None:
+            _lib.check(self.lib.cp_head_glove_temp(C.byref(cfg), z.data_ptr(), zg.data_ptr(), labels.data_ptr(), G, V,
+                                                   1 if want_grad else 0, ws, nb, gws, gnb, out.data_ptr(), pred.data_ptr(),
+                                                   logits.data_ptr() if want_logits else None, self.logit_scale.data_ptr(),
+                                                   self.d_logit_scale.data_ptr(), self._stream()), "cp_head_glove_temp")
+            return out, pred, logits
         _lib.check(self.lib.cp_head_glove(C.byref(cfg), z.data_ptr(), zg.data_ptr(), labels.data_ptr(), G, V,
                                           1 if want_grad else 0, ws, nb, gws, gnb, out.data_ptr(), pred.data_ptr(),
                                           logits.data_ptr() if want_logits else None, self._stream()), "cp_head_glove")
@@ -568,7 +618,19 @@ class Engine:
                                             self._tab_numel, self._tab_group, self._tab_l2, self._tab_n, C.byref(h),
                                             self.adam_steps, self._opt_scratch.data_ptr(), self._l2_out.data_ptr(),
                                             self._stream()), "cp_l2_adam_step")
+        self._clamp_logit_scale()
         return self._l2_out
+
+    def _clamp_logit_scale(self):
+        # a learnt temperature stays inside [-ln 100, ln 100] (as CLIP clamps it): one scalar, in stream (and in a captured step)
+        if self.learn_temperature:
+            self.logit_scale.clamp_(-LOGIT_SCALE_MAX, LOGIT_SCALE_MAX)
+
+    def temperature(self) -> Optional[float]:
+        """tau = exp(clamp(logit_scale)) as the head applies it, or None without the option.  One host sync."""
+        if self.logit_scale is None:
+            return None
+        return float(np.exp(np.clip(np.float64(self.logit_scale.item()), -LOGIT_SCALE_MAX, LOGIT_SCALE_MAX)))
 
     def adam_step_graph(self, params: dict, grad_scale: float = 1.0) -> torch.Tensor:
         """cp_l2_adam_step with learning rates and bias corrections read from the device step state (graph capture)."""
@@ -578,6 +640,7 @@ class Engine:
                                                   self._tab_numel, self._tab_group, self._tab_l2, self._tab_n, C.byref(h),
                                                   self._graph_state.data_ptr(), self._opt_scratch.data_ptr(),
                                                   self._l2_out.data_ptr(), self._stream()), "cp_l2_adam_step_graph")
+        self._clamp_logit_scale()
         return self._l2_out
 
     # ------------------------------------------------------------------ debug (tests)
@@ -661,6 +724,8 @@ class Engine:
         g = torch.Generator().manual_seed(seed)
         bns = set(bn_bases(self.adabn)) | {glove_bn_base(self.adabn)}
         for k, shp in self.specs.items():
+            if k == LOGIT_SCALE_KEY:                         # ln tau0, set by the constructor: not drawn
+                continue
             base = k.rsplit(".", 1)[0]
             if base in bns:
                 self.values.views[k].fill_(1.0 if k.endswith("weight") else 0.0)
@@ -677,6 +742,8 @@ class Engine:
     def load_named(self, sd: Dict[str, torch.Tensor]):
         for k in self.specs:
             self.values.views[k].copy_(sd[k].to(self.device, torch.float32))
+        if self.logit_scale is not None and not self.learn_temperature and LOGIT_SCALE_KEY in sd:
+            self.logit_scale.copy_(sd[LOGIT_SCALE_KEY].to(self.device, torch.float32))
         for k in self.running:
             if k in sd:
                 self.running[k].copy_(sd[k].to(self.device))

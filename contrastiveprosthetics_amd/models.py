@@ -106,7 +106,8 @@ class _L2Fn(torch.autograd.Function):
 class Model(nn.Module):
     def __init__(self, params, adabn=True, train_model=True, prediction=False, glove=False, device="cuda",
                  dtype: str = "f32", seed: int = 42, class_encoder: str = "onehot", dropout_seed: int = None,
-                 global_negatives: bool = False, sync_bn: bool = False):
+                 global_negatives: bool = False, sync_bn: bool = False, temperature: float = None,
+                 learn_temperature: bool = True):
         """class_encoder="glove" (additive): class embeddings come from the glove-angle rows that
         TaskWrapper already delivers, through the layers GLOVENet keeps as comments (code/models.py:386-391, 461),
         instead of the one-hot table.  (The reference's own `glove` flag belongs to its --prediction classifier.)
@@ -116,7 +117,11 @@ class Model(nn.Module):
         batch): training batches take the class->EMG direction of the loss over the z embeddings of the GLOBAL batch
         (global_negatives=True or "gather": one RCCL all-gather of z per step, cp_global_negatives / cp_head_gneg;
         "reduce": the same table from per-rank partial sums and two 64-float all-reduces, cp_global_negatives_g / _h, no z
-        moves) / every BatchNorm of the sEMG encoder uses the statistics of the global batch (cp_config.stats_allreduce)."""
+        moves) / every BatchNorm of the sEMG encoder uses the statistics of the global batch (cp_config.stats_allreduce).
+        temperature=tau0 (additive, off by default = the reference's loss on raw cosines): logits = tau * cosines with
+        tau = exp(clamp(logit_scale, -ln 100, ln 100)) and logit_scale initialised to ln tau0 -- the CLIP temperature the reference
+        creates and never uses.  learn_temperature=True trains it with the class encoder's Adam (lr_glove and its schedule, no L2)
+        and clamps it after every step; False keeps tau0.  temperature() reads it back."""
         super().__init__()
         if prediction or glove:
             raise NotImplementedError("only the contrastive mode (prediction=False, glove=False) is accelerated; "
@@ -128,9 +133,11 @@ class Model(nn.Module):
         self.glove = glove
         self.device = torch.device(device)
         self.class_encoder = class_encoder
+        if global_negatives and temperature is not None:
+            raise NotImplementedError("global negatives with a temperature: the {G, H} table would need tau as well")
         self.engine = Engine(adabn=adabn, dtype=dtype, dp_emg=float(params.get("dp_emg", 0.0)), device=device,
                              d_e=int(params["d_e"]), seed=seed if dropout_seed is None else dropout_seed,
-                             class_encoder=class_encoder)
+                             class_encoder=class_encoder, temperature=temperature, learn_temperature=learn_temperature)
         self.engine.init_parameters(seed)
         self.global_negatives = bool(global_negatives)
         self.global_negatives_mode = global_negatives if isinstance(global_negatives, str) else "gather"
@@ -150,7 +157,12 @@ class Model(nn.Module):
             _attach(self, k, v, buffer=True)
         # code/models.py:81: created, stored in the state_dict, never used, in no optimiser
         # (own parameters precede child modules in state_dict(), so it is the first key as in the reference)
-        self.logit_scale = nn.Parameter(torch.zeros((), device=self.device))
+        # with temperature=: the device scalar the head reads -- the trailing entry of the parameter table when it is learnt
+        # (attached above: an own parameter, so still the first key), else a constant that travels in the state_dict all the same
+        if self.engine.logit_scale is None:
+            self.logit_scale = nn.Parameter(torch.zeros((), device=self.device))
+        elif not self.engine.learn_temperature:
+            self.logit_scale = nn.Parameter(self.engine.logit_scale, requires_grad=False)
         self.lr_scale = [1.0, 1.0]
         self.reset()
         self._last_logits = None
@@ -183,6 +195,11 @@ class Model(nn.Module):
         self.voting: List[torch.Tensor] = []
         self.y_pred: List[torch.Tensor] = []
         self.y_true: List[torch.Tensor] = []
+
+    def temperature(self):
+        """tau as the head applies it (a float; None for a model built without temperature=).  Pass it as `scale=` to
+        finetune.finetune for a model trained this way."""
+        return self.engine.temperature()
 
     # -- state ----------------------------------------------------------------------------------------
     def state_dict(self, *args, **kwargs):

@@ -770,7 +770,8 @@ class OnlineDecoder(_EnrollMixin):
         The decoder's own encoder embeds the windows once (the adaptive form with its current statistics frozen:
         `bn_statistics()` does not move), then `steps` Adam steps run on the device without a host synchronisation
         (include/cpnative.h, "head fine-tuning"; `finetune.finetune_reference` is the definition): rates lr (projection) and
-        lr_rows (rows; default lr); scale multiplies the cosines (1.0: the reference's loss); anchor pulls every trained
+        lr_rows (rows; default lr); scale multiplies the cosines (1.0: the reference's loss; for a model trained with
+        Model(temperature=...) pass `model.temperature()`, the tau its encoder was trained at); anchor pulls every trained
         tensor back to where it started with anchor * (theta - theta_0); balanced weighs every class with windows alike,
         else every window alike.  Training starts from `projection()` and the rows of `class_table()` and ends by installing
         what it trained: `set_projection(W, b)` (train_projection) and `set_classes(table=E, ids=...)` (train_rows), so the

@@ -179,7 +179,8 @@ def main(a):
     params = {"d_e": int(d_e), "epochs": args.final_epochs, "lr_emg": lr_e * k, "dp_emg": dp_e, "reg_emg": reg_e,
               "lr_glove": lr_g * k, "dp_glove": dp_g, "reg_glove": reg_g}
     model = Model(params=params, train_model=True, adabn=args.no_adabn, prediction=args.prediction, glove=args.glove,
-                  device="cuda", dtype=args.dtype).to(torch.float32)
+                  device="cuda", dtype=args.dtype, temperature=args.temperature,
+                  learn_temperature=not args.fixed_temperature).to(torch.float32)
     ckpt = os.path.join(args.checkpoint_dir, "contrastive.pt")
     if os.path.exists(ckpt):
         model.load_state_dict(torch.load(ckpt, weights_only=True))
@@ -217,6 +218,10 @@ def build_parser():
     parser.add_argument("--checkpoint_dir", default="../checkpoints")
     parser.add_argument("--save", default="../data/")
     parser.add_argument("--subset_trials", type=int, default=0, help="random subsets per size for the README curve (144)")
+    parser.add_argument("--temperature", type=float, default=None,
+                        help="the model was trained with train.py --temperature: the checkpoint's logit_scale scales the logits "
+                             "(the value given here only initialises it; absent: raw cosines)")
+    parser.add_argument("--fixed_temperature", action="store_true", help="as given to train.py")
     parser.add_argument("--robustness", action="store_true",
                         help="also evaluate the test split under ring shifts -3..3 x one dead electrode (robustness.npy, (7, 13, 2))")
     return parser

@@ -98,7 +98,9 @@ def train_loop(dataset, params, checkpoint=False, checkpoint_dir="../checkpoints
                   device="cuda", dtype=args.dtype, class_encoder=getattr(args, "class_encoder", "onehot"),
                   dropout_seed=42 + rank,
                   global_negatives=(getattr(args, "global_negatives_mode", "gather") if getattr(args, "global_negatives", False) and not solo else False),
-                  sync_bn=bool(getattr(args, "sync_bn", False)) and not solo).to(torch.float32)
+                  sync_bn=bool(getattr(args, "sync_bn", False)) and not solo,
+                  temperature=getattr(args, "temperature", None),
+                  learn_temperature=not getattr(args, "fixed_temperature", False)).to(torch.float32)
     if load is not None:
         print("Loading model")
         model.load_state_dict(torch.load(load + ".pt", weights_only=True))
@@ -257,6 +259,9 @@ def main(a):
                                    load=checkpoint_dir if args.load_model else None, solo=solo_final)
     print("Final validation model statistics")
     print(final_vals)
+    if model.temperature() is not None:
+        print("Temperature: tau = %.4f (logit_scale %.4f, %s)" % (model.temperature(), float(model.logit_scale.item()),
+                                                                  "learnt" if model.engine.learn_temperature else "fixed"))
     if not solo_final:
         cpdist.barrier()                  # nobody reads the checkpoint while rank 0 may still be writing it
     if os.path.exists(checkpoint_dir + ".pt"):
@@ -304,6 +309,10 @@ def build_parser():
     parser.add_argument("--sync_bn", action="store_true",
                         help="extension: BatchNorm statistics over the global batch under data parallelism (18 small all-reduces "
                              "per step); off = every rank uses its shard's statistics, the reference at B_local")
+    parser.add_argument("--temperature", type=float, default=None,
+                        help="initial temperature tau of the contrastive head: logits = tau * cosines, learnt with the class encoder's "
+                             "Adam (absent: the reference's loss on raw cosines)")
+    parser.add_argument("--fixed_temperature", action="store_true", help="keep --temperature at its initial value")
     parser.add_argument("--graph", action="store_true",
                         help="replay each training step as one captured HIP graph (single process, one-hot class encoder)")
     parser.add_argument("--aug_shift", type=int, default=0,

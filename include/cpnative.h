@@ -382,6 +382,29 @@ int cp_head_glove(const cp_config* cfg, const float* z, const float* zg, const i
                   int32_t V, int32_t want_grad, void* ws, size_t ws_bytes, void* gws, size_t gws_bytes,
                   float* loss_correct, int32_t* pred, float* logits, void* stream);
 
+/* ---- learnable temperature (an opt-in EXTENSION of the loss: the CLIP ingredient the reference leaves switched off) ----
+ * logit_scale: ONE device float s (read on the stream, so a replayed graph sees what the optimiser left there).  With
+ * S = ln 100 and tau = exp(min(max(s, -S), S)):
+ *     logits[g][i][j] = tau * z_hat[g,i] . E_hat[label(g,j)]        (the logits that come back are the scaled ones)
+ * loss, loss_correct[1], pred and the vote are cp_head's functions of those logits (pred does not depend on tau).  With
+ * dl = dL/dlogits formed on the scaled logits:
+ *     dz_hat = tau * dl E_hat,   dE_hat = tau * dl^T z_hat,
+ *     dL/ds  = sum_{g,i,j} dl[g,i,j] * logits[g,i,j]  for -S <= s <= S, and 0 outside that range.
+ * With 8-bit logits (CP_FP8 without "fp8_head_f32") the gradient products keep the f32 operands (straight-through) and
+ * dL/ds sums dl times the quantised, scaled logit.
+ * cp_head_temp / cp_head_glove_temp = cp_head / cp_head_glove with that factor: same arguments, outputs and refusals, plus
+ * logit_scale (NULL: CP_ERR_ARG) and d_logit_scale (one device float, written when want_grad; NULL with want_grad:
+ * CP_ERR_ARG).  At s = 0 every output equals the twin's bit for bit.  There is no global-negatives twin: its {G, H} table
+ * would need tau as well.  cp_debug_head_grad / cp_debug_glove_head_grad read what these calls left. */
+int cp_head_temp(const cp_config* cfg, const cp_params* p, const float* z, const int64_t* labels,
+                 int64_t n_groups, int32_t V, int32_t want_grad, void* ws, size_t ws_bytes,
+                 float* loss_correct, int32_t* pred, float* logits, cp_params* grads,
+                 const float* logit_scale, float* d_logit_scale, void* stream);
+int cp_head_glove_temp(const cp_config* cfg, const float* z, const float* zg, const int64_t* labels, int64_t n_groups,
+                       int32_t V, int32_t want_grad, void* ws, size_t ws_bytes, void* gws, size_t gws_bytes,
+                       float* loss_correct, int32_t* pred, float* logits,
+                       const float* logit_scale, float* d_logit_scale, void* stream);
+
 /* autograd of the glove encoder: consumes dL/dzg left in gws, writes w1, bn_g, bn_b, last_w of `grads`. */
 int cp_glove_backward(const cp_config* cfg, const cp_glove_params* gp, int64_t rows, void* gws, size_t gws_bytes,
                       cp_glove_params* grads, void* stream);
